@@ -21,23 +21,29 @@ emission-measure map to the step (a third field, em0: 24 B/cell); `--layout comp
 3 / 5 fields per cell (the line always prices SURVEY 8(d)'s five-field byte model on the wide
 kernel, live, as `frac_8d`).
 
+A plain run sets up, warms up, times the K steps and prints the contract line (`metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  `--dump-outputs DIR` writes
+what the last timed step computed to DIR/<name>.npy.  Everything else below -- `roofline`, the
+extra legs, the other configurations, `cpu_baseline` -- is measured with `--full` only.
+
 N > 1 (no data-path collective, one gather/reduce per step over RCCL; "scaling": "strong"):
   every config timed region = BASELINE's workload itself, the ONE grid split into n_x/N row slabs
                (x-slabs: sightlines are independent), every rank runs the whole step on its
-               rows, per-channel fluxes all_reduced.  For cfg4 / cfg2 the same line carries
-               three more measured legs, each labelled: `strong_xslab_gather_maps` (the step
-               ends with BASELINE config 4's "RCCL gather": the tau and flux slabs of every
-               rank gathered into whole cubes on rank 0 -- compute, gather and total reported
-               separately), `weak_epochs` (every rank holds the whole grid and scans another
-               burst-time epoch per step, flux-vs-time vectors all_gathered) and
-               `channel_sharded` (the north star's frequency-sharded sweep: every rank scans
-               the whole grid and maps F/N channels -- continuum channels share the grid
-               pass, SURVEY finding 2, so this cannot scale the scan).
-N = 1, default config: `rank_share` prices rank 0's share of a 2- / 4- / 8-way split of cfg4, cfg5
-and cfg3 as a stand-alone workload on this one GPU (projected strong-scaling speedup).
+               rows, per-channel fluxes all_reduced.  With --full, for cfg4 / cfg2 the same
+               line carries three more measured legs, each labelled:
+               `strong_xslab_gather_maps` (the step ends with BASELINE config 4's "RCCL
+               gather": the tau and flux slabs of every rank gathered into whole cubes on
+               rank 0 -- compute, gather and total reported separately), `weak_epochs`
+               (every rank holds the whole grid and scans another burst-time epoch per step,
+               flux-vs-time vectors all_gathered) and `channel_sharded` (the north star's
+               frequency-sharded sweep: every rank scans the whole grid and maps F/N channels
+               -- continuum channels share the grid pass, SURVEY finding 2, so this cannot
+               scale the scan).
+N = 1, default config, --full: `rank_share` prices rank 0's share of a 2- / 4- / 8-way split of
+cfg4, cfg5 and cfg3 as a stand-alone workload on this one GPU (projected strong-scaling speedup).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline`,
-`cpu_baseline` (N = 1), `sustained`, `ranks_seen` and, for N > 1, `n1` and `legs`.
+Prints ONE JSON line (rank 0) with the driver's contract fields and `ranks_seen`; with --full
+also `roofline`, `cpu_baseline` (N = 1), `sustained` and, for N > 1, `n1` and `legs`.
 """
 import argparse
 import json
@@ -58,6 +64,8 @@ MAX_CPU_PROCS = 96               # cap of the all-cores CPU leg (host memory, se
 HBM_PEAK_GBS = 8000.0            # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 YEAR = 31536000.0
 SEED = 20240504
+DUMP_MAX_VALUES = 2 ** 20        # --dump-outputs: larger arrays are written as a seeded sample
+DUMP_BUDGET_BYTES = 60 * 2 ** 20  # --dump-outputs: all files of one run together
 
 CONFIGS = {
     # name: (shape, n_chan, n_epochs_total or None, kind) -- BASELINE.json configs[1..4]
@@ -137,6 +145,17 @@ def parse(argv=None):
                          "cfg5 measured in the same process after the contract timing)")
     ap.add_argument("--no-api-level", action="store_true",
                     help="skip the PCIe-inclusive leg (step + copy of the cubes to pinned host)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure as well: roofline, sustained and "
+                         "PCIe-inclusive legs, the other configurations, rank shares, the N > 1 "
+                         "legs and the CPU baseline (the --no-* / --*-seconds options above "
+                         "shape these).  Without it a run sets up, warms up, times the steps "
+                         "and prints the contract line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as "
+                         "DIR/<name>.npy (float64; arrays of more than %d values as a fixed, "
+                         "seeded sample of them, %d MiB at most in all)"
+                    % (DUMP_MAX_VALUES, DUMP_BUDGET_BYTES >> 20))
     return ap.parse_args(argv)
 
 
@@ -615,11 +634,25 @@ class Workload:
         if self.rrl:
             tau_rrl = eng.rrl_scan(self.fields, self.bursts, self.my_epochs[0], self.line,
                                    self.freqs)
-            _, res = eng.rrl_maps(tau_rrl, self.tau.reshape(self.nchan, self.P), self.tavg,
-                                  self.flux.reshape(self.nchan, self.P), self.cfl_rrl,
-                                  self.hnu_k)
+            flux_rrl, res = eng.rrl_maps(tau_rrl, self.tau.reshape(self.nchan, self.P), self.tavg,
+                                         self.flux.reshape(self.nchan, self.P), self.cfl_rrl,
+                                         self.hnu_k)
+            self.line_maps = (tau_rrl, flux_rrl)          # (kept for --dump-outputs)
             res = res.reshape(1, self.nchan)
         return res
+
+    def outputs(self, res):
+        """What the last step handed its caller, by name: `res` (the step's collected result) and
+        this rank's maps (device tensors)."""
+        out = {("line_flux_total" if self.rrl else "flux_total"): res}
+        if self.rrl:
+            out["line_tau"], out["line_flux"] = self.line_maps
+            out["flux_total"] = self.ftot
+        for name, t in (("tau", self.tau), ("flux", self.flux), ("sum_a", self.sumA),
+                        ("em", self.em)):
+            if t is not None:
+                out[name] = t
+        return out
 
     def step(self):
         res = collect(self.local_step(), self.pl, self.rank, self.world, self.args.backend)
@@ -979,6 +1012,97 @@ def measure_rank_share(eng, args, torch, base):
     return out
 
 
+def dump_outputs(arrays, out_dir, rank=0, world=1):
+    """--dump-outputs: every array of `arrays` (name -> tensor) as out_dir/<name>.npy in float64.
+    An array of more than DUMP_MAX_VALUES values (fewer when many arrays share the budget) is
+    written as a sample: the sorted distinct flat indices of a generator seeded by SEED and the
+    name, so two runs with the same arguments sample the same cells.  With several ranks, rank 0
+    writes the collected result and every rank its own maps as <name>_rank<r>.npy.  Returns
+    {file name: shape written}."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    if world > 1:
+        first = next(iter(arrays))
+        arrays = dict(((k if k == first else "%s_rank%d" % (k, rank)), v)
+                      for k, v in arrays.items() if k != first or rank == 0)
+    cap = min(DUMP_MAX_VALUES, DUMP_BUDGET_BYTES // 8 // max(1, len(arrays) * world))
+    written = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        if n > cap:
+            rng = np.random.default_rng([SEED, zlib.crc32(name.encode())])
+            idx = np.unique(rng.integers(0, n, cap))
+            import torch
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.cpu().numpy().astype(np.float64, copy=False)
+        if n <= cap:
+            a = a.reshape(tuple(t.shape))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name + ".npy"] = list(a.shape)
+    return written
+
+
+def layout_description(wl):
+    """What the timed step's scans read per cell (the line's config.layout)."""
+    has_tau = wl.fields.a0 is not None
+    if wl.rrl:
+        return "K3 reads the 6 wide fields; K1 %s" % ("tau" if has_tau else "compact")
+    nf = wl.fields.scan_fields(wl.gmode, wl.em is not None)
+    return {2: "tau (a0, ts: 2 fields/cell)", 5: "wide (5 fields/cell)",
+            3: "tau + EM (a0, em0, ts: 3 fields/cell)" if has_tau
+            else "compact (3 fields/cell)"}.get(nf)
+
+
+def contract_line(args, world, sharding, value, ms_step, total_epochs, layout_desc, ranks_seen,
+                  devices, distinct_devices, rehearsal, n1=None, workload_note=""):
+    """The fields of the result line that a plain run and a --full run share."""
+    shape, nchan_total, n_ep_cfg, kind = CONFIGS[args.config]
+    rrl = kind == "rrl"
+    result = {
+        "metric": "Mvoxel-freq/s", "value": value, "unit": "Mvoxel-freq/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_step, "higher_is_better": True,
+        # (the same word at every N: the driver's N = 1, 2, 4, 8 values are one curve)
+        "scaling": "weak" if sharding == "epochs" else "strong",
+        "vs_baseline": None, "dtype": "f64", "storage_dtype": args.storage,
+        "data": "synthetic",
+        "config": {"workload": "%s: %dx%dx%d grid x %d %s, %d epoch(s) per step, %s"
+                               % ((args.config,) + shape + (
+                                   nchan_total, "H66a channels of 100 kHz" if rrl else
+                                   "continuum channels 1-50 GHz", total_epochs,
+                                   "K3 RRL scan + K1/K2 continuum + line flux cube" if rrl else
+                                   "K1 scan + K2 flux-vs-time" if n_ep_cfg else
+                                   "K1 scan + K2 tau/flux cubes" +
+                                   (" + EM map" if args.em else ""))) + workload_note,
+                   "storage": args.storage, "gaunt": args.gaunt,
+                   "arithmetic": "f64 accumulation and transcendental functions; storage "
+                                 "dtype of the 3-D fields as given",
+                   "layout": layout_desc,
+                   "sharding": sharding, "gather": GATHER[sharding]},
+        "ranks_seen": ranks_seen,
+        "backend": (args.backend if world > 1 else None),
+        "devices": devices, "distinct_devices": distinct_devices,
+        "full": bool(args.full),
+    }
+    if world > 1 and result["scaling"] == "strong":
+        # "how much faster is ONE model on N GPUs": `value` itself (x-slabs of the one grid)
+        result["strong_value"] = value
+        result["strong_speedup_vs_n1"] = value / n1["value"] if n1 else None
+    if rehearsal:
+        # several ranks on one device and / or gloo instead of RCCL: plumbing only
+        result["rehearsal"] = True
+        result["rehearsal_value"] = result["value"]
+        result["value"] = None
+        if "strong_value" in result:
+            result["rehearsal_strong_value"] = result.pop("strong_value")
+        result["rehearsal_why"] = ("--share-gpu" if args.share_gpu else
+                                   "%d distinct device(s) for %d ranks" % (distinct_devices, world)
+                                   if distinct_devices < world else
+                                   "backend %s, not RCCL" % args.backend)
+    return result
+
+
 def device_identity(torch, index):
     """What physically distinguishes the GPU behind cuda:<index>: UUID and PCI address (plus the
     host name, so that the ids of a multi-node job could not collide)."""
@@ -1079,6 +1203,8 @@ def main(argv=None):
     total_epochs = wl.total_epochs
     value = rate(ms_step, total_epochs)
     chk = float(out.sum().item())
+    if args.dump_outputs:
+        dump_outputs(wl.outputs(out), args.dump_outputs, rank, world)
 
     # every rank really took part: an all_reduce of ones over the job's process group
     ranks_seen = 1
@@ -1104,6 +1230,18 @@ def main(argv=None):
                   % (world, distinct_devices, json.dumps(devices)), file=sys.stderr)
         dist.destroy_process_group()
         sys.exit(3)
+    layout_desc = layout_description(wl)
+
+    if not args.full:
+        # a plain run: the headline figure is all it measures (every other leg is --full)
+        if rank == 0:
+            result = contract_line(args, world, sharding, value, ms_step, total_epochs,
+                                   layout_desc, ranks_seen, devices, distinct_devices, rehearsal)
+            result["checksum_flux_total_jy"] = chk
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- sustained leg: ~10 s of back-to-back steps (clock / power droop would show) ----
     sustained = None
@@ -1149,8 +1287,11 @@ def main(argv=None):
                 pass
     else:
         want_em = wl.em is not None
-        k_ms = eng.time_ff_scan(fields, wl.bursts, wl.my_epochs, wl.gmode, reps=5 if n_ep_cfg else 30,
-                                want_em=want_em, want_tavg=False)
+        # the median of three windows (as the wide figure below is a median): one stall of the
+        # shared host inside a single window of launches would otherwise lift the mean of all
+        k_ms = float(np.median([eng.time_ff_scan(fields, wl.bursts, wl.my_epochs, wl.gmode,
+                                                 reps=5 if n_ep_cfg else 10, want_em=want_em,
+                                                 want_tavg=False) for _ in range(3)]))
         # epoch tiles share a pass over the grid: 32 uniformly spaced epochs, 16 below that,
         # else 8 (f64 lanes) or 4 (f32 lanes)
         # fields K1 streams per cell (DESIGN.md "Data layout"): a0, ts on the tau layout (+ em0
@@ -1304,11 +1445,6 @@ def main(argv=None):
     has_tau = wl.fields.a0 is not None
     nf = roof_extra.get("fields_streamed_per_cell")
     lay_tag = {2: "_tau2", 3: "_tau3" if has_tau else "", 5: "_wide5"}.get(nf, "")
-    k1_layout = {2: "tau (a0, ts: 2 fields/cell)", 5: "wide (5 fields/cell)",
-                 3: "tau + EM (a0, em0, ts: 3 fields/cell)" if has_tau
-                 else "compact (3 fields/cell)"}.get(nf)
-    layout_desc = k1_layout if not rrl else \
-        "K3 reads the 6 wide fields; K1 %s" % ("tau" if has_tau else "compact")
     if roof_extra.get("scan_path") == "lt":
         lay_tag = "_lt"
     elif roof_extra.get("scan_path") == "moments":
@@ -1558,52 +1694,15 @@ def main(argv=None):
             if n1 and "value" in leg:
                 leg["speedup_vs_n1"] = leg["value"] / n1["value"]
 
-    result = {
-        "metric": "Mvoxel-freq/s", "value": value, "unit": "Mvoxel-freq/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_step, "higher_is_better": True,
-        # (the same word at every N: the driver's N = 1, 2, 4, 8 values are one curve)
-        "scaling": "weak" if sharding == "epochs" else "strong",
-        "vs_baseline": None, "dtype": "f64", "storage_dtype": args.storage,
-        "data": "synthetic",
-        "config": {"workload": "%s: %dx%dx%d grid x %d %s, %d epoch(s) per step, %s"
-                               % ((args.config,) + shape + (
-                                   nchan_total, "H66a channels of 100 kHz" if rrl else
-                                   "continuum channels 1-50 GHz", total_epochs,
-                                   "K3 RRL scan + K1/K2 continuum + line flux cube" if rrl else
-                                   "K1 scan + K2 flux-vs-time" if n_ep_cfg else
-                                   "K1 scan + K2 tau/flux cubes" +
-                                   (" + EM map" if args.em else ""))) + (
-                           "; the scan reads the per-MODEL scan fields a0 = (n x)^2 pf T^-1.5|-1.35 "
-                           "and ts (16 B/cell), T_avg is a per-model map: their one-off costs are "
-                           "roofline.per_model_state_ms, and value_from_model_fields is the same "
-                           "step from the five model fields (SURVEY 8(d))"
-                           if (not rrl and not n_ep_cfg and roofline.get("timed_step_kernel")) else ""),
-                   "storage": args.storage, "gaunt": args.gaunt,
-                   "arithmetic": "f64 accumulation and transcendental functions; storage "
-                                 "dtype of the 3-D fields as given",
-                   "layout": layout_desc,
-                   "sharding": sharding, "gather": GATHER[sharding]},
-        "ranks_seen": ranks_seen,
-        "backend": (args.backend if world > 1 else None),
-        "devices": devices, "distinct_devices": distinct_devices,
-        "roofline": roofline,
-    }
-    if world > 1 and result["scaling"] == "strong":
-        # "how much faster is ONE model on N GPUs": `value` itself (x-slabs of the one grid)
-        result["strong_value"] = value
-        result["strong_speedup_vs_n1"] = value / n1["value"] if n1 else None
-    if rehearsal:
-        # several ranks on one device and / or gloo instead of RCCL: plumbing only
-        result["rehearsal"] = True
-        result["rehearsal_value"] = result["value"]
-        result["value"] = None
-        if "strong_value" in result:
-            result["rehearsal_strong_value"] = result.pop("strong_value")
-        result["rehearsal_why"] = ("--share-gpu" if args.share_gpu else
-                                   "%d distinct device(s) for %d ranks" % (distinct_devices, world)
-                                   if distinct_devices < world else
-                                   "backend %s, not RCCL" % args.backend)
+    note = ("; the scan reads the per-MODEL scan fields a0 = (n x)^2 pf T^-1.5|-1.35 "
+            "and ts (16 B/cell), T_avg is a per-model map: their one-off costs are "
+            "roofline.per_model_state_ms, and value_from_model_fields is the same "
+            "step from the five model fields (SURVEY 8(d))"
+            if (not rrl and not n_ep_cfg and roofline.get("timed_step_kernel")) else "")
+    result = contract_line(args, world, sharding, value, ms_step, total_epochs, layout_desc,
+                           ranks_seen, devices, distinct_devices, rehearsal, n1=n1,
+                           workload_note=note)
+    result["roofline"] = roofline
     if not rrl and "wide_ms_per_launch" in roofline:
         # SURVEY 8(d)'s workload literally: ONE epoch from the five model fields (nd, xi, temp,
         # pf, ts) -- the wide kernel's scan (tau + EM + T_avg sums) + this step's map stage

@@ -1067,18 +1067,22 @@ class Pipeline:
         self._log = new_log
 
     def save(self, save_file, absolute_directories=False):
-        """Pickle the pipeline state (classes.py:2215-2258)."""
+        """Pickle the pipeline state (classes.py:2215-2258).  Without `absolute_directories` the
+        FILE holds the paths with the home directory as '~'; the runs and parameters of this
+        pipeline keep their absolute paths (the products of a run stay where they are)."""
+        import copy
         home = os.path.expanduser('~')
-        mf = self.model_file
+        runs, params, mf = self.runs, self._params, self.model_file
         if not absolute_directories:
-            for run in self.runs:
+            runs = [copy.copy(run) for run in self.runs]
+            for run in runs:
                 run.dcy = run.dcy.replace(home, '~')
-            self._params['dcys']['model_dcy'] = \
-                self._params['dcys']['model_dcy'].replace(home, '~')
+            params = dict(self._params, dcys=dict(self._params['dcys']))
+            params['dcys']['model_dcy'] = params['dcys']['model_dcy'].replace(home, '~')
             mf = mf.replace(home, '~')
         self.log.add_entry("INFO", "Saving pipeline to " + save_file)
         with open(save_file, 'wb') as f:
-            pickle.dump({"runs": self.runs, "params": self._params, "model_file": mf,
+            pickle.dump({"runs": runs, "params": params, "model_file": mf,
                          'log': self.log}, f)
 
     def execute(self, simobserve=True, verbose=True, dryrun=False, resume=True, clobber=False):

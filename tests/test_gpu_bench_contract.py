@@ -18,7 +18,7 @@ REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 @pytest.mark.parametrize("config", ["tiny", "tiny_rrl"])
 def test_bench_prints_one_contract_line(config):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
-                          "--steps", "3", "--warmup", "1", "--config", config,
+                          "--steps", "3", "--warmup", "1", "--config", config, "--full",
                           "--cpu-seconds", "0.5", "--sustained-seconds", "0.2"] +
                          (["--no-cpu-all-cores"] if config == "tiny_rrl" else []),
                          capture_output=True, text=True, timeout=600)
@@ -75,6 +75,62 @@ def test_bench_prints_one_contract_line(config):
         assert "all_cores" not in cb
 
 
+MOVED = {"roofline", "cpu_baseline", "sustained", "api_level", "configs", "rank_share", "legs",
+         "n1", "value_from_model_fields", "value_r02_workload"}
+TINY = {"tiny": ((16, 64, 64), 8, 1), "tiny5": ((16, 64, 64), 8, 32),
+        "tiny_rrl": ((8, 64, 64), 40, 1)}
+
+
+def _plain_run(config, steps, dump):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+                          "--steps", str(steps), "--warmup", "1", "--config", config,
+                          "--dump-outputs", dump], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+
+@pytest.mark.parametrize("config", sorted(TINY))
+def test_plain_run_times_the_steps_and_dumps_the_last_one(config, tmp_path):
+    """Without --full the line is the headline alone, and --dump-outputs writes what the last
+    timed step computed: the same arrays, to the last bit of rounding, on a second run."""
+    import numpy as np
+    r = _plain_run(config, 4, str(tmp_path / "a"))
+    assert r["n_gpus"] == 1 and r["steps"] == 4 and r["warmup"] == 1 and r["full"] is False
+    assert r["metric"] == "Mvoxel-freq/s" and r["unit"] == "Mvoxel-freq/s"
+    assert r["higher_is_better"] is True and r["dtype"] == "f64"
+    assert r["value"] > 0 and r["ms_per_step"] > 0
+    assert r["ranks_seen"] == 1 and r["distinct_devices"] == 1 and r["config"]["layout"]
+    assert not MOVED & set(r), MOVED & set(r)
+    (nx, _, nz), nch, E = TINY[config]
+    P = nx * nz
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64e6
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(f.endswith(".npy") for f in files)
+    assert all(a.dtype == np.float64 for a in got.values())
+    rrl = config == "tiny_rrl"
+    total = got["line_flux_total" if rrl else "flux_total"]
+    assert total.shape == (E, nch)
+    assert abs(total.sum() - r["checksum_flux_total_jy"]) <= 1e-12 * abs(total.sum())
+    assert got["sum_a"].shape == (E, P)
+    if config == "tiny5":                       # flux-vs-time: the maps stay on the device
+        assert set(got) == {"flux_total", "sum_a"}
+    else:
+        assert got["tau"].shape == got["flux"].shape == (1, nch, P)
+        np.testing.assert_allclose(np.nansum(got["flux"], axis=-1), got["flux_total"],
+                                   rtol=1e-11)
+    if rrl:
+        assert got["line_tau"].shape == got["line_flux"].shape == (nch, P)
+        np.testing.assert_allclose(np.nansum(got["line_flux"], axis=-1), total[0], rtol=1e-11)
+    r2 = _plain_run(config, 2, str(tmp_path / "b"))
+    assert r2["steps"] == 2 and sorted(os.listdir(tmp_path / "b")) == files
+    for k, a in got.items():
+        np.testing.assert_allclose(np.load(tmp_path / "b" / (k + ".npy")), a, rtol=1e-12,
+                                   atol=0, err_msg=k)
+
+
 def test_bench_refuses_mismatched_world_size():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2",
                           "--config", "tiny"], capture_output=True, text=True, timeout=300,
@@ -93,7 +149,7 @@ def test_bench_launches_its_own_ranks(config, sharding, scaling):
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2",
                           "--steps", "3", "--warmup", "1", "--config", config, "--backend",
-                          "gloo", "--share-gpu", "--sustained-seconds", "0.05"],
+                          "gloo", "--share-gpu", "--full", "--sustained-seconds", "0.05"],
                          capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]

@@ -375,21 +375,27 @@ def _pipeline_worker(rank, world, port, dcy, ret):
         pp["continuum"]["times"] = np.array([0., 0.5, 1., 2., 3.])
         pl = classes.Pipeline(classes.JetModel(example_params(), log=log), pp, log=log)
         pl.execute(simobserve=False, verbose=False, dryrun=False, resume=False, clobber=True)
-        ok = all(r.completed for r in pl.runs) and all("flux" in r.results for r in pl.runs)
+        why = ["run #%d not completed or without a flux" % (i + 1) for i, r in enumerate(pl.runs)
+               if not (r.completed and "flux" in r.results)]
         dist.barrier()
         if rank == 0:
             jm = classes.JetModel(example_params(), log=log)
             for r in pl.runs:
                 jm.time = r.year * YEAR
-                for path in (r.fits_em, r.fits_tau, r.fits_flux):
-                    ok = ok and os.path.exists(path)
-                if r.obs_type == "continuum":
+                why += ["missing " + path for path in (r.fits_em, r.fits_tau, r.fits_flux)
+                        if not os.path.exists(path)]
+                if r.obs_type == "continuum" and "flux" in r.results:
                     want = np.nansum(np.nanmean(jm.flux_ff(r.chan_freqs), axis=0))
-                    ok = ok and np.isclose(r.results["flux"], want, rtol=1e-12)
                     data = fits.read(r.fits_flux)[0]
-                    ok = ok and np.isclose(np.nansum(np.nanmean(data, axis=0)), want, rtol=1e-12)
-            ok = ok and os.path.exists(os.path.join(dcy, "pipeline.save"))
-        ret[rank] = bool(ok)
+                    for what, got in (("result", r.results["flux"]),
+                                      ("FITS", np.nansum(np.nanmean(data, axis=0)))):
+                        if not np.isclose(got, want, rtol=1e-12):
+                            why.append("%s of the %.1f yr run: %r, one model alone: %r"
+                                       % (what, r.year, got, want))
+            if not os.path.exists(os.path.join(dcy, "pipeline.save")):
+                why.append("no pipeline.save")
+        ret[rank] = not why
+        ret["why%d" % rank] = why
     finally:
         dist.destroy_process_group()
 

@@ -383,6 +383,31 @@ def pline_params(dcy):
     }
 
 
+def test_pipeline_save_keeps_the_runs_where_they_are(tmp_path, monkeypatch):
+    """A save without absolute_directories writes '~' for the home directory into the FILE
+    (the reference's portable form) but leaves the pipeline's own runs and parameters alone:
+    a run under the home directory still names its products by their real paths."""
+    import pickle
+    monkeypatch.setenv("HOME", str(tmp_path))
+    dcy = str(tmp_path / "out")
+    os.makedirs(dcy)
+    log = logger.Log(os.path.join(dcy, "model.log"), verbose=False)
+    jm = classes.JetModel(example_params(), log=log)
+    pl = classes.Pipeline(jm, pline_params(dcy), log=log)
+    before = [(r.dcy, r.fits_flux) for r in pl.runs]
+    jm.save(pl.model_file)
+    pl.save(pl.save_file)
+    assert [(r.dcy, r.fits_flux) for r in pl.runs] == before
+    assert all(p.startswith(dcy) for _, p in before)
+    assert pl.params["dcys"]["model_dcy"] == dcy
+    saved = pickle.load(open(pl.save_file, "rb"))
+    assert all(r.dcy == "~/out" for r in saved["runs"])
+    assert saved["params"]["dcys"]["model_dcy"] == "~/out"
+    assert saved["model_file"] == "~/out/jetmodel.save"
+    back = classes.Pipeline.load_pipeline(pl.save_file)
+    assert [(r.dcy, r.fits_flux) for r in back.runs] == before
+
+
 def test_pipeline_run_table_matches_reference(tmp_path, rec):
     dcy = str(tmp_path / "out")
     os.makedirs(dcy)

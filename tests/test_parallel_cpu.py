@@ -216,6 +216,35 @@ def test_bench_refuses_mismatched_world_size_cpu():
     assert out.returncode == 2 and "WORLD_SIZE" in out.stderr
 
 
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: small arrays whole, large ones as the same seeded sample on every run,
+    float64, within the size budget; with several ranks the collected result comes from rank 0
+    alone and every rank's maps carry its rank.  A plain run measures the steps alone."""
+    import bench
+    args = bench.parse(["--dump-outputs", str(tmp_path)])
+    assert args.full is False and args.dump_outputs == str(tmp_path)
+    assert bench.parse(["--full"]).full is True
+    g = torch.Generator().manual_seed(7)
+    arrays = {"flux_total": torch.rand(1, 256, dtype=torch.float64, generator=g),
+              "tau": torch.rand(1, 256, 64 * 1024, dtype=torch.float64, generator=g),
+              "sum_a": torch.rand(1, 64 * 1024, dtype=torch.float64, generator=g)}
+    w1 = bench.dump_outputs(arrays, str(tmp_path / "a"))
+    w2 = bench.dump_outputs(arrays, str(tmp_path / "b"))
+    assert w1 == w2 and set(w1) == {"flux_total.npy", "tau.npy", "sum_a.npy"}
+    assert w1["flux_total.npy"] == [1, 256] and w1["sum_a.npy"] == [1, 64 * 1024]
+    assert 0.9 * bench.DUMP_MAX_VALUES < w1["tau.npy"][0] <= bench.DUMP_MAX_VALUES
+    for f in w1:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    flat = arrays["tau"].reshape(-1).numpy()
+    assert np.isin(np.load(tmp_path / "a" / "tau.npy"), flat).all()
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in w1) <= bench.DUMP_BUDGET_BYTES
+    assert set(bench.dump_outputs(arrays, str(tmp_path / "r0"), 0, 2)) == {
+        "flux_total.npy", "tau_rank0.npy", "sum_a_rank0.npy"}
+    assert set(bench.dump_outputs(arrays, str(tmp_path / "r1"), 1, 2)) == {
+        "tau_rank1.npy", "sum_a_rank1.npy"}
+
+
 def _failing_pipeline_worker(rank, world, port, dcy, ret):
     """One rank's run raises: every rank must still reach the result gather and the barrier
     and then raise -- not leave its peers waiting in a collective."""

@@ -22,8 +22,9 @@ def main():
     extra = sys.argv[2:]
     rows, lines = [], []
     for cfg, storage, env, more in RUNS:
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--storage",
-               storage, "--steps", "5", "--warmup", "2", "--sustained-seconds", "0.5"] + more + extra
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", cfg,
+               "--storage", storage, "--steps", "5", "--warmup", "2", "--sustained-seconds",
+               "0.5"] + more + extra
         out = subprocess.run(cmd, env=dict(os.environ, **env), capture_output=True, text=True,
                              timeout=900)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]

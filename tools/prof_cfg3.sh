@@ -10,7 +10,7 @@ prof="$root/profiles"
 mkdir -p "$out"
 export TMPDIR=/tmp
 cd /tmp
-B=(python3 "$root/bench.py" --config cfg3 --steps 4 --warmup 1 --no-cpu-baseline --no-api-level --sustained-seconds 0 --no-other-configs)
+B=(python3 "$root/bench.py" --full --config cfg3 --steps 4 --warmup 1 --no-cpu-baseline --no-api-level --sustained-seconds 0 --no-other-configs)
 "${B[@]}" > "$out/${tag}_cfg3_f64_bench.json" 2> "$out/${tag}_cfg3_f64_bench.err"
 echo "bench done"
 rocprofv3 --kernel-trace --stats -d "$out/${tag}_cfg3_stats" -o run --output-format csv -- "${B[@]}" \

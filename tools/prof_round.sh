@@ -23,7 +23,7 @@ for variant in tau2 tau3 wide5; do
     wide5) flags=(--layout wide --em); kern="ff_scan_table_wide_kernel" ;;
   esac
   sfx="_${variant}"
-  B=(python3 "$root/bench.py" "${flags[@]}")
+  B=(python3 "$root/bench.py" --full "${flags[@]}")
   if [[ $variant == tau2 ]]; then
     "${B[@]}" > "$out/${tag}_cfg4_f64${sfx}_bench.json" 2> "$out/${tag}_cfg4_f64${sfx}_bench.err"
   else
