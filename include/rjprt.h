@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define RJP_VERSION 109          /* 0.1.9 */
+#define RJP_VERSION 110          /* 0.1.10 */
 #define RJP_RANGE_BLOCKS 2048    /* partial (min, max) pairs rjp_field_range writes */
 #define RJP_MAX_EPOCH_TILE 32    /* most epochs evaluated per grid pass: 32 uniformly spaced ones (with or without d_em), 16 when only 16-31 are left, else tiles of 8, 4, 2, 1 */
 
@@ -166,6 +166,34 @@ typedef struct rjp_fields {
    * whenever d_a0, d_ts, the range or the set of jets with bursts changes. */
   double* d_mom_cache;
   int32_t mom_cache_K, mom_cache_N;
+  /* Optional launch-time-bucketed layout of (a0, ts) for SINGLE-epoch scans, built once per model
+   * by rjp_srt_count() + rjp_srt_fill() (all NULL / 0 = absent).  Every group of 64 consecutive
+   * sightlines g holds each lane's OWN cells sorted by key q = jet * srt_K + bin (srt_K bins per
+   * jet over [ts_lo, ts_hi]):
+   *   d_srt_cells[(d_srt_rowbase[g] + r) * 64 + lane] = (|a0|, ts)     16 bytes
+   * where the cells of key q of sightline p are rows [d_srt_start[q * P + p], d_srt_start[(q + 1)
+   * * P + p]) (d_srt_start[2 srt_K * P + p] = the sightline's length); lanes are padded at the END
+   * only, up to the group's longest lane (d_srt_rowbase[g + 1] - d_srt_rowbase[g] rows).
+   * d_srt_cum[q * P + p] = the sum of |a0| over the sightline's cells of the keys below q (2 srt_K
+   * + 1 entries per sightline, like d_srt_start); d_srt_aux = 3 P doubles as d_lt_aux (NaN
+   * launch times per jet, infinite weights); h_srt_hist = HOST array of 2 srt_K cell counts per
+   * key over the whole map.  Cells with a0 == 0 or NaN, infinite a0 or a NaN launch time are not
+   * in the layout (the aux sums stand for them, so the maps keep nansum's semantics).
+   * Outside the bursts' support chi(t - ts) == 1 (to 1e-17), so a single-epoch scan on the table
+   * path reads only the rows of the bins in the support of each jet at that epoch and adds the
+   * |a0| sums of the other bins: the bytes read depend on the epoch.  rjp_ff_scan / rjp_ff_step
+   * take it when the table path applies (single epoch, no d_em, no d_tavg) and at most 90 % of
+   * the cells (h_srt_hist) fall into those bins, else they scan a0 / ts in grid order;
+   * rjp_last_scan_layout() says which.  It belongs to the d_a0, d_ts, ts_lo, ts_hi it was built
+   * from: rebuild after any of them changes. */
+  const void* d_srt_cells;
+  const int32_t* d_srt_start;
+  const double* d_srt_cum;
+  const int64_t* d_srt_rowbase;
+  const double* d_srt_aux;
+  const int64_t* h_srt_hist;
+  int32_t srt_K;            /* launch-time bins per jet, 1..32 */
+  int32_t reserved3_;       /* 0 */
 } rjp_fields;
 
 /* Ejection bursts (classes.py:399-463): mdot(t)/mdot_ss = 1 + sum_b amp_rel_b *
@@ -294,6 +322,12 @@ int rjp_range_guard(rjp_ctx* ctx);
  * For tests and the bench line. */
 int rjp_last_scan_path(const rjp_ctx* ctx, double* worst_rel_err, int32_t* moment_shape);
 
+/* Which layout of (a0, ts) the last rjp_ff_scan / rjp_ff_step of this context read: 0 = the grid
+ * order (every cell of the occupied y-ranges), 1 = the launch-time-bucketed layout of
+ * rjp_fields.d_srt_cells (only the bins inside the bursts' support; rjp_last_scan_path then
+ * reports 3: chi still comes from the table).  For tests and the bench line. */
+int rjp_last_scan_layout(const rjp_ctx* ctx);
+
 /* Host wall time [ms] the last table build of this context took (the coefficient tables of the
  * moment paths are built and checked on the device when the bursts or epochs of a sweep change:
  * one small launch and ONE stream synchronisation inside that rjp_ff_scan; a repeated request
@@ -321,6 +355,24 @@ int rjp_lt_count(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, int32_t* d_r
                  int64_t* h_total_rows, void* stream);
 int rjp_lt_fill(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, const int32_t* d_rowoff,
                 void* d_cells, double* d_aux, void* stream);
+
+/* ---- launch-time-bucketed layout (rjp_fields.d_srt_*) ------------------------------------
+ * Two calls, because the size of the layout is known only after counting:
+ *   rjp_srt_index_entries(nx, nz, K)  entries of d_start (int32) and of d_cum (double) each:
+ *                  (2 K + 1) nx nz; d_rowbase holds ceil(nx nz / 64) + 1 int64
+ *   rjp_srt_count  counts every sightline's cells per (jet, bin), writes d_start (the lane-local
+ *                  start rows) and d_rowbase (the groups' first rows), fills h_hist[2 K] (host)
+ *                  and returns the total number of rows in *h_total_rows (synchronises the
+ *                  stream; checks the launch-time range as rjp_lt_count does);
+ *   rjp_srt_fill   writes d_cells (total_rows * 64 * 16 bytes), d_cum and d_aux (3 nx nz doubles).
+ * Needs RJP_F64 fields with d_a0, d_ts and ts_lo / ts_hi; 1 <= K <= 32.  Cost: two passes over a0
+ * and ts plus 16-byte scattered writes, once per model; memory ~1.03 x the bytes of a0 + ts. */
+size_t rjp_srt_index_entries(int32_t nx, int32_t nz, int32_t K);
+int rjp_srt_count(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, int32_t* d_start,
+                  int64_t* d_rowbase, int64_t* h_hist, int64_t* h_total_rows, void* stream);
+int rjp_srt_fill(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, const int32_t* d_start,
+                 const int64_t* d_rowbase, void* d_cells, double* d_cum, double* d_aux,
+                 void* stream);
 
 /* ---- K2: per-channel map stage --------------------------------------------------------
  * Replaces the map-level arithmetic of optical_depth_ff / intensity_ff / flux_ff

@@ -18,7 +18,7 @@ RJP_F32, RJP_F64 = 4, 8
 RJP_GFF_SCALAR, RJP_GFF_POWERLAW = 0, 1
 RJP_MAX_EPOCH_TILE = 32
 RJP_RANGE_BLOCKS = 2048
-RJP_VERSION = 109             # include/rjprt.h; the binding below matches exactly this ABI
+RJP_VERSION = 110             # include/rjprt.h; the binding below matches exactly this ABI
 RJP_OK = 0
 RJP_ERR_ARG, RJP_ERR_HIP, RJP_ERR_NODEVICE, RJP_ERR_WORKSPACE, RJP_ERR_DEGENERATE = \
     -1, -2, -3, -4, -5
@@ -43,7 +43,11 @@ class Fields(C.Structure):
                 ("d_lt_cells", C.c_void_p), ("d_lt_rowoff", C.c_void_p),
                 ("d_lt_aux", C.c_void_p), ("lt_K", C.c_int32), ("reserved2_", C.c_int32),
                 ("d_mom_cache", C.c_void_p), ("mom_cache_K", C.c_int32),
-                ("mom_cache_N", C.c_int32)]
+                ("mom_cache_N", C.c_int32),
+                ("d_srt_cells", C.c_void_p), ("d_srt_start", C.c_void_p),
+                ("d_srt_cum", C.c_void_p), ("d_srt_rowbase", C.c_void_p),
+                ("d_srt_aux", C.c_void_p), ("h_srt_hist", C.c_void_p),
+                ("srt_K", C.c_int32), ("reserved3_", C.c_int32)]
 
 
 class Bursts(C.Structure):
@@ -99,11 +103,16 @@ SIGNATURES = {
                               C.c_int32, _P, _P, _P, _P, C.c_size_t, _P]),
     "rjp_range_guard": (C.c_int, [_P]),
     "rjp_last_scan_path": (C.c_int, [_P, _DP, C.POINTER(C.c_int32)]),
+    "rjp_last_scan_layout": (C.c_int, [_P]),
     "rjp_last_table_build_ms": (C.c_double, [_P]),
     "rjp_moment_cache_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rjp_lt_rowoff_entries": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "rjp_lt_count": (C.c_int, [_P, C.POINTER(Fields), C.c_int32, _P, C.POINTER(C.c_int64), _P]),
     "rjp_lt_fill": (C.c_int, [_P, C.POINTER(Fields), C.c_int32, _P, _P, _P, _P]),
+    "rjp_srt_index_entries": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "rjp_srt_count": (C.c_int, [_P, C.POINTER(Fields), C.c_int32, _P, _P, _P,
+                                C.POINTER(C.c_int64), _P]),
+    "rjp_srt_fill": (C.c_int, [_P, C.POINTER(Fields), C.c_int32, _P, _P, _P, _P, _P, _P]),
     "rjp_ff_maps_workspace": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "rjp_ff_maps": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, _DP, _DP, C.c_int32,
                               _P, _P, _P, _P, C.c_size_t, _P]),

@@ -203,6 +203,192 @@ hipError_t lt_fill_launch(const rjp_fields* fl, int K, const int32_t* d_rowoff, 
   return hipGetLastError();
 }
 
+// ---- launch-time-bucketed layout for single-epoch scans (rjp_fields.d_srt_*) -------------------
+// The same bins and the same keep rule as above, but every lane keeps its OWN rows: the cells of
+// sightline p are sorted by key and padded only at the end, up to its group's longest lane.  A
+// single-epoch scan then reads, per lane, one contiguous run of rows per jet (the bins inside the
+// bursts' support) and adds the |a0| sums of the other bins (ff_scan_tab.hip).
+size_t srt_index_entries(int nx, int nz, int K) { return (size_t)(2 * K + 1) * nx * nz; }
+
+// One workgroup of four waves per group counts; wave 0 then writes every lane's start rows
+// (exclusive prefix over the keys) and the group's length, all waves add to the map's histogram.
+__global__ __launch_bounds__(256) void srt_count_kernel(const double* __restrict__ a0,
+                                                        const double* __restrict__ ts, int ny,
+                                                        int nz, int64_t npix, LtBins b,
+                                                        int32_t* __restrict__ start,
+                                                        int64_t* __restrict__ rowlen,
+                                                        unsigned long long* __restrict__ hist,
+                                                        int* __restrict__ guard) {
+  extern __shared__ unsigned srt_cnt[];       // [Q][64]
+  const int Q = 2 * b.K;
+  for (int i = threadIdx.x; i < Q * kLtLanes; i += 256) srt_cnt[i] = 0;
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t p = (int64_t)blockIdx.x * kLtLanes + lane;
+  if (p < npix) {
+    const int64_t x = p / nz;
+    const int z = (int)(p - x * nz);
+    const int64_t col = x * (int64_t)ny * nz + z;
+    for (int y0 = wv; y0 < ny; y0 += 4 * 8) {
+      double a[8], t[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int y = y0 + 4 * u;
+        const int64_t o = col + (int64_t)(y < ny ? y : ny - 1) * nz;
+        a[u] = __builtin_nontemporal_load(a0 + o);
+        t[u] = __builtin_nontemporal_load(ts + o);
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (y0 + 4 * u < ny && lt_keeps(a[u], t[u])) {
+          const double kw = __builtin_floor((t[u] - b.s0) * b.inv_h);      // (range guard)
+          if ((kw < 0.0 || kw > (double)b.K) && __builtin_fabs(kw) < __builtin_inf()) *guard = 1;
+          atomicAdd(&srt_cnt[lt_key(a[u], t[u], b) * kLtLanes + lane], 1u);
+        }
+    }
+  }
+  __syncthreads();
+  if (wv == 0) {
+    unsigned r = 0;
+    for (int q = 0; q < Q; ++q) {
+      if (p < npix) start[(int64_t)q * npix + p] = (int32_t)r;
+      r += srt_cnt[q * kLtLanes + lane];
+    }
+    if (p < npix) start[(int64_t)Q * npix + p] = (int32_t)r;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) r = max(r, (unsigned)__shfl_xor((int)r, d, RJP_WAVE));
+    if (lane == 0) rowlen[blockIdx.x] = (int64_t)r;
+  }
+  for (int q = wv; q < Q; q += 4) {
+    unsigned c = srt_cnt[q * kLtLanes + lane];
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) c += (unsigned)__shfl_xor((int)c, d, RJP_WAVE);
+    if (lane == 0 && c) atomicAdd(&hist[q], (unsigned long long)c);
+  }
+}
+
+// in-place exclusive prefix of n int64 lengths (one workgroup), the total goes to off[n]
+__global__ __launch_bounds__(1024) void srt_scan_kernel(int64_t* __restrict__ off, int64_t n) {
+  __shared__ long long part[1024];
+  const int64_t per = (n + 1023) / 1024;
+  const int64_t i0 = min(n, (int64_t)threadIdx.x * per), i1 = min(n, i0 + per);
+  long long s = 0;
+  for (int64_t i = i0; i < i1; ++i) s += off[i];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    long long r = 0;
+    for (int i = 0; i < 1024; ++i) { const long long v = part[i]; part[i] = r; r += v; }
+    off[n] = r;
+  }
+  __syncthreads();
+  long long r = part[threadIdx.x];
+  for (int64_t i = i0; i < i1; ++i) { const int64_t c = off[i]; off[i] = r; r += c; }
+}
+
+// One wave per group walks y once: the next free row of (lane, key) comes from LDS, the |a0| sums
+// per (lane, key) are added in LDS (each lane owns its column: no atomics) and written as prefix
+// sums at the end; aux as lt_fill_kernel's.  Rows behind a lane's cells, up to the group's
+// length, get (0, ts_lo); so do the rows of the lanes past the map's last sightline.
+__global__ __launch_bounds__(64) void srt_fill_kernel(const double* __restrict__ a0,
+                                                      const double* __restrict__ ts, int ny,
+                                                      int nz, int64_t npix, LtBins b,
+                                                      const int32_t* __restrict__ start,
+                                                      const int64_t* __restrict__ rowbase,
+                                                      rjp_d2* __restrict__ cells,
+                                                      double* __restrict__ cum,
+                                                      double* __restrict__ aux) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char srt_lds[];
+  const int Q = 2 * b.K;
+  double* sum = reinterpret_cast<double*>(srt_lds);                        // [Q][64]
+  unsigned* pos = reinterpret_cast<unsigned*>(srt_lds + (size_t)Q * kLtLanes * 8);   // [Q][64]
+  const int lane = threadIdx.x;
+  const int64_t p = (int64_t)blockIdx.x * kLtLanes + lane;
+  const bool live = p < npix;
+  for (int q = 0; q < Q; ++q) {
+    pos[q * kLtLanes + lane] = live ? (unsigned)start[(int64_t)q * npix + p] : 0u;
+    sum[q * kLtLanes + lane] = 0.0;
+  }
+  rjp_d2* base = cells + rowbase[blockIdx.x] * kLtLanes + lane;
+  const int nrow = (int)(rowbase[blockIdx.x + 1] - rowbase[blockIdx.x]);
+  int len = 0;
+  if (live) {
+    double nan_r = 0.0, nan_b = 0.0, has_inf = 0.0;
+    const int64_t x = p / nz;
+    const int z = (int)(p - x * nz);
+    const int64_t col = x * (int64_t)ny * nz + z;
+    for (int y0 = 0; y0 < ny; y0 += 8) {
+      double a[8], t[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int y = y0 + u;
+        const int64_t o = col + (int64_t)(y < ny ? y : ny - 1) * nz;
+        a[u] = __builtin_nontemporal_load(a0 + o);
+        t[u] = __builtin_nontemporal_load(ts + o);
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        if (y0 + u >= ny) continue;
+        const double am = __builtin_fabs(a[u]);
+        if (lt_keeps(a[u], t[u])) {
+          const int q = lt_key(a[u], t[u], b);
+          const unsigned r = pos[q * kLtLanes + lane];
+          pos[q * kLtLanes + lane] = r + 1;
+          sum[q * kLtLanes + lane] += am;
+          rjp_d2 c; c.x = am; c.y = t[u];
+          base[(int64_t)r * kLtLanes] = c;
+        } else if (am > 0.0) {                     // (NaN and zero weights: nansum drops them)
+          if (!(t[u] == t[u])) { if (signbit_d(a[u])) nan_r += am; else nan_b += am; }
+          else has_inf = 1.0;                      // finite launch time, infinite weight
+        }
+      }
+    }
+    aux[p] = nan_r;
+    aux[npix + p] = nan_b;
+    aux[2 * npix + p] = has_inf;
+    double c = 0.0;
+    for (int q = 0; q < Q; ++q) {
+      cum[(int64_t)q * npix + p] = c;
+      c += sum[q * kLtLanes + lane];
+    }
+    cum[(int64_t)Q * npix + p] = c;
+    len = start[(int64_t)Q * npix + p];
+  }
+  rjp_d2 pad; pad.x = 0.0; pad.y = b.s0;
+  for (int r = len; r < nrow; ++r) base[(int64_t)r * kLtLanes] = pad;
+}
+
+static LtBins srt_bins(const rjp_fields* fl, int K) {
+  const double span = fl->ts_hi - fl->ts_lo;
+  return LtBins{fl->ts_lo, span > 0.0 ? K / span : 1.0, K};
+}
+
+hipError_t srt_count_launch(const rjp_fields* fl, int K, int32_t* d_start, int64_t* d_rowbase,
+                            unsigned long long* d_hist, int* d_guard, hipStream_t st) {
+  const int64_t npix = (int64_t)fl->nx * fl->nz;
+  const int64_t G = (npix + kLtLanes - 1) / kLtLanes;
+  hipError_t e = hipMemsetAsync(d_hist, 0, (size_t)2 * K * sizeof(unsigned long long), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(srt_count_kernel, dim3((unsigned)G), dim3(256), (size_t)2 * K * kLtLanes * 4,
+                     st, (const double*)fl->d_a0, (const double*)fl->d_ts, fl->ny, fl->nz, npix,
+                     srt_bins(fl, K), d_start, d_rowbase, d_hist, d_guard);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(srt_scan_kernel, dim3(1), dim3(1024), 0, st, d_rowbase, G);
+  return hipGetLastError();
+}
+
+hipError_t srt_fill_launch(const rjp_fields* fl, int K, const int32_t* d_start,
+                           const int64_t* d_rowbase, void* d_cells, double* d_cum, double* d_aux,
+                           hipStream_t st) {
+  const int64_t npix = (int64_t)fl->nx * fl->nz;
+  const int64_t G = (npix + kLtLanes - 1) / kLtLanes;
+  hipLaunchKernelGGL(srt_fill_kernel, dim3((unsigned)G), dim3(64), (size_t)2 * K * kLtLanes * 12, st,
+                     (const double*)fl->d_a0, (const double*)fl->d_ts, fl->ny, fl->nz, npix,
+                     srt_bins(fl, K), d_start, d_rowbase, (rjp_d2*)d_cells, d_cum, d_aux);
+  return hipGetLastError();
+}
+
 // ---- the sweep ----------------------------------------------------------------------------------
 __device__ __forceinline__ rjp_d2 lt_load(const rjp_d2* p) { return __builtin_nontemporal_load(p); }
 

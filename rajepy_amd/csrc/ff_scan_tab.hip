@@ -220,6 +220,111 @@ __global__ __launch_bounds__(kBlock) void ff_scan_table_kernel(
   }
 }
 
+// The same scan on the launch-time-bucketed layout (rjp_fields.d_srt_*, built by ff_lt.hip): one
+// wave per group of 64 sightlines.  Outside a jet's bursts' support chi == 1 (to 1e-17), so per jet
+// only the bins [b0, b1) that meet the support at this epoch are read -- in every lane one run of
+// rows, [start(b0), start(b1)) -- and the |a0| sums of the other bins (prefix sums kept with the
+// layout) stand for the rest.  The wave streams the rows from the smallest start to the largest
+// end over its lanes, a lane masking the rows outside its own run; lanes are padded at their end
+// only, so the runs of a group line up to the Poisson noise of the counts.  The cells in the layout
+// are finite and non-zero with a finite launch time inside [ts_lo, ts_hi] (the build checked the
+// range); the dropped ones come back through aux as in the launch-time-ordered sweep: a NaN launch
+// time counts with chi = 1 when its jet has no bursts (what rjp_unmask_launch_times gives the
+// grid-order scan), an infinite weight makes the sightline +inf.
+#ifndef RJP_SRT_U
+#define RJP_SRT_U 8              /* rows of 16-byte loads in flight per lane */
+#endif
+constexpr int kSrtBlock = 512;   // 8 groups per workgroup: 512 workgroups at cfg4, one round
+struct SrtDev {
+  const rjp_d2* cells;
+  const int32_t* start;
+  const double* cum;
+  const int64_t* rowbase;
+  const double* aux;
+  int64_t npix;
+  int K;
+  int b0[2], b1[2], hb[2];
+};
+
+template <int U>
+__global__ __launch_bounds__(kSrtBlock) void ff_scan_sorted_kernel(SrtDev s, ChiTabDev t,
+                                                                   double t_epoch,
+                                                                   const double* __restrict__ tab,
+                                                                   double* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) double s_chi[];       // [2][ni][10]
+  for (int i = threadIdx.x; i < 2 * t.ni * kChiStride; i += kSrtBlock) s_chi[i] = tab[i];
+  __syncthreads();
+  const int lane = threadIdx.x & (RJP_WAVE - 1);
+  const int64_t g = (int64_t)blockIdx.x * (kSrtBlock / RJP_WAVE) + threadIdx.x / RJP_WAVE;
+  const int64_t npix = s.npix;
+  if (g * RJP_WAVE >= npix) return;                    // (whole waves)
+  const int64_t p = g * RJP_WAVE + lane;
+  const bool live = p < npix;
+  const rjp_d2* base = s.cells + s.rowbase[g] * RJP_WAVE + lane;
+  const double wmax = t.wmax;
+  double total = 0.0;
+#pragma unroll 1
+  for (int j = 0; j < 2; ++j) {
+    const int q0 = j * s.K, b0 = s.b0[j], b1 = s.b1[j];
+    int rs = 0, re = 0;
+    double skipped = 0.0;
+    if (live) {
+      const double* c = s.cum + p;
+      if (b0 < b1) {
+        skipped = (c[(int64_t)(q0 + s.K) * npix] - c[(int64_t)(q0 + b1) * npix]) +
+                  (c[(int64_t)(q0 + b0) * npix] - c[(int64_t)q0 * npix]);
+        rs = s.start[(int64_t)(q0 + b0) * npix + p];
+        re = s.start[(int64_t)(q0 + b1) * npix + p];
+      } else {
+        skipped = c[(int64_t)(q0 + s.K) * npix] - c[(int64_t)q0 * npix];
+      }
+    }
+    // the wave's rows: from the smallest start to the largest end of the lanes' non-empty runs
+    int lo = rs < re ? rs : 0x7fffffff, hi = rs < re ? re : 0;
+#pragma unroll
+    for (int d = RJP_WAVE / 2; d > 0; d >>= 1) {
+      lo = min(lo, __shfl_xor(lo, d, RJP_WAVE));
+      hi = max(hi, __shfl_xor(hi, d, RJP_WAVE));
+    }
+    lo = __builtin_amdgcn_readfirstlane(lo);
+    hi = __builtin_amdgcn_readfirstlane(hi);
+    const int koff = j == 0 ? 0 : t.ni;                // red jet: the first half of the table
+    double acc = 0.0;
+    for (int r = lo; r < hi; r += U) {
+      rjp_d2 cl[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int rr = r + u < hi ? r + u : hi - 1;    // (never past the wave's last row)
+        cl[u] = __builtin_nontemporal_load(base + (int64_t)rr * RJP_WAVE);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        double w = (t_epoch - cl[u].y - t.lo) * t.inv_h;
+        w = __builtin_fmin(__builtin_fmax(w, 0.0), wmax);
+        const double kf = __builtin_floor(w);
+        const double xi = __builtin_fma(2.0, w - kf, -1.0);
+        const rjp_d2* cp = reinterpret_cast<const rjp_d2*>(s_chi + ((int)kf + koff) * kChiStride);
+        const rjp_d2 c01 = cp[0], c23 = cp[1], c45 = cp[2], c67 = cp[3];
+        double chi = __builtin_fma(c67.y, xi, c67.x);
+        chi = __builtin_fma(chi, xi, c45.y);
+        chi = __builtin_fma(chi, xi, c45.x);
+        chi = __builtin_fma(chi, xi, c23.y);
+        chi = __builtin_fma(chi, xi, c23.x);
+        chi = __builtin_fma(chi, xi, c01.y);
+        chi = __builtin_fma(chi, xi, c01.x);
+        const bool mine = r + u >= rs && r + u < re;
+        acc = __builtin_fma(mine ? cl[u].x : 0.0, chi * chi, acc);
+      }
+    }
+    total += acc + skipped;
+  }
+  if (!live) return;
+  if (!s.hb[0]) total += s.aux[p];
+  if (!s.hb[1]) total += s.aux[npix + p];
+  if (s.aux[2 * npix + p] != 0.0) total = __builtin_inf();
+  out[p] = total;
+}
+
 // The same scan from the five MODEL fields (nd, xi, temp, pf, ts: SURVEY 8(d)'s byte model, what
 // a model without the derived scan fields a0 / em0 streams): optical-depth sums, emission measure
 // and T_avg of the epoch in one pass, the burst factor from the table.  Per-product NaN semantics
@@ -452,6 +557,44 @@ bool chi_table_plan(const rjp_fields* fl, const rjp_bursts* hb, const double* ep
   return true;
 }
 
+// The bins of the launch-time-bucketed layout a scan at t_epoch reads: per jet, those that meet
+// [t - s_hi, t - s_lo], the launch times for which the jet's own bursts' support (chi_reach, as
+// the table's) is reached.  A cell of a bin at the edge may lie outside the support: it is read,
+// and the table gives it chi = 1 to the table's bound, as the grid-order scan does.
+bool srt_plan(const rjp_fields* fl, const rjp_bursts* hb, double t_epoch, SrtPlan& sp) {
+  const int K = fl->srt_K;
+  if (!fl->d_srt_cells || !fl->d_srt_start || !fl->d_srt_cum || !fl->d_srt_rowbase ||
+      !fl->d_srt_aux || !fl->h_srt_hist || K < 1 || K > RJP_SRT_MAX_K || !hb)
+    return false;
+  const double span = fl->ts_hi - fl->ts_lo;
+  const double inv_h = span > 0.0 ? K / span : 1.0;           // (srt_bins: the layout's bins)
+  int64_t all = 0, read = 0;
+  for (int j = 0; j < 2; ++j) {
+    sp.hb[j] = hb->n[j] > 0;
+    sp.b0[j] = sp.b1[j] = 0;
+    if (sp.hb[j]) {
+      double s_lo = INFINITY, s_hi = -INFINITY;
+      for (int i = 0; i < hb->n[j]; ++i) {
+        const double sigma = std::sqrt(0.5 / hb->inv2s2[j][i]);
+        s_lo = std::min(s_lo, hb->t0[j][i] - chi_reach(hb->amp_rel[j][i]) * sigma);
+        s_hi = std::max(s_hi, hb->t0[j][i] + chi_reach(hb->amp_rel[j][i]) * sigma);
+      }
+      const double w0 = std::floor((t_epoch - s_hi - fl->ts_lo) * inv_h);
+      const double w1 = std::floor((t_epoch - s_lo - fl->ts_lo) * inv_h) + 1.0;
+      const int b0 = (int)std::min(std::max(w0, 0.0), (double)K);
+      const int b1 = (int)std::min(std::max(w1, 0.0), (double)K);
+      if (b1 > b0) { sp.b0[j] = b0; sp.b1[j] = b1; }
+    }
+    for (int b = 0; b < K; ++b) {
+      const int64_t n = fl->h_srt_hist[j * K + b];
+      all += n;
+      if (b >= sp.b0[j] && b < sp.b1[j]) read += n;
+    }
+  }
+  sp.share = all > 0 ? (double)read / (double)all : 0.0;
+  return sp.share <= 0.9;
+}
+
 // y-ranges of the table scan on a map of `npix` sightlines and `ny` rows: one when the sightline
 // chunks alone give every CU two workgroups, else as many as it takes (powers of two, >= 64 rows
 // each; the partials are reduced in ff_reduce_kernel's fixed order)
@@ -475,7 +618,8 @@ size_t chi_table_workspace_bytes(int64_t npix, int ny) {
 
 hipError_t chi_table_scan(const rjp_fields* fl, const ChiPlan& cp, const double* d_stage,
                           double t_epoch, int mode, double* sumA, double* em, double* tavg,
-                          double* ws, size_t work_bytes, int* d_guard, hipStream_t st) {
+                          double* ws, size_t work_bytes, int* d_guard, hipStream_t st,
+                          const SrtPlan* sp) {
   const int64_t npix = (int64_t)fl->nx * fl->nz;
   const int64_t nchunks = npix / 2;
   const size_t tab_doubles = (size_t)2 * cp.ni * kChiStride;
@@ -514,7 +658,21 @@ hipError_t chi_table_scan(const rjp_fields* fl, const ChiPlan& cp, const double*
     e = hipFuncSetAttribute((const void*)ff_scan_table_kernel<RJP_TAB_U_EM, true>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, kMaxShm);
     if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute((const void*)ff_scan_sorted_kernel<RJP_SRT_U>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, kMaxShm);
+    if (e != hipSuccess) return e;
     cp.attr_set = true;
+  }
+  if (sp && !cp.wide && !em) {
+    // the launch-time-bucketed layout: sums straight to the map, no y-ranges
+    const SrtDev s{(const rjp_d2*)fl->d_srt_cells, fl->d_srt_start, fl->d_srt_cum, fl->d_srt_rowbase,
+                   fl->d_srt_aux, npix, fl->srt_K, {sp->b0[0], sp->b0[1]}, {sp->b1[0], sp->b1[1]},
+                   {sp->hb[0], sp->hb[1]}};
+    const int64_t groups = (npix + RJP_WAVE - 1) / RJP_WAVE;
+    const int64_t per = kSrtBlock / RJP_WAVE;
+    hipLaunchKernelGGL((ff_scan_sorted_kernel<RJP_SRT_U>), dim3((unsigned)((groups + per - 1) / per)),
+                       dim3(kSrtBlock), shm, st, s, t, t_epoch, (const double*)d_tab, sumA);
+    return hipGetLastError();
   }
   const dim3 grid((unsigned)(wgs * nsplit));
   if (cp.wide) {

@@ -78,9 +78,19 @@ struct ChiPlan {
 size_t chi_table_workspace_bytes(int64_t npix, int ny);
 bool chi_table_plan(const rjp_fields* fl, const rjp_bursts* hb, const double* epochs, int n_epochs,
                     int mode, bool want_em, size_t work_bytes, ChiPlan& cp);
+// the bins a single-epoch scan reads from the launch-time-bucketed layout: per jet [b0, b1) (the
+// bins that meet the jet's bursts' support at the epoch; empty for a jet without bursts)
+struct SrtPlan {
+  int b0[2] = {0, 0}, b1[2] = {0, 0};
+  int hb[2] = {0, 0};             // the jet has bursts
+  double share = 0.0;             // the map's cells in those bins / all cells in the layout
+};
+// false: no layout attached, or too large a share of it would be read (the grid order is as fast)
+bool srt_plan(const rjp_fields* fl, const rjp_bursts* hb, double t_epoch, SrtPlan& sp);
 hipError_t chi_table_scan(const rjp_fields* fl, const ChiPlan& cp, const double* d_stage,
                           double t_epoch, int mode, double* sumA, double* em, double* tavg,
-                          double* ws, size_t work_bytes, int* d_guard, hipStream_t st);
+                          double* ws, size_t work_bytes, int* d_guard, hipStream_t st,
+                          const SrtPlan* sp = nullptr);
 
 // ---- ff_moments.hip: epoch sweeps by launch-time moments --------------------------------------
 #define RJP_MOM_MAX_IDX 1280      /* 2 jets x K bins x N Chebyshev moments <= this (160 KB of LDS
@@ -145,6 +155,14 @@ hipError_t lt_fill_launch(const rjp_fields* fl, int K, const int32_t* d_rowoff, 
                           double* d_aux, hipStream_t st);
 hipError_t lt_run(const rjp_fields* fl, const MomPlan& mp, int n_epochs, double* sumA, double* ws,
                   size_t work_bytes, hipStream_t st);
+// launch-time-bucketed layout for single-epoch scans (ff_lt.hip; its scan: ff_scan_tab.hip)
+#define RJP_SRT_MAX_K 32         /* the fill pass keeps 12 bytes per (lane, key) in LDS: 48 KiB */
+size_t srt_index_entries(int nx, int nz, int K);
+hipError_t srt_count_launch(const rjp_fields* fl, int K, int32_t* d_start, int64_t* d_rowbase,
+                            unsigned long long* d_hist, int* d_guard, hipStream_t st);
+hipError_t srt_fill_launch(const rjp_fields* fl, int K, const int32_t* d_start,
+                           const int64_t* d_rowbase, void* d_cells, double* d_cum, double* d_aux,
+                           hipStream_t st);
 hipError_t field_range_launch(const void* d_field, int64_t n, int dtype, double* d_part,
                               hipStream_t st);
 hipError_t range_check_launch(const void* d_field, int64_t n, int dtype, double lo, double hi,

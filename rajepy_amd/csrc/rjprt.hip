@@ -24,6 +24,7 @@ struct rjp_ctx {
   rjp::MomPlan mom;               // last moment-path request (its tables are reused)
   rjp::ChiPlan chi;               // the burst-factor table of the last single-epoch scan
   int last_path = 0;              // 0 = epoch tiles, 1 = LDS moments, 2 = launch-time-ordered layout
+  int last_layout = 0;            // 0 = grid order, 1 = launch-time-bucketed layout (rjp_last_scan_layout)
   static constexpr int kSlots = 8;
   struct Slot {
     double* h = nullptr;
@@ -43,6 +44,7 @@ struct rjp_ctx {
   // checked against their launch-time field with a pass of its own (most recent first).
   int* guard = nullptr;
   unsigned long long* d_count = nullptr;      // device word of rjp_occupied_cells
+  unsigned long long* d_srt_hist = nullptr;   // RJP_SRT_MAX_K * 2 counters of rjp_srt_count
   struct RangeKey {
     const void* d_ts = nullptr;
     int64_t n = 0;
@@ -276,6 +278,7 @@ int rjp_ctx_destroy(rjp_ctx* ctx) {
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
   if (ctx->guard) (void)hipHostFree(ctx->guard);
   if (ctx->d_count) (void)hipFree(ctx->d_count);
+  if (ctx->d_srt_hist) (void)hipFree(ctx->d_srt_hist);
   rjp::moments_release(ctx->mom);
   delete ctx;
   return RJP_OK;
@@ -422,6 +425,7 @@ static int ff_scan_impl(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts
   if (work_bytes < rjp::ff_scan_workspace_bytes(fields->nx, fields->ny, fields->nz, n_epochs))
     return fail(ctx, RJP_ERR_WORKSPACE, "rjp_ff_scan: workspace smaller than rjp_ff_scan_workspace()");
   hipStream_t st = (hipStream_t)stream;
+  ctx->last_layout = 0;
   // epoch sweeps by launch-time moments (ff_moments.hip) when the caller provided the launch-time
   // range and the host-side accuracy check of the expansion passes
   const int mr = rjp::moments_plan(fields, bursts, h_epochs_s, n_epochs, gff_mode, d_em != nullptr,
@@ -488,13 +492,19 @@ static int ff_scan_impl(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts
     // single epoch on the tau layout: the burst factor from a table in LDS (ff_scan_tab.hip)
     if (int r = check_ts_range(ctx, fields, st)) return r;
     ctx->last_path = 3;
+    // ... reading only the launch-time bins inside the bursts' support when the caller attached
+    // the bucketed layout and the epoch leaves enough of it out
+    rjp::SrtPlan sp;
+    const bool srt = !ctx->chi.wide && !d_em && rjp::srt_plan(fields, bursts, h_epochs_s[0], sp);
+    ctx->last_layout = srt ? 1 : 0;
     const double* src[1] = {ctx->chi.stage.data()};
     const size_t len[1] = {ctx->chi.stage.size()};
     double* dev[1];
     if (int r = stage_tables(ctx, st, src, len, 1, dev)) return r;
     return finish_staged(ctx, st, rjp::chi_table_scan(fields, ctx->chi, dev[0], h_epochs_s[0],
                                                       gff_mode, d_sumA, d_em, d_tavg,
-                                                      (double*)d_work, work_bytes, ctx->guard, st),
+                                                      (double*)d_work, work_bytes, ctx->guard, st,
+                                                      srt ? &sp : nullptr),
                          "chi_table_scan");
   }
   ctx->last_path = 0;
@@ -545,6 +555,8 @@ int rjp_last_scan_path(const rjp_ctx* ctx, double* worst_rel_err, int32_t* momen
   }
   return ctx->last_path;
 }
+
+int rjp_last_scan_layout(const rjp_ctx* ctx) { return ctx ? ctx->last_layout : RJP_ERR_ARG; }
 
 double rjp_last_table_build_ms(const rjp_ctx* ctx) { return ctx ? ctx->mom.build_ms : 0.0; }
 
@@ -599,6 +611,64 @@ int rjp_lt_fill(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, const int32_t
   if (int r = check_lt(ctx, fields, K)) return r;
   if (!d_rowoff || !d_cells || !d_aux) return fail(ctx, RJP_ERR_ARG, "rjp_lt_fill: NULL argument");
   RJP_HIP(ctx, rjp::lt_fill_launch(fields, K, d_rowoff, d_cells, d_aux, (hipStream_t)stream));
+  return RJP_OK;
+}
+
+size_t rjp_srt_index_entries(int32_t nx, int32_t nz, int32_t K) {
+  if (nx <= 0 || nz <= 0 || K < 1 || K > RJP_SRT_MAX_K) return 0;
+  return rjp::srt_index_entries(nx, nz, K);
+}
+
+static int check_srt(rjp_ctx* ctx, const rjp_fields* f, int32_t K) {
+  if (!f) return fail(ctx, RJP_ERR_ARG, "fields is NULL");
+  if (f->dtype != RJP_F64 || !f->d_a0 || !f->d_ts)
+    return fail(ctx, RJP_ERR_ARG, "launch-time-bucketed layout: needs RJP_F64 fields with d_a0 and d_ts");
+  if (f->nx <= 0 || f->ny <= 0 || f->nz <= 0)
+    return fail(ctx, RJP_ERR_ARG, "launch-time-bucketed layout: grid dimensions must be positive");
+  if (K < 1 || K > RJP_SRT_MAX_K)
+    return fail(ctx, RJP_ERR_ARG, "launch-time-bucketed layout: 1 <= K <= 32");
+  if (!(f->ts_hi >= f->ts_lo) || !std::isfinite(f->ts_lo) || !std::isfinite(f->ts_hi) ||
+      (f->ts_lo == 0.0 && f->ts_hi == 0.0))
+    return fail(ctx, RJP_ERR_ARG, "launch-time-bucketed layout: fields.ts_lo / ts_hi (rjp_field_range) required");
+  return RJP_OK;
+}
+
+int rjp_srt_count(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, int32_t* d_start,
+                  int64_t* d_rowbase, int64_t* h_hist, int64_t* h_total_rows, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = check_srt(ctx, fields, K)) return r;
+  if (!d_start || !d_rowbase || !h_hist || !h_total_rows)
+    return fail(ctx, RJP_ERR_ARG, "rjp_srt_count: NULL output");
+  hipStream_t st = (hipStream_t)stream;
+  if (!ctx->d_srt_hist)
+    RJP_HIP(ctx, hipMalloc((void**)&ctx->d_srt_hist, 2 * RJP_SRT_MAX_K * sizeof(unsigned long long)));
+  RJP_HIP(ctx, rjp::srt_count_launch(fields, K, d_start, d_rowbase, ctx->d_srt_hist, ctx->guard, st));
+  const int64_t G = ((int64_t)fields->nx * fields->nz + 63) / 64;
+  int64_t total = 0;
+  unsigned long long hist[2 * RJP_SRT_MAX_K];
+  RJP_HIP(ctx, hipMemcpyAsync(&total, d_rowbase + G, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  RJP_HIP(ctx, hipMemcpyAsync(hist, ctx->d_srt_hist, 2 * K * sizeof(unsigned long long),
+                              hipMemcpyDeviceToHost, st));
+  RJP_HIP(ctx, hipStreamSynchronize(st));
+  if (*(volatile int*)ctx->guard != 0) {
+    *(volatile int*)ctx->guard = 0;
+    return fail(ctx, RJP_ERR_ARG, "rjp_srt_count: fields.ts_lo / ts_hi do not contain every launch "
+                                  "time of the cells the layout keeps (rjp_field_range)");
+  }
+  for (int q = 0; q < 2 * K; ++q) h_hist[q] = (int64_t)hist[q];
+  *h_total_rows = total;
+  return RJP_OK;
+}
+
+int rjp_srt_fill(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, const int32_t* d_start,
+                 const int64_t* d_rowbase, void* d_cells, double* d_cum, double* d_aux,
+                 void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = check_srt(ctx, fields, K)) return r;
+  if (!d_start || !d_rowbase || !d_cells || !d_cum || !d_aux)
+    return fail(ctx, RJP_ERR_ARG, "rjp_srt_fill: NULL argument");
+  RJP_HIP(ctx, rjp::srt_fill_launch(fields, K, d_start, d_rowbase, d_cells, d_cum, d_aux,
+                                    (hipStream_t)stream));
   return RJP_OK;
 }
 

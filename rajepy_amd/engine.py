@@ -38,6 +38,7 @@ class DeviceFields:
         self._ts_range_of = None            # ... and the `ts` tensor it was measured on
         self.lt = None                      # optional launch-time-ordered layout (RTEngine.build_lt)
         self.mom_cache = None               # optional cache of the launch-time moment maps of a0
+        self.srt = None                     # optional launch-time-bucketed layout (RTEngine.build_sorted)
 
     @property
     def ncells(self):
@@ -151,6 +152,10 @@ class RTEngine:
         # single-epoch scans of large maps on the tau layout take the burst factor from a table in
         # LDS (ff_scan_tab.hip; needs the launch-time range); False: always the Gaussians
         self.use_chi_table = True
+        # ... and read only the launch-time bins inside the bursts' support from the bucketed
+        # layout the producers attach (build_sorted); False: always the grid order (A/B runs)
+        self.use_sorted = True
+        self.srt_min_free = 0.2        # the layout is built only if this share of HBM stays free
         # keep the launch-time moment maps of a model that is swept repeatedly (2.7 GB at
         # 512 x 512 sightlines): from the second long sweep on only the contraction runs
         self.cache_moments = True
@@ -279,6 +284,7 @@ class RTEngine:
         fields.lt = None
         fields.mom_cache = None
         fields._ts_unmasked = None
+        fields.srt = None
 
     def tavg(self, fields):
         """T_avg map of the model, nanmean_y(T where T > 0) -> device tensor [P] (rjp_tavg):
@@ -357,6 +363,80 @@ class RTEngine:
                      "key": (fields.a0.data_ptr(), fields.ts.data_ptr(), fs.ts_lo, fs.ts_hi)}
         return fields.lt
 
+    @staticmethod
+    def _srt_key(fields, fs):
+        """What the launch-time-bucketed layout was built from: `_version` catches in-place edits
+        of a0 / ts under the same pointer."""
+        return (fields.a0.data_ptr(), fields.a0._version, fields.ts.data_ptr(),
+                fields.ts._version, fs.ts_lo, fs.ts_hi, int(fields.a0_mode))
+
+    def _srt_qualifies(self, fields):
+        """Maps the single-epoch table path takes (include/rjprt.h `rjp_fields.ts_lo`: f64, tau
+        layout, >= 32768 sightlines) -- the only scans that read the layout -- with sightlines of
+        >= 256 rows: a scan reads <= 80 bytes of the index per sightline, <= 2 % of its cells'."""
+        nx, ny, nz = fields.shape
+        return (self.use_sorted and fields.dtype == RJP_F64 and fields.a0 is not None and
+                fields.ts is not None and (nx * nz) // 2 >= 64 * 256 and ny >= 256)
+
+    def build_sorted(self, fields, K=32):
+        """Attach the launch-time-bucketed layout of (a0, ts) (rjp_srt_count + rjp_srt_fill;
+        include/rjprt.h `rjp_fields.d_srt_cells`): per group of 64 sightlines every lane's cells
+        sorted by (jet, launch-time bin), padded at the lane's end only.  A single-epoch scan then
+        reads only the bins inside the bursts' support at its epoch.  Per-model state like a0:
+        ~1.03 x the bytes of a0 + ts; built only when `srt_min_free` of the HBM stays free
+        afterwards (returns None and attaches nothing otherwise).  Rebuild after `a0` or `ts`
+        change (a stale layout is never attached: the key holds the tensors' versions)."""
+        torch = _torch()
+        fields.srt = None
+        if fields.a0 is None or fields.ts is None or fields.dtype != RJP_F64:
+            raise ValueError("the launch-time-bucketed layout needs f64 fields with the tau "
+                             "layout (a0) and launch times")
+        if self.launch_time_range(fields) is None:
+            return None
+        fs = fields.struct()
+        nx, ny, nz = fields.shape
+        n_idx = self.lib.rjp_srt_index_entries(nx, nz, int(K))
+        if n_idx == 0:
+            raise ValueError("K must be 1..32")
+        groups = (fields.npix + 63) // 64
+        start = torch.empty(n_idx, dtype=torch.int32, device=self.device)
+        rowbase = torch.empty(groups + 1, dtype=torch.int64, device=self.device)
+        hist = (C.c_int64 * (2 * int(K)))()
+        total = C.c_int64()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        ev[0].record()
+        _lib.check(self.lib.rjp_srt_count(self.ctx, C.byref(fs), int(K), start.data_ptr(),
+                                          rowbase.data_ptr(), hist, C.byref(total),
+                                          self._stream()), self.ctx, "rjp_srt_count")
+        ev[1].record()
+        need = total.value * 64 * 16 + n_idx * 8 + 3 * fields.npix * 8
+        free, hbm = torch.cuda.mem_get_info(self.device)
+        free += torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
+        if free - need < self.srt_min_free * hbm:
+            return None
+        cells = torch.empty(max(1, total.value) * 64 * 2, dtype=torch.float64, device=self.device)
+        cum = torch.empty(n_idx, dtype=torch.float64, device=self.device)
+        aux = torch.empty(3 * fields.npix, dtype=torch.float64, device=self.device)
+        ev[2].record()
+        _lib.check(self.lib.rjp_srt_fill(self.ctx, C.byref(fs), int(K), start.data_ptr(),
+                                         rowbase.data_ptr(), cells.data_ptr(), cum.data_ptr(),
+                                         aux.data_ptr(), self._stream()),
+                   self.ctx, "rjp_srt_fill")
+        ev[3].record()
+        torch.cuda.synchronize(self.device)
+        fields.srt = {"cells": cells, "start": start, "cum": cum, "rowbase": rowbase, "aux": aux,
+                      "hist": hist, "K": int(K), "rows": int(total.value),
+                      "build_ms": ev[0].elapsed_time(ev[1]) + ev[2].elapsed_time(ev[3]),
+                      "build_with_allocation_ms": ev[0].elapsed_time(ev[3]),
+                      "bytes": need, "key": self._srt_key(fields, fs)}
+        return fields.srt
+
+    def _attach_sorted(self, fields):
+        """Producers: the bucketed layout right after a0, for maps that take the table path."""
+        if self._srt_qualifies(fields):
+            self.build_sorted(fields)
+        return fields
+
     def compute_y_bounds(self, fields):
         """Attach the per-sightline occupied y-range to `fields` (rjp_y_bounds): later scans
         skip the rows no cell of which can contribute.  Recompute after changing a field."""
@@ -395,6 +475,7 @@ class RTEngine:
         setattr(fields, name, dst)
         if name in ("ts", "xi", "temp"):
             fields.lt = None                    # the launch-time-ordered layout holds (a0, ts)
+            fields.srt = None                   # ... and so does the bucketed one
             fields.mom_cache = None             # ... and the moment maps are sums over them
         if name == "ts":
             # what was measured on / derived from the old launch times (the new tensor may well
@@ -453,9 +534,12 @@ class RTEngine:
             out.em0 = em0
             if a0 is not None:
                 out.a0, out.a0_mode = a0, int(tau_mode)
+                self._attach_sorted(out)
             return out
         out = self.compact(out)
-        return self.tau_layout(out, tau_mode) if tau_mode is not None else out
+        if tau_mode is None:
+            return out
+        return self._attach_sorted(self.tau_layout(out, tau_mode))
 
     def build_wide(self, fields, geom):
         """Attach the wide fields a lean model left out (K4 again, writing nd / xi / pf / vy only):
@@ -507,9 +591,11 @@ class RTEngine:
         if em0 is not None:
             out.em0 = em0
         if em0 is not None or not with_em0:
-            return out
+            return self._attach_sorted(out) if a0 is not None else out
         out = self.compact(out)
-        return self.tau_layout(out, tau_mode) if tau_mode is not None else out
+        if tau_mode is None:
+            return out
+        return self._attach_sorted(self.tau_layout(out, tau_mode))
 
     # -- K1 / K2 -----------------------------------------------------------------------------
     def _scan_struct(self, fields, bursts, n_epochs=1):
@@ -529,6 +615,19 @@ class RTEngine:
         if not (self.use_lt and self.use_moments):
             fs.d_lt_cells = fs.d_lt_rowoff = fs.d_lt_aux = None
             fs.lt_K = 0
+        srt = fields.srt
+        if (srt is not None and n_epochs == 1 and self.use_sorted and self.use_chi_table and
+                fields.a0 is not None and fields.ts is not None and
+                srt["key"] == self._srt_key(fields, fs)):
+            # (built from fields.ts itself: a jet without bursts gets its NaN launch times back
+            # through the layout's aux sums, whatever copy of the launch times the scan is given)
+            fs.d_srt_cells = srt["cells"].data_ptr()
+            fs.d_srt_start = srt["start"].data_ptr()
+            fs.d_srt_cum = srt["cum"].data_ptr()
+            fs.d_srt_rowbase = srt["rowbase"].data_ptr()
+            fs.d_srt_aux = srt["aux"].data_ptr()
+            fs.h_srt_hist = C.cast(srt["hist"], C.c_void_p)
+            fs.srt_K = srt["K"]
         if not self.use_moments and n_epochs != 1:
             fs.ts_lo = fs.ts_hi = 0.0
         elif self.force_moments:
@@ -679,6 +778,12 @@ class RTEngine:
         path = self.lib.rjp_last_scan_path(self.ctx, C.byref(err), shape)
         self.last_moment_shape = (int(shape[0]), int(shape[1]))      # (bins, order); (0, 0) = tiles
         return {0: "tiles", 1: "moments", 2: "lt", 3: "table", 4: "cached"}[path], err.value
+
+    def last_scan_layout(self):
+        """Which layout of (a0, ts) the last scan read (rjp_last_scan_layout): 'grid' (grid
+        order) or 'sorted' (the launch-time-bucketed layout, only the bins inside the bursts'
+        support).  `last_scan_path` says 'table' for both: chi comes from the table either way."""
+        return {0: "grid", 1: "sorted"}[self.lib.rjp_last_scan_layout(self.ctx)]
 
     def last_table_build_ms(self):
         """Host wall time of the last coefficient-table build (a new bursts / epochs request)."""
