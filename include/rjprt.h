@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define RJP_VERSION 110          /* 0.1.10 */
+#define RJP_VERSION 111          /* 0.1.11 */
 #define RJP_RANGE_BLOCKS 2048    /* partial (min, max) pairs rjp_field_range writes */
 #define RJP_MAX_EPOCH_TILE 32    /* most epochs evaluated per grid pass: 32 uniformly spaced ones (with or without d_em), 16 when only 16-31 are left, else tiles of 8, 4, 2, 1 */
 
@@ -185,15 +185,27 @@ typedef struct rjp_fields {
    * take it when the table path applies (single epoch, no d_em, no d_tavg) and at most 90 % of
    * the cells (h_srt_hist) fall into those bins, else they scan a0 / ts in grid order;
    * rjp_last_scan_layout() says which.  It belongs to the d_a0, d_ts, ts_lo, ts_hi it was built
-   * from: rebuild after any of them changes. */
+   * from: rebuild after any of them changes.
+   * Optional with it (NULL / 0 = absent: every bin of the support is read): the layout's Chebyshev
+   * moments, built by rjp_srt_moments() from the layout alone,
+   *   d_srt_mom[(q * (srt_N - 1) + n - 1) * P + p] = sum |a0| T_n(x),  n = 1 .. srt_N - 1,
+   * over the cells of key q of sightline p, x = 2 (w - bin) - 1 in [-1, 1] with w = (ts - ts_lo)
+   * srt_K / (ts_hi - ts_lo) (the layout's bins, clamping included; M_0 is the d_srt_cum step).
+   * Per call, a small kernel interpolates chi^2 on every bin of the support at srt_N Chebyshev
+   * nodes and accepts the bin when the interpolant matches, at 4 srt_N points across it, both the
+   * exact chi^2 and the table's to 2e-14 relative; the scan then contracts an accepted bin from
+   * its moments ((srt_N - 1) x 8 bytes per sightline) instead of reading its cells (16 bytes
+   * each) wherever that reads fewer bytes for the group.  rjp_last_srt_bins() counts both kinds.
+   * The moments belong to the layout: rebuild them with it. */
   const void* d_srt_cells;
   const int32_t* d_srt_start;
   const double* d_srt_cum;
   const int64_t* d_srt_rowbase;
   const double* d_srt_aux;
   const int64_t* h_srt_hist;
+  const double* d_srt_mom;
   int32_t srt_K;            /* launch-time bins per jet, 1..32 */
-  int32_t reserved3_;       /* 0 */
+  int32_t srt_N;            /* order of d_srt_mom: 16, 20 or 24 (0 = no moments) */
 } rjp_fields;
 
 /* Ejection bursts (classes.py:399-463): mdot(t)/mdot_ss = 1 + sum_b amp_rel_b *
@@ -328,6 +340,12 @@ int rjp_last_scan_path(const rjp_ctx* ctx, double* worst_rel_err, int32_t* momen
  * reports 3: chi still comes from the table).  For tests and the bench line. */
 int rjp_last_scan_layout(const rjp_ctx* ctx);
 
+/* (jet, bin) decisions of the last rjp_ff_scan / rjp_ff_step of this context on the bucketed
+ * layout with moments attached, summed over the groups of 64 sightlines that hold the jet: in
+ * *contracted the bins taken from rjp_fields.d_srt_mom, in *read the bins of the support read cell
+ * by cell (both 0 after a scan without moments).  SYNCHRONISES the device.  For tests. */
+int rjp_last_srt_bins(rjp_ctx* ctx, int64_t* contracted, int64_t* read);
+
 /* Host wall time [ms] the last table build of this context took (the coefficient tables of the
  * moment paths are built and checked on the device when the bursts or epochs of a sweep change:
  * one small launch and ONE stream synchronisation inside that rjp_ff_scan; a repeated request
@@ -373,6 +391,14 @@ int rjp_srt_count(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, int32_t* d_
 int rjp_srt_fill(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, const int32_t* d_start,
                  const int64_t* d_rowbase, void* d_cells, double* d_cum, double* d_aux,
                  void* stream);
+/* The layout's Chebyshev moments (rjp_fields.d_srt_mom): rjp_srt_moment_entries(nx, nz, K, N) =
+ * 2 K (N - 1) nx nz doubles (0 for an N other than 16, 20, 24 or a bad K), written by
+ * rjp_srt_moments from a layout rjp_srt_fill has built with the same fields and K.  One pass over
+ * the layout's rows (~1.03 x the bytes of a0 + ts), f64 sums in a fixed order. */
+size_t rjp_srt_moment_entries(int32_t nx, int32_t nz, int32_t K, int32_t N);
+int rjp_srt_moments(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, int32_t N,
+                    const int32_t* d_start, const int64_t* d_rowbase, const void* d_cells,
+                    double* d_mom, void* stream);
 
 /* ---- K2: per-channel map stage --------------------------------------------------------
  * Replaces the map-level arithmetic of optical_depth_ff / intensity_ff / flux_ff

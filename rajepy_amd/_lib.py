@@ -18,7 +18,7 @@ RJP_F32, RJP_F64 = 4, 8
 RJP_GFF_SCALAR, RJP_GFF_POWERLAW = 0, 1
 RJP_MAX_EPOCH_TILE = 32
 RJP_RANGE_BLOCKS = 2048
-RJP_VERSION = 110             # include/rjprt.h; the binding below matches exactly this ABI
+RJP_VERSION = 111             # include/rjprt.h; the binding below matches exactly this ABI
 RJP_OK = 0
 RJP_ERR_ARG, RJP_ERR_HIP, RJP_ERR_NODEVICE, RJP_ERR_WORKSPACE, RJP_ERR_DEGENERATE = \
     -1, -2, -3, -4, -5
@@ -47,7 +47,7 @@ class Fields(C.Structure):
                 ("d_srt_cells", C.c_void_p), ("d_srt_start", C.c_void_p),
                 ("d_srt_cum", C.c_void_p), ("d_srt_rowbase", C.c_void_p),
                 ("d_srt_aux", C.c_void_p), ("h_srt_hist", C.c_void_p),
-                ("srt_K", C.c_int32), ("reserved3_", C.c_int32)]
+                ("d_srt_mom", C.c_void_p), ("srt_K", C.c_int32), ("srt_N", C.c_int32)]
 
 
 class Bursts(C.Structure):
@@ -104,6 +104,7 @@ SIGNATURES = {
     "rjp_range_guard": (C.c_int, [_P]),
     "rjp_last_scan_path": (C.c_int, [_P, _DP, C.POINTER(C.c_int32)]),
     "rjp_last_scan_layout": (C.c_int, [_P]),
+    "rjp_last_srt_bins": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "rjp_last_table_build_ms": (C.c_double, [_P]),
     "rjp_moment_cache_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rjp_lt_rowoff_entries": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
@@ -113,6 +114,9 @@ SIGNATURES = {
     "rjp_srt_count": (C.c_int, [_P, C.POINTER(Fields), C.c_int32, _P, _P, _P,
                                 C.POINTER(C.c_int64), _P]),
     "rjp_srt_fill": (C.c_int, [_P, C.POINTER(Fields), C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "rjp_srt_moment_entries": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "rjp_srt_moments": (C.c_int, [_P, C.POINTER(Fields), C.c_int32, C.c_int32, _P, _P, _P, _P,
+                                  _P]),
     "rjp_ff_maps_workspace": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "rjp_ff_maps": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, _DP, _DP, C.c_int32,
                               _P, _P, _P, _P, C.c_size_t, _P]),

@@ -389,6 +389,109 @@ hipError_t srt_fill_launch(const rjp_fields* fl, int K, const int32_t* d_start,
   return hipGetLastError();
 }
 
+// ---- Chebyshev moments of the bucketed layout (rjp_fields.d_srt_mom) ---------------------------
+// Per sightline p, key q and order n = 1..N-1: M_n = sum |a0| T_n(x) over the cells of the key,
+// x = 2 (w - k) - 1 with w = (ts - ts_lo) K / span and k the cell's bin (lt_key's bin, clamping
+// included: a cell at ts_hi has x = 1).  M_0 is the d_srt_cum difference.  A single-epoch scan
+// contracts them with the Chebyshev coefficients of chi^2 on the bin (ff_scan_tab.hip) instead of
+// reading the bin's cells.  One wave per group streams its rows once, in the fill's order; every
+// lane keeps the moments of its current key in registers and writes them (key-major, sightline-
+// minor: mom[(q (N - 1) + n - 1) P + p]) when its key changes -- every key, empty ones as zeros.
+// The key of a row follows from the lane's jet boundary (d_srt_start at key K) and the bin of ts,
+// computed as lt_key computes it.  f64, one fixed order per lane.
+size_t srt_moment_entries(int nx, int nz, int K, int N) {
+  return (size_t)2 * K * (N - 1) * nx * nz;
+}
+
+constexpr int kSrtMomRows = 8;               // rows of 16-byte loads in flight per lane
+
+template <int N>
+__global__ __launch_bounds__(256) void srt_moments_kernel(const rjp_d2* __restrict__ cells,
+                                                          const int32_t* __restrict__ start,
+                                                          const int64_t* __restrict__ rowbase,
+                                                          int64_t npix, LtBins b,
+                                                          double* __restrict__ mom) {
+  constexpr int U = kSrtMomRows;
+  const int lane = threadIdx.x & (kLtLanes - 1);
+  const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g * kLtLanes >= npix) return;                    // (whole waves)
+  const int64_t p = g * kLtLanes + lane;
+  const bool live = p < npix;
+  const int Q = 2 * b.K;
+  const int len = live ? start[(int64_t)Q * npix + p] : 0;
+  const int blue = live ? start[(int64_t)b.K * npix + p] : 0;      // the lane's first blue row
+  const int nrow = (int)(rowbase[g + 1] - rowbase[g]);
+  const rjp_d2* base = cells + rowbase[g] * kLtLanes + lane;
+  double M[N - 1];
+#pragma unroll
+  for (int n = 0; n < N - 1; ++n) M[n] = 0.0;
+  int qc = 0;
+  // the moments of keys qc .. qe - 1 (all but the first empty) go out, qc becomes qe
+  auto flush_to = [&](int qe) __attribute__((always_inline)) {
+    for (; qc < qe; ++qc) {
+      double* o = mom + (int64_t)qc * (N - 1) * npix + p;
+#pragma unroll
+      for (int n = 0; n < N - 1; ++n) {
+        o[(int64_t)n * npix] = M[n];
+        M[n] = 0.0;
+      }
+    }
+  };
+  for (int r = 0; r < nrow; r += U) {
+    rjp_d2 cl[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int rr = r + u < nrow ? r + u : nrow - 1;  // (never past the group's last row)
+      cl[u] = __builtin_nontemporal_load(base + (int64_t)rr * kLtLanes);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (r + u >= len) continue;
+      const double w = (cl[u].y - b.s0) * b.inv_h;
+      const double kf = __builtin_fmin(__builtin_fmax(__builtin_floor(w), 0.0), (double)(b.K - 1));
+      const int q = (r + u >= blue ? b.K : 0) + (int)kf;
+      if (q != qc) flush_to(q);
+      const double x = __builtin_fma(2.0, w - kf, -1.0);
+      double tm = cl[u].x, tc = cl[u].x * x;
+      const double x2 = x + x;
+      M[0] += tc;
+#pragma unroll
+      for (int n = 1; n < N - 1; ++n) {
+        const double tn = __builtin_fma(x2, tc, -tm);
+        tm = tc; tc = tn;
+        M[n] += tn;
+      }
+    }
+  }
+  if (live) flush_to(Q);
+}
+
+hipError_t srt_moments_launch(const rjp_fields* fl, int K, int N, const int32_t* d_start,
+                              const int64_t* d_rowbase, const void* d_cells, double* d_mom,
+                              hipStream_t st) {
+  const int64_t npix = (int64_t)fl->nx * fl->nz;
+  const int64_t G = (npix + kLtLanes - 1) / kLtLanes;
+  const dim3 grid((unsigned)((G + 3) / 4));
+  const LtBins b = srt_bins(fl, K);
+  switch (N) {
+    case 16:
+      hipLaunchKernelGGL(srt_moments_kernel<16>, grid, dim3(256), 0, st, (const rjp_d2*)d_cells,
+                         d_start, d_rowbase, npix, b, d_mom);
+      break;
+    case 20:
+      hipLaunchKernelGGL(srt_moments_kernel<20>, grid, dim3(256), 0, st, (const rjp_d2*)d_cells,
+                         d_start, d_rowbase, npix, b, d_mom);
+      break;
+    case 24:
+      hipLaunchKernelGGL(srt_moments_kernel<24>, grid, dim3(256), 0, st, (const rjp_d2*)d_cells,
+                         d_start, d_rowbase, npix, b, d_mom);
+      break;
+    default:
+      return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
 // ---- the sweep ----------------------------------------------------------------------------------
 __device__ __forceinline__ rjp_d2 lt_load(const rjp_d2* p) { return __builtin_nontemporal_load(p); }
 

@@ -325,6 +325,228 @@ __global__ __launch_bounds__(kSrtBlock) void ff_scan_sorted_kernel(SrtDev s, Chi
   out[p] = total;
 }
 
+// ---- bins contracted from the layout's Chebyshev moments (rjp_fields.d_srt_mom) ----------------
+// On bin k of a jet, F(ts) = chi^2(t - ts) as a function of the bin's coordinate x = 2 (w - k) - 1
+// (the moments' x) is smooth wherever the bursts are wide against the bin.  When the Chebyshev
+// interpolant p(x) = sum_n W_n T_n(x) of degree N - 1 equals F there, the bin's sum is
+//   sum_cells |a0| F(ts) = sum_n W_n M_n,   M_n = sum_cells |a0| T_n(x)   (M_0: the d_srt_cum step)
+// -- (N - 1) 8 bytes per sightline instead of 16 per cell.  srt_coef_kernel builds W on the device
+// for every (jet, bin) in the support (N Chebyshev nodes of the exact F) and accepts the bin only if
+// p matches at 4 N points across it BOTH the exact F and the table's chi^2 (what the cell path and
+// the grid-order scan compute) to kSrtMomTol relative: a contracted bin then differs from the same
+// bin read cell by cell by <= kSrtMomTol relative, as the tests against the grid order require.
+constexpr double kSrtMomTol = 2e-14;
+constexpr int kSrtCoefThreads = 128;           // >= 4 N check points for N <= 24
+constexpr int kSrtMaxN = 24;
+
+struct SrtCoefDev {
+  double s0, inv_h;                            // the layout's bins (srt_bins in ff_lt.hip)
+  int K, N;
+  int b0[2], b1[2];                            // the bins in each jet's support (SrtPlan)
+  double* W;                                   // [2 K][N]
+  int* ok;                                     // [2 K]
+  unsigned long long* diag;                    // zeroed here for the scan behind, or null
+};
+
+__device__ __forceinline__ double chi_exact(const double* bj, int nb, double tl) {
+  double chi = 1.0;
+  for (int b = 0; b < nb; ++b) {
+    const double d = tl - bj[b];
+    chi += bj[nb + b] * exp(-d * d * bj[2 * nb + b]);
+  }
+  return chi;
+}
+
+// one workgroup per key q = jet * K + bin; `tab` / `t` / `stage` as chi_table_kernel's
+__global__ __launch_bounds__(kSrtCoefThreads) void srt_coef_kernel(const double* __restrict__ stage,
+                                                                   int nb0, int nb1, ChiTabDev t,
+                                                                   double t_epoch,
+                                                                   const double* __restrict__ tab,
+                                                                   SrtCoefDev c) {
+  __shared__ double sF[kSrtMaxN], sW[kSrtMaxN];
+  const int q = blockIdx.x, i = threadIdx.x;
+  const int j = q / c.K, k = q - j * c.K;
+  if (q == 0 && c.diag && i < 2) c.diag[i] = 0ull;
+  if (k < c.b0[j] || k >= c.b1[j]) {
+    if (i == 0) c.ok[q] = 0;
+    return;
+  }
+  const int N = c.N, nb = j == 0 ? nb0 : nb1;
+  const double* bj = stage + kChiNC * kChiNC + kChiNC + (j == 0 ? 0 : 3 * nb0);
+  const double h = 1.0 / c.inv_h;
+  auto ts_of = [&](double x) { return c.s0 + (k + 0.5 * (x + 1.0)) * h; };
+  if (i < N) {
+    const double chi = chi_exact(bj, nb, t_epoch - ts_of(cospi((i + 0.5) / N)));
+    sF[i] = chi * chi;
+  }
+  __syncthreads();
+  if (i < N) {
+    // W_n = (2 / N) sum_m F(x_m) T_n(x_m), T_n(x_m) = cos(pi n (2 m + 1) / (2 N)); W_0 halved
+    double s = 0.0;
+    for (int m = 0; m < N; ++m) s += sF[m] * cospi((double)((i * (2 * m + 1)) % (4 * N)) / (2 * N));
+    s *= (i == 0 ? 1.0 : 2.0) / N;
+    sW[i] = s;
+    c.W[(size_t)q * N + i] = s;
+  }
+  __syncthreads();
+  int ok = 1;
+  if (i < 4 * N) {
+    const double x = -1.0 + 2.0 * i / (4 * N - 1);
+    double u1 = 0.0, u2 = 0.0;                 // Clenshaw
+    for (int n = N - 1; n >= 1; --n) {
+      const double un = __builtin_fma(2.0 * x, u1, sW[n] - u2);
+      u2 = u1; u1 = un;
+    }
+    const double pv = __builtin_fma(x, u1, sW[0] - u2);
+    const double ts = ts_of(x);
+    const double chi = chi_exact(bj, nb, t_epoch - ts);
+    const double F = chi * chi;
+    // the table's chi at this launch time, as the scans evaluate it
+    double w = (t_epoch - ts - t.lo) * t.inv_h;
+    w = __builtin_fmin(__builtin_fmax(w, 0.0), t.wmax);
+    const double kf = __builtin_floor(w);
+    const double xi = __builtin_fma(2.0, w - kf, -1.0);
+    const double* cp = tab + ((int)kf + (j == 0 ? 0 : t.ni)) * kChiStride;
+    double ct = cp[7];
+    for (int n = 6; n >= 0; --n) ct = __builtin_fma(ct, xi, cp[n]);
+    const double T = ct * ct;
+    ok = __builtin_fabs(pv - F) <= kSrtMomTol * F && __builtin_fabs(pv - T) <= kSrtMomTol * T;
+  }
+  ok = __syncthreads_and(ok);
+  if (i == 0) c.ok[q] = ok;
+}
+
+// The sorted scan with contracted bins: per group and jet, a bin of the support is contracted
+// from the moments when srt_coef_kernel accepted it AND that reads fewer bytes for this group
+// than its cells (the longest lane run of the bin x 16 B > (N - 1) x 8 B); every maximal run of
+// the other bins is streamed as ff_scan_sorted_kernel streams its one run.  A jet no lane of the
+// group holds is skipped (its sums are 0).  Without contracted bins the sums are
+// ff_scan_sorted_kernel's, bit for bit.
+struct SrtMomDev {
+  const double* mom;                           // [2 K (N - 1)][P]
+  const double* W;                             // [2 K][N]
+  const int* ok;                               // [2 K]
+  unsigned long long* diag;                    // += (contracted, read) (group, jet, bin) triples
+};
+
+template <int U, int N>
+__global__ __launch_bounds__(kSrtBlock) void ff_scan_hybrid_kernel(SrtDev s, SrtMomDev m,
+                                                                   ChiTabDev t, double t_epoch,
+                                                                   const double* __restrict__ tab,
+                                                                   double* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) double s_chi[];       // [2][ni][10]
+  for (int i = threadIdx.x; i < 2 * t.ni * kChiStride; i += kSrtBlock) s_chi[i] = tab[i];
+  __syncthreads();
+  const int lane = threadIdx.x & (RJP_WAVE - 1);
+  const int64_t g = (int64_t)blockIdx.x * (kSrtBlock / RJP_WAVE) + threadIdx.x / RJP_WAVE;
+  const int64_t npix = s.npix;
+  if (g * RJP_WAVE >= npix) return;                    // (whole waves)
+  const int64_t p = g * RJP_WAVE + lane;
+  const bool live = p < npix;
+  const rjp_d2* base = s.cells + s.rowbase[g] * RJP_WAVE + lane;
+  const double wmax = t.wmax;
+  const int K = s.K;
+  auto start_at = [&](int q) { return live ? s.start[(int64_t)q * npix + p] : 0; };
+  auto cum_at = [&](int q) { return live ? s.cum[(int64_t)q * npix + p] : 0.0; };
+  auto wave_max = [](int v) {
+#pragma unroll
+    for (int d = RJP_WAVE / 2; d > 0; d >>= 1) v = max(v, __shfl_xor(v, d, RJP_WAVE));
+    return __builtin_amdgcn_readfirstlane(v);
+  };
+  unsigned n_con = 0, n_read = 0;
+  double total = 0.0;
+#pragma unroll 1
+  for (int j = 0; j < 2; ++j) {
+    const int q0 = j * K, b0 = s.b0[j], b1 = s.b1[j];
+    if (wave_max(start_at(q0 + K) - start_at(q0)) == 0) continue;       // no lane holds the jet
+    if (b0 >= b1) {
+      total += cum_at(q0 + K) - cum_at(q0);
+      continue;
+    }
+    const double skipped = (cum_at(q0 + K) - cum_at(q0 + b1)) + (cum_at(q0 + b0) - cum_at(q0));
+    // which bins of the support this group contracts
+    unsigned cmask = 0;
+    int sprev = start_at(q0 + b0);
+    for (int b = b0; b < b1; ++b) {
+      const int snext = start_at(q0 + b + 1);
+      if (m.ok[q0 + b] && wave_max(snext - sprev) * 16 > (N - 1) * 8) cmask |= 1u << b;
+      sprev = snext;
+    }
+    const int nc = __builtin_popcount(cmask);
+    n_con += nc;
+    n_read += (b1 - b0) - nc;
+    const int koff = j == 0 ? 0 : t.ni;                // red jet: the first half of the table
+    double acc = 0.0;
+    for (int b = b0; b < b1;) {
+      if ((cmask >> b) & 1u) {
+        if (live) {
+          const double* w = m.W + (size_t)(q0 + b) * N;
+          const double* mp = m.mom + (int64_t)(q0 + b) * (N - 1) * npix + p;
+          double v[N - 1];
+#pragma unroll
+          for (int n = 0; n < N - 1; ++n) v[n] = __builtin_nontemporal_load(mp + (int64_t)n * npix);
+          double sum = w[0] * (cum_at(q0 + b + 1) - cum_at(q0 + b));
+#pragma unroll
+          for (int n = 0; n < N - 1; ++n) sum = __builtin_fma(w[n + 1], v[n], sum);
+          acc += sum;
+        }
+        ++b;
+        continue;
+      }
+      int e = b + 1;
+      while (e < b1 && !((cmask >> e) & 1u)) ++e;
+      // bins [b, e) cell by cell: the wave's rows from the smallest start to the largest end of
+      // the lanes' non-empty runs, as ff_scan_sorted_kernel
+      const int rs = start_at(q0 + b), re = start_at(q0 + e);
+      int lo = rs < re ? rs : 0x7fffffff, hi = rs < re ? re : 0;
+#pragma unroll
+      for (int d = RJP_WAVE / 2; d > 0; d >>= 1) {
+        lo = min(lo, __shfl_xor(lo, d, RJP_WAVE));
+        hi = max(hi, __shfl_xor(hi, d, RJP_WAVE));
+      }
+      lo = __builtin_amdgcn_readfirstlane(lo);
+      hi = __builtin_amdgcn_readfirstlane(hi);
+      for (int r = lo; r < hi; r += U) {
+        rjp_d2 cl[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int rr = r + u < hi ? r + u : hi - 1;  // (never past the wave's last row)
+          cl[u] = __builtin_nontemporal_load(base + (int64_t)rr * RJP_WAVE);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          double w = (t_epoch - cl[u].y - t.lo) * t.inv_h;
+          w = __builtin_fmin(__builtin_fmax(w, 0.0), wmax);
+          const double kf = __builtin_floor(w);
+          const double xi = __builtin_fma(2.0, w - kf, -1.0);
+          const rjp_d2* cp = reinterpret_cast<const rjp_d2*>(s_chi + ((int)kf + koff) * kChiStride);
+          const rjp_d2 c01 = cp[0], c23 = cp[1], c45 = cp[2], c67 = cp[3];
+          double chi = __builtin_fma(c67.y, xi, c67.x);
+          chi = __builtin_fma(chi, xi, c45.y);
+          chi = __builtin_fma(chi, xi, c45.x);
+          chi = __builtin_fma(chi, xi, c23.y);
+          chi = __builtin_fma(chi, xi, c23.x);
+          chi = __builtin_fma(chi, xi, c01.y);
+          chi = __builtin_fma(chi, xi, c01.x);
+          const bool mine = r + u >= rs && r + u < re;
+          acc = __builtin_fma(mine ? cl[u].x : 0.0, chi * chi, acc);
+        }
+      }
+      b = e;
+    }
+    total += acc + skipped;
+  }
+  if (m.diag && lane == 0 && (n_con | n_read)) {
+    atomicAdd(&m.diag[0], (unsigned long long)n_con);
+    atomicAdd(&m.diag[1], (unsigned long long)n_read);
+  }
+  if (!live) return;
+  if (!s.hb[0]) total += s.aux[p];
+  if (!s.hb[1]) total += s.aux[npix + p];
+  if (s.aux[2 * npix + p] != 0.0) total = __builtin_inf();
+  out[p] = total;
+}
+
 // The same scan from the five MODEL fields (nd, xi, temp, pf, ts: SURVEY 8(d)'s byte model, what
 // a model without the derived scan fields a0 / em0 streams): optical-depth sums, emission measure
 // and T_avg of the epoch in one pass, the burst factor from the table.  Per-product NaN semantics
@@ -592,6 +814,7 @@ bool srt_plan(const rjp_fields* fl, const rjp_bursts* hb, double t_epoch, SrtPla
     }
   }
   sp.share = all > 0 ? (double)read / (double)all : 0.0;
+  sp.N = fl->d_srt_mom && srt_moment_order_ok(fl->srt_N) ? fl->srt_N : 0;
   return sp.share <= 0.9;
 }
 
@@ -661,6 +884,13 @@ hipError_t chi_table_scan(const rjp_fields* fl, const ChiPlan& cp, const double*
     e = hipFuncSetAttribute((const void*)ff_scan_sorted_kernel<RJP_SRT_U>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, kMaxShm);
     if (e != hipSuccess) return e;
+    const void* hyb[3] = {(const void*)ff_scan_hybrid_kernel<RJP_SRT_U, 16>,
+                          (const void*)ff_scan_hybrid_kernel<RJP_SRT_U, 20>,
+                          (const void*)ff_scan_hybrid_kernel<RJP_SRT_U, 24>};
+    for (const void* f : hyb) {
+      e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxShm);
+      if (e != hipSuccess) return e;
+    }
     cp.attr_set = true;
   }
   if (sp && !cp.wide && !em) {
@@ -670,8 +900,38 @@ hipError_t chi_table_scan(const rjp_fields* fl, const ChiPlan& cp, const double*
                    {sp->hb[0], sp->hb[1]}};
     const int64_t groups = (npix + RJP_WAVE - 1) / RJP_WAVE;
     const int64_t per = kSrtBlock / RJP_WAVE;
-    hipLaunchKernelGGL((ff_scan_sorted_kernel<RJP_SRT_U>), dim3((unsigned)((groups + per - 1) / per)),
-                       dim3(kSrtBlock), shm, st, s, t, t_epoch, (const double*)d_tab, sumA);
+    const dim3 sgrid((unsigned)((groups + per - 1) / per));
+    if (sp->N == 0) {
+      hipLaunchKernelGGL((ff_scan_sorted_kernel<RJP_SRT_U>), sgrid, dim3(kSrtBlock), shm, st, s, t,
+                         t_epoch, (const double*)d_tab, sumA);
+      return hipGetLastError();
+    }
+    // ... with the bins whose chi^2 the moments' interpolant matches contracted: the coefficients
+    // and verdicts of every (jet, bin) go to plane 0 of the workspace (unused by this scan)
+    const int K = fl->srt_K, N = sp->N;
+    double* d_W = ws;
+    int* d_ok = reinterpret_cast<int*>(ws + (size_t)2 * K * N);
+    const SrtCoefDev c{fl->ts_lo, fl->ts_hi > fl->ts_lo ? K / (fl->ts_hi - fl->ts_lo) : 1.0, K, N,
+                       {sp->b0[0], sp->b0[1]}, {sp->b1[0], sp->b1[1]}, d_W, d_ok, sp->diag};
+    hipLaunchKernelGGL(srt_coef_kernel, dim3((unsigned)(2 * K)), dim3(kSrtCoefThreads), 0, st,
+                       d_stage, cp.n[0], cp.n[1], t, t_epoch, (const double*)d_tab, c);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const SrtMomDev m{fl->d_srt_mom, d_W, d_ok, sp->diag};
+    switch (N) {
+      case 16:
+        hipLaunchKernelGGL((ff_scan_hybrid_kernel<RJP_SRT_U, 16>), sgrid, dim3(kSrtBlock), shm, st,
+                           s, m, t, t_epoch, (const double*)d_tab, sumA);
+        break;
+      case 20:
+        hipLaunchKernelGGL((ff_scan_hybrid_kernel<RJP_SRT_U, 20>), sgrid, dim3(kSrtBlock), shm, st,
+                           s, m, t, t_epoch, (const double*)d_tab, sumA);
+        break;
+      default:
+        hipLaunchKernelGGL((ff_scan_hybrid_kernel<RJP_SRT_U, 24>), sgrid, dim3(kSrtBlock), shm, st,
+                           s, m, t, t_epoch, (const double*)d_tab, sumA);
+        break;
+    }
     return hipGetLastError();
   }
   const dim3 grid((unsigned)(wgs * nsplit));

@@ -84,6 +84,10 @@ struct SrtPlan {
   int b0[2] = {0, 0}, b1[2] = {0, 0};
   int hb[2] = {0, 0};             // the jet has bursts
   double share = 0.0;             // the map's cells in those bins / all cells in the layout
+  // Chebyshev moments of the layout attached (rjp_fields.d_srt_mom): their order N, else 0.  The
+  // bins in the support whose chi^2 the degree-(N-1) interpolant matches are contracted from them
+  unsigned long long* diag = nullptr;   // (contracted, read) bin counters of the scan, or null
+  int N = 0;
 };
 // false: no layout attached, or too large a share of it would be read (the grid order is as fast)
 bool srt_plan(const rjp_fields* fl, const rjp_bursts* hb, double t_epoch, SrtPlan& sp);
@@ -163,6 +167,12 @@ hipError_t srt_count_launch(const rjp_fields* fl, int K, int32_t* d_start, int64
 hipError_t srt_fill_launch(const rjp_fields* fl, int K, const int32_t* d_start,
                            const int64_t* d_rowbase, void* d_cells, double* d_cum, double* d_aux,
                            hipStream_t st);
+// orders of the layout's Chebyshev moments (rjp_fields.srt_N) the kernels are instantiated for
+inline bool srt_moment_order_ok(int N) { return N == 16 || N == 20 || N == 24; }
+size_t srt_moment_entries(int nx, int nz, int K, int N);
+hipError_t srt_moments_launch(const rjp_fields* fl, int K, int N, const int32_t* d_start,
+                              const int64_t* d_rowbase, const void* d_cells, double* d_mom,
+                              hipStream_t st);
 hipError_t field_range_launch(const void* d_field, int64_t n, int dtype, double* d_part,
                               hipStream_t st);
 hipError_t range_check_launch(const void* d_field, int64_t n, int dtype, double lo, double hi,

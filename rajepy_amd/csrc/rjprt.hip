@@ -25,6 +25,7 @@ struct rjp_ctx {
   rjp::ChiPlan chi;               // the burst-factor table of the last single-epoch scan
   int last_path = 0;              // 0 = epoch tiles, 1 = LDS moments, 2 = launch-time-ordered layout
   int last_layout = 0;            // 0 = grid order, 1 = launch-time-bucketed layout (rjp_last_scan_layout)
+  bool last_srt_mom = false;      // the last scan contracted bins from the layout's moments
   static constexpr int kSlots = 8;
   struct Slot {
     double* h = nullptr;
@@ -45,6 +46,7 @@ struct rjp_ctx {
   int* guard = nullptr;
   unsigned long long* d_count = nullptr;      // device word of rjp_occupied_cells
   unsigned long long* d_srt_hist = nullptr;   // RJP_SRT_MAX_K * 2 counters of rjp_srt_count
+  unsigned long long* d_srt_diag = nullptr;   // (contracted, read) bins of rjp_last_srt_bins
   struct RangeKey {
     const void* d_ts = nullptr;
     int64_t n = 0;
@@ -279,6 +281,7 @@ int rjp_ctx_destroy(rjp_ctx* ctx) {
   if (ctx->guard) (void)hipHostFree(ctx->guard);
   if (ctx->d_count) (void)hipFree(ctx->d_count);
   if (ctx->d_srt_hist) (void)hipFree(ctx->d_srt_hist);
+  if (ctx->d_srt_diag) (void)hipFree(ctx->d_srt_diag);
   rjp::moments_release(ctx->mom);
   delete ctx;
   return RJP_OK;
@@ -426,6 +429,7 @@ static int ff_scan_impl(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts
     return fail(ctx, RJP_ERR_WORKSPACE, "rjp_ff_scan: workspace smaller than rjp_ff_scan_workspace()");
   hipStream_t st = (hipStream_t)stream;
   ctx->last_layout = 0;
+  ctx->last_srt_mom = false;
   // epoch sweeps by launch-time moments (ff_moments.hip) when the caller provided the launch-time
   // range and the host-side accuracy check of the expansion passes
   const int mr = rjp::moments_plan(fields, bursts, h_epochs_s, n_epochs, gff_mode, d_em != nullptr,
@@ -497,6 +501,13 @@ static int ff_scan_impl(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts
     rjp::SrtPlan sp;
     const bool srt = !ctx->chi.wide && !d_em && rjp::srt_plan(fields, bursts, h_epochs_s[0], sp);
     ctx->last_layout = srt ? 1 : 0;
+    if (srt && sp.N > 0) {
+      // (once per context: the bin counters of rjp_last_srt_bins, zeroed by every such scan)
+      if (!ctx->d_srt_diag)
+        RJP_HIP(ctx, hipMalloc((void**)&ctx->d_srt_diag, 2 * sizeof(unsigned long long)));
+      sp.diag = ctx->d_srt_diag;
+      ctx->last_srt_mom = true;
+    }
     const double* src[1] = {ctx->chi.stage.data()};
     const size_t len[1] = {ctx->chi.stage.size()};
     double* dev[1];
@@ -557,6 +568,19 @@ int rjp_last_scan_path(const rjp_ctx* ctx, double* worst_rel_err, int32_t* momen
 }
 
 int rjp_last_scan_layout(const rjp_ctx* ctx) { return ctx ? ctx->last_layout : RJP_ERR_ARG; }
+
+int rjp_last_srt_bins(rjp_ctx* ctx, int64_t* contracted, int64_t* read) {
+  if (int r = bind(ctx)) return r;
+  if (!contracted || !read) return fail(ctx, RJP_ERR_ARG, "rjp_last_srt_bins: NULL output");
+  *contracted = *read = 0;
+  if (!ctx->last_srt_mom) return RJP_OK;
+  unsigned long long h[2] = {0, 0};
+  RJP_HIP(ctx, hipDeviceSynchronize());
+  RJP_HIP(ctx, hipMemcpy(h, ctx->d_srt_diag, sizeof(h), hipMemcpyDeviceToHost));
+  *contracted = (int64_t)h[0];
+  *read = (int64_t)h[1];
+  return RJP_OK;
+}
 
 double rjp_last_table_build_ms(const rjp_ctx* ctx) { return ctx ? ctx->mom.build_ms : 0.0; }
 
@@ -669,6 +693,25 @@ int rjp_srt_fill(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, const int32_
     return fail(ctx, RJP_ERR_ARG, "rjp_srt_fill: NULL argument");
   RJP_HIP(ctx, rjp::srt_fill_launch(fields, K, d_start, d_rowbase, d_cells, d_cum, d_aux,
                                     (hipStream_t)stream));
+  return RJP_OK;
+}
+
+size_t rjp_srt_moment_entries(int32_t nx, int32_t nz, int32_t K, int32_t N) {
+  if (nx <= 0 || nz <= 0 || K < 1 || K > RJP_SRT_MAX_K || !rjp::srt_moment_order_ok(N)) return 0;
+  return rjp::srt_moment_entries(nx, nz, K, N);
+}
+
+int rjp_srt_moments(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, int32_t N,
+                    const int32_t* d_start, const int64_t* d_rowbase, const void* d_cells,
+                    double* d_mom, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = check_srt(ctx, fields, K)) return r;
+  if (!rjp::srt_moment_order_ok(N))
+    return fail(ctx, RJP_ERR_ARG, "rjp_srt_moments: N must be 16, 20 or 24");
+  if (!d_start || !d_rowbase || !d_cells || !d_mom)
+    return fail(ctx, RJP_ERR_ARG, "rjp_srt_moments: NULL argument");
+  RJP_HIP(ctx, rjp::srt_moments_launch(fields, K, N, d_start, d_rowbase, d_cells, d_mom,
+                                       (hipStream_t)stream));
   return RJP_OK;
 }
 

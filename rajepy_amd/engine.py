@@ -156,6 +156,12 @@ class RTEngine:
         # layout the producers attach (build_sorted); False: always the grid order (A/B runs)
         self.use_sorted = True
         self.srt_min_free = 0.2        # the layout is built only if this share of HBM stays free
+        # ... with its Chebyshev moments of order srt_N (16, 20 or 24), from which the bins where
+        # chi^2 is smooth are contracted instead of read; False: every bin of the support is read
+        # (A/B runs).  The moments count in the srt_min_free rule: the layout is attached without
+        # them when they do not fit.
+        self.use_srt_moments = True
+        self.srt_N = 20                # K1 at cfg4, 1 yr: 0.68 / 0.57 / 0.59 ms at N = 16 / 20 / 24
         # keep the launch-time moment maps of a model that is swept repeatedly (2.7 GB at
         # 512 x 512 sightlines): from the second long sweep on only the contraction runs
         self.cache_moments = True
@@ -385,7 +391,10 @@ class RTEngine:
         reads only the bins inside the bursts' support at its epoch.  Per-model state like a0:
         ~1.03 x the bytes of a0 + ts; built only when `srt_min_free` of the HBM stays free
         afterwards (returns None and attaches nothing otherwise).  Rebuild after `a0` or `ts`
-        change (a stale layout is never attached: the key holds the tensors' versions)."""
+        change (a stale layout is never attached: the key holds the tensors' versions).
+        With `use_srt_moments` the layout's Chebyshev moments of order `srt_N` are built with it
+        (rjp_srt_moments: 2 K (srt_N - 1) doubles per sightline, "mom" in the returned dict, None
+        when they would break the `srt_min_free` rule)."""
         torch = _torch()
         fields.srt = None
         if fields.a0 is None or fields.ts is None or fields.dtype != RJP_F64:
@@ -410,10 +419,14 @@ class RTEngine:
                                           self._stream()), self.ctx, "rjp_srt_count")
         ev[1].record()
         need = total.value * 64 * 16 + n_idx * 8 + 3 * fields.npix * 8
+        n_mom = (self.lib.rjp_srt_moment_entries(nx, nz, int(K), int(self.srt_N))
+                 if self.use_srt_moments else 0)
         free, hbm = torch.cuda.mem_get_info(self.device)
         free += torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
         if free - need < self.srt_min_free * hbm:
             return None
+        if free - need - n_mom * 8 < self.srt_min_free * hbm:
+            n_mom = 0                           # the layout fits, its moments do not
         cells = torch.empty(max(1, total.value) * 64 * 2, dtype=torch.float64, device=self.device)
         cum = torch.empty(n_idx, dtype=torch.float64, device=self.device)
         aux = torch.empty(3 * fields.npix, dtype=torch.float64, device=self.device)
@@ -423,12 +436,26 @@ class RTEngine:
                                          aux.data_ptr(), self._stream()),
                    self.ctx, "rjp_srt_fill")
         ev[3].record()
+        mom, mom_ms = None, 0.0
+        if n_mom:
+            mom = torch.empty(n_mom, dtype=torch.float64, device=self.device)
+            ev_m = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev_m[0].record()
+            _lib.check(self.lib.rjp_srt_moments(self.ctx, C.byref(fs), int(K), int(self.srt_N),
+                                                start.data_ptr(), rowbase.data_ptr(),
+                                                cells.data_ptr(), mom.data_ptr(), self._stream()),
+                       self.ctx, "rjp_srt_moments")
+            ev_m[1].record()
         torch.cuda.synchronize(self.device)
+        if mom is not None:
+            mom_ms = ev_m[0].elapsed_time(ev_m[1])
         fields.srt = {"cells": cells, "start": start, "cum": cum, "rowbase": rowbase, "aux": aux,
                       "hist": hist, "K": int(K), "rows": int(total.value),
                       "build_ms": ev[0].elapsed_time(ev[1]) + ev[2].elapsed_time(ev[3]),
                       "build_with_allocation_ms": ev[0].elapsed_time(ev[3]),
-                      "bytes": need, "key": self._srt_key(fields, fs)}
+                      "bytes": need, "key": self._srt_key(fields, fs),
+                      "mom": mom, "N": int(self.srt_N) if mom is not None else 0,
+                      "mom_build_ms": mom_ms, "mom_bytes": n_mom * 8}
         return fields.srt
 
     def _attach_sorted(self, fields):
@@ -628,6 +655,9 @@ class RTEngine:
             fs.d_srt_aux = srt["aux"].data_ptr()
             fs.h_srt_hist = C.cast(srt["hist"], C.c_void_p)
             fs.srt_K = srt["K"]
+            if self.use_srt_moments and srt.get("mom") is not None:
+                fs.d_srt_mom = srt["mom"].data_ptr()
+                fs.srt_N = srt["N"]
         if not self.use_moments and n_epochs != 1:
             fs.ts_lo = fs.ts_hi = 0.0
         elif self.force_moments:
@@ -784,6 +814,15 @@ class RTEngine:
         order) or 'sorted' (the launch-time-bucketed layout, only the bins inside the bursts'
         support).  `last_scan_path` says 'table' for both: chi comes from the table either way."""
         return {0: "grid", 1: "sorted"}[self.lib.rjp_last_scan_layout(self.ctx)]
+
+    def last_srt_bins(self):
+        """(contracted, read): the (jet, bin) decisions of the last scan on the bucketed layout
+        with moments, summed over its groups of 64 sightlines (rjp_last_srt_bins; synchronises
+        the device).  (0, 0) after a scan without moments."""
+        c, r = C.c_int64(), C.c_int64()
+        _lib.check(self.lib.rjp_last_srt_bins(self.ctx, C.byref(c), C.byref(r)), self.ctx,
+                   "rjp_last_srt_bins")
+        return int(c.value), int(r.value)
 
     def last_table_build_ms(self):
         """Host wall time of the last coefficient-table build (a new bursts / epochs request)."""
