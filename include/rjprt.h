@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define RJP_VERSION 111          /* 0.1.11 */
+#define RJP_VERSION 112          /* 0.1.12 */
 #define RJP_RANGE_BLOCKS 2048    /* partial (min, max) pairs rjp_field_range writes */
 #define RJP_MAX_EPOCH_TILE 32    /* most epochs evaluated per grid pass: 32 uniformly spaced ones (with or without d_em), 16 when only 16-31 are left, else tiles of 8, 4, 2, 1 */
 
@@ -451,6 +451,29 @@ int rjp_ff_cells(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* burst
 int rjp_rrl_cells(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
                   double time_s, const rjp_line* line, const double* h_nu, int32_t n_chan,
                   double* d_tau_cells, void* stream);
+
+/* ---- K5: free-free intensity by the formal solution along the line of sight ----------------
+ * The reference's intensity_ff / flux_ff (classes.py:1466-1541) are isothermal:
+ * S = c[f] T_avg (1 - e^-tau) with T_avg = nanmean_y(T > 0), exact only where T is constant along
+ * the sightline.  This entry point sums the emission of every cell attenuated by the cells in
+ * front of it:
+ *   d_out[f * P + p] = h_csrc[f] * sum_i T_i (1 - e^-dtau_i) exp(-sum_{j in front of i} dtau_j)
+ *   dtau_i = h_ctau[f] |a0_i| chi_i^2
+ * with a0 (= (n x)^2 pf T^-1.5 | T^-1.35 for gff_mode) and the burst factor chi(time_s - ts)
+ * exactly as the tau scans form them (rjp_ff_scan; the tau, compact and wide layouts are all
+ * accepted and give bit-identical f64 maps; d_temp is always read).  h_ctau as for rjp_ff_maps;
+ * h_csrc[f] is the Rayleigh-Jeans source factor per kelvin: h_cflux of rjp_ff_maps for Jy/pixel,
+ * 2 nu^2 k / c^2 for W m^-2 Hz^-1 sr^-1.
+ * OBSERVER SIDE: the iy = 0 end of axis 1 -- the reference's Doppler shift is nu0 (1 - v/c)
+ * (physics.py:557-558), so gas with vel[1] > 0 recedes and lies at larger iy.
+ * A cell contributes exactly when its term enters the nansum of the tau scans; d_out is NaN
+ * exactly where T_avg is (no cell of the sightline has T > 0).  With a constant T the sum
+ * telescopes to T (1 - e^-tau): the reference's maps are the isothermal special case.
+ * d_ylo / d_yhi are honoured; the launch-time range (ts_lo / ts_hi) is not used.  One epoch per
+ * call; every argument is validated before anything is enqueued (RJP_ERR_ARG otherwise). */
+int rjp_ff_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
+                  double time_s, int32_t gff_mode, const double* h_ctau, const double* h_csrc,
+                  int32_t n_chan, double* d_out, void* stream);
 
 /* Map stage of intensity_rrl / flux_rrl (classes.py:1280-1282, 1339-1343;
  * rrls.py:444-449; physics.py:571-574):

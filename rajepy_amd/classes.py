@@ -594,13 +594,14 @@ class JetModel:
     FITS_DEVICE_MIN_BYTES = 8 << 20      # products from this size on are laid out for FITS on the GPU
 
     def _ff_products(self, freq, tau=False, flux=False, intensity=False, device=False,
-                     keep=False):
+                     keep=False, formal=False):
         """`keep`: remember the device cube so that a following _save_cube can build the FITS
-        payload (axis order + byte order) on the GPU instead of in three host passes."""
+        payload (axis order + byte order) on the GPU instead of in three host passes.
+        `formal`: flux / intensity by the formal solution along the line of sight
+        (RTEngine.ff_formal) instead of the isothermal T_avg (1 - e^-tau)."""
         from . import engine as E
         scalar = np.isscalar(freq)
         freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
-        sumA, _, tavg = self._base_maps()
         gv = None
         if self.gff_mode == _lib.RJP_GFF_SCALAR:
             gv = [mphys.gff(nu, self.params['properties']['T_0']) for nu in freqs]
@@ -608,9 +609,16 @@ class JetModel:
                                           self.gff_mode, gv)
         if intensity:        # W m^-2 Hz^-1 sr^-1 (classes.py:1475, 1488)
             cflux = 2. * freqs ** 2. * con.k / con.c ** 2.
-        t, s, _ = self.engine.ff_maps(sumA, tavg, ctau, cflux, want_tau=tau,
-                                      want_flux=flux or intensity, want_ftot=False)
-        out = t if tau else s
+        if formal:
+            if tau:
+                raise ValueError("the formal solution gives intensities and fluxes, not tau")
+            out = self.engine.ff_formal(self.device_fields, self._rjp_bursts(), float(self.time),
+                                        self.gff_mode, ctau, cflux)
+        else:
+            sumA, _, tavg = self._base_maps()
+            t, s, _ = self.engine.ff_maps(sumA, tavg, ctau, cflux, want_tau=tau,
+                                          want_flux=flux or intensity, want_ftot=False)
+            out = t if tau else s
         if device:
             return out.reshape(len(freqs), self.nx, self.nz)
         arr = self._map(out, (len(freqs),))
@@ -683,16 +691,19 @@ class JetModel:
         self._save_cube(tff, savefits, 'tau', freq)
         return tff
 
-    def intensity_ff(self, freq, savefits=False):
-        """Radio intensity [W m^-2 Hz^-1 sr^-1] (classes.py:1449-1496)."""
-        ints = self._ff_products(freq, intensity=True, keep=bool(savefits))
-        self._save_cube(ints, savefits, 'intensity', freq)
+    def intensity_ff(self, freq, savefits=False, formal=False):
+        """Radio intensity [W m^-2 Hz^-1 sr^-1] (classes.py:1449-1496).  `formal=True`: by the
+        formal solution along the line of sight (every cell's emission attenuated by the cells in
+        front of it, observer at the iy = 0 end of axis 1) instead of the reference's isothermal
+        T_avg (1 - e^-tau); the two agree where T is constant along the sightline."""
+        ints = self._ff_products(freq, intensity=True, keep=bool(savefits), formal=formal)
+        self._save_cube(ints, savefits, 'intensity', freq, formal=formal)
         return ints
 
-    def flux_ff(self, freq, savefits=False):
-        """Flux density [Jy/pixel] (classes.py:1498-1541)."""
-        fluxes = self._ff_products(freq, flux=True, keep=bool(savefits))
-        self._save_cube(fluxes, savefits, 'flux', freq)
+    def flux_ff(self, freq, savefits=False, formal=False):
+        """Flux density [Jy/pixel] (classes.py:1498-1541).  `formal`: see `intensity_ff`."""
+        fluxes = self._ff_products(freq, flux=True, keep=bool(savefits), formal=formal)
+        self._save_cube(fluxes, savefits, 'flux', freq, formal=formal)
         return fluxes
 
     def _rrl_tau_device(self, rrl, freqs):
@@ -758,7 +769,9 @@ class JetModel:
         return fluxes
 
     # ------------------------------------------------------------------ products ----
-    def _save_cube(self, data, savefits, image_type, freq):
+    FORMAL_HISTORY = "Formal solution along the line of sight, observer at iy = 0"
+
+    def _save_cube(self, data, savefits, image_type, freq, formal=False):
         dev, self._dev_product = getattr(self, "_dev_product", None), None
         if not savefits:
             return
@@ -775,10 +788,12 @@ class JetModel:
             arr = np.transpose(data, (0, 2, 1))
         else:
             arr = np.transpose(data, (1, 0))
-        self.save_fits(arr, savefits, image_type, freq)
+        self.save_fits(arr, savefits, image_type, freq,
+                       history=self.FORMAL_HISTORY if formal else None)
 
-    def save_fits(self, data, filename, image_type, freq=None):
-        """Write a map/cube with the reference's header (classes.py:1543-1652)."""
+    def save_fits(self, data, filename, image_type, freq=None, history=None):
+        """Write a map/cube with the reference's header (classes.py:1543-1652); `history`: one
+        more HISTORY line (the formal-solution products say so)."""
         if image_type not in ('flux', 'tau', 'em', 'intensity'):
             raise ValueError("arg image_type must be one of 'flux', 'tau' or 'em'")
         ndims = len(data.shape if isinstance(data, _fits.BigEndian) else np.shape(data))
@@ -819,6 +834,8 @@ class JetModel:
                         'em': 'pc cm^-6', 'tau': 'dimensionless'}[image_type])
         lines = self.__str__().split('\n')
         h.add_history((' ' * (72 - len(lines[0]))).join(lines))
+        if history is not None:
+            h.add_history(history)
         _fits.writeto(filename, data, h)
 
     def save(self, filename):
@@ -1085,9 +1102,16 @@ class Pipeline:
             pickle.dump({"runs": runs, "params": params, "model_file": mf,
                          'log': self.log}, f)
 
-    def execute(self, simobserve=True, verbose=True, dryrun=False, resume=True, clobber=False):
+    def execute(self, simobserve=True, verbose=True, dryrun=False, resume=True, clobber=False,
+                formal=False):
         """Radiative transfer for every run; writes EM/Tau/Flux FITS products, records
-        `results['flux']`, pickles model and pipeline state (classes.py:2296-2479)."""
+        `results['flux']`, pickles model and pipeline state (classes.py:2296-2479).
+        `formal=True`: the flux cubes (and `results['flux']` from them) by the formal solution
+        along the line of sight (`JetModel.flux_ff(formal=True)`); continuum runs only -- a run
+        table with an RRL run is refused before any run starts."""
+        if formal and any(r.obs_type != 'continuum' for r in self.runs):
+            raise ValueError("formal=True: the formal solution covers continuum runs only; the "
+                             "run table holds radio-recombination-line runs")
         self.log.add_entry("INFO", "Beginning pipeline execution")
         if verbose != self.log.verbose:
             self.log.verbose = verbose
@@ -1106,6 +1130,7 @@ class Pipeline:
         owner = {y: i % world for i, y in enumerate(years)}
         mine = [i for i, r in enumerate(self.runs) if owner[float(r.year)] == rank]
         self._multi_rank = world > 1
+        self._formal = bool(formal)
 
         pending = []
         if not dryrun:
@@ -1219,7 +1244,8 @@ class Pipeline:
                 fluxes = m.flux_rrl(run.line, run.chan_freqs, contsub=False,
                                     savefits=run.fits_flux)
             else:
-                fluxes = m.flux_ff(run.chan_freqs, savefits=run.fits_flux)
+                fluxes = m.flux_ff(run.chan_freqs, savefits=run.fits_flux,
+                                   formal=getattr(self, "_formal", False))
         else:
             self.log.add_entry("INFO", f"Fluxes already exist -> {run.fits_flux}",
                                timestamp=False)

@@ -1,0 +1,233 @@
+// K5: free-free intensity by the formal solution of the transfer equation along the line of sight.
+//
+// The reference's map stage is isothermal: S = c_S[f] T_avg (1 - e^-tau) with T_avg the nanmean of
+// the sightline's T > 0 (classes.py:1466-1475; K2 here), exact only where T is constant along the
+// sightline.  This kernel sums the emission of every cell attenuated by the cells in front of it:
+//   out[f, p] = csrc[f] sum_i T_i (1 - e^-dtau_i) exp(-sum_{j in front of i} dtau_j),
+//   dtau_i = ctau[f] b_i,  b_i = |a0_i| chi_i^2
+// with a0 and chi exactly as the tau scans form them (tau, compact and wide layouts give the same
+// b bit for bit in f64) and the observer at the iy = 0 end of axis 1: the reference's Doppler shift
+// is nu0 (1 - v/c) (physics.py:557-558), so gas with vel[1] > 0 recedes, i.e. lies behind.  With a
+// constant T the sum telescopes to T (1 - e^-tau): the isothermal maps are a special case.  A cell
+// contributes exactly when its term enters the tau scans' nansum (b == 0 / NaN: skipped); the
+// output is NaN exactly where T_avg is (no cell of the sightline has T > 0).
+//
+// Layout of K3 (rrl_scan.hip): a 256-thread workgroup owns ZT z-adjacent sightlines of one x-row
+// and a block of LF channels (lanes over channels, G = 256 / LF sightline groups):
+//   phase 1  one thread per cell of a slab of YC y-rows: b and T to LDS;
+//   phase 2  every lane walks the slab's rows in increasing iy for its NZP sightlines:
+//            om = 1 - e^(-ctau b), I += T om Theta, Theta -= Theta om (two FMAs), with b and T
+//            LDS broadcasts.  A row whose cells are all dead is skipped (wave-uniform for LF >= 64).
+// Compute-bound (vector FP64): ~26 instructions per (cell, channel) update, 21 of them in
+// one_minus_exp_neg (relative error < 4e-15 for every tau); HBM traffic is 3 fields per cell
+// (a0, temp, ts on the tau layout) once per channel block.
+#include "rjp_host.h"
+
+namespace rjp {
+
+constexpr int kFB = 256;     // threads per workgroup
+
+template <int LF> struct FormalTile {
+  static constexpr int ZT = LF == 256 ? 8 : 16;   // sightlines per workgroup
+  static constexpr int YC = kFB / ZT;             // y-rows per slab
+  static constexpr int G = kFB / LF;              // sightline groups
+  static constexpr int NZP = ZT / G;              // sightlines per thread
+};
+
+template <typename T>
+struct FormalFields {
+  const T* nd;
+  const T* xi;
+  const T* temp;
+  const T* pf;
+  const T* ts;
+  const T* em0;
+  const double* a0;
+  const int32_t* ylo;      // optional occupied y-range per sightline
+  const int32_t* yhi;
+};
+
+// b = |a0| chi^2 of one cell, 0 when it contributes nothing.  |a0| as the scans of the layout form
+// it (ff_scan_kernels.h load_rows / compute_rows): the stored tau field, |em0| T^-1.5|-1.35, or
+// (|nd| xi)^2 pf T^-1.5|-1.35; chi exactly from the bursts (K3's cell_line) -- a NaN launch time
+// gives NaN where the cell's jet has bursts (the term is dropped, as nansum drops it) and chi = 1
+// where it has none (classes.py:232-233).
+template <typename T, int LAY, bool BURSTS>
+__device__ __forceinline__ double formal_b(const FormalFields<T>& f, int64_t o, int mode,
+                                           const BurstsDev& bd, double time_s, double Tk) {
+  double a;
+  bool red;
+  if constexpr (LAY == LAY_TAU) {
+    const double v = f.a0[o];
+    red = signbit_d(v);
+    a = fabs(v);
+  } else if constexpr (LAY == LAY_CMP) {
+    const double g = (double)f.em0[o];
+    red = signbit_d(g);
+    a = fabs(g) * tau_weight(Tk, mode);
+  } else {
+    const double nd = (double)f.nd[o];
+    const double n0 = fabs(nd) * (double)f.xi[o];
+    red = signbit_d(nd);
+    a = n0 * n0 * (double)f.pf[o] * tau_weight(Tk, mode);
+  }
+  double b = a;
+  if (BURSTS) {
+    const double c = chi_cell(bd, red, time_s - (double)f.ts[o]);
+    b = a * (c * c);
+  }
+  return b == b ? b : 0.0;
+}
+
+#ifndef RJP_FORMAL_WAVES
+#define RJP_FORMAL_WAVES 4      /* 128-VGPR budget */
+#endif
+template <typename T, int LAY, int LF, bool BURSTS>
+__global__ __launch_bounds__(kFB, RJP_FORMAL_WAVES) void ff_formal_kernel(
+    FormalFields<T> f, int nx, int ny, int nz, int mode, BurstsDev bd, double time_s,
+    const double* __restrict__ ctau, const double* __restrict__ csrc, int nchan,
+    double* __restrict__ out) {
+  using TL = FormalTile<LF>;
+  constexpr int ZT = TL::ZT, YC = TL::YC, NZP = TL::NZP;
+  static_assert(ZT % TL::G == 0, "tile/group mismatch");
+
+  __shared__ rjp_d2 s_bt[kFB];      // (b, T) of the slab's cells, [row * ZT + sightline]
+  __shared__ int s_hot[ZT];         // the sightline has a cell with T > 0 (T_avg is not NaN)
+
+  const int ntz = (nz + ZT - 1) / ZT;
+  const int x = (int)blockIdx.x / ntz;
+  const int z0 = ((int)blockIdx.x - x * ntz) * ZT;
+  const int tid = threadIdx.x;
+  const int fl = tid % LF;
+  const int g = tid / LF;
+  const int fi = (int)blockIdx.y * LF + fl;
+  const bool chan_live = fi < nchan;
+  const double ct = chan_live ? ctau[fi] : 0.0;     // dead lanes: dtau = 0, om = 0 exactly
+  const int cy = tid / ZT, cz = tid % ZT;           // this thread's cell in the slab (phase 1)
+  const int cb = g * NZP;                           // first sightline of this thread (phase 2)
+
+  if (tid < ZT) s_hot[tid] = 0;
+  __syncthreads();
+  int ya = 0, ye = ny;
+  if (f.ylo) {
+    // sparse models: only the rows inside the tile's occupied y-range
+    __shared__ int s_lo, s_hi;
+    if (tid == 0) { s_lo = ny; s_hi = 0; }
+    __syncthreads();
+    if (tid < ZT && z0 + tid < nz) {
+      const int64_t p = (int64_t)x * nz + z0 + tid;
+      const int lo = f.ylo[p], hi = f.yhi[p];
+      if (lo < hi) { atomicMin(&s_lo, lo); atomicMax(&s_hi, hi); }
+    }
+    __syncthreads();
+    ya = s_lo;
+    ye = s_hi;
+  }
+
+  double I[NZP], Th[NZP];
+#pragma unroll
+  for (int j = 0; j < NZP; ++j) { I[j] = 0.0; Th[j] = 1.0; }
+
+  for (int yb = ya; yb < ye; yb += YC) {
+    // ---- phase 1: b and T of one cell per thread ------------------------------------------
+    {
+      const int yy = yb + cy, zz = z0 + cz;
+      double bb = 0.0, tk = 0.0;
+      if (yy < ye && zz < nz) {
+        const int64_t o = ((int64_t)x * ny + yy) * nz + zz;
+        const double Tk = (double)f.temp[o];
+        if (Tk > 0.0) s_hot[cz] = 1;                  // (every writer stores the same value)
+        bb = formal_b<T, LAY, BURSTS>(f, o, mode, bd, time_s, Tk);
+        tk = bb != 0.0 ? Tk : 0.0;                    // a dead cell adds T * 0 = 0, not NaN
+      }
+      rjp_d2 v;
+      v.x = bb;
+      v.y = tk;
+      s_bt[tid] = v;
+    }
+    __syncthreads();
+
+    // ---- phase 2: lanes over channels, rows front to back -----------------------------------
+#pragma unroll 2
+    for (int r = 0; r < YC; ++r) {
+      rjp_d2 c[NZP];
+      bool any = false;
+#pragma unroll
+      for (int j = 0; j < NZP; ++j) {
+        c[j] = s_bt[r * ZT + cb + j];
+        any |= c[j].x != 0.0;
+      }
+      if (!any) continue;
+#pragma unroll
+      for (int j = 0; j < NZP; ++j) {
+        const double om = one_minus_exp_neg(ct * c[j].x);
+        I[j] = __builtin_fma(c[j].y * om, Th[j], I[j]);
+        Th[j] = __builtin_fma(-Th[j], om, Th[j]);
+      }
+    }
+    __syncthreads();
+  }
+
+  if (chan_live) {
+    const double cs = csrc[fi];
+    const int64_t base = (int64_t)fi * nx * nz + (int64_t)x * nz + z0 + cb;
+#pragma unroll
+    for (int j = 0; j < NZP; ++j)
+      if (z0 + cb + j < nz) out[base + j] = s_hot[cb + j] ? cs * I[j] : __builtin_nan("");
+  }
+}
+
+template <typename T, int LAY, int LF>
+static hipError_t formal_launch_t(const FormalFields<T>& f, const rjp_fields* fl, int mode,
+                                  const BurstsDev& b, bool bursts, double time_s,
+                                  const double* ctau, const double* csrc, int nchan, double* out,
+                                  hipStream_t st) {
+  const int ntz = (fl->nz + FormalTile<LF>::ZT - 1) / FormalTile<LF>::ZT;
+  const dim3 grid((unsigned)((int64_t)fl->nx * ntz), (unsigned)((nchan + LF - 1) / LF));
+  if (bursts)
+    hipLaunchKernelGGL((ff_formal_kernel<T, LAY, LF, true>), grid, dim3(kFB), 0, st, f, fl->nx,
+                       fl->ny, fl->nz, mode, b, time_s, ctau, csrc, nchan, out);
+  else
+    hipLaunchKernelGGL((ff_formal_kernel<T, LAY, LF, false>), grid, dim3(kFB), 0, st, f, fl->nx,
+                       fl->ny, fl->nz, mode, b, time_s, ctau, csrc, nchan, out);
+  return hipGetLastError();
+}
+
+// channel lanes: the narrowest layout that holds every channel up to 32 channels; blocks of 64
+// lanes up to 128 channels, of 256 beyond
+template <typename T, int LAY>
+static hipError_t formal_launch_lf(const FormalFields<T>& f, const rjp_fields* fl, int mode,
+                                   const BurstsDev& b, bool bursts, double time_s,
+                                   const double* ctau, const double* csrc, int nchan, double* out,
+                                   hipStream_t st) {
+  if (nchan > 128) return formal_launch_t<T, LAY, 256>(f, fl, mode, b, bursts, time_s, ctau, csrc, nchan, out, st);
+  if (nchan > 32) return formal_launch_t<T, LAY, 64>(f, fl, mode, b, bursts, time_s, ctau, csrc, nchan, out, st);
+  if (nchan > 16) return formal_launch_t<T, LAY, 32>(f, fl, mode, b, bursts, time_s, ctau, csrc, nchan, out, st);
+  return formal_launch_t<T, LAY, 16>(f, fl, mode, b, bursts, time_s, ctau, csrc, nchan, out, st);
+}
+
+hipError_t ff_formal_launch(const rjp_fields* fl, const rjp_bursts* hb, const double* d_ext,
+                            double time_s, int mode, const double* d_ctau, const double* d_csrc,
+                            int nchan, double* out, hipStream_t st) {
+  BurstsDev b;
+  const bool bursts = bursts_to_dev(hb, b, d_ext);
+  if (bursts && !fl->d_ts) return hipErrorInvalidValue;
+  const bool tau = fl->d_a0 && fl->dtype == RJP_F64 && fl->a0_mode == mode;
+  if (fl->dtype == RJP_F64) {
+    using T = double;
+    FormalFields<T> f{(const T*)fl->d_nd, (const T*)fl->d_xi, (const T*)fl->d_temp,
+                      (const T*)fl->d_pf, (const T*)fl->d_ts, (const T*)fl->d_em0,
+                      (const double*)fl->d_a0, fl->d_ylo, fl->d_yhi};
+    if (tau) return formal_launch_lf<T, LAY_TAU>(f, fl, mode, b, bursts, time_s, d_ctau, d_csrc, nchan, out, st);
+    if (fl->d_em0) return formal_launch_lf<T, LAY_CMP>(f, fl, mode, b, bursts, time_s, d_ctau, d_csrc, nchan, out, st);
+    return formal_launch_lf<T, LAY_WIDE>(f, fl, mode, b, bursts, time_s, d_ctau, d_csrc, nchan, out, st);
+  }
+  using T = float;
+  FormalFields<T> f{(const T*)fl->d_nd, (const T*)fl->d_xi, (const T*)fl->d_temp,
+                    (const T*)fl->d_pf, (const T*)fl->d_ts, (const T*)fl->d_em0, nullptr,
+                    fl->d_ylo, fl->d_yhi};
+  if (fl->d_em0) return formal_launch_lf<T, LAY_CMP>(f, fl, mode, b, bursts, time_s, d_ctau, d_csrc, nchan, out, st);
+  return formal_launch_lf<T, LAY_WIDE>(f, fl, mode, b, bursts, time_s, d_ctau, d_csrc, nchan, out, st);
+}
+
+}  // namespace rjp

@@ -53,6 +53,10 @@ hipError_t occupied_launch(const int32_t* ylo, const int32_t* yhi, int64_t npix,
 hipError_t ff_cells_launch(const rjp_fields* fl, const rjp_bursts* hb, const double* d_ext,
                            double time_s, int mode, const double* d_ctau, int nchan, double* out,
                            hipStream_t st);
+// ff_formal.hip: the formal solution along the line of sight (K5), out[F * P]
+hipError_t ff_formal_launch(const rjp_fields* fl, const rjp_bursts* hb, const double* d_ext,
+                            double time_s, int mode, const double* d_ctau, const double* d_csrc,
+                            int nchan, double* out, hipStream_t st);
 size_t ff_maps_workspace_bytes(int64_t npix, int n_epochs, int n_chan);
 hipError_t ff_maps_launch(const double* sumA, const double* tavg, int64_t npix, int n_epochs,
                           const double* d_ctau, const double* d_cflux, int n_chan, double* tau,

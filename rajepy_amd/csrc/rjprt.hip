@@ -832,6 +832,29 @@ int rjp_ff_cells(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* burst
                                     gff_mode, dev[0], n_chan, d_tau_cells, st), "ff_cells_launch");
 }
 
+int rjp_ff_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
+                  double time_s, int32_t gff_mode, const double* h_ctau, const double* h_csrc,
+                  int32_t n_chan, double* d_out, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (gff_mode != RJP_GFF_SCALAR && gff_mode != RJP_GFF_POWERLAW)
+    return fail(ctx, RJP_ERR_ARG, "bad gff_mode");
+  if (int r = check_fields(ctx, fields, false, true, gff_mode)) return r;
+  if (!fields->d_temp)
+    return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal: fields.d_temp must be a device pointer");
+  if (int r = check_bursts(ctx, bursts, fields)) return r;
+  if (!h_ctau || !h_csrc || n_chan < 1 || !d_out)
+    return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal: NULL table / output or n_chan < 1");
+  hipStream_t st = (hipStream_t)stream;
+  const std::vector<double> ext = burst_ext_table(bursts);
+  const double* src[3] = {h_ctau, h_csrc, ext.data()};
+  const size_t len[3] = {(size_t)n_chan, (size_t)n_chan, ext.size()};
+  double* dev[3];
+  if (int r = stage_tables(ctx, st, src, len, 3, dev)) return r;
+  return finish_staged(ctx, st, rjp::ff_formal_launch(fields, bursts, ext.empty() ? nullptr : dev[2],
+                                                      time_s, gff_mode, dev[0], dev[1], n_chan,
+                                                      d_out, st), "ff_formal_launch");
+}
+
 int rjp_rrl_cells(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
                   double time_s, const rjp_line* line, const double* h_nu, int32_t n_chan,
                   double* d_tau_cells, void* stream) {

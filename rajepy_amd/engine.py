@@ -880,6 +880,22 @@ class RTEngine:
             self._stream()), self.ctx, "rjp_ff_cells")
         return out
 
+    def ff_formal(self, fields, bursts, time_s, gff_mode, ctau, csrc, out=None):
+        """Free-free intensity by the formal solution along the line of sight (rjp_ff_formal):
+        csrc[f] * sum_i T_i (1 - e^-dtau_i) exp(-sum_{j in front} dtau_j), observer at the iy = 0
+        end of axis 1 -> device tensor [F, P] (float64), NaN where the sightline has no T > 0.
+        `ctau` as for `ff_maps`; `csrc` = its `cflux` for Jy/pixel, or 2 nu^2 k / c^2 for
+        W m^-2 Hz^-1 sr^-1.  One epoch (`time_s` [s]) per call; any layout of `fields`."""
+        F = len(ctau)
+        if out is None:
+            out = self._f64(F, fields.npix)
+        fs = fields.struct()
+        _lib.check(self.lib.rjp_ff_formal(
+            self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None,
+            float(time_s), int(gff_mode), _lib.dbl_array(ctau), _lib.dbl_array(csrc), F,
+            out.data_ptr(), self._stream()), self.ctx, "rjp_ff_formal")
+        return out
+
     def rrl_cells(self, fields, bursts, time_s, line, nus):
         """collapse=False: per-cell RRL optical depths -> device tensor [F, N]."""
         F = len(nus)
