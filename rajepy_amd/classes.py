@@ -211,7 +211,7 @@ class JetModel:
         self._engine = engine
         self._dev = None
         self._version = 0            # bumped whenever a field or the burst list changes
-        self._scan_cache = collections.OrderedDict()   # time -> (sumA[1,P], em[1,P]) tensors
+        self._scan_cache = collections.OrderedDict()   # time -> (sumA[1,P], em[1,P] | None) tensors
         self._tavg = None
         self._vxz = None
         self._rrl_cache = None
@@ -558,11 +558,14 @@ class JetModel:
             self._tavg = self.engine.tavg(self.device_fields)
         return self._tavg
 
-    def prefetch_epochs(self, times_s):
+    def prefetch_epochs(self, times_s, want_em=True):
         """Scan the grid for several model times at once (8-32 epochs share one pass over
-        HBM); later RT calls at those times reuse the base maps."""
+        HBM); later RT calls at those times reuse the base maps.  `want_em=False`: the
+        optical-depth sums only, no emission-measure maps -- the only single-epoch scans that
+        may read the launch-time-bucketed layout (include/rjprt.h `rjp_fields.d_srt_cells`);
+        `emission_measure` scans again for an epoch cached that way."""
         todo = [t for t in dict.fromkeys(float(t) for t in times_s)
-                if t not in self._scan_cache]
+                if t not in self._scan_cache or (want_em and self._scan_cache[t][1] is None)]
         if not todo:
             return
         # the cache is bounded (a long sweep must not pin an [E, P] pair per epoch for ever):
@@ -572,20 +575,25 @@ class JetModel:
         dev = self.device_fields
         self._model_tavg()
         sumA, em, _ = self.engine.ff_scan(dev, self._rjp_bursts(), todo, self.gff_mode,
-                                          want_tavg=False)
+                                          want_em=want_em, want_tavg=False)
         for i, t in enumerate(todo):
             # own copies: a slice would keep the whole [E, P] result alive
-            self._scan_cache[t] = (sumA[i:i + 1].clone(), em[i:i + 1].clone())
+            self._scan_cache[t] = (sumA[i:i + 1].clone(),
+                                   em[i:i + 1].clone() if em is not None else None)
         while len(self._scan_cache) > self.SCAN_CACHE_EPOCHS:
             old = next(iter(self._scan_cache))
             if old in todo:
                 break
             del self._scan_cache[old]
 
-    def _base_maps(self):
+    def _base_maps(self, want_em=False):
+        """(sumA, em | None, T_avg) of the model's time.  The emission-measure map is scanned only
+        for the caller that reads it: without it a single-epoch scan streams two fields per cell
+        instead of three and may take the launch-time-bucketed layout K4 attached."""
         t = float(self.time)
-        if t not in self._scan_cache:
-            self.prefetch_epochs([t])
+        hit = self._scan_cache.get(t)
+        if hit is None or (want_em and hit[1] is None):
+            self.prefetch_epochs([t], want_em=want_em)
         return self._scan_cache[t] + (self._model_tavg(),)
 
     def _map(self, tensor, lead=()):
@@ -677,7 +685,7 @@ class JetModel:
     # ------------------------------------------------------------------ RT methods ----
     def emission_measure(self, savefits=False):
         """Emission measure along y [pc cm^-6] (classes.py:1101-1128)."""
-        _, em, _ = self._base_maps()
+        _, em, _ = self._base_maps(want_em=True)
         ems = self._map(em)
         if savefits:
             self.save_fits(np.transpose(ems, (1, 0)), savefits, 'em')
