@@ -194,8 +194,12 @@ typedef struct rjp_fields {
    * Per call, a small kernel interpolates chi^2 on every bin of the support at srt_N Chebyshev
    * nodes and accepts the bin when the interpolant matches, at 4 srt_N points across it, both the
    * exact chi^2 and the table's to 2e-14 relative; the scan then contracts an accepted bin from
-   * its moments ((srt_N - 1) x 8 bytes per sightline) instead of reading its cells (16 bytes
-   * each) wherever that reads fewer bytes for the group.  rjp_last_srt_bins() counts both kinds.
+   * its moments instead of reading its cells (16 bytes each) wherever (srt_N - 1) x 8 bytes per
+   * sightline are fewer bytes for the group; of those planes it reads the first m - 1 only, m the
+   * number of coefficients that matter on the bin (the dropped tail is below 5e-15 of its
+   * smallest chi^2 and the truncated interpolant passes the same checks).  The planes are read as
+   * 16-byte pairs of sightlines: d_srt_mom must be 16-byte aligned and P even, else the scan
+   * fails.  rjp_last_srt_bins() counts both kinds.
    * The moments belong to the layout: rebuild them with it. */
   const void* d_srt_cells;
   const int32_t* d_srt_start;

@@ -336,6 +336,29 @@ __global__ __launch_bounds__(kSrtBlock) void ff_scan_sorted_kernel(SrtDev s, Chi
 // the grid-order scan compute) to kSrtMomTol relative: a contracted bin then differs from the same
 // bin read cell by cell by <= kSrtMomTol relative, as the tests against the grid order require.
 constexpr double kSrtMomTol = 2e-14;
+// How many of a contracted bin's N coefficients the scan sums.  The W_n of a smooth bin fall to the
+// rounding of their own sums long before n = N - 1 (the far tail of a wide burst: 6-12 orders), and
+// every order not summed is a moment plane not read.  srt_coef_kernel keeps the first m, m the
+// smallest count whose dropped tail  sum_{n >= m} |W_n|  is <= kSrtTailFrac kSrtMomTol F_min (F_min:
+// the smallest exact F at the check points).  The moments' weights |a0| are >= 0 and |T_n| <= 1 on
+// the bin, so |M_n| <= M_0 and the dropped terms are <= tail M_0 <= kSrtTailFrac kSrtMomTol x the
+// bin's sum (every F >= F_min): a bound in moment space that holds between the check points too.
+// The fraction is set from below by the coefficients' own rounding: W_n is (2 / N) x a sum of N
+// terms <= F_max, each rounded twice (cospi, the product), so a coefficient that is "zero" carries
+// up to ~2 x 2^-53 F_max and N - 1 of them up to 4.2e-15 F_max at N = 20 -- a tail bound below
+// that is never met on a flat bin (F_max ~ F_min).  1 / 4 (5e-15) is the smallest simple fraction
+// above it, and leaves the sum of both errors (2e-14 at the check points, 0.5e-14 from the
+// truncation between them) inside the 1e-13 the hybrid scan is held to against the other orders.
+// The truncated interpolant is then put through checks (a) and (b) again, the same 4 N points and
+// tolerance; where it fails, m = N: what the scan sums is exactly what was checked, and a bin
+// accepted with N coefficients stays accepted whatever happens here.
+constexpr double kSrtTailFrac = 0.25;
+#ifndef RJP_SRT_TRUNC
+#define RJP_SRT_TRUNC 1          /* 0: a build that sums all N coefficients of every contracted bin, for A/B only */
+#endif
+#ifndef RJP_SRT_PAIR
+#define RJP_SRT_PAIR 1           /* 0: a build that loads the moment planes 8 bytes per lane, for A/B only */
+#endif
 constexpr int kSrtCoefThreads = 128;           // >= 4 N check points for N <= 24
 constexpr int kSrtMaxN = 24;
 
@@ -344,7 +367,7 @@ struct SrtCoefDev {
   int K, N;
   int b0[2], b1[2];                            // the bins in each jet's support (SrtPlan)
   double* W;                                   // [2 K][N]
-  int* ok;                                     // [2 K]
+  int* ok;                                     // [2 K]: 0 = read the bin, else the coefficients to sum
   unsigned long long* diag;                    // zeroed here for the scan behind, or null
 };
 
@@ -363,7 +386,7 @@ __global__ __launch_bounds__(kSrtCoefThreads) void srt_coef_kernel(const double*
                                                                    double t_epoch,
                                                                    const double* __restrict__ tab,
                                                                    SrtCoefDev c) {
-  __shared__ double sF[kSrtMaxN], sW[kSrtMaxN];
+  __shared__ double sF[kSrtMaxN], sW[kSrtMaxN], sFc[4 * kSrtMaxN];
   const int q = blockIdx.x, i = threadIdx.x;
   const int j = q / c.K, k = q - j * c.K;
   if (q == 0 && c.diag && i < 2) c.diag[i] = 0ull;
@@ -389,18 +412,13 @@ __global__ __launch_bounds__(kSrtCoefThreads) void srt_coef_kernel(const double*
     c.W[(size_t)q * N + i] = s;
   }
   __syncthreads();
-  int ok = 1;
+  // checks (a) and (b) at this thread's point, for the first `cnt` coefficients
+  const double x = -1.0 + 2.0 * i / (4 * N - 1);
+  double F = 1.0, T = 1.0;
   if (i < 4 * N) {
-    const double x = -1.0 + 2.0 * i / (4 * N - 1);
-    double u1 = 0.0, u2 = 0.0;                 // Clenshaw
-    for (int n = N - 1; n >= 1; --n) {
-      const double un = __builtin_fma(2.0 * x, u1, sW[n] - u2);
-      u2 = u1; u1 = un;
-    }
-    const double pv = __builtin_fma(x, u1, sW[0] - u2);
     const double ts = ts_of(x);
     const double chi = chi_exact(bj, nb, t_epoch - ts);
-    const double F = chi * chi;
+    F = chi * chi;
     // the table's chi at this launch time, as the scans evaluate it
     double w = (t_epoch - ts - t.lo) * t.inv_h;
     w = __builtin_fmin(__builtin_fmax(w, 0.0), t.wmax);
@@ -409,11 +427,31 @@ __global__ __launch_bounds__(kSrtCoefThreads) void srt_coef_kernel(const double*
     const double* cp = tab + ((int)kf + (j == 0 ? 0 : t.ni)) * kChiStride;
     double ct = cp[7];
     for (int n = 6; n >= 0; --n) ct = __builtin_fma(ct, xi, cp[n]);
-    const double T = ct * ct;
-    ok = __builtin_fabs(pv - F) <= kSrtMomTol * F && __builtin_fabs(pv - T) <= kSrtMomTol * T;
+    T = ct * ct;
+    sFc[i] = F;
   }
-  ok = __syncthreads_and(ok);
-  if (i == 0) c.ok[q] = ok;
+  auto passes = [&](int cnt) {
+    if (i >= 4 * N) return 1;
+    double u1 = 0.0, u2 = 0.0;                 // Clenshaw
+    for (int n = cnt - 1; n >= 1; --n) {
+      const double un = __builtin_fma(2.0 * x, u1, sW[n] - u2);
+      u2 = u1; u1 = un;
+    }
+    const double pv = __builtin_fma(x, u1, sW[0] - u2);
+    return (int)(__builtin_fabs(pv - F) <= kSrtMomTol * F && __builtin_fabs(pv - T) <= kSrtMomTol * T);
+  };
+  const int ok = __syncthreads_and(passes(N));         // (the barrier publishes sFc as well)
+  int m = N;
+  if (ok != 0 && RJP_SRT_TRUNC != 0) {
+    // every thread finds the same m from the same shared values
+    double fmin = sFc[0];
+    for (int n = 1; n < 4 * N; ++n) fmin = __builtin_fmin(fmin, sFc[n]);
+    const double lim = kSrtTailFrac * kSrtMomTol * fmin;
+    double tail = 0.0;
+    while (m > 1 && (tail += __builtin_fabs(sW[m - 1])) <= lim) --m;
+    if (m < N && !__syncthreads_and(passes(m))) m = N;  // (m is uniform: so is the branch)
+  }
+  if (i == 0) c.ok[q] = ok ? m : 0;
 }
 
 // The sorted scan with contracted bins: per group and jet, a bin of the support is contracted
@@ -422,15 +460,27 @@ __global__ __launch_bounds__(kSrtCoefThreads) void srt_coef_kernel(const double*
 // the other bins is streamed as ff_scan_sorted_kernel streams its one run.  A jet no lane of the
 // group holds is skipped (its sums are 0).  Without contracted bins the sums are
 // ff_scan_sorted_kernel's, bit for bit.
+// A contracted bin sums W_0 M_0 (each lane's own d_srt_cum step) and planes 1 .. m - 1 of its
+// moments, m = srt_coef_kernel's count (the byte rule keeps N - 1: which bins are contracted does
+// not depend on m).  The planes are read 16 bytes per lane: a plane's 64 sightlines of the group
+// are 512 contiguous, 16-byte-aligned bytes (P is even on the table path), so lanes 0-31 take
+// plane n as sightline pairs (2 l, 2 l + 1) and lanes 32-63 plane n + 1 the same way -- one wave
+// instruction per two planes.  Each lane keeps the two sums of ITS PAIR (times W_n or W_n+1, by
+// half-wave) across all contracted bins of both jets; the sums are linear, so the two half-waves
+// are added and every sightline's sum moves to its own lane once, at the end of the scan.
+// One wave serves a group and on a map like the bench's every wave is resident at once, so a
+// wave's chain of dependent loads is the kernel's time: the index rows, verdicts, W_0 and cum
+// steps of eight bins travel together, and a batch of N / 2 plane pairs runs on into the next
+// contracted bin (same-buffer A/B of these shapes: profiles/r08_cfg4_hybrid_ab.json).
 struct SrtMomDev {
   const double* mom;                           // [2 K (N - 1)][P]
   const double* W;                             // [2 K][N]
-  const int* ok;                               // [2 K]
+  const int* ok;                               // [2 K]: 0 = read the bin, else the coefficients to sum
   unsigned long long* diag;                    // += (contracted, read) (group, jet, bin) triples
 };
 
 template <int U, int N>
-__global__ __launch_bounds__(kSrtBlock) void ff_scan_hybrid_kernel(SrtDev s, SrtMomDev m,
+__global__ __launch_bounds__(kSrtBlock) __attribute__((amdgpu_waves_per_eu(4))) void ff_scan_hybrid_kernel(SrtDev s, SrtMomDev m,
                                                                    ChiTabDev t, double t_epoch,
                                                                    const double* __restrict__ tab,
                                                                    double* __restrict__ out) {
@@ -455,6 +505,13 @@ __global__ __launch_bounds__(kSrtBlock) void ff_scan_hybrid_kernel(SrtDev s, Srt
   };
   unsigned n_con = 0, n_read = 0;
   double total = 0.0;
+  // the moment planes' sums: of this lane's sightline pair and half of the planes (RJP_SRT_PAIR),
+  // else of its own sightline in .x
+  static_assert(N % 2 == 0 && N <= kSrtMaxN, "the moment planes are read in pairs");
+  [[maybe_unused]] constexpr int NP = N / 2;                            // pairs of planes (the last one is half empty)
+  [[maybe_unused]] const int half = lane >> 5;
+  [[maybe_unused]] const bool pair_live = g * RJP_WAVE + 2 * (lane & 31) < npix;
+  rjp_d2 pacc{0.0, 0.0};
 #pragma unroll 1
   for (int j = 0; j < 2; ++j) {
     const int q0 = j * K, b0 = s.b0[j], b1 = s.b1[j];
@@ -464,32 +521,103 @@ __global__ __launch_bounds__(kSrtBlock) void ff_scan_hybrid_kernel(SrtDev s, Srt
       continue;
     }
     const double skipped = (cum_at(q0 + K) - cum_at(q0 + b1)) + (cum_at(q0 + b0) - cum_at(q0));
-    // which bins of the support this group contracts
+    // which bins of the support this group contracts, and the M_0 terms of those: eight bins'
+    // index rows, verdicts and W_0 per round trip to memory
     unsigned cmask = 0;
-    int sprev = start_at(q0 + b0);
-    for (int b = b0; b < b1; ++b) {
-      const int snext = start_at(q0 + b + 1);
-      if (m.ok[q0 + b] && wave_max(snext - sprev) * 16 > (N - 1) * 8) cmask |= 1u << b;
-      sprev = snext;
+    unsigned long long cnt[3] = {0ull, 0ull, 0ull};    // coefficient counts, 5 bits per bin, 12 per word
+    auto count_of = [&](int b) {
+      return (int)(((b < 12 ? cnt[0] : b < 24 ? cnt[1] : cnt[2]) >> (5 * (b % 12))) & 31u);
+    };
+    double acc = 0.0;
+    for (int bb = b0; bb < b1; bb += 8) {
+      int st[9], wm[8];
+      double cu[9], w0[8];
+      unsigned mo[8];
+#pragma unroll
+      for (int u = 0; u < 9; ++u) {
+        st[u] = start_at(q0 + min(bb + u, b1));
+        cu[u] = cum_at(q0 + min(bb + u, b1));
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        mo[u] = (unsigned)m.ok[q0 + min(bb + u, b1 - 1)];
+        w0[u] = m.W[(size_t)(q0 + min(bb + u, b1 - 1)) * N];
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) wm[u] = wave_max(st[u + 1] - st[u]);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int b = bb + u;
+        if (b < b1) {
+          const unsigned mb = (unsigned)__builtin_amdgcn_readfirstlane(mo[u]);
+          if (mb && wm[u] * 16 > (N - 1) * 8) {
+            cmask |= 1u << b;
+            acc = __builtin_fma(w0[u], cu[u + 1] - cu[u], acc);
+          }
+          const unsigned long long bits = (unsigned long long)mb << (5 * (b % 12));
+          cnt[0] |= b < 12 ? bits : 0ull;
+          cnt[1] |= b >= 12 && b < 24 ? bits : 0ull;
+          cnt[2] |= b >= 24 ? bits : 0ull;
+        }
+      }
     }
     const int nc = __builtin_popcount(cmask);
     n_con += nc;
     n_read += (b1 - b0) - nc;
+#if RJP_SRT_PAIR
+    // the planes of the contracted bins, NP plane pairs per round trip, a batch running on into
+    // the next contracted bin: with m - 1 = 0 .. 16 planes a bin fills a batch rarely
+    {
+      auto next_bin = [&](int b) {
+        while (b < b1 && !(((cmask >> b) & 1u) && count_of(b) > 1)) ++b;
+        return b;
+      };
+      const double* mlane = m.mom + (int64_t)half * npix + g * RJP_WAVE + 2 * (lane & 31);
+      int cb = next_bin(b0), ci = 0;                    // the next plane pair: bin, pair of the bin
+      while (cb < b1) {
+        rjp_d2 v[NP];
+        double wn[NP];
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+          v[i] = rjp_d2{0.0, 0.0};
+          wn[i] = 0.0;
+          if (cb < b1) {                                // (wave-uniform)
+            const int m1 = count_of(cb) - 1, pl = 2 * ci + half;
+            // W_pl+1 of this half-wave's plane (the empty half of an odd last pair: W_N-1 x 0)
+            wn[i] = m.W[(size_t)(q0 + cb) * N + min(pl + 1, N - 1)];
+            if (pl < m1 && pair_live)
+              v[i] = __builtin_nontemporal_load(reinterpret_cast<const rjp_d2*>(
+                  mlane + ((int64_t)(q0 + cb) * (N - 1) + 2 * ci) * npix));
+            if (2 * ++ci >= m1) { cb = next_bin(cb + 1); ci = 0; }
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+          pacc.x = __builtin_fma(wn[i], v[i].x, pacc.x);
+          pacc.y = __builtin_fma(wn[i], v[i].y, pacc.y);
+        }
+      }
+    }
+#endif
     const int koff = j == 0 ? 0 : t.ni;                // red jet: the first half of the table
-    double acc = 0.0;
     for (int b = b0; b < b1;) {
       if ((cmask >> b) & 1u) {
+#if !RJP_SRT_PAIR
         if (live) {
           const double* w = m.W + (size_t)(q0 + b) * N;
+          const int m1 = count_of(b) - 1;                               // planes to read
           const double* mp = m.mom + (int64_t)(q0 + b) * (N - 1) * npix + p;
           double v[N - 1];
 #pragma unroll
-          for (int n = 0; n < N - 1; ++n) v[n] = __builtin_nontemporal_load(mp + (int64_t)n * npix);
-          double sum = w[0] * (cum_at(q0 + b + 1) - cum_at(q0 + b));
+          for (int n = 0; n < N - 1; ++n)
+            if (n < m1) v[n] = __builtin_nontemporal_load(mp + (int64_t)n * npix);
+          double sum = 0.0;
 #pragma unroll
-          for (int n = 0; n < N - 1; ++n) sum = __builtin_fma(w[n + 1], v[n], sum);
-          acc += sum;
+          for (int n = 0; n < N - 1; ++n)
+            if (n < m1) sum = __builtin_fma(w[n + 1], v[n], sum);
+          pacc.x += sum;
         }
+#endif
         ++b;
         continue;
       }
@@ -540,6 +668,15 @@ __global__ __launch_bounds__(kSrtBlock) void ff_scan_hybrid_kernel(SrtDev s, Srt
     atomicAdd(&m.diag[0], (unsigned long long)n_con);
     atomicAdd(&m.diag[1], (unsigned long long)n_read);
   }
+#if RJP_SRT_PAIR
+  // both halves of the planes, then sightline l from the pair of lane l / 2 (all lanes are here)
+  pacc.x += __shfl_xor(pacc.x, 32, RJP_WAVE);
+  pacc.y += __shfl_xor(pacc.y, 32, RJP_WAVE);
+  const double px = __shfl(pacc.x, lane >> 1, RJP_WAVE), py = __shfl(pacc.y, lane >> 1, RJP_WAVE);
+  total += (lane & 1) ? py : px;
+#else
+  total += pacc.x;
+#endif
   if (!live) return;
   if (!s.hb[0]) total += s.aux[p];
   if (!s.hb[1]) total += s.aux[npix + p];
@@ -909,6 +1046,8 @@ hipError_t chi_table_scan(const rjp_fields* fl, const ChiPlan& cp, const double*
     // ... with the bins whose chi^2 the moments' interpolant matches contracted: the coefficients
     // and verdicts of every (jet, bin) go to plane 0 of the workspace (unused by this scan)
     const int K = fl->srt_K, N = sp->N;
+    // the scan reads the moment planes in 16-byte pairs of sightlines (n_z is even on this path)
+    if ((npix & 1) || ((uintptr_t)fl->d_srt_mom % 16) != 0) return hipErrorInvalidValue;
     double* d_W = ws;
     int* d_ok = reinterpret_cast<int*>(ws + (size_t)2 * K * N);
     const SrtCoefDev c{fl->ts_lo, fl->ts_hi > fl->ts_lo ? K / (fl->ts_hi - fl->ts_lo) : 1.0, K, N,
