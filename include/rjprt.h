@@ -163,7 +163,11 @@ typedef struct rjp_fields {
    * workspace; when mom_cache_K / mom_cache_N equal the shape that sweep selects, the pass over
    * the grid is SKIPPED (rjp_last_scan_path returns 4).  The caller sets mom_cache_K / _N to the
    * shape rjp_last_scan_path reported after a call that filled the buffer, and back to 0
-   * whenever d_a0, d_ts, the range or the set of jets with bursts changes. */
+   * whenever d_a0, d_ts (their contents, not only the pointers), the range or the set of jets
+   * with bursts changes.  The cache is VOID after a range-guard report (rjp_range_guard() == 1,
+   * or an entry point that returns RJP_ERR_ARG with the guard's message): a pass that filled it
+   * since the last clean report may have written the NaN sums of the sightlines concerned, so
+   * the caller sets mom_cache_K / _N back to 0 then as well. */
   double* d_mom_cache;
   int32_t mom_cache_K, mom_cache_N;
   /* Optional launch-time-bucketed layout of (a0, ts) for SINGLE-epoch scans, built once per model

@@ -6,6 +6,7 @@ the CPU: without a GPU or without the built library, construction raises.
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -19,8 +20,42 @@ def _torch():
     return torch
 
 
+def _tensor_key(t):
+    """(address, version) of a tensor: the version counter catches in-place edits under the same
+    pointer, the pointer a new tensor (whose counter starts again)."""
+    return (t.data_ptr(), t._version)
+
+
+def lt_key(a0, ts, ts_lo, ts_hi):
+    """What a launch-time-ordered layout was built from."""
+    return _tensor_key(a0) + _tensor_key(ts) + (float(ts_lo), float(ts_hi))
+
+
+def mom_cache_key(a0, ts, d_ts, ts_lo, ts_hi, bursts_red, bursts_blue):
+    """What the cached moment maps are sums over: a0, the launch times (`d_ts`: the tensor the
+    scan reads, `ts` or its unmasked copy), the range and WHICH jets have bursts."""
+    return _tensor_key(a0) + _tensor_key(ts) + (d_ts, float(ts_lo), float(ts_hi),
+                                                bool(bursts_red), bool(bursts_blue))
+
+
+def unmasked_key(jet, ts, flag, rng):
+    """What the unmasked launch-time copy was made from."""
+    return (int(jet),) + _tensor_key(ts) + _tensor_key(flag) + (rng,)
+
+
 class DeviceFields:
-    """The packed per-cell state in HBM (include/rjprt.h `rjp_fields`)."""
+    """The packed per-cell state in HBM (include/rjprt.h `rjp_fields`).
+
+    Derived state and its keys (DESIGN.md "Derived state"): everything built FROM `a0` / `ts` --
+    the launch-time-ordered layout `lt`, the bucketed layout `srt`, the cached moment maps
+    `mom_cache`, the unmasked launch-time copy -- is keyed on those tensors' address AND
+    `_version`, so an in-place edit of `a0` or `ts` (a jet flag flipped, cells moved to other
+    launch times) makes it stale: a stale item is dropped or rebuilt, never attached.  The
+    launch-time range is the one exception: it is a DECLARATION the kernels watch (the range
+    guard), measured once per `ts` tensor; an in-place edit that leaves it poisons the sightlines
+    concerned and is reported by the next call.  In-place edits of the OTHER fields (nd, xi, temp,
+    pf, em0) are the caller's duty: rebuild what depends on them (`RTEngine.compact`,
+    `tau_layout`, `compute_y_bounds`), or go through `RTEngine.replace_field`, which does."""
 
     def __init__(self, shape, dtype, csize_au, nd, xi, temp, pf, ts=None, vy=None,
                  ff_raw=None, areas_raw=None):
@@ -68,8 +103,9 @@ class DeviceFields:
         f.occupied_cells = int(self.occupied_cells) if self.ylo is not None else 0
         lt = self.lt
         if (lt is not None and self.a0 is not None and self.ts is not None and
-                lt["key"] == (self.a0.data_ptr(), self.ts.data_ptr(), f.ts_lo, f.ts_hi)):
-            # (the layout belongs to the a0 / ts / launch-time range it was built from)
+                lt["key"] == lt_key(self.a0, self.ts, f.ts_lo, f.ts_hi)):
+            # (the layout belongs to the a0 / ts -- address and version -- and the launch-time
+            # range it was built from)
             f.d_lt_cells = lt["cells"].data_ptr()
             f.d_lt_rowoff = lt["rowoff"].data_ptr()
             f.d_lt_aux = lt["aux"].data_ptr()
@@ -139,7 +175,7 @@ class RTEngine:
         self.device = torch.device("cuda", self.device_index)
         torch.cuda.set_device(self.device)
         ctx = C.c_void_p()
-        _lib.check(self.lib.rjp_ctx_create(self.device_index, C.byref(ctx)), None,
+        self._check(self.lib.rjp_ctx_create(self.device_index, C.byref(ctx)), None,
                    "rjp_ctx_create")
         self.ctx = ctx
         self._work = None
@@ -166,6 +202,8 @@ class RTEngine:
         # 512 x 512 sightlines): from the second long sweep on only the contraction runs
         self.cache_moments = True
         self.last_moment_shape = (0, 0)
+        self._unreported = {}          # fields whose moment cache a pass filled since the last
+        #                                clean range-guard report (weak references by id)
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -179,6 +217,32 @@ class RTEngine:
             pass
 
     # -- helpers ---------------------------------------------------------------------------
+    GUARD_MESSAGE = "an earlier scan of this context met finite launch times outside"
+
+    def _check(self, status, ctx=None, what=""):
+        """`_lib.check`, and: an entry point that reports the range guard (RJP_ERR_ARG with the
+        guard's message: some EARLIER, asynchronous pass met launch times outside its declared
+        range and wrote NaN sums) voids whatever such passes filled."""
+        try:
+            _lib.check(status, ctx, what)
+        except _lib.RjprtError as e:
+            if self.GUARD_MESSAGE in str(e):
+                self._void_unreported()
+            raise
+
+    def _void_unreported(self):
+        """The moment maps filled since the last clean report may hold the NaNs of a pass the
+        guard flagged: their recorded shape is void (the next long sweep makes its own pass).
+        The layouts need no such rule: rjp_lt_count / rjp_srt_count check the range inside their
+        own, synchronous counting pass and refuse, so none is ever built from a flagged pass."""
+        for ref in self._unreported.values():
+            fields = ref()
+            mc = getattr(fields, "mom_cache", None)
+            if mc is not None:
+                mc["K"] = mc["N"] = 0
+                mc.pop("held", None)
+        self._unreported = {}
+
     def _stream(self):
         return C.c_void_p(_torch().cuda.current_stream(self.device).cuda_stream)
 
@@ -224,7 +288,7 @@ class RTEngine:
 
         def pack(src, den=None, redt=None):
             dst = self._empty(n, dtype)
-            _lib.check(self.lib.rjp_pack_field(
+            self._check(self.lib.rjp_pack_field(
                 self.ctx, src.data_ptr(), den.data_ptr() if den is not None else None,
                 redt.data_ptr() if redt is not None else None, dst.data_ptr(), n, dtype, st),
                 self.ctx, "rjp_pack_field")
@@ -257,7 +321,7 @@ class RTEngine:
         em0 = self._empty(fields.ncells, fields.dtype)
         bad = torch.empty(1, dtype=torch.int64, device=self.device)
         fs = fields.struct()
-        _lib.check(self.lib.rjp_compact_fields(self.ctx, C.byref(fs), em0.data_ptr(),
+        self._check(self.lib.rjp_compact_fields(self.ctx, C.byref(fs), em0.data_ptr(),
                                                bad.data_ptr(), self._stream()), self.ctx,
                    "rjp_compact_fields")
         if int(bad.item()) == 0:
@@ -276,7 +340,7 @@ class RTEngine:
             return fields
         a0 = self._f64(fields.ncells)
         fs = fields.struct()
-        _lib.check(self.lib.rjp_tau_field(self.ctx, C.byref(fs), int(gff_mode), a0.data_ptr(),
+        self._check(self.lib.rjp_tau_field(self.ctx, C.byref(fs), int(gff_mode), a0.data_ptr(),
                                           self._stream()), self.ctx, "rjp_tau_field")
         fields.a0, fields.a0_mode = a0, int(gff_mode)
         return fields
@@ -300,7 +364,7 @@ class RTEngine:
         wb = self.lib.rjp_ff_scan_workspace(nx, ny, nz, 1)
         work = self._workspace(wb)
         fs = fields.struct()
-        _lib.check(self.lib.rjp_tavg(self.ctx, C.byref(fs), out.data_ptr(), work.data_ptr(),
+        self._check(self.lib.rjp_tavg(self.ctx, C.byref(fs), out.data_ptr(), work.data_ptr(),
                                      work.numel(), self._stream()), self.ctx, "rjp_tavg")
         return out
 
@@ -313,7 +377,7 @@ class RTEngine:
         if fields.ts_range is not None and fields._ts_range_of == fields.ts.data_ptr():
             return fields.ts_range
         part = self._f64(2 * _lib.RJP_RANGE_BLOCKS)
-        _lib.check(self.lib.rjp_field_range(self.ctx, fields.ts.data_ptr(), fields.ncells,
+        self._check(self.lib.rjp_field_range(self.ctx, fields.ts.data_ptr(), fields.ncells,
                                             fields.dtype, part.data_ptr(), self._stream()),
                    self.ctx, "rjp_field_range")
         h = part.cpu().numpy().reshape(-1, 2)
@@ -329,7 +393,8 @@ class RTEngine:
         Chebyshev moments in registers -- no LDS atomics, no moment maps in HBM.  A one-off per
         model (two passes + scattered 16-byte writes: ~50 ms for 1.07e9 cells, ~1.2 x the bytes of
         a0 + ts resident): worth it for a model that is swept many times.  Rebuild after `a0` or
-        `ts` change (a stale layout is ignored by `struct()`).  K bins per jet: fewer, wider bins
+        `ts` change, in place or not (a stale layout is ignored by `struct()`: its key holds the
+        tensors' versions).  K bins per jet: fewer, wider bins
         pad less (rows are as long as the fullest of 64 lanes: 1.15 x at K = 16, 1.17 x at 20,
         1.22 x at 32 on the dense benchmark grid) but need a higher order for the same bursts
         (24 / 20 / 16 for the example's); 20 measured fastest there."""
@@ -349,14 +414,14 @@ class RTEngine:
         total = C.c_int64()
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         ev[0].record()
-        _lib.check(self.lib.rjp_lt_count(self.ctx, C.byref(fs), int(K), rowoff.data_ptr(),
+        self._check(self.lib.rjp_lt_count(self.ctx, C.byref(fs), int(K), rowoff.data_ptr(),
                                          C.byref(total), self._stream()), self.ctx, "rjp_lt_count")
         ev[1].record()
         # (allocating ~1.2 x the bytes of a0 + ts is the slow part of a first build: hipMalloc)
         cells = torch.empty(max(1, total.value) * 64 * 2, dtype=torch.float64, device=self.device)
         aux = torch.empty(3 * fields.npix, dtype=torch.float64, device=self.device)
         ev[2].record()
-        _lib.check(self.lib.rjp_lt_fill(self.ctx, C.byref(fs), int(K), rowoff.data_ptr(),
+        self._check(self.lib.rjp_lt_fill(self.ctx, C.byref(fs), int(K), rowoff.data_ptr(),
                                         cells.data_ptr(), aux.data_ptr(), self._stream()),
                    self.ctx, "rjp_lt_fill")
         ev[3].record()
@@ -366,7 +431,7 @@ class RTEngine:
                      "rows": int(total.value), "build_ms": kernels_ms,
                      "build_with_allocation_ms": ev[0].elapsed_time(ev[3]),
                      "bytes": cells.numel() * 8,
-                     "key": (fields.a0.data_ptr(), fields.ts.data_ptr(), fs.ts_lo, fs.ts_hi)}
+                     "key": lt_key(fields.a0, fields.ts, fs.ts_lo, fs.ts_hi)}
         return fields.lt
 
     @staticmethod
@@ -414,7 +479,7 @@ class RTEngine:
         total = C.c_int64()
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         ev[0].record()
-        _lib.check(self.lib.rjp_srt_count(self.ctx, C.byref(fs), int(K), start.data_ptr(),
+        self._check(self.lib.rjp_srt_count(self.ctx, C.byref(fs), int(K), start.data_ptr(),
                                           rowbase.data_ptr(), hist, C.byref(total),
                                           self._stream()), self.ctx, "rjp_srt_count")
         ev[1].record()
@@ -431,7 +496,7 @@ class RTEngine:
         cum = torch.empty(n_idx, dtype=torch.float64, device=self.device)
         aux = torch.empty(3 * fields.npix, dtype=torch.float64, device=self.device)
         ev[2].record()
-        _lib.check(self.lib.rjp_srt_fill(self.ctx, C.byref(fs), int(K), start.data_ptr(),
+        self._check(self.lib.rjp_srt_fill(self.ctx, C.byref(fs), int(K), start.data_ptr(),
                                          rowbase.data_ptr(), cells.data_ptr(), cum.data_ptr(),
                                          aux.data_ptr(), self._stream()),
                    self.ctx, "rjp_srt_fill")
@@ -441,7 +506,7 @@ class RTEngine:
             mom = torch.empty(n_mom, dtype=torch.float64, device=self.device)
             ev_m = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
             ev_m[0].record()
-            _lib.check(self.lib.rjp_srt_moments(self.ctx, C.byref(fs), int(K), int(self.srt_N),
+            self._check(self.lib.rjp_srt_moments(self.ctx, C.byref(fs), int(K), int(self.srt_N),
                                                 start.data_ptr(), rowbase.data_ptr(),
                                                 cells.data_ptr(), mom.data_ptr(), self._stream()),
                        self.ctx, "rjp_srt_moments")
@@ -473,13 +538,13 @@ class RTEngine:
         lo = torch.empty(fields.npix, dtype=torch.int32, device=self.device)
         hi = torch.empty(fields.npix, dtype=torch.int32, device=self.device)
         fs = fields.struct()
-        _lib.check(self.lib.rjp_y_bounds(self.ctx, C.byref(fs), lo.data_ptr(), hi.data_ptr(),
+        self._check(self.lib.rjp_y_bounds(self.ctx, C.byref(fs), lo.data_ptr(), hi.data_ptr(),
                                          self._stream()), self.ctx, "rjp_y_bounds")
         fields.ylo, fields.yhi = lo, hi
         # (hint for the tiles-or-moments choice of long epoch sweeps, include/rjprt.h; summed by
         # the library: the first use of the equivalent torch ops costs ~0.2 s of lazy loading)
         n = C.c_int64()
-        _lib.check(self.lib.rjp_occupied_cells(self.ctx, lo.data_ptr(), hi.data_ptr(),
+        self._check(self.lib.rjp_occupied_cells(self.ctx, lo.data_ptr(), hi.data_ptr(),
                                                fields.npix, C.byref(n), self._stream()),
                    self.ctx, "rjp_occupied_cells")
         fields.occupied_cells = int(n.value)
@@ -495,7 +560,7 @@ class RTEngine:
         if src.numel() != fields.ncells:
             raise ValueError("grid shape mismatch")
         dst = self._empty(fields.ncells, fields.dtype)
-        _lib.check(self.lib.rjp_pack_field(self.ctx, src.data_ptr(), None, None,
+        self._check(self.lib.rjp_pack_field(self.ctx, src.data_ptr(), None, None,
                                            dst.data_ptr(), fields.ncells, fields.dtype,
                                            self._stream()), self.ctx, "rjp_pack_field")
         self.synchronize()
@@ -550,7 +615,7 @@ class RTEngine:
         vxr = self._f64(n) if want_vxz else None
         vzr = self._f64(n) if want_vxz else None
         ptr = lambda t: t.data_ptr() if t is not None else None
-        _lib.check(self.lib.rjp_build_fields(
+        self._check(self.lib.rjp_build_fields(
             self.ctx, C.byref(geom), dtype, ptr(nd), ptr(xi), temp.data_ptr(), ptr(pf), ptr(ts),
             ptr(vy), ptr(ffr), ptr(arr), ptr(vxr), ptr(vzr), ptr(em0), ptr(a0),
             int(tau_mode or 0), self._stream()), self.ctx, "rjp_build_fields")
@@ -578,7 +643,7 @@ class RTEngine:
         if not new:
             return fields
         ptr = lambda k: new[k].data_ptr() if k in new else None
-        _lib.check(self.lib.rjp_build_fields(
+        self._check(self.lib.rjp_build_fields(
             self.ctx, C.byref(geom), fields.dtype, ptr("nd"), ptr("xi"), None, ptr("pf"), None,
             ptr("vy"), None, None, None, None, None, None, 0, self._stream()), self.ctx,
             "rjp_build_fields")
@@ -608,7 +673,7 @@ class RTEngine:
         temp, ts = self._empty(n, dtype), self._empty(n, dtype)
         vy = self._empty(n, dtype) if with_vy else None
         ptr = lambda t: t.data_ptr() if t is not None else None
-        _lib.check(self.lib.rjp_synth_fields(
+        self._check(self.lib.rjp_synth_fields(
             self.ctx, int(seed), int(temp_mode), int(nz), int(cell0), int(n), dtype,
             ptr(nd), ptr(xi), temp.data_ptr(), ptr(pf), ts.data_ptr(), ptr(vy), ptr(em0),
             ptr(a0), int(tau_mode or 0), self._stream()), self.ctx, "rjp_synth_fields")
@@ -674,11 +739,11 @@ class RTEngine:
         # copy obeys the range it is scanned under: measure the range first, key the copy on it)
         rng = self.launch_time_range(fields)
         full = fields.struct()
-        key = (jet, fields.ts.data_ptr(), flag.data_ptr(), rng)
+        key = unmasked_key(jet, fields.ts, flag, rng)
         cached = getattr(fields, "_ts_unmasked", None)
         if cached is None or cached[0] != key:
             out = self._empty(fields.ncells, fields.dtype)
-            _lib.check(self.lib.rjp_unmask_launch_times(self.ctx, C.byref(full), jet,
+            self._check(self.lib.rjp_unmask_launch_times(self.ctx, C.byref(full), jet,
                                                         out.data_ptr(), self._stream()),
                        self.ctx, "rjp_unmask_launch_times")
             cached = fields._ts_unmasked = (key, out)
@@ -704,7 +769,7 @@ class RTEngine:
         fs = self._scan_struct(fields, bursts, E)
         mkey = self._attach_moment_cache(fields, bursts, fs, E, em is not None)
         ep = _lib.dbl_array(epochs_s)
-        _lib.check(self.lib.rjp_ff_scan(
+        self._check(self.lib.rjp_ff_scan(
             self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None, ep, E,
             int(gff_mode), sumA.data_ptr(), em.data_ptr() if em is not None else None,
             tavg.data_ptr() if tavg is not None else None, work.data_ptr(), work.numel(),
@@ -728,7 +793,7 @@ class RTEngine:
         fs = self._scan_struct(fields, bursts, E)
         mkey = self._attach_moment_cache(fields, bursts, fs, E, em is not None)
         ptr = lambda t: t.data_ptr() if t is not None else None
-        _lib.check(self.lib.rjp_ff_step(
+        self._check(self.lib.rjp_ff_step(
             self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None,
             _lib.dbl_array(epochs_s), E, int(gff_mode), tavg.data_ptr(), _lib.dbl_array(ctau),
             _lib.dbl_array(cflux), F, sumA.data_ptr(), ptr(em), ptr(tau), ptr(flux), ptr(ftot),
@@ -742,7 +807,12 @@ class RTEngine:
         """True when a scan of this engine met finite launch times outside the range its fields
         declared (rjp_range_guard; the sums of those sightlines are NaN).  Synchronises."""
         self.synchronize()
-        return self.lib.rjp_range_guard(self.ctx) == 1
+        raised = self.lib.rjp_range_guard(self.ctx) == 1
+        if raised:
+            self._void_unreported()
+        else:
+            self._unreported = {}     # (synchronised and clean: everything filled so far is good)
+        return raised
 
     def _attach_moment_cache(self, fields, bursts, fs, n_epochs, want_em):
         """The caller-kept moment maps of include/rjprt.h `rjp_fields.d_mom_cache`.  A long sweep
@@ -755,8 +825,8 @@ class RTEngine:
                 bursts is not None and fields.a0 is not None and fields.ts is not None and
                 fs.ts_lo != fs.ts_hi):
             return None
-        key = (fields.a0.data_ptr(), fs.d_ts, fs.ts_lo, fs.ts_hi, int(bursts.n[0]) > 0,
-               int(bursts.n[1]) > 0)
+        key = mom_cache_key(fields.a0, fields.ts, fs.d_ts, fs.ts_lo, fs.ts_hi,
+                            int(bursts.n[0]) > 0, int(bursts.n[1]) > 0)
         mc = fields.mom_cache
         if mc is None and (fields.ylo is None or
                            2 * int(fields.occupied_cells) >= fields.ncells):
@@ -792,6 +862,11 @@ class RTEngine:
             else:
                 mc["K"], mc["N"] = self.last_moment_shape     # this sweep's pass filled it
                 mc["key"] = key
+                mc.pop("held", None)
+                if path == "moments":
+                    # (an asynchronous pass: whether the range guard flagged it is known only
+                    # when a later entry point reports -- `_check` then voids the shape)
+                    self._unreported[id(fields)] = weakref.ref(fields)
         elif mc is not None:
             # another path ran (tiles, the launch-time-ordered layout): nothing was written -- the
             # buffer holds what it held; one that has never held moments is given back
@@ -820,7 +895,7 @@ class RTEngine:
         with moments, summed over its groups of 64 sightlines (rjp_last_srt_bins; synchronises
         the device).  (0, 0) after a scan without moments."""
         c, r = C.c_int64(), C.c_int64()
-        _lib.check(self.lib.rjp_last_srt_bins(self.ctx, C.byref(c), C.byref(r)), self.ctx,
+        self._check(self.lib.rjp_last_srt_bins(self.ctx, C.byref(c), C.byref(r)), self.ctx,
                    "rjp_last_srt_bins")
         return int(c.value), int(r.value)
 
@@ -841,7 +916,7 @@ class RTEngine:
         fs = self._scan_struct(fields, bursts, E)
         ep = _lib.dbl_array(epochs_s)
         ms = C.c_double()
-        _lib.check(self.lib.rjp_time_ff_scan(
+        self._check(self.lib.rjp_time_ff_scan(
             self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None, ep, E,
             int(gff_mode), sumA.data_ptr(), em.data_ptr() if want_em else None,
             tavg.data_ptr() if want_tavg else None, work.data_ptr(), work.numel(),
@@ -863,7 +938,7 @@ class RTEngine:
         work = self._workspace_maps(wb) if ftot is not None else None
         a, b = _lib.dbl_array(ctau), _lib.dbl_array(cflux)
         ptr = lambda t: t.data_ptr() if t is not None else None
-        _lib.check(self.lib.rjp_ff_maps(
+        self._check(self.lib.rjp_ff_maps(
             self.ctx, sumA.data_ptr(), tavg.data_ptr(), P, E, a, b, F, ptr(tau), ptr(flux),
             ptr(ftot), ptr(work), work.numel() if work is not None else 0, self._stream()),
             self.ctx, "rjp_ff_maps")
@@ -874,7 +949,7 @@ class RTEngine:
         F = len(ctau)
         out = self._f64(F, fields.ncells)
         fs = fields.struct()
-        _lib.check(self.lib.rjp_ff_cells(
+        self._check(self.lib.rjp_ff_cells(
             self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None,
             float(time_s), int(gff_mode), _lib.dbl_array(ctau), F, out.data_ptr(),
             self._stream()), self.ctx, "rjp_ff_cells")
@@ -890,7 +965,7 @@ class RTEngine:
         if out is None:
             out = self._f64(F, fields.npix)
         fs = fields.struct()
-        _lib.check(self.lib.rjp_ff_formal(
+        self._check(self.lib.rjp_ff_formal(
             self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None,
             float(time_s), int(gff_mode), _lib.dbl_array(ctau), _lib.dbl_array(csrc), F,
             out.data_ptr(), self._stream()), self.ctx, "rjp_ff_formal")
@@ -901,7 +976,7 @@ class RTEngine:
         F = len(nus)
         out = self._f64(F, fields.ncells)
         fs = fields.struct()
-        _lib.check(self.lib.rjp_rrl_cells(
+        self._check(self.lib.rjp_rrl_cells(
             self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None,
             float(time_s), C.byref(line), _lib.dbl_array(nus), F, out.data_ptr(),
             self._stream()), self.ctx, "rjp_rrl_cells")
@@ -914,7 +989,7 @@ class RTEngine:
         tau = self._f64(F, fields.npix)
         fs = fields.struct()
         nu = _lib.dbl_array(nus)
-        _lib.check(self.lib.rjp_rrl_scan(
+        self._check(self.lib.rjp_rrl_scan(
             self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None,
             float(time_s), C.byref(line), nu, F, tau.data_ptr(), self._stream()), self.ctx,
             "rjp_rrl_scan")
@@ -929,7 +1004,7 @@ class RTEngine:
         work = self._workspace_maps(wb) if want_ftot else None
         a, b = _lib.dbl_array(cflux_rrl), _lib.dbl_array(hnu_k)
         ptr = lambda t: t.data_ptr() if t is not None else None
-        _lib.check(self.lib.rjp_rrl_maps(
+        self._check(self.lib.rjp_rrl_maps(
             self.ctx, tau_rrl.data_ptr(), tau_ff.data_ptr(), tavg.data_ptr(), ptr(flux_ff), P,
             a, b, F, flux.data_ptr(), ptr(ftot), ptr(work),
             work.numel() if work is not None else 0, self._stream()), self.ctx,

@@ -108,6 +108,27 @@ CHI_MAX_NI = 460             # kChiMaxNI: intervals of the LDS table
 SRT_SHARE = 0.9              # srt_plan: the bucketed layout is read iff <= 90 % of the cells are
 
 
+GAUSS_RTOL = 3e-12           # scans that keep the Gaussians (tests/test_gpu_random_parity.py)
+
+
+def single_epoch_bound(ny):
+    """Bound on a single-epoch table / sorted / hybrid map against ref_single_epoch (derived at
+    the top of tests/test_gpu_single_epoch_reference.py): kChiTol on chi >= 1 gives 2e-13 on
+    chi^2, kSrtMomTol for a contracted bin, plus the rounding of an f64 sum of n_y terms."""
+    return 2.2e-13 + ny * 2.0 ** -53
+
+
+def against(got, ref, rtol, what):
+    """Identical zero / NaN / inf patterns and |got - ref| <= rtol ref; -> worst relative diff."""
+    assert np.array_equal(got == 0, ref == 0), what
+    assert np.array_equal(np.isnan(got), np.isnan(ref)), what
+    assert np.array_equal(np.isinf(got), np.isinf(ref)), what
+    ok = np.isfinite(ref) & (ref != 0)
+    rel = float(np.max(np.abs(got[ok] - ref[ok]) / ref[ok])) if ok.any() else 0.0
+    assert rel <= rtol, (what, rel, rtol)
+    return rel
+
+
 def example_burst_lists(only=None):
     """The reference example's four bursts as (red, blue) lists; `only` = "R" / "B": that jet's."""
     p = example_bursts_params()

@@ -23,12 +23,9 @@ pytestmark = pytest.mark.gpu
 YEAR = orc.YEAR
 SEED = 20250301
 MID = (128, 480, 256)              # 32768 sightlines x 480 rows = 1.6e7 cells: the sweeps' map
-GAUSS_RTOL = 3e-12
+GAUSS_RTOL = U.GAUSS_RTOL
 T0 = time.time()
-
-
-def bound(ny):
-    return 2.2e-13 + ny * 2.0 ** -53
+bound = U.single_epoch_bound       # (shared with tests/test_gpu_model_life.py)
 
 
 @pytest.fixture(scope="module")
@@ -97,15 +94,7 @@ def _scan(m, bursts, t, sorted_=True, moments=True):
     return a.cpu().numpy()[0], eng.last_scan_path()[0], eng.last_scan_layout(), eng.last_srt_bins()
 
 
-def _against(got, ref, rtol, what):
-    """Identical zero / NaN / inf patterns and |got - ref| <= rtol ref; -> worst relative diff."""
-    assert np.array_equal(got == 0, ref == 0), what
-    assert np.array_equal(np.isnan(got), np.isnan(ref)), what
-    assert np.array_equal(np.isinf(got), np.isinf(ref)), what
-    ok = np.isfinite(ref) & (ref != 0)
-    rel = float(np.max(np.abs(got[ok] - ref[ok]) / ref[ok])) if ok.any() else 0.0
-    assert rel <= rtol, (what, rel, rtol)
-    return rel
+_against = U.against
 
 
 def check_case(m, bursts, t, what=""):
