@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define RJP_VERSION 112          /* 0.1.12 */
+#define RJP_VERSION 113          /* 0.1.13 */
 #define RJP_RANGE_BLOCKS 2048    /* partial (min, max) pairs rjp_field_range writes */
 #define RJP_MAX_EPOCH_TILE 32    /* most epochs evaluated per grid pass: 32 uniformly spaced ones (with or without d_em), 16 when only 16-31 are left, else tiles of 8, 4, 2, 1 */
 
@@ -39,7 +39,7 @@ enum rjp_status {
   RJP_ERR_NODEVICE = -3,   /* no usable gfx950 device */
   RJP_ERR_WORKSPACE = -4,  /* workspace too small */
   RJP_ERR_DEGENERATE = -5  /* rjp_build_fields: the launch-time integral's 2F1 is a logarithmic
-                              case the device series does not cover; nothing was enqueued --
+                              case (or too close to one) for the device series; nothing was enqueued --
                               the caller evaluates `ts` itself (scipy hyp2f1, as the reference
                               does, maths/geometry.py:166-171) and uploads it */
 };
@@ -521,9 +521,12 @@ typedef struct rjp_geometry {
  * the un-packed fill factors / areas that JetModel.save pickles (classes.py:1704-1709);
  * d_vx_raw / d_vz_raw (float64, optional) the transverse components of JetModel.vel.
  * Launch times: closed form for q^d_v = 0, otherwise Gauss' 2F1(a, b; b+1; -A) of
- * maths/geometry.py:166-171 evaluated on the device (Pfaff + 1/z connection formula);
- * RJP_ERR_DEGENERATE if a-b or b is a non-positive integer (logarithmic cases) and
- * d_ts != NULL.
+ * maths/geometry.py:166-171 evaluated on the device (Pfaff series up to a switch point chosen
+ * per model, the 1/z connection formula above it; narrow jets, b ~ 1/epsilon of several hundred,
+ * included); RJP_ERR_DEGENERATE if d_ts != NULL and a-b or b is a non-positive integer
+ * (logarithmic cases) or a-b is so close to one (about 1e-5 for a-b near -1, 1e-7 near -3) that
+ * the connection formula would cancel below 1e-11.
+ * RJP_ERR_ARG for epsilon = 0 / mod_r_0 = 0 (the reference's rho = |r|/r_0 branch is not built).
  * d_em0 (optional, RJP_F64 only): the compact scan field of rjp_fields.d_em0 written in the
  * same pass, bit-identical to what rjp_compact_fields derives from nd, xi, pf -- with d_nd,
  * d_xi, d_pf NULL a continuum-only model occupies 24 B/cell (12e9 cells per 288 GB GPU).

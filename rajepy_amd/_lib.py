@@ -18,7 +18,7 @@ RJP_F32, RJP_F64 = 4, 8
 RJP_GFF_SCALAR, RJP_GFF_POWERLAW = 0, 1
 RJP_MAX_EPOCH_TILE = 32
 RJP_RANGE_BLOCKS = 2048
-RJP_VERSION = 112             # include/rjprt.h; the binding below matches exactly this ABI
+RJP_VERSION = 113             # include/rjprt.h; the binding below matches exactly this ABI
 RJP_OK = 0
 RJP_ERR_ARG, RJP_ERR_HIP, RJP_ERR_NODEVICE, RJP_ERR_WORKSPACE, RJP_ERR_DEGENERATE = \
     -1, -2, -3, -4, -5

@@ -266,26 +266,35 @@ __device__ __forceinline__ double powerlaw(double zero, double rho_, double reff
   return v;
 }
 
-// S(a, beta, s) = 2F1(a, 1; beta + 1; s) = sum_k (a)_k / (beta + 1)_k s^k for 0 <= s <= 1/2
-// (terms keep one sign after the first: no cancellation; <= 60 terms to 1e-16).
+// S(a, beta, s) = 2F1(a, 1; beta + 1; s) = sum_k (a)_k / (beta + 1)_k s^k for 0 <= s < 1.  A term
+// below kHypStop of the sum ends the series -- but only once the denominators beta + 1 + k are
+// positive and the term ratio is below 1: with beta = a - b < 0 (the connection formula) the terms
+// first fall, far below kHypStop for large b, and rise again to order one around
+// k = (b - a)(1 + 1/A); a series cut in the dip is wrong by that hump.  hyp_plan (rjprt.hip) keeps
+// every series the kernel meets within kHypMaxTerms.
 __device__ __forceinline__ double hyp_series(double a, double beta, double s) {
   double term = 1.0, sum = 1.0;
-  for (int k = 0; k < 80; ++k) {
-    term *= (a + k) / (beta + 1.0 + k) * s;
+  for (int k = 0; k < kHypMaxTerms; ++k) {
+    const double den = beta + 1.0 + k;
+    const double ratio = (a + k) / den * s;
+    term *= ratio;
     sum += term;
-    if (fabs(term) <= 1e-17 * fabs(sum)) break;
+    if (fabs(term) <= kHypStop * fabs(sum) && den > 0.0 && fabs(ratio) < 1.0) break;
   }
   return sum;
 }
 
 // A^a * 2F1(a, b; b+1; -A) for A > 0: the product p2*p3*p4 of maths/geometry.py:159-171
-// (p2 p3 = (1 + 1/A)^-a (A + 1)^a = A^a).  Pfaff's transformation for A <= 1, the 1/z
-// connection formula (DLMF 15.8.2 with c = b + 1) followed by Pfaff for A > 1.
+// (p2 p3 = (1 + 1/A)^-a (A + 1)^a = A^a).  Pfaff's transformation for A <= hy_switch, the 1/z
+// connection formula (DLMF 15.8.2 with c = b + 1) followed by Pfaff above it.  hy_switch is 1
+// where the connection formula is sound from there on; for large b, or a - b close to a
+// non-positive integer, it cancels (or needs hundreds of terms) near A = 1 and the host moves the
+// switch up.
 __device__ __forceinline__ double hyp_flow_factor(const GeomDev& g, double A) {
   const double a = g.hy_a, b = g.hy_b;
   const double s = A / (1.0 + A);
   const double sa = pow(s, a);                     // A^a (1 + A)^-a
-  if (A <= 1.0) return sa * hyp_series(a, b, s);
+  if (A <= g.hy_switch) return sa * hyp_series(a, b, s);
   return sa * g.hy_k1 * hyp_series(a, a - b, 1.0 / (1.0 + A)) + g.hy_k2 * pow(A, a - b);
 }
 

@@ -197,6 +197,12 @@ hipError_t scan_f32(int vec, int lay, const rjp_fields* fl, const BurstsDev& b, 
                     double* ws, bool want_em, hipStream_t st);
 
 // ---- fields.hip ---------------------------------------------------------------------------
+// K4's two 2F1 series (hyp_series): no series may need more than kHypMaxTerms terms, and a term
+// below kHypStop of the sum ends one.  hyp_plan (host) only hands the device a model for which
+// both hold, with the same summation in double.
+constexpr int kHypMaxTerms = 400;
+constexpr double kHypStop = 1e-17;
+
 struct GeomDev {
   int nx, ny, nz, ccw;
   int ix0, nx_total;              // x-slab: rows [ix0, ix0+nx) of an nx_total-wide grid
@@ -212,8 +218,10 @@ struct GeomDev {
   double ts_const, ts_pow, ts_base;   // ts = ts_const * (rad^ts_pow - ts_base)  [q^d_v == 0]
   int ts_mode;                        // 0 = skip, 1 = closed form (q^d_v = 0), 2 = with 2F1
   // q^d_v != 0 (maths/geometry.py:150-178): a = q^d_v, b = (1 - q_v + eps q^d_v)/eps,
-  // hypergeometric connection coefficients K1 = b/(b-a), K2 = Gamma(b+1)Gamma(a-b)/Gamma(a)
-  double hy_a, hy_b, hy_k1, hy_k2, hy_axis;
+  // hypergeometric connection coefficients K1 = b/(b-a), K2 = Gamma(b+1)Gamma(a-b)/Gamma(a);
+  // hy_switch: the Pfaff series serves A <= hy_switch, the connection formula A > hy_switch
+  // (chosen per model by hyp_plan, rjprt.hip; +inf = the Pfaff series alone)
+  double hy_a, hy_b, hy_k1, hy_k2, hy_axis, hy_switch;
   double r1_m, r2_m, w0_m, mr0_m, r0_m;
 };
 

@@ -892,6 +892,85 @@ int rjp_rrl_maps(rjp_ctx* ctx, const double* d_tau_rrl, const double* d_tau_ff,
                                     n_chan, d_flux, d_ftot, (double*)d_work, st), "rrl_maps_launch");
 }
 
+}  // extern "C"
+
+// ---- K4's 2F1: which series where ---------------------------------------------------------------
+// hyp_series of fields.hip on the host, also returning the largest |term| (the leading 1 included)
+// and the number of terms taken (kHypMaxTerms + 1: the series did not end).
+struct HypSum { double sum, big; int taken; };
+
+static HypSum hyp_series_host(double a, double beta, double s) {
+  HypSum r = {1.0, 1.0, rjp::kHypMaxTerms + 1};
+  double term = 1.0;
+  for (int k = 0; k < rjp::kHypMaxTerms; ++k) {
+    const double den = beta + 1.0 + k;
+    const double ratio = (a + k) / den * s;
+    term *= ratio;
+    r.sum += term;
+    r.big = std::max(r.big, fabs(term));
+    if (fabs(term) <= rjp::kHypStop * fabs(r.sum) && den > 0.0 && fabs(ratio) < 1.0) {
+      r.taken = k + 1;
+      break;
+    }
+  }
+  return r;
+}
+
+// Gamma(b + 1) Gamma(a - b) / Gamma(a); through lgamma where a factor leaves the double range
+// (b + 1 > 171: inf * 0)
+static double hyp_gamma_ratio(double b, double amb, double a) {
+  const double v = tgamma(b + 1.) * tgamma(amb) / tgamma(a);
+  if (std::isfinite(v) && v != 0.0) return v;
+  int s1 = 1, s2 = 1, s3 = 1;
+  const double lg = lgamma_r(b + 1., &s1) + lgamma_r(amb, &s2) - lgamma_r(a, &s3);
+  return (double)(s1 * s2 * s3) * exp(lg);
+}
+
+// The launch-time integral A^a 2F1(a, b; b + 1; -A) is summed by the Pfaff series for A <= switch
+// and by the 1/z connection formula above it (fields.hip: hyp_flow_factor).  The connection
+// formula is sound from A = 1 on for b of a few units.  For large b (narrow jets: b ~ 1/eps) its
+// series first falls and then comes back to order one around k = (b - a)(1 + 1/A): hundreds of
+// terms near A = 1.  For a - b within ~1e-4 of a non-positive integer its two parts cancel like
+// 1/(distance A).  So the switch is the smallest of kHypSwitch at which (probed at five A from the
+// switch upwards) the connection formula ends within kHypConnTerms terms and loses at most
+// kHypMaxLoss to cancellation, while the Pfaff series ends within kHypMaxTerms at the switch; +inf
+// (the Pfaff series for every A) serves large b.  No such switch: refused (false).
+static bool hyp_plan(double a, double b, double* k1, double* k2, double* a_switch) {
+  constexpr double kHypSwitch[] = {1.0, 1.25, 1.5, 2.0, 3.0, 4.0, 6.0, 8.0, 16.0, 64.0, HUGE_VAL};
+  constexpr double kHypProbe[] = {1.0, 1.5, 2.0, 4.0, 16.0};
+  constexpr int kHypConnTerms = 100;
+  constexpr double kHypMaxLoss = 4096.0;
+  const double amb = a - b;
+  auto nonpos_int = [](double v, double tol) { return v < 0.5 && fabs(v - nearbyint(v)) < tol; };
+  if (nonpos_int(amb, 1e-9) || nonpos_int(b, 1e-6) || nonpos_int(b + 1., 1e-6) || b == a)
+    return false;
+  *k1 = b / (b - a);
+  *k2 = (a <= 0.0 && a == nearbyint(a)) ? 0.0 : hyp_gamma_ratio(b, amb, a);
+  if (!std::isfinite(*k1) || !std::isfinite(*k2)) return false;
+  for (double sw : kHypSwitch) {
+    const bool all = !std::isfinite(sw);
+    if (hyp_series_host(a, b, all ? 1.0 : sw / (1.0 + sw)).taken > rjp::kHypMaxTerms)
+      return false;                                   // a larger switch needs still more terms
+    bool ok = true;
+    for (int i = 0; ok && !all && i < 5; ++i) {
+      const double A = sw * kHypProbe[i];
+      const double sa = pow(A / (1.0 + A), a);
+      const HypSum c = hyp_series_host(a, amb, 1.0 / (1.0 + A));
+      const double t2 = *k2 * pow(A, amb);
+      const double tot = sa * *k1 * c.sum + t2;
+      const double loss = std::max(fabs(sa * *k1) * c.big, fabs(t2)) / fabs(tot);
+      ok = c.taken <= kHypConnTerms && loss <= kHypMaxLoss;      // (false for NaN)
+    }
+    if (ok) {
+      *a_switch = sw;
+      return true;
+    }
+  }
+  return false;
+}
+
+extern "C" {
+
 int rjp_build_fields(rjp_ctx* ctx, const rjp_geometry* gm, int dtype, void* d_nd, void* d_xi,
                      void* d_temp, void* d_pf, void* d_ts, void* d_vy, double* d_ff_raw,
                      double* d_areas_raw, double* d_vx_raw, double* d_vz_raw, void* d_em0,
@@ -901,6 +980,10 @@ int rjp_build_fields(rjp_ctx* ctx, const rjp_geometry* gm, int dtype, void* d_nd
   if (dtype != RJP_F32 && dtype != RJP_F64) return fail(ctx, RJP_ERR_ARG, "bad dtype tag");
   if (gm->nx <= 0 || gm->ny <= 0 || gm->nz <= 0 || !(gm->csize > 0))
     return fail(ctx, RJP_ERR_ARG, "bad grid in geometry");
+  if (gm->epsilon == 0.0 || gm->mod_r_0 == 0.0)
+    return fail(ctx, RJP_ERR_ARG, "rjp_build_fields: epsilon = 0 / mod_r_0 = 0 (a cylindrical jet, "
+                                  "for which the reference scales rho = |r| / r_0) is not "
+                                  "implemented: every field would be inf or NaN");
   if ((d_em0 || d_a0) && dtype != RJP_F64)
     return fail(ctx, RJP_ERR_ARG, "rjp_build_fields: d_em0 / d_a0 are written for RJP_F64 storage "
                                   "only (float storage goes through rjp_compact_fields' range check)");
@@ -939,17 +1022,16 @@ int rjp_build_fields(rjp_ctx* ctx, const rjp_geometry* gm, int dtype, void* d_nd
     g.hy_axis = 1. + gm->qd_v / (1. - gm->q_v);
     g.hy_k1 = g.hy_k2 = 0.0;
     g.ts_mode = d_ts ? 1 : 0;
+    g.hy_switch = 1.0;
     if (d_ts && a != 0.0) {
-      // connection coefficients need Gamma(a-b) and 1/Gamma(a): degenerate when a - b or b
-      // is an integer <= 0 (logarithmic cases) -> refuse, the caller evaluates ts itself
-      const double amb = a - b;
-      auto nonpos_int = [](double v) { return v < 0.5 && fabs(v - nearbyint(v)) < 1e-6; };
-      if (nonpos_int(amb) || nonpos_int(b) || nonpos_int(b + 1.) || b == a)
+      // the connection formula needs Gamma(a-b) and 1/Gamma(a): logarithmic cases when a - b or
+      // b is an integer <= 0.  hyp_plan refuses those and every model whose series would cancel
+      // or not end -> the caller evaluates ts itself
+      if (!hyp_plan(a, b, &g.hy_k1, &g.hy_k2, &g.hy_switch))
         return fail(ctx, RJP_ERR_DEGENERATE,
-                    "rjp_build_fields: degenerate 2F1 parameters (a-b or b a non-positive "
-                    "integer); pass d_ts = NULL and upload host-computed launch times");
-      g.hy_k1 = b / (b - a);
-      g.hy_k2 = nonpos_int(a) ? 0.0 : tgamma(b + 1.) * tgamma(amb) / tgamma(a);
+                    "rjp_build_fields: degenerate 2F1 parameters (a-b or b at or too close to a "
+                    "non-positive integer for the device series); pass d_ts = NULL and upload "
+                    "host-computed launch times");
       g.ts_mode = 2;
     }
   }
