@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define RJP_VERSION 113          /* 0.1.13 */
+#define RJP_VERSION 114          /* 0.1.14 */
 #define RJP_RANGE_BLOCKS 2048    /* partial (min, max) pairs rjp_field_range writes */
 #define RJP_MAX_EPOCH_TILE 32    /* most epochs evaluated per grid pass: 32 uniformly spaced ones (with or without d_em), 16 when only 16-31 are left, else tiles of 8, 4, 2, 1 */
 
@@ -493,6 +493,34 @@ int rjp_rrl_maps(rjp_ctx* ctx, const double* d_tau_rrl, const double* d_tau_ff,
                  const double* h_cflux_rrl, const double* h_hnu_k, int32_t n_chan,
                  double* d_flux, double* d_ftot, void* d_work, size_t work_bytes,
                  void* stream);
+
+/* ---- K6: recombination-line intensity by the formal solution along the line of sight --------
+ * The reference's intensity_rrl / flux_rrl (classes.py:1280-1282, 1339-1343; rrls.py:444-449;
+ * physics.py:571-574; rjp_rrl_maps here) are isothermal: I_L = B_nu(T_avg) e^-tau_ff
+ * (1 - e^-tau_rrl), exact only where T is constant along the sightline and never negative.  This
+ * entry point walks every sightline front to back (observer at the iy = 0 end of axis 1, as
+ * rjp_ff_formal) with, per cell i and channel f,
+ *   c_i = h_ctau[f] b_i     the free-free optical depth, b_i as rjp_ff_formal forms it from the
+ *                           wide fields ((|nd| xi)^2 pf T^-1.5 | T^-1.35, times chi^2),
+ *   l_i                     the line optical depth, exactly the term rjp_rrl_scan sums and
+ *                           rjp_rrl_cells writes (classes.py:1159-1214; rrls.py:350-354, 383-389),
+ *   B_i = 1 / expm1(h_hnu_k[f] / T_i)                                  (physics.py:571-574),
+ *   I_tot  = sum_i B_i (1 - e^-(c_i + l_i)) exp(-sum_{j < i} (c_j + l_j)),  I_cont: the same, l = 0,
+ *   d_out[f * P + p] = h_csrc[f] (I_tot - I_cont)  (+ d_add[f * P + p] when d_add != NULL),
+ * the difference accumulated without cancellation.  With a constant T it
+ * telescopes to B e^-tau_ff (1 - e^-tau_rrl): the reference's maps are the isothermal special case;
+ * with a temperature gradient a pixel can be negative (line absorption against hotter gas behind).
+ * h_nu: the channel frequencies [Hz]; h_ctau as for rjp_ff_maps; h_csrc / h_hnu_k as rjp_rrl_maps'
+ * h_cflux_rrl / h_hnu_k (divide h_csrc by omega / 1e-26 for intensity).  d_add: typically
+ * rjp_ff_formal's flux, for the line-plus-continuum product (contsub=False).
+ * A cell contributes its c_i exactly when rjp_ff_formal counts it and its l_i exactly when
+ * rjp_rrl_scan does; d_out is NaN exactly where T_avg is.  Reads the wide fields only (d_nd, d_xi,
+ * d_temp, d_pf, d_vy; d_ts with bursts), RJP_F32 or RJP_F64; d_ylo / d_yhi are honoured.  One epoch
+ * per call; every argument is validated before anything is enqueued (RJP_ERR_ARG otherwise). */
+int rjp_rrl_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
+                   double time_s, int32_t gff_mode, const rjp_line* line, const double* h_nu,
+                   const double* h_ctau, const double* h_csrc, const double* h_hnu_k,
+                   int32_t n_chan, const double* d_add, double* d_out, void* stream);
 
 /* ---- K4: geometry -> fields on the device --------------------------------------------
  * Replaces the lazily cached grids of JetModel (fill_factor/areas classes.py:657-669,

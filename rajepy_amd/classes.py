@@ -740,13 +740,34 @@ class JetModel:
         self._save_cube(tau, savefits, 'tau', freq)
         return tau
 
-    def _rrl_flux(self, rrl, freq, lte, contsub, intensity=False):
+    def _rrl_flux(self, rrl, freq, lte, contsub, intensity=False, formal=False):
         from . import engine as E
         if not lte:
             raise ValueError("Non-LTE RRL calculations not yet supported")   # classes.py:1261
         scalar = np.isscalar(freq)
         freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
         F, P = len(freqs), self.nx * self.nz
+        if formal:
+            # the line by the formal solution (RTEngine.rrl_formal); with contsub=False on top of
+            # the formal continuum, which keeps the reference's Rayleigh-Jeans convention
+            gv = None
+            if self.gff_mode == _lib.RJP_GFF_SCALAR:
+                gv = [mphys.gff(nu, self.params['properties']['T_0']) for nu in freqs]
+            ctau, _ = E.ff_channel_coeffs(freqs, self.csize, self.params["target"]["dist"],
+                                          self.gff_mode, gv)
+            cfl, hnu = E.rrl_channel_coeffs(freqs, self.csize, self.params["target"]["dist"])
+            if intensity:
+                cfl = cfl / (E.solid_angle(self.csize, self.params["target"]["dist"]) / 1e-26)
+            add = None
+            if not contsub:
+                add = self._ff_products(freqs, flux=True, device=True, formal=True).reshape(F, P)
+            flux = self.engine.rrl_formal(self._wide_fields(), self._rjp_bursts(),
+                                          float(self.time), self.gff_mode,
+                                          _lib.Line(**mrrl.line_constants(rrl)), freqs, ctau, cfl,
+                                          hnu, add=add)
+            out = self._map(flux, (F,))
+            self._dev_product = flux.reshape(F, self.nx, self.nz)
+            return out[0] if scalar else out
         tau_rrl = self._rrl_tau_device(rrl, freqs)
         tau_ff = self._ff_products(freqs, tau=True, device=True).reshape(F, P)
         flux_ff = None
@@ -761,19 +782,24 @@ class JetModel:
         self._dev_product = flux.reshape(F, self.nx, self.nz)
         return out[0] if scalar else out
 
-    def intensity_rrl(self, rrl, freq, lte=True, savefits=False):
+    def intensity_rrl(self, rrl, freq, lte=True, savefits=False, formal=False):
         """RRL intensity [W m^-2 Hz^-1 sr^-1] (classes.py:1231-1290).  Arrays of
         frequencies are handled channel by channel; the reference's own array branch raises
-        (it passes the whole array where a scalar is meant, classes.py:1266-1271)."""
-        ints = self._rrl_flux(rrl, freq, lte, contsub=True, intensity=True)
-        self._save_cube(ints, savefits, 'intensity', freq)
+        (it passes the whole array where a scalar is meant, classes.py:1266-1271).
+        `formal=True`: by the formal solution along the line of sight (every cell's line emission
+        minus its absorption of what lies behind it, observer at the iy = 0 end of axis 1)
+        instead of the reference's isothermal B(T_avg) e^-tau_ff (1 - e^-tau_rrl); the two agree
+        where T is constant along the sightline, and only the formal one can be negative."""
+        ints = self._rrl_flux(rrl, freq, lte, contsub=True, intensity=True, formal=formal)
+        self._save_cube(ints, savefits, 'intensity', freq, formal=formal)
         return ints
 
-    def flux_rrl(self, rrl, freq, lte=True, contsub=True, savefits=False):
+    def flux_rrl(self, rrl, freq, lte=True, contsub=True, savefits=False, formal=False):
         """RRL flux [Jy/pixel], continuum-subtracted unless contsub=False
-        (classes.py:1292-1351)."""
-        fluxes = self._rrl_flux(rrl, freq, lte, contsub)
-        self._save_cube(fluxes, savefits, 'flux', freq)
+        (classes.py:1292-1351).  `formal`: see `intensity_rrl`; with contsub=False the continuum
+        added is `flux_ff(formal=True)`."""
+        fluxes = self._rrl_flux(rrl, freq, lte, contsub, formal=formal)
+        self._save_cube(fluxes, savefits, 'flux', freq, formal=formal)
         return fluxes
 
     # ------------------------------------------------------------------ products ----
@@ -1111,15 +1137,19 @@ class Pipeline:
                          'log': self.log}, f)
 
     def execute(self, simobserve=True, verbose=True, dryrun=False, resume=True, clobber=False,
-                formal=False):
+                formal=False, formal_rrl=False):
         """Radiative transfer for every run; writes EM/Tau/Flux FITS products, records
         `results['flux']`, pickles model and pipeline state (classes.py:2296-2479).
-        `formal=True`: the flux cubes (and `results['flux']` from them) by the formal solution
-        along the line of sight (`JetModel.flux_ff(formal=True)`); continuum runs only -- a run
-        table with an RRL run is refused before any run starts."""
-        if formal and any(r.obs_type != 'continuum' for r in self.runs):
+        `formal=True`: the flux cubes of continuum runs (and `results['flux']` from them) by the
+        formal solution along the line of sight (`JetModel.flux_ff(formal=True)`).
+        `formal_rrl=True`: those of radio-recombination-line runs by
+        `JetModel.flux_rrl(formal=True)`; the Tau products are unchanged.  `formal=True` alone
+        covers continuum runs only: a run table with an RRL run is then refused before any run
+        starts; `formal=True, formal_rrl=True` makes both kinds of run formal."""
+        if formal and not formal_rrl and any(r.obs_type != 'continuum' for r in self.runs):
             raise ValueError("formal=True: the formal solution covers continuum runs only; the "
-                             "run table holds radio-recombination-line runs")
+                             "run table holds radio-recombination-line runs (formal_rrl=True "
+                             "makes those formal too)")
         self.log.add_entry("INFO", "Beginning pipeline execution")
         if verbose != self.log.verbose:
             self.log.verbose = verbose
@@ -1139,6 +1169,7 @@ class Pipeline:
         mine = [i for i, r in enumerate(self.runs) if owner[float(r.year)] == rank]
         self._multi_rank = world > 1
         self._formal = bool(formal)
+        self._formal_rrl = bool(formal_rrl)
 
         pending = []
         if not dryrun:
@@ -1250,7 +1281,8 @@ class Pipeline:
             self.log.add_entry("INFO", f"Calculating fluxes and saving to {run.fits_flux}")
             if rrl:
                 fluxes = m.flux_rrl(run.line, run.chan_freqs, contsub=False,
-                                    savefits=run.fits_flux)
+                                    savefits=run.fits_flux,
+                                    formal=getattr(self, "_formal_rrl", False))
             else:
                 fluxes = m.flux_ff(run.chan_freqs, savefits=run.fits_flux,
                                    formal=getattr(self, "_formal", False))

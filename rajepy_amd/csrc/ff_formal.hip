@@ -21,63 +21,9 @@
 // Compute-bound (vector FP64): ~26 instructions per (cell, channel) update, 21 of them in
 // one_minus_exp_neg (relative error < 4e-15 for every tau); HBM traffic is 3 fields per cell
 // (a0, temp, ts on the tau layout) once per channel block.
-#include "rjp_host.h"
+#include "ff_formal.h"
 
 namespace rjp {
-
-constexpr int kFB = 256;     // threads per workgroup
-
-template <int LF> struct FormalTile {
-  static constexpr int ZT = LF == 256 ? 8 : 16;   // sightlines per workgroup
-  static constexpr int YC = kFB / ZT;             // y-rows per slab
-  static constexpr int G = kFB / LF;              // sightline groups
-  static constexpr int NZP = ZT / G;              // sightlines per thread
-};
-
-template <typename T>
-struct FormalFields {
-  const T* nd;
-  const T* xi;
-  const T* temp;
-  const T* pf;
-  const T* ts;
-  const T* em0;
-  const double* a0;
-  const int32_t* ylo;      // optional occupied y-range per sightline
-  const int32_t* yhi;
-};
-
-// b = |a0| chi^2 of one cell, 0 when it contributes nothing.  |a0| as the scans of the layout form
-// it (ff_scan_kernels.h load_rows / compute_rows): the stored tau field, |em0| T^-1.5|-1.35, or
-// (|nd| xi)^2 pf T^-1.5|-1.35; chi exactly from the bursts (K3's cell_line) -- a NaN launch time
-// gives NaN where the cell's jet has bursts (the term is dropped, as nansum drops it) and chi = 1
-// where it has none (classes.py:232-233).
-template <typename T, int LAY, bool BURSTS>
-__device__ __forceinline__ double formal_b(const FormalFields<T>& f, int64_t o, int mode,
-                                           const BurstsDev& bd, double time_s, double Tk) {
-  double a;
-  bool red;
-  if constexpr (LAY == LAY_TAU) {
-    const double v = f.a0[o];
-    red = signbit_d(v);
-    a = fabs(v);
-  } else if constexpr (LAY == LAY_CMP) {
-    const double g = (double)f.em0[o];
-    red = signbit_d(g);
-    a = fabs(g) * tau_weight(Tk, mode);
-  } else {
-    const double nd = (double)f.nd[o];
-    const double n0 = fabs(nd) * (double)f.xi[o];
-    red = signbit_d(nd);
-    a = n0 * n0 * (double)f.pf[o] * tau_weight(Tk, mode);
-  }
-  double b = a;
-  if (BURSTS) {
-    const double c = chi_cell(bd, red, time_s - (double)f.ts[o]);
-    b = a * (c * c);
-  }
-  return b == b ? b : 0.0;
-}
 
 #ifndef RJP_FORMAL_WAVES
 #define RJP_FORMAL_WAVES 4      /* 128-VGPR budget */

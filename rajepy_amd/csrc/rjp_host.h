@@ -1,6 +1,6 @@
 // Host-side interface between the translation units of librjprt (rjprt.hip = the C-ABI,
-// ff_scan.hip, ff_scan_inst.hip x 5, fields.hip, rrl_scan.hip): launch wrappers and the small
-// structs they exchange.  Nothing here is exported; the library's surface is include/rjprt.h.
+// ff_scan.hip, ff_scan_inst.hip x 5, fields.hip, rrl_scan.hip, rrl_formal.hip, ...): launch
+// wrappers and the small structs they exchange.  Nothing here is exported; the library's surface is include/rjprt.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -250,5 +250,12 @@ hipError_t rrl_maps_launch(const double* tau_rrl, const double* tau_ff, const do
                            const double* flux_ff, int64_t npix, const double* d_cflux,
                            const double* d_hnu_k, int nchan, double* flux, double* ftot,
                            double* part, hipStream_t st);
+
+// rrl_formal.hip: the line intensity by the formal solution along the line of sight (K6), out[F * P]
+hipError_t rrl_formal_launch(const rjp_fields* fl, const rjp_bursts* hb, const double* d_ext,
+                             double time_s, int mode, const rjp_line* line, const double* h_nu,
+                             const double* d_nu, const double* d_ctau, const double* d_csrc,
+                             const double* d_hnu_k, int nchan, const double* d_add, double* out,
+                             hipStream_t st);
 
 }  // namespace rjp

@@ -855,6 +855,31 @@ int rjp_ff_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* burs
                                                       d_out, st), "ff_formal_launch");
 }
 
+int rjp_rrl_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
+                   double time_s, int32_t gff_mode, const rjp_line* line, const double* h_nu,
+                   const double* h_ctau, const double* h_csrc, const double* h_hnu_k,
+                   int32_t n_chan, const double* d_add, double* d_out, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (gff_mode != RJP_GFF_SCALAR && gff_mode != RJP_GFF_POWERLAW)
+    return fail(ctx, RJP_ERR_ARG, "bad gff_mode");
+  // the wide fields only: nd, xi, temp, pf, vy (and ts with bursts)
+  if (int r = check_fields(ctx, fields, true)) return r;
+  if (int r = check_bursts(ctx, bursts, fields)) return r;
+  if (!line || !h_nu || !h_ctau || !h_csrc || !h_hnu_k || n_chan < 1 || !d_out)
+    return fail(ctx, RJP_ERR_ARG, "rjp_rrl_formal: NULL line / table / output or n_chan < 1");
+  hipStream_t st = (hipStream_t)stream;
+  const std::vector<double> ext = burst_ext_table(bursts);
+  const double* src[5] = {h_nu, h_ctau, h_csrc, h_hnu_k, ext.data()};
+  const size_t len[5] = {(size_t)n_chan, (size_t)n_chan, (size_t)n_chan, (size_t)n_chan,
+                         ext.size()};
+  double* dev[5];
+  if (int r = stage_tables(ctx, st, src, len, 5, dev)) return r;
+  return finish_staged(ctx, st, rjp::rrl_formal_launch(fields, bursts, ext.empty() ? nullptr : dev[4],
+                                                       time_s, gff_mode, line, h_nu, dev[0], dev[1],
+                                                       dev[2], dev[3], n_chan, d_add, d_out, st),
+                       "rrl_formal_launch");
+}
+
 int rjp_rrl_cells(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
                   double time_s, const rjp_line* line, const double* h_nu, int32_t n_chan,
                   double* d_tau_cells, void* stream) {

@@ -995,6 +995,37 @@ class RTEngine:
             "rjp_rrl_scan")
         return tau
 
+    def rrl_formal(self, fields, bursts, time_s, gff_mode, line, nus, ctau, csrc, hnu_k,
+                   add=None, out=None):
+        """LTE recombination-line intensity by the formal solution along the line of sight
+        (rjp_rrl_formal): csrc[f] * (I_tot - I_cont), the line's emission minus its absorption of
+        what lies behind it, cell by cell with B_i = 1 / expm1(hnu_k[f] / T_i), observer at the
+        iy = 0 end of axis 1 -> device tensor [F, P] (float64), NaN where the sightline has no
+        T > 0; negative where the line absorbs against hotter gas behind.  `ctau` as for `ff_maps`;
+        `csrc`, `hnu_k` = `rrl_channel_coeffs` (csrc divided by omega / 1e-26 for intensity).
+        `add` [F, P]: added to the result (the formal continuum, for contsub=False).  One epoch
+        (`time_s` [s]) per call; `fields` must hold the wide layout (nd, xi, temp, pf, vy)."""
+        F = len(nus)
+        if not (len(ctau) == len(csrc) == len(hnu_k) == F):
+            raise ValueError("rrl_formal: nus, ctau, csrc and hnu_k must have one entry per channel")
+        torch = _torch()
+        for name, t in (("add", add), ("out", out)):
+            # the kernel reads / writes F * P device doubles through the bare pointer
+            if t is not None and not (t.dtype == torch.float64 and t.device == self.device and
+                                      t.is_contiguous() and t.numel() == F * fields.npix):
+                raise ValueError("rrl_formal: `%s` must be a contiguous float64 tensor of F * P "
+                                 "values on %s" % (name, self.device))
+        if out is None:
+            out = self._f64(F, fields.npix)
+        fs = fields.struct()
+        self._check(self.lib.rjp_rrl_formal(
+            self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None,
+            float(time_s), int(gff_mode), C.byref(line), _lib.dbl_array(nus),
+            _lib.dbl_array(ctau), _lib.dbl_array(csrc), _lib.dbl_array(hnu_k), F,
+            add.data_ptr() if add is not None else None, out.data_ptr(), self._stream()),
+            self.ctx, "rjp_rrl_formal")
+        return out
+
     def rrl_maps(self, tau_rrl, tau_ff, tavg, flux_ff, cflux_rrl, hnu_k, want_ftot=True):
         """-> (flux[F,P], ftot[F])."""
         F, P = tau_rrl.shape

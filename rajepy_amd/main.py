@@ -3,7 +3,8 @@
     python -m rajepy_amd.main [-v] [-rt] [-so] [-r] [-c] model_params.py pipeline_params.py
 
 `--formal` (not in the reference) writes the flux cubes of continuum runs by the formal solution
-along the line of sight instead of the isothermal T_avg (1 - e^-tau).
+along the line of sight instead of the isothermal T_avg (1 - e^-tau); `--formal-rrl` does the same
+for the flux cubes of radio-recombination-line runs (instead of B(T_avg) e^-tau_ff (1 - e^-tau_rrl)).
 
 Several GPUs of one node: launch one process per GPU and the epochs of the run table are
 shared out between them (each rank writes the products of its runs, rank 0 the state files):
@@ -41,6 +42,10 @@ def main(argv=None):
                         help="Flux cubes by the formal solution along the line of sight "
                              "(observer at iy = 0) instead of the isothermal T_avg (1 - e^-tau); "
                              "continuum runs only")
+    parser.add_argument("--formal-rrl", action="store_true",
+                        help="Flux cubes of radio-recombination-line runs by the formal solution "
+                             "along the line of sight (observer at iy = 0) instead of the "
+                             "isothermal B(T_avg) e^-tau_ff (1 - e^-tau_rrl)")
     args = parser.parse_args(argv)
     jet_file = os.path.abspath(args.model_param_file)
     pline_file = os.path.abspath(args.pipeline_param_file)
@@ -70,7 +75,8 @@ def main(argv=None):
     pline.log.add_entry("INFO", "Pipeline initiated using model parameters defined in {}, and "
                                 "pipeline parameters defined in {}".format(jet_file, pline_file))
     pline.execute(resume=args.resume, clobber=args.clobber, simobserve=args.simobserve,
-                  verbose=args.verbose, dryrun=not args.radiative_transfer, formal=args.formal)
+                  verbose=args.verbose, dryrun=not args.radiative_transfer, formal=args.formal,
+                  formal_rrl=args.formal_rrl)
     for f in (jet_file, pline_file) if rank == 0 else ():
         dest = os.path.expanduser(os.sep.join([pline.params['dcys']['model_dcy'],
                                                os.path.basename(f)]))
