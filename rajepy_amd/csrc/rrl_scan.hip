@@ -25,12 +25,17 @@
 // pole term, centred lattice) are designed for <= 1e-8 relative on Re w against
 // scipy.special.wofz over their whole domain -- one order inside SURVEY.md section 7's 1e-7,
 // three inside BASELINE.json's 1e-5 on the maps: lattice step h = 0.675 with 8 node pairs
-// (3.4e-9), 6- and 4-term far-field series (4.1e-9 / 1.2e-9), pole term skipped where a
-// rigorous bound puts it below 3e-8 Re w (measured <= 1.5e-9), centred lattice with 7 nodes a
-// side (7e-10); tools/voigt_design.py restates each path in NumPy and prints this table.
+// (3.5e-9, at x = 0 and y = pi/h, where the pole term ends), 6- and 4-term far-field series
+// (4.1e-9 / 1.2e-9), pole term skipped where a rigorous bound puts it below 3e-8 Re w (measured
+// <= 1.5e-9 on the plain lattice, <= 2.9e-9 on the centred one), centred lattice with 7 nodes a
+// side (7.2e-10 with its pole term); tools/voigt_design.py restates each path in NumPy and prints
+// this table.
 // Rounds 1-2 held them to 1e-11 (h = 0.6, 10 pairs, 8/5 terms): 131 instead of ~102
 // instructions.  The generic per-lane path (16-lane layout, collapse=False, irregular cells)
-// keeps h = 0.6 / 10 pairs / 1e-11.
+// keeps h = 0.6 / 10 pairs: core 1.3e-11 (worst at x = 0, y = pi/h, where its pole term ends; below
+// 1e-11 elsewhere), far-field continued fraction 3e-10.  tests/test_k3_voigt_reference_cpu.py runs
+// the tool and holds its figures to the ones stated here; tests/test_gpu_k3_evaluations.py holds the
+// kernels to K3_RTOL_WAVE / K3_RTOL_LANE one evaluation at a time (measured: DESIGN.md section 3).
 #include "rrl_voigt.h"
 
 namespace rjp {

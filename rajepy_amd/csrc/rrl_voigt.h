@@ -17,9 +17,9 @@ constexpr int kRB = 256;     // threads per workgroup
 //  * y < 0.03, where sum and pole term of the plain lattice would cancel near a node:
 //    - kernels whose waves work on one cell: lattice centred on x (voigt_centred below);
 //    - otherwise: lattice shifted by h/2 whenever x is within h/4 of a node.
-// Generic per-lane code (voigt_rew): h = 0.6, 10 node pairs: relative error of Re w < 1e-11
-// for 1e-10 <= y <= 1e3, 0 <= x <= 1e4 (measured against scipy.special.wofz, which the reference
-// calls); far field (|z|^2 > 64 and (x^2 > 64 or y > 1)): 6-level Laplace continued fraction,
+// Generic per-lane code (voigt_rew): h = 0.6, 10 node pairs: relative error of Re w <= 1.3e-11
+// for 1e-10 <= y <= 1e3, 0 <= x <= 1e4 (against scipy.special.wofz, which the reference calls;
+// worst at x = 0, y = pi/h, where the pole term ends; tools/voigt_design.py); far field (|z|^2 > 64 and (x^2 > 64 or y > 1)): 6-level Laplace continued fraction,
 // relative error < 3e-10 there.
 constexpr double kH = 0.6;
 constexpr int kNPair = 10;
@@ -343,7 +343,7 @@ __device__ __forceinline__ double voigt_centred(double ax, double y, double ky, 
     s = __builtin_fma(e, t[-j], s);
   }
   s *= ky;                                                      // y h / pi
-  // pole term: below 3e-8 Re w by a rigorous bound (measured: 1e-9) once x^2 exceeds the
+  // pole term: below 3e-8 Re w by a rigorous bound (measured: 2.9e-9, at y = 1e-10) once x^2 exceeds the
   // per-cell bound cq; skipped when no lane of the wave needs it
   const double x2 = ax * ax;
   if (__builtin_amdgcn_ballot_w64(x2 < cq) != 0) {
@@ -502,7 +502,7 @@ __device__ __forceinline__ double voigt_far_series(double ax, double y) {
 // d_n are >= y^4 >= 8e-7 with at most one pair near its minimum and <= ~|z|^4 each: their
 // product stays inside the FP64 range for |z| < 1e9 (path_code sends waves with |x| > 1e6
 // to the generic path).  Near a node d_n loses digits ~ t_n^2 / y^2, as the factored form
-// of the generic path does.  Relative error <= 3.4e-9 against wofz for 0.03 <= y, x^2 <= 64,
+// of the generic path does.  Relative error <= 3.5e-9 against wofz for 0.03 <= y, x^2 <= 64,
 // pole term included (worst at x = 0 just above y = pi/h, where the pole term ends;
 // tools/voigt_design.py).  Rounds 1-2: h = 0.6, ten pairs, 1e-11.
 // `ky` = y h / pi, staged per cell.  `ax` may carry either sign (see the channel loop).

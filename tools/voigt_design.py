@@ -122,8 +122,15 @@ def pole_bound_cq(y, rmax2=67.0):
             np.log(1.0 / TOL_POLE) + np.log(rmax2))
 
 
-def centred(x, y):
-    """Lattice centred on x (voigt_centred), y < CEN_YMAX, x <= 16."""
+def centred_cq(y):
+    """x^2 above which the centred lattice leaves its pole term out (cell_line): |P| <= e^{y^2-x^2}
+    against Re w >= y / (4 (|z|^2 + 1)) with |z|^2 <= 16^2 + 1."""
+    return y * y - np.log(y) + np.log(1.0 / TOL_POLE) + np.log(4.0 * 258.0)
+
+
+def centred(x, y, pole=True):
+    """Lattice centred on x (voigt_centred), y < CEN_YMAX, x <= 16; pole=False: as a lane beyond
+    the per-cell bound centred_cq runs it."""
     km = np.rint(-x / H - 0.5)
     tm = (km + 0.5) * H + x
     w = tm * tm
@@ -152,20 +159,72 @@ def centred(x, y):
     t2 = th * th
     c = horner([1.0 / 40320.0, -1.0 / 720.0, 1.0 / 24.0, -0.5, 1.0], t2)     # cos, degree 8
     gq = 2.0 * q * np.exp(y * y) / (1.0 + q)       # staged per cell
-    return s + exp_neg_k(x * x) * c * gq
+    return s + exp_neg_k(x * x) * c * gq if pole else s
+
+
+# ---- generic per-lane code (voigt_rew<false>: 16-lane layout, collapse=False, irregular cells) ----
+H_GEN = 0.6                # its lattice step
+NPAIR_GEN = 10
+TOL_POLE_GEN = 1e-13       # pole term kept down to this * Re w
+
+
+def generic_core(x, y):
+    """voigt_rew<false> without its far-field branch (the core formula is valid everywhere, and a
+    wave that straddles the far-field boundary runs it on every lane): plain lattice + pole term
+    for y >= 0.03, the lattice shifted by h/2 near a node below (voigt_core_shifted)."""
+    x, y = np.broadcast_arrays(np.asarray(x, dtype=float), np.asarray(y, dtype=float))
+    r2 = x * x + y * y
+    U = r2 * r2
+    W = 2.0 * (y * y - x * x)
+    u = x * (1.0 / H_GEN)
+    fr = u - np.floor(u)
+    half = (y < CEN_YMAX) & ~((fr >= 0.25) & (fr < 0.75))
+    s = np.zeros_like(r2)
+    for n in range(NPAIR_GEN):
+        t0, t1 = (n * H_GEN) ** 2, ((n + 0.5) * H_GEN) ** 2
+        tau = np.where(half, t1, t0)
+        c2 = np.where(half, 2.0 * np.exp(-t1), 1.0 if n == 0 else 2.0 * np.exp(-t0))
+        s = s + (c2 * r2 + c2 * tau) / (tau * (W + tau) + U)
+    s = s * (y * (H_GEN / np.pi))
+    lnq = -2.0 * (np.pi / H_GEN) * y
+    q = np.exp(lnq)
+    e = y * y - x * x
+    omq = -np.expm1(lnq)
+    cq = (y * y + lnq + np.log(6.0) - 2.0 * np.log(omq) - np.log(0.25 * y) +
+          np.log(1.0 / TOL_POLE_GEN) + np.log(67.0))
+    th = 2.0 * np.pi * (fr - np.where(half, 0.5, 0.0))
+    ph = 2.0 * x * y
+    den = q * (q - 2.0 * np.cos(th)) + 1.0
+    # y >= 0.03: q cos(phi) - cos(theta - phi); below: the same, written out (cos and sin of both)
+    num = q * np.cos(ph) - np.cos(th - ph)
+    P = 2.0 * np.exp(e) * q * num / den
+    need = np.where(y < CEN_YMAX, e + lnq > np.log(s) - 31.0, (y < np.pi / H_GEN) & (x * x < cq))
+    return s + np.where(need, P, 0.0)
+
+
+def generic_far(x, y):
+    """voigt_far: 6 levels of the Laplace continued fraction."""
+    wr, wi = x * np.ones_like(y), y * np.ones_like(x)
+    for k in range(6, 0, -1):
+        s = (0.5 * k) / (wr * wr + wi * wi)
+        wr, wi = x - s * wr, y + s * wi
+    return 0.56418958354775628695 * wi / (wr * wr + wi * wi)
 
 
 def rel(a, ref):
     return np.abs(a - ref) / np.abs(ref)
 
 
-def main():
-    print("H = %.4f  pi/H = %.4f  NPAIR = %d  CEN_J = %d" % (H, np.pi / H, NPAIR, CEN_J))
+def measure():
+    """Worst relative error of every path over its domain against scipy.special.wofz:
+    {name: (error, (x, y))} -- the figures of the accuracy budget at the head of rrl_scan.hip."""
+    out = {}
     # ---- plain lattice (+ pole term) over its domain: 0.03 <= y, |z|^2 <= 64 or (x^2 <= 64, y <= 1)
     worst = (0, None)
     worst_skip = (0, None)
     for y in np.concatenate([np.geomspace(CEN_YMAX, 1, 80), np.linspace(1, 8.1, 143),
-                             POLE_LITE_Y + np.array([0.0, 1e-9, 0.01, 0.03])]):
+                             POLE_LITE_Y + np.array([0.0, 1e-9, 0.01, 0.03]),
+                             (np.pi / H) * np.array([1.0 - 1e-9, 1.0, 1.0 + 1e-9])]):
         x = np.linspace(0, 8.0, 6401)
         x = x[(x * x + y * y <= 64.0) | ((x * x <= 64.0) & (y <= 1.0))]
         if x.size == 0:
@@ -186,21 +245,21 @@ def main():
                 j = int(np.argmax(e2))
                 if e2[j] > worst_skip[0]:
                     worst_skip = (e2[j], (x[m][j], y))
-    print("plain lattice (pole term where y < pi/H): max rel err %.2e at x=%.3f y=%.4f"
-          % (worst[0], worst[1][0], worst[1][1]))
-    print("plain lattice, pole term skipped beyond cq:  max rel err %.2e at x=%.3f y=%.4f"
-          % (worst_skip[0], worst_skip[1][0], worst_skip[1][1]))
+    out["plain"] = worst
+    out["plain_skip"] = worst_skip
     # ---- far field
     for K, r2 in FAR:
-        worst = 0.0
+        worst = (0, None)
         for y in np.geomspace(1e-10, 1e3, 260):
             x0 = np.sqrt(max(r2 - y * y, 64.0 if y <= 1.0 else 0.0))
             x = x0 * (1.0 + 1e-9) + np.concatenate([np.linspace(0, 4, 81), np.geomspace(4, 1e4, 40)])
             ok = x * x + y * y > r2
             ref = wofz(x + 1j * y).real
-            worst = max(worst, float(rel(far_series(x, y, K), ref)[ok].max()))
-        print("far series K = %d, every lane |z|^2 > %g and (x^2 > 64 or y > 1): max rel err %.2e"
-              % (K, r2, worst))
+            e = np.where(ok, rel(far_series(x, y, K), ref), 0.0)
+            i = int(np.argmax(e))
+            if e[i] > worst[0]:
+                worst = (e[i], (x[i], y))
+        out["far%d" % K] = worst
     # ---- centred lattice
     worst = (0, None)
     for y in np.geomspace(1e-10, CEN_YMAX, 60):
@@ -210,8 +269,60 @@ def main():
         i = int(np.argmax(e))
         if e[i] > worst[0]:
             worst = (e[i], (x[i], y))
+    out["centred"] = worst
+    # lanes beyond the per-cell bound run without the pole term
+    worst = (0, None)
+    for y in np.geomspace(1e-10, CEN_YMAX, 240):
+        x0 = np.sqrt(centred_cq(y))
+        x = x0 + np.linspace(0.0, 1.0, 401)
+        x = x[x <= 16.0]
+        ref = wofz(x + 1j * y).real
+        e = rel(centred(x, y, pole=False), ref)
+        i = int(np.argmax(e))
+        if e[i] > worst[0]:
+            worst = (e[i], (x[i], y))
+    out["centred_skip"] = worst
+    # ---- generic per-lane code: the core formula over the whole range of the header of
+    # rrl_voigt.h (1e-10 <= y <= 1e3, 0 <= x <= 1e4), the continued fraction over its far field
+    worst_core, worst_far = (0, None), (0, None)
+    xs = np.concatenate([np.linspace(0, 8.4, 6721), np.geomspace(8.4, 1e4, 400)])
+    for y in np.concatenate([np.geomspace(1e-10, 1e3, 131), CEN_YMAX * np.array([1 - 1e-9, 1.0]),
+                             (np.pi / H_GEN) * np.array([1 - 1e-9, 1.0])]):
+        ref = wofz(xs + 1j * y).real
+        e = rel(generic_core(xs, y), ref)
+        i = int(np.argmax(e))
+        if e[i] > worst_core[0]:
+            worst_core = (e[i], (xs[i], y))
+        far = (xs * xs + y * y > 64.0) & ((xs * xs > 64.0) | (y > 1.0))
+        if far.any():
+            e = np.where(far, rel(generic_far(xs, np.full_like(xs, y)), ref), 0.0)
+            i = int(np.argmax(e))
+            if e[i] > worst_far[0]:
+                worst_far = (e[i], (xs[i], y))
+    out["generic_core"] = worst_core
+    out["generic_far"] = worst_far
+    return out
+
+
+def main():
+    print("H = %.4f  pi/H = %.4f  NPAIR = %d  CEN_J = %d" % (H, np.pi / H, NPAIR, CEN_J))
+    m = measure()
+    print("plain lattice (pole term where y < pi/H): max rel err %.2e at x=%.3f y=%.4f"
+          % (m["plain"][0], m["plain"][1][0], m["plain"][1][1]))
+    print("plain lattice, pole term skipped beyond cq:  max rel err %.2e at x=%.3f y=%.4f"
+          % (m["plain_skip"][0], m["plain_skip"][1][0], m["plain_skip"][1][1]))
+    for K, r2 in FAR:
+        print("far series K = %d, every lane |z|^2 > %g and (x^2 > 64 or y > 1): max rel err %.2e"
+              % (K, r2, m["far%d" % K][0]))
     print("centred lattice (y < %.2f, x <= 16): max rel err %.2e at x=%.3f y=%.3e"
-          % (CEN_YMAX, worst[0], worst[1][0], worst[1][1]))
+          % (CEN_YMAX, m["centred"][0], m["centred"][1][0], m["centred"][1][1]))
+    print("centred lattice, pole term skipped beyond cq: max rel err %.2e at x=%.3f y=%.3e"
+          % (m["centred_skip"][0], m["centred_skip"][1][0], m["centred_skip"][1][1]))
+    print("generic per-lane core (h = %.1f, %d pairs; 1e-10 <= y <= 1e3, x <= 1e4): max rel err "
+          "%.2e at x=%.4f y=%.3e" % (H_GEN, NPAIR_GEN, m["generic_core"][0],
+                                     m["generic_core"][1][0], m["generic_core"][1][1]))
+    print("generic per-lane far field (continued fraction, 6 levels): max rel err %.2e at x=%.4f "
+          "y=%.3e" % (m["generic_far"][0], m["generic_far"][1][0], m["generic_far"][1][1]))
     # ---- constants for the kernel
     tau = [(n * H) ** 2 for n in range(NPAIR)]
     w2 = [1.0] + [2.0 * float(np.exp(-t)) for t in tau[1:]]
