@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define RJP_VERSION 114          /* 0.1.14 */
+#define RJP_VERSION 115          /* 0.1.15 */
 #define RJP_RANGE_BLOCKS 2048    /* partial (min, max) pairs rjp_field_range writes */
 #define RJP_MAX_EPOCH_TILE 32    /* most epochs evaluated per grid pass: 32 uniformly spaced ones (with or without d_em), 16 when only 16-31 are left, else tiles of 8, 4, 2, 1 */
 
@@ -482,6 +482,49 @@ int rjp_rrl_cells(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* burs
 int rjp_ff_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
                   double time_s, int32_t gff_mode, const double* h_ctau, const double* h_csrc,
                   int32_t n_chan, double* d_out, void* stream);
+
+/* ---- K7: sensitivities of the light curves to the ejection-burst parameters --------------------
+ * Generalises the burst factor of number_density (classes.py:861-875), the y-reduction of
+ * optical_depth_ff (classes.py:1395-1432) and the flux sum of flux_ff (classes.py:1519-1521) to
+ * their derivatives with respect to the members of rjp_bursts.  For the bursts b of a cell's jet,
+ * with d = t_e - ts, G_b = exp(-(d - t0_b)^2 inv2s2_b) and chi = 1 + sum_b amp_rel_b G_b:
+ *   S[e, p]           = sum_y |a0| chi^2                            (what rjp_ff_scan returns)
+ *   dS/dt0_b          = sum_y |a0| 2 chi amp_rel_b G_b 2 inv2s2_b (d - t0_b)
+ *   dS/damp_rel_b     = sum_y |a0| 2 chi G_b
+ *   dS/dinv2s2_b      = sum_y |a0| 2 chi amp_rel_b G_b (-(d - t0_b)^2)
+ * (sums over the cells of burst b's jet only), from ONE pass over (d_a0, d_ts) per tile of up to
+ * four epochs, and
+ *   F[e, f]           = sum_p h_cflux[f] tavg[p] (1 - exp(-h_ctau[f] S[e, p]))
+ *   dF[e, f]/dtheta_k = sum_p h_cflux[f] tavg[p] h_ctau[f] exp(-h_ctau[f] S[e, p]) dS[e, p]/dtheta_k
+ * (h_ctau / h_cflux as for rjp_ff_maps; F with the arithmetic of its d_ftot).
+ * n_par = 3 (n[0] + n[1]); parameter k = 3 b + c, where b counts the red jet's bursts first and
+ * then the blue jet's, and c = 0: t0 [s], 1: amp_rel, 2: inv2s2 [s^-2].
+ * Outputs (device, any may be NULL, not all four):
+ *   d_sumA [E * P]                        S
+ *   d_dsumA[(e * n_par + k) * P + p]      dS/dtheta_k
+ *   d_ftot [E * F]                        F
+ *   d_dftot[(e * F + f) * n_par + k]      dF/dtheta_k
+ * With d_dsumA NULL the derivative maps live in the workspace one epoch tile at a time.
+ * Semantics: nansum as rjp_ff_scan (a NaN d_a0, or a NaN launch time in a jet that has bursts,
+ * drops the cell; a NaN tavg drops the pixel from the totals); the cells of a jet WITHOUT bursts
+ * have chi = 1 whatever their launch time (classes.py:232-233) -- they add |a0| to S and nothing to
+ * any derivative; the call applies that rule itself, d_ts is the model's own field (no
+ * rjp_unmask_launch_times copy).  A Gaussian below 2^-1021 counts as zero.  Negative amplitudes are
+ * fine.  Sums in a fixed order: bit-reproducible.  d_ylo / d_yhi are honoured; ts_lo / ts_hi, the
+ * layouts and the moment cache are not used.
+ * Needs RJP_F64 fields with d_a0 (a0_mode == gff_mode) and d_ts; d_tavg, h_ctau, h_cflux and
+ * n_chan >= 1 only when d_ftot or d_dftot is asked for.  RJP_ERR_ARG, with nothing enqueued, for:
+ * no burst at all, more than 8 bursts in a jet, a non-finite epoch or burst parameter, all four
+ * outputs NULL, a wrong dtype or layout; RJP_ERR_WORKSPACE for d_work smaller than
+ * rjp_ff_grad_workspace() (n_chan = 0 there: no totals).  Every argument is validated before the
+ * first launch. */
+size_t rjp_ff_grad_workspace(int32_t nx, int32_t ny, int32_t nz, int32_t n_epochs,
+                             int32_t n_par, int32_t n_chan);
+int rjp_ff_grad(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
+                const double* h_epochs_s, int32_t n_epochs, int32_t gff_mode,
+                const double* d_tavg, const double* h_ctau, const double* h_cflux, int32_t n_chan,
+                double* d_sumA, double* d_dsumA, double* d_ftot, double* d_dftot,
+                void* d_work, size_t work_bytes, void* stream);
 
 /* Map stage of intensity_rrl / flux_rrl (classes.py:1280-1282, 1339-1343;
  * rrls.py:444-449; physics.py:571-574):

@@ -1,5 +1,5 @@
 // Host-side interface between the translation units of librjprt (rjprt.hip = the C-ABI,
-// ff_scan.hip, ff_scan_inst.hip x 5, fields.hip, rrl_scan.hip, rrl_formal.hip, ...): launch
+// ff_scan.hip, ff_scan_inst.hip x 5, fields.hip, rrl_scan.hip, rrl_formal.hip, ff_grad.hip, ...): launch
 // wrappers and the small structs they exchange.  Nothing here is exported; the library's surface is include/rjprt.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -181,6 +181,16 @@ hipError_t field_range_launch(const void* d_field, int64_t n, int dtype, double*
                               hipStream_t st);
 hipError_t range_check_launch(const void* d_field, int64_t n, int dtype, double lo, double hi,
                               int* d_flag, hipStream_t st);
+
+// ---- ff_grad.hip: sensitivities to the burst parameters (K7) -----------------------------------
+size_t ff_grad_workspace_bytes(int nx, int ny, int nz, int n_epochs, int npar, int nchan);
+// d_scale[1 + npar]: 1, then per parameter the constant its plane is multiplied with (2 amp inv2s2
+// for t0, 1 for amp_rel, -amp for inv2s2); d_tavg / d_ctau / d_cflux only with ftot or dftot
+hipError_t ff_grad_run(const rjp_fields* fl, const rjp_bursts* hb, const double* epochs,
+                       int n_epochs, const double* d_scale, const double* d_tavg,
+                       const double* d_ctau, const double* d_cflux, int nchan, double* sumA,
+                       double* dsumA, double* ftot, double* dftot, double* ws, size_t work_bytes,
+                       hipStream_t st);
 
 // ---- ff_scan_inst.hip: one slice of the K1 kernel family per translation unit -------------
 #define RJP_SCAN_SLICE_ARGS                                                                  \

@@ -855,6 +855,66 @@ int rjp_ff_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* burs
                                                       d_out, st), "ff_formal_launch");
 }
 
+size_t rjp_ff_grad_workspace(int32_t nx, int32_t ny, int32_t nz, int32_t n_epochs,
+                             int32_t n_par, int32_t n_chan) {
+  if (nx <= 0 || ny <= 0 || nz <= 0 || n_epochs <= 0 || n_par <= 0 || n_chan < 0) return 0;
+  return rjp::ff_grad_workspace_bytes(nx, ny, nz, n_epochs, n_par, n_chan);
+}
+
+int rjp_ff_grad(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
+                const double* h_epochs_s, int32_t n_epochs, int32_t gff_mode,
+                const double* d_tavg, const double* h_ctau, const double* h_cflux, int32_t n_chan,
+                double* d_sumA, double* d_dsumA, double* d_ftot, double* d_dftot,
+                void* d_work, size_t work_bytes, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (!mode_ok(gff_mode)) return fail(ctx, RJP_ERR_ARG, "bad gff_mode");
+  if (!fields) return fail(ctx, RJP_ERR_ARG, "fields is NULL");
+  if (fields->dtype != RJP_F64 || !fields->d_a0 || fields->a0_mode != gff_mode)
+    return fail(ctx, RJP_ERR_ARG,
+                "rjp_ff_grad: needs RJP_F64 fields with the tau layout (d_a0) built for gff_mode");
+  if (int r = check_fields(ctx, fields, false, false, gff_mode)) return r;
+  if (!fields->d_ts) return fail(ctx, RJP_ERR_ARG, "rjp_ff_grad: fields.d_ts required");
+  if (!bursts || bursts->n[0] + bursts->n[1] <= 0 || bursts->n[0] < 0 || bursts->n[1] < 0)
+    return fail(ctx, RJP_ERR_ARG, "rjp_ff_grad: no burst to differentiate with respect to");
+  if (int r = check_bursts(ctx, bursts, fields)) return r;
+  if (bursts->n[0] > RJP_SGPR_BURSTS || bursts->n[1] > RJP_SGPR_BURSTS)
+    return fail(ctx, RJP_ERR_ARG, "rjp_ff_grad: more than 8 bursts in a jet");
+  if (!h_epochs_s || n_epochs < 1)
+    return fail(ctx, RJP_ERR_ARG, "rjp_ff_grad: NULL epochs or n_epochs < 1");
+  for (int e = 0; e < n_epochs; ++e)
+    if (!std::isfinite(h_epochs_s[e]))
+      return fail(ctx, RJP_ERR_ARG, "rjp_ff_grad: non-finite epoch");
+  const int npar = 3 * (bursts->n[0] + bursts->n[1]);
+  std::vector<double> scale(1 + npar, 1.0);
+  for (int j = 0, k = 1; j < 2; ++j)
+    for (int i = 0; i < bursts->n[j]; ++i, k += 3) {
+      const double t0 = bursts->t0[j][i], amp = bursts->amp_rel[j][i], inv = bursts->inv2s2[j][i];
+      if (!std::isfinite(t0) || !std::isfinite(amp) || !std::isfinite(inv))
+        return fail(ctx, RJP_ERR_ARG, "rjp_ff_grad: non-finite burst parameter");
+      scale[k] = 2.0 * amp * inv;
+      scale[k + 2] = -amp;
+    }
+  if (!d_sumA && !d_dsumA && !d_ftot && !d_dftot)
+    return fail(ctx, RJP_ERR_ARG, "rjp_ff_grad: all four outputs are NULL");
+  const bool totals = d_ftot || d_dftot;
+  if (totals && (!d_tavg || !h_ctau || !h_cflux || n_chan < 1))
+    return fail(ctx, RJP_ERR_ARG,
+                "rjp_ff_grad: d_ftot / d_dftot need d_tavg, the channel tables and n_chan >= 1");
+  const int nch = totals ? n_chan : 0;
+  if (!d_work || work_bytes < rjp::ff_grad_workspace_bytes(fields->nx, fields->ny, fields->nz,
+                                                           n_epochs, npar, nch))
+    return fail(ctx, RJP_ERR_WORKSPACE, "rjp_ff_grad: workspace smaller than rjp_ff_grad_workspace()");
+  hipStream_t st = (hipStream_t)stream;
+  const double* src[3] = {scale.data(), h_ctau, h_cflux};
+  const size_t len[3] = {scale.size(), (size_t)nch, (size_t)nch};
+  double* dev[3];
+  if (int r = stage_tables(ctx, st, src, len, 3, dev)) return r;
+  return finish_staged(ctx, st, rjp::ff_grad_run(fields, bursts, h_epochs_s, n_epochs, dev[0], d_tavg,
+                                                 dev[1], dev[2], nch, d_sumA, d_dsumA, d_ftot,
+                                                 d_dftot, (double*)d_work, work_bytes, st),
+                       "ff_grad_run");
+}
+
 int rjp_rrl_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
                    double time_s, int32_t gff_mode, const rjp_line* line, const double* h_nu,
                    const double* h_ctau, const double* h_csrc, const double* h_hnu_k,

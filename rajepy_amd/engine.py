@@ -971,6 +971,40 @@ class RTEngine:
             out.data_ptr(), self._stream()), self.ctx, "rjp_ff_formal")
         return out
 
+    def ff_grad(self, fields, bursts, epochs_s, gff_mode, tavg=None, ctau=None, cflux=None,
+                want_maps=False):
+        """Sensitivities to the burst parameters (rjp_ff_grad): one pass over (a0, ts) per tile of
+        epochs gives S = sum_y |a0| chi^2 and its derivatives with respect to (t0, amp_rel, inv2s2)
+        of every burst -- parameter k = 3 b + c, b counting the red jet's bursts first, then the
+        blue jet's, as `make_bursts` lists them.
+        -> (sumA[E, P], dsumA[E, n_par, P] | None, ftot[E, F] | None, dftot[E, F, n_par] | None)
+        device tensors (float64): `dsumA` only with `want_maps`, the light curves `ftot` and their
+        Jacobian `dftot` only with the channel coefficients (`tavg`, `ctau`, `cflux` as for
+        `ff_maps`).  Needs the tau layout built for `gff_mode`, at least one burst and at most 8
+        per jet; `fields.ts` is read as it is (the call applies the rule for a jet without bursts
+        itself)."""
+        E, P = len(epochs_s), fields.npix
+        nx, ny, nz = fields.shape
+        n_par = 3 * (int(bursts.n[0]) + int(bursts.n[1])) if bursts is not None else 0
+        totals = ctau is not None
+        if totals and (tavg is None or cflux is None or len(cflux) != len(ctau)):
+            raise ValueError("the light-curve Jacobian needs tavg, ctau and cflux (same length)")
+        F = len(ctau) if totals else 0
+        sumA = self._f64(E, P)
+        dsumA = self._f64(E, n_par, P) if want_maps else None
+        ftot = self._f64(E, F) if totals else None
+        dftot = self._f64(E, F, n_par) if totals else None
+        work = self._workspace(max(1, self.lib.rjp_ff_grad_workspace(nx, ny, nz, E, n_par, F)))
+        fs = fields.struct()
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        self._check(self.lib.rjp_ff_grad(
+            self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None,
+            _lib.dbl_array(epochs_s), E, int(gff_mode), ptr(tavg),
+            _lib.dbl_array(ctau) if totals else None, _lib.dbl_array(cflux) if totals else None,
+            F, ptr(sumA), ptr(dsumA), ptr(ftot), ptr(dftot), work.data_ptr(), work.numel(),
+            self._stream()), self.ctx, "rjp_ff_grad")
+        return sumA, dsumA, ftot, dftot
+
     def rrl_cells(self, fields, bursts, time_s, line, nus):
         """collapse=False: per-cell RRL optical depths -> device tensor [F, N]."""
         F = len(nus)
