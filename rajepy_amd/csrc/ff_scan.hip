@@ -197,6 +197,9 @@ __global__ __launch_bounds__(kBlock) void ff_maps_kernel(
 // once per channel and LANE, as in ff_ftot_kernel below.  Same arithmetic per (pixel, channel);
 // the totals are summed in another (fixed) order.
 constexpr int kMapsFC = 16;      // channels per workgroup (gridDim.z slices the channel axis)
+#ifndef RJP_K2_CHOUTER
+#define RJP_K2_CHOUTER 1         /* 0: a build that walks pixel group after pixel group (k outer, channels inner), for A/B only */
+#endif
 template <int VEC, bool FT, int KP>
 __global__ __launch_bounds__(kBlock) void ff_maps_acc_kernel(
     const double* __restrict__ sumA, const double* __restrict__ tavg, int64_t npix,
@@ -219,6 +222,32 @@ __global__ __launch_bounds__(kBlock) void ff_maps_acc_kernel(
     load_plain(sumA + (int64_t)e * npix + pc, A[k]);
     load_plain(tavg + pc, ta[k]);
   }
+#if RJP_K2_CHOUTER
+  // channel after channel: a lane's KP stores of a channel and cube go to ONE map back to back (a
+  // workgroup writes KP x 4 KiB of it in one burst, then leaves it for good) instead of walking
+  // the slice's kMapsFC maps KP times.  acc[j] still takes pixel group after pixel group, v after
+  // v: the totals are the k-outer order's bit for bit.
+#pragma unroll
+  for (int j = 0; j < kMapsFC; ++j) {
+    if (j < nf) {
+      const double ct = ctau[f0 + j], cf = cflux[f0 + j];
+      const int64_t o = ((int64_t)e * nchan + f0 + j) * npix;
+#pragma unroll
+      for (int k = 0; k < KP; ++k) {
+        if (pk[k] >= npix) continue;
+        double t[VEC], s[VEC];
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+          t[v] = ct * A[k][v];
+          s[v] = cf * (ta[k][v] * one_minus_exp_neg(t[v]));
+          if (FT) acc[j] += s[v] == s[v] ? s[v] : 0.0;                 // nansum
+        }
+        if (tau) store_cube(tau + o + pk[k], t);
+        if (flux) store_cube(flux + o + pk[k], s);
+      }
+    }
+  }
+#else
 #pragma unroll
   for (int k = 0; k < KP; ++k) {
     if (pk[k] >= npix) continue;
@@ -239,6 +268,7 @@ __global__ __launch_bounds__(kBlock) void ff_maps_acc_kernel(
       }
     }
   }
+#endif
   if (FT) {
     const int slot = blockIdx.x * (kBlock / RJP_WAVE) + threadIdx.x / RJP_WAVE;
 #pragma unroll

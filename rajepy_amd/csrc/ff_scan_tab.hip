@@ -225,14 +225,20 @@ __global__ __launch_bounds__(kBlock) void ff_scan_table_kernel(
 // only the bins [b0, b1) that meet the support at this epoch are read -- in every lane one run of
 // rows, [start(b0), start(b1)) -- and the |a0| sums of the other bins (prefix sums kept with the
 // layout) stand for the rest.  The wave streams the rows from the smallest start to the largest
-// end over its lanes, a lane masking the rows outside its own run; lanes are padded at their end
-// only, so the runs of a group line up to the Poisson noise of the counts.  The cells in the layout
+// end over its lanes, a lane loading (and summing) the rows of its own run only; lanes are padded
+// at their end only, so the runs of a group line up to the Poisson noise of the counts.  The cells in the layout
 // are finite and non-zero with a finite launch time inside [ts_lo, ts_hi] (the build checked the
 // range); the dropped ones come back through aux as in the launch-time-ordered sweep: a NaN launch
 // time counts with chi = 1 when its jet has no bursts (what rjp_unmask_launch_times gives the
 // grid-order scan), an infinite weight makes the sightline +inf.
 #ifndef RJP_SRT_U
 #define RJP_SRT_U 8              /* rows of 16-byte loads in flight per lane */
+#endif
+#ifndef RJP_SRT_DIAG
+#define RJP_SRT_DIAG 1           /* 0: a build whose hybrid scan keeps no bin counters (rjp_last_srt_bins then reads stale slots), for A/B only */
+#endif
+#ifndef RJP_SRT_OWNROWS
+#define RJP_SRT_OWNROWS 1        /* 0: a build in which every lane loads every row of its wave's window, for A/B only */
 #endif
 constexpr int kSrtBlock = 512;   // 8 groups per workgroup: 512 workgroups at cfg4, one round
 struct SrtDev {
@@ -294,8 +300,15 @@ __global__ __launch_bounds__(kSrtBlock) void ff_scan_sorted_kernel(SrtDev s, Chi
       rjp_d2 cl[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
+#if RJP_SRT_OWNROWS
+        // a lane loads the rows of its own run only (see ff_scan_hybrid_kernel)
+        cl[u] = rjp_d2{0.0, 0.0};
+        if (r + u >= rs && r + u < re)
+          cl[u] = __builtin_nontemporal_load(base + (int64_t)(r + u) * RJP_WAVE);
+#else
         const int rr = r + u < hi ? r + u : hi - 1;    // (never past the wave's last row)
         cl[u] = __builtin_nontemporal_load(base + (int64_t)rr * RJP_WAVE);
+#endif
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -312,8 +325,12 @@ __global__ __launch_bounds__(kSrtBlock) void ff_scan_sorted_kernel(SrtDev s, Chi
         chi = __builtin_fma(chi, xi, c23.x);
         chi = __builtin_fma(chi, xi, c01.y);
         chi = __builtin_fma(chi, xi, c01.x);
+#if RJP_SRT_OWNROWS
+        acc = __builtin_fma(cl[u].x, chi * chi, acc);      // (a row outside the run: weight 0.0)
+#else
         const bool mine = r + u >= rs && r + u < re;
         acc = __builtin_fma(mine ? cl[u].x : 0.0, chi * chi, acc);
+#endif
       }
     }
     total += acc + skipped;
@@ -368,7 +385,6 @@ struct SrtCoefDev {
   int b0[2], b1[2];                            // the bins in each jet's support (SrtPlan)
   double* W;                                   // [2 K][N]
   int* ok;                                     // [2 K]: 0 = read the bin, else the coefficients to sum
-  unsigned long long* diag;                    // zeroed here for the scan behind, or null
 };
 
 __device__ __forceinline__ double chi_exact(const double* bj, int nb, double tl) {
@@ -389,7 +405,6 @@ __global__ __launch_bounds__(kSrtCoefThreads) void srt_coef_kernel(const double*
   __shared__ double sF[kSrtMaxN], sW[kSrtMaxN], sFc[4 * kSrtMaxN];
   const int q = blockIdx.x, i = threadIdx.x;
   const int j = q / c.K, k = q - j * c.K;
-  if (q == 0 && c.diag && i < 2) c.diag[i] = 0ull;
   if (k < c.b0[j] || k >= c.b1[j]) {
     if (i == 0) c.ok[q] = 0;
     return;
@@ -476,7 +491,10 @@ struct SrtMomDev {
   const double* mom;                           // [2 K (N - 1)][P]
   const double* W;                             // [2 K][N]
   const int* ok;                               // [2 K]: 0 = read the bin, else the coefficients to sum
-  unsigned long long* diag;                    // += (contracted, read) (group, jet, bin) triples
+  // (contracted, read) (jet, bin) pairs of every group, [groups][2], or null: lane 0 of a group's
+  // wave stores its own pair, zeros included -- every slot of a scan is written by that scan,
+  // nothing is zeroed in front of it and no two waves share a word
+  unsigned long long* diag;
 };
 
 template <int U, int N>
@@ -638,8 +656,16 @@ __global__ __launch_bounds__(kSrtBlock) __attribute__((amdgpu_waves_per_eu(4))) 
         rjp_d2 cl[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
+#if RJP_SRT_OWNROWS
+          // a lane loads the rows of its own run only: a row outside it is never fetched for the
+          // lane, and nothing that row holds (a NaN included) can reach the lane's sum
+          cl[u] = rjp_d2{0.0, 0.0};
+          if (r + u >= rs && r + u < re)
+            cl[u] = __builtin_nontemporal_load(base + (int64_t)(r + u) * RJP_WAVE);
+#else
           const int rr = r + u < hi ? r + u : hi - 1;  // (never past the wave's last row)
           cl[u] = __builtin_nontemporal_load(base + (int64_t)rr * RJP_WAVE);
+#endif
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -656,18 +682,24 @@ __global__ __launch_bounds__(kSrtBlock) __attribute__((amdgpu_waves_per_eu(4))) 
           chi = __builtin_fma(chi, xi, c23.x);
           chi = __builtin_fma(chi, xi, c01.y);
           chi = __builtin_fma(chi, xi, c01.x);
+#if RJP_SRT_OWNROWS
+          acc = __builtin_fma(cl[u].x, chi * chi, acc);      // (a row outside the run: weight 0.0)
+#else
           const bool mine = r + u >= rs && r + u < re;
           acc = __builtin_fma(mine ? cl[u].x : 0.0, chi * chi, acc);
+#endif
         }
       }
       b = e;
     }
     total += acc + skipped;
   }
-  if (m.diag && lane == 0 && (n_con | n_read)) {
-    atomicAdd(&m.diag[0], (unsigned long long)n_con);
-    atomicAdd(&m.diag[1], (unsigned long long)n_read);
+#if RJP_SRT_DIAG
+  if (m.diag && lane == 0) {
+    m.diag[2 * g] = (unsigned long long)n_con;
+    m.diag[2 * g + 1] = (unsigned long long)n_read;
   }
+#endif
 #if RJP_SRT_PAIR
   // both halves of the planes, then sightline l from the pair of lane l / 2 (all lanes are here)
   pacc.x += __shfl_xor(pacc.x, 32, RJP_WAVE);
@@ -1051,7 +1083,7 @@ hipError_t chi_table_scan(const rjp_fields* fl, const ChiPlan& cp, const double*
     double* d_W = ws;
     int* d_ok = reinterpret_cast<int*>(ws + (size_t)2 * K * N);
     const SrtCoefDev c{fl->ts_lo, fl->ts_hi > fl->ts_lo ? K / (fl->ts_hi - fl->ts_lo) : 1.0, K, N,
-                       {sp->b0[0], sp->b0[1]}, {sp->b1[0], sp->b1[1]}, d_W, d_ok, sp->diag};
+                       {sp->b0[0], sp->b0[1]}, {sp->b1[0], sp->b1[1]}, d_W, d_ok};
     hipLaunchKernelGGL(srt_coef_kernel, dim3((unsigned)(2 * K)), dim3(kSrtCoefThreads), 0, st,
                        d_stage, cp.n[0], cp.n[1], t, t_epoch, (const double*)d_tab, c);
     e = hipGetLastError();

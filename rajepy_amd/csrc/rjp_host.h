@@ -90,7 +90,7 @@ struct SrtPlan {
   double share = 0.0;             // the map's cells in those bins / all cells in the layout
   // Chebyshev moments of the layout attached (rjp_fields.d_srt_mom): their order N, else 0.  The
   // bins in the support whose chi^2 the degree-(N-1) interpolant matches are contracted from them
-  unsigned long long* diag = nullptr;   // (contracted, read) bin counters of the scan, or null
+  unsigned long long* diag = nullptr;   // (contracted, read) bin counters of the scan, a pair per group, or null
   int N = 0;
 };
 // false: no layout attached, or too large a share of it would be read (the grid order is as fast)

@@ -46,7 +46,11 @@ struct rjp_ctx {
   int* guard = nullptr;
   unsigned long long* d_count = nullptr;      // device word of rjp_occupied_cells
   unsigned long long* d_srt_hist = nullptr;   // RJP_SRT_MAX_K * 2 counters of rjp_srt_count
-  unsigned long long* d_srt_diag = nullptr;   // (contracted, read) bins of rjp_last_srt_bins
+  // (contracted, read) bins of rjp_last_srt_bins: one pair per group of 64 sightlines, written
+  // by the group's wave with plain stores (ff_scan_hybrid_kernel); grown when a scan has more
+  // groups than it holds.  `srt_diag_groups`: the pairs the last such scan wrote.
+  unsigned long long* d_srt_diag = nullptr;
+  int64_t srt_diag_cap = 0, srt_diag_groups = 0;
   struct RangeKey {
     const void* d_ts = nullptr;
     int64_t n = 0;
@@ -502,9 +506,20 @@ static int ff_scan_impl(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts
     const bool srt = !ctx->chi.wide && !d_em && rjp::srt_plan(fields, bursts, h_epochs_s[0], sp);
     ctx->last_layout = srt ? 1 : 0;
     if (srt && sp.N > 0) {
-      // (once per context: the bin counters of rjp_last_srt_bins, zeroed by every such scan)
-      if (!ctx->d_srt_diag)
-        RJP_HIP(ctx, hipMalloc((void**)&ctx->d_srt_diag, 2 * sizeof(unsigned long long)));
+      // the bin counters of rjp_last_srt_bins, a pair per group: every pair is stored by the scan
+      // itself, so nothing is zeroed.  Growing it (a larger map than any before on this context)
+      // costs a hipFree, which synchronises the whole device and so also waits for a scan that
+      // still writes the old buffer: accepted for a diagnostic, it happens once per map size
+      const int64_t groups = ((int64_t)fields->nx * fields->nz + 63) / 64;
+      if (groups > ctx->srt_diag_cap) {
+        if (ctx->d_srt_diag) RJP_HIP(ctx, hipFree(ctx->d_srt_diag));
+        ctx->d_srt_diag = nullptr;
+        ctx->srt_diag_cap = 0;
+        RJP_HIP(ctx, hipMalloc((void**)&ctx->d_srt_diag,
+                               (size_t)groups * 2 * sizeof(unsigned long long)));
+        ctx->srt_diag_cap = groups;
+      }
+      ctx->srt_diag_groups = groups;
       sp.diag = ctx->d_srt_diag;
       ctx->last_srt_mom = true;
     }
@@ -574,11 +589,17 @@ int rjp_last_srt_bins(rjp_ctx* ctx, int64_t* contracted, int64_t* read) {
   if (!contracted || !read) return fail(ctx, RJP_ERR_ARG, "rjp_last_srt_bins: NULL output");
   *contracted = *read = 0;
   if (!ctx->last_srt_mom) return RJP_OK;
-  unsigned long long h[2] = {0, 0};
+  std::vector<unsigned long long> h((size_t)ctx->srt_diag_groups * 2);
   RJP_HIP(ctx, hipDeviceSynchronize());
-  RJP_HIP(ctx, hipMemcpy(h, ctx->d_srt_diag, sizeof(h), hipMemcpyDeviceToHost));
-  *contracted = (int64_t)h[0];
-  *read = (int64_t)h[1];
+  RJP_HIP(ctx, hipMemcpy(h.data(), ctx->d_srt_diag, h.size() * sizeof(unsigned long long),
+                         hipMemcpyDeviceToHost));
+  int64_t con = 0, rd = 0;
+  for (size_t g = 0; g < h.size(); g += 2) {
+    con += (int64_t)h[g];
+    rd += (int64_t)h[g + 1];
+  }
+  *contracted = con;
+  *read = rd;
   return RJP_OK;
 }
 

@@ -10,7 +10,9 @@ the first named build's.
         trunc=rajepy_amd/librjprt_trunc.so pair=rajepy_amd/librjprt_pair.so
 
 (the default build takes part as "new"; the variants are builds with -DRJP_SRT_PAIR=0 /
--DRJP_SRT_TRUNC=0, see ff_scan_tab.hip)
+-DRJP_SRT_TRUNC=0 / -DRJP_SRT_DIAG=0 / -DRJP_SRT_OWNROWS=0, see ff_scan_tab.hip; a build without
+the counters, RJP_SRT_DIAG=0, reports whatever its slots held; --no-moments times the moment-free
+ff_scan_sorted_kernel of every build instead)
 """
 import argparse
 import ctypes as C
@@ -36,6 +38,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--rounds", type=int, default=6)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--no-moments", action="store_true",
+                    help="scan without the layout's moments: every build runs ff_scan_sorted_kernel")
     args = ap.parse_args()
     eng = E.RTEngine(0)
     mode = E.RJP_GFF_SCALAR
@@ -58,8 +62,9 @@ def main():
     nx, ny, nz = SHAPE
     P = fields.npix
     work = eng._workspace(eng.lib.rjp_ff_scan_workspace(nx, ny, nz, 1))
+    eng.use_srt_moments = not args.no_moments
     fs = eng._scan_struct(fields, bursts, 1)
-    res = {"shape": SHAPE, "K": fields.srt["K"], "N": fields.srt["N"], "reps": args.reps,
+    res = {"shape": SHAPE, "K": fields.srt["K"], "N": int(fs.srt_N), "reps": args.reps,
            "rounds": args.rounds, "epochs": {}}
     for years in (1.0, 0.3, 2.6):
         ep = _lib.dbl_array([years * orc.YEAR])
