@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define RJP_VERSION 115          /* 0.1.15 */
+#define RJP_VERSION 116          /* 0.1.16 */
 #define RJP_RANGE_BLOCKS 2048    /* partial (min, max) pairs rjp_field_range writes */
 #define RJP_MAX_EPOCH_TILE 32    /* most epochs evaluated per grid pass: 32 uniformly spaced ones (with or without d_em), 16 when only 16-31 are left, else tiles of 8, 4, 2, 1 */
 
@@ -482,6 +482,34 @@ int rjp_rrl_cells(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* burs
 int rjp_ff_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
                   double time_s, int32_t gff_mode, const double* h_ctau, const double* h_csrc,
                   int32_t n_chan, double* d_out, void* stream);
+
+/* ---- K8: light curves and map sweeps by the formal solution ------------------------------------
+ * The reference's light curves loop over `time` and sum a flux_ff map per epoch (Pipeline results,
+ * classes.py:2461-2467, with the isothermal maps of classes.py:1466-1541); with rjp_ff_formal that
+ * is one call, one [F, P] map and one host-side nansum per epoch.  This entry point walks the
+ * fields ONCE for all epochs:
+ *   d_out [(e * F + f) * P + p]   rjp_ff_formal's map at time h_epochs_s[e]          (or NULL)
+ *   d_ftot[e * F + f]             nansum_p of that map: a pixel whose sightline has no T > 0 is
+ *                                 NaN in the map and adds nothing                     (or NULL)
+ * The burst factor is evaluated once per (cell, epoch) whatever the number of channels; with d_out
+ * NULL no map touches memory.  Every map equals rjp_ff_formal's at that epoch BIT FOR BIT on the
+ * same fields (tau, compact or wide layout, RJP_F32 or RJP_F64, any number of bursts or none): the
+ * two kernels share the code that forms b and each (sightline, epoch, channel) value is one
+ * sequential chain.  The totals are summed in a fixed order without floating-point atomics: a
+ * repeated call, or a call with d_out NULL, gives the same bits.  Epochs need not be sorted, evenly
+ * spaced or distinct.  h_ctau / h_csrc, the observer side, d_ylo / d_yhi: as rjp_ff_formal; the
+ * launch-time range, the layouts ordered by launch time and the moment cache are not used.
+ * d_work (rjp_ff_formal_sweep_workspace bytes; 0 from it = a bad argument) is needed with d_ftot
+ * only.  Every argument is validated before anything is enqueued: RJP_ERR_ARG for a bad gff_mode,
+ * NULL tables, n_epochs < 1, n_chan < 1, a non-finite epoch, both outputs NULL, or bursts without
+ * d_ts; RJP_ERR_WORKSPACE for a d_work smaller than rjp_ff_formal_sweep_workspace(). */
+size_t rjp_ff_formal_sweep_workspace(int32_t nx, int32_t ny, int32_t nz, int32_t n_epochs,
+                                     int32_t n_chan);
+int rjp_ff_formal_sweep(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
+                        const double* h_epochs_s, int32_t n_epochs, int32_t gff_mode,
+                        const double* h_ctau, const double* h_csrc, int32_t n_chan,
+                        double* d_out, double* d_ftot, void* d_work, size_t work_bytes,
+                        void* stream);
 
 /* ---- K7: sensitivities of the light curves to the ejection-burst parameters --------------------
  * Generalises the burst factor of number_density (classes.py:861-875), the y-reduction of

@@ -18,7 +18,7 @@ RJP_F32, RJP_F64 = 4, 8
 RJP_GFF_SCALAR, RJP_GFF_POWERLAW = 0, 1
 RJP_MAX_EPOCH_TILE = 32
 RJP_RANGE_BLOCKS = 2048
-RJP_VERSION = 115             # include/rjprt.h; the binding below matches exactly this ABI
+RJP_VERSION = 116             # include/rjprt.h; the binding below matches exactly this ABI
 RJP_OK = 0
 RJP_ERR_ARG, RJP_ERR_HIP, RJP_ERR_NODEVICE, RJP_ERR_WORKSPACE, RJP_ERR_DEGENERATE = \
     -1, -2, -3, -4, -5
@@ -129,6 +129,10 @@ SIGNATURES = {
                                _DP, C.c_int32, _P, _P]),
     "rjp_ff_formal": (C.c_int, [_P, C.POINTER(Fields), C.POINTER(Bursts), C.c_double, C.c_int32,
                                 _DP, _DP, C.c_int32, _P, _P]),
+    "rjp_ff_formal_sweep_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                   C.c_int32]),
+    "rjp_ff_formal_sweep": (C.c_int, [_P, C.POINTER(Fields), C.POINTER(Bursts), _DP, C.c_int32,
+                                      C.c_int32, _DP, _DP, C.c_int32, _P, _P, _P, C.c_size_t, _P]),
     "rjp_ff_grad_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_int32]),
     "rjp_ff_grad": (C.c_int, [_P, C.POINTER(Fields), C.POINTER(Bursts), _DP, C.c_int32, C.c_int32,

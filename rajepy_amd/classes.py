@@ -669,7 +669,7 @@ class JetModel:
         arr = _to_host(out).reshape(len(freqs), self.nx, self.ny, self.nz)
         return arr[0] if scalar else arr
 
-    def flux_vs_time(self, times_s, freq):
+    def flux_vs_time(self, times_s, freq, formal=False):
         """Light curves: total flux density [Jy] of the whole map at every (model time,
         frequency) -> array (len(times), len(freq)).  The reference gets these numbers by
         looping `time` and summing `flux_ff` maps (Pipeline results, classes.py:2461-2467);
@@ -679,11 +679,17 @@ class JetModel:
         >= 12 epochs (1280 doubles per sightline: 2.7 GB at 512 x 512 sightlines) so that later
         sweeps -- other epochs, other burst parameters -- are contractions only; a pipeline that
         holds many such models sets `model.engine.cache_moments = False` (every sweep then makes
-        its own pass over the grid), and a setter that replaces a field drops the maps."""
+        its own pass over the grid), and a setter that replaces a field drops the maps.
+        `formal=True`: every flux by the formal solution along the line of sight (the per-epoch
+        `nansum(flux_ff(freq, formal=True))`), all epochs of a rank in one walk of the grid
+        (`RTEngine.ff_formal_sweep`).  It equals the default curve where the temperature is
+        constant along every sightline (q_T = q^d_T = 0) and differs wherever it varies -- by more
+        than 1e-3 on a model with a temperature gradient; no cached state is involved (neither
+        T_avg nor the moment maps are read or kept)."""
         from . import parallel
         rank, world, _ = _dist_info()
         return parallel.sweep_flux_vs_time(self, np.atleast_1d(np.asarray(times_s, float)),
-                                           freq, rank=rank, world=world)
+                                           freq, rank=rank, world=world, formal=bool(formal))
 
     def _ejection_slots(self):
         """Per ejection, in the order of `self.ejections`: (first kernel parameter k = 3 b of its

@@ -1,0 +1,264 @@
+// K8: epoch sweeps of the formal solution along the line of sight -- the maps of K5 (ff_formal.hip)
+// at E epochs and their per-channel totals (light curves) from ONE pass over the fields.
+//
+//   out[e, f, p] = csrc[f] sum_i T_i (1 - e^-dtau_i) exp(-sum_{j in front of i} dtau_j),
+//   dtau_i = ctau[f] b_i(e),  b_i(e) = |a0_i| chi_i(t_e - ts_i)^2,     ftot[e, f] = nansum_p out
+//
+// K5's tile and walk with the lane axis turned from channels to EPOCHS (light curves have 1-8
+// channels and tens to hundreds of epochs): a 256-thread workgroup owns ZT = 16 z-adjacent
+// sightlines of one x-row, LE epochs (lanes; G = 256 / LE sightline groups, NZP = 16 / G sightlines
+// per thread) and a register block of FC channels.
+//   phase 1  one thread per cell of a slab of YC y-rows stages what does not depend on the epoch:
+//            the signed a (|a0| as formal_a forms it for the layout, jet flag in the sign), T, ts;
+//   phase 2  every lane walks the slab's rows in increasing iy for its sightlines: per cell
+//            b = a chi^2(t_e - ts) ONCE, then for each channel of the block K5's statements
+//            om = 1 - e^(-ctau b), I += T om Theta, Theta -= Theta om.
+// LE = 64: the lanes of a wave look at the same cell (LDS broadcast), so the cell's jet is
+// wave-uniform -- the burst parameters are scalar operands (chi_jet) and a dead cell (a == 0) is
+// skipped by the whole wave.  LE = 16: four sightlines per wave, chi_cell's per-lane select.
+// chi is evaluated once per (cell, epoch) however many channels there are; channels beyond FC go
+// to further workgroups (gridDim.y), which repeat it.  Epochs: blocks of 64 lanes, the tail by
+// blocks of 16 unless it fills more than three of them -- the only dead lanes are the last
+// block's.
+// b comes from the code K5 uses (ff_formal.h) and the recurrence is K5's statement for statement:
+// each (sightline, epoch, channel) value is one sequential chain that no layout reorders, so every
+// map equals rjp_ff_formal's at that epoch bit for bit.
+// Totals: the tile's values pass through LDS ([epoch][sightline]); one thread per epoch adds its 16
+// sightlines in a fixed order (NaN pixels add nothing, as nansum) to one partial per (epoch,
+// channel, workgroup), and sum_partials_launch finishes.  No floating-point atomics.  The same
+// transpose makes the map stores 128-byte runs along z.
+#include "ff_formal.h"
+
+namespace rjp {
+
+#ifndef RJP_FORMAL_WAVES
+#define RJP_FORMAL_WAVES 4      /* 128-VGPR budget */
+#endif
+
+template <typename T, int LAY, int LE, int FC>
+__global__ __launch_bounds__(kFB, RJP_FORMAL_WAVES) void ff_formal_sweep_kernel(
+    FormalFields<T> f, int nx, int ny, int nz, int mode, BurstsDev bd,
+    const double* __restrict__ epochs, int e_lo, int e_hi,
+    const double* __restrict__ ctau, const double* __restrict__ csrc, int nchan,
+    double* __restrict__ out, double* __restrict__ part) {
+  using TL = FormalTile<LE>;
+  constexpr int ZT = TL::ZT, YC = TL::YC, NZP = TL::NZP;
+  static_assert(ZT % TL::G == 0 && ZT == 16, "tile/group mismatch");
+
+  __shared__ rjp_d2 s_at[kFB];      // (signed a, T) of the slab's cells, [row * ZT + sightline]
+  __shared__ double s_ts[kFB];      // their launch times
+  __shared__ double s_x[LE * ZT];   // one channel's pixel values of the tile, [epoch lane][sightline]
+  __shared__ int s_hot[ZT];         // the sightline has a cell with T > 0 (T_avg is not NaN)
+
+  const int ntz = (nz + ZT - 1) / ZT;
+  const int x = (int)blockIdx.x / ntz;
+  const int z0 = ((int)blockIdx.x - x * ntz) * ZT;
+  const int tid = threadIdx.x;
+  const int el = tid % LE;
+  const int g = tid / LE;
+  const int e_blk = e_lo + (int)blockIdx.z * LE;     // first epoch of this workgroup
+  const int ei = e_blk + el;
+  const double te = ei < e_hi ? epochs[ei] : 0.0;    // (a dead lane walks epoch 0 s and stores nothing)
+  const int f0 = (int)blockIdx.y * FC;
+  const int nf = nchan - f0 < FC ? nchan - f0 : FC;  // live channels of the block (workgroup-uniform)
+  double ct[FC];
+#pragma unroll
+  for (int k = 0; k < FC; ++k) ct[k] = k < nf ? ctau[f0 + k] : 0.0;
+  const int cy = tid / ZT, cz = tid % ZT;            // this thread's cell in the slab (phase 1)
+  const int cb = g * NZP;                            // first sightline of this thread (phase 2)
+
+  if (tid < ZT) s_hot[tid] = 0;
+  __syncthreads();
+  int ya = 0, ye = ny;
+  if (f.ylo) {
+    // sparse models: only the rows inside the tile's occupied y-range
+    __shared__ int s_lo, s_hi;
+    if (tid == 0) { s_lo = ny; s_hi = 0; }
+    __syncthreads();
+    if (tid < ZT && z0 + tid < nz) {
+      const int64_t p = (int64_t)x * nz + z0 + tid;
+      const int lo = f.ylo[p], hi = f.yhi[p];
+      if (lo < hi) { atomicMin(&s_lo, lo); atomicMax(&s_hi, hi); }
+    }
+    __syncthreads();
+    ya = s_lo;
+    ye = s_hi;
+  }
+
+  double I[NZP][FC], Th[NZP][FC];
+#pragma unroll
+  for (int j = 0; j < NZP; ++j)
+#pragma unroll
+    for (int k = 0; k < FC; ++k) { I[j][k] = 0.0; Th[j][k] = 1.0; }
+
+  for (int yb = ya; yb < ye; yb += YC) {
+    // ---- phase 1: signed a, T and ts of one cell per thread ----------------------------------
+    {
+      const int yy = yb + cy, zz = z0 + cz;
+      double sa = 0.0, tk = 0.0, ts = 0.0;
+      if (yy < ye && zz < nz) {
+        const int64_t o = ((int64_t)x * ny + yy) * nz + zz;
+        tk = (double)f.temp[o];
+        if (tk > 0.0) s_hot[cz] = 1;                  // (every writer stores the same value)
+        bool red;
+        const double a = formal_a<T, LAY>(f, o, mode, tk, red);
+        sa = red ? -a : a;
+        if (f.ts) ts = (double)f.ts[o];               // (null without bursts: chi = 1 whatever ts)
+      }
+      rjp_d2 v;
+      v.x = sa;
+      v.y = tk;
+      s_at[tid] = v;
+      s_ts[tid] = ts;
+    }
+    __syncthreads();
+
+    // ---- phase 2: lanes over epochs, rows front to back ---------------------------------------
+#pragma unroll 1
+    for (int r = 0; r < YC; ++r) {
+#pragma unroll
+      for (int j = 0; j < NZP; ++j) {
+        const int ci = r * ZT + cb + j;
+        const rjp_d2 c = s_at[ci];
+        if (!(c.x != 0.0)) continue;                  // a dead cell (wave-uniform for LE = 64)
+        const double tl = te - s_ts[ci];
+        double chi;
+        if constexpr (LE >= RJP_WAVE) {
+          const int jet = (int)__builtin_amdgcn_readfirstlane(hi_dword(c.x)) < 0 ? 0 : 1;
+          chi = chi_jet(bd, jet, tl);
+        } else {
+          chi = chi_cell(bd, signbit_d(c.x), tl);
+        }
+        const double b = formal_live(formal_weigh(fabs(c.x), chi));
+        const double tk = b != 0.0 ? c.y : 0.0;       // a dead cell adds T * 0 = 0, not NaN
+#pragma unroll
+        for (int k = 0; k < FC; ++k) {
+          if (k < nf) {
+            const double om = one_minus_exp_neg(ct[k] * b);
+            I[j][k] = __builtin_fma(tk * om, Th[j][k], I[j][k]);
+            Th[j][k] = __builtin_fma(-Th[j][k], om, Th[j][k]);
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+  // ---- the tile's maps and its share of the totals, one channel at a time -----------------------
+  const int ne = e_hi - e_blk < LE ? e_hi - e_blk : LE;        // live epochs of this workgroup
+  const int64_t npix = (int64_t)nx * nz;
+#pragma unroll
+  for (int k = 0; k < FC; ++k) {
+    if (k < nf) {
+      const double cs = csrc[f0 + k];
+#pragma unroll
+      for (int j = 0; j < NZP; ++j)
+        s_x[el * ZT + cb + j] =
+            (z0 + cb + j < nz && s_hot[cb + j]) ? cs * I[j][k] : __builtin_nan("");
+      __syncthreads();
+      if (out) {
+        for (int i = tid; i < ne * ZT; i += kFB) {
+          const int zz = z0 + i % ZT;
+          if (zz < nz)
+            out[((int64_t)(e_blk + i / ZT) * nchan + f0 + k) * npix + (int64_t)x * nz + zz] = s_x[i];
+        }
+      }
+      if (part && tid < ne) {
+        double tot = 0.0;
+        for (int zz = 0; zz < ZT; ++zz) {
+          const double v = s_x[tid * ZT + zz];
+          tot += v == v ? v : 0.0;
+        }
+        part[((int64_t)(e_blk + tid) * nchan + f0 + k) * gridDim.x + blockIdx.x] = tot;
+      }
+      __syncthreads();
+    }
+  }
+}
+
+size_t ff_formal_sweep_workspace_bytes(int nx, int nz, int n_epochs, int n_chan) {
+  // one partial per (epoch, channel, workgroup of 16 sightlines)
+  const size_t nwg = (size_t)nx * (size_t)((nz + 15) / 16);
+  return nwg * (size_t)n_epochs * (size_t)n_chan * sizeof(double) + 256;
+}
+
+namespace {
+
+struct SweepArgs {
+  const rjp_fields* fl;
+  int mode;
+  BurstsDev b;
+  const double* epochs;
+  int n_epochs;
+  const double *ctau, *csrc;
+  int nchan;
+  double *out, *part;
+  hipStream_t st;
+};
+
+template <typename T, int LAY, int LE, int FC>
+hipError_t sweep_launch_t(const FormalFields<T>& f, const SweepArgs& a, int e_lo, int e_hi) {
+  const int ntz = (a.fl->nz + FormalTile<LE>::ZT - 1) / FormalTile<LE>::ZT;
+  const dim3 grid((unsigned)((int64_t)a.fl->nx * ntz), (unsigned)((a.nchan + FC - 1) / FC),
+                  (unsigned)((e_hi - e_lo + LE - 1) / LE));
+  hipLaunchKernelGGL((ff_formal_sweep_kernel<T, LAY, LE, FC>), grid, dim3(kFB), 0, a.st, f,
+                     a.fl->nx, a.fl->ny, a.fl->nz, a.mode, a.b, a.epochs, e_lo, e_hi, a.ctau,
+                     a.csrc, a.nchan, a.out, a.part);
+  return hipGetLastError();
+}
+
+// channel block: every channel in registers up to 2 channels, blocks of 4 beyond
+template <typename T, int LAY, int LE>
+hipError_t sweep_launch_fc(const FormalFields<T>& f, const SweepArgs& a, int e_lo, int e_hi) {
+  if (a.nchan == 1) return sweep_launch_t<T, LAY, LE, 1>(f, a, e_lo, e_hi);
+  if (a.nchan == 2) return sweep_launch_t<T, LAY, LE, 2>(f, a, e_lo, e_hi);
+  return sweep_launch_t<T, LAY, LE, 4>(f, a, e_lo, e_hi);
+}
+
+// epoch lanes: blocks of 64 while they are full; a tail of up to 48 epochs by blocks of 16
+template <typename T, int LAY>
+hipError_t sweep_launch_le(const FormalFields<T>& f, const SweepArgs& a) {
+  int n64 = a.n_epochs / RJP_WAVE * RJP_WAVE;
+  if (a.n_epochs - n64 > 48) n64 = a.n_epochs;
+  if (n64 > 0) {
+    const hipError_t e = sweep_launch_fc<T, LAY, 64>(f, a, 0, n64);
+    if (e != hipSuccess) return e;
+  }
+  if (n64 < a.n_epochs) return sweep_launch_fc<T, LAY, 16>(f, a, n64, a.n_epochs);
+  return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t ff_formal_sweep_launch(const rjp_fields* fl, const rjp_bursts* hb, const double* d_ext,
+                                  const double* d_epochs, int n_epochs, int mode,
+                                  const double* d_ctau, const double* d_csrc, int nchan,
+                                  double* out, double* ftot, double* part, hipStream_t st) {
+  SweepArgs a{fl, mode, {}, d_epochs, n_epochs, d_ctau, d_csrc, nchan, out, ftot ? part : nullptr, st};
+  const bool bursts = bursts_to_dev(hb, a.b, d_ext);
+  if (bursts && !fl->d_ts) return hipErrorInvalidValue;
+  const void* ts = bursts ? fl->d_ts : nullptr;
+  const bool tau = fl->d_a0 && fl->dtype == RJP_F64 && fl->a0_mode == mode;
+  hipError_t e;
+  if (fl->dtype == RJP_F64) {
+    using T = double;
+    FormalFields<T> f{(const T*)fl->d_nd, (const T*)fl->d_xi, (const T*)fl->d_temp,
+                      (const T*)fl->d_pf, (const T*)ts, (const T*)fl->d_em0,
+                      (const double*)fl->d_a0, fl->d_ylo, fl->d_yhi};
+    if (tau) e = sweep_launch_le<T, LAY_TAU>(f, a);
+    else if (fl->d_em0) e = sweep_launch_le<T, LAY_CMP>(f, a);
+    else e = sweep_launch_le<T, LAY_WIDE>(f, a);
+  } else {
+    using T = float;
+    FormalFields<T> f{(const T*)fl->d_nd, (const T*)fl->d_xi, (const T*)fl->d_temp,
+                      (const T*)fl->d_pf, (const T*)ts, (const T*)fl->d_em0, nullptr,
+                      fl->d_ylo, fl->d_yhi};
+    if (fl->d_em0) e = sweep_launch_le<T, LAY_CMP>(f, a);
+    else e = sweep_launch_le<T, LAY_WIDE>(f, a);
+  }
+  if (e != hipSuccess || !ftot) return e;
+  const int nwg = fl->nx * ((fl->nz + 15) / 16);
+  return sum_partials_launch(part, n_epochs * nchan, nwg, ftot, st);
+}
+
+}  // namespace rjp

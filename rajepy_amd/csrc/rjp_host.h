@@ -1,5 +1,6 @@
 // Host-side interface between the translation units of librjprt (rjprt.hip = the C-ABI,
-// ff_scan.hip, ff_scan_inst.hip x 5, fields.hip, rrl_scan.hip, rrl_formal.hip, ff_grad.hip, ...): launch
+// ff_scan.hip, ff_scan_inst.hip x 5, fields.hip, rrl_scan.hip, rrl_formal.hip, ff_grad.hip,
+// ff_formal_sweep.hip, ...): launch
 // wrappers and the small structs they exchange.  Nothing here is exported; the library's surface is include/rjprt.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -57,6 +58,13 @@ hipError_t ff_cells_launch(const rjp_fields* fl, const rjp_bursts* hb, const dou
 hipError_t ff_formal_launch(const rjp_fields* fl, const rjp_bursts* hb, const double* d_ext,
                             double time_s, int mode, const double* d_ctau, const double* d_csrc,
                             int nchan, double* out, hipStream_t st);
+// ff_formal_sweep.hip: K5's maps at E epochs and their totals from one pass (K8), out[E * F * P]
+// and / or ftot[E * F]; `part` (ff_formal_sweep_workspace_bytes) only with ftot
+size_t ff_formal_sweep_workspace_bytes(int nx, int nz, int n_epochs, int n_chan);
+hipError_t ff_formal_sweep_launch(const rjp_fields* fl, const rjp_bursts* hb, const double* d_ext,
+                                  const double* d_epochs, int n_epochs, int mode,
+                                  const double* d_ctau, const double* d_csrc, int nchan,
+                                  double* out, double* ftot, double* part, hipStream_t st);
 size_t ff_maps_workspace_bytes(int64_t npix, int n_epochs, int n_chan);
 hipError_t ff_maps_launch(const double* sumA, const double* tavg, int64_t npix, int n_epochs,
                           const double* d_ctau, const double* d_cflux, int n_chan, double* tau,

@@ -876,6 +876,51 @@ int rjp_ff_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* burs
                                                       d_out, st), "ff_formal_launch");
 }
 
+size_t rjp_ff_formal_sweep_workspace(int32_t nx, int32_t ny, int32_t nz, int32_t n_epochs,
+                                     int32_t n_chan) {
+  if (nx <= 0 || ny <= 0 || nz <= 0 || n_epochs <= 0 || n_chan <= 0) return 0;
+  return rjp::ff_formal_sweep_workspace_bytes(nx, nz, n_epochs, n_chan);
+}
+
+int rjp_ff_formal_sweep(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
+                        const double* h_epochs_s, int32_t n_epochs, int32_t gff_mode,
+                        const double* h_ctau, const double* h_csrc, int32_t n_chan,
+                        double* d_out, double* d_ftot, void* d_work, size_t work_bytes,
+                        void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (!mode_ok(gff_mode)) return fail(ctx, RJP_ERR_ARG, "bad gff_mode");
+  if (int r = check_fields(ctx, fields, false, true, gff_mode)) return r;
+  if (!fields->d_temp)
+    return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_sweep: fields.d_temp must be a device pointer");
+  if (int r = check_bursts(ctx, bursts, fields)) return r;
+  if (!h_epochs_s || n_epochs < 1)
+    return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_sweep: NULL epochs or n_epochs < 1");
+  for (int e = 0; e < n_epochs; ++e)
+    if (!std::isfinite(h_epochs_s[e]))
+      return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_sweep: non-finite epoch");
+  if (!h_ctau || !h_csrc || n_chan < 1)
+    return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_sweep: NULL table or n_chan < 1");
+  if (!d_out && !d_ftot)
+    return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_sweep: both outputs are NULL");
+  if ((int64_t)n_epochs * n_chan > INT32_MAX)
+    return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_sweep: n_epochs * n_chan exceeds 2^31 - 1");
+  if (d_ftot && (!d_work || work_bytes < rjp::ff_formal_sweep_workspace_bytes(
+                                             fields->nx, fields->nz, n_epochs, n_chan)))
+    return fail(ctx, RJP_ERR_WORKSPACE,
+                "rjp_ff_formal_sweep: workspace smaller than rjp_ff_formal_sweep_workspace()");
+  hipStream_t st = (hipStream_t)stream;
+  const std::vector<double> ext = burst_ext_table(bursts);
+  const double* src[4] = {h_ctau, h_csrc, h_epochs_s, ext.data()};
+  const size_t len[4] = {(size_t)n_chan, (size_t)n_chan, (size_t)n_epochs, ext.size()};
+  double* dev[4];
+  if (int r = stage_tables(ctx, st, src, len, 4, dev)) return r;
+  return finish_staged(ctx, st,
+                       rjp::ff_formal_sweep_launch(fields, bursts, ext.empty() ? nullptr : dev[3],
+                                                   dev[2], n_epochs, gff_mode, dev[0], dev[1],
+                                                   n_chan, d_out, d_ftot, (double*)d_work, st),
+                       "ff_formal_sweep_launch");
+}
+
 size_t rjp_ff_grad_workspace(int32_t nx, int32_t ny, int32_t nz, int32_t n_epochs,
                              int32_t n_par, int32_t n_chan) {
   if (nx <= 0 || ny <= 0 || nz <= 0 || n_epochs <= 0 || n_par <= 0 || n_chan < 0) return 0;

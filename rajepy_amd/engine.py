@@ -971,6 +971,36 @@ class RTEngine:
             out.data_ptr(), self._stream()), self.ctx, "rjp_ff_formal")
         return out
 
+    def ff_formal_sweep(self, fields, bursts, epochs_s, gff_mode, ctau, csrc, want_maps=False,
+                        want_totals=True):
+        """Epoch sweep of the formal solution (rjp_ff_formal_sweep): ONE pass over the fields for
+        all of `epochs_s` [s] -> (maps[E, F, P] | None, ftot[E, F] | None) device tensors
+        (float64).  `maps[e]` equals `ff_formal` at `epochs_s[e]` bit for bit; `ftot[e, f]` is the
+        nansum of that map over the pixels, summed on the device in a fixed order -- with
+        `want_maps=False` (light curves) no map touches memory.  The burst factor is evaluated
+        once per (cell, epoch) whatever the number of channels.  Epochs in any order; `ctau`,
+        `csrc` as for `ff_formal`; any layout of `fields`; no cached state is read or written."""
+        E, F = len(epochs_s), len(ctau)
+        if len(csrc) != F:
+            raise ValueError("ff_formal_sweep: ctau and csrc must have one entry per channel")
+        if not (want_maps or want_totals):
+            raise ValueError("ff_formal_sweep: neither maps nor totals asked for")
+        nx, ny, nz = fields.shape
+        maps = self._f64(E, F, fields.npix) if want_maps else None
+        ftot = self._f64(E, F) if want_totals else None
+        work = None
+        if want_totals:
+            work = self._workspace(max(1, self.lib.rjp_ff_formal_sweep_workspace(nx, ny, nz, E, F)))
+        fs = fields.struct()
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        self._check(self.lib.rjp_ff_formal_sweep(
+            self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None,
+            _lib.dbl_array(epochs_s), E, int(gff_mode), _lib.dbl_array(ctau),
+            _lib.dbl_array(csrc), F, ptr(maps), ptr(ftot), ptr(work),
+            work.numel() if work is not None else 0, self._stream()), self.ctx,
+            "rjp_ff_formal_sweep")
+        return maps, ftot
+
     def ff_grad(self, fields, bursts, epochs_s, gff_mode, tavg=None, ctau=None, cflux=None,
                 want_maps=False):
         """Sensitivities to the burst parameters (rjp_ff_grad): one pass over (a0, ts) per tile of

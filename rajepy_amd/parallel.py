@@ -235,10 +235,15 @@ def gather_slabs_to_root(local, shards, rank, axis, root=0, group=None, out=None
     return finish()
 
 
-def sweep_flux_vs_time(model, epochs_s, freqs, rank=0, world=1, group=None):
+def sweep_flux_vs_time(model, epochs_s, freqs, rank=0, world=1, group=None, formal=False):
     """Epoch-sharded continuum sweep through the JetModel API: every rank scans its epochs
     (8-32 per pass over HBM), reduces each (epoch, channel) map to its total flux on the
-    device and the [E, F] light curves are all_gathered.  Returns a host array [E, F] [Jy]."""
+    device and the [E, F] light curves are all_gathered.  Returns a host array [E, F] [Jy].
+    `formal=True`: the fluxes by the formal solution along the line of sight instead of the
+    isothermal T_avg (1 - e^-tau) -- each rank's shard is ONE `RTEngine.ff_formal_sweep` call
+    without maps; sharding and gather are the same.  The two curves agree where T is constant
+    along every sightline and differ wherever it varies; the formal path reads and writes no
+    cached state (no T_avg map, no launch-time moments)."""
     from . import engine as E
     from .maths import physics as mphys
     shards = EpochShards(epochs_s, world)
@@ -251,7 +256,11 @@ def sweep_flux_vs_time(model, epochs_s, freqs, rank=0, world=1, group=None):
         gv = [mphys.gff(nu, model.params['properties']['T_0']) for nu in freqs]
     ctau, cflux = E.ff_channel_coeffs(freqs, model.csize, model.params["target"]["dist"],
                                       model.gff_mode, gv)
-    if mine:
+    if mine and formal:
+        # one call into the library per sweep: the line-of-sight walk of every local epoch
+        _, ftot = eng.ff_formal_sweep(dev, model._rjp_bursts(), mine, model.gff_mode, ctau, cflux,
+                                      want_maps=False)
+    elif mine:
         # one call into the library per sweep: scan + light-curve stage (rjp_ff_step)
         ftot = eng._f64(len(mine), len(freqs))
         eng.ff_step(dev, model._rjp_bursts(), mine, model.gff_mode, model._model_tavg(), ctau,
