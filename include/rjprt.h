@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define RJP_VERSION 116          /* 0.1.16 */
+#define RJP_VERSION 117          /* 0.1.17 */
 #define RJP_RANGE_BLOCKS 2048    /* partial (min, max) pairs rjp_field_range writes */
 #define RJP_MAX_EPOCH_TILE 32    /* most epochs evaluated per grid pass: 32 uniformly spaced ones (with or without d_em), 16 when only 16-31 are left, else tiles of 8, 4, 2, 1 */
 
@@ -341,6 +341,15 @@ int rjp_range_guard(rjp_ctx* ctx);
  * that call, in moment_shape[0..1] the (bins, order) shape it chose; zeros for the tiles).
  * For tests and the bench line. */
 int rjp_last_scan_path(const rjp_ctx* ctx, double* worst_rel_err, int32_t* moment_shape);
+
+/* Which epoch tiles the last rjp_ff_scan / rjp_ff_step of this context launched: *n_tiles tiles,
+ * and in tiles[5 * k .. 5 * k + 4] for tile k: its first epoch e0, its epochs et, whether it ran
+ * the uniform-spacing recurrence (1) or evaluated every epoch directly (0), its y-ranges nsplit
+ * and the sightlines per lane it was dispatched with (1 for et >= 16).  Zero tiles after a scan
+ * on any other path (moments, cached moments, bucketed layout, table) and before the first scan.
+ * `tiles` holds room for `cap` tiles; with more tiles than that only *n_tiles is written and
+ * RJP_ERR_ARG returned.  Host-only: it synchronises and enqueues nothing.  For tests. */
+int rjp_last_scan_tiles(const rjp_ctx* ctx, int32_t* n_tiles, int32_t* tiles, int32_t cap);
 
 /* Which layout of (a0, ts) the last rjp_ff_scan / rjp_ff_step of this context read: 0 = the grid
  * order (every cell of the occupied y-ranges), 1 = the launch-time-bucketed layout of

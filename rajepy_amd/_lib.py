@@ -18,7 +18,7 @@ RJP_F32, RJP_F64 = 4, 8
 RJP_GFF_SCALAR, RJP_GFF_POWERLAW = 0, 1
 RJP_MAX_EPOCH_TILE = 32
 RJP_RANGE_BLOCKS = 2048
-RJP_VERSION = 116             # include/rjprt.h; the binding below matches exactly this ABI
+RJP_VERSION = 117             # include/rjprt.h; the binding below matches exactly this ABI
 RJP_OK = 0
 RJP_ERR_ARG, RJP_ERR_HIP, RJP_ERR_NODEVICE, RJP_ERR_WORKSPACE, RJP_ERR_DEGENERATE = \
     -1, -2, -3, -4, -5
@@ -103,6 +103,7 @@ SIGNATURES = {
                               C.c_int32, _P, _P, _P, _P, C.c_size_t, _P]),
     "rjp_range_guard": (C.c_int, [_P]),
     "rjp_last_scan_path": (C.c_int, [_P, _DP, C.POINTER(C.c_int32)]),
+    "rjp_last_scan_tiles": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32]),
     "rjp_last_scan_layout": (C.c_int, [_P]),
     "rjp_last_srt_bins": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "rjp_last_table_build_ms": (C.c_double, [_P]),

@@ -14,9 +14,10 @@
 // epochs (since round 4 on the device: mom_tables_kernel below).  F is entire (a polynomial in
 // Gaussians): the expansion converges faster than geometrically, and it is CHECKED -- the
 // interpolant is compared with F at 2N+1 points of every (jet, bin, epoch) and the path is used
-// only when the worst relative error stays below 1e-11 (the agreement the recurrence tiles have
-// with the direct ones); a launch-time range too wide for the narrowest burst simply keeps the
-// tiles.  The moment maps themselves depend on neither epochs nor burst parameters: a caller may
+// only when the worst relative error stays below 1e-11 (RJP_MOM_TOL; the tiles themselves keep
+// every Gaussian that matters within 1.2e-12, evaluated directly or by the recurrences up to
+// their 28 sigma limit: derived in tests/sweep_ref.py); a launch-time range too wide for the
+// narrowest burst simply keeps the tiles.  The moment maps themselves depend on neither epochs nor burst parameters: a caller may
 // keep them (rjp_fields.d_mom_cache) and later sweeps of the model are contractions only.
 //
 // Moment pass: launch times are uncorrelated along y in general (and in the synthetic set), so

@@ -26,6 +26,9 @@ struct rjp_ctx {
   int last_path = 0;              // 0 = epoch tiles, 1 = LDS moments, 2 = launch-time-ordered layout
   int last_layout = 0;            // 0 = grid order, 1 = launch-time-bucketed layout (rjp_last_scan_layout)
   bool last_srt_mom = false;      // the last scan contracted bins from the layout's moments
+  // (e0, et, uniform, nsplit, vec) of every epoch tile the last scan launched (rjp_last_scan_tiles);
+  // empty after a scan on another path
+  std::vector<int32_t> last_tiles;
   static constexpr int kSlots = 8;
   struct Slot {
     double* h = nullptr;
@@ -434,6 +437,7 @@ static int ff_scan_impl(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts
   hipStream_t st = (hipStream_t)stream;
   ctx->last_layout = 0;
   ctx->last_srt_mom = false;
+  ctx->last_tiles.clear();
   // epoch sweeps by launch-time moments (ff_moments.hip) when the caller provided the launch-time
   // range and the host-side accuracy check of the expansion passes
   const int mr = rjp::moments_plan(fields, bursts, h_epochs_s, n_epochs, gff_mode, d_em != nullptr,
@@ -536,6 +540,11 @@ static int ff_scan_impl(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts
   ctx->last_path = 0;
   rjp::ScanPlan plan;
   rjp::ff_scan_plan(fields, bursts, h_epochs_s, n_epochs, gff_mode, d_em != nullptr, plan);
+  for (const rjp::ScanTile& tl : plan.tiles) {
+    // (tiles of >= 16 epochs run one sightline per lane: ff_scan_run)
+    const int32_t row[5] = {tl.e0, tl.et, tl.un.on, tl.nsplit, tl.et < 16 ? plan.vec : 1};
+    ctx->last_tiles.insert(ctx->last_tiles.end(), row, row + 5);
+  }
   double* d_ext = nullptr;
   if (!plan.ext.empty()) {
     const double* src[1] = {plan.ext.data()};
@@ -580,6 +589,15 @@ int rjp_last_scan_path(const rjp_ctx* ctx, double* worst_rel_err, int32_t* momen
     moment_shape[1] = mom ? ctx->mom.N : ctx->last_path == 3 ? 8 : 0;
   }
   return ctx->last_path;
+}
+
+int rjp_last_scan_tiles(const rjp_ctx* ctx, int32_t* n_tiles, int32_t* tiles, int32_t cap) {
+  if (!ctx || !n_tiles || cap < 0 || (cap > 0 && !tiles)) return RJP_ERR_ARG;
+  const int32_t n = (int32_t)(ctx->last_tiles.size() / 5);
+  *n_tiles = n;
+  if (n > cap) return RJP_ERR_ARG;
+  for (size_t i = 0; i < ctx->last_tiles.size(); ++i) tiles[i] = ctx->last_tiles[i];
+  return RJP_OK;
 }
 
 int rjp_last_scan_layout(const rjp_ctx* ctx) { return ctx ? ctx->last_layout : RJP_ERR_ARG; }

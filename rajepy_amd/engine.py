@@ -884,6 +884,21 @@ class RTEngine:
         self.last_moment_shape = (int(shape[0]), int(shape[1]))      # (bins, order); (0, 0) = tiles
         return {0: "tiles", 1: "moments", 2: "lt", 3: "table", 4: "cached"}[path], err.value
 
+    def last_scan_tiles(self):
+        """[(e0, et, uniform, nsplit, vec)] of the epoch tiles the last rjp_ff_scan / rjp_ff_step of
+        this engine launched (rjp_last_scan_tiles): first epoch, epochs, 1 where the tile ran the
+        uniform-spacing recurrence, y-ranges, sightlines per lane.  [] after a scan on another
+        path.  Host-only; for tests."""
+        n = C.c_int32()
+        rc = self.lib.rjp_last_scan_tiles(self.ctx, C.byref(n), None, 0)
+        if n.value == 0:
+            self._check(rc, self.ctx, "rjp_last_scan_tiles")
+            return []
+        buf = (C.c_int32 * (5 * n.value))()
+        self._check(self.lib.rjp_last_scan_tiles(self.ctx, C.byref(n), buf, n.value), self.ctx,
+                    "rjp_last_scan_tiles")
+        return [tuple(int(buf[5 * k + i]) for i in range(5)) for k in range(n.value)]
+
     def last_scan_layout(self):
         """Which layout of (a0, ts) the last scan read (rjp_last_scan_layout): 'grid' (grid
         order) or 'sorted' (the launch-time-bucketed layout, only the bins inside the bursts'

@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_header_version_symbols_and_argtypes():
     from rajepy_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "rjprt.h")).read()
-    assert int(re.search(r"#define RJP_VERSION (\d+)", hdr).group(1)) == _lib.RJP_VERSION == 116
+    assert int(re.search(r"#define RJP_VERSION (\d+)", hdr).group(1)) == _lib.RJP_VERSION == 117
     assert "size_t rjp_ff_formal_sweep_workspace(" in hdr and "int rjp_ff_formal_sweep(" in hdr
     res, args = _lib.SIGNATURES["rjp_ff_formal_sweep_workspace"]
     assert res is C.c_size_t and args == [C.c_int32] * 5
@@ -31,7 +31,7 @@ def test_header_version_symbols_and_argtypes():
     assert args == [vp, C.POINTER(_lib.Fields), C.POINTER(_lib.Bursts), dp, C.c_int32, C.c_int32,
                     dp, dp, C.c_int32, vp, vp, vp, C.c_size_t, vp]
     lib = _lib.load()
-    assert lib.rjp_version() == 116
+    assert lib.rjp_version() == 117
     assert lib.rjp_ff_formal_sweep.argtypes == args
     assert lib.rjp_ff_formal_sweep_workspace.restype is C.c_size_t
 

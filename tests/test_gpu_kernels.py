@@ -452,11 +452,25 @@ def test_shape_edge_cases_with_and_without_bounds(eng, shape):
 
 
 @pytest.mark.parametrize("dtype", [8, 4])
-@pytest.mark.parametrize("n_ep,t1", [(8, 3.5), (16, 5.0), (12, 0.55), (4, 2.0)])
+@pytest.mark.parametrize("n_ep,t1", [(8, 3.5), (16, 5.0), (12, 0.55), (4, 2.0), (4, 0.15),
+                                     (8, 0.35)])
 def test_uniform_epoch_sweeps_use_the_recurrence_correctly(eng, dtype, n_ep, t1):
     """Uniformly spaced epochs take the two-exp-per-burst recurrence (tiles of 8 and 4, and a
     ragged tail); results must equal the oracle at every epoch, including epochs far from any
-    burst (anchor Gaussian underflows) and bursts that peak inside a tile."""
+    burst (anchor Gaussian underflows) and bursts that peak inside a tile.
+
+    What each case runs (the planted burst has hl = 0.02 yr, sigma = 0.017 yr, and a tile whose
+    half-span exceeds 28 sigma = 0.476 yr evaluates every epoch directly; asserted through
+    last_scan_tiles against tests/sweep_ref.tile_plan_host):
+      (8, 3.5)    one tile of 8, half-span 2.0 yr: direct
+      (16, 5.0)   two tiles of 8, half-span 1.33 yr: direct
+      (12, 0.55)  tiles of 8 and 4, dt = 0.05 yr: the recurrence in both
+      (4, 2.0)    one tile of 4, half-span 1.33 yr: direct
+      (4, 0.15)   one tile of 4, dt = 0.05 yr: the recurrence at ET = 4
+      (8, 0.35)   one tile of 8, dt = 0.05 yr: the recurrence at ET = 8
+    f32 storage runs 4-wide lanes, hence tiles of 4 throughout; its short tiles keep their
+    float-accuracy exponential whatever `uniform` says."""
+    from tests import sweep_ref as R
     from rajepy_amd import engine as E
     shape = (4, 37, 16)
     seed = 20240507
@@ -471,6 +485,16 @@ def test_uniform_epoch_sweeps_use_the_recurrence_correctly(eng, dtype, n_ep, t1)
     years = np.linspace(0., t1, n_ep)
     sumA, em, tavg = eng.ff_scan(fields, U.bursts_from_oracle(jet), years * orc.YEAR,
                                  E.RJP_GFF_SCALAR)
+    assert eng.last_scan_path()[0] == "tiles"
+    tiles = [(e0, et, un, vec) for e0, et, un, _, vec in eng.last_scan_tiles()]
+    from tests.f32_ref import burst_lists_of
+    assert tiles == R.tile_plan_host(years * orc.YEAR, burst_lists_of(jet), dtype=dtype,
+                                     layout="cmp", want_em=True, nz=shape[2])
+    ran = sorted(et for _, et, un, _ in tiles if un)
+    if dtype == 8:
+        assert ran == {(12, 0.55): [4, 8], (4, 0.15): [4], (8, 0.35): [8]}.get((n_ep, t1), [])
+    else:
+        assert ran == [4] * {(12, 0.55): 3, (4, 0.15): 1, (8, 0.35): 2}.get((n_ep, t1), 0)
     eng.synchronize()
     tol = 1e-11 if dtype == 8 else RTOL
     em_h = em.cpu().numpy().reshape(n_ep, shape[0], shape[2])
@@ -750,9 +774,22 @@ def test_32_epoch_tiles_follow_the_oracle(eng, store, n_ep, t1):
     years = np.linspace(0.0, t1, n_ep)
     ep = [y * orc.YEAR for y in years]
     bursts = U.bursts_from_oracle(jet)
+    from tests import sweep_ref as R
+    from tests.f32_ref import burst_lists_of
+    plan = R.tile_plan_host(ep, burst_lists_of(jet), dtype=dtype, layout="cmp", nz=shape[2])
+    if dtype == 8:
+        # which tiles ran: 32-epoch recurrences, except (32, 8.0) whose half-span is too wide
+        assert [et for _, et, _, _ in plan] == {(32, 5.0): [32], (45, 4.0): [32, 8, 4, 1],
+                                               (64, 2.0): [32, 32], (33, 0.6): [32, 1],
+                                               (32, 8.0): [16, 16]}[(n_ep, t1)]
+        assert all(un == (et >= 4) for _, et, un, _ in plan)
     a32, none, _ = eng.ff_scan(fields, bursts, ep, E.RJP_GFF_POWERLAW, want_em=False)
+    assert eng.last_scan_path()[0] == "tiles"
+    assert [(e0, et, un, vec) for e0, et, un, _, vec in eng.last_scan_tiles()] == plan
     a32 = a32.clone()
     a16, em16, _ = eng.ff_scan(fields, bursts, ep, E.RJP_GFF_POWERLAW, want_em=True)
+    assert eng.last_scan_path()[0] == "tiles"
+    assert [(e0, et, un, vec) for e0, et, un, _, vec in eng.last_scan_tiles()] == plan
     eng.synchronize()
     assert none is None
     tol = 1e-11 if dtype == 8 else RTOL

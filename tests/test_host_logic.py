@@ -121,6 +121,35 @@ def test_abi_struct_layouts_match_header_as_compiled(tmp_path):
         assert comp[st]["members"] == _ctypes_layout(cls), st
 
 
+def test_last_scan_tiles_prototype_as_compiled_and_null_refusals(tmp_path):
+    """rjp_last_scan_tiles as the C++ compiler reads include/rjprt.h -- a function pointer of the
+    documented type takes its address -- against the binding's argtypes; and the refusals that need
+    no context: a NULL context or a NULL count is RJP_ERR_ARG, nothing is written."""
+    import shutil
+    import subprocess
+    src = tmp_path / "proto.cpp"
+    src.write_text('#include "rjprt.h"\n'
+                   "int (*const fp)(const rjp_ctx*, int32_t*, int32_t*, int32_t) = "
+                   "&rjp_last_scan_tiles;\n"
+                   "int (*const fq)(const rjp_ctx*, double*, int32_t*) = &rjp_last_scan_path;\n"
+                   "int main() { return fp && fq ? 0 : 1; }\n")
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("hipcc")
+    assert cxx, "no C++ compiler"
+    subprocess.run([cxx, "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "include"),
+                    str(src)], check=True)
+    res, args = _lib.SIGNATURES["rjp_last_scan_tiles"]
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    assert res is ctypes.c_int and args == [ctypes.c_void_p, i32p, i32p, ctypes.c_int32]
+    hdr = open(os.path.join(ROOT, "include", "rjprt.h")).read()
+    decl = hdr[:hdr.index("int rjp_last_scan_tiles(")]
+    assert decl.rstrip().endswith("For tests. */")               # beside rjp_last_scan_path's wording
+    lib = _lib.load()
+    n = ctypes.c_int32(-5)
+    buf = (ctypes.c_int32 * 5)(*([-7] * 5))
+    assert lib.rjp_last_scan_tiles(None, ctypes.byref(n), buf, 1) == _lib.RJP_ERR_ARG
+    assert n.value == -5 and list(buf) == [-7] * 5
+
+
 def _integration_md_binding():
     """exec()s the ctypes stub printed in INTEGRATION.md (section B, `RaJePy/_rjprt.py`) with
     the CDLL call replaced by a recorder; returns (namespace, recorder)."""
