@@ -1,12 +1,18 @@
-// The tile of the formal-solution kernels and a cell's free-free optical-depth factor b: K5
-// (ff_formal.hip), K6 (rrl_formal.hip) and K8 (ff_formal_sweep.hip) include this header, so that
-// all three count and weigh a cell's continuum opacity with the same code.
+// What the formal-solution kernels share: K5 (ff_formal.hip), K6 (rrl_formal.hip) and K8
+// (ff_formal_sweep.hip) count and weigh a cell's continuum opacity with the code below, and K5 and
+// K8 take their tile, their recurrence, their dead-cell and output rules and their host dispatch
+// from here -- a sweep's maps are K5's bit for bit because both run these statements.
 #pragma once
+#include <type_traits>
+
 #include "rjp_host.h"
 
 namespace rjp {
 
 constexpr int kFB = 256;     // threads per workgroup
+#ifndef RJP_FORMAL_WAVES
+#define RJP_FORMAL_WAVES 4      /* 128-VGPR budget */
+#endif
 
 template <int LF> struct FormalTile {
   static constexpr int ZT = LF == 256 ? 8 : 16;   // sightlines per workgroup
@@ -15,8 +21,27 @@ template <int LF> struct FormalTile {
   static constexpr int NZP = ZT / G;              // sightlines per thread
 };
 
+// A thread's places in the tile of workgroup blockIdx.x: the ZT sightlines from z0 of row x; LF =
+// lanes along the kernel's lane axis (K5: channels, K8: epochs)
+template <int LF> struct FormalPlace {
+  int x, z0;
+  int cy, cz;      // this thread's cell in a slab (phase 1)
+  int cb;          // first sightline of this thread (phase 2)
+  __device__ __forceinline__ explicit FormalPlace(int nz) {
+    constexpr int ZT = FormalTile<LF>::ZT;
+    const int ntz = (nz + ZT - 1) / ZT;
+    const int tid = threadIdx.x;
+    x = (int)blockIdx.x / ntz;
+    z0 = ((int)blockIdx.x - x * ntz) * ZT;
+    cy = tid / ZT;
+    cz = tid % ZT;
+    cb = tid / LF * FormalTile<LF>::NZP;
+  }
+};
+
 template <typename T>
 struct FormalFields {
+  using value_type = T;
   const T* nd;
   const T* xi;
   const T* temp;
@@ -67,6 +92,40 @@ __device__ __forceinline__ double formal_b(const FormalFields<T>& f, int64_t o, 
   double b = a;
   if (BURSTS) b = formal_weigh(a, chi_cell(bd, red, time_s - (double)f.ts[o]));
   return formal_live(b);
+}
+
+// The walk, front to back: one cell of optical depth dtau = ctau b and temperature T, with
+// om = 1 - e^-dtau.  A dead cell (b == 0) adds T * 0 = 0, not NaN; a sightline without a cell of
+// T > 0 (`hot` false) is NaN, as T_avg is.
+__device__ __forceinline__ double formal_temp(double b, double Tk) { return b != 0.0 ? Tk : 0.0; }
+__device__ __forceinline__ void formal_update(double tk, double om, double& I, double& Th) {
+  I = __builtin_fma(tk * om, Th, I);
+  Th = __builtin_fma(-Th, om, Th);
+}
+__device__ __forceinline__ double formal_out(bool hot, double cs, double I) {
+  return hot ? cs * I : __builtin_nan("");
+}
+
+// Host: the fields as FormalFields<T> and the layout the scans of this model stream, handed to
+// go(fields, std::integral_constant<int, LAY>) -- tau layout (f64 only), compact, else wide.  `ts`:
+// the launch times the kernel is to see (K8 passes null without bursts).
+template <typename T>
+FormalFields<T> formal_fields(const rjp_fields* fl, const void* ts) {
+  return {(const T*)fl->d_nd, (const T*)fl->d_xi, (const T*)fl->d_temp, (const T*)fl->d_pf,
+          (const T*)ts, (const T*)fl->d_em0,
+          std::is_same<T, double>::value ? (const double*)fl->d_a0 : nullptr, fl->d_ylo, fl->d_yhi};
+}
+template <typename Go>
+hipError_t formal_dispatch(const rjp_fields* fl, int mode, const void* ts, Go&& go) {
+  auto lay = [&](auto f, bool tau) {
+    if constexpr (std::is_same<decltype(f), FormalFields<double>>::value)
+      if (tau) return go(f, std::integral_constant<int, LAY_TAU>{});
+    if (fl->d_em0) return go(f, std::integral_constant<int, LAY_CMP>{});
+    return go(f, std::integral_constant<int, LAY_WIDE>{});
+  };
+  if (fl->dtype == RJP_F64)
+    return lay(formal_fields<double>(fl, ts), fl->d_a0 && fl->a0_mode == mode);
+  return lay(formal_fields<float>(fl, ts), false);
 }
 
 }  // namespace rjp

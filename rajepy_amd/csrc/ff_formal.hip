@@ -12,8 +12,9 @@
 // contributes exactly when its term enters the tau scans' nansum (b == 0 / NaN: skipped); the
 // output is NaN exactly where T_avg is (no cell of the sightline has T > 0).
 //
-// Layout of K3 (rrl_scan.hip): a 256-thread workgroup owns ZT z-adjacent sightlines of one x-row
-// and a block of LF channels (lanes over channels, G = 256 / LF sightline groups):
+// A 256-thread workgroup owns ZT z-adjacent sightlines of one x-row and a block of LF channels
+// (lanes over channels, G = 256 / LF sightline groups; FormalTile / FormalPlace in ff_formal.h,
+// which K8 shares together with the recurrence and the rules for dead cells and empty sightlines):
 //   phase 1  one thread per cell of a slab of YC y-rows: b and T to LDS;
 //   phase 2  every lane walks the slab's rows in increasing iy for its NZP sightlines:
 //            om = 1 - e^(-ctau b), I += T om Theta, Theta -= Theta om (two FMAs), with b and T
@@ -25,9 +26,6 @@
 
 namespace rjp {
 
-#ifndef RJP_FORMAL_WAVES
-#define RJP_FORMAL_WAVES 4      /* 128-VGPR budget */
-#endif
 template <typename T, int LAY, int LF, bool BURSTS>
 __global__ __launch_bounds__(kFB, RJP_FORMAL_WAVES) void ff_formal_kernel(
     FormalFields<T> f, int nx, int ny, int nz, int mode, BurstsDev bd, double time_s,
@@ -40,35 +38,17 @@ __global__ __launch_bounds__(kFB, RJP_FORMAL_WAVES) void ff_formal_kernel(
   __shared__ rjp_d2 s_bt[kFB];      // (b, T) of the slab's cells, [row * ZT + sightline]
   __shared__ int s_hot[ZT];         // the sightline has a cell with T > 0 (T_avg is not NaN)
 
-  const int ntz = (nz + ZT - 1) / ZT;
-  const int x = (int)blockIdx.x / ntz;
-  const int z0 = ((int)blockIdx.x - x * ntz) * ZT;
+  const FormalPlace<LF> pl(nz);
+  const int x = pl.x, z0 = pl.z0, cy = pl.cy, cz = pl.cz, cb = pl.cb;
   const int tid = threadIdx.x;
-  const int fl = tid % LF;
-  const int g = tid / LF;
-  const int fi = (int)blockIdx.y * LF + fl;
+  const int fi = (int)blockIdx.y * LF + tid % LF;
   const bool chan_live = fi < nchan;
   const double ct = chan_live ? ctau[fi] : 0.0;     // dead lanes: dtau = 0, om = 0 exactly
-  const int cy = tid / ZT, cz = tid % ZT;           // this thread's cell in the slab (phase 1)
-  const int cb = g * NZP;                           // first sightline of this thread (phase 2)
 
   if (tid < ZT) s_hot[tid] = 0;
   __syncthreads();
-  int ya = 0, ye = ny;
-  if (f.ylo) {
-    // sparse models: only the rows inside the tile's occupied y-range
-    __shared__ int s_lo, s_hi;
-    if (tid == 0) { s_lo = ny; s_hi = 0; }
-    __syncthreads();
-    if (tid < ZT && z0 + tid < nz) {
-      const int64_t p = (int64_t)x * nz + z0 + tid;
-      const int lo = f.ylo[p], hi = f.yhi[p];
-      if (lo < hi) { atomicMin(&s_lo, lo); atomicMax(&s_hi, hi); }
-    }
-    __syncthreads();
-    ya = s_lo;
-    ye = s_hi;
-  }
+  int ya, ye;
+  tile_y_range<ZT>(f.ylo, f.yhi, x, z0, nz, ny, ya, ye);
 
   double I[NZP], Th[NZP];
 #pragma unroll
@@ -84,7 +64,7 @@ __global__ __launch_bounds__(kFB, RJP_FORMAL_WAVES) void ff_formal_kernel(
         const double Tk = (double)f.temp[o];
         if (Tk > 0.0) s_hot[cz] = 1;                  // (every writer stores the same value)
         bb = formal_b<T, LAY, BURSTS>(f, o, mode, bd, time_s, Tk);
-        tk = bb != 0.0 ? Tk : 0.0;                    // a dead cell adds T * 0 = 0, not NaN
+        tk = formal_temp(bb, Tk);
       }
       rjp_d2 v;
       v.x = bb;
@@ -106,9 +86,7 @@ __global__ __launch_bounds__(kFB, RJP_FORMAL_WAVES) void ff_formal_kernel(
       if (!any) continue;
 #pragma unroll
       for (int j = 0; j < NZP; ++j) {
-        const double om = one_minus_exp_neg(ct * c[j].x);
-        I[j] = __builtin_fma(c[j].y * om, Th[j], I[j]);
-        Th[j] = __builtin_fma(-Th[j], om, Th[j]);
+        formal_update(c[j].y, one_minus_exp_neg(ct * c[j].x), I[j], Th[j]);
       }
     }
     __syncthreads();
@@ -119,7 +97,7 @@ __global__ __launch_bounds__(kFB, RJP_FORMAL_WAVES) void ff_formal_kernel(
     const int64_t base = (int64_t)fi * nx * nz + (int64_t)x * nz + z0 + cb;
 #pragma unroll
     for (int j = 0; j < NZP; ++j)
-      if (z0 + cb + j < nz) out[base + j] = s_hot[cb + j] ? cs * I[j] : __builtin_nan("");
+      if (z0 + cb + j < nz) out[base + j] = formal_out(s_hot[cb + j], cs, I[j]);
   }
 }
 
@@ -158,22 +136,11 @@ hipError_t ff_formal_launch(const rjp_fields* fl, const rjp_bursts* hb, const do
   BurstsDev b;
   const bool bursts = bursts_to_dev(hb, b, d_ext);
   if (bursts && !fl->d_ts) return hipErrorInvalidValue;
-  const bool tau = fl->d_a0 && fl->dtype == RJP_F64 && fl->a0_mode == mode;
-  if (fl->dtype == RJP_F64) {
-    using T = double;
-    FormalFields<T> f{(const T*)fl->d_nd, (const T*)fl->d_xi, (const T*)fl->d_temp,
-                      (const T*)fl->d_pf, (const T*)fl->d_ts, (const T*)fl->d_em0,
-                      (const double*)fl->d_a0, fl->d_ylo, fl->d_yhi};
-    if (tau) return formal_launch_lf<T, LAY_TAU>(f, fl, mode, b, bursts, time_s, d_ctau, d_csrc, nchan, out, st);
-    if (fl->d_em0) return formal_launch_lf<T, LAY_CMP>(f, fl, mode, b, bursts, time_s, d_ctau, d_csrc, nchan, out, st);
-    return formal_launch_lf<T, LAY_WIDE>(f, fl, mode, b, bursts, time_s, d_ctau, d_csrc, nchan, out, st);
-  }
-  using T = float;
-  FormalFields<T> f{(const T*)fl->d_nd, (const T*)fl->d_xi, (const T*)fl->d_temp,
-                    (const T*)fl->d_pf, (const T*)fl->d_ts, (const T*)fl->d_em0, nullptr,
-                    fl->d_ylo, fl->d_yhi};
-  if (fl->d_em0) return formal_launch_lf<T, LAY_CMP>(f, fl, mode, b, bursts, time_s, d_ctau, d_csrc, nchan, out, st);
-  return formal_launch_lf<T, LAY_WIDE>(f, fl, mode, b, bursts, time_s, d_ctau, d_csrc, nchan, out, st);
+  return formal_dispatch(fl, mode, fl->d_ts, [&](const auto& f, auto lay) {
+    using T = typename std::decay_t<decltype(f)>::value_type;
+    return formal_launch_lf<T, decltype(lay)::value>(f, fl, mode, b, bursts, time_s, d_ctau,
+                                                     d_csrc, nchan, out, st);
+  });
 }
 
 }  // namespace rjp

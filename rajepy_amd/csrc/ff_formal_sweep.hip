@@ -4,14 +4,15 @@
 //   out[e, f, p] = csrc[f] sum_i T_i (1 - e^-dtau_i) exp(-sum_{j in front of i} dtau_j),
 //   dtau_i = ctau[f] b_i(e),  b_i(e) = |a0_i| chi_i(t_e - ts_i)^2,     ftot[e, f] = nansum_p out
 //
-// K5's tile and walk with the lane axis turned from channels to EPOCHS (light curves have 1-8
-// channels and tens to hundreds of epochs): a 256-thread workgroup owns ZT = 16 z-adjacent
+// The tile and walk of ff_formal.h (FormalTile, FormalPlace, tile_y_range) with the lane axis
+// turned from channels to EPOCHS (light curves have 1-8 channels and tens to hundreds of epochs):
+// a 256-thread workgroup owns ZT = 16 z-adjacent
 // sightlines of one x-row, LE epochs (lanes; G = 256 / LE sightline groups, NZP = 16 / G sightlines
 // per thread) and a register block of FC channels.
 //   phase 1  one thread per cell of a slab of YC y-rows stages what does not depend on the epoch:
 //            the signed a (|a0| as formal_a forms it for the layout, jet flag in the sign), T, ts;
 //   phase 2  every lane walks the slab's rows in increasing iy for its sightlines: per cell
-//            b = a chi^2(t_e - ts) ONCE, then for each channel of the block K5's statements
+//            b = a chi^2(t_e - ts) ONCE, then for each channel of the block formal_update:
 //            om = 1 - e^(-ctau b), I += T om Theta, Theta -= Theta om.
 // LE = 64: the lanes of a wave look at the same cell (LDS broadcast), so the cell's jet is
 // wave-uniform -- the burst parameters are scalar operands (chi_jet) and a dead cell (a == 0) is
@@ -20,7 +21,8 @@
 // to further workgroups (gridDim.y), which repeat it.  Epochs: blocks of 64 lanes, the tail by
 // blocks of 16 unless it fills more than three of them -- the only dead lanes are the last
 // block's.
-// b comes from the code K5 uses (ff_formal.h) and the recurrence is K5's statement for statement:
+// b, the recurrence, the dead-cell rule and the output rule are the functions K5 calls
+// (ff_formal.h: formal_a / formal_weigh / formal_live, formal_update, formal_temp, formal_out):
 // each (sightline, epoch, channel) value is one sequential chain that no layout reorders, so every
 // map equals rjp_ff_formal's at that epoch bit for bit.
 // Totals: the tile's values pass through LDS ([epoch][sightline]); one thread per epoch adds its 16
@@ -30,10 +32,6 @@
 #include "ff_formal.h"
 
 namespace rjp {
-
-#ifndef RJP_FORMAL_WAVES
-#define RJP_FORMAL_WAVES 4      /* 128-VGPR budget */
-#endif
 
 template <typename T, int LAY, int LE, int FC>
 __global__ __launch_bounds__(kFB, RJP_FORMAL_WAVES) void ff_formal_sweep_kernel(
@@ -50,12 +48,10 @@ __global__ __launch_bounds__(kFB, RJP_FORMAL_WAVES) void ff_formal_sweep_kernel(
   __shared__ double s_x[LE * ZT];   // one channel's pixel values of the tile, [epoch lane][sightline]
   __shared__ int s_hot[ZT];         // the sightline has a cell with T > 0 (T_avg is not NaN)
 
-  const int ntz = (nz + ZT - 1) / ZT;
-  const int x = (int)blockIdx.x / ntz;
-  const int z0 = ((int)blockIdx.x - x * ntz) * ZT;
+  const FormalPlace<LE> pl(nz);
+  const int x = pl.x, z0 = pl.z0, cy = pl.cy, cz = pl.cz, cb = pl.cb;
   const int tid = threadIdx.x;
   const int el = tid % LE;
-  const int g = tid / LE;
   const int e_blk = e_lo + (int)blockIdx.z * LE;     // first epoch of this workgroup
   const int ei = e_blk + el;
   const double te = ei < e_hi ? epochs[ei] : 0.0;    // (a dead lane walks epoch 0 s and stores nothing)
@@ -64,26 +60,11 @@ __global__ __launch_bounds__(kFB, RJP_FORMAL_WAVES) void ff_formal_sweep_kernel(
   double ct[FC];
 #pragma unroll
   for (int k = 0; k < FC; ++k) ct[k] = k < nf ? ctau[f0 + k] : 0.0;
-  const int cy = tid / ZT, cz = tid % ZT;            // this thread's cell in the slab (phase 1)
-  const int cb = g * NZP;                            // first sightline of this thread (phase 2)
 
   if (tid < ZT) s_hot[tid] = 0;
   __syncthreads();
-  int ya = 0, ye = ny;
-  if (f.ylo) {
-    // sparse models: only the rows inside the tile's occupied y-range
-    __shared__ int s_lo, s_hi;
-    if (tid == 0) { s_lo = ny; s_hi = 0; }
-    __syncthreads();
-    if (tid < ZT && z0 + tid < nz) {
-      const int64_t p = (int64_t)x * nz + z0 + tid;
-      const int lo = f.ylo[p], hi = f.yhi[p];
-      if (lo < hi) { atomicMin(&s_lo, lo); atomicMax(&s_hi, hi); }
-    }
-    __syncthreads();
-    ya = s_lo;
-    ye = s_hi;
-  }
+  int ya, ye;
+  tile_y_range<ZT>(f.ylo, f.yhi, x, z0, nz, ny, ya, ye);
 
   double I[NZP][FC], Th[NZP][FC];
 #pragma unroll
@@ -130,14 +111,10 @@ __global__ __launch_bounds__(kFB, RJP_FORMAL_WAVES) void ff_formal_sweep_kernel(
           chi = chi_cell(bd, signbit_d(c.x), tl);
         }
         const double b = formal_live(formal_weigh(fabs(c.x), chi));
-        const double tk = b != 0.0 ? c.y : 0.0;       // a dead cell adds T * 0 = 0, not NaN
+        const double tk = formal_temp(b, c.y);
 #pragma unroll
         for (int k = 0; k < FC; ++k) {
-          if (k < nf) {
-            const double om = one_minus_exp_neg(ct[k] * b);
-            I[j][k] = __builtin_fma(tk * om, Th[j][k], I[j][k]);
-            Th[j][k] = __builtin_fma(-Th[j][k], om, Th[j][k]);
-          }
+          if (k < nf) formal_update(tk, one_minus_exp_neg(ct[k] * b), I[j][k], Th[j][k]);
         }
       }
     }
@@ -153,8 +130,7 @@ __global__ __launch_bounds__(kFB, RJP_FORMAL_WAVES) void ff_formal_sweep_kernel(
       const double cs = csrc[f0 + k];
 #pragma unroll
       for (int j = 0; j < NZP; ++j)
-        s_x[el * ZT + cb + j] =
-            (z0 + cb + j < nz && s_hot[cb + j]) ? cs * I[j][k] : __builtin_nan("");
+        s_x[el * ZT + cb + j] = formal_out(z0 + cb + j < nz && s_hot[cb + j], cs, I[j][k]);
       __syncthreads();
       if (out) {
         for (int i = tid; i < ne * ZT; i += kFB) {
@@ -238,24 +214,10 @@ hipError_t ff_formal_sweep_launch(const rjp_fields* fl, const rjp_bursts* hb, co
   const bool bursts = bursts_to_dev(hb, a.b, d_ext);
   if (bursts && !fl->d_ts) return hipErrorInvalidValue;
   const void* ts = bursts ? fl->d_ts : nullptr;
-  const bool tau = fl->d_a0 && fl->dtype == RJP_F64 && fl->a0_mode == mode;
-  hipError_t e;
-  if (fl->dtype == RJP_F64) {
-    using T = double;
-    FormalFields<T> f{(const T*)fl->d_nd, (const T*)fl->d_xi, (const T*)fl->d_temp,
-                      (const T*)fl->d_pf, (const T*)ts, (const T*)fl->d_em0,
-                      (const double*)fl->d_a0, fl->d_ylo, fl->d_yhi};
-    if (tau) e = sweep_launch_le<T, LAY_TAU>(f, a);
-    else if (fl->d_em0) e = sweep_launch_le<T, LAY_CMP>(f, a);
-    else e = sweep_launch_le<T, LAY_WIDE>(f, a);
-  } else {
-    using T = float;
-    FormalFields<T> f{(const T*)fl->d_nd, (const T*)fl->d_xi, (const T*)fl->d_temp,
-                      (const T*)fl->d_pf, (const T*)ts, (const T*)fl->d_em0, nullptr,
-                      fl->d_ylo, fl->d_yhi};
-    if (fl->d_em0) e = sweep_launch_le<T, LAY_CMP>(f, a);
-    else e = sweep_launch_le<T, LAY_WIDE>(f, a);
-  }
+  const hipError_t e = formal_dispatch(fl, mode, ts, [&](const auto& f, auto lay) {
+    using T = typename std::decay_t<decltype(f)>::value_type;
+    return sweep_launch_le<T, decltype(lay)::value>(f, a);
+  });
   if (e != hipSuccess || !ftot) return e;
   const int nwg = fl->nx * ((fl->nz + 15) / 16);
   return sum_partials_launch(part, n_epochs * nchan, nwg, ftot, st);

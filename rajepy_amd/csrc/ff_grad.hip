@@ -174,28 +174,10 @@ __global__ __launch_bounds__(kBlock) void ff_grad_kernel(
     const int32_t* __restrict__ ylo, const int32_t* __restrict__ yhi, int ny, int nz,
     int64_t nchunks, int64_t npix, int ylen, int nsplit, BurstsDev b, GradEpochs<ET> ep,
     double* __restrict__ ws) {
-  const int split = (int)(blockIdx.x % (unsigned)nsplit);
-  const int64_t c = (int64_t)(blockIdx.x / (unsigned)nsplit) * kBlock + threadIdx.x;
-  const bool lane_live = c < nchunks;
-  const int64_t p0 = c * VEC;
-  int y0 = split * ylen;
-  int y1 = min(ny, y0 + ylen);
-  if (ylo) {
-    // sparse models: clip this workgroup's rows to the occupied range of its sightlines
-    __shared__ int s_lo, s_hi;
-    if (threadIdx.x == 0) { s_lo = ny; s_hi = 0; }
-    __syncthreads();
-    if (lane_live) {
-      int lo = ny, hi = 0;
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) { lo = min(lo, ylo[p0 + v]); hi = max(hi, yhi[p0 + v]); }
-      if (lo < hi) { atomicMin(&s_lo, lo); atomicMax(&s_hi, hi); }
-    }
-    __syncthreads();
-    y0 = max(y0, s_lo);
-    y1 = min(y1, s_hi);
-  }
-  if (!lane_live) return;
+  const LaneRange lr = lane_y_range<VEC, kBlock>(nsplit, ylen, ny, nchunks, ylo, yhi);
+  if (!lr.live) return;
+  const int split = lr.split, y0 = lr.y0, y1 = lr.y1;
+  const int64_t p0 = lr.p0;
   const int64_t x = p0 / nz;
   const int z = (int)(p0 - x * nz);
 

@@ -27,35 +27,18 @@
 namespace rjp {
 // ---- T_avg = nanmean_y(T where T > 0) (classes.py:1471-1472, 1484-1485) ----------------------
 // Depends on neither frequency nor epoch: one pass over the temperature field per MODEL (the
-// tau layout's scans never read T).  Same lane / y-range structure and the same summation
-// order as the single-epoch ff_scan_kernel, so the map is bit-identical to the one that kernel
+// tau layout's scans never read T).  Lanes and rows from lane_y_range (rjp_device.h), as
+// ff_scan_kernel's, and that kernel's summation order, so the map is bit-identical to the one it
 // derives on the wide and compact layouts.  Partials: ws[split][0|1][pixel].
 template <typename T, int VEC>
 __global__ __launch_bounds__(kBlock) void tavg_kernel(FieldPtrs<T> f, int ny, int nz,
                                                       int64_t nchunks, int64_t npix, int ylen,
                                                       int nsplit, double* __restrict__ ws) {
   constexpr int U = 8;
-  const int split = (int)(blockIdx.x % (unsigned)nsplit);
-  const int64_t c = (int64_t)(blockIdx.x / (unsigned)nsplit) * kBlock + threadIdx.x;
-  const bool lane_live = c < nchunks;
-  const int64_t p0 = c * VEC;
-  int y0 = split * ylen;
-  int y1 = min(ny, y0 + ylen);
-  if (f.ylo) {
-    __shared__ int s_lo, s_hi;
-    if (threadIdx.x == 0) { s_lo = ny; s_hi = 0; }
-    __syncthreads();
-    if (lane_live) {
-      int lo = ny, hi = 0;
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) { lo = min(lo, f.ylo[p0 + v]); hi = max(hi, f.yhi[p0 + v]); }
-      if (lo < hi) { atomicMin(&s_lo, lo); atomicMax(&s_hi, hi); }
-    }
-    __syncthreads();
-    y0 = max(y0, s_lo);
-    y1 = min(y1, s_hi);
-  }
-  if (!lane_live) return;
+  const LaneRange lr = lane_y_range<VEC, kBlock>(nsplit, ylen, ny, nchunks, f.ylo, f.yhi);
+  if (!lr.live) return;
+  const int split = lr.split, y0 = lr.y0, y1 = lr.y1;
+  const int64_t p0 = lr.p0;
   const int64_t x = p0 / nz;
   const int z = (int)(p0 - x * nz);
   double accT[VEC];

@@ -313,31 +313,10 @@ __global__ __launch_bounds__(kBlock) void ff_scan_kernel(
     FieldPtrs<T> f, int ny, int nz, int64_t nchunks, int64_t npix, int ylen, int nsplit,
     BurstsDev b, EpochTile<ET> ep, double* __restrict__ ws) {
   constexpr int kUnroll = unroll_for(VEC, ET, LAY, MODE, EM);
-  // 1-D grid with the y-split index fastest: workgroups that run together stream consecutive
-  // y-ranges of the same sightlines, i.e. neighbouring memory, instead of ranges 16 MiB apart
-  // (n_y n_z elements) -- +5 % on cfg4 (6.0 -> 6.3 TB/s)
-  const int split = (int)(blockIdx.x % (unsigned)nsplit);
-  const int64_t c = (int64_t)(blockIdx.x / (unsigned)nsplit) * kBlock + threadIdx.x;
-  const bool lane_live = c < nchunks;
-  const int64_t p0 = c * VEC;              // first sightline (pixel) of this lane
-  int y0 = split * ylen;
-  int y1 = min(ny, y0 + ylen);
-  if (f.ylo) {
-    // sparse models: clip this workgroup's rows to the occupied range of its sightlines
-    __shared__ int s_lo, s_hi;
-    if (threadIdx.x == 0) { s_lo = ny; s_hi = 0; }
-    __syncthreads();
-    if (lane_live) {
-      int lo = ny, hi = 0;
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) { lo = min(lo, f.ylo[p0 + v]); hi = max(hi, f.yhi[p0 + v]); }
-      if (lo < hi) { atomicMin(&s_lo, lo); atomicMax(&s_hi, hi); }
-    }
-    __syncthreads();
-    y0 = max(y0, s_lo);
-    y1 = min(y1, s_hi);
-  }
-  if (!lane_live) return;
+  const LaneRange lr = lane_y_range<VEC, kBlock>(nsplit, ylen, ny, nchunks, f.ylo, f.yhi);
+  if (!lr.live) return;
+  const int split = lr.split, y0 = lr.y0, y1 = lr.y1;
+  const int64_t p0 = lr.p0;
   const int64_t x = p0 / nz;
   const int z = (int)(p0 - x * nz);
 
@@ -419,23 +398,11 @@ void ff_scan_tile_kernel(
   constexpr int kWaves = kBlock / RJP_WAVE;
   // [wave][buffer][field][row 0: 64 sightlines | row 1: 64 sightlines]
   __shared__ double s_rows[kWaves][2][NF][2 * RJP_WAVE];
-  __shared__ int s_lo, s_hi;
-  const int split = (int)(blockIdx.x % (unsigned)nsplit);
-  const int64_t p0 = (int64_t)(blockIdx.x / (unsigned)nsplit) * kBlock + threadIdx.x;
-  const bool lane_live = p0 < npix;
-  int y0 = split * ylen;
-  int y1 = min(ny, y0 + ylen);
-  if (f.ylo) {
-    if (threadIdx.x == 0) { s_lo = ny; s_hi = 0; }
-    __syncthreads();
-    if (lane_live) {
-      const int lo = f.ylo[p0], hi = f.yhi[p0];
-      if (lo < hi) { atomicMin(&s_lo, lo); atomicMax(&s_hi, hi); }
-    }
-    __syncthreads();
-    y0 = max(y0, s_lo);
-    y1 = min(y1, s_hi);
-  }
+  // (one sightline per lane; a dead lane walks on: it fetches for the wave)
+  const LaneRange lr = lane_y_range<1, kBlock>(nsplit, ylen, ny, npix, f.ylo, f.yhi);
+  const int split = lr.split, y0 = lr.y0, y1 = lr.y1;
+  const int64_t p0 = lr.p0;
+  const bool lane_live = lr.live;
 
   double accA[ET][1], accE[EM ? ET : 1][1], accT[1];
   int cnt[1];

@@ -118,27 +118,11 @@ __global__ __launch_bounds__(kBlock) void ff_scan_table_kernel(
   constexpr int VEC = 2;
   extern __shared__ __attribute__((aligned(16))) double s_chi[];       // [2][ni][10]
   for (int i = threadIdx.x; i < 2 * t.ni * kChiStride; i += kBlock) s_chi[i] = tab[i];
-  __shared__ int s_lo, s_hi;
-  if (threadIdx.x == 0) { s_lo = ny; s_hi = 0; }
-  __syncthreads();
-  const int split = (int)(blockIdx.x % (unsigned)nsplit);
-  const int64_t c = (int64_t)(blockIdx.x / (unsigned)nsplit) * kBlock + threadIdx.x;
-  const bool lane_live = c < nchunks;
-  const int64_t p0 = c * VEC;
-  int y0 = split * ylen;
-  int y1 = min(ny, y0 + ylen);
-  if (ylo) {
-    if (lane_live) {
-      int lo = ny, hi = 0;
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) { lo = min(lo, ylo[p0 + v]); hi = max(hi, yhi[p0 + v]); }
-      if (lo < hi) { atomicMin(&s_lo, lo); atomicMax(&s_hi, hi); }
-    }
-    __syncthreads();
-    y0 = max(y0, s_lo);
-    y1 = min(y1, s_hi);
-  }
-  if (!lane_live) return;
+  const LaneRange lr = lane_y_range<VEC, kBlock>(nsplit, ylen, ny, nchunks, ylo, yhi);
+  __syncthreads();                           // the table is staged
+  if (!lr.live) return;
+  const int split = lr.split, y0 = lr.y0, y1 = lr.y1;
+  const int64_t p0 = lr.p0;
   const int64_t x = p0 / nz;
   const int z = (int)(p0 - x * nz);
   const double wmax = t.wmax;
@@ -730,27 +714,11 @@ __global__ __launch_bounds__(kBlock) void ff_scan_table_wide_kernel(
   constexpr int VEC = 2;
   extern __shared__ __attribute__((aligned(16))) double s_chi[];       // [2][ni][10]
   for (int i = threadIdx.x; i < 2 * t.ni * kChiStride; i += kBlock) s_chi[i] = tab[i];
-  __shared__ int s_lo, s_hi;
-  if (threadIdx.x == 0) { s_lo = ny; s_hi = 0; }
-  __syncthreads();
-  const int split = (int)(blockIdx.x % (unsigned)nsplit);
-  const int64_t c = (int64_t)(blockIdx.x / (unsigned)nsplit) * kBlock + threadIdx.x;
-  const bool lane_live = c < nchunks;
-  const int64_t p0 = c * VEC;
-  int y0 = split * ylen;
-  int y1 = min(ny, y0 + ylen);
-  if (f.ylo) {
-    if (lane_live) {
-      int lo = ny, hi = 0;
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) { lo = min(lo, f.ylo[p0 + v]); hi = max(hi, f.yhi[p0 + v]); }
-      if (lo < hi) { atomicMin(&s_lo, lo); atomicMax(&s_hi, hi); }
-    }
-    __syncthreads();
-    y0 = max(y0, s_lo);
-    y1 = min(y1, s_hi);
-  }
-  if (!lane_live) return;
+  const LaneRange lr = lane_y_range<VEC, kBlock>(nsplit, ylen, ny, nchunks, f.ylo, f.yhi);
+  __syncthreads();                           // the table is staged
+  if (!lr.live) return;
+  const int split = lr.split, y0 = lr.y0, y1 = lr.y1;
+  const int64_t p0 = lr.p0;
   const int64_t x = p0 / nz;
   const int z = (int)(p0 - x * nz);
   const double wmax = t.wmax;

@@ -667,6 +667,78 @@ __device__ __forceinline__ double tau_weight(double T, int gff_mode) {
   return out[0];
 }
 
+// ---- the y-range of a sightline walk ----------------------------------------------------
+// Sparse models carry the occupied y-range [ylo, yhi) of every sightline (an empty one is
+// [n_y, 0)); a workgroup then walks only the union of its sightlines' ranges.  Every walk along
+// y takes its rows from one of the two helpers below, so that a scan with the bounds attached
+// differs from the same scan without them in the rows it visits and in nothing else.  EVERY
+// thread of the workgroup has to call them (two barriers when the bounds are attached).
+//
+// Lane form: a lane owns VEC adjacent sightlines from p0, the workgroup one of `nsplit` y-ranges
+// of `ylen` rows.  1-D grid with the y-split index fastest: workgroups that run together stream
+// consecutive y-ranges of the same sightlines, i.e. neighbouring memory, instead of ranges 16 MiB
+// apart (n_y n_z elements) -- +5 % on cfg4 (6.0 -> 6.3 TB/s).  A dead lane (the last workgroup's)
+// may return NO EARLIER than behind the call, where both barriers lie behind it, and behind every
+// barrier of the caller's own (the table scans' comes first); ff_scan_tile_kernel's never return.
+struct LaneRange {
+  int split;       // which y-range of the sightlines
+  int64_t p0;      // first sightline (pixel) of this lane
+  bool live;
+  int y0, y1;      // rows to walk
+};
+template <int VEC, int BLOCK>
+__device__ __forceinline__ LaneRange lane_y_range(int nsplit, int ylen, int ny, int64_t nchunks,
+                                                  const int32_t* __restrict__ ylo,
+                                                  const int32_t* __restrict__ yhi) {
+  LaneRange r;
+  r.split = (int)(blockIdx.x % (unsigned)nsplit);
+  const int64_t c = (int64_t)(blockIdx.x / (unsigned)nsplit) * BLOCK + threadIdx.x;
+  r.live = c < nchunks;
+  r.p0 = c * VEC;
+  r.y0 = r.split * ylen;
+  r.y1 = min(ny, r.y0 + ylen);
+  if (ylo) {
+    __shared__ int s_lo, s_hi;
+    if (threadIdx.x == 0) { s_lo = ny; s_hi = 0; }
+    __syncthreads();
+    if (r.live) {
+      int lo = ny, hi = 0;
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) { lo = min(lo, ylo[r.p0 + v]); hi = max(hi, yhi[r.p0 + v]); }
+      if (lo < hi) { atomicMin(&s_lo, lo); atomicMax(&s_hi, hi); }
+    }
+    __syncthreads();
+    r.y0 = max(r.y0, s_lo);
+    r.y1 = min(r.y1, s_hi);
+  }
+  return r;
+}
+
+// Tile form: the workgroup owns the ZT z-adjacent sightlines of row x from z0 and walks their
+// whole occupied range [lo, hi) -- [0, ny) without bounds, empty (lo >= hi) when every sightline
+// of the tile is.
+template <int ZT>
+__device__ __forceinline__ void tile_y_range(const int32_t* __restrict__ ylo,
+                                             const int32_t* __restrict__ yhi, int x, int z0, int nz,
+                                             int ny, int& lo, int& hi) {
+  lo = 0;
+  hi = ny;
+  if (ylo) {
+    __shared__ int s_lo, s_hi;
+    const int tid = threadIdx.x;
+    if (tid == 0) { s_lo = ny; s_hi = 0; }
+    __syncthreads();
+    if (tid < ZT && z0 + tid < nz) {
+      const int64_t p = (int64_t)x * nz + z0 + tid;
+      const int l = ylo[p], h = yhi[p];
+      if (l < h) { atomicMin(&s_lo, l); atomicMax(&s_hi, h); }
+    }
+    __syncthreads();
+    lo = s_lo;
+    hi = s_hi;
+  }
+}
+
 // ---- splitmix64 counter hash for the synthetic generator -------------------------------
 __host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ull;

@@ -15,11 +15,14 @@
 //   e_c = e^-c, om_l = 1 - e^-l, u = 1 - e^-(c + l) = (1 - e_c) + e_c om_l
 //   I += B (e_c om_l Theta_C - u D);  D = e_c (D + (Theta_C - D) om_l);  Theta_C *= e_c.
 // With a constant T the sum telescopes to B e^-tau_C (1 - e^-tau_L): the reference's product.
-// A cell contributes its c exactly when K5 counts it (b != 0) and its l exactly when K3 does
-// (CellLine::C != 0); the output is NaN exactly where T_avg is.
+// A cell contributes its c exactly when K5 counts it (formal_b != 0) and its l exactly when K3
+// does (CellLine::C != 0, i.e. path_code != kPathSkip); the output is NaN exactly where T_avg is
+// (formal_out).
 //
-// Layout: K5's tile and walk, K3's channel loop.  A 256-thread workgroup owns ZT z-adjacent
-// sightlines of one x-row and a block of LF channels;
+// Layout: a tile walked front to back like K5's (tile_y_range, rjp_device.h) with K3's channel
+// loop, whose pieces both kernels take from rrl_voigt.h: the XCD tile map, the folded channel
+// lanes, the waves' frequency ranges and the path-code stream.  A 256-thread
+// workgroup owns ZT z-adjacent sightlines of one x-row and a block of LF channels;
 //   phase 1  one thread per cell of a slab of YC y-rows: K3's line constants, b, the two constants
 //            of the Planck expansion and one path code per (cell, wave) to LDS;
 //   phase 2  a wave works on one cell per trip (LF >= 64), rows in increasing iy: Re w by the
@@ -79,7 +82,8 @@ __global__ __launch_bounds__(kRB, 4) void rrl_formal_kernel(
   constexpr bool CEN = LF >= RJP_WAVE;       // the waves work on one cell at a time
 
   // per-cell constants of the slab, [row * ZT + sightline].  Wave-uniform layouts stage the forms
-  // K3's channel loop reads: s_C <- A, s_nu0 <- c1, s_E0 <- B, s_q / s_cq as in K3, s_ky = y h / pi;
+  // voigt_wave_path and the line factor A + B dnu read: s_C <- A, s_nu0 <- c1, s_E0 <- B,
+  // s_q / s_cq as in K3, s_ky = y h / pi;
   // the per-lane layout keeps the plain constants, and s_ky carries h / kT.
   __shared__ double s_nu0[NC], s_is2[NC], s_y[NC], s_C[NC], s_E0[NC], s_q[NC], s_cq[NC],
       s_ky[NC];
@@ -97,22 +101,15 @@ __global__ __launch_bounds__(kRB, 4) void rrl_formal_kernel(
   __shared__ int s_hot[ZT];                  // the sightline has a cell with T > 0
 
   const int ntz = (nz + ZT - 1) / ZT;
-  // K3's XCD-aware tile map: z-neighbours, which share 128-byte lines, run on one XCD
-  unsigned bx = blockIdx.x;
-  {
-    const unsigned per = gridDim.x / 8;
-    if (bx < 8 * per) bx = (bx % 8) * per + bx / 8;
-  }
+  // z-neighbours, which share 128-byte lines, run on one XCD
+  const unsigned bx = xcd_tile(blockIdx.x, gridDim.x);
   const int x = (int)bx / ntz;
   const int z0 = ((int)bx - x * ntz) * ZT;
   const int tid = threadIdx.x;
-  const int fl = tid % LF;
   const int g = tid / LF;
-  // channels folded about the block centre, as K3: a wave holds a narrow range of |x|
-  const int fbase = blockIdx.y * LF;
-  const int nblk = min(LF, nchan - fbase);
-  const int fi = fbase + ((fl & 1) ? nblk - 1 - (fl >> 1) : (fl >> 1));
-  const bool chan_live = fl < nblk;
+  const ChannelLane<LF> ch(nchan);               // (folded about the block centre)
+  const int fl = ch.fl, fi = ch.fi;
+  const bool chan_live = ch.live;
   const double hk_ref = ln.h_over_k * ln.nu_ref;
   const double nu_f0 = chan_live ? nu[fi] : ln.nu_ref;
   // dead lanes: c = 0 and a finite B; nothing of theirs is stored
@@ -128,43 +125,14 @@ __global__ __launch_bounds__(kRB, 4) void rrl_formal_kernel(
   }
   if (tid < ZT) s_hot[tid] = 0;
 
-  if constexpr (CEN) {
-    // frequency range of this wave's even and odd lanes (its two runs of channels)
-    const double inf = __builtin_inf();
-    double r0 = (chan_live && !(fl & 1)) ? nu_f0 : inf, r1 = (chan_live && !(fl & 1)) ? nu_f0 : -inf;
-    double r2 = (chan_live && (fl & 1)) ? nu_f0 : inf, r3 = (chan_live && (fl & 1)) ? nu_f0 : -inf;
-#pragma unroll
-    for (int d = RJP_WAVE / 2; d > 0; d >>= 1) {
-      r0 = fmin(r0, __shfl_xor(r0, d, RJP_WAVE));
-      r1 = fmax(r1, __shfl_xor(r1, d, RJP_WAVE));
-      r2 = fmin(r2, __shfl_xor(r2, d, RJP_WAVE));
-      r3 = fmax(r3, __shfl_xor(r3, d, RJP_WAVE));
-    }
-    if ((tid & (RJP_WAVE - 1)) == 0) {
-      const int w = fl / RJP_WAVE;               // LF = 64: every wave holds the same channels
-      s_rng[w][0] = r0; s_rng[w][1] = r1; s_rng[w][2] = r2; s_rng[w][3] = r3;
-    }
-  }
+  if constexpr (CEN) wave_channel_range(ch, nu_f0, s_rng);
   __syncthreads();
 
   const PoleTop ptop = pole_top();
   const int cy = tid / ZT, cz = tid % ZT;       // this thread's cell in the slab (phase 1)
 
-  int ya = 0, ye = ny;
-  if (f.ylo) {
-    // sparse models: only the rows inside the tile's occupied y-range
-    __shared__ int s_lo, s_hi;
-    if (tid == 0) { s_lo = ny; s_hi = 0; }
-    __syncthreads();
-    if (tid < ZT && z0 + tid < nz) {
-      const int64_t p = (int64_t)x * nz + z0 + tid;
-      const int lo = f.ylo[p], hi = f.yhi[p];
-      if (lo < hi) { atomicMin(&s_lo, lo); atomicMax(&s_hi, hi); }
-    }
-    __syncthreads();
-    ya = s_lo;
-    ye = s_hi;
-  }
+  int ya, ye;
+  tile_y_range<ZT>(f.ylo, f.yhi, x, z0, nz, ny, ya, ye);
 
   const FormalFields<T> ff{f.nd, f.xi, f.temp, f.pf, f.ts, nullptr, nullptr, nullptr, nullptr};
   // (a scalar: the path code must reach the branches below as a wave-uniform value)
@@ -223,19 +191,11 @@ __global__ __launch_bounds__(kRB, 4) void rrl_formal_kernel(
     for (int j = 0; j < NZP; ++j) {
       double I = s_I[j * kRB + tid], Th = s_Th[j * kRB + tid], D = s_D[j * kRB + tid];
       if constexpr (CEN) {
-        const uint8_t* cb = s_cb + (wave * ZT + g * NZP + j) * YC;
-        uint32_t q_lo = 0, q_hi = 0;            // the codes of eight rows, in an SGPR pair
+        CodeStream codes(s_cb + (wave * ZT + g * NZP + j) * YC);
 #pragma unroll 1
         for (int r = 0; r < YC; ++r) {
           const int ci = r * ZT + g * NZP + j;
-          if ((r & 7) == 0) {
-            const uint2 v = *reinterpret_cast<const uint2*>(cb + r);
-            q_lo = __builtin_amdgcn_readfirstlane(v.x);
-            q_hi = __builtin_amdgcn_readfirstlane(v.y);
-          }
-          const int pc = (int)(q_lo & 0xffu);
-          q_lo = (q_lo >> 8) | (q_hi << 24);
-          q_hi >>= 8;
+          const int pc = codes.next(r);
           if (pc == 0) continue;                // dead in both opacities
           const int path = pc & 7;
           double om_l = 0.0;                    // C == 0: the continuum's update alone
@@ -294,7 +254,7 @@ __global__ __launch_bounds__(kRB, 4) void rrl_formal_kernel(
 #pragma unroll
     for (int j = 0; j < NZP; ++j)
       if (z0 + g * NZP + j < nz) {
-        double v = s_hot[g * NZP + j] ? cs * s_I[j * kRB + tid] : __builtin_nan("");
+        double v = formal_out(s_hot[g * NZP + j], cs, s_I[j * kRB + tid]);
         if (add) v += add[base + j];
         out[base + j] = v;
       }

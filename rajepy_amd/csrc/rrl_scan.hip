@@ -105,20 +105,10 @@ __global__ __launch_bounds__(kRB, RJP_K3_WAVES) void rrl_scan_kernel(
   __shared__ double s_rng[NWC][4];
 
   const int ntz = (nz + ZT - 1) / ZT;
-  // XCD-aware tile map (round 5): a tile's rows are 64-byte runs (8 sightlines x 8 B), half of a
-  // 128-byte line; workgroups are dealt round-robin to the 8 XCDs, so with the identity map the
-  // z-neighbour that needs the other half ran on ANOTHER XCD (its own L2) and every line came
-  // from HBM twice -- FETCH_SIZE 71.7 GB raw for 26.3 GB algorithmic, profiles/r04_cfg3_f64_pmc.json.
-  // Every XCD now takes a contiguous range of tiles in dispatch order: neighbours share an L2.
-  // (K3 is FP64-vector-bound: this is about wasted traffic, not time.)
 #ifndef RJP_K3_XCD
-#define RJP_K3_XCD 1
+#define RJP_K3_XCD 1      /* 0: A/B build with the identity tile map */
 #endif
-  unsigned bx = blockIdx.x;
-  if (RJP_K3_XCD) {
-    const unsigned per = gridDim.x / 8;                    // (the tail past 8 * per: identity)
-    if (bx < 8 * per) bx = (bx % 8) * per + bx / 8;
-  }
+  const unsigned bx = RJP_K3_XCD ? xcd_tile(blockIdx.x, gridDim.x) : blockIdx.x;
   const int x = (int)bx / ntz;
   const int z0 = ((int)bx - x * ntz) * ZT;
   const int tid = threadIdx.x;
@@ -136,16 +126,10 @@ __global__ __launch_bounds__(kRB, RJP_K3_WAVES) void rrl_scan_kernel(
 #endif
   constexpr bool ROT = LF == 256 && RJP_K3_ROT != 0;
   __shared__ double s_nu[ROT ? kRB : 1];
-  const int fl = tid % LF;
   const int g = tid / LF;
-  // Lanes take the channels of this block folded about the block centre: lane 0 -> first,
-  // lane 1 -> last, lane 2 -> second, ...  A band centred on the line then gives each wave
-  // a narrow range of |x|: the outermost wave is entirely far-field (asymptotic series) and
-  // only the innermost needs the pole term, instead of every wave straddling both regimes.
-  const int fbase = blockIdx.y * LF;
-  const int nblk = min(LF, nchan - fbase);
-  const int fi = fbase + ((fl & 1) ? nblk - 1 - (fl >> 1) : (fl >> 1));
-  const bool chan_live = fl < nblk;
+  const ChannelLane<LF> ch(nchan);               // (folded about the block centre)
+  const int fl = ch.fl, fi = ch.fi;
+  const bool chan_live = ch.live;
   const double nu_f0 = chan_live ? nu[fi] : ln.nu_ref;
   if constexpr (ROT) s_nu[tid] = nu_f0;          // (visible after the barrier of the range block)
 
@@ -153,42 +137,16 @@ __global__ __launch_bounds__(kRB, RJP_K3_WAVES) void rrl_scan_kernel(
   for (int j = 0; j < NZP; ++j) s_acc[j * kRB + tid] = 0.0;
 
   if constexpr (CEN) {
-    // frequency range of this wave's even and odd lanes (its two runs of channels)
-    const double inf = __builtin_inf();
-    double r0 = (chan_live && !(fl & 1)) ? nu_f0 : inf, r1 = (chan_live && !(fl & 1)) ? nu_f0 : -inf;
-    double r2 = (chan_live && (fl & 1)) ? nu_f0 : inf, r3 = (chan_live && (fl & 1)) ? nu_f0 : -inf;
-#pragma unroll
-    for (int d = RJP_WAVE / 2; d > 0; d >>= 1) {
-      r0 = fmin(r0, __shfl_xor(r0, d, RJP_WAVE));
-      r1 = fmax(r1, __shfl_xor(r1, d, RJP_WAVE));
-      r2 = fmin(r2, __shfl_xor(r2, d, RJP_WAVE));
-      r3 = fmax(r3, __shfl_xor(r3, d, RJP_WAVE));
-    }
-    if ((tid & (RJP_WAVE - 1)) == 0) {
-      const int w = fl / RJP_WAVE;               // LF = 64: every wave holds the same channels
-      s_rng[w][0] = r0; s_rng[w][1] = r1; s_rng[w][2] = r2; s_rng[w][3] = r3;
-    }
+    wave_channel_range(ch, nu_f0, s_rng);
     __syncthreads();
   }
 
   const PoleTop ptop = pole_top();
   const int cy = tid / ZT, cz = tid % ZT;       // this thread's cell in the slab (phase 1)
 
-  int ya = 0, ye = ny;
-  if (f.ylo) {
-    // sparse models: only the slabs that intersect the tile's occupied y-range
-    __shared__ int s_lo, s_hi;
-    if (tid == 0) { s_lo = ny; s_hi = 0; }
-    __syncthreads();
-    if (tid < ZT && z0 + tid < nz) {
-      const int64_t p = (int64_t)x * nz + z0 + tid;
-      const int lo = f.ylo[p], hi = f.yhi[p];
-      if (lo < hi) { atomicMin(&s_lo, lo); atomicMax(&s_hi, hi); }
-    }
-    __syncthreads();
-    ya = (s_lo / YC) * YC;
-    ye = s_hi;
-  }
+  int ya, ye;
+  tile_y_range<ZT>(f.ylo, f.yhi, x, z0, nz, ny, ya, ye);
+  ya = (ya / YC) * YC;          // (K3's own: its slabs keep the boundaries of the full walk)
 
   // (a scalar: the path code must reach the branches below as a wave-uniform value)
   const int wave = (CEN && LF > RJP_WAVE) ? __builtin_amdgcn_readfirstlane(fl / RJP_WAVE) : 0;
@@ -235,19 +193,11 @@ __global__ __launch_bounds__(kRB, RJP_K3_WAVES) void rrl_scan_kernel(
       double acc = s_acc[j * kRB + slot];
       if constexpr (CEN) {
         // the wave works on ONE cell per trip: its path was decided in phase 1
-        const uint8_t* cb = s_cb + (wq * ZT + g * NZP + j) * YC;
-        uint32_t q_lo = 0, q_hi = 0;            // the codes of eight rows, in an SGPR pair
+        CodeStream codes(s_cb + (wq * ZT + g * NZP + j) * YC);
 #pragma unroll 1
         for (int r = 0; r < YC; ++r) {
           const int ci = r * ZT + g * NZP + j;
-          if ((r & 7) == 0) {
-            const uint2 v = *reinterpret_cast<const uint2*>(cb + r);
-            q_lo = __builtin_amdgcn_readfirstlane(v.x);
-            q_hi = __builtin_amdgcn_readfirstlane(v.y);
-          }
-          const int pc = (int)(q_lo & 0xffu);
-          q_lo = (q_lo >> 8) | (q_hi << 24);
-          q_hi >>= 8;
+          const int pc = codes.next(r);
           if (pc == kPathSkip) continue;
           const int path = pc & 7;
           if (path == kPathGeneric) {

@@ -749,6 +749,78 @@ __device__ __attribute__((noinline)) double line_term_generic(const RrlFields<T>
   return line_term<false>(c, nu_f, dnu, ln.dnu_max, nullptr);
 }
 
+// ---- the channel loop of K3 (rrl_scan.hip) and K6 (rrl_formal.hip) --------------------------
+// XCD-aware tile map: a tile's rows are 64-byte runs (8 sightlines x 8 B), half of a 128-byte
+// line; workgroups are dealt round-robin to the 8 XCDs, so with the identity map the z-neighbour
+// that needs the other half ran on ANOTHER XCD (its own L2) and every line came from HBM twice --
+// FETCH_SIZE 71.7 GB raw for 26.3 GB algorithmic, profiles/r04_cfg3_f64_pmc.json.  With this map
+// every XCD takes a contiguous range of tiles in dispatch order: neighbours share an L2.  (The
+// kernels are FP64-vector-bound: this is about wasted traffic, not time.)
+__device__ __forceinline__ unsigned xcd_tile(unsigned bx, unsigned ntiles) {
+  const unsigned per = ntiles / 8;                       // (the tail past 8 * per: identity)
+  return bx < 8 * per ? (bx % 8) * per + bx / 8 : bx;
+}
+
+// Lanes take the channels of block blockIdx.y folded about the block centre: lane 0 -> first,
+// lane 1 -> last, lane 2 -> second, ...  A band centred on the line then gives each wave a narrow
+// range of |x|: the outermost wave is entirely far-field (asymptotic series) and only the
+// innermost needs the pole term, instead of every wave straddling both regimes.
+template <int LF> struct ChannelLane {
+  int fl;          // lane along the channel axis
+  int fi;          // its channel
+  bool live;
+  __device__ __forceinline__ explicit ChannelLane(int nchan) {
+    fl = threadIdx.x % LF;
+    const int fbase = blockIdx.y * LF;
+    const int nblk = min(LF, nchan - fbase);
+    fi = fbase + ((fl & 1) ? nblk - 1 - (fl >> 1) : (fl >> 1));
+    live = fl < nblk;
+  }
+};
+
+// Frequency range of a wave's even and odd lanes (its two runs of channels) to rng[wave of the
+// channel block][lo_e, hi_e, lo_o, hi_o], what path_code takes; visible after the next barrier.
+template <int LF>
+__device__ __forceinline__ void wave_channel_range(const ChannelLane<LF>& ch, double nu_f,
+                                                   double (*rng)[4]) {
+  const double inf = __builtin_inf();
+  const int fl = ch.fl;
+  double r0 = (ch.live && !(fl & 1)) ? nu_f : inf, r1 = (ch.live && !(fl & 1)) ? nu_f : -inf;
+  double r2 = (ch.live && (fl & 1)) ? nu_f : inf, r3 = (ch.live && (fl & 1)) ? nu_f : -inf;
+#pragma unroll
+  for (int d = RJP_WAVE / 2; d > 0; d >>= 1) {
+    r0 = fmin(r0, __shfl_xor(r0, d, RJP_WAVE));
+    r1 = fmax(r1, __shfl_xor(r1, d, RJP_WAVE));
+    r2 = fmin(r2, __shfl_xor(r2, d, RJP_WAVE));
+    r3 = fmax(r3, __shfl_xor(r3, d, RJP_WAVE));
+  }
+  if ((threadIdx.x & (RJP_WAVE - 1)) == 0) {
+    const int w = fl / RJP_WAVE;               // LF = 64: every wave holds the same channels
+    rng[w][0] = r0; rng[w][1] = r1; rng[w][2] = r2; rng[w][3] = r3;
+  }
+}
+
+// The path codes of one sightline's rows, one byte per row and rows adjacent: a wave fetches the
+// codes of eight rows with ONE 8-byte read and two readfirstlane, then shifts them out of an SGPR
+// pair (it used to read, add an address and readfirstlane per evaluation).  next(r) for
+// r = 0, 1, 2, ... in turn.
+struct CodeStream {
+  const uint8_t* cb;              // 8-byte aligned
+  uint32_t lo = 0, hi = 0;
+  __device__ __forceinline__ explicit CodeStream(const uint8_t* codes) : cb(codes) {}
+  __device__ __forceinline__ int next(int r) {
+    if ((r & 7) == 0) {
+      const uint2 v = *reinterpret_cast<const uint2*>(cb + r);
+      lo = __builtin_amdgcn_readfirstlane(v.x);
+      hi = __builtin_amdgcn_readfirstlane(v.y);
+    }
+    const int pc = (int)(lo & 0xffu);
+    lo = (lo >> 8) | (hi << 24);
+    hi >>= 8;
+    return pc;
+  }
+};
+
 // host: the line constants of one call; the channel block is expanded about the middle of the band
 inline void fill_line(const rjp_fields* fl, const rjp_line* line, const double* h_nu, int nchan,
                       LineDev& ln) {

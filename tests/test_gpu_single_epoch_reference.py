@@ -319,6 +319,71 @@ def test_dead_lanes_of_the_last_group(eng, shape):
                 P, years, r["bins"], r["triples"], r["rel"]))
 
 
+# ---- occupied y-ranges on the two grid-order table scans ---------------------------------------------
+@pytest.mark.parametrize("layout", ["tau", "wide"])
+def test_grid_order_table_scans_with_occupied_y_ranges(eng, layout):
+    """ff_scan_table_kernel (tau layout) and ff_scan_table_wide_kernel (the five model fields) with
+    d_ylo / d_yhi attached: the same bits as without them, and without them within the table bound
+    of the reference.  The smallest map the table scans take (32768 sightlines, 64 rows) grown to
+    n_y = 65 (no multiple of the rows in flight, one y-range per sightline is not forced), n_z = 254
+    (no multiple of 16) and 33274 sightlines (58 live lanes in the last wave, dead lanes in the last
+    workgroup); 60 % holes, empty rows at both ends, an empty sightline and a first workgroup whose
+    512 sightlines are all empty.
+    Bound: U.single_epoch_bound(n_y) against ref_single_epoch on the device's own |a0|; the wide scan
+    forms |a0| = (|nd| xi)^2 pf T^-1.5 itself -- four roundings, 4 * 2^-53 on every term, added."""
+    import torch
+    from rajepy_amd import engine as E
+    shape = (131, 65, 254)
+    nx, ny, nz = shape
+    mode = E.RJP_GFF_SCALAR
+    f = eng.synth_fields(shape, SEED + 11, 0, 8, csize_au=0.5, wide=True, tau_mode=mode)
+    assert f.npix % 64 == 58 and (f.npix // 2) % 256 != 0
+    g = torch.Generator(device=eng.device)
+    g.manual_seed(29)
+    hole = (torch.rand(f.ncells, device=eng.device, generator=g) < 0.6).view(nx, ny, nz)
+    hole[:, :9, :] = True                          # empty rows at both ends
+    hole[:, ny - 6:, :] = True
+    hole[70, :, 33] = True                         # an empty sightline
+    hole[:3, :, :] = True                          # 762 sightlines: the whole first workgroup
+    hole = hole.reshape(-1)
+    nan = float("nan")
+    for t in (f.nd, f.xi, f.temp, f.pf, f.em0, f.a0):
+        t[hole] = nan
+    a0 = f.a0.cpu().numpy().reshape(shape)
+    ts = f.ts.cpu().numpy().reshape(shape)
+    if layout == "wide":
+        f.a0 = f.em0 = None                        # scan the five model fields
+    bursts = U.example_burst_lists()
+    t_epoch = 1.0 * YEAR
+    ref = U.ref_single_epoch(a0, ts, bursts, t_epoch).ravel()
+    assert ref[70 * nz + 33] == 0.0 and not ref[:512].any() and (ref > 0).sum() > f.npix // 2
+
+    def scan():
+        eng.use_sorted = False
+        try:
+            a = eng.ff_scan(f, E.make_bursts(*bursts), [t_epoch], mode, want_em=False,
+                            want_tavg=False)[0].clone()
+        finally:
+            eng.use_sorted = True
+        eng.synchronize()
+        assert not eng.range_guard()
+        assert (eng.last_scan_path()[0], eng.last_scan_layout()) == ("table", "grid")
+        assert eng.last_scan_tiles() == []
+        return a.cpu().numpy()[0]
+
+    free = scan()
+    lo, hi = eng.compute_y_bounds(f)
+    assert f.ylo is not None
+    lo, hi = lo.cpu().numpy(), hi.cpu().numpy()
+    assert (lo[:512] == ny).all() and (hi[:512] == 0).all()          # [n_y, 0): empty
+    assert lo[70 * nz + 33] == ny and lo[lo < ny].min() >= 9 and hi.max() <= ny - 6
+    clipped = scan()
+    rtol = bound(ny) + (4 * 2.0 ** -53 if layout == "wide" else 0.0)
+    rel = _against(free, ref, rtol, layout)
+    print("%s table scan, %s: worst relative difference %.3g of %.3g" % (layout, shape, rel, rtol))
+    assert np.array_equal(clipped.view(np.int64), free.view(np.int64)), layout
+
+
 # ---- n_y across the byte rule ------------------------------------------------------------------------
 @pytest.mark.parametrize("ny", [96, 320, 480, 2048])
 def test_ny_across_the_byte_rule(eng, ny):

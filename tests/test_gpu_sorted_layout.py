@@ -125,13 +125,17 @@ def test_sorted_layout_both_jets_nan_zero_inf_and_y_ranges(eng):
             _agree(got, ref, 1e-13)
             assert got[0, 5 * nz + 7].item() == 0.0 and got[0, 6 * nz + 9].item() == 0.0
             assert np.isinf(got[0, 3 * nz + 5].item()) and np.isinf(got[0, 100 * nz + 255].item())
-    # occupied y-ranges (from the producer): the same maps
-    eng.compute_y_bounds(fields)
+    # occupied y-ranges (from the producer): the same maps, and the grid-order scan's same bits
     bursts = _example_bursts()
+    free, path, layout = _scan(eng, fields, bursts, 1.0, sorted_=False)
+    assert (path, layout) == ("table", "grid")
+    eng.compute_y_bounds(fields)
     got, path, layout = _scan(eng, fields, bursts, 1.0)
     assert layout == "sorted"
-    ref = _scan(eng, fields, bursts, 1.0, sorted_=False)[0]
+    ref, path, layout = _scan(eng, fields, bursts, 1.0, sorted_=False)
+    assert (path, layout) == ("table", "grid")
     _agree(got, ref, 1e-13)
+    assert torch.equal(ref.view(torch.int64), free.view(torch.int64))
 
 
 def test_ff_step_is_scan_plus_maps_on_the_sorted_layout(eng):
