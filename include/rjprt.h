@@ -563,6 +563,46 @@ int rjp_ff_grad(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts
                 double* d_sumA, double* d_dsumA, double* d_ftot, double* d_dftot,
                 void* d_work, size_t work_bytes, void* stream);
 
+/* ---- K9: sensitivities of the formal-solution light curves to the burst parameters -------------
+ * rjp_ff_grad differentiates the isothermal light curves; this entry point differentiates
+ * rjp_ff_formal_sweep's.  For one sightline, cells i from the observer side back, c = h_ctau[f]:
+ *   b_i = |a0_i| chi_i^2   dtau_i = c b_i   om_i = 1 - e^-dtau_i   Theta_i = exp(-sum_{j<i} dtau_j)
+ *   I              = sum_i T_i om_i Theta_i                              (rjp_ff_formal's pixel)
+ *   g_ik           = db_i/dtheta_k, K7's three terms, non-zero only for the bursts of cell i's jet:
+ *                    |a0| 2 chi amp G 2 inv2s2 (d - t0),  |a0| 2 chi G,  |a0| 2 chi amp G (-(d - t0)^2)
+ *   D_ik           = sum_{j<i} g_jk
+ *   dI/dtheta_k    = sum_i c T_i Theta_i [ e^-dtau_i g_ik - om_i D_ik ]
+ * -- a cell's own emission rises with its opacity, and what lies behind it is hidden: the two terms
+ * have opposite signs.  ONE walk of the fields serves all epochs (lanes over epochs, as K8); the
+ * parameters are spread over workgroups in blocks of whole bursts.
+ * n_par = 3 (n[0] + n[1]); parameter k = 3 b + c exactly as in rjp_ff_grad: b counts the red jet's
+ * bursts first, then the blue jet's; c = 0: t0 [s], 1: amp_rel, 2: inv2s2 [s^-2].
+ * Outputs (device, any may be NULL, not all three):
+ *   d_ftot [e * F + f]                        rjp_ff_formal_sweep's d_ftot, BIT FOR BIT
+ *   d_dftot[(e * F + f) * n_par + k]          nansum_p of the derivative map
+ *   d_dout [((e * F + f) * n_par + k) * P + p] h_csrc[f] dI/dtheta_k: NaN exactly where
+ *                                             rjp_ff_formal's map is NaN (no T > 0 on the sightline;
+ *                                             such a pixel adds nothing to a total); an exact zero
+ *                                             where no cell of burst k's jet lies on the sightline
+ * Semantics as K8 and K7: a NaN a0, or a NaN launch time in a jet that has bursts, drops the cell;
+ * the cells of a jet WITHOUT bursts have chi = 1 whatever their launch time -- g = 0 there, and
+ * they still attenuate (the call applies the rule itself, d_ts is the model's own field); a
+ * Gaussian below 2^-1021 counts as zero in g; negative amplitudes are fine.  Sums in a fixed order
+ * without floating-point atomics: a repeated call, or a call with other outputs NULL, gives the
+ * same bits.  d_ylo / d_yhi are honoured; any RJP_F64 layout (tau, compact, wide).
+ * RJP_ERR_ARG, nothing enqueued and no output touched, for: a bad gff_mode, no burst at all, more
+ * than 8 bursts in a jet, a non-finite epoch or burst parameter, all three outputs NULL, NULL
+ * tables, n_epochs < 1, n_chan < 1, n_epochs * n_chan * n_par > 2^31 - 1, RJP_F32 fields, fields
+ * without d_ts or d_temp; RJP_ERR_WORKSPACE for d_work smaller than rjp_ff_formal_grad_workspace()
+ * (which is 0 for a non-positive argument). */
+size_t rjp_ff_formal_grad_workspace(int32_t nx, int32_t ny, int32_t nz, int32_t n_epochs,
+                                    int32_t n_par, int32_t n_chan);
+int rjp_ff_formal_grad(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
+                       const double* h_epochs_s, int32_t n_epochs, int32_t gff_mode,
+                       const double* h_ctau, const double* h_csrc, int32_t n_chan,
+                       double* d_ftot, double* d_dftot, double* d_dout,
+                       void* d_work, size_t work_bytes, void* stream);
+
 /* Map stage of intensity_rrl / flux_rrl (classes.py:1280-1282, 1339-1343;
  * rrls.py:444-449; physics.py:571-574):
  *   I_L = B_nu(tavg) exp(-tau_ff) (1 - exp(-tau_rrl)) 1e-3 ; S = I_L * omega / 1e-26

@@ -728,7 +728,7 @@ class JetModel:
         return freqs, E.ff_channel_coeffs(freqs, self.csize, self.params["target"]["dist"],
                                           self.gff_mode, gv)
 
-    def flux_vs_time_jac(self, times_s, freq):
+    def flux_vs_time_jac(self, times_s, freq, formal=False):
         """The light curves of `flux_vs_time` AND their exact derivatives with respect to the
         parameters of every ejection event: -> (flux[E, F] [Jy], jac[E, F, n_ej, 3]), the last axis
         (t_0 [s], peak_jml [kg/s], half_life [s]), `n_ej` in the order of `model.ejections`.
@@ -742,7 +742,14 @@ class JetModel:
         Jacobian (512 x 4096 x 512 dense cells, 32 epochs, 15 parameters: 34 ms for the 30 sweeps
         against 211 ms here; against sweeps on the epoch tiles this call is 2.1-5.1 x faster,
         DESIGN.md section 3, K7); this call is the one for sparse jets, sweeps of fewer than 12
-        epochs and exact derivatives."""
+        epochs and exact derivatives.
+        `formal=True`: the light curves of `flux_vs_time(formal=True)` (bit for bit) and THEIR
+        derivatives, from one line-of-sight walk for all epochs (`RTEngine.ff_formal_grad`,
+        rjp_ff_formal_grad) -- the route for a model whose temperature varies along the sightlines,
+        where the two Jacobians differ by more than 1e-3.  Any f64 layout (a model with negative
+        path factors included); f32 storage raises ValueError."""
+        if formal:
+            return self._flux_vs_time_jac_formal(times_s, freq)
         times = [float(t) for t in np.atleast_1d(np.asarray(times_s, float))]
         freqs, (ctau, cflux) = self._channel_coeffs(freq)
         dev = self._grad_fields()
@@ -759,6 +766,23 @@ class JetModel:
             return ftot.cpu().numpy(), jac
         _, _, ftot, dftot = eng.ff_grad(dev, self._rjp_bursts(), times, self.gff_mode,
                                         self._model_tavg(), ctau, cflux)
+        raw = dftot.cpu().numpy()
+        for i, (k, chain) in enumerate(slots):
+            jac[:, :, i, :] = raw[:, :, k:k + 3] * np.asarray(chain)
+        return ftot.cpu().numpy(), jac
+
+    def _flux_vs_time_jac_formal(self, times_s, freq):
+        if self._dtype != _lib.RJP_F64:
+            raise ValueError("burst-parameter sensitivities need f64 storage")
+        times = [float(t) for t in np.atleast_1d(np.asarray(times_s, float))]
+        freqs, (ctau, cflux) = self._channel_coeffs(freq)
+        slots = self._ejection_slots()
+        jac = np.zeros((len(times), len(freqs), len(slots), 3))
+        if not times or not slots:
+            return np.asarray(self.flux_vs_time(times, freqs, formal=True)).reshape(
+                len(times), len(freqs)), jac
+        ftot, dftot, _ = self.engine.ff_formal_grad(self.device_fields, self._rjp_bursts(), times,
+                                                    self.gff_mode, ctau, cflux)
         raw = dftot.cpu().numpy()
         for i, (k, chain) in enumerate(slots):
             jac[:, :, i, :] = raw[:, :, k:k + 3] * np.asarray(chain)

@@ -106,6 +106,62 @@ __device__ __forceinline__ double formal_out(bool hot, double cs, double I) {
   return hot ? cs * I : __builtin_nan("");
 }
 
+// ---- what the epoch-lane kernels (K8, K9 = ff_formal_grad.hip) share ---------------------------
+// Phase 1 of a slab: the thread's cell (row yy, sightline zz of row x) -> what does not depend on
+// the epoch: the signed a (|a0| as formal_a forms it, jet flag in the sign), T and ts; marks the
+// sightline hot where T > 0.  A cell outside the tile or the y-range is (0, 0, 0): dead.
+template <typename T, int LAY>
+__device__ __forceinline__ void formal_stage_cell(const FormalFields<T>& f, int x, int yy, int zz,
+                                                  int ye, int ny, int nz, int mode, int* s_hot_cz,
+                                                  rjp_d2& at, double& ts) {
+  double sa = 0.0, tk = 0.0;
+  ts = 0.0;
+  if (yy < ye && zz < nz) {
+    const int64_t o = ((int64_t)x * ny + yy) * nz + zz;
+    tk = (double)f.temp[o];
+    if (tk > 0.0) *s_hot_cz = 1;                      // (every writer stores the same value)
+    bool red;
+    const double a = formal_a<T, LAY>(f, o, mode, tk, red);
+    sa = red ? -a : a;
+    if (f.ts) ts = (double)f.ts[o];                   // (null without bursts: chi = 1 whatever ts)
+  }
+  at.x = sa;
+  at.y = tk;
+}
+
+// One plane of the tile, s_x[epoch lane * 16 + sightline] (a barrier lies between its writes and
+// this call): the map rows of the `ne` live epochs, 128-byte runs along z, to row[e * estride +
+// sightline], and the epoch's 16 values added in a fixed order (NaN pixels add nothing, as
+// nansum) to prow[e * pstride].  Either pointer may be null.  Ends with a barrier.
+__device__ __forceinline__ void formal_tile_emit(const double* s_x, int ne, int z0, int nz,
+                                                 double* row, int64_t estride, double* prow,
+                                                 int64_t pstride) {
+  constexpr int ZT = 16;
+  const int tid = threadIdx.x;
+  if (row) {
+    for (int i = tid; i < ne * ZT; i += kFB) {
+      const int zz = z0 + i % ZT;
+      if (zz < nz) row[(int64_t)(i / ZT) * estride + i % ZT] = s_x[i];
+    }
+  }
+  if (prow && tid < ne) {
+    double tot = 0.0;
+    for (int zz = 0; zz < ZT; ++zz) {
+      const double v = s_x[tid * ZT + zz];
+      tot += v == v ? v : 0.0;
+    }
+    prow[(int64_t)tid * pstride] = tot;
+  }
+  __syncthreads();
+}
+
+// Host: epochs [0, n64) go to blocks of 64 lanes, the tail to blocks of 16 unless it fills more
+// than three of them -- the only dead lanes are the last block's.
+inline int formal_epochs64(int n_epochs) {
+  const int n64 = n_epochs / RJP_WAVE * RJP_WAVE;
+  return n_epochs - n64 > 48 ? n_epochs : n64;
+}
+
 // Host: the fields as FormalFields<T> and the layout the scans of this model stream, handed to
 // go(fields, std::integral_constant<int, LAY>) -- tau layout (f64 only), compact, else wide.  `ts`:
 // the launch times the kernel is to see (K8 passes null without bursts).

@@ -75,20 +75,9 @@ __global__ __launch_bounds__(kFB, RJP_FORMAL_WAVES) void ff_formal_sweep_kernel(
   for (int yb = ya; yb < ye; yb += YC) {
     // ---- phase 1: signed a, T and ts of one cell per thread ----------------------------------
     {
-      const int yy = yb + cy, zz = z0 + cz;
-      double sa = 0.0, tk = 0.0, ts = 0.0;
-      if (yy < ye && zz < nz) {
-        const int64_t o = ((int64_t)x * ny + yy) * nz + zz;
-        tk = (double)f.temp[o];
-        if (tk > 0.0) s_hot[cz] = 1;                  // (every writer stores the same value)
-        bool red;
-        const double a = formal_a<T, LAY>(f, o, mode, tk, red);
-        sa = red ? -a : a;
-        if (f.ts) ts = (double)f.ts[o];               // (null without bursts: chi = 1 whatever ts)
-      }
       rjp_d2 v;
-      v.x = sa;
-      v.y = tk;
+      double ts;
+      formal_stage_cell<T, LAY>(f, x, yb + cy, z0 + cz, ye, ny, nz, mode, &s_hot[cz], v, ts);
       s_at[tid] = v;
       s_ts[tid] = ts;
     }
@@ -132,22 +121,10 @@ __global__ __launch_bounds__(kFB, RJP_FORMAL_WAVES) void ff_formal_sweep_kernel(
       for (int j = 0; j < NZP; ++j)
         s_x[el * ZT + cb + j] = formal_out(z0 + cb + j < nz && s_hot[cb + j], cs, I[j][k]);
       __syncthreads();
-      if (out) {
-        for (int i = tid; i < ne * ZT; i += kFB) {
-          const int zz = z0 + i % ZT;
-          if (zz < nz)
-            out[((int64_t)(e_blk + i / ZT) * nchan + f0 + k) * npix + (int64_t)x * nz + zz] = s_x[i];
-        }
-      }
-      if (part && tid < ne) {
-        double tot = 0.0;
-        for (int zz = 0; zz < ZT; ++zz) {
-          const double v = s_x[tid * ZT + zz];
-          tot += v == v ? v : 0.0;
-        }
-        part[((int64_t)(e_blk + tid) * nchan + f0 + k) * gridDim.x + blockIdx.x] = tot;
-      }
-      __syncthreads();
+      const int64_t pl0 = (int64_t)e_blk * nchan + f0 + k;        // the plane of the first epoch
+      formal_tile_emit(s_x, ne, z0, nz, out ? out + pl0 * npix + (int64_t)x * nz + z0 : nullptr,
+                       (int64_t)nchan * npix, part ? part + pl0 * gridDim.x + blockIdx.x : nullptr,
+                       (int64_t)nchan * gridDim.x);
     }
   }
 }
@@ -194,8 +171,7 @@ hipError_t sweep_launch_fc(const FormalFields<T>& f, const SweepArgs& a, int e_l
 // epoch lanes: blocks of 64 while they are full; a tail of up to 48 epochs by blocks of 16
 template <typename T, int LAY>
 hipError_t sweep_launch_le(const FormalFields<T>& f, const SweepArgs& a) {
-  int n64 = a.n_epochs / RJP_WAVE * RJP_WAVE;
-  if (a.n_epochs - n64 > 48) n64 = a.n_epochs;
+  const int n64 = formal_epochs64(a.n_epochs);
   if (n64 > 0) {
     const hipError_t e = sweep_launch_fc<T, LAY, 64>(f, a, 0, n64);
     if (e != hipSuccess) return e;

@@ -276,7 +276,8 @@ __device__ __forceinline__ double exp_any(double x) {
 // -tau = k ln2 + r,  1 - e^-tau = (1 - 2^k) - 2^k expm1(r), and 1 - 2^k is exact.  ~21
 // instructions against ~45 for libm's exp and the subtraction; tau = inf gives 1, NaN gives 1
 // (a tau map holds no NaN: its sums are nansums).
-__device__ __forceinline__ double one_minus_exp_neg(double tau) {
+// (the reduction and expm1(r): s = 2^k, em1 = expm1(r) with -tau = k ln2 + r)
+__device__ __forceinline__ void exp_neg_parts(double tau, double& s, double& em1) {
   const double L2E = 1.4426950408889634074;
   const double LN2_HI = 6.93147180369123816490e-01;
   const double LN2_LO = 1.90821492927058770002e-10;
@@ -292,8 +293,21 @@ __device__ __forceinline__ double one_minus_exp_neg(double tau) {
   g = __builtin_fma(g, r, RJP_EXP_C5);
   g = __builtin_fma(g, r, RJP_EXP_C4);
   g = __builtin_fma(g, r, RJP_EXP_C3);
-  const double em1 = __builtin_fma(r * r, __builtin_fma(r, g, 0.5), r);     // expm1(r)
-  const double s = __builtin_ldexp(1.0, (int)kd);                           // 2^k, k <= 0
+  em1 = __builtin_fma(r * r, __builtin_fma(r, g, 0.5), r);                  // expm1(r)
+  s = __builtin_ldexp(1.0, (int)kd);                                        // 2^k, k <= 0
+}
+__device__ __forceinline__ double one_minus_exp_neg(double tau) {
+  double s, em1;
+  exp_neg_parts(tau, s, em1);
+  return __builtin_fma(-s, em1, 1.0 - s);
+}
+// the same 1 - e^-tau (bit for bit) together with e^-tau = 2^k + 2^k expm1(r) at the same relative
+// error: where 1 - e^-tau has rounded to 1, e^-tau is still known (K9's attenuation; tau above
+// 800 counts as 800)
+__device__ __forceinline__ double one_minus_exp_neg(double tau, double& e) {
+  double s, em1;
+  exp_neg_parts(tau, s, em1);
+  e = __builtin_fma(s, em1, s);
   return __builtin_fma(-s, em1, 1.0 - s);
 }
 

@@ -1,6 +1,6 @@
 // Host-side interface between the translation units of librjprt (rjprt.hip = the C-ABI,
 // ff_scan.hip, ff_scan_inst.hip x 5, fields.hip, rrl_scan.hip, rrl_formal.hip, ff_grad.hip,
-// ff_formal_sweep.hip, ...): launch
+// ff_formal_sweep.hip, ff_formal_grad.hip, ...): launch
 // wrappers and the small structs they exchange.  Nothing here is exported; the library's surface is include/rjprt.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -199,6 +199,16 @@ hipError_t ff_grad_run(const rjp_fields* fl, const rjp_bursts* hb, const double*
                        const double* d_ctau, const double* d_cflux, int nchan, double* sumA,
                        double* dsumA, double* ftot, double* dftot, double* ws, size_t work_bytes,
                        hipStream_t st);
+
+// ---- ff_formal_grad.hip: sensitivities of K8's light curves to the burst parameters (K9) -------
+size_t ff_formal_grad_workspace_bytes(int nx, int nz, int n_epochs, int n_par, int n_chan);
+// d_scale[npar]: the constant each parameter's plane is multiplied with (2 amp inv2s2 for t0, 1
+// for amp_rel, -amp for inv2s2); `work` (ff_formal_grad_workspace_bytes) with ftot or dftot
+hipError_t ff_formal_grad_launch(const rjp_fields* fl, const rjp_bursts* hb,
+                                 const double* d_epochs, int n_epochs, int mode,
+                                 const double* d_ctau, const double* d_csrc, int nchan,
+                                 const double* d_scale, double* ftot, double* dftot, double* dout,
+                                 double* work, hipStream_t st);
 
 // ---- ff_scan_inst.hip: one slice of the K1 kernel family per translation unit -------------
 #define RJP_SCAN_SLICE_ARGS                                                                  \

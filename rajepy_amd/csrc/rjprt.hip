@@ -999,6 +999,68 @@ int rjp_ff_grad(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts
                        "ff_grad_run");
 }
 
+size_t rjp_ff_formal_grad_workspace(int32_t nx, int32_t ny, int32_t nz, int32_t n_epochs,
+                                    int32_t n_par, int32_t n_chan) {
+  if (nx <= 0 || ny <= 0 || nz <= 0 || n_epochs <= 0 || n_par <= 0 || n_chan <= 0) return 0;
+  return rjp::ff_formal_grad_workspace_bytes(nx, nz, n_epochs, n_par, n_chan);
+}
+
+int rjp_ff_formal_grad(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
+                       const double* h_epochs_s, int32_t n_epochs, int32_t gff_mode,
+                       const double* h_ctau, const double* h_csrc, int32_t n_chan,
+                       double* d_ftot, double* d_dftot, double* d_dout,
+                       void* d_work, size_t work_bytes, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (!mode_ok(gff_mode)) return fail(ctx, RJP_ERR_ARG, "bad gff_mode");
+  if (!fields) return fail(ctx, RJP_ERR_ARG, "fields is NULL");
+  if (fields->dtype != RJP_F64)
+    return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_grad: needs RJP_F64 fields");
+  if (int r = check_fields(ctx, fields, false, true, gff_mode)) return r;
+  if (!fields->d_temp || !fields->d_ts)
+    return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_grad: fields.d_temp and fields.d_ts required");
+  if (!bursts || bursts->n[0] + bursts->n[1] <= 0 || bursts->n[0] < 0 || bursts->n[1] < 0)
+    return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_grad: no burst to differentiate with respect to");
+  if (int r = check_bursts(ctx, bursts, fields)) return r;
+  if (bursts->n[0] > RJP_SGPR_BURSTS || bursts->n[1] > RJP_SGPR_BURSTS)
+    return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_grad: more than 8 bursts in a jet");
+  if (!h_epochs_s || n_epochs < 1)
+    return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_grad: NULL epochs or n_epochs < 1");
+  for (int e = 0; e < n_epochs; ++e)
+    if (!std::isfinite(h_epochs_s[e]))
+      return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_grad: non-finite epoch");
+  const int npar = 3 * (bursts->n[0] + bursts->n[1]);
+  std::vector<double> scale(npar, 1.0);
+  for (int j = 0, k = 0; j < 2; ++j)
+    for (int i = 0; i < bursts->n[j]; ++i, k += 3) {
+      const double t0 = bursts->t0[j][i], amp = bursts->amp_rel[j][i], inv = bursts->inv2s2[j][i];
+      if (!std::isfinite(t0) || !std::isfinite(amp) || !std::isfinite(inv))
+        return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_grad: non-finite burst parameter");
+      scale[k] = 2.0 * amp * inv;
+      scale[k + 2] = -amp;
+    }
+  if (!h_ctau || !h_csrc || n_chan < 1)
+    return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_grad: NULL table or n_chan < 1");
+  if (!d_ftot && !d_dftot && !d_dout)
+    return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_grad: all three outputs are NULL");
+  if ((int64_t)n_epochs * n_chan * npar > INT32_MAX)
+    return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_grad: n_epochs * n_chan * n_par exceeds 2^31 - 1");
+  if ((d_ftot || d_dftot) &&
+      (!d_work || work_bytes < rjp::ff_formal_grad_workspace_bytes(fields->nx, fields->nz, n_epochs,
+                                                                   npar, n_chan)))
+    return fail(ctx, RJP_ERR_WORKSPACE,
+                "rjp_ff_formal_grad: workspace smaller than rjp_ff_formal_grad_workspace()");
+  hipStream_t st = (hipStream_t)stream;
+  const double* src[4] = {h_ctau, h_csrc, h_epochs_s, scale.data()};
+  const size_t len[4] = {(size_t)n_chan, (size_t)n_chan, (size_t)n_epochs, scale.size()};
+  double* dev[4];
+  if (int r = stage_tables(ctx, st, src, len, 4, dev)) return r;
+  return finish_staged(ctx, st,
+                       rjp::ff_formal_grad_launch(fields, bursts, dev[2], n_epochs, gff_mode, dev[0],
+                                                  dev[1], n_chan, dev[3], d_ftot, d_dftot, d_dout,
+                                                  (double*)d_work, st),
+                       "ff_formal_grad_launch");
+}
+
 int rjp_rrl_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
                    double time_s, int32_t gff_mode, const rjp_line* line, const double* h_nu,
                    const double* h_ctau, const double* h_csrc, const double* h_hnu_k,

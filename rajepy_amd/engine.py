@@ -1050,6 +1050,33 @@ class RTEngine:
             self._stream()), self.ctx, "rjp_ff_grad")
         return sumA, dsumA, ftot, dftot
 
+    def ff_formal_grad(self, fields, bursts, epochs_s, gff_mode, ctau, csrc, want_maps=False):
+        """Sensitivities of the formal-solution light curves to the burst parameters
+        (rjp_ff_formal_grad): ONE walk of the fields for all of `epochs_s` [s] gives the totals of
+        `ff_formal_sweep` (bit for bit) and their exact derivatives with respect to (t0, amp_rel,
+        inv2s2) of every burst -- parameter k = 3 b + c as in `ff_grad`.
+        -> (ftot[E, F], dftot[E, F, n_par], dmaps[E, F, n_par, P] | None) device tensors (float64);
+        `dmaps` (csrc[f] dI/dtheta_k per pixel, NaN where `ff_formal`'s map is) only with
+        `want_maps`.  Any f64 layout of `fields`; at least one burst, at most 8 per jet;
+        `fields.ts` is read as it is.  `ctau`, `csrc` as for `ff_formal`."""
+        E, F = len(epochs_s), len(ctau)
+        if len(csrc) != F:
+            raise ValueError("ff_formal_grad: ctau and csrc must have one entry per channel")
+        nx, ny, nz = fields.shape
+        n_par = 3 * (int(bursts.n[0]) + int(bursts.n[1])) if bursts is not None else 0
+        ftot = self._f64(E, F)
+        dftot = self._f64(E, F, n_par)
+        dmaps = self._f64(E, F, n_par, fields.npix) if want_maps else None
+        work = self._workspace(max(1, self.lib.rjp_ff_formal_grad_workspace(nx, ny, nz, E, n_par, F)))
+        fs = fields.struct()
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        self._check(self.lib.rjp_ff_formal_grad(
+            self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None,
+            _lib.dbl_array(epochs_s), E, int(gff_mode), _lib.dbl_array(ctau),
+            _lib.dbl_array(csrc), F, ptr(ftot), ptr(dftot), ptr(dmaps), work.data_ptr(),
+            work.numel(), self._stream()), self.ctx, "rjp_ff_formal_grad")
+        return ftot, dftot, dmaps
+
     def rrl_cells(self, fields, bursts, time_s, line, nus):
         """collapse=False: per-cell RRL optical depths -> device tensor [F, N]."""
         F = len(nus)
