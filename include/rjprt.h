@@ -642,6 +642,38 @@ int rjp_rrl_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bur
                    const double* h_ctau, const double* h_csrc, const double* h_hnu_k,
                    int32_t n_chan, const double* d_add, double* d_out, void* stream);
 
+/* ---- K10: model visibilities of a stack of maps at given (u, v) points --------------------------
+ * An interferometer samples the Fourier transform of the sky; the reference reaches that plane only
+ * through FITS files and CASA simobserve, outside this library.  This entry
+ * point evaluates the transform of any stack of maps directly at the baselines the caller gives --
+ * a direct sum, no gridding, no FFT:
+ *   V[m, k] = sum_{ix, iz} I[m, ix nz + iz] exp(-2 pi i (a (ix - (nx-1)/2) + b (iz - (nz-1)/2)))
+ *             a = h_su[m] d_u[k],  b = h_sv[m] d_v[k]                      (cycles per cell)
+ *   d_maps [n_maps * P]      float64 maps in the library's pixel order p = ix nz + iz: the fluxes of
+ *                            the ff / rrl map stages and formal solutions, or K9's d_dout (the
+ *                            transform is linear: derivative maps give dV/dtheta)
+ *   h_su, h_sv [n_maps]      HOST: cycles per cell per unit of d_u / d_v, signs included -- the ABI
+ *                            carries no sky convention (every channel has its own scale)
+ *   d_u, d_v [n_vis]         the baselines, in the unit the scales are per
+ *   d_vis [n_maps][n_vis][2] (re, im)
+ * A NaN pixel adds nothing (the nansum rule of every total here; the maps are NaN off the jet); a map
+ * that is NaN everywhere gives exact zeros.  A non-finite d_u[k] or d_v[k] makes visibility k NaN
+ * (in every map) and no other.  The sums run in a fixed order without floating-point atomics: a
+ * repeated call gives the same bits.
+ * ARGUMENT RANGE: every phase a (ix - (nx-1)/2), b (iz - (nz-1)/2) is formed as one double product
+ * and reduced to a quarter turn; that needs |a| nx / 2 and |b| nz / 2 below 2^29 cycles (beyond, the
+ * result is meaningless, not refused: the baselines live on the device).  The product's rounding
+ * costs 2 pi (|a| nx / 2 + |b| nz / 2) 2^-53 of sum |I|: 1e-16 per cycle across the map.
+ * Everything else is validated before anything is enqueued, and no output is touched on a refusal:
+ * RJP_ERR_ARG for a NULL pointer, n_maps, nx, nz or n_vis < 1, a non-finite h_su / h_sv, or more
+ * than 2^31 - 1 tiles (n_maps x ceil(nx / 128) x ceil(n_vis / 64)); RJP_ERR_WORKSPACE for a d_work
+ * smaller than the workspace query (16 bytes per map, visibility and tile of 128 x-rows; 0 from it
+ * = a bad argument). */
+size_t rjp_vis_workspace(int32_t n_maps, int32_t nx, int32_t nz, int32_t n_vis);
+int rjp_vis(rjp_ctx* ctx, const double* d_maps, int32_t n_maps, int32_t nx, int32_t nz,
+            const double* h_su, const double* h_sv, const double* d_u, const double* d_v,
+            int32_t n_vis, double* d_vis, void* d_work, size_t work_bytes, void* stream);
+
 /* ---- K4: geometry -> fields on the device --------------------------------------------
  * Replaces the lazily cached grids of JetModel (fill_factor/areas classes.py:657-669,
  * 763-764; grid_rwp 521-525; rreff 549-555; _nd 877-897; ion_fraction 915-934;

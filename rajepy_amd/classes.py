@@ -875,7 +875,8 @@ class JetModel:
         self._save_cube(tau, savefits, 'tau', freq)
         return tau
 
-    def _rrl_flux(self, rrl, freq, lte, contsub, intensity=False, formal=False):
+    def _rrl_flux(self, rrl, freq, lte, contsub, intensity=False, formal=False, device=False):
+        """`device`: the [F, P] device cube itself, nothing copied to the host."""
         from . import engine as E
         if not lte:
             raise ValueError("Non-LTE RRL calculations not yet supported")   # classes.py:1261
@@ -900,6 +901,8 @@ class JetModel:
                                           float(self.time), self.gff_mode,
                                           _lib.Line(**mrrl.line_constants(rrl)), freqs, ctau, cfl,
                                           hnu, add=add)
+            if device:
+                return flux
             out = self._map(flux, (F,))
             self._dev_product = flux.reshape(F, self.nx, self.nz)
             return out[0] if scalar else out
@@ -913,6 +916,8 @@ class JetModel:
             cfl = cfl / (E.solid_angle(self.csize, self.params["target"]["dist"]) / 1e-26)
         flux, _ = self.engine.rrl_maps(tau_rrl, tau_ff, self._model_tavg(), flux_ff, cfl, hnu,
                                        want_ftot=False)
+        if device:
+            return flux
         out = self._map(flux, (F,))
         self._dev_product = flux.reshape(F, self.nx, self.nz)
         return out[0] if scalar else out
@@ -936,6 +941,118 @@ class JetModel:
         fluxes = self._rrl_flux(rrl, freq, lte, contsub, formal=formal)
         self._save_cube(fluxes, savefits, 'flux', freq, formal=formal)
         return fluxes
+
+    # ------------------------------------------------------------------ visibilities ----
+    VIS_STACK_BYTES = 1 << 30    # most bytes of maps one `RTEngine.vis` call of a sweep transforms
+
+    def _vis_scales(self, freqs):
+        from . import engine as E
+        return E.vis_scales(freqs, self.csize, self.params["target"]["dist"])
+
+    def _vis_chunk(self, maps_per_epoch):
+        """Epochs per chunk of a sweep so that the map stack stays under VIS_STACK_BYTES."""
+        per = int(maps_per_epoch) * self.nx * self.nz * 8
+        return max(1, self.VIS_STACK_BYTES // per)
+
+    def visibilities_ff(self, u_m, v_m, freq, formal=False):
+        """Noise-free model visibilities [Jy] of the `flux_ff` maps at the model's time, at the
+        baselines (`u_m`, `v_m`) in metres -> complex array (F, K).  The direct Fourier sum of
+        every channel's map at its own (u, v) / lambda (`RTEngine.vis`, rjp_vis; convention:
+        `engine.vis_scales` -- phase centre = map centre, RA decreasing with ix); the maps stay on
+        the device.  V(0, 0) is the total flux `flux_vs_time` returns.  `formal`: as `flux_ff`.
+        Inside a torch.distributed group the call runs on the calling rank only."""
+        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
+        maps = self._ff_products(freqs, flux=True, device=True, formal=formal)
+        su, sv = self._vis_scales(freqs)
+        return self.engine.vis(maps.reshape(len(freqs), -1), self.nx, self.nz, su, sv,
+                               u_m, v_m).cpu().numpy()
+
+    def visibilities_rrl(self, rrl, u_m, v_m, freq, contsub=True, formal=False):
+        """Model visibilities [Jy] of the `flux_rrl` maps (same arguments) -> complex (F, K); see
+        `visibilities_ff`."""
+        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
+        maps = self._rrl_flux(rrl, freqs, True, contsub, formal=formal, device=True)
+        su, sv = self._vis_scales(freqs)
+        return self.engine.vis(maps.reshape(len(freqs), -1), self.nx, self.nz, su, sv,
+                               u_m, v_m).cpu().numpy()
+
+    def visibilities_vs_time(self, times_s, u_m, v_m, freq, formal=False):
+        """Model visibilities [Jy] of the continuum at every (model time, frequency, baseline)
+        -> complex array (E, F, K): `visibilities_ff` at each of `times_s` [s], without touching
+        `model.time`.  `formal=True`: the maps of one line-of-sight walk per chunk of epochs
+        (`RTEngine.ff_formal_sweep`), else the isothermal maps (`prefetch_epochs` + `ff_maps`);
+        epochs are processed in chunks whose map stack stays under 1 GiB.  Calling rank only."""
+        eng = self.engine
+        times = [float(t) for t in np.atleast_1d(np.asarray(times_s, float))]
+        freqs, (ctau, cflux) = self._channel_coeffs(freq)
+        F = len(freqs)
+        su, sv = self._vis_scales(freqs)
+        u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
+        out = np.zeros((len(times), F, int(u_d.numel())), dtype=np.complex128)
+        step = self._vis_chunk(F)
+        if not formal:
+            step = min(step, self.SCAN_CACHE_EPOCHS)     # what one prefetch keeps resident
+        for e0 in range(0, len(times), step):
+            chunk = times[e0:e0 + step]
+            if formal:
+                maps, _ = eng.ff_formal_sweep(self.device_fields, self._rjp_bursts(), chunk,
+                                              self.gff_mode, ctau, cflux, want_maps=True,
+                                              want_totals=False)
+            else:
+                import torch
+                self.prefetch_epochs(chunk, want_em=False)
+                rows = []
+                for t in chunk:
+                    if t not in self._scan_cache:    # evicted by the chunk's own new epochs
+                        self.prefetch_epochs([t], want_em=False)
+                    rows.append(self._scan_cache[t][0])
+                sumA = torch.cat(rows, dim=0)
+                maps = eng.ff_maps(sumA, self._model_tavg(), ctau, cflux, want_tau=False,
+                                   want_ftot=False)[1]
+            V = eng.vis(maps.reshape(len(chunk) * F, -1), self.nx, self.nz,
+                        np.tile(su, len(chunk)), np.tile(sv, len(chunk)), u_d, v_d)
+            out[e0:e0 + len(chunk)] = V.cpu().numpy().reshape(len(chunk), F, -1)
+            del maps, V
+        return out
+
+    def visibilities_vs_time_jac(self, times_s, u_m, v_m, freq):
+        """The visibilities of `visibilities_vs_time(formal=True)` (bit for bit) AND their exact
+        derivatives with respect to the parameters of every ejection event -> (V[E, F, K],
+        dV[E, F, n_ej, 3, K]), axis 3 = (t_0 [s], peak_jml [kg/s], half_life [s]), `n_ej` in the
+        order of `model.ejections`: the transform is linear, so the derivative maps of
+        `RTEngine.ff_formal_grad` go through the same `RTEngine.vis` and `ejection_chain_rule`,
+        as `flux_vs_time_jac(formal=True)` does for the totals (dV at u = v = 0 is its Jacobian).
+        Chunks of epochs whose derivative maps stay under 1 GiB.  f32 storage raises ValueError;
+        a model without ejections returns n_ej = 0.  Calling rank only."""
+        if self._dtype != _lib.RJP_F64:
+            raise ValueError("burst-parameter sensitivities need f64 storage")
+        eng = self.engine
+        times = [float(t) for t in np.atleast_1d(np.asarray(times_s, float))]
+        freqs, (ctau, cflux) = self._channel_coeffs(freq)
+        F = len(freqs)
+        u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
+        K = int(u_d.numel())
+        slots = self._ejection_slots()
+        V = self.visibilities_vs_time(times, u_d, v_d, freqs, formal=True)
+        dV = np.zeros((len(times), F, len(slots), 3, K), dtype=np.complex128)
+        if not times or not slots:
+            return V, dV
+        bursts = self._rjp_bursts()
+        n_par = 3 * (int(bursts.n[0]) + int(bursts.n[1]))
+        su, sv = self._vis_scales(freqs)
+        su, sv = np.repeat(su, n_par), np.repeat(sv, n_par)
+        step = self._vis_chunk(F * n_par)
+        for e0 in range(0, len(times), step):
+            chunk = times[e0:e0 + step]
+            dmaps = eng.ff_formal_grad(self.device_fields, bursts, chunk, self.gff_mode, ctau,
+                                       cflux, want_maps=True)[2]
+            raw = eng.vis(dmaps.reshape(len(chunk) * F * n_par, -1), self.nx, self.nz,
+                          np.tile(su, len(chunk)), np.tile(sv, len(chunk)), u_d, v_d)
+            raw = raw.cpu().numpy().reshape(len(chunk), F, n_par, K)
+            del dmaps
+            for i, (k, chain) in enumerate(slots):
+                dV[e0:e0 + len(chunk), :, i] = raw[:, :, k:k + 3] * np.asarray(chain)[:, None]
+        return V, dV
 
     # ------------------------------------------------------------------ products ----
     FORMAL_HISTORY = "Formal solution along the line of sight, observer at iy = 0"

@@ -765,3 +765,35 @@ __host__ __device__ __forceinline__ double hash_u01(uint64_t seed, uint64_t fiel
   uint64_t h = splitmix64(seed ^ (field << 60) ^ cell);
   return (double)(h >> 11) * (1.0 / 9007199254740992.0);
 }
+
+// ---- sin / cos of an argument in turns --------------------------------------------------------
+// sin(2 pi u), cos(2 pi u): quarter-turn reduction, Taylor polynomials on |w| <= pi/4
+// (truncation < 2e-14 / 1e-15).  |u| < 2^30.  Used by the Voigt pole terms (rrl_voigt.h) and the
+// phasors of K10 (vis.hip).
+__device__ __forceinline__ void sincos_2pi(double u, double& sn, double& cs) {
+  const double k = __builtin_rint(4.0 * u);
+  const double w = 6.28318530717958647692 * __builtin_fma(-0.25, k, u);
+  const double w2 = w * w;
+  double ps = -7.6471637318198164759e-13;                 // -1/15!
+  ps = __builtin_fma(ps, w2, 1.6059043836821614599e-10);  //  1/13!
+  ps = __builtin_fma(ps, w2, -2.5052108385441718775e-08); // -1/11!
+  ps = __builtin_fma(ps, w2, 2.7557319223985890653e-06);  //  1/9!
+  ps = __builtin_fma(ps, w2, -1.9841269841269841253e-04); // -1/7!
+  ps = __builtin_fma(ps, w2, 8.3333333333333332177e-03);  //  1/5!
+  ps = __builtin_fma(ps, w2, -1.6666666666666665741e-01); // -1/3!
+  const double s0 = __builtin_fma(ps * w2, w, w);
+  double pc = 4.7794773323873852974e-14;                  //  1/16!
+  pc = __builtin_fma(pc, w2, -1.1470745597729724714e-11); // -1/14!
+  pc = __builtin_fma(pc, w2, 2.0876756987868098979e-09);  //  1/12!
+  pc = __builtin_fma(pc, w2, -2.7557319223985888276e-07); // -1/10!
+  pc = __builtin_fma(pc, w2, 2.4801587301587301566e-05);  //  1/8!
+  pc = __builtin_fma(pc, w2, -1.3888888888888889419e-03); // -1/6!
+  pc = __builtin_fma(pc, w2, 4.1666666666666664354e-02);  //  1/4!
+  pc = __builtin_fma(pc, w2, -0.5);
+  const double c0 = __builtin_fma(pc, w2, 1.0);
+  const int q = (int)k & 3;
+  const double a = (q & 1) ? c0 : s0;       // q=0: s,c  q=1: c,-s  q=2: -s,-c  q=3: -c,s
+  const double b = (q & 1) ? s0 : c0;
+  sn = (q & 2) ? -a : a;
+  cs = (q == 1 || q == 2) ? -b : b;
+}

@@ -1,6 +1,6 @@
 // Host-side interface between the translation units of librjprt (rjprt.hip = the C-ABI,
 // ff_scan.hip, ff_scan_inst.hip x 5, fields.hip, rrl_scan.hip, rrl_formal.hip, ff_grad.hip,
-// ff_formal_sweep.hip, ff_formal_grad.hip, ...): launch
+// ff_formal_sweep.hip, ff_formal_grad.hip, vis.hip, ...): launch
 // wrappers and the small structs they exchange.  Nothing here is exported; the library's surface is include/rjprt.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -209,6 +209,16 @@ hipError_t ff_formal_grad_launch(const rjp_fields* fl, const rjp_bursts* hb,
                                  const double* d_ctau, const double* d_csrc, int nchan,
                                  const double* d_scale, double* ftot, double* dftot, double* dout,
                                  double* work, hipStream_t st);
+
+// ---- vis.hip: visibilities of a stack of maps at given (u, v) points (K10) ----------------------
+size_t vis_workspace_bytes(int n_maps, int nx, int nz, int n_vis);
+// false: more workgroups than one launch takes
+bool vis_grid_ok(int n_maps, int nx, int n_vis);
+// d_su / d_sv[n_maps]: device copies of the scales; `part` (vis_workspace_bytes) holds the row
+// tiles' partial sums when nx spans more than one tile
+hipError_t vis_launch(const double* maps, int n_maps, int nx, int nz, const double* d_su,
+                      const double* d_sv, const double* u, const double* v, int n_vis, double* vis,
+                      double* part, hipStream_t st);
 
 // ---- ff_scan_inst.hip: one slice of the K1 kernel family per translation unit -------------
 #define RJP_SCAN_SLICE_ARGS                                                                  \

@@ -1061,6 +1061,39 @@ int rjp_ff_formal_grad(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts*
                        "ff_formal_grad_launch");
 }
 
+size_t rjp_vis_workspace(int32_t n_maps, int32_t nx, int32_t nz, int32_t n_vis) {
+  if (n_maps <= 0 || nx <= 0 || nz <= 0 || n_vis <= 0) return 0;
+  return rjp::vis_workspace_bytes(n_maps, nx, nz, n_vis);
+}
+
+int rjp_vis(rjp_ctx* ctx, const double* d_maps, int32_t n_maps, int32_t nx, int32_t nz,
+            const double* h_su, const double* h_sv, const double* d_u, const double* d_v,
+            int32_t n_vis, double* d_vis, void* d_work, size_t work_bytes, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (!d_maps || !h_su || !h_sv || !d_u || !d_v || !d_vis)
+    return fail(ctx, RJP_ERR_ARG, "rjp_vis: NULL maps, scales, baselines or output");
+  if (n_maps < 1 || nx < 1 || nz < 1 || n_vis < 1)
+    return fail(ctx, RJP_ERR_ARG, "rjp_vis: n_maps, nx, nz and n_vis must be positive");
+  for (int m = 0; m < n_maps; ++m)
+    if (!std::isfinite(h_su[m]) || !std::isfinite(h_sv[m]))
+      return fail(ctx, RJP_ERR_ARG, "rjp_vis: non-finite h_su / h_sv");
+  if (!rjp::vis_grid_ok(n_maps, nx, n_vis))
+    return fail(ctx, RJP_ERR_ARG, "rjp_vis: more than 2^31 - 1 tiles");
+  const size_t need = rjp::vis_workspace_bytes(n_maps, nx, nz, n_vis);
+  if (need == 0) return fail(ctx, RJP_ERR_ARG, "rjp_vis: the workspace size overflows");
+  if (!d_work || work_bytes < need)
+    return fail(ctx, RJP_ERR_WORKSPACE, "rjp_vis: workspace smaller than rjp_vis_workspace()");
+  hipStream_t st = (hipStream_t)stream;
+  const double* src[2] = {h_su, h_sv};
+  const size_t len[2] = {(size_t)n_maps, (size_t)n_maps};
+  double* dev[2];
+  if (int r = stage_tables(ctx, st, src, len, 2, dev)) return r;
+  return finish_staged(ctx, st,
+                       rjp::vis_launch(d_maps, n_maps, nx, nz, dev[0], dev[1], d_u, d_v, n_vis,
+                                       d_vis, (double*)d_work, st),
+                       "vis_launch");
+}
+
 int rjp_rrl_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
                    double time_s, int32_t gff_mode, const rjp_line* line, const double* h_nu,
                    const double* h_ctau, const double* h_csrc, const double* h_hnu_k,

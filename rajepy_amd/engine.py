@@ -1077,6 +1077,47 @@ class RTEngine:
             work.numel(), self._stream()), self.ctx, "rjp_ff_formal_grad")
         return ftot, dftot, dmaps
 
+    # -- K10 -----------------------------------------------------------------------------------
+    def _device_f64(self, values):
+        """Host array or tensor -> contiguous float64 vector on this engine's device."""
+        torch = _torch()
+        if not isinstance(values, torch.Tensor):
+            values = torch.from_numpy(np.ascontiguousarray(values, dtype=np.float64).reshape(-1))
+        return values.to(device=self.device, dtype=torch.float64).reshape(-1).contiguous()
+
+    def vis(self, maps, nx, nz, su, sv, u, v):
+        """Model visibilities of a stack of maps (rjp_vis): the direct Fourier sum
+        V[m, k] = sum_{ix, iz} maps[m, ix nz + iz] exp(-2 pi i (su[m] u[k] (ix - (nx-1)/2) +
+        sv[m] v[k] (iz - (nz-1)/2))) -> complex128 device tensor [n_maps, n_vis].
+        `maps`: float64 device tensor of n_maps * nx * nz values in the library's pixel order (any
+        flux stack of this engine, or the derivative maps of `ff_formal_grad`); NaN pixels add
+        nothing.  `su`, `sv` [n_maps]: cycles per cell per unit of `u`, `v` (`vis_scales` builds
+        them for baselines in metres); `u`, `v` [n_vis]: host arrays or device tensors.  Sums in a
+        fixed order: a repeated call gives the same bits."""
+        torch = _torch()
+        nx, nz = int(nx), int(nz)
+        if not (isinstance(maps, torch.Tensor) and maps.dtype == torch.float64 and
+                maps.device == self.device and maps.is_contiguous()):
+            raise ValueError("vis: `maps` must be a contiguous float64 tensor on %s" % self.device)
+        if nx < 1 or nz < 1 or maps.numel() == 0 or maps.numel() % (nx * nz):
+            raise ValueError("vis: `maps` must hold a whole number (>= 1) of nx * nz maps")
+        M = maps.numel() // (nx * nz)
+        su = np.ascontiguousarray(su, dtype=np.float64).reshape(-1)
+        sv = np.ascontiguousarray(sv, dtype=np.float64).reshape(-1)
+        if su.size != M or sv.size != M:
+            raise ValueError("vis: su and sv must have one entry per map (%d)" % M)
+        du, dv = self._device_f64(u), self._device_f64(v)
+        K = du.numel()
+        if K < 1 or dv.numel() != K:
+            raise ValueError("vis: u and v must have the same length >= 1")
+        out = self._f64(M, K, 2)
+        work = self._workspace(max(1, self.lib.rjp_vis_workspace(M, nx, nz, K)))
+        self._check(self.lib.rjp_vis(
+            self.ctx, maps.data_ptr(), M, nx, nz, _lib.dbl_array(su), _lib.dbl_array(sv),
+            du.data_ptr(), dv.data_ptr(), K, out.data_ptr(), work.data_ptr(), work.numel(),
+            self._stream()), self.ctx, "rjp_vis")
+        return torch.view_as_complex(out)
+
     def rrl_cells(self, fields, bursts, time_s, line, nus):
         """collapse=False: per-cell RRL optical depths -> device tensor [F, N]."""
         F = len(nus)
@@ -1152,6 +1193,21 @@ class RTEngine:
 # -- host-side per-channel coefficients (scalars; classes.py:1395-1397, 1473-1475, 1519-1521) --
 def solid_angle(csize_au, dist_pc):
     return np.arctan((csize_au * con.au) / (dist_pc * con.parsec)) ** 2.
+
+
+def vis_scales(freqs, csize_au, dist_pc):
+    """su[f], sv[f] of `RTEngine.vis` / rjp_vis for baselines (u, v) in METRES, as measurement sets
+    store them -- the one place that holds the sky convention:
+      * V(u, v) = sum_p I_p exp(-2 pi i (u l_p + v m_p)), (l, m) the direction cosines towards
+        East (RA) and North (Dec), u and v in wavelengths = metres * nu / c;
+      * the phase centre is the map centre, pixel ((nx-1)/2, (nz-1)/2): CRPIX of `save_fits`;
+      * one cell subtends cell = arctan(csize au / (dist pc)) radians (the square root of
+        `solid_angle`); the FITS header `save_fits` writes has CDELT1 < 0 -- RA decreases with
+        ix -- and CDELT2 > 0, so l = -cell (ix - (nx-1)/2), m = +cell (iz - (nz-1)/2):
+        su = -cell nu / c,  sv = +cell nu / c   [cycles per cell per metre]."""
+    freqs = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
+    cell = np.arctan((csize_au * con.au) / (dist_pc * con.parsec))
+    return -cell * freqs / con.c, cell * freqs / con.c
 
 
 def ff_channel_coeffs(freqs, csize_au, dist_pc, gff_mode, gff_values=None):
