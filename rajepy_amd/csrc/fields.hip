@@ -1,6 +1,8 @@
 // Field layout kernels: upload packing, K4 (geometry -> fields on the device) and the
 // synthetic dense-field generator of the measurement harness.
 #include <algorithm>
+#include <cmath>
+#include <string>
 
 #include "rjp_host.h"
 
@@ -270,7 +272,7 @@ __device__ __forceinline__ double powerlaw(double zero, double rho_, double reff
 // below kHypStop of the sum ends the series -- but only once the denominators beta + 1 + k are
 // positive and the term ratio is below 1: with beta = a - b < 0 (the connection formula) the terms
 // first fall, far below kHypStop for large b, and rise again to order one around
-// k = (b - a)(1 + 1/A); a series cut in the dip is wrong by that hump.  hyp_plan (rjprt.hip) keeps
+// k = (b - a)(1 + 1/A); a series cut in the dip is wrong by that hump.  hyp_plan (below) keeps
 // every series the kernel meets within kHypMaxTerms.
 __device__ __forceinline__ double hyp_series(double a, double beta, double s) {
   double term = 1.0, sum = 1.0;
@@ -451,6 +453,138 @@ hipError_t build_fields_launch(const GeomDev& g, int dtype, void* nd, void* xi, 
                        (float*)xi, (float*)temp, (float*)pf, (float*)ts, (float*)vy, ff_raw,
                        areas_raw, vx_raw, vz_raw, (float*)nullptr, (float*)nullptr, 0);
   return hipGetLastError();
+}
+
+// ---- K4's 2F1: which series where ---------------------------------------------------------------
+// hyp_series (above) on the host, also returning the largest |term| (the leading 1 included)
+// and the number of terms taken (kHypMaxTerms + 1: the series did not end).
+struct HypSum { double sum, big; int taken; };
+
+static HypSum hyp_series_host(double a, double beta, double s) {
+  HypSum r = {1.0, 1.0, kHypMaxTerms + 1};
+  double term = 1.0;
+  for (int k = 0; k < kHypMaxTerms; ++k) {
+    const double den = beta + 1.0 + k;
+    const double ratio = (a + k) / den * s;
+    term *= ratio;
+    r.sum += term;
+    r.big = std::max(r.big, fabs(term));
+    if (fabs(term) <= kHypStop * fabs(r.sum) && den > 0.0 && fabs(ratio) < 1.0) {
+      r.taken = k + 1;
+      break;
+    }
+  }
+  return r;
+}
+
+// Gamma(b + 1) Gamma(a - b) / Gamma(a); through lgamma where a factor leaves the double range
+// (b + 1 > 171: inf * 0)
+static double hyp_gamma_ratio(double b, double amb, double a) {
+  const double v = tgamma(b + 1.) * tgamma(amb) / tgamma(a);
+  if (std::isfinite(v) && v != 0.0) return v;
+  int s1 = 1, s2 = 1, s3 = 1;
+  const double lg = lgamma_r(b + 1., &s1) + lgamma_r(amb, &s2) - lgamma_r(a, &s3);
+  return (double)(s1 * s2 * s3) * exp(lg);
+}
+
+// The launch-time integral A^a 2F1(a, b; b + 1; -A) is summed by the Pfaff series for A <= switch
+// and by the 1/z connection formula above it (hyp_flow_factor).  The connection
+// formula is sound from A = 1 on for b of a few units.  For large b (narrow jets: b ~ 1/eps) its
+// series first falls and then comes back to order one around k = (b - a)(1 + 1/A): hundreds of
+// terms near A = 1.  For a - b within ~1e-4 of a non-positive integer its two parts cancel like
+// 1/(distance A).  So the switch is the smallest of kHypSwitch at which (probed at five A from the
+// switch upwards) the connection formula ends within kHypConnTerms terms and loses at most
+// kHypMaxLoss to cancellation, while the Pfaff series ends within kHypMaxTerms at the switch; +inf
+// (the Pfaff series for every A) serves large b.  No such switch: refused (false).
+static bool hyp_plan(double a, double b, double* k1, double* k2, double* a_switch) {
+  constexpr double kHypSwitch[] = {1.0, 1.25, 1.5, 2.0, 3.0, 4.0, 6.0, 8.0, 16.0, 64.0, HUGE_VAL};
+  constexpr double kHypProbe[] = {1.0, 1.5, 2.0, 4.0, 16.0};
+  constexpr int kHypConnTerms = 100;
+  constexpr double kHypMaxLoss = 4096.0;
+  const double amb = a - b;
+  auto nonpos_int = [](double v, double tol) { return v < 0.5 && fabs(v - nearbyint(v)) < tol; };
+  if (nonpos_int(amb, 1e-9) || nonpos_int(b, 1e-6) || nonpos_int(b + 1., 1e-6) || b == a)
+    return false;
+  *k1 = b / (b - a);
+  *k2 = (a <= 0.0 && a == nearbyint(a)) ? 0.0 : hyp_gamma_ratio(b, amb, a);
+  if (!std::isfinite(*k1) || !std::isfinite(*k2)) return false;
+  for (double sw : kHypSwitch) {
+    const bool all = !std::isfinite(sw);
+    if (hyp_series_host(a, b, all ? 1.0 : sw / (1.0 + sw)).taken > kHypMaxTerms)
+      return false;                                   // a larger switch needs still more terms
+    bool ok = true;
+    for (int i = 0; ok && !all && i < 5; ++i) {
+      const double A = sw * kHypProbe[i];
+      const double sa = pow(A / (1.0 + A), a);
+      const HypSum c = hyp_series_host(a, amb, 1.0 / (1.0 + A));
+      const double t2 = *k2 * pow(A, amb);
+      const double tot = sa * *k1 * c.sum + t2;
+      const double loss = std::max(fabs(sa * *k1) * c.big, fabs(t2)) / fabs(tot);
+      ok = c.taken <= kHypConnTerms && loss <= kHypMaxLoss;      // (false for NaN)
+    }
+    if (ok) {
+      *a_switch = sw;
+      return true;
+    }
+  }
+  return false;
+}
+
+// K4's host half: rjp_geometry -> the kernel's GeomDev (rotations, SI lengths, the launch-time
+// constants and, with `want_ts`, the plan of the 2F1).  Returns RJP_OK, or the status and message
+// rjp_build_fields refuses the model with (an x-slab outside the grid; RJP_ERR_DEGENERATE).
+int geometry_to_dev(const rjp_geometry* gm, bool want_ts, GeomDev& g, std::string& err) {
+  auto refuse = [&](int code, const char* what) {
+    err = what;
+    return code;
+  };
+  const double au = 149597870700.0, d2r = M_PI / 180.0;
+  g.nx = gm->nx; g.ny = gm->ny; g.nz = gm->nz; g.ccw = gm->rotation_ccw;
+  g.nx_total = gm->nx_total > 0 ? gm->nx_total : gm->nx;
+  g.ix0 = gm->ix0;
+  if (g.ix0 < 0 || g.ix0 + g.nx > g.nx_total)
+    return refuse(RJP_ERR_ARG, "rjp_build_fields: x-slab [ix0, ix0+nx) outside [0, nx_total)");
+  g.cs = gm->csize;
+  // numpy.radians(x) = x * (pi/180); cos/sin in libm double, as maths/geometry.py:249-253
+  const double a = (gm->inc - 90.) * d2r, b = gm->pa * d2r;
+  g.ca = cos(a); g.sa = sin(a); g.cb = cos(b); g.sb = sin(b);
+  const double a2 = (90. - gm->inc) * d2r, b2 = -gm->pa * d2r;
+  g.ca2 = cos(a2); g.sa2 = sin(a2); g.cb2 = cos(b2); g.sb2 = sin(b2);
+  g.w_0 = gm->w_0; g.r_0 = gm->r_0; g.mr0 = gm->mod_r_0; g.eps = gm->epsilon;
+  g.R_1 = gm->R_1; g.R_2 = gm->R_2;
+  g.gm = 6.6743e-11 * gm->M_star * 1.98847e30;
+  g.v_lsr = gm->v_lsr;
+  g.n_0 = gm->n_0; g.x_0 = gm->x_0; g.T_0 = gm->T_0; g.v_0 = gm->v_0;
+  g.q_n = gm->q_n; g.q_x = gm->q_x; g.q_T = gm->q_T; g.q_v = gm->q_v;
+  g.qd_n = gm->qd_n; g.qd_x = gm->qd_x; g.qd_T = gm->qd_T; g.qd_v = gm->qd_v;
+  g.rb_frac = gm->rb_frac;
+  {
+    // maths/geometry.py:150-156
+    const double mr0 = gm->mod_r_0 * au, r0 = gm->r_0 * au, v0 = gm->v_0 * 1e3;
+    const double a = gm->qd_v, b = (1. - gm->q_v + gm->epsilon * gm->qd_v) / gm->epsilon;
+    g.ts_pow = 1. - gm->q_v;
+    g.ts_const = pow(mr0, gm->q_v) / (v0 * (1. - gm->q_v + gm->epsilon * gm->qd_v));
+    g.ts_base = g.ts_const * pow(r0 + mr0 - r0, g.ts_pow);
+    g.mr0_m = mr0; g.r0_m = r0;
+    g.r1_m = gm->R_1 * au; g.r2_m = gm->R_2 * au; g.w0_m = gm->w_0 * au;
+    g.hy_a = a; g.hy_b = b;
+    g.hy_axis = 1. + gm->qd_v / (1. - gm->q_v);
+    g.hy_k1 = g.hy_k2 = 0.0;
+    g.ts_mode = want_ts ? 1 : 0;
+    g.hy_switch = 1.0;
+    if (want_ts && a != 0.0) {
+      // the connection formula needs Gamma(a-b) and 1/Gamma(a): logarithmic cases when a - b or
+      // b is an integer <= 0.  hyp_plan refuses those and every model whose series would cancel
+      // or not end -> the caller evaluates ts itself
+      if (!hyp_plan(a, b, &g.hy_k1, &g.hy_k2, &g.hy_switch))
+        return refuse(RJP_ERR_DEGENERATE,
+                      "rjp_build_fields: degenerate 2F1 parameters (a-b or b at or too close to a "
+                      "non-positive integer for the device series); pass d_ts = NULL and upload "
+                      "host-computed launch times");
+      g.ts_mode = 2;
+    }
+  }
+  return RJP_OK;
 }
 
 }  // namespace rjp

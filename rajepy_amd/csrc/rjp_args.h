@@ -1,0 +1,129 @@
+// The argument checks of the C entry points (rjprt.hip) that are pure functions of the caller's
+// structs: no HIP call, nothing but include/rjprt.h and the standard library, so that a plain C++
+// program can feed them hand-built structs (tests/test_host_logic.py).  Each returns RJP_OK or the
+// status of the refusal and writes its message to `err`; rjprt.hip hands both to fail().  The
+// messages are part of the library's behaviour (tests/golden/abi_refusals.json).  Limits that
+// live with the kernels (RJP_SGPR_BURSTS, RJP_LT_MAX_K, RJP_SRT_MAX_K) are passed in.
+#pragma once
+#include <cmath>
+#include <string>
+
+#include "../../include/rjprt.h"
+
+namespace rjp_args {
+
+inline bool mode_ok(int m) { return m == RJP_GFF_SCALAR || m == RJP_GFF_POWERLAW; }
+
+inline int refuse(std::string& err, const std::string& what, int code = RJP_ERR_ARG) {
+  err = what;
+  return code;
+}
+
+inline int check_y_pair(const rjp_fields* f, std::string& err) {
+  if ((f->d_ylo == nullptr) != (f->d_yhi == nullptr))
+    return refuse(err, "fields.d_ylo and d_yhi must both be set or both be NULL");
+  return RJP_OK;
+}
+
+// storage tag and dimensions of a non-NULL rjp_fields; `y_pair`: and the d_ylo / d_yhi pairing
+inline int check_grid(const rjp_fields* f, bool y_pair, std::string& err) {
+  if (f->dtype != RJP_F32 && f->dtype != RJP_F64)
+    return refuse(err, "fields.dtype must be RJP_F32 (4) or RJP_F64 (8)");
+  if (f->nx <= 0 || f->ny <= 0 || f->nz <= 0)
+    return refuse(err, "grid dimensions must be positive");
+  return y_pair ? check_y_pair(f, err) : RJP_OK;
+}
+
+// `compact_ok`: the entry point can run from the compact layout alone (d_em0 + d_temp);
+// `tau_mode` >= 0: ... or from the tau layout alone (d_a0 built for that mode)
+inline int check_fields(const rjp_fields* f, bool need_vy, bool compact_ok, int tau_mode,
+                        std::string& err) {
+  if (!f) return refuse(err, "fields is NULL");
+  if (int r = check_grid(f, false, err)) return r;
+  if (f->d_a0 && (f->dtype != RJP_F64 || !mode_ok(f->a0_mode)))
+    return refuse(err, "fields.d_a0 needs RJP_F64 storage and a valid a0_mode");
+  if (tau_mode >= 0 && f->d_a0 && f->a0_mode == tau_mode) {
+    // nothing else is needed for the scan itself (d_em0 / d_temp are checked where asked for)
+  } else if (compact_ok && f->d_em0) {
+    if (!f->d_temp) return refuse(err, "fields.d_temp must be a device pointer");
+  } else if (!f->d_nd || !f->d_xi || !f->d_temp || !f->d_pf) {
+    return refuse(err, "fields nd/xi/temp/pf must be device pointers");
+  }
+  if (need_vy && !f->d_vy) return refuse(err, "fields.d_vy required for RRL");
+  if (!(f->csize_au > 0.0)) return refuse(err, "fields.csize_au must be > 0");
+  return check_y_pair(f, err);
+}
+
+// (`f` non-NULL: after check_fields)
+inline int check_bursts(const rjp_bursts* b, const rjp_fields* f, std::string& err) {
+  if (!b) return RJP_OK;
+  for (int j = 0; j < 2; ++j) {
+    if (b->n[j] < 0 || b->n[j] > (1 << 20)) return refuse(err, "bursts.n must be >= 0");
+    if (b->n[j] > 0 && (!b->t0[j] || !b->amp_rel[j] || !b->inv2s2[j]))
+      return refuse(err, "bursts: NULL parameter array for a jet with n > 0");
+    if (b->n[j] > 0 && !f->d_ts)
+      return refuse(err, "fields.d_ts required when bursts are present");
+  }
+  return RJP_OK;
+}
+
+// the epoch list of a sweep; `finite`: every epoch must be a finite number
+inline int check_epochs(const double* epochs, int n_epochs, bool finite, const char* who,
+                        std::string& err) {
+  if (!epochs || n_epochs < 1)
+    return refuse(err, std::string(who) + ": NULL epochs or n_epochs < 1");
+  for (int e = 0; finite && e < n_epochs; ++e)
+    if (!std::isfinite(epochs[e])) return refuse(err, std::string(who) + ": non-finite epoch");
+  return RJP_OK;
+}
+
+// The bursts a sensitivity call differentiates with respect to, and its epochs, in the order the
+// entry points refuse them: no burst, check_bursts, more than `max_bursts` in a jet, the epochs,
+// a non-finite burst parameter.  Fills the chain-rule table -- per burst (2 amp inv2s2, 1, -amp)
+// for (t0, amp_rel, inv2s2), behind a leading 1 with `lead` -- into `scale`, which holds
+// lead + 6 * max_bursts doubles, and returns its length in `n_scale`.
+inline int check_grad_bursts(const rjp_bursts* b, const rjp_fields* f, const double* epochs,
+                             int n_epochs, int max_bursts, bool lead, const char* who,
+                             double* scale, int* n_scale, std::string& err) {
+  const std::string w(who);
+  if (!b || b->n[0] + b->n[1] <= 0 || b->n[0] < 0 || b->n[1] < 0)
+    return refuse(err, w + ": no burst to differentiate with respect to");
+  if (int r = check_bursts(b, f, err)) return r;
+  if (b->n[0] > max_bursts || b->n[1] > max_bursts)
+    return refuse(err, w + ": more than " + std::to_string(max_bursts) + " bursts in a jet");
+  if (int r = check_epochs(epochs, n_epochs, true, who, err)) return r;
+  int k = 0;
+  if (lead) scale[k++] = 1.0;
+  for (int j = 0; j < 2; ++j)
+    for (int i = 0; i < b->n[j]; ++i, k += 3) {
+      const double t0 = b->t0[j][i], amp = b->amp_rel[j][i], inv = b->inv2s2[j][i];
+      if (!std::isfinite(t0) || !std::isfinite(amp) || !std::isfinite(inv))
+        return refuse(err, w + ": non-finite burst parameter");
+      scale[k] = 2.0 * amp * inv;
+      scale[k + 1] = 1.0;
+      scale[k + 2] = -amp;
+    }
+  *n_scale = k;
+  return RJP_OK;
+}
+
+// What a launch-time layout (`name`: "launch-time-ordered layout", ...) is built from: f64 fields
+// with d_a0 and d_ts, 1 <= K <= max_K bins per jet, the launch-time range; `max_ny` > 0: n_y
+// below it
+inline int check_layout(const rjp_fields* f, int K, const char* name, int max_K, int max_ny,
+                        std::string& err) {
+  const std::string w(name);
+  if (!f) return refuse(err, "fields is NULL");
+  if (f->dtype != RJP_F64 || !f->d_a0 || !f->d_ts)
+    return refuse(err, w + ": needs RJP_F64 fields with d_a0 and d_ts");
+  if (f->nx <= 0 || f->ny <= 0 || f->nz <= 0 || (max_ny > 0 && f->ny >= max_ny))
+    return refuse(err, w + ": grid dimensions must be positive" +
+                           (max_ny > 0 ? ", n_y < " + std::to_string(max_ny) : std::string()));
+  if (K < 1 || K > max_K) return refuse(err, w + ": 1 <= K <= " + std::to_string(max_K));
+  if (!(f->ts_hi >= f->ts_lo) || !std::isfinite(f->ts_lo) || !std::isfinite(f->ts_hi) ||
+      (f->ts_lo == 0.0 && f->ts_hi == 0.0))
+    return refuse(err, w + ": fields.ts_lo / ts_hi (rjp_field_range) required");
+  return RJP_OK;
+}
+
+}  // namespace rjp_args

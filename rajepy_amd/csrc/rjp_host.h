@@ -7,6 +7,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <string>
 #include <vector>
 
 #include "rjp_device.h"
@@ -258,11 +259,14 @@ struct GeomDev {
   // q^d_v != 0 (maths/geometry.py:150-178): a = q^d_v, b = (1 - q_v + eps q^d_v)/eps,
   // hypergeometric connection coefficients K1 = b/(b-a), K2 = Gamma(b+1)Gamma(a-b)/Gamma(a);
   // hy_switch: the Pfaff series serves A <= hy_switch, the connection formula A > hy_switch
-  // (chosen per model by hyp_plan, rjprt.hip; +inf = the Pfaff series alone)
+  // (chosen per model by hyp_plan, fields.hip; +inf = the Pfaff series alone)
   double hy_a, hy_b, hy_k1, hy_k2, hy_axis, hy_switch;
   double r1_m, r2_m, w0_m, mr0_m, r0_m;
 };
 
+// K4's host half: rjp_geometry -> GeomDev, with the plan of the 2F1 when the launch times are
+// asked for (`want_ts`).  RJP_OK, or the status and message rjp_build_fields reports.
+int geometry_to_dev(const rjp_geometry* gm, bool want_ts, GeomDev& g, std::string& err);
 hipError_t pack_field_launch(const double* src, const double* den, const uint8_t* red, void* dst,
                              int64_t n, int dtype, hipStream_t st);
 hipError_t compact_fields_launch(const rjp_fields* fl, void* d_em0, int64_t* d_n_bad,

@@ -1,6 +1,7 @@
 // librjprt.so -- C-ABI entry points (include/rjprt.h) over the gfx950 kernels.
 // The kernels live in their own translation units (ff_scan*.hip, fields.hip, rrl_scan.hip;
 // csrc/Makefile builds them in parallel); rjp_host.h declares their launch wrappers.
+// The argument checks that are pure functions of the caller's structs live in rjp_args.h.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -11,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "rjp_args.h"
 #include "rjp_host.h"
 
 struct rjp_ctx {
@@ -85,17 +87,23 @@ static const char* const kGuardMsg =
     "sums of those sightlines were set to NaN (pass what rjp_field_range returns for d_ts, or "
     "zeros)";
 
+// Reads and clears the range guard; true: it was raised.  `void_ranges`: what raised it was an
+// earlier, asynchronous scan, so the ranges check_ts_range has passed are void with it.
+static bool take_guard(rjp_ctx* ctx, bool void_ranges) {
+  if (*(volatile int*)ctx->guard == 0) return false;
+  *(volatile int*)ctx->guard = 0;
+  if (void_ranges)
+    for (auto& k : ctx->range_ok) k = rjp_ctx::RangeKey();
+  return true;
+}
+
 static int bind(rjp_ctx* ctx) {
   if (!ctx) return fail(nullptr, RJP_ERR_ARG, "null context");
   hipError_t e = hipSetDevice(ctx->device);
   if (e != hipSuccess) return fail(ctx, RJP_ERR_HIP, "hipSetDevice", e);
   // the range guard is sticky until reported once (a kernel of an earlier, asynchronous call
   // raised it; whatever this call would enqueue is refused)
-  if (ctx->guard && *(volatile int*)ctx->guard != 0) {
-    *(volatile int*)ctx->guard = 0;
-    for (auto& k : ctx->range_ok) k = rjp_ctx::RangeKey();
-    return fail(ctx, RJP_ERR_ARG, kGuardMsg);
-  }
+  if (ctx->guard && take_guard(ctx, true)) return fail(ctx, RJP_ERR_ARG, kGuardMsg);
   return RJP_OK;
 }
 
@@ -111,20 +119,18 @@ static int check_ts_range(rjp_ctx* ctx, const rjp_fields* f, hipStream_t st) {
       return RJP_OK;
   RJP_HIP(ctx, rjp::range_check_launch(f->d_ts, n, f->dtype, f->ts_lo, f->ts_hi, ctx->guard, st));
   RJP_HIP(ctx, hipStreamSynchronize(st));
-  if (*(volatile int*)ctx->guard != 0) {
-    *(volatile int*)ctx->guard = 0;
+  if (take_guard(ctx, false))
     return fail(ctx, RJP_ERR_ARG,
                 "fields.ts_lo / ts_hi do not contain every finite launch time of fields.d_ts "
                 "(pass what rjp_field_range returns for it, or zeros); nothing was enqueued");
-  }
   for (int i = 3; i > 0; --i) ctx->range_ok[i] = ctx->range_ok[i - 1];
   ctx->range_ok[0].d_ts = f->d_ts; ctx->range_ok[0].n = n; ctx->range_ok[0].dtype = f->dtype;
   ctx->range_ok[0].lo = f->ts_lo; ctx->range_ok[0].hi = f->ts_hi;
   return RJP_OK;
 }
 
-// Stage up to four small host tables into one slot of the context's table ring and return
-// device pointers.  The caller records `release_tables()` after enqueueing the readers.
+// Stage small host tables into one slot of the context's table ring and return device
+// pointers (the first half of staged(), which records the slot's release event).
 static int stage_tables(rjp_ctx* ctx, hipStream_t st, const double* const* src,
                         const size_t* len, int ntab, double** dev_out) {
   size_t tot = 0;
@@ -170,65 +176,71 @@ static int stage_tables(rjp_ctx* ctx, hipStream_t st, const double* const* src,
   return RJP_OK;
 }
 
-static int release_tables(rjp_ctx* ctx, hipStream_t st) {
-  RJP_HIP(ctx, hipEventRecord(ctx->slot[ctx->cur_slot].free_ev, st));
+// A small host table of a call
+struct Tab {
+  const double* p;
+  size_t n;       // doubles
+};
+constexpr int kMaxTabs = 5;
+constexpr int kMaxScale = 1 + 6 * RJP_SGPR_BURSTS;   // the chain-rule table of a sensitivity call
+
+// A call that reads small host tables on the device: stages up to kMaxTabs of them (a slot
+// whose content on this stream equals them is reused without an upload), runs
+// `launch(dev, d_ext)` -> hipError_t with their device copies in the order given, and records
+// the slot's release event on EVERY path -- after a failed launch too, since the slot's upload
+// (and anything enqueued before the failure) may still be in flight when the ring comes round to
+// it again.  `bursts`: the parameters of a single-epoch call's bursts beyond RJP_SGPR_BURSTS
+// travel as one more table, `d_ext` (nullptr when no jet has that many; always so without
+// `bursts`).  No heap allocation unless there are such bursts.
+template <class Launch>
+static int staged(rjp_ctx* ctx, hipStream_t st, const char* what, const rjp_bursts* bursts,
+                  std::initializer_list<Tab> tabs, Launch&& launch) {
+  const double* src[kMaxTabs];
+  size_t len[kMaxTabs];
+  double* dev[kMaxTabs];
+  int n = 0;
+  if (tabs.size() + (bursts ? 1 : 0) > (size_t)kMaxTabs)   // (a slip in this file, no caller's)
+    return fail(ctx, RJP_ERR_ARG, "staged: more tables than one call stages");
+  for (const Tab& t : tabs) { src[n] = t.p; len[n++] = t.n; }
+  // host image of the overflow-burst table (parameters only)
+  std::vector<double> ext(bursts_ext_doubles(bursts), 0.0);
+  if (!ext.empty()) {
+    bursts_fill_ext(bursts, ext.data());
+    src[n] = ext.data();
+    len[n++] = ext.size();
+  }
+  if (int r = stage_tables(ctx, st, src, len, n, dev)) return r;
+  const hipError_t e = launch(dev, ext.empty() ? nullptr : dev[n - 1]);
+  const hipError_t rel = hipEventRecord(ctx->slot[ctx->cur_slot].free_ev, st);
+  if (e != hipSuccess) return fail(ctx, RJP_ERR_HIP, what, e);
+  if (rel != hipSuccess)
+    return fail(ctx, RJP_ERR_HIP, "hipEventRecord(ctx->slot[ctx->cur_slot].free_ev, st)", rel);
   return RJP_OK;
 }
 
-// End of a call that staged tables: the slot's release event is recorded on EVERY path -- after
-// a failed launch too, since the slot's upload (and anything enqueued before the failure) may
-// still be in flight when the ring comes round to it again.
-static int finish_staged(rjp_ctx* ctx, hipStream_t st, hipError_t e, const char* what) {
-  const int r = release_tables(ctx, st);
-  if (e != hipSuccess) return fail(ctx, RJP_ERR_HIP, what, e);
-  return r;
+using rjp_args::mode_ok;
+
+// rjp_args.h's checks with their message routed into fail()
+template <class Check>
+static int checked(rjp_ctx* ctx, Check&& check) {
+  std::string m;
+  const int r = check(m);
+  return r ? fail(ctx, r, m.c_str()) : RJP_OK;
 }
 
-static bool mode_ok(int m) { return m == RJP_GFF_SCALAR || m == RJP_GFF_POWERLAW; }
-
-// `compact_ok`: the entry point can run from the compact layout alone (d_em0 + d_temp);
-// `tau_mode` >= 0: ... or from the tau layout alone (d_a0 built for that mode)
 static int check_fields(rjp_ctx* ctx, const rjp_fields* f, bool need_vy, bool compact_ok = false,
                         int tau_mode = -1) {
-  if (!f) return fail(ctx, RJP_ERR_ARG, "fields is NULL");
-  if (f->dtype != RJP_F32 && f->dtype != RJP_F64)
-    return fail(ctx, RJP_ERR_ARG, "fields.dtype must be RJP_F32 (4) or RJP_F64 (8)");
-  if (f->nx <= 0 || f->ny <= 0 || f->nz <= 0)
-    return fail(ctx, RJP_ERR_ARG, "grid dimensions must be positive");
-  if (f->d_a0 && (f->dtype != RJP_F64 || !mode_ok(f->a0_mode)))
-    return fail(ctx, RJP_ERR_ARG, "fields.d_a0 needs RJP_F64 storage and a valid a0_mode");
-  if (tau_mode >= 0 && f->d_a0 && f->a0_mode == tau_mode) {
-    // nothing else is needed for the scan itself (d_em0 / d_temp are checked where asked for)
-  } else if (compact_ok && f->d_em0) {
-    if (!f->d_temp) return fail(ctx, RJP_ERR_ARG, "fields.d_temp must be a device pointer");
-  } else if (!f->d_nd || !f->d_xi || !f->d_temp || !f->d_pf) {
-    return fail(ctx, RJP_ERR_ARG, "fields nd/xi/temp/pf must be device pointers");
-  }
-  if (need_vy && !f->d_vy) return fail(ctx, RJP_ERR_ARG, "fields.d_vy required for RRL");
-  if (!(f->csize_au > 0.0)) return fail(ctx, RJP_ERR_ARG, "fields.csize_au must be > 0");
-  if ((f->d_ylo == nullptr) != (f->d_yhi == nullptr))
-    return fail(ctx, RJP_ERR_ARG, "fields.d_ylo and d_yhi must both be set or both be NULL");
-  return RJP_OK;
+  return checked(ctx, [&](std::string& m) {
+    return rjp_args::check_fields(f, need_vy, compact_ok, tau_mode, m);
+  });
 }
 
 static int check_bursts(rjp_ctx* ctx, const rjp_bursts* b, const rjp_fields* f) {
-  if (!b) return RJP_OK;
-  for (int j = 0; j < 2; ++j) {
-    if (b->n[j] < 0 || b->n[j] > (1 << 20))
-      return fail(ctx, RJP_ERR_ARG, "bursts.n must be >= 0");
-    if (b->n[j] > 0 && (!b->t0[j] || !b->amp_rel[j] || !b->inv2s2[j]))
-      return fail(ctx, RJP_ERR_ARG, "bursts: NULL parameter array for a jet with n > 0");
-    if (b->n[j] > 0 && !f->d_ts)
-      return fail(ctx, RJP_ERR_ARG, "fields.d_ts required when bursts are present");
-  }
-  return RJP_OK;
+  return checked(ctx, [&](std::string& m) { return rjp_args::check_bursts(b, f, m); });
 }
 
-// host image of the overflow-burst table of a single-epoch call (parameters only)
-static std::vector<double> burst_ext_table(const rjp_bursts* b) {
-  std::vector<double> t(bursts_ext_doubles(b), 0.0);
-  if (!t.empty()) bursts_fill_ext(b, t.data());
-  return t;
+static int check_grid(rjp_ctx* ctx, const rjp_fields* f, bool y_pair) {
+  return checked(ctx, [&](std::string& m) { return rjp_args::check_grid(f, y_pair, m); });
 }
 
 extern "C" {
@@ -334,10 +346,7 @@ int rjp_unmask_launch_times(rjp_ctx* ctx, const rjp_fields* fields, int32_t jet,
   if (int r = bind(ctx)) return r;
   if (!fields || !fields->d_ts || !d_ts_out)
     return fail(ctx, RJP_ERR_ARG, "rjp_unmask_launch_times: fields.d_ts / d_ts_out is NULL");
-  if (fields->dtype != RJP_F32 && fields->dtype != RJP_F64)
-    return fail(ctx, RJP_ERR_ARG, "fields.dtype must be RJP_F32 (4) or RJP_F64 (8)");
-  if (fields->nx <= 0 || fields->ny <= 0 || fields->nz <= 0)
-    return fail(ctx, RJP_ERR_ARG, "grid dimensions must be positive");
+  if (int r = check_grid(ctx, fields, false)) return r;
   if (jet != 0 && jet != 1) return fail(ctx, RJP_ERR_ARG, "jet must be 0 (red) or 1 (blue)");
   if (!fields->d_a0 && !fields->d_em0 && !fields->d_nd)
     return fail(ctx, RJP_ERR_ARG, "rjp_unmask_launch_times: needs a field that carries the jet "
@@ -359,12 +368,7 @@ int rjp_tavg(rjp_ctx* ctx, const rjp_fields* fields, double* d_tavg, void* d_wor
              size_t work_bytes, void* stream) {
   if (int r = bind(ctx)) return r;
   if (!fields || !fields->d_temp) return fail(ctx, RJP_ERR_ARG, "rjp_tavg: fields.d_temp is NULL");
-  if (fields->dtype != RJP_F32 && fields->dtype != RJP_F64)
-    return fail(ctx, RJP_ERR_ARG, "fields.dtype must be RJP_F32 (4) or RJP_F64 (8)");
-  if (fields->nx <= 0 || fields->ny <= 0 || fields->nz <= 0)
-    return fail(ctx, RJP_ERR_ARG, "grid dimensions must be positive");
-  if ((fields->d_ylo == nullptr) != (fields->d_yhi == nullptr))
-    return fail(ctx, RJP_ERR_ARG, "fields.d_ylo and d_yhi must both be set or both be NULL");
+  if (int r = check_grid(ctx, fields, true)) return r;
   if (!d_tavg || !d_work) return fail(ctx, RJP_ERR_ARG, "rjp_tavg: d_tavg / d_work is NULL");
   if (work_bytes < rjp::ff_scan_workspace_bytes(fields->nx, fields->ny, fields->nz, 1))
     return fail(ctx, RJP_ERR_WORKSPACE, "rjp_tavg: workspace smaller than rjp_ff_scan_workspace(.., 1)");
@@ -448,12 +452,12 @@ static int ff_scan_impl(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts
   if (mr == 2) {
     // a new (bursts, epochs) request: its coefficient tables are built and checked on the device
     const auto t0 = std::chrono::steady_clock::now();
-    const double* src[1] = {ctx->mom.stage.data()};
-    const size_t len[1] = {ctx->mom.stage.size()};
-    double* dev[1];
-    if (int r = stage_tables(ctx, st, src, len, 1, dev)) return r;
-    const hipError_t e = rjp::moments_build(ctx->mom, dev[0], st);
-    if (int r = finish_staged(ctx, st, e, "moments_build")) return r;
+    if (int r = staged(ctx, st, "moments_build", nullptr,
+                       {{ctx->mom.stage.data(), ctx->mom.stage.size()}},
+                       [&](double* const* d, const double*) {
+                         return rjp::moments_build(ctx->mom, d[0], st);
+                       }))
+      return r;
     ctx->mom.build_ms =
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
@@ -527,15 +531,13 @@ static int ff_scan_impl(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts
       sp.diag = ctx->d_srt_diag;
       ctx->last_srt_mom = true;
     }
-    const double* src[1] = {ctx->chi.stage.data()};
-    const size_t len[1] = {ctx->chi.stage.size()};
-    double* dev[1];
-    if (int r = stage_tables(ctx, st, src, len, 1, dev)) return r;
-    return finish_staged(ctx, st, rjp::chi_table_scan(fields, ctx->chi, dev[0], h_epochs_s[0],
-                                                      gff_mode, d_sumA, d_em, d_tavg,
-                                                      (double*)d_work, work_bytes, ctx->guard, st,
-                                                      srt ? &sp : nullptr),
-                         "chi_table_scan");
+    return staged(ctx, st, "chi_table_scan", nullptr,
+                  {{ctx->chi.stage.data(), ctx->chi.stage.size()}},
+                  [&](double* const* d, const double*) {
+                    return rjp::chi_table_scan(fields, ctx->chi, d[0], h_epochs_s[0], gff_mode,
+                                               d_sumA, d_em, d_tavg, (double*)d_work, work_bytes,
+                                               ctx->guard, st, srt ? &sp : nullptr);
+                  });
   }
   ctx->last_path = 0;
   rjp::ScanPlan plan;
@@ -545,19 +547,15 @@ static int ff_scan_impl(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts
     const int32_t row[5] = {tl.e0, tl.et, tl.un.on, tl.nsplit, tl.et < 16 ? plan.vec : 1};
     ctx->last_tiles.insert(ctx->last_tiles.end(), row, row + 5);
   }
-  double* d_ext = nullptr;
-  if (!plan.ext.empty()) {
-    const double* src[1] = {plan.ext.data()};
-    const size_t len[1] = {plan.ext.size()};
-    double* dev[1];
-    if (int r = stage_tables(ctx, st, src, len, 1, dev)) return r;
-    d_ext = dev[0];
-  }
-  const hipError_t e = rjp::ff_scan_run(fields, bursts, plan, d_ext, h_epochs_s, n_epochs,
-                                        gff_mode, d_sumA, d_em, d_tavg, (double*)d_work, st);
-  // the staged slot is marked busy up to here on EVERY path (its upload, and whatever was
-  // enqueued before a failure, may still be in flight)
-  if (d_ext) return finish_staged(ctx, st, e, "ff_scan_run");
+  auto run = [&](const double* d_ext) {
+    return rjp::ff_scan_run(fields, bursts, plan, d_ext, h_epochs_s, n_epochs, gff_mode, d_sumA,
+                            d_em, d_tavg, (double*)d_work, st);
+  };
+  // (the plan's own overflow table: the bursts' parameters and the tiles' constants in one)
+  if (!plan.ext.empty())
+    return staged(ctx, st, "ff_scan_run", nullptr, {{plan.ext.data(), plan.ext.size()}},
+                  [&](double* const* d, const double*) { return run(d[0]); });
+  const hipError_t e = run(nullptr);
   if (e != hipSuccess) return fail(ctx, RJP_ERR_HIP, "ff_scan_run", e);
   return RJP_OK;
 }
@@ -572,9 +570,7 @@ int rjp_ff_scan(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts
 
 int rjp_range_guard(rjp_ctx* ctx) {
   if (!ctx || !ctx->guard) return RJP_ERR_ARG;
-  if (*(volatile int*)ctx->guard == 0) return 0;
-  *(volatile int*)ctx->guard = 0;
-  for (auto& k : ctx->range_ok) k = rjp_ctx::RangeKey();
+  if (!take_guard(ctx, true)) return 0;
   ctx->err = kGuardMsg;
   return 1;
 }
@@ -634,17 +630,9 @@ size_t rjp_lt_rowoff_entries(int32_t nx, int32_t nz, int32_t K) {
 }
 
 static int check_lt(rjp_ctx* ctx, const rjp_fields* f, int32_t K) {
-  if (!f) return fail(ctx, RJP_ERR_ARG, "fields is NULL");
-  if (f->dtype != RJP_F64 || !f->d_a0 || !f->d_ts)
-    return fail(ctx, RJP_ERR_ARG, "launch-time-ordered layout: needs RJP_F64 fields with d_a0 and d_ts");
-  if (f->nx <= 0 || f->ny <= 0 || f->nz <= 0 || f->ny >= 65536)
-    return fail(ctx, RJP_ERR_ARG, "launch-time-ordered layout: grid dimensions must be positive, n_y < 65536");
-  if (K < 1 || K > RJP_LT_MAX_K)
-    return fail(ctx, RJP_ERR_ARG, "launch-time-ordered layout: 1 <= K <= 80");
-  if (!(f->ts_hi >= f->ts_lo) || !std::isfinite(f->ts_lo) || !std::isfinite(f->ts_hi) ||
-      (f->ts_lo == 0.0 && f->ts_hi == 0.0))
-    return fail(ctx, RJP_ERR_ARG, "launch-time-ordered layout: fields.ts_lo / ts_hi (rjp_field_range) required");
-  return RJP_OK;
+  return checked(ctx, [&](std::string& m) {
+    return rjp_args::check_layout(f, K, "launch-time-ordered layout", RJP_LT_MAX_K, 65536, m);
+  });
 }
 
 int rjp_lt_count(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, int32_t* d_rowoff,
@@ -658,11 +646,9 @@ int rjp_lt_count(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, int32_t* d_r
   const size_t n = rjp::lt_rowoff_entries(fields->nx, fields->nz, K);
   RJP_HIP(ctx, hipMemcpyAsync(&total, d_rowoff + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
   RJP_HIP(ctx, hipStreamSynchronize(st));
-  if (*(volatile int*)ctx->guard != 0) {
-    *(volatile int*)ctx->guard = 0;
+  if (take_guard(ctx, false))
     return fail(ctx, RJP_ERR_ARG, "rjp_lt_count: fields.ts_lo / ts_hi do not contain every launch "
                                   "time of the cells the layout keeps (rjp_field_range)");
-  }
   if (total < 0) return fail(ctx, RJP_ERR_ARG, "rjp_lt_count: more than 2^31 rows");
   *h_total_rows = total;
   return RJP_OK;
@@ -683,17 +669,9 @@ size_t rjp_srt_index_entries(int32_t nx, int32_t nz, int32_t K) {
 }
 
 static int check_srt(rjp_ctx* ctx, const rjp_fields* f, int32_t K) {
-  if (!f) return fail(ctx, RJP_ERR_ARG, "fields is NULL");
-  if (f->dtype != RJP_F64 || !f->d_a0 || !f->d_ts)
-    return fail(ctx, RJP_ERR_ARG, "launch-time-bucketed layout: needs RJP_F64 fields with d_a0 and d_ts");
-  if (f->nx <= 0 || f->ny <= 0 || f->nz <= 0)
-    return fail(ctx, RJP_ERR_ARG, "launch-time-bucketed layout: grid dimensions must be positive");
-  if (K < 1 || K > RJP_SRT_MAX_K)
-    return fail(ctx, RJP_ERR_ARG, "launch-time-bucketed layout: 1 <= K <= 32");
-  if (!(f->ts_hi >= f->ts_lo) || !std::isfinite(f->ts_lo) || !std::isfinite(f->ts_hi) ||
-      (f->ts_lo == 0.0 && f->ts_hi == 0.0))
-    return fail(ctx, RJP_ERR_ARG, "launch-time-bucketed layout: fields.ts_lo / ts_hi (rjp_field_range) required");
-  return RJP_OK;
+  return checked(ctx, [&](std::string& m) {
+    return rjp_args::check_layout(f, K, "launch-time-bucketed layout", RJP_SRT_MAX_K, 0, m);
+  });
 }
 
 int rjp_srt_count(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, int32_t* d_start,
@@ -713,11 +691,9 @@ int rjp_srt_count(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, int32_t* d_
   RJP_HIP(ctx, hipMemcpyAsync(hist, ctx->d_srt_hist, 2 * K * sizeof(unsigned long long),
                               hipMemcpyDeviceToHost, st));
   RJP_HIP(ctx, hipStreamSynchronize(st));
-  if (*(volatile int*)ctx->guard != 0) {
-    *(volatile int*)ctx->guard = 0;
+  if (take_guard(ctx, false))
     return fail(ctx, RJP_ERR_ARG, "rjp_srt_count: fields.ts_lo / ts_hi do not contain every launch "
                                   "time of the cells the layout keeps (rjp_field_range)");
-  }
   for (int q = 0; q < 2 * K; ++q) h_hist[q] = (int64_t)hist[q];
   *h_total_rows = total;
   return RJP_OK;
@@ -791,12 +767,12 @@ static int ff_maps_impl(rjp_ctx* ctx, const double* d_sumA, const double* d_tavg
   if (d_ftot && (!d_work || work_bytes < rjp::ff_maps_workspace_bytes(n_pix, n_epochs, n_chan)))
     return fail(ctx, RJP_ERR_WORKSPACE, "rjp_ff_maps: workspace smaller than rjp_ff_maps_workspace()");
   hipStream_t st = (hipStream_t)stream;
-  const double* src[2] = {h_ctau, h_cflux};
-  const size_t len[2] = {(size_t)n_chan, (size_t)n_chan};
-  double* dev[2];
-  if (int r = stage_tables(ctx, st, src, len, 2, dev)) return r;
-  return finish_staged(ctx, st, rjp::ff_maps_launch(d_sumA, d_tavg, n_pix, n_epochs, dev[0], dev[1], n_chan, d_tau,
-                                   d_flux, d_ftot, (double*)d_work, st), "ff_maps_launch");
+  const size_t F = (size_t)n_chan;
+  return staged(ctx, st, "ff_maps_launch", nullptr, {{h_ctau, F}, {h_cflux, F}},
+                [&](double* const* d, const double*) {
+                  return rjp::ff_maps_launch(d_sumA, d_tavg, n_pix, n_epochs, d[0], d[1], n_chan,
+                                             d_tau, d_flux, d_ftot, (double*)d_work, st);
+                });
 }
 
 int rjp_ff_maps(rjp_ctx* ctx, const double* d_sumA, const double* d_tavg, int64_t n_pix,
@@ -842,13 +818,11 @@ int rjp_rrl_scan(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* burst
   if (!line || !h_nu || n_chan < 1 || !d_tau_rrl)
     return fail(ctx, RJP_ERR_ARG, "rjp_rrl_scan: NULL line / nu / output or n_chan < 1");
   hipStream_t st = (hipStream_t)stream;
-  const std::vector<double> ext = burst_ext_table(bursts);
-  const double* src[2] = {h_nu, ext.data()};
-  const size_t len[2] = {(size_t)n_chan, ext.size()};
-  double* dev[2];
-  if (int r = stage_tables(ctx, st, src, len, 2, dev)) return r;
-  return finish_staged(ctx, st, rjp::rrl_scan_launch(fields, bursts, ext.empty() ? nullptr : dev[1], time_s, line,
-                                    h_nu, dev[0], n_chan, d_tau_rrl, st), "rrl_scan_launch");
+  return staged(ctx, st, "rrl_scan_launch", bursts, {{h_nu, (size_t)n_chan}},
+                [&](double* const* d, const double* d_ext) {
+                  return rjp::rrl_scan_launch(fields, bursts, d_ext, time_s, line, h_nu, d[0],
+                                              n_chan, d_tau_rrl, st);
+                });
 }
 
 int rjp_ff_cells(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts, double time_s,
@@ -859,24 +833,20 @@ int rjp_ff_cells(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* burst
   if (int r = check_bursts(ctx, bursts, fields)) return r;
   if (!h_ctau || n_chan < 1 || !d_tau_cells)
     return fail(ctx, RJP_ERR_ARG, "rjp_ff_cells: NULL table / output or n_chan < 1");
-  if (gff_mode != RJP_GFF_SCALAR && gff_mode != RJP_GFF_POWERLAW)
-    return fail(ctx, RJP_ERR_ARG, "bad gff_mode");
+  if (!mode_ok(gff_mode)) return fail(ctx, RJP_ERR_ARG, "bad gff_mode");
   hipStream_t st = (hipStream_t)stream;
-  const std::vector<double> ext = burst_ext_table(bursts);
-  const double* src[2] = {h_ctau, ext.data()};
-  const size_t len[2] = {(size_t)n_chan, ext.size()};
-  double* dev[2];
-  if (int r = stage_tables(ctx, st, src, len, 2, dev)) return r;
-  return finish_staged(ctx, st, rjp::ff_cells_launch(fields, bursts, ext.empty() ? nullptr : dev[1], time_s,
-                                    gff_mode, dev[0], n_chan, d_tau_cells, st), "ff_cells_launch");
+  return staged(ctx, st, "ff_cells_launch", bursts, {{h_ctau, (size_t)n_chan}},
+                [&](double* const* d, const double* d_ext) {
+                  return rjp::ff_cells_launch(fields, bursts, d_ext, time_s, gff_mode, d[0],
+                                              n_chan, d_tau_cells, st);
+                });
 }
 
 int rjp_ff_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
                   double time_s, int32_t gff_mode, const double* h_ctau, const double* h_csrc,
                   int32_t n_chan, double* d_out, void* stream) {
   if (int r = bind(ctx)) return r;
-  if (gff_mode != RJP_GFF_SCALAR && gff_mode != RJP_GFF_POWERLAW)
-    return fail(ctx, RJP_ERR_ARG, "bad gff_mode");
+  if (!mode_ok(gff_mode)) return fail(ctx, RJP_ERR_ARG, "bad gff_mode");
   if (int r = check_fields(ctx, fields, false, true, gff_mode)) return r;
   if (!fields->d_temp)
     return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal: fields.d_temp must be a device pointer");
@@ -884,14 +854,12 @@ int rjp_ff_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* burs
   if (!h_ctau || !h_csrc || n_chan < 1 || !d_out)
     return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal: NULL table / output or n_chan < 1");
   hipStream_t st = (hipStream_t)stream;
-  const std::vector<double> ext = burst_ext_table(bursts);
-  const double* src[3] = {h_ctau, h_csrc, ext.data()};
-  const size_t len[3] = {(size_t)n_chan, (size_t)n_chan, ext.size()};
-  double* dev[3];
-  if (int r = stage_tables(ctx, st, src, len, 3, dev)) return r;
-  return finish_staged(ctx, st, rjp::ff_formal_launch(fields, bursts, ext.empty() ? nullptr : dev[2],
-                                                      time_s, gff_mode, dev[0], dev[1], n_chan,
-                                                      d_out, st), "ff_formal_launch");
+  const size_t F = (size_t)n_chan;
+  return staged(ctx, st, "ff_formal_launch", bursts, {{h_ctau, F}, {h_csrc, F}},
+                [&](double* const* d, const double* d_ext) {
+                  return rjp::ff_formal_launch(fields, bursts, d_ext, time_s, gff_mode, d[0], d[1],
+                                               n_chan, d_out, st);
+                });
 }
 
 size_t rjp_ff_formal_sweep_workspace(int32_t nx, int32_t ny, int32_t nz, int32_t n_epochs,
@@ -911,11 +879,10 @@ int rjp_ff_formal_sweep(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts
   if (!fields->d_temp)
     return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_sweep: fields.d_temp must be a device pointer");
   if (int r = check_bursts(ctx, bursts, fields)) return r;
-  if (!h_epochs_s || n_epochs < 1)
-    return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_sweep: NULL epochs or n_epochs < 1");
-  for (int e = 0; e < n_epochs; ++e)
-    if (!std::isfinite(h_epochs_s[e]))
-      return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_sweep: non-finite epoch");
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_epochs(h_epochs_s, n_epochs, true, "rjp_ff_formal_sweep", m);
+      }))
+    return r;
   if (!h_ctau || !h_csrc || n_chan < 1)
     return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_sweep: NULL table or n_chan < 1");
   if (!d_out && !d_ftot)
@@ -927,16 +894,14 @@ int rjp_ff_formal_sweep(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts
     return fail(ctx, RJP_ERR_WORKSPACE,
                 "rjp_ff_formal_sweep: workspace smaller than rjp_ff_formal_sweep_workspace()");
   hipStream_t st = (hipStream_t)stream;
-  const std::vector<double> ext = burst_ext_table(bursts);
-  const double* src[4] = {h_ctau, h_csrc, h_epochs_s, ext.data()};
-  const size_t len[4] = {(size_t)n_chan, (size_t)n_chan, (size_t)n_epochs, ext.size()};
-  double* dev[4];
-  if (int r = stage_tables(ctx, st, src, len, 4, dev)) return r;
-  return finish_staged(ctx, st,
-                       rjp::ff_formal_sweep_launch(fields, bursts, ext.empty() ? nullptr : dev[3],
-                                                   dev[2], n_epochs, gff_mode, dev[0], dev[1],
-                                                   n_chan, d_out, d_ftot, (double*)d_work, st),
-                       "ff_formal_sweep_launch");
+  const size_t F = (size_t)n_chan;
+  return staged(ctx, st, "ff_formal_sweep_launch", bursts,
+                {{h_ctau, F}, {h_csrc, F}, {h_epochs_s, (size_t)n_epochs}},
+                [&](double* const* d, const double* d_ext) {
+                  return rjp::ff_formal_sweep_launch(fields, bursts, d_ext, d[2], n_epochs,
+                                                     gff_mode, d[0], d[1], n_chan, d_out, d_ftot,
+                                                     (double*)d_work, st);
+                });
 }
 
 size_t rjp_ff_grad_workspace(int32_t nx, int32_t ny, int32_t nz, int32_t n_epochs,
@@ -958,26 +923,14 @@ int rjp_ff_grad(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts
                 "rjp_ff_grad: needs RJP_F64 fields with the tau layout (d_a0) built for gff_mode");
   if (int r = check_fields(ctx, fields, false, false, gff_mode)) return r;
   if (!fields->d_ts) return fail(ctx, RJP_ERR_ARG, "rjp_ff_grad: fields.d_ts required");
-  if (!bursts || bursts->n[0] + bursts->n[1] <= 0 || bursts->n[0] < 0 || bursts->n[1] < 0)
-    return fail(ctx, RJP_ERR_ARG, "rjp_ff_grad: no burst to differentiate with respect to");
-  if (int r = check_bursts(ctx, bursts, fields)) return r;
-  if (bursts->n[0] > RJP_SGPR_BURSTS || bursts->n[1] > RJP_SGPR_BURSTS)
-    return fail(ctx, RJP_ERR_ARG, "rjp_ff_grad: more than 8 bursts in a jet");
-  if (!h_epochs_s || n_epochs < 1)
-    return fail(ctx, RJP_ERR_ARG, "rjp_ff_grad: NULL epochs or n_epochs < 1");
-  for (int e = 0; e < n_epochs; ++e)
-    if (!std::isfinite(h_epochs_s[e]))
-      return fail(ctx, RJP_ERR_ARG, "rjp_ff_grad: non-finite epoch");
-  const int npar = 3 * (bursts->n[0] + bursts->n[1]);
-  std::vector<double> scale(1 + npar, 1.0);
-  for (int j = 0, k = 1; j < 2; ++j)
-    for (int i = 0; i < bursts->n[j]; ++i, k += 3) {
-      const double t0 = bursts->t0[j][i], amp = bursts->amp_rel[j][i], inv = bursts->inv2s2[j][i];
-      if (!std::isfinite(t0) || !std::isfinite(amp) || !std::isfinite(inv))
-        return fail(ctx, RJP_ERR_ARG, "rjp_ff_grad: non-finite burst parameter");
-      scale[k] = 2.0 * amp * inv;
-      scale[k + 2] = -amp;
-    }
+  double scale[kMaxScale];          // 1, then the chain-rule constant of every parameter
+  int n_scale = 0;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_grad_bursts(bursts, fields, h_epochs_s, n_epochs, RJP_SGPR_BURSTS,
+                                           true, "rjp_ff_grad", scale, &n_scale, m);
+      }))
+    return r;
+  const int npar = n_scale - 1;
   if (!d_sumA && !d_dsumA && !d_ftot && !d_dftot)
     return fail(ctx, RJP_ERR_ARG, "rjp_ff_grad: all four outputs are NULL");
   const bool totals = d_ftot || d_dftot;
@@ -989,14 +942,13 @@ int rjp_ff_grad(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts
                                                            n_epochs, npar, nch))
     return fail(ctx, RJP_ERR_WORKSPACE, "rjp_ff_grad: workspace smaller than rjp_ff_grad_workspace()");
   hipStream_t st = (hipStream_t)stream;
-  const double* src[3] = {scale.data(), h_ctau, h_cflux};
-  const size_t len[3] = {scale.size(), (size_t)nch, (size_t)nch};
-  double* dev[3];
-  if (int r = stage_tables(ctx, st, src, len, 3, dev)) return r;
-  return finish_staged(ctx, st, rjp::ff_grad_run(fields, bursts, h_epochs_s, n_epochs, dev[0], d_tavg,
-                                                 dev[1], dev[2], nch, d_sumA, d_dsumA, d_ftot,
-                                                 d_dftot, (double*)d_work, work_bytes, st),
-                       "ff_grad_run");
+  return staged(ctx, st, "ff_grad_run", nullptr,
+                {{scale, (size_t)n_scale}, {h_ctau, (size_t)nch}, {h_cflux, (size_t)nch}},
+                [&](double* const* d, const double*) {
+                  return rjp::ff_grad_run(fields, bursts, h_epochs_s, n_epochs, d[0], d_tavg, d[1],
+                                          d[2], nch, d_sumA, d_dsumA, d_ftot, d_dftot,
+                                          (double*)d_work, work_bytes, st);
+                });
 }
 
 size_t rjp_ff_formal_grad_workspace(int32_t nx, int32_t ny, int32_t nz, int32_t n_epochs,
@@ -1018,26 +970,13 @@ int rjp_ff_formal_grad(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts*
   if (int r = check_fields(ctx, fields, false, true, gff_mode)) return r;
   if (!fields->d_temp || !fields->d_ts)
     return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_grad: fields.d_temp and fields.d_ts required");
-  if (!bursts || bursts->n[0] + bursts->n[1] <= 0 || bursts->n[0] < 0 || bursts->n[1] < 0)
-    return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_grad: no burst to differentiate with respect to");
-  if (int r = check_bursts(ctx, bursts, fields)) return r;
-  if (bursts->n[0] > RJP_SGPR_BURSTS || bursts->n[1] > RJP_SGPR_BURSTS)
-    return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_grad: more than 8 bursts in a jet");
-  if (!h_epochs_s || n_epochs < 1)
-    return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_grad: NULL epochs or n_epochs < 1");
-  for (int e = 0; e < n_epochs; ++e)
-    if (!std::isfinite(h_epochs_s[e]))
-      return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_grad: non-finite epoch");
-  const int npar = 3 * (bursts->n[0] + bursts->n[1]);
-  std::vector<double> scale(npar, 1.0);
-  for (int j = 0, k = 0; j < 2; ++j)
-    for (int i = 0; i < bursts->n[j]; ++i, k += 3) {
-      const double t0 = bursts->t0[j][i], amp = bursts->amp_rel[j][i], inv = bursts->inv2s2[j][i];
-      if (!std::isfinite(t0) || !std::isfinite(amp) || !std::isfinite(inv))
-        return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_grad: non-finite burst parameter");
-      scale[k] = 2.0 * amp * inv;
-      scale[k + 2] = -amp;
-    }
+  double scale[kMaxScale];          // the chain-rule constant of every parameter
+  int npar = 0;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_grad_bursts(bursts, fields, h_epochs_s, n_epochs, RJP_SGPR_BURSTS,
+                                           false, "rjp_ff_formal_grad", scale, &npar, m);
+      }))
+    return r;
   if (!h_ctau || !h_csrc || n_chan < 1)
     return fail(ctx, RJP_ERR_ARG, "rjp_ff_formal_grad: NULL table or n_chan < 1");
   if (!d_ftot && !d_dftot && !d_dout)
@@ -1050,15 +989,14 @@ int rjp_ff_formal_grad(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts*
     return fail(ctx, RJP_ERR_WORKSPACE,
                 "rjp_ff_formal_grad: workspace smaller than rjp_ff_formal_grad_workspace()");
   hipStream_t st = (hipStream_t)stream;
-  const double* src[4] = {h_ctau, h_csrc, h_epochs_s, scale.data()};
-  const size_t len[4] = {(size_t)n_chan, (size_t)n_chan, (size_t)n_epochs, scale.size()};
-  double* dev[4];
-  if (int r = stage_tables(ctx, st, src, len, 4, dev)) return r;
-  return finish_staged(ctx, st,
-                       rjp::ff_formal_grad_launch(fields, bursts, dev[2], n_epochs, gff_mode, dev[0],
-                                                  dev[1], n_chan, dev[3], d_ftot, d_dftot, d_dout,
-                                                  (double*)d_work, st),
-                       "ff_formal_grad_launch");
+  const size_t F = (size_t)n_chan;
+  return staged(ctx, st, "ff_formal_grad_launch", nullptr,
+                {{h_ctau, F}, {h_csrc, F}, {h_epochs_s, (size_t)n_epochs}, {scale, (size_t)npar}},
+                [&](double* const* d, const double*) {
+                  return rjp::ff_formal_grad_launch(fields, bursts, d[2], n_epochs, gff_mode, d[0],
+                                                    d[1], n_chan, d[3], d_ftot, d_dftot, d_dout,
+                                                    (double*)d_work, st);
+                });
 }
 
 size_t rjp_vis_workspace(int32_t n_maps, int32_t nx, int32_t nz, int32_t n_vis) {
@@ -1084,14 +1022,11 @@ int rjp_vis(rjp_ctx* ctx, const double* d_maps, int32_t n_maps, int32_t nx, int3
   if (!d_work || work_bytes < need)
     return fail(ctx, RJP_ERR_WORKSPACE, "rjp_vis: workspace smaller than rjp_vis_workspace()");
   hipStream_t st = (hipStream_t)stream;
-  const double* src[2] = {h_su, h_sv};
-  const size_t len[2] = {(size_t)n_maps, (size_t)n_maps};
-  double* dev[2];
-  if (int r = stage_tables(ctx, st, src, len, 2, dev)) return r;
-  return finish_staged(ctx, st,
-                       rjp::vis_launch(d_maps, n_maps, nx, nz, dev[0], dev[1], d_u, d_v, n_vis,
-                                       d_vis, (double*)d_work, st),
-                       "vis_launch");
+  return staged(ctx, st, "vis_launch", nullptr, {{h_su, (size_t)n_maps}, {h_sv, (size_t)n_maps}},
+                [&](double* const* d, const double*) {
+                  return rjp::vis_launch(d_maps, n_maps, nx, nz, d[0], d[1], d_u, d_v, n_vis,
+                                         d_vis, (double*)d_work, st);
+                });
 }
 
 int rjp_rrl_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
@@ -1099,24 +1034,21 @@ int rjp_rrl_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bur
                    const double* h_ctau, const double* h_csrc, const double* h_hnu_k,
                    int32_t n_chan, const double* d_add, double* d_out, void* stream) {
   if (int r = bind(ctx)) return r;
-  if (gff_mode != RJP_GFF_SCALAR && gff_mode != RJP_GFF_POWERLAW)
-    return fail(ctx, RJP_ERR_ARG, "bad gff_mode");
+  if (!mode_ok(gff_mode)) return fail(ctx, RJP_ERR_ARG, "bad gff_mode");
   // the wide fields only: nd, xi, temp, pf, vy (and ts with bursts)
   if (int r = check_fields(ctx, fields, true)) return r;
   if (int r = check_bursts(ctx, bursts, fields)) return r;
   if (!line || !h_nu || !h_ctau || !h_csrc || !h_hnu_k || n_chan < 1 || !d_out)
     return fail(ctx, RJP_ERR_ARG, "rjp_rrl_formal: NULL line / table / output or n_chan < 1");
   hipStream_t st = (hipStream_t)stream;
-  const std::vector<double> ext = burst_ext_table(bursts);
-  const double* src[5] = {h_nu, h_ctau, h_csrc, h_hnu_k, ext.data()};
-  const size_t len[5] = {(size_t)n_chan, (size_t)n_chan, (size_t)n_chan, (size_t)n_chan,
-                         ext.size()};
-  double* dev[5];
-  if (int r = stage_tables(ctx, st, src, len, 5, dev)) return r;
-  return finish_staged(ctx, st, rjp::rrl_formal_launch(fields, bursts, ext.empty() ? nullptr : dev[4],
-                                                       time_s, gff_mode, line, h_nu, dev[0], dev[1],
-                                                       dev[2], dev[3], n_chan, d_add, d_out, st),
-                       "rrl_formal_launch");
+  const size_t F = (size_t)n_chan;
+  return staged(ctx, st, "rrl_formal_launch", bursts,
+                {{h_nu, F}, {h_ctau, F}, {h_csrc, F}, {h_hnu_k, F}},
+                [&](double* const* d, const double* d_ext) {
+                  return rjp::rrl_formal_launch(fields, bursts, d_ext, time_s, gff_mode, line,
+                                                h_nu, d[0], d[1], d[2], d[3], n_chan, d_add, d_out,
+                                                st);
+                });
 }
 
 int rjp_rrl_cells(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
@@ -1128,13 +1060,11 @@ int rjp_rrl_cells(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* burs
   if (!line || !h_nu || n_chan < 1 || !d_tau_cells)
     return fail(ctx, RJP_ERR_ARG, "rjp_rrl_cells: NULL line / nu / output or n_chan < 1");
   hipStream_t st = (hipStream_t)stream;
-  const std::vector<double> ext = burst_ext_table(bursts);
-  const double* src[2] = {h_nu, ext.data()};
-  const size_t len[2] = {(size_t)n_chan, ext.size()};
-  double* dev[2];
-  if (int r = stage_tables(ctx, st, src, len, 2, dev)) return r;
-  return finish_staged(ctx, st, rjp::rrl_cells_launch(fields, bursts, ext.empty() ? nullptr : dev[1], time_s,
-                                     line, h_nu, dev[0], n_chan, d_tau_cells, st), "rrl_cells_launch");
+  return staged(ctx, st, "rrl_cells_launch", bursts, {{h_nu, (size_t)n_chan}},
+                [&](double* const* d, const double* d_ext) {
+                  return rjp::rrl_cells_launch(fields, bursts, d_ext, time_s, line, h_nu, d[0],
+                                               n_chan, d_tau_cells, st);
+                });
 }
 
 int rjp_rrl_maps(rjp_ctx* ctx, const double* d_tau_rrl, const double* d_tau_ff,
@@ -1148,92 +1078,13 @@ int rjp_rrl_maps(rjp_ctx* ctx, const double* d_tau_rrl, const double* d_tau_ff,
   if (d_ftot && (!d_work || work_bytes < rjp::ff_maps_workspace_bytes(n_pix, 1, n_chan)))
     return fail(ctx, RJP_ERR_WORKSPACE, "rjp_rrl_maps: workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  const double* src[2] = {h_cflux_rrl, h_hnu_k};
-  const size_t len[2] = {(size_t)n_chan, (size_t)n_chan};
-  double* dev[2];
-  if (int r = stage_tables(ctx, st, src, len, 2, dev)) return r;
-  return finish_staged(ctx, st, rjp::rrl_maps_launch(d_tau_rrl, d_tau_ff, d_tavg, d_flux_ff, n_pix, dev[0], dev[1],
-                                    n_chan, d_flux, d_ftot, (double*)d_work, st), "rrl_maps_launch");
+  const size_t F = (size_t)n_chan;
+  return staged(ctx, st, "rrl_maps_launch", nullptr, {{h_cflux_rrl, F}, {h_hnu_k, F}},
+                [&](double* const* d, const double*) {
+                  return rjp::rrl_maps_launch(d_tau_rrl, d_tau_ff, d_tavg, d_flux_ff, n_pix, d[0],
+                                              d[1], n_chan, d_flux, d_ftot, (double*)d_work, st);
+                });
 }
-
-}  // extern "C"
-
-// ---- K4's 2F1: which series where ---------------------------------------------------------------
-// hyp_series of fields.hip on the host, also returning the largest |term| (the leading 1 included)
-// and the number of terms taken (kHypMaxTerms + 1: the series did not end).
-struct HypSum { double sum, big; int taken; };
-
-static HypSum hyp_series_host(double a, double beta, double s) {
-  HypSum r = {1.0, 1.0, rjp::kHypMaxTerms + 1};
-  double term = 1.0;
-  for (int k = 0; k < rjp::kHypMaxTerms; ++k) {
-    const double den = beta + 1.0 + k;
-    const double ratio = (a + k) / den * s;
-    term *= ratio;
-    r.sum += term;
-    r.big = std::max(r.big, fabs(term));
-    if (fabs(term) <= rjp::kHypStop * fabs(r.sum) && den > 0.0 && fabs(ratio) < 1.0) {
-      r.taken = k + 1;
-      break;
-    }
-  }
-  return r;
-}
-
-// Gamma(b + 1) Gamma(a - b) / Gamma(a); through lgamma where a factor leaves the double range
-// (b + 1 > 171: inf * 0)
-static double hyp_gamma_ratio(double b, double amb, double a) {
-  const double v = tgamma(b + 1.) * tgamma(amb) / tgamma(a);
-  if (std::isfinite(v) && v != 0.0) return v;
-  int s1 = 1, s2 = 1, s3 = 1;
-  const double lg = lgamma_r(b + 1., &s1) + lgamma_r(amb, &s2) - lgamma_r(a, &s3);
-  return (double)(s1 * s2 * s3) * exp(lg);
-}
-
-// The launch-time integral A^a 2F1(a, b; b + 1; -A) is summed by the Pfaff series for A <= switch
-// and by the 1/z connection formula above it (fields.hip: hyp_flow_factor).  The connection
-// formula is sound from A = 1 on for b of a few units.  For large b (narrow jets: b ~ 1/eps) its
-// series first falls and then comes back to order one around k = (b - a)(1 + 1/A): hundreds of
-// terms near A = 1.  For a - b within ~1e-4 of a non-positive integer its two parts cancel like
-// 1/(distance A).  So the switch is the smallest of kHypSwitch at which (probed at five A from the
-// switch upwards) the connection formula ends within kHypConnTerms terms and loses at most
-// kHypMaxLoss to cancellation, while the Pfaff series ends within kHypMaxTerms at the switch; +inf
-// (the Pfaff series for every A) serves large b.  No such switch: refused (false).
-static bool hyp_plan(double a, double b, double* k1, double* k2, double* a_switch) {
-  constexpr double kHypSwitch[] = {1.0, 1.25, 1.5, 2.0, 3.0, 4.0, 6.0, 8.0, 16.0, 64.0, HUGE_VAL};
-  constexpr double kHypProbe[] = {1.0, 1.5, 2.0, 4.0, 16.0};
-  constexpr int kHypConnTerms = 100;
-  constexpr double kHypMaxLoss = 4096.0;
-  const double amb = a - b;
-  auto nonpos_int = [](double v, double tol) { return v < 0.5 && fabs(v - nearbyint(v)) < tol; };
-  if (nonpos_int(amb, 1e-9) || nonpos_int(b, 1e-6) || nonpos_int(b + 1., 1e-6) || b == a)
-    return false;
-  *k1 = b / (b - a);
-  *k2 = (a <= 0.0 && a == nearbyint(a)) ? 0.0 : hyp_gamma_ratio(b, amb, a);
-  if (!std::isfinite(*k1) || !std::isfinite(*k2)) return false;
-  for (double sw : kHypSwitch) {
-    const bool all = !std::isfinite(sw);
-    if (hyp_series_host(a, b, all ? 1.0 : sw / (1.0 + sw)).taken > rjp::kHypMaxTerms)
-      return false;                                   // a larger switch needs still more terms
-    bool ok = true;
-    for (int i = 0; ok && !all && i < 5; ++i) {
-      const double A = sw * kHypProbe[i];
-      const double sa = pow(A / (1.0 + A), a);
-      const HypSum c = hyp_series_host(a, amb, 1.0 / (1.0 + A));
-      const double t2 = *k2 * pow(A, amb);
-      const double tot = sa * *k1 * c.sum + t2;
-      const double loss = std::max(fabs(sa * *k1) * c.big, fabs(t2)) / fabs(tot);
-      ok = c.taken <= kHypConnTerms && loss <= kHypMaxLoss;      // (false for NaN)
-    }
-    if (ok) {
-      *a_switch = sw;
-      return true;
-    }
-  }
-  return false;
-}
-
-extern "C" {
 
 int rjp_build_fields(rjp_ctx* ctx, const rjp_geometry* gm, int dtype, void* d_nd, void* d_xi,
                      void* d_temp, void* d_pf, void* d_ts, void* d_vy, double* d_ff_raw,
@@ -1252,53 +1103,11 @@ int rjp_build_fields(rjp_ctx* ctx, const rjp_geometry* gm, int dtype, void* d_nd
     return fail(ctx, RJP_ERR_ARG, "rjp_build_fields: d_em0 / d_a0 are written for RJP_F64 storage "
                                   "only (float storage goes through rjp_compact_fields' range check)");
   if (d_a0 && !mode_ok(a0_mode)) return fail(ctx, RJP_ERR_ARG, "rjp_build_fields: bad a0_mode");
-  const double au = 149597870700.0, d2r = M_PI / 180.0;
   rjp::GeomDev g;
-  g.nx = gm->nx; g.ny = gm->ny; g.nz = gm->nz; g.ccw = gm->rotation_ccw;
-  g.nx_total = gm->nx_total > 0 ? gm->nx_total : gm->nx;
-  g.ix0 = gm->ix0;
-  if (g.ix0 < 0 || g.ix0 + g.nx > g.nx_total)
-    return fail(ctx, RJP_ERR_ARG, "rjp_build_fields: x-slab [ix0, ix0+nx) outside [0, nx_total)");
-  g.cs = gm->csize;
-  // numpy.radians(x) = x * (pi/180); cos/sin in libm double, as maths/geometry.py:249-253
-  const double a = (gm->inc - 90.) * d2r, b = gm->pa * d2r;
-  g.ca = cos(a); g.sa = sin(a); g.cb = cos(b); g.sb = sin(b);
-  const double a2 = (90. - gm->inc) * d2r, b2 = -gm->pa * d2r;
-  g.ca2 = cos(a2); g.sa2 = sin(a2); g.cb2 = cos(b2); g.sb2 = sin(b2);
-  g.w_0 = gm->w_0; g.r_0 = gm->r_0; g.mr0 = gm->mod_r_0; g.eps = gm->epsilon;
-  g.R_1 = gm->R_1; g.R_2 = gm->R_2;
-  g.gm = 6.6743e-11 * gm->M_star * 1.98847e30;
-  g.v_lsr = gm->v_lsr;
-  g.n_0 = gm->n_0; g.x_0 = gm->x_0; g.T_0 = gm->T_0; g.v_0 = gm->v_0;
-  g.q_n = gm->q_n; g.q_x = gm->q_x; g.q_T = gm->q_T; g.q_v = gm->q_v;
-  g.qd_n = gm->qd_n; g.qd_x = gm->qd_x; g.qd_T = gm->qd_T; g.qd_v = gm->qd_v;
-  g.rb_frac = gm->rb_frac;
-  {
-    // maths/geometry.py:150-156
-    const double mr0 = gm->mod_r_0 * au, r0 = gm->r_0 * au, v0 = gm->v_0 * 1e3;
-    const double a = gm->qd_v, b = (1. - gm->q_v + gm->epsilon * gm->qd_v) / gm->epsilon;
-    g.ts_pow = 1. - gm->q_v;
-    g.ts_const = pow(mr0, gm->q_v) / (v0 * (1. - gm->q_v + gm->epsilon * gm->qd_v));
-    g.ts_base = g.ts_const * pow(r0 + mr0 - r0, g.ts_pow);
-    g.mr0_m = mr0; g.r0_m = r0;
-    g.r1_m = gm->R_1 * au; g.r2_m = gm->R_2 * au; g.w0_m = gm->w_0 * au;
-    g.hy_a = a; g.hy_b = b;
-    g.hy_axis = 1. + gm->qd_v / (1. - gm->q_v);
-    g.hy_k1 = g.hy_k2 = 0.0;
-    g.ts_mode = d_ts ? 1 : 0;
-    g.hy_switch = 1.0;
-    if (d_ts && a != 0.0) {
-      // the connection formula needs Gamma(a-b) and 1/Gamma(a): logarithmic cases when a - b or
-      // b is an integer <= 0.  hyp_plan refuses those and every model whose series would cancel
-      // or not end -> the caller evaluates ts itself
-      if (!hyp_plan(a, b, &g.hy_k1, &g.hy_k2, &g.hy_switch))
-        return fail(ctx, RJP_ERR_DEGENERATE,
-                    "rjp_build_fields: degenerate 2F1 parameters (a-b or b at or too close to a "
-                    "non-positive integer for the device series); pass d_ts = NULL and upload "
-                    "host-computed launch times");
-      g.ts_mode = 2;
-    }
-  }
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp::geometry_to_dev(gm, d_ts != nullptr, g, m);
+      }))
+    return r;
   RJP_HIP(ctx, rjp::build_fields_launch(g, dtype, d_nd, d_xi, d_temp, d_pf, d_ts, d_vy, d_ff_raw,
                                         d_areas_raw, d_vx_raw, d_vz_raw, d_em0, d_a0, (int)a0_mode,
                                         (hipStream_t)stream));

@@ -20,6 +20,16 @@ def _torch():
     return torch
 
 
+def _ptr(t):
+    """Device address of a tensor; NULL for None."""
+    return t.data_ptr() if t is not None else None
+
+
+def _ref(s):
+    """An optional struct (rjp_bursts) by reference; NULL for None."""
+    return C.byref(s) if s is not None else None
+
+
 def _tensor_key(t):
     """(address, version) of a tensor: the version counter catches in-place edits under the same
     pointer, the pointer a new tensor (whose counter starts again)."""
@@ -85,7 +95,7 @@ class DeviceFields:
 
     def struct(self):
         f = _lib.Fields()
-        f.d_nd, f.d_xi, f.d_temp, f.d_pf = (t.data_ptr() if t is not None else None for t in
+        f.d_nd, f.d_xi, f.d_temp, f.d_pf = (_ptr(t) for t in
                                             (self.nd, self.xi, self.temp, self.pf))
         f.d_em0 = self.em0.data_ptr() if self.em0 is not None else None
         f.d_a0 = self.a0.data_ptr() if self.a0 is not None else None
@@ -230,6 +240,10 @@ class RTEngine:
                 self._void_unreported()
             raise
 
+    def _call(self, name, *args):
+        """`name`(ctx, *args, the current stream), its status checked under that name."""
+        self._check(getattr(self.lib, name)(self.ctx, *args, self._stream()), self.ctx, name)
+
     def _void_unreported(self):
         """The moment maps filled since the last clean report may hold the NaNs of a pass the
         guard flagged: their recorded shape is void (the next long sweep makes its own pass).
@@ -280,7 +294,6 @@ class RTEngine:
         torch = _torch()
         shape = np.shape(nd)
         n = int(np.prod(shape))
-        st = self._stream()
 
         def up(a):
             return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).ravel()).to(
@@ -288,10 +301,8 @@ class RTEngine:
 
         def pack(src, den=None, redt=None):
             dst = self._empty(n, dtype)
-            self._check(self.lib.rjp_pack_field(
-                self.ctx, src.data_ptr(), den.data_ptr() if den is not None else None,
-                redt.data_ptr() if redt is not None else None, dst.data_ptr(), n, dtype, st),
-                self.ctx, "rjp_pack_field")
+            self._call("rjp_pack_field", src.data_ptr(), _ptr(den), _ptr(redt), dst.data_ptr(), n,
+                       dtype)
             return dst
 
         red_t = torch.from_numpy(np.ascontiguousarray(red, dtype=np.uint8).ravel()).to(
@@ -321,9 +332,7 @@ class RTEngine:
         em0 = self._empty(fields.ncells, fields.dtype)
         bad = torch.empty(1, dtype=torch.int64, device=self.device)
         fs = fields.struct()
-        self._check(self.lib.rjp_compact_fields(self.ctx, C.byref(fs), em0.data_ptr(),
-                                               bad.data_ptr(), self._stream()), self.ctx,
-                   "rjp_compact_fields")
+        self._call("rjp_compact_fields", C.byref(fs), em0.data_ptr(), bad.data_ptr())
         if int(bad.item()) == 0:
             fields.em0 = em0
         return fields
@@ -340,8 +349,7 @@ class RTEngine:
             return fields
         a0 = self._f64(fields.ncells)
         fs = fields.struct()
-        self._check(self.lib.rjp_tau_field(self.ctx, C.byref(fs), int(gff_mode), a0.data_ptr(),
-                                          self._stream()), self.ctx, "rjp_tau_field")
+        self._call("rjp_tau_field", C.byref(fs), int(gff_mode), a0.data_ptr())
         fields.a0, fields.a0_mode = a0, int(gff_mode)
         return fields
 
@@ -364,8 +372,7 @@ class RTEngine:
         wb = self.lib.rjp_ff_scan_workspace(nx, ny, nz, 1)
         work = self._workspace(wb)
         fs = fields.struct()
-        self._check(self.lib.rjp_tavg(self.ctx, C.byref(fs), out.data_ptr(), work.data_ptr(),
-                                     work.numel(), self._stream()), self.ctx, "rjp_tavg")
+        self._call("rjp_tavg", C.byref(fs), out.data_ptr(), work.data_ptr(), work.numel())
         return out
 
     def launch_time_range(self, fields):
@@ -377,9 +384,8 @@ class RTEngine:
         if fields.ts_range is not None and fields._ts_range_of == fields.ts.data_ptr():
             return fields.ts_range
         part = self._f64(2 * _lib.RJP_RANGE_BLOCKS)
-        self._check(self.lib.rjp_field_range(self.ctx, fields.ts.data_ptr(), fields.ncells,
-                                            fields.dtype, part.data_ptr(), self._stream()),
-                   self.ctx, "rjp_field_range")
+        self._call("rjp_field_range", fields.ts.data_ptr(), fields.ncells, fields.dtype,
+                   part.data_ptr())
         h = part.cpu().numpy().reshape(-1, 2)
         lo, hi = float(h[:, 0].min()), float(h[:, 1].max())
         fields.ts_range = (lo, hi) if np.isfinite(lo) and np.isfinite(hi) and hi >= lo else None
@@ -414,16 +420,14 @@ class RTEngine:
         total = C.c_int64()
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         ev[0].record()
-        self._check(self.lib.rjp_lt_count(self.ctx, C.byref(fs), int(K), rowoff.data_ptr(),
-                                         C.byref(total), self._stream()), self.ctx, "rjp_lt_count")
+        self._call("rjp_lt_count", C.byref(fs), int(K), rowoff.data_ptr(), C.byref(total))
         ev[1].record()
         # (allocating ~1.2 x the bytes of a0 + ts is the slow part of a first build: hipMalloc)
         cells = torch.empty(max(1, total.value) * 64 * 2, dtype=torch.float64, device=self.device)
         aux = torch.empty(3 * fields.npix, dtype=torch.float64, device=self.device)
         ev[2].record()
-        self._check(self.lib.rjp_lt_fill(self.ctx, C.byref(fs), int(K), rowoff.data_ptr(),
-                                        cells.data_ptr(), aux.data_ptr(), self._stream()),
-                   self.ctx, "rjp_lt_fill")
+        self._call("rjp_lt_fill", C.byref(fs), int(K), rowoff.data_ptr(), cells.data_ptr(),
+                   aux.data_ptr())
         ev[3].record()
         torch.cuda.synchronize(self.device)
         kernels_ms = ev[0].elapsed_time(ev[1]) + ev[2].elapsed_time(ev[3])
@@ -479,9 +483,8 @@ class RTEngine:
         total = C.c_int64()
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         ev[0].record()
-        self._check(self.lib.rjp_srt_count(self.ctx, C.byref(fs), int(K), start.data_ptr(),
-                                          rowbase.data_ptr(), hist, C.byref(total),
-                                          self._stream()), self.ctx, "rjp_srt_count")
+        self._call("rjp_srt_count", C.byref(fs), int(K), start.data_ptr(), rowbase.data_ptr(),
+                   hist, C.byref(total))
         ev[1].record()
         need = total.value * 64 * 16 + n_idx * 8 + 3 * fields.npix * 8
         n_mom = (self.lib.rjp_srt_moment_entries(nx, nz, int(K), int(self.srt_N))
@@ -496,20 +499,16 @@ class RTEngine:
         cum = torch.empty(n_idx, dtype=torch.float64, device=self.device)
         aux = torch.empty(3 * fields.npix, dtype=torch.float64, device=self.device)
         ev[2].record()
-        self._check(self.lib.rjp_srt_fill(self.ctx, C.byref(fs), int(K), start.data_ptr(),
-                                         rowbase.data_ptr(), cells.data_ptr(), cum.data_ptr(),
-                                         aux.data_ptr(), self._stream()),
-                   self.ctx, "rjp_srt_fill")
+        self._call("rjp_srt_fill", C.byref(fs), int(K), start.data_ptr(), rowbase.data_ptr(),
+                   cells.data_ptr(), cum.data_ptr(), aux.data_ptr())
         ev[3].record()
         mom, mom_ms = None, 0.0
         if n_mom:
             mom = torch.empty(n_mom, dtype=torch.float64, device=self.device)
             ev_m = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
             ev_m[0].record()
-            self._check(self.lib.rjp_srt_moments(self.ctx, C.byref(fs), int(K), int(self.srt_N),
-                                                start.data_ptr(), rowbase.data_ptr(),
-                                                cells.data_ptr(), mom.data_ptr(), self._stream()),
-                       self.ctx, "rjp_srt_moments")
+            self._call("rjp_srt_moments", C.byref(fs), int(K), int(self.srt_N), start.data_ptr(),
+                       rowbase.data_ptr(), cells.data_ptr(), mom.data_ptr())
             ev_m[1].record()
         torch.cuda.synchronize(self.device)
         if mom is not None:
@@ -538,15 +537,12 @@ class RTEngine:
         lo = torch.empty(fields.npix, dtype=torch.int32, device=self.device)
         hi = torch.empty(fields.npix, dtype=torch.int32, device=self.device)
         fs = fields.struct()
-        self._check(self.lib.rjp_y_bounds(self.ctx, C.byref(fs), lo.data_ptr(), hi.data_ptr(),
-                                         self._stream()), self.ctx, "rjp_y_bounds")
+        self._call("rjp_y_bounds", C.byref(fs), lo.data_ptr(), hi.data_ptr())
         fields.ylo, fields.yhi = lo, hi
         # (hint for the tiles-or-moments choice of long epoch sweeps, include/rjprt.h; summed by
         # the library: the first use of the equivalent torch ops costs ~0.2 s of lazy loading)
         n = C.c_int64()
-        self._check(self.lib.rjp_occupied_cells(self.ctx, lo.data_ptr(), hi.data_ptr(),
-                                               fields.npix, C.byref(n), self._stream()),
-                   self.ctx, "rjp_occupied_cells")
+        self._call("rjp_occupied_cells", lo.data_ptr(), hi.data_ptr(), fields.npix, C.byref(n))
         fields.occupied_cells = int(n.value)
         return lo, hi
 
@@ -560,9 +556,8 @@ class RTEngine:
         if src.numel() != fields.ncells:
             raise ValueError("grid shape mismatch")
         dst = self._empty(fields.ncells, fields.dtype)
-        self._check(self.lib.rjp_pack_field(self.ctx, src.data_ptr(), None, None,
-                                           dst.data_ptr(), fields.ncells, fields.dtype,
-                                           self._stream()), self.ctx, "rjp_pack_field")
+        self._call("rjp_pack_field", src.data_ptr(), None, None, dst.data_ptr(), fields.ncells,
+                   fields.dtype)
         self.synchronize()
         setattr(fields, name, dst)
         if name in ("ts", "xi", "temp"):
@@ -614,11 +609,9 @@ class RTEngine:
         arr = self._f64(n) if want_raw else None
         vxr = self._f64(n) if want_vxz else None
         vzr = self._f64(n) if want_vxz else None
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        self._check(self.lib.rjp_build_fields(
-            self.ctx, C.byref(geom), dtype, ptr(nd), ptr(xi), temp.data_ptr(), ptr(pf), ptr(ts),
-            ptr(vy), ptr(ffr), ptr(arr), ptr(vxr), ptr(vzr), ptr(em0), ptr(a0),
-            int(tau_mode or 0), self._stream()), self.ctx, "rjp_build_fields")
+        self._call("rjp_build_fields", C.byref(geom), dtype, _ptr(nd), _ptr(xi), temp.data_ptr(),
+                   _ptr(pf), _ptr(ts), _ptr(vy), _ptr(ffr), _ptr(arr), _ptr(vxr), _ptr(vzr),
+                   _ptr(em0), _ptr(a0), int(tau_mode or 0))
         out = DeviceFields((geom.nx, geom.ny, geom.nz), dtype, geom.csize, nd, xi, temp, pf,
                            ts, vy, ffr, arr)
         out.vx_raw, out.vz_raw = vxr, vzr
@@ -642,11 +635,9 @@ class RTEngine:
                if getattr(fields, k) is None}
         if not new:
             return fields
-        ptr = lambda k: new[k].data_ptr() if k in new else None
-        self._check(self.lib.rjp_build_fields(
-            self.ctx, C.byref(geom), fields.dtype, ptr("nd"), ptr("xi"), None, ptr("pf"), None,
-            ptr("vy"), None, None, None, None, None, None, 0, self._stream()), self.ctx,
-            "rjp_build_fields")
+        nd, xi, pf, vy = (_ptr(new.get(k)) for k in ("nd", "xi", "pf", "vy"))
+        self._call("rjp_build_fields", C.byref(geom), fields.dtype, nd, xi, None, pf, None, vy,
+                   None, None, None, None, None, None, 0)
         for k, t in new.items():
             setattr(fields, k, t)
         return fields
@@ -672,11 +663,9 @@ class RTEngine:
         nd, xi, pf = ((self._empty(n, dtype) for _ in range(3)) if wide else (None, None, None))
         temp, ts = self._empty(n, dtype), self._empty(n, dtype)
         vy = self._empty(n, dtype) if with_vy else None
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        self._check(self.lib.rjp_synth_fields(
-            self.ctx, int(seed), int(temp_mode), int(nz), int(cell0), int(n), dtype,
-            ptr(nd), ptr(xi), temp.data_ptr(), ptr(pf), ts.data_ptr(), ptr(vy), ptr(em0),
-            ptr(a0), int(tau_mode or 0), self._stream()), self.ctx, "rjp_synth_fields")
+        self._call("rjp_synth_fields", int(seed), int(temp_mode), int(nz), int(cell0), int(n),
+                   dtype, _ptr(nd), _ptr(xi), temp.data_ptr(), _ptr(pf), ts.data_ptr(), _ptr(vy),
+                   _ptr(em0), _ptr(a0), int(tau_mode or 0))
         out = DeviceFields(shape, dtype, csize_au, nd, xi, temp, pf, ts, vy)
         if a0 is not None:
             out.a0, out.a0_mode = a0, int(tau_mode)
@@ -743,9 +732,7 @@ class RTEngine:
         cached = getattr(fields, "_ts_unmasked", None)
         if cached is None or cached[0] != key:
             out = self._empty(fields.ncells, fields.dtype)
-            self._check(self.lib.rjp_unmask_launch_times(self.ctx, C.byref(full), jet,
-                                                        out.data_ptr(), self._stream()),
-                       self.ctx, "rjp_unmask_launch_times")
+            self._call("rjp_unmask_launch_times", C.byref(full), jet, out.data_ptr())
             cached = fields._ts_unmasked = (key, out)
         fs.d_ts = cached[1].data_ptr()
         return fs
@@ -769,11 +756,8 @@ class RTEngine:
         fs = self._scan_struct(fields, bursts, E)
         mkey = self._attach_moment_cache(fields, bursts, fs, E, em is not None)
         ep = _lib.dbl_array(epochs_s)
-        self._check(self.lib.rjp_ff_scan(
-            self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None, ep, E,
-            int(gff_mode), sumA.data_ptr(), em.data_ptr() if em is not None else None,
-            tavg.data_ptr() if tavg is not None else None, work.data_ptr(), work.numel(),
-            self._stream()), self.ctx, "rjp_ff_scan")
+        self._call("rjp_ff_scan", C.byref(fs), _ref(bursts), ep, E, int(gff_mode), sumA.data_ptr(),
+                   _ptr(em), _ptr(tavg), work.data_ptr(), work.numel())
         if mkey is not None:
             self._note_moment_sweep(fields, mkey)
         return sumA, em, tavg
@@ -792,13 +776,10 @@ class RTEngine:
             if ftot is not None else None
         fs = self._scan_struct(fields, bursts, E)
         mkey = self._attach_moment_cache(fields, bursts, fs, E, em is not None)
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        self._check(self.lib.rjp_ff_step(
-            self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None,
-            _lib.dbl_array(epochs_s), E, int(gff_mode), tavg.data_ptr(), _lib.dbl_array(ctau),
-            _lib.dbl_array(cflux), F, sumA.data_ptr(), ptr(em), ptr(tau), ptr(flux), ptr(ftot),
-            work.data_ptr(), work.numel(), ptr(wm), wm.numel() if wm is not None else 0,
-            self._stream()), self.ctx, "rjp_ff_step")
+        self._call("rjp_ff_step", C.byref(fs), _ref(bursts), _lib.dbl_array(epochs_s), E,
+                   int(gff_mode), tavg.data_ptr(), _lib.dbl_array(ctau), _lib.dbl_array(cflux), F,
+                   sumA.data_ptr(), _ptr(em), _ptr(tau), _ptr(flux), _ptr(ftot), work.data_ptr(),
+                   work.numel(), _ptr(wm), wm.numel() if wm is not None else 0)
         if mkey is not None:
             self._note_moment_sweep(fields, mkey)
         return out
@@ -932,9 +913,9 @@ class RTEngine:
         ep = _lib.dbl_array(epochs_s)
         ms = C.c_double()
         self._check(self.lib.rjp_time_ff_scan(
-            self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None, ep, E,
-            int(gff_mode), sumA.data_ptr(), em.data_ptr() if want_em else None,
-            tavg.data_ptr() if want_tavg else None, work.data_ptr(), work.numel(),
+            self.ctx, C.byref(fs), _ref(bursts), ep, E,
+            int(gff_mode), sumA.data_ptr(), _ptr(em),
+            _ptr(tavg), work.data_ptr(), work.numel(),
             self._stream(), int(reps), C.byref(ms)), self.ctx, "rjp_time_ff_scan")
         return ms.value
 
@@ -952,11 +933,8 @@ class RTEngine:
         wb = self.lib.rjp_ff_maps_workspace(P, E, F)
         work = self._workspace_maps(wb) if ftot is not None else None
         a, b = _lib.dbl_array(ctau), _lib.dbl_array(cflux)
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        self._check(self.lib.rjp_ff_maps(
-            self.ctx, sumA.data_ptr(), tavg.data_ptr(), P, E, a, b, F, ptr(tau), ptr(flux),
-            ptr(ftot), ptr(work), work.numel() if work is not None else 0, self._stream()),
-            self.ctx, "rjp_ff_maps")
+        self._call("rjp_ff_maps", sumA.data_ptr(), tavg.data_ptr(), P, E, a, b, F, _ptr(tau),
+                   _ptr(flux), _ptr(ftot), _ptr(work), work.numel() if work is not None else 0)
         return tau, flux, ftot
 
     def ff_cells(self, fields, bursts, time_s, gff_mode, ctau):
@@ -964,10 +942,8 @@ class RTEngine:
         F = len(ctau)
         out = self._f64(F, fields.ncells)
         fs = fields.struct()
-        self._check(self.lib.rjp_ff_cells(
-            self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None,
-            float(time_s), int(gff_mode), _lib.dbl_array(ctau), F, out.data_ptr(),
-            self._stream()), self.ctx, "rjp_ff_cells")
+        self._call("rjp_ff_cells", C.byref(fs), _ref(bursts), float(time_s), int(gff_mode),
+                   _lib.dbl_array(ctau), F, out.data_ptr())
         return out
 
     def ff_formal(self, fields, bursts, time_s, gff_mode, ctau, csrc, out=None):
@@ -980,10 +956,8 @@ class RTEngine:
         if out is None:
             out = self._f64(F, fields.npix)
         fs = fields.struct()
-        self._check(self.lib.rjp_ff_formal(
-            self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None,
-            float(time_s), int(gff_mode), _lib.dbl_array(ctau), _lib.dbl_array(csrc), F,
-            out.data_ptr(), self._stream()), self.ctx, "rjp_ff_formal")
+        self._call("rjp_ff_formal", C.byref(fs), _ref(bursts), float(time_s), int(gff_mode),
+                   _lib.dbl_array(ctau), _lib.dbl_array(csrc), F, out.data_ptr())
         return out
 
     def ff_formal_sweep(self, fields, bursts, epochs_s, gff_mode, ctau, csrc, want_maps=False,
@@ -1007,13 +981,9 @@ class RTEngine:
         if want_totals:
             work = self._workspace(max(1, self.lib.rjp_ff_formal_sweep_workspace(nx, ny, nz, E, F)))
         fs = fields.struct()
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        self._check(self.lib.rjp_ff_formal_sweep(
-            self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None,
-            _lib.dbl_array(epochs_s), E, int(gff_mode), _lib.dbl_array(ctau),
-            _lib.dbl_array(csrc), F, ptr(maps), ptr(ftot), ptr(work),
-            work.numel() if work is not None else 0, self._stream()), self.ctx,
-            "rjp_ff_formal_sweep")
+        self._call("rjp_ff_formal_sweep", C.byref(fs), _ref(bursts), _lib.dbl_array(epochs_s), E,
+                   int(gff_mode), _lib.dbl_array(ctau), _lib.dbl_array(csrc), F, _ptr(maps),
+                   _ptr(ftot), _ptr(work), work.numel() if work is not None else 0)
         return maps, ftot
 
     def ff_grad(self, fields, bursts, epochs_s, gff_mode, tavg=None, ctau=None, cflux=None,
@@ -1041,13 +1011,10 @@ class RTEngine:
         dftot = self._f64(E, F, n_par) if totals else None
         work = self._workspace(max(1, self.lib.rjp_ff_grad_workspace(nx, ny, nz, E, n_par, F)))
         fs = fields.struct()
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        self._check(self.lib.rjp_ff_grad(
-            self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None,
-            _lib.dbl_array(epochs_s), E, int(gff_mode), ptr(tavg),
-            _lib.dbl_array(ctau) if totals else None, _lib.dbl_array(cflux) if totals else None,
-            F, ptr(sumA), ptr(dsumA), ptr(ftot), ptr(dftot), work.data_ptr(), work.numel(),
-            self._stream()), self.ctx, "rjp_ff_grad")
+        self._call("rjp_ff_grad", C.byref(fs), _ref(bursts), _lib.dbl_array(epochs_s), E,
+                   int(gff_mode), _ptr(tavg), _lib.dbl_array(ctau) if totals else None,
+                   _lib.dbl_array(cflux) if totals else None, F, _ptr(sumA), _ptr(dsumA),
+                   _ptr(ftot), _ptr(dftot), work.data_ptr(), work.numel())
         return sumA, dsumA, ftot, dftot
 
     def ff_formal_grad(self, fields, bursts, epochs_s, gff_mode, ctau, csrc, want_maps=False):
@@ -1069,12 +1036,9 @@ class RTEngine:
         dmaps = self._f64(E, F, n_par, fields.npix) if want_maps else None
         work = self._workspace(max(1, self.lib.rjp_ff_formal_grad_workspace(nx, ny, nz, E, n_par, F)))
         fs = fields.struct()
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        self._check(self.lib.rjp_ff_formal_grad(
-            self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None,
-            _lib.dbl_array(epochs_s), E, int(gff_mode), _lib.dbl_array(ctau),
-            _lib.dbl_array(csrc), F, ptr(ftot), ptr(dftot), ptr(dmaps), work.data_ptr(),
-            work.numel(), self._stream()), self.ctx, "rjp_ff_formal_grad")
+        self._call("rjp_ff_formal_grad", C.byref(fs), _ref(bursts), _lib.dbl_array(epochs_s), E,
+                   int(gff_mode), _lib.dbl_array(ctau), _lib.dbl_array(csrc), F, _ptr(ftot),
+                   _ptr(dftot), _ptr(dmaps), work.data_ptr(), work.numel())
         return ftot, dftot, dmaps
 
     # -- K10 -----------------------------------------------------------------------------------
@@ -1112,10 +1076,8 @@ class RTEngine:
             raise ValueError("vis: u and v must have the same length >= 1")
         out = self._f64(M, K, 2)
         work = self._workspace(max(1, self.lib.rjp_vis_workspace(M, nx, nz, K)))
-        self._check(self.lib.rjp_vis(
-            self.ctx, maps.data_ptr(), M, nx, nz, _lib.dbl_array(su), _lib.dbl_array(sv),
-            du.data_ptr(), dv.data_ptr(), K, out.data_ptr(), work.data_ptr(), work.numel(),
-            self._stream()), self.ctx, "rjp_vis")
+        self._call("rjp_vis", maps.data_ptr(), M, nx, nz, _lib.dbl_array(su), _lib.dbl_array(sv),
+                   du.data_ptr(), dv.data_ptr(), K, out.data_ptr(), work.data_ptr(), work.numel())
         return torch.view_as_complex(out)
 
     def rrl_cells(self, fields, bursts, time_s, line, nus):
@@ -1123,10 +1085,8 @@ class RTEngine:
         F = len(nus)
         out = self._f64(F, fields.ncells)
         fs = fields.struct()
-        self._check(self.lib.rjp_rrl_cells(
-            self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None,
-            float(time_s), C.byref(line), _lib.dbl_array(nus), F, out.data_ptr(),
-            self._stream()), self.ctx, "rjp_rrl_cells")
+        self._call("rjp_rrl_cells", C.byref(fs), _ref(bursts), float(time_s), C.byref(line),
+                   _lib.dbl_array(nus), F, out.data_ptr())
         return out
 
     # -- K3 ------------------------------------------------------------------------------------
@@ -1136,10 +1096,8 @@ class RTEngine:
         tau = self._f64(F, fields.npix)
         fs = fields.struct()
         nu = _lib.dbl_array(nus)
-        self._check(self.lib.rjp_rrl_scan(
-            self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None,
-            float(time_s), C.byref(line), nu, F, tau.data_ptr(), self._stream()), self.ctx,
-            "rjp_rrl_scan")
+        self._call("rjp_rrl_scan", C.byref(fs), _ref(bursts), float(time_s), C.byref(line), nu, F,
+                   tau.data_ptr())
         return tau
 
     def rrl_formal(self, fields, bursts, time_s, gff_mode, line, nus, ctau, csrc, hnu_k,
@@ -1165,12 +1123,9 @@ class RTEngine:
         if out is None:
             out = self._f64(F, fields.npix)
         fs = fields.struct()
-        self._check(self.lib.rjp_rrl_formal(
-            self.ctx, C.byref(fs), C.byref(bursts) if bursts is not None else None,
-            float(time_s), int(gff_mode), C.byref(line), _lib.dbl_array(nus),
-            _lib.dbl_array(ctau), _lib.dbl_array(csrc), _lib.dbl_array(hnu_k), F,
-            add.data_ptr() if add is not None else None, out.data_ptr(), self._stream()),
-            self.ctx, "rjp_rrl_formal")
+        self._call("rjp_rrl_formal", C.byref(fs), _ref(bursts), float(time_s), int(gff_mode),
+                   C.byref(line), _lib.dbl_array(nus), _lib.dbl_array(ctau), _lib.dbl_array(csrc),
+                   _lib.dbl_array(hnu_k), F, _ptr(add), out.data_ptr())
         return out
 
     def rrl_maps(self, tau_rrl, tau_ff, tavg, flux_ff, cflux_rrl, hnu_k, want_ftot=True):
@@ -1181,12 +1136,9 @@ class RTEngine:
         wb = self.lib.rjp_ff_maps_workspace(P, 1, F)
         work = self._workspace_maps(wb) if want_ftot else None
         a, b = _lib.dbl_array(cflux_rrl), _lib.dbl_array(hnu_k)
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        self._check(self.lib.rjp_rrl_maps(
-            self.ctx, tau_rrl.data_ptr(), tau_ff.data_ptr(), tavg.data_ptr(), ptr(flux_ff), P,
-            a, b, F, flux.data_ptr(), ptr(ftot), ptr(work),
-            work.numel() if work is not None else 0, self._stream()), self.ctx,
-            "rjp_rrl_maps")
+        self._call("rjp_rrl_maps", tau_rrl.data_ptr(), tau_ff.data_ptr(), tavg.data_ptr(),
+                   _ptr(flux_ff), P, a, b, F, flux.data_ptr(), _ptr(ftot), _ptr(work),
+                   work.numel() if work is not None else 0)
         return flux, ftot
 
 

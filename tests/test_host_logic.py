@@ -664,3 +664,41 @@ def test_burst_gaussian_polynomial_meets_its_documented_bound():
     ref = np.exp2(f)
     assert np.max(np.abs(horner("RJP_EXP2_D", 8) / ref - 1.0)) < 1.2e-12
     assert np.max(np.abs(horner("RJP_EXP2_C", 10) / ref - 1.0)) < 1e-15
+
+
+def test_pure_argument_checks_from_plain_cpp(tmp_path):
+    """rajepy_amd/csrc/rjp_args.h -- the argument checks that are pure functions of the caller's
+    structs -- compiled into a stand-alone program by plain g++ (tests/rjp_args_cases.cpp: no HIP,
+    hand-built structs).  Every refusal it prints must be, status and message, what the library
+    gave for the same case on the GPU (tests/golden/abi_refusals.json); the calls it marks valid
+    pass; the chain-rule table of the sensitivity calls holds (2 amp inv2s2, 1, -amp) per burst,
+    behind a leading 1 for rjp_ff_grad."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "no C++ compiler"
+    exe = tmp_path / "rjp_args_cases"
+    subprocess.run([cxx, "-std=c++17", "-Wall", "-Werror", "-I",
+                    os.path.join(ROOT, "rajepy_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "rjp_args_cases.cpp"), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    golden = json.load(open(os.path.join(GOLDEN, "abi_refusals.json")))
+    refusals, valid, scales = set(), 0, {}
+    for line in out.splitlines():
+        entry, case, *rest = line.split("\t")
+        if entry == "scale":
+            scales.setdefault(case, []).append([float(v) for v in rest])
+        elif case == "valid":
+            assert rest == ["0", ""], line
+            valid += 1
+        else:
+            assert [int(rest[0]), rest[1]] == golden[entry][case], line
+            refusals.add(entry)
+    # (one entry point per check and flag combination the program drives)
+    assert refusals == {"rjp_compact_fields", "rjp_y_bounds", "rjp_rrl_scan", "rjp_tavg",
+                        "rjp_ff_formal_sweep", "rjp_ff_grad", "rjp_ff_formal_grad",
+                        "rjp_lt_count", "rjp_srt_count"} and valid > 0
+    per_burst = {0: [2.0 * 2.0 * 1e-14, 1.0, -2.0], 1: [2.0 * 1.0 * 1e-14, 1.0, -1.0]}
+    for who, lead in (("rjp_ff_grad", [1.0]), ("rjp_ff_formal_grad", [])):
+        assert scales[who] == [lead + per_burst[0] + per_burst[1],
+                               lead + per_burst[0] * 8 + per_burst[1] * 8], who

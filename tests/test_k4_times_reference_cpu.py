@@ -6,8 +6,8 @@ without a GPU:
     -- the baseline the device bound of tests/test_gpu_k4_reference.py is judged against;
   * `JetModel._host_launch_times`, the fallback of a refused model, holds the bound on the exactly
     degenerate case;
-  * a float64 NumPy restatement of the device's evaluation (fields.hip: hyp_series, hyp_flow_factor;
-    rjprt.hip: hyp_plan, which picks the switch point between the two series and refuses what neither
+  * a float64 NumPy restatement of the device's evaluation (fields.hip: hyp_series, hyp_flow_factor,
+    and its host half hyp_plan, which picks the switch point between the two series and refuses what neither
     can hold) meets the bound on every case it does not refuse, and refuses only what may be refused.
 
 The bound on a launch time is the project's own: |got - ref| <= 1e-10 |ref| + 1e-3 s.
@@ -26,7 +26,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 FIXTURE = os.path.join(HERE, "golden", "k4_times.npz")
 RTOL, ATOL = 1e-10, 1e-3
 
-# ---- restatement of rjprt.hip:hyp_plan and fields.hip:hyp_series / hyp_flow_factor ---------------
+# ---- restatement of fields.hip: hyp_plan (host) and hyp_series / hyp_flow_factor (device) ---------
 HYP_MAX_TERMS = 400                    # kHypMaxTerms: no series may need more
 HYP_CONN_TERMS = 100                   # kHypConnTerms: ... and the connection series not more than this
 HYP_STOP = 1e-17                       # a term below this share of the sum ends a series
