@@ -674,6 +674,44 @@ int rjp_vis(rjp_ctx* ctx, const double* d_maps, int32_t n_maps, int32_t nx, int3
             const double* h_su, const double* h_sv, const double* d_u, const double* d_v,
             int32_t n_vis, double* d_vis, void* d_work, size_t work_bytes, void* stream);
 
+/* ---- K11: dirty images from visibilities, the transpose of K10 ------------------------------------
+ * The reference goes from the uv-plane back to the sky only outside itself: CASA tclean transforms
+ * the simulated visibilities into the dirty image that imfit then measures (classes.py:2770-2782);
+ * nothing inside RaJePy does it.  This entry point evaluates that image directly -- a direct sum, no
+ * gridding, no FFT -- for a stack of n_maps visibility sets on the same n_vis baselines:
+ *   D[m, ix nz + iz] = sum_k w[k] Re( V[m, k] exp(+2 pi i (a (ix - (nx-1)/2) + b (iz - (nz-1)/2))) )
+ *                      a = h_su[m] d_u[k],  b = h_sv[m] d_v[k]              (cycles per cell)
+ *   d_vis [n_maps][n_vis][2] (re, im), the layout rjp_vis writes
+ *   h_su, h_sv [n_maps]      HOST: cycles per cell per unit of d_u / d_v, signs included; no sky
+ *                            convention here either
+ *   d_u, d_v [n_vis]         the baselines;  d_w [n_vis] the weights, NULL = all ones
+ *   nx, nz                   the OUTPUT grid, pixel order p = ix nz + iz, centre ((nx-1)/2, (nz-1)/2):
+ *                            with the scales it need not be the grid the visibilities came from
+ *   d_img [n_maps * nx * nz] float64, NOT normalised (divide by sum w for Jy per beam)
+ * With the same scales and grid, D is exactly the real transpose of rjp_vis:
+ * sum_k w_k Re(conj(Y_k) V_k) = sum_p I_p D_p for V = rjp_vis of I and D = this call on Y.
+ * FLAGS: visibility k of map m adds nothing when any of Re V[m,k], Im V[m,k], w[k], d_u[k], d_v[k]
+ * is non-finite (the nansum rule; rjp_vis writes NaN for a non-finite baseline, so the chain flags
+ * consistently); a map whose visibilities are all flagged gives exact zeros.  The sums run in a
+ * fixed order without floating-point atomics: a repeated call gives the same bits.
+ * ARGUMENT RANGE: as rjp_vis -- one double product per phase, |a| nx / 2 and |b| nz / 2 below 2^29
+ * cycles; the product's rounding costs 2 pi (|a| nx / 2 + |b| nz / 2) 2^-53 of sum_k |w_k| |V_k|
+ * per pixel, the sum over k about 2 n_vis 2^-53 more.
+ * RETURNS the number of workgroups (output tiles) it enqueued, > 0 -- n_maps x row tiles (128 rows,
+ * 64 for nx <= 64) x column tiles (128) x k-splits (fewer than 256 tiles: the visibilities are split
+ * over workgroups, at least 64 each, and the partial images summed in split order) -- or a negative
+ * RJP_ERR_*: the one entry point whose return value is not a bare status.  Everything is validated
+ * before anything is enqueued, and no output or workspace byte is touched on a refusal: RJP_ERR_ARG
+ * for a NULL ctx, d_vis, h_su, h_sv, d_u, d_v or d_img, n_maps, n_vis, nx or nz < 1, a non-finite
+ * h_su / h_sv, or more than 2^31 - 1 workgroups; RJP_ERR_WORKSPACE for a d_work smaller than the
+ * workspace query (8 bytes per map, k-split and pixel, 16 without a split; 0 from it = a bad
+ * argument). */
+size_t rjp_vis_adjoint_workspace(int32_t n_maps, int32_t nx, int32_t nz, int32_t n_vis);
+int64_t rjp_vis_adjoint(rjp_ctx* ctx, const double* d_vis, int32_t n_maps, int32_t n_vis,
+                        const double* h_su, const double* h_sv, const double* d_u, const double* d_v,
+                        const double* d_w, int32_t nx, int32_t nz, double* d_img,
+                        void* d_work, size_t work_bytes, void* stream);
+
 /* ---- K4: geometry -> fields on the device --------------------------------------------
  * Replaces the lazily cached grids of JetModel (fill_factor/areas classes.py:657-669,
  * 763-764; grid_rwp 521-525; rreff 549-555; _nd 877-897; ion_fraction 915-934;

@@ -1054,6 +1054,106 @@ class JetModel:
                 dV[e0:e0 + len(chunk), :, i] = raw[:, :, k:k + 3] * np.asarray(chain)[:, None]
         return V, dV
 
+    # ------------------------------------------------------------------ dirty images ----
+    def _image_grid(self, shape, cell_as):
+        """(ni, nj, cell [rad]) of an imaging grid: the model's own by default."""
+        ni, nj = (self.nx, self.nz) if shape is None else (int(shape[0]), int(shape[1]))
+        if ni < 1 or nj < 1:
+            raise ValueError("dirty image: `shape` must be two positive sizes")
+        if cell_as is None:
+            cell = np.arctan((self.csize * con.au) / (self.params["target"]["dist"] * con.parsec))
+        else:
+            cell = np.radians(float(cell_as) / 3600.)
+            if not (np.isfinite(cell) and cell > 0.):
+                raise ValueError("dirty image: `cell_as` must be a positive number of arcseconds")
+        return ni, nj, float(cell)
+
+    def _dirty_images(self, V, u_d, v_d, freqs, weights, shape, cell_as, mfs):
+        """Dirty images [Jy / beam] of the visibilities `V` (complex device tensor [F, K]) at the
+        baselines (`u_d`, `v_d`) [m] -> host array (F, ni, nj), or (1, ni, nj) with `mfs`.
+        `RTEngine.vis_adjoint` on chunks of channels whose images stay under VIS_STACK_BYTES
+        (K10's `_vis_chunk` rule on the imaging grid), divided by the sum of the weights of the
+        baselines that are not flagged; nothing but the images leaves the device."""
+        import torch
+        from . import engine as E
+        eng = self.engine
+        ni, nj, cell = self._image_grid(shape, cell_as)
+        su, sv = E.image_scales(freqs, cell)
+        F, K = int(V.shape[0]), int(V.shape[1])
+        w_d = eng._device_f64(weights) if weights is not None else None
+        if w_d is not None and w_d.numel() != K:
+            raise ValueError("dirty image: `weights` must have one entry per baseline (%d)" % K)
+        good = torch.isfinite(u_d) & torch.isfinite(v_d)
+        if w_d is not None:
+            good = good & torch.isfinite(w_d)
+        wsum = (torch.where(good, w_d, torch.zeros_like(w_d)).sum() if w_d is not None
+                else good.sum().to(torch.float64))
+        if mfs:
+            # one visibility set of F K points, baselines in cycles per cell, scale 1
+            dsu = torch.from_numpy(np.ascontiguousarray(su)).to(eng.device)
+            dsv = torch.from_numpy(np.ascontiguousarray(sv)).to(eng.device)
+            ua = (dsu[:, None] * u_d[None, :]).reshape(-1)
+            va = (dsv[:, None] * v_d[None, :]).reshape(-1)
+            wa = w_d.repeat(F) if w_d is not None else None
+            img = eng.vis_adjoint(V.reshape(1, F * K), ni, nj, [1.0], [1.0], ua, va, wa)
+            return (img / (wsum * F)).cpu().numpy().reshape(1, ni, nj)
+        out = np.zeros((F, ni, nj))
+        step = max(1, self.VIS_STACK_BYTES // (ni * nj * 8))
+        for f0 in range(0, F, step):
+            img = eng.vis_adjoint(V[f0:f0 + step].contiguous(), ni, nj, su[f0:f0 + step],
+                                  sv[f0:f0 + step], u_d, v_d, w_d)
+            out[f0:f0 + step] = (img / wsum).cpu().numpy().reshape(-1, ni, nj)
+            del img
+        return out
+
+    def dirty_image_ff(self, u_m, v_m, freq, weights=None, shape=None, cell_as=None, formal=False,
+                       mfs=False):
+        """Dirty images [Jy / beam] of the `flux_ff` maps as an array with the baselines (`u_m`,
+        `v_m`) in metres sees them -> float64 (F, ni, nj): `visibilities_ff`'s direct Fourier sum
+        followed by its transpose (`RTEngine.vis_adjoint`, rjp_vis_adjoint), no gridding and no
+        deconvolution -- what CASA tclean with niter = 0 makes of the simulated measurement set,
+        without the measurement set.  `weights` [K]: the imaging weights (None = natural, all
+        ones); the image is divided by their sum, so a point source of S Jy at the phase centre
+        peaks at S.  `shape` = (ni, nj) and `cell_as` [arcsec] describe the imaging grid (the
+        model's own by default; the reference images at a quarter of the beam on >= 500 pixels);
+        convention: `engine.image_scales`.  `formal`: as `flux_ff`.  `mfs=True`: the channels go
+        into ONE image (1, ni, nj), every channel at its own (u, v) / lambda, as tclean
+        specmode='mfs' combines them.  A baseline with a non-finite u, v or weight is flagged.
+        Calling rank only."""
+        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
+        eng = self.engine
+        u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
+        maps = self._ff_products(freqs, flux=True, device=True, formal=formal)
+        su, sv = self._vis_scales(freqs)
+        V = eng.vis(maps.reshape(len(freqs), -1), self.nx, self.nz, su, sv, u_d, v_d)
+        return self._dirty_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs)
+
+    def dirty_image_rrl(self, rrl, u_m, v_m, freq, weights=None, shape=None, cell_as=None,
+                        contsub=True, formal=False, mfs=False):
+        """Dirty images [Jy / beam] of the `flux_rrl` maps (same arguments) -> (F, ni, nj); see
+        `dirty_image_ff`."""
+        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
+        eng = self.engine
+        u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
+        maps = self._rrl_flux(rrl, freqs, True, contsub, formal=formal, device=True)
+        su, sv = self._vis_scales(freqs)
+        V = eng.vis(maps.reshape(len(freqs), -1), self.nx, self.nz, su, sv, u_d, v_d)
+        return self._dirty_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs)
+
+    def dirty_beam(self, u_m, v_m, freq, weights=None, shape=None, cell_as=None, mfs=False):
+        """The dirty beam (point-spread function) of the (u, v) coverage at every frequency ->
+        float64 (F, ni, nj), or (1, ni, nj) with `mfs`: `dirty_image_ff` of visibilities that are
+        all 1.  At the centre pixel of an odd-sized grid every phase is exactly 0 and the beam
+        is 1 (to the last bit with unit weights); it is symmetric under point reflection."""
+        import torch
+        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
+        eng = self.engine
+        u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
+        V = torch.zeros(len(freqs), int(u_d.numel()), 2, dtype=torch.float64, device=eng.device)
+        V[..., 0] = 1.0
+        return self._dirty_images(torch.view_as_complex(V), u_d, v_d, freqs, weights, shape,
+                                  cell_as, mfs)
+
     # ------------------------------------------------------------------ products ----
     FORMAL_HISTORY = "Formal solution along the line of sight, observer at iy = 0"
 

@@ -126,4 +126,19 @@ inline int check_layout(const rjp_fields* f, int K, const char* name, int max_K,
   return RJP_OK;
 }
 
+// What rjp_vis_adjoint takes, in the order it refuses: NULL pointers, counts below 1, a non-finite
+// scale.  (`d_w` may be NULL; the grid and the workspace are checked where the tiling lives.)
+inline int check_vis_adjoint(const double* d_vis, int n_maps, int n_vis, const double* h_su,
+                             const double* h_sv, const double* d_u, const double* d_v, int nx,
+                             int nz, const double* d_img, std::string& err) {
+  if (!d_vis || !h_su || !h_sv || !d_u || !d_v || !d_img)
+    return refuse(err, "rjp_vis_adjoint: NULL visibilities, scales, baselines or output");
+  if (n_maps < 1 || n_vis < 1 || nx < 1 || nz < 1)
+    return refuse(err, "rjp_vis_adjoint: n_maps, n_vis, nx and nz must be positive");
+  for (int m = 0; m < n_maps; ++m)
+    if (!std::isfinite(h_su[m]) || !std::isfinite(h_sv[m]))
+      return refuse(err, "rjp_vis_adjoint: non-finite h_su / h_sv");
+  return RJP_OK;
+}
+
 }  // namespace rjp_args

@@ -769,7 +769,7 @@ __host__ __device__ __forceinline__ double hash_u01(uint64_t seed, uint64_t fiel
 // ---- sin / cos of an argument in turns --------------------------------------------------------
 // sin(2 pi u), cos(2 pi u): quarter-turn reduction, Taylor polynomials on |w| <= pi/4
 // (truncation < 2e-14 / 1e-15).  |u| < 2^30.  Used by the Voigt pole terms (rrl_voigt.h) and the
-// phasors of K10 (vis.hip).
+// phasors of K10 and K11 (vis.hip, vis_adjoint.hip).
 __device__ __forceinline__ void sincos_2pi(double u, double& sn, double& cs) {
   const double k = __builtin_rint(4.0 * u);
   const double w = 6.28318530717958647692 * __builtin_fma(-0.25, k, u);

@@ -1,6 +1,6 @@
 // Host-side interface between the translation units of librjprt (rjprt.hip = the C-ABI,
 // ff_scan.hip, ff_scan_inst.hip x 5, fields.hip, rrl_scan.hip, rrl_formal.hip, ff_grad.hip,
-// ff_formal_sweep.hip, ff_formal_grad.hip, vis.hip, ...): launch
+// ff_formal_sweep.hip, ff_formal_grad.hip, vis.hip, vis_adjoint.hip, ...): launch
 // wrappers and the small structs they exchange.  Nothing here is exported; the library's surface is include/rjprt.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -220,6 +220,22 @@ bool vis_grid_ok(int n_maps, int nx, int n_vis);
 hipError_t vis_launch(const double* maps, int n_maps, int nx, int nz, const double* d_su,
                       const double* d_sv, const double* u, const double* v, int n_vis, double* vis,
                       double* part, hipStream_t st);
+
+// ---- vis_adjoint.hip: dirty images from visibilities, the transpose of K10 (K11) ----------------
+struct VisAdjointTiling {
+  int row_tiles, col_tiles;     // of 128 (nx > 64) or 64 rows x 128 columns
+  int k_splits;                 // ranges of visibilities over workgroups ...
+  int64_t k_per_split;          // ... of this many each, a multiple of 16 (may pass 2^31 - 1)
+  int64_t workgroups;           // n_maps x row_tiles x col_tiles x k_splits; INT64_MAX: too many
+};
+VisAdjointTiling vis_adjoint_tiling(int n_maps, int nx, int nz, int n_vis);
+// >= 16; 0: does not fit a size_t
+size_t vis_adjoint_workspace_bytes(int n_maps, int nx, int nz, int n_vis);
+// d_su / d_sv[n_maps]: device copies of the scales; `w` may be nullptr (all ones); `part`
+// (vis_adjoint_workspace_bytes) holds the k-splits' partial images when there are any
+hipError_t vis_adjoint_launch(const double* vis, int n_maps, int n_vis, const double* d_su,
+                              const double* d_sv, const double* u, const double* v, const double* w,
+                              int nx, int nz, double* img, double* part, hipStream_t st);
 
 // ---- ff_scan_inst.hip: one slice of the K1 kernel family per translation unit -------------
 #define RJP_SCAN_SLICE_ARGS                                                                  \

@@ -1029,6 +1029,39 @@ int rjp_vis(rjp_ctx* ctx, const double* d_maps, int32_t n_maps, int32_t nx, int3
                 });
 }
 
+size_t rjp_vis_adjoint_workspace(int32_t n_maps, int32_t nx, int32_t nz, int32_t n_vis) {
+  if (n_maps <= 0 || nx <= 0 || nz <= 0 || n_vis <= 0) return 0;
+  return rjp::vis_adjoint_workspace_bytes(n_maps, nx, nz, n_vis);
+}
+
+int64_t rjp_vis_adjoint(rjp_ctx* ctx, const double* d_vis, int32_t n_maps, int32_t n_vis,
+                        const double* h_su, const double* h_sv, const double* d_u,
+                        const double* d_v, const double* d_w, int32_t nx, int32_t nz,
+                        double* d_img, void* d_work, size_t work_bytes, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_vis_adjoint(d_vis, n_maps, n_vis, h_su, h_sv, d_u, d_v, nx, nz,
+                                           d_img, m);
+      }))
+    return r;
+  const rjp::VisAdjointTiling t = rjp::vis_adjoint_tiling(n_maps, nx, nz, n_vis);
+  if (t.workgroups > (int64_t)INT32_MAX)
+    return fail(ctx, RJP_ERR_ARG, "rjp_vis_adjoint: more than 2^31 - 1 workgroups");
+  const size_t need = rjp::vis_adjoint_workspace_bytes(n_maps, nx, nz, n_vis);
+  if (need == 0) return fail(ctx, RJP_ERR_ARG, "rjp_vis_adjoint: the workspace size overflows");
+  if (!d_work || work_bytes < need)
+    return fail(ctx, RJP_ERR_WORKSPACE,
+                "rjp_vis_adjoint: workspace smaller than rjp_vis_adjoint_workspace()");
+  hipStream_t st = (hipStream_t)stream;
+  const int r = staged(ctx, st, "vis_adjoint_launch", nullptr,
+                       {{h_su, (size_t)n_maps}, {h_sv, (size_t)n_maps}},
+                       [&](double* const* d, const double*) {
+                         return rjp::vis_adjoint_launch(d_vis, n_maps, n_vis, d[0], d[1], d_u, d_v,
+                                                        d_w, nx, nz, d_img, (double*)d_work, st);
+                       });
+  return r ? r : t.workgroups;
+}
+
 int rjp_rrl_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
                    double time_s, int32_t gff_mode, const rjp_line* line, const double* h_nu,
                    const double* h_ctau, const double* h_csrc, const double* h_hnu_k,

@@ -1080,6 +1080,48 @@ class RTEngine:
                    du.data_ptr(), dv.data_ptr(), K, out.data_ptr(), work.data_ptr(), work.numel())
         return torch.view_as_complex(out)
 
+    # -- K11 -----------------------------------------------------------------------------------
+    def vis_adjoint(self, vis, nx, nz, su, sv, u, v, w=None):
+        """Dirty images of a stack of visibility sets (rjp_vis_adjoint), the real transpose of
+        `vis`: D[m, ix nz + iz] = sum_k w[k] Re(vis[m, k] exp(+2 pi i (su[m] u[k] (ix - (nx-1)/2) +
+        sv[m] v[k] (iz - (nz-1)/2)))) -> float64 device tensor [n_maps, nx * nz], NOT normalised.
+        `vis`: complex128 [n_maps, n_vis] or float64 [n_maps, n_vis, 2] device tensor (what `vis`
+        returns); `nx`, `nz`, `su`, `sv` describe the OUTPUT grid (`image_scales` builds the scales
+        of any cell size for baselines in metres); `u`, `v`, `w` [n_vis]: host arrays or device
+        tensors, `w` None = all ones.  A visibility with a non-finite value, weight or baseline
+        adds nothing.  Sums in a fixed order: a repeated call gives the same bits.  The number of
+        tiles the call enqueued is kept in `last_vis_adjoint_tiles`."""
+        torch = _torch()
+        nx, nz = int(nx), int(nz)
+        if isinstance(vis, torch.Tensor) and vis.dtype == torch.complex128:
+            vis = torch.view_as_real(vis)
+        if not (isinstance(vis, torch.Tensor) and vis.dtype == torch.float64 and
+                vis.device == self.device and vis.is_contiguous() and vis.dim() == 3 and
+                vis.shape[2] == 2 and vis.shape[0] >= 1 and vis.shape[1] >= 1):
+            raise ValueError("vis_adjoint: `vis` must be a contiguous complex128 [M, K] or float64 "
+                             "[M, K, 2] tensor on %s" % self.device)
+        if nx < 1 or nz < 1:
+            raise ValueError("vis_adjoint: nx and nz must be positive")
+        M, K = int(vis.shape[0]), int(vis.shape[1])
+        su = np.ascontiguousarray(su, dtype=np.float64).reshape(-1)
+        sv = np.ascontiguousarray(sv, dtype=np.float64).reshape(-1)
+        if su.size != M or sv.size != M:
+            raise ValueError("vis_adjoint: su and sv must have one entry per map (%d)" % M)
+        du, dv = self._device_f64(u), self._device_f64(v)
+        dw = self._device_f64(w) if w is not None else None
+        if du.numel() != K or dv.numel() != K or (dw is not None and dw.numel() != K):
+            raise ValueError("vis_adjoint: u, v and w must have one entry per visibility (%d)" % K)
+        out = self._f64(M, nx * nz)
+        work = self._workspace(max(1, self.lib.rjp_vis_adjoint_workspace(M, nx, nz, K)))
+        tiles = self.lib.rjp_vis_adjoint(self.ctx, vis.data_ptr(), M, K, _lib.dbl_array(su),
+                                         _lib.dbl_array(sv), du.data_ptr(), dv.data_ptr(),
+                                         _ptr(dw), nx, nz, out.data_ptr(), work.data_ptr(),
+                                         work.numel(), self._stream())
+        if tiles <= 0:
+            self._check(int(tiles), self.ctx, "rjp_vis_adjoint")
+        self.last_vis_adjoint_tiles = int(tiles)
+        return out
+
     def rrl_cells(self, fields, bursts, time_s, line, nus):
         """collapse=False: per-cell RRL optical depths -> device tensor [F, N]."""
         F = len(nus)
@@ -1159,6 +1201,17 @@ def vis_scales(freqs, csize_au, dist_pc):
         su = -cell nu / c,  sv = +cell nu / c   [cycles per cell per metre]."""
     freqs = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
     cell = np.arctan((csize_au * con.au) / (dist_pc * con.parsec))
+    return -cell * freqs / con.c, cell * freqs / con.c
+
+
+def image_scales(freqs, cell_rad):
+    """su[f], sv[f] of an image grid whose cells subtend `cell_rad` radians, for baselines in
+    METRES, under the sky convention of `vis_scales` (phase centre = grid centre, RA decreasing
+    with ix): su = -cell nu / c, sv = +cell nu / c.  `vis_scales` is the special case
+    cell = arctan(csize au / dist).  For `RTEngine.vis_adjoint` (any imaging grid) and
+    `RTEngine.vis`."""
+    freqs = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
+    cell = float(cell_rad)
     return -cell * freqs / con.c, cell * freqs / con.c
 
 
