@@ -712,6 +712,69 @@ int64_t rjp_vis_adjoint(rjp_ctx* ctx, const double* d_vis, int32_t n_maps, int32
                         const double* d_w, int32_t nx, int32_t nz, double* d_img,
                         void* d_work, size_t work_bytes, void* stream);
 
+/* ---- K12: Hogbom CLEAN minor cycles on a stack of images -------------------------------------------
+ * The reference deconvolves outside itself: CASA tclean(niter=500) on the simulated measurement set
+ * (classes.py:2770-2808).  This entry point runs the minor cycles of Hogbom's CLEAN on the dirty
+ * images and beams that rjp_vis_adjoint leaves on the device, one fused launch per iteration for the
+ * whole stack and nothing going to the host until the end:
+ *   d_res [n_maps][nx nz]    the dirty images on entry, the residuals on exit (IN PLACE), pixel order
+ *                            p = ix nz + iz
+ *   d_psf [n_psf][px pz]     the beams; n_psf = n_maps, or 1 for one beam shared by all maps; px and
+ *                            pz ODD, the centre ((px-1)/2, (pz-1)/2) is a pixel.  px = 2 nx - 1,
+ *                            pz = 2 nz - 1 is full Hogbom, a smaller beam subtracts only inside its
+ *                            window.  Used as given, nothing is normalised (rjp_vis_adjoint of unit
+ *                            visibilities on an odd grid, over the sum of the weights, is 1 at the
+ *                            centre)
+ *   d_mask [nx nz]           uint8, non-zero = the pixel may hold a component; NULL = all pixels; one
+ *                            mask for all maps
+ *   h_thresh [n_maps]        HOST: each >= 0 and finite;  gain in (0, 1];  n_iter >= 1
+ *   d_cpix, d_cflux [n_maps][n_iter], d_ncomp [n_maps]   the components, in the order found
+ *   d_model [n_maps][nx nz]  (optional) ADDED to, not overwritten: zero it first
+ *   d_peak [n_maps]          (optional) the final masked max |R|, 0 when no pixel qualifies
+ * Iteration t of map m: among the pixels that are unmasked and hold a finite R[p], p* is the one with
+ * the largest |R[p]|, the lowest p on a tie.  With no such pixel, or |R[p*]| <= h_thresh[m], the map
+ * is finished and nothing of it changes any more.  Otherwise f = gain R[p*]; (p*, f) goes to slot t
+ * of the map's row of d_cpix / d_cflux, d_model[m][p*] += f, and
+ *   R[q] = fma(-f, B[q - p* + centre], R[q])   for every q whose beam index lies inside the beam
+ * (one rounding per update).  d_ncomp[m] is the number of components; slots at and beyond it are not
+ * written.  A non-finite pixel of R is never picked and is left as it is.  A second call on the
+ * residuals (same model) continues the same clean.  Fixed reduction and update order, no atomics: a
+ * repeated call on the same input gives the same bits in every output.
+ * The workspace holds the per-tile partial maxima (tiles of 1024 consecutive pixels), double
+ * buffered: 2 x 12 bytes per map and tile, rounded up to 16.  1 + n_iter (+ 1 with d_peak) launches
+ * are enqueued back to back without a host synchronisation.
+ * RETURNS, like rjp_vis_adjoint, the number of workgroups of one iteration's launch, > 0 --
+ * n_maps x ceil(nx nz / 1024) -- or a negative RJP_ERR_*.  Everything is validated before anything
+ * is enqueued, and no output or workspace byte is touched on a refusal: RJP_ERR_ARG for a NULL ctx,
+ * d_res, d_psf, h_thresh, d_cpix, d_cflux or d_ncomp; n_maps, nx, nz, px or pz < 1; an even px or
+ * pz; an n_psf that is neither 1 nor n_maps; nx nz > 2^31 - 1; a gain outside (0, 1]; n_iter < 1; a
+ * negative or non-finite threshold; more than 2^31 - 1 workgroups.  RJP_ERR_WORKSPACE for a d_work
+ * smaller than the workspace query (0 from it = a bad argument). */
+size_t rjp_clean_workspace(int32_t n_maps, int32_t nx, int32_t nz);
+int64_t rjp_clean(rjp_ctx* ctx, double* d_res, int32_t n_maps, int32_t nx, int32_t nz,
+                  const double* d_psf, int32_t n_psf, int32_t px, int32_t pz,
+                  const uint8_t* d_mask, const double* h_thresh, double gain, int32_t n_iter,
+                  int32_t* d_cpix, double* d_cflux, int32_t* d_ncomp, double* d_model,
+                  double* d_peak, void* d_work, size_t work_bytes, void* stream);
+
+/* ---- K13: clean components convolved with the clean beam, plus the residual ------------------------
+ *   out[m][q] = add[m][q] + sum_{c < ncomp[m]} f_c exp(-(A dx^2 + 2 B dx dz + C dz^2))
+ * (dx, dz) the offset of pixel q from component c in cells; (A, B, C) = h_beam[m] in cells^-2 (HOST,
+ * [n_maps][3]), a positive definite form: A > 0, C > 0, A C > B^2.  d_cpix / d_cflux / d_ncomp as
+ * rjp_clean writes them, rows comp_stride apart (d_ncomp[m] is clamped into [0, comp_stride]);
+ * d_add [n_maps][nx nz] the residuals, or NULL; d_out [n_maps][nx nz].  The component fluxes are in
+ * Jy when the dirty beam peaks at 1, so the result is Jy per clean beam with no further scale.
+ * The sum runs in list order (one fma per term, exp at < 1e-14 relative); a term whose exponent lies
+ * below -700 adds an exact zero; the residual is added last.  The same bits on every call.
+ * RETURNS the number of workgroups enqueued, > 0 -- n_maps x ceil(nx nz / 256) -- or a negative
+ * RJP_ERR_*; nothing is enqueued or touched on a refusal: RJP_ERR_ARG for a NULL ctx, d_cpix, d_cflux,
+ * d_ncomp, h_beam or d_out; n_maps, comp_stride, nx or nz < 1; nx nz > 2^31 - 1; a beam that is not
+ * finite and positive definite; more than 2^31 - 1 workgroups. */
+int64_t rjp_restore(rjp_ctx* ctx, const int32_t* d_cpix, const double* d_cflux,
+                    const int32_t* d_ncomp, int32_t n_maps, int32_t comp_stride,
+                    const double* h_beam, const double* d_add, int32_t nx, int32_t nz,
+                    double* d_out, void* stream);
+
 /* ---- K4: geometry -> fields on the device --------------------------------------------
  * Replaces the lazily cached grids of JetModel (fill_factor/areas classes.py:657-669,
  * 763-764; grid_rwp 521-525; rreff 549-555; _nd 877-897; ion_fraction 915-934;

@@ -149,6 +149,12 @@ SIGNATURES = {
     "rjp_vis_adjoint_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "rjp_vis_adjoint": (C.c_int64, [_P, _P, C.c_int32, C.c_int32, _DP, _DP, _P, _P, _P, C.c_int32,
                                     C.c_int32, _P, _P, C.c_size_t, _P]),
+    "rjp_clean_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "rjp_clean": (C.c_int64, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32,
+                              C.c_int32, _P, _DP, C.c_double, C.c_int32, _P, _P, _P, _P, _P, _P,
+                              C.c_size_t, _P]),
+    "rjp_restore": (C.c_int64, [_P, _P, _P, _P, C.c_int32, C.c_int32, _DP, _P, C.c_int32,
+                                C.c_int32, _P, _P]),
     "rjp_rrl_formal": (C.c_int, [_P, C.POINTER(Fields), C.POINTER(Bursts), C.c_double, C.c_int32,
                                  C.POINTER(Line), _DP, _DP, _DP, _DP, C.c_int32, _P, _P, _P]),
     "rjp_rrl_cells": (C.c_int, [_P, C.POINTER(Fields), C.POINTER(Bursts), C.c_double,

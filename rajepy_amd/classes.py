@@ -124,6 +124,11 @@ def _load_params_file(py_file, checker):
     return params
 
 
+# what `JetModel.clean_image_ff` / `clean_image_rrl` return
+CleanResult = collections.namedtuple(
+    "CleanResult", ["image", "residual", "model", "components", "beam", "peak_residual"])
+
+
 class JetModel:
     """Physical model of an ionised jet + its line-of-sight radiative transfer."""
     _arr_indexing = 'ij'
@@ -1068,9 +1073,10 @@ class JetModel:
                 raise ValueError("dirty image: `cell_as` must be a positive number of arcseconds")
         return ni, nj, float(cell)
 
-    def _dirty_images(self, V, u_d, v_d, freqs, weights, shape, cell_as, mfs):
+    def _dirty_images(self, V, u_d, v_d, freqs, weights, shape, cell_as, mfs, device=False):
         """Dirty images [Jy / beam] of the visibilities `V` (complex device tensor [F, K]) at the
-        baselines (`u_d`, `v_d`) [m] -> host array (F, ni, nj), or (1, ni, nj) with `mfs`.
+        baselines (`u_d`, `v_d`) [m] -> host array (F, ni, nj), or (1, ni, nj) with `mfs`;
+        `device=True`: the same numbers as a device tensor [F or 1, ni * nj] (for `_clean_images`).
         `RTEngine.vis_adjoint` on chunks of channels whose images stay under VIS_STACK_BYTES
         (K10's `_vis_chunk` rule on the imaging grid), divided by the sum of the weights of the
         baselines that are not flagged; nothing but the images leaves the device."""
@@ -1096,15 +1102,19 @@ class JetModel:
             va = (dsv[:, None] * v_d[None, :]).reshape(-1)
             wa = w_d.repeat(F) if w_d is not None else None
             img = eng.vis_adjoint(V.reshape(1, F * K), ni, nj, [1.0], [1.0], ua, va, wa)
-            return (img / (wsum * F)).cpu().numpy().reshape(1, ni, nj)
-        out = np.zeros((F, ni, nj))
+            img = img / (wsum * F)
+            return img if device else img.cpu().numpy().reshape(1, ni, nj)
+        out = [] if device else np.zeros((F, ni, nj))
         step = max(1, self.VIS_STACK_BYTES // (ni * nj * 8))
         for f0 in range(0, F, step):
             img = eng.vis_adjoint(V[f0:f0 + step].contiguous(), ni, nj, su[f0:f0 + step],
                                   sv[f0:f0 + step], u_d, v_d, w_d)
-            out[f0:f0 + step] = (img / wsum).cpu().numpy().reshape(-1, ni, nj)
+            if device:
+                out.append(img / wsum)
+            else:
+                out[f0:f0 + step] = (img / wsum).cpu().numpy().reshape(-1, ni, nj)
             del img
-        return out
+        return torch.cat(out, dim=0) if device else out
 
     def dirty_image_ff(self, u_m, v_m, freq, weights=None, shape=None, cell_as=None, formal=False,
                        mfs=False):
@@ -1154,8 +1164,130 @@ class JetModel:
         return self._dirty_images(torch.view_as_complex(V), u_d, v_d, freqs, weights, shape,
                                   cell_as, mfs)
 
+    # ------------------------------------------------------------------ CLEAN ----
+    BEAM_PATCH = 33          # side of the central patch of the dirty beam that `fit_beam` sees
+
+    def _clean_mask(self, mask, ni, nj):
+        """None, a box (i0, i1, j0, j1) of inclusive pixel corners (as the reference hands
+        tclean a box) or a boolean array (ni, nj) -> None or a bool array (ni, nj)."""
+        if mask is None:
+            return None
+        m = np.asarray(mask)
+        if m.ndim == 1 and m.size == 4:
+            i0, i1, j0, j1 = (int(x) for x in m)
+            if not (0 <= i0 <= i1 < ni and 0 <= j0 <= j1 < nj):
+                raise ValueError("clean: the box (i0, i1, j0, j1) must lie inside the image")
+            out = np.zeros((ni, nj), dtype=bool)
+            out[i0:i1 + 1, j0:j1 + 1] = True
+            return out
+        if m.shape != (ni, nj):
+            raise ValueError("clean: `mask` must be None, a box (i0, i1, j0, j1) or an array of "
+                             "the image's shape (%d, %d)" % (ni, nj))
+        return m != 0
+
+    def _clean_images(self, V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
+                      threshold_jy, mask, beam, psf_shape):
+        """Hogbom CLEAN of the dirty images of `V` (see `clean_image_ff`), in chunks of channels
+        whose dirty images AND beams stay under VIS_STACK_BYTES.  Per chunk, on the device:
+        `_dirty_images` of V and of unit visibilities (the beams, on the `psf_shape` grid),
+        `RTEngine.clean`, `RTEngine.restore`; only the central patch of each beam goes to the
+        host before the end (for `fit_beam`)."""
+        import torch
+        from . import engine as E
+        eng = self.engine
+        ni, nj, cell = self._image_grid(shape, cell_as)
+        pi_, pj = (2 * ni - 1, 2 * nj - 1) if psf_shape is None else (int(psf_shape[0]),
+                                                                      int(psf_shape[1]))
+        if pi_ < 1 or pj < 1 or pi_ % 2 == 0 or pj % 2 == 0:
+            raise ValueError("clean: `psf_shape` must be two odd positive sizes")
+        niter = int(niter)
+        if niter < 1 or not (0. < float(gain) <= 1.) or not (float(threshold_jy) >= 0.):
+            raise ValueError("clean: niter >= 1, 0 < gain <= 1 and threshold_jy >= 0")
+        mk = self._clean_mask(mask, ni, nj)
+        F, K = int(V.shape[0]), int(V.shape[1])
+        n_out = 1 if mfs else F
+        ones = torch.zeros(F, K, 2, dtype=torch.float64, device=eng.device)
+        ones[..., 0] = 1.0
+        ones = torch.view_as_complex(ones)
+        res = CleanResult(image=np.zeros((n_out, ni, nj)), residual=np.zeros((n_out, ni, nj)),
+                          model=np.zeros((n_out, ni, nj)), components=[], beam=[],
+                          peak_residual=np.zeros(n_out))
+        step = F if mfs else max(1, self.VIS_STACK_BYTES // ((ni * nj * 3 + pi_ * pj) * 8))
+        hi, hj = min(self.BEAM_PATCH, pi_) // 2, min(self.BEAM_PATCH, pj) // 2
+        for f0 in range(0, F, step):
+            sl = slice(f0, f0 + step)
+            dirty = self._dirty_images(V[sl], u_d, v_d, freqs[sl], weights, (ni, nj), cell_as,
+                                       mfs, device=True)
+            psf = self._dirty_images(ones[sl], u_d, v_d, freqs[sl], weights, (pi_, pj), cell_as,
+                                     mfs, device=True)
+            M = int(dirty.shape[0])
+            if beam is None:
+                ci, cj = (pi_ - 1) // 2, (pj - 1) // 2
+                patch = psf.reshape(M, pi_, pj)[:, ci - hi:ci + hi + 1, cj - hj:cj + hj + 1]
+                abc = [E.fit_beam(p) for p in patch.cpu().numpy()]
+            else:
+                abc = [E.beam_quadratic(beam[0], beam[1], beam[2], cell)] * M
+            model = torch.zeros_like(dirty)
+            cpix, cflux, ncomp, peak = eng.clean(dirty, ni, nj, psf, pi_, pj, niter, gain,
+                                                 float(threshold_jy), mask=mk, model=model)
+            image = eng.restore(cpix, cflux, ncomp, abc, ni, nj, add=dirty)
+            o = slice(f0, f0 + M)
+            res.image[o] = image.cpu().numpy().reshape(M, ni, nj)
+            res.residual[o] = dirty.cpu().numpy().reshape(M, ni, nj)
+            res.model[o] = model.cpu().numpy().reshape(M, ni, nj)
+            res.peak_residual[o] = peak.cpu().numpy()
+            hp, hf, hn = cpix.cpu().numpy(), cflux.cpu().numpy(), ncomp.cpu().numpy()
+            for m in range(M):
+                n = int(hn[m])
+                res.components.append(np.stack([hp[m, :n] // nj, hp[m, :n] % nj, hf[m, :n]],
+                                               axis=1).astype(np.float64).reshape(n, 3))
+                res.beam.append(E.beam_from_quadratic(*abc[m], cell))
+            del dirty, psf, model, image, cpix, cflux, ncomp, peak
+        return res
+
+    def clean_image_ff(self, u_m, v_m, freq, weights=None, shape=None, cell_as=None, formal=False,
+                       mfs=False, niter=500, gain=0.1, threshold_jy=0.0, mask=None, beam=None,
+                       psf_shape=None):
+        """CLEANed, restored images [Jy / clean beam] of the `flux_ff` maps as an array with the
+        baselines (`u_m`, `v_m`) in metres sees them: `dirty_image_ff` and `dirty_beam` (same
+        arguments, kept on the device), Hogbom's CLEAN of every image with its own beam
+        (`RTEngine.clean`, rjp_clean) and the components convolved with a Gaussian clean beam plus
+        the residual (`RTEngine.restore`, rjp_restore) -- what the reference gets from CASA tclean
+        (classes.py:2770-2808), whose defaults `niter`, `gain`, `threshold_jy` [Jy / beam] are.
+        -> `CleanResult`: `image`, `residual`, `model` (F, ni, nj) -- (1, ni, nj) with `mfs` --
+        `components` (per map an array [n, 3] of (ix, iz, flux [Jy]) in the order found), `beam`
+        (per map (bmaj_as, bmin_as, bpa_deg), convention: `engine.beam_quadratic`) and
+        `peak_residual` (per map, the masked max |residual|).
+        `mask`: None, a box (i0, i1, j0, j1) of inclusive pixel corners or a boolean (ni, nj)
+        array: where components may lie.  `beam`: None = fitted to the main lobe of every map's
+        dirty beam (`engine.fit_beam`), or (bmaj_as, bmin_as, bpa_deg).  `psf_shape`: the (odd)
+        grid the dirty beam is computed on, None = (2 ni - 1, 2 nj - 1), full Hogbom; smaller =
+        the subtraction is windowed.  Everything else as `dirty_image_ff`.  Calling rank only."""
+        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
+        eng = self.engine
+        u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
+        maps = self._ff_products(freqs, flux=True, device=True, formal=formal)
+        su, sv = self._vis_scales(freqs)
+        V = eng.vis(maps.reshape(len(freqs), -1), self.nx, self.nz, su, sv, u_d, v_d)
+        return self._clean_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
+                                  threshold_jy, mask, beam, psf_shape)
+
+    def clean_image_rrl(self, rrl, u_m, v_m, freq, weights=None, shape=None, cell_as=None,
+                        contsub=True, formal=False, mfs=False, niter=500, gain=0.1,
+                        threshold_jy=0.0, mask=None, beam=None, psf_shape=None):
+        """CLEANed, restored images of the `flux_rrl` maps (same arguments) -> `CleanResult`; see
+        `clean_image_ff`."""
+        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
+        eng = self.engine
+        u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
+        maps = self._rrl_flux(rrl, freqs, True, contsub, formal=formal, device=True)
+        su, sv = self._vis_scales(freqs)
+        V = eng.vis(maps.reshape(len(freqs), -1), self.nx, self.nz, su, sv, u_d, v_d)
+        return self._clean_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
+                                  threshold_jy, mask, beam, psf_shape)
+
     # ------------------------------------------------------------------ products ----
-    FORMAL_HISTORY = "Formal solution along the line of sight, observer at iy = 0"
+    FORMAL_HISTORY ="Formal solution along the line of sight, observer at iy = 0"
 
     def _save_cube(self, data, savefits, image_type, freq, formal=False):
         dev, self._dev_product = getattr(self, "_dev_product", None), None

@@ -141,4 +141,49 @@ inline int check_vis_adjoint(const double* d_vis, int n_maps, int n_vis, const d
   return RJP_OK;
 }
 
+// What rjp_clean takes, in the order it refuses: NULL pointers, sizes below 1, an even beam, the
+// beam count, the image size, the gain, n_iter, the thresholds.  (`d_mask`, `d_model`, `d_peak`
+// may be NULL; the grid and the workspace are checked where the tiling lives.)
+inline int check_clean(const double* d_res, int n_maps, int nx, int nz, const double* d_psf,
+                       int n_psf, int px, int pz, const double* h_thresh, double gain, int n_iter,
+                       const int32_t* d_cpix, const double* d_cflux, const int32_t* d_ncomp,
+                       std::string& err) {
+  if (!d_res || !d_psf || !h_thresh || !d_cpix || !d_cflux || !d_ncomp)
+    return refuse(err, "rjp_clean: NULL images, beams, thresholds or component outputs");
+  if (n_maps < 1 || nx < 1 || nz < 1 || px < 1 || pz < 1)
+    return refuse(err, "rjp_clean: n_maps, nx, nz, px and pz must be positive");
+  if (px % 2 == 0 || pz % 2 == 0)
+    return refuse(err, "rjp_clean: px and pz must be odd (the beam's centre is a pixel)");
+  if (n_psf != 1 && n_psf != n_maps)
+    return refuse(err, "rjp_clean: n_psf must be 1 or n_maps");
+  if ((int64_t)nx * nz > (int64_t)INT32_MAX)
+    return refuse(err, "rjp_clean: nx * nz exceeds 2^31 - 1");
+  if (!(gain > 0.0 && gain <= 1.0)) return refuse(err, "rjp_clean: gain must lie in (0, 1]");
+  if (n_iter < 1) return refuse(err, "rjp_clean: n_iter < 1");
+  for (int m = 0; m < n_maps; ++m)
+    if (!(h_thresh[m] >= 0.0) || !std::isfinite(h_thresh[m]))
+      return refuse(err, "rjp_clean: negative or non-finite threshold");
+  return RJP_OK;
+}
+
+// What rjp_restore takes, in the order it refuses: NULL pointers, sizes below 1, the image size, a
+// beam whose quadratic form is not positive definite (or not finite).  (`d_add` may be NULL.)
+inline int check_restore(const int32_t* d_cpix, const double* d_cflux, const int32_t* d_ncomp,
+                         int n_maps, int comp_stride, const double* h_beam, int nx, int nz,
+                         const double* d_out, std::string& err) {
+  if (!d_cpix || !d_cflux || !d_ncomp || !h_beam || !d_out)
+    return refuse(err, "rjp_restore: NULL components, beams or output");
+  if (n_maps < 1 || comp_stride < 1 || nx < 1 || nz < 1)
+    return refuse(err, "rjp_restore: n_maps, comp_stride, nx and nz must be positive");
+  if ((int64_t)nx * nz > (int64_t)INT32_MAX)
+    return refuse(err, "rjp_restore: nx * nz exceeds 2^31 - 1");
+  for (int m = 0; m < n_maps; ++m) {
+    const double A = h_beam[3 * m], B = h_beam[3 * m + 1], C = h_beam[3 * m + 2];
+    if (!std::isfinite(A) || !std::isfinite(B) || !std::isfinite(C) || !(A > 0.0) || !(C > 0.0) ||
+        !(A * C > B * B))
+      return refuse(err, "rjp_restore: the beam (A, B, C) must be positive definite");
+  }
+  return RJP_OK;
+}
+
 }  // namespace rjp_args

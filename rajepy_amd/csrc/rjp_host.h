@@ -1,6 +1,6 @@
 // Host-side interface between the translation units of librjprt (rjprt.hip = the C-ABI,
 // ff_scan.hip, ff_scan_inst.hip x 5, fields.hip, rrl_scan.hip, rrl_formal.hip, ff_grad.hip,
-// ff_formal_sweep.hip, ff_formal_grad.hip, vis.hip, vis_adjoint.hip, ...): launch
+// ff_formal_sweep.hip, ff_formal_grad.hip, vis.hip, vis_adjoint.hip, clean.hip, ...): launch
 // wrappers and the small structs they exchange.  Nothing here is exported; the library's surface is include/rjprt.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -236,6 +236,26 @@ size_t vis_adjoint_workspace_bytes(int n_maps, int nx, int nz, int n_vis);
 hipError_t vis_adjoint_launch(const double* vis, int n_maps, int n_vis, const double* d_su,
                               const double* d_sv, const double* u, const double* v, const double* w,
                               int nx, int nz, double* img, double* part, hipStream_t st);
+
+// ---- clean.hip: Hogbom CLEAN on a stack of images (K12) and the restored image (K13) -------------
+struct CleanTiling {
+  int64_t tiles;                // of 1024 consecutive pixels, per map
+  int64_t workgroups;           // n_maps x tiles: the grid of every iteration's launch
+};
+CleanTiling clean_tiling(int n_maps, int nx, int nz);
+// >= 16; 0: does not fit a size_t
+size_t clean_workspace_bytes(int n_maps, int nx, int nz);
+// d_thresh[n_maps]: device copy of the thresholds; `mask`, `model`, `peak` may be nullptr;
+// 1 + n_iter (+ 1 with `peak`) launches, no host synchronisation
+hipError_t clean_launch(double* res, int n_maps, int nx, int nz, const double* psf, int n_psf,
+                        int px, int pz, const uint8_t* mask, const double* d_thresh, double gain,
+                        int n_iter, int32_t* cpix, double* cflux, int32_t* ncomp, double* model,
+                        double* peak, void* work, hipStream_t st);
+int64_t restore_workgroups(int n_maps, int nx, int nz);
+// d_beam[n_maps][3]: device copy of the quadratic forms; `add` may be nullptr
+hipError_t restore_launch(const int32_t* cpix, const double* cflux, const int32_t* ncomp,
+                          int n_maps, int comp_stride, const double* d_beam, const double* add,
+                          int nx, int nz, double* out, hipStream_t st);
 
 // ---- ff_scan_inst.hip: one slice of the K1 kernel family per translation unit -------------
 #define RJP_SCAN_SLICE_ARGS                                                                  \

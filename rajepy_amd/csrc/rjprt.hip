@@ -1062,6 +1062,60 @@ int64_t rjp_vis_adjoint(rjp_ctx* ctx, const double* d_vis, int32_t n_maps, int32
   return r ? r : t.workgroups;
 }
 
+size_t rjp_clean_workspace(int32_t n_maps, int32_t nx, int32_t nz) {
+  if (n_maps <= 0 || nx <= 0 || nz <= 0) return 0;
+  return rjp::clean_workspace_bytes(n_maps, nx, nz);
+}
+
+int64_t rjp_clean(rjp_ctx* ctx, double* d_res, int32_t n_maps, int32_t nx, int32_t nz,
+                  const double* d_psf, int32_t n_psf, int32_t px, int32_t pz,
+                  const uint8_t* d_mask, const double* h_thresh, double gain, int32_t n_iter,
+                  int32_t* d_cpix, double* d_cflux, int32_t* d_ncomp, double* d_model,
+                  double* d_peak, void* d_work, size_t work_bytes, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_clean(d_res, n_maps, nx, nz, d_psf, n_psf, px, pz, h_thresh, gain,
+                                     n_iter, d_cpix, d_cflux, d_ncomp, m);
+      }))
+    return r;
+  const rjp::CleanTiling t = rjp::clean_tiling(n_maps, nx, nz);
+  if (t.workgroups > (int64_t)INT32_MAX)
+    return fail(ctx, RJP_ERR_ARG, "rjp_clean: more than 2^31 - 1 workgroups");
+  const size_t need = rjp::clean_workspace_bytes(n_maps, nx, nz);
+  if (!d_work || work_bytes < need)
+    return fail(ctx, RJP_ERR_WORKSPACE, "rjp_clean: workspace smaller than rjp_clean_workspace()");
+  hipStream_t st = (hipStream_t)stream;
+  const int r = staged(ctx, st, "clean_launch", nullptr, {{h_thresh, (size_t)n_maps}},
+                       [&](double* const* d, const double*) {
+                         return rjp::clean_launch(d_res, n_maps, nx, nz, d_psf, n_psf, px, pz,
+                                                  d_mask, d[0], gain, n_iter, d_cpix, d_cflux,
+                                                  d_ncomp, d_model, d_peak, d_work, st);
+                       });
+  return r ? r : t.workgroups;
+}
+
+int64_t rjp_restore(rjp_ctx* ctx, const int32_t* d_cpix, const double* d_cflux,
+                    const int32_t* d_ncomp, int32_t n_maps, int32_t comp_stride,
+                    const double* h_beam, const double* d_add, int32_t nx, int32_t nz,
+                    double* d_out, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_restore(d_cpix, d_cflux, d_ncomp, n_maps, comp_stride, h_beam, nx,
+                                       nz, d_out, m);
+      }))
+    return r;
+  const int64_t wgs = rjp::restore_workgroups(n_maps, nx, nz);
+  if (wgs > (int64_t)INT32_MAX)
+    return fail(ctx, RJP_ERR_ARG, "rjp_restore: more than 2^31 - 1 workgroups");
+  hipStream_t st = (hipStream_t)stream;
+  const int r = staged(ctx, st, "restore_launch", nullptr, {{h_beam, 3 * (size_t)n_maps}},
+                       [&](double* const* d, const double*) {
+                         return rjp::restore_launch(d_cpix, d_cflux, d_ncomp, n_maps, comp_stride,
+                                                    d[0], d_add, nx, nz, d_out, st);
+                       });
+  return r ? r : wgs;
+}
+
 int rjp_rrl_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
                    double time_s, int32_t gff_mode, const rjp_line* line, const double* h_nu,
                    const double* h_ctau, const double* h_csrc, const double* h_hnu_k,

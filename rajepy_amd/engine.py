@@ -1122,6 +1122,104 @@ class RTEngine:
         self.last_vis_adjoint_tiles = int(tiles)
         return out
 
+    # -- K12 / K13 -----------------------------------------------------------------------------
+    def _stack_f64(self, who, name, t, n):
+        """`t` is a contiguous float64 tensor of `n` values on this engine's device."""
+        torch = _torch()
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and
+                t.device == self.device and t.is_contiguous() and t.numel() == n):
+            raise ValueError("%s: `%s` must be a contiguous float64 tensor of %d values on %s"
+                             % (who, name, n, self.device))
+
+    def clean(self, res, nx, nz, psf, px, pz, n_iter, gain, thresh, mask=None, model=None):
+        """Hogbom CLEAN minor cycles on a stack of dirty images (rjp_clean), one fused launch per
+        iteration for the whole stack, nothing going to the host -> (cpix[M, n_iter] int32,
+        cflux[M, n_iter] float64, ncomp[M] int32, peak[M] float64) device tensors; slots at and
+        beyond ncomp[m] are not written.  `res`: float64 device tensor of M * nx * nz values, the
+        dirty images on entry and the residuals on exit (IN PLACE).  `psf`: M beams or one shared
+        beam of px * pz values, px and pz odd (2 nx - 1, 2 nz - 1: full Hogbom; smaller: the
+        subtraction is windowed), used as given.  `thresh`: one number or one per map [the unit of
+        `res`]; `mask`: None or nx * nz values, non-zero = may hold a component; `model`: a
+        float64 tensor like `res` that every component's flux is ADDED to.  Per iteration and map:
+        the unmasked finite pixel of largest |R| (lowest index on a tie); stop at |R| <= thresh;
+        else f = gain R, R -= f B shifted to the pixel.  A second call on `res` continues the
+        clean.  The same bits on every call.  The number of workgroups per iteration is kept in
+        `last_clean_tiles`."""
+        torch = _torch()
+        nx, nz, px, pz, n_iter = int(nx), int(nz), int(px), int(pz), int(n_iter)
+        if nx < 1 or nz < 1 or px < 1 or pz < 1 or n_iter < 1:
+            raise ValueError("clean: nx, nz, px, pz and n_iter must be positive")
+        if not (isinstance(res, torch.Tensor) and res.numel() >= nx * nz and
+                res.numel() % (nx * nz) == 0):
+            raise ValueError("clean: `res` must hold a whole number (>= 1) of nx * nz images")
+        M = res.numel() // (nx * nz)
+        self._stack_f64("clean", "res", res, M * nx * nz)
+        if not (isinstance(psf, torch.Tensor) and psf.numel() in (px * pz, M * px * pz)):
+            raise ValueError("clean: `psf` must hold one beam or one per map of px * pz values")
+        n_psf = psf.numel() // (px * pz)
+        self._stack_f64("clean", "psf", psf, n_psf * px * pz)
+        if model is not None:
+            self._stack_f64("clean", "model", model, M * nx * nz)
+        dmask = None
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor):
+                mask = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0))
+            dmask = (mask != 0).to(device=self.device, dtype=torch.uint8).reshape(-1).contiguous()
+            if dmask.numel() != nx * nz:
+                raise ValueError("clean: `mask` must have nx * nz entries")
+        th = np.asarray(thresh, dtype=np.float64).reshape(-1)
+        if th.size not in (1, M):
+            raise ValueError("clean: `thresh` must be one number or one per map (%d)" % M)
+        th = np.ascontiguousarray(np.broadcast_to(th, (M,)))
+        cpix = torch.empty(M, n_iter, dtype=torch.int32, device=self.device)
+        cflux = self._f64(M, n_iter)
+        ncomp = torch.empty(M, dtype=torch.int32, device=self.device)
+        peak = self._f64(M)
+        work = self._workspace(max(1, self.lib.rjp_clean_workspace(M, nx, nz)))
+        tiles = self.lib.rjp_clean(self.ctx, res.data_ptr(), M, nx, nz, psf.data_ptr(), n_psf, px,
+                                   pz, _ptr(dmask), _lib.dbl_array(th), float(gain), n_iter,
+                                   cpix.data_ptr(), cflux.data_ptr(), ncomp.data_ptr(),
+                                   _ptr(model), peak.data_ptr(), work.data_ptr(), work.numel(),
+                                   self._stream())
+        if tiles <= 0:
+            self._check(int(tiles), self.ctx, "rjp_clean")
+        self.last_clean_tiles = int(tiles)
+        return cpix, cflux, ncomp, peak
+
+    def restore(self, cpix, cflux, ncomp, beam_abc, nx, nz, add=None):
+        """Clean components convolved with the clean beam, plus `add` (rjp_restore):
+        out[m, q] = add[m, q] + sum_{c < ncomp[m]} cflux[m, c] exp(-(A dx^2 + 2 B dx dz + C dz^2))
+        -> float64 device tensor [M, nx * nz].  `cpix`, `cflux` [M, stride], `ncomp` [M]: what
+        `clean` returns; `beam_abc`: (A, B, C) in cells^-2, one triple or one per map
+        (`beam_quadratic`); `add`: the residuals [M, nx * nz] or None.  Sum in list order, the
+        same bits on every call."""
+        torch = _torch()
+        nx, nz = int(nx), int(nz)
+        if nx < 1 or nz < 1:
+            raise ValueError("restore: nx and nz must be positive")
+        ok = lambda t, dt: (isinstance(t, torch.Tensor) and t.dtype == dt and
+                            t.device == self.device and t.is_contiguous())
+        if not (ok(cpix, torch.int32) and ok(cflux, torch.float64) and ok(ncomp, torch.int32) and
+                cpix.dim() == 2 and cpix.shape == cflux.shape and cpix.shape[1] >= 1 and
+                ncomp.numel() == cpix.shape[0] >= 1):
+            raise ValueError("restore: cpix [M, S] int32, cflux [M, S] float64 and ncomp [M] int32 "
+                             "must be contiguous tensors on %s" % self.device)
+        M, S = int(cpix.shape[0]), int(cpix.shape[1])
+        abc = np.asarray(beam_abc, dtype=np.float64).reshape(-1, 3)
+        if abc.shape[0] == 1:
+            abc = np.repeat(abc, M, axis=0)
+        if abc.shape[0] != M:
+            raise ValueError("restore: `beam_abc` must be one (A, B, C) or one per map (%d)" % M)
+        if add is not None:
+            self._stack_f64("restore", "add", add, M * nx * nz)
+        out = self._f64(M, nx * nz)
+        wgs = self.lib.rjp_restore(self.ctx, cpix.data_ptr(), cflux.data_ptr(), ncomp.data_ptr(),
+                                   M, S, _lib.dbl_array(abc), _ptr(add), nx, nz, out.data_ptr(),
+                                   self._stream())
+        if wgs <= 0:
+            self._check(int(wgs), self.ctx, "rjp_restore")
+        return out
+
     def rrl_cells(self, fields, bursts, time_s, line, nus):
         """collapse=False: per-cell RRL optical depths -> device tensor [F, N]."""
         F = len(nus)
@@ -1213,6 +1311,72 @@ def image_scales(freqs, cell_rad):
     freqs = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
     cell = float(cell_rad)
     return -cell * freqs / con.c, cell * freqs / con.c
+
+
+_FOUR_LN2 = 4. * np.log(2.)
+
+
+def beam_quadratic(bmaj_as, bmin_as, bpa_deg, cell_rad):
+    """(A, B, C) [cells^-2] of `RTEngine.restore` / rjp_restore for an elliptical Gaussian clean
+    beam exp(-(A dx^2 + 2 B dx dz + C dz^2)) -- the one place that holds the convention:
+      * `bmaj_as`, `bmin_as` [arcsec] are FWHM: along an axis of FWHM w the beam is
+        exp(-4 ln2 s^2 / w^2);
+      * `bpa_deg` is the position angle of the major axis, from North through East.  North is +z
+        and East is DECREASING ix (RA decreases with ix: `vis_scales`), so the major axis points
+        along (dx, dz) = (-sin bpa, cos bpa): with bpa = 0 it lies along z;
+      * (dx, dz) are in cells of `cell_rad` radians."""
+    cell_as = np.degrees(float(cell_rad)) * 3600.
+    ka = _FOUR_LN2 / (float(bmaj_as) / cell_as) ** 2
+    kb = _FOUR_LN2 / (float(bmin_as) / cell_as) ** 2
+    s, c = np.sin(np.radians(float(bpa_deg))), np.cos(np.radians(float(bpa_deg)))
+    return (float(ka * s * s + kb * c * c), float((kb - ka) * s * c),
+            float(ka * c * c + kb * s * s))
+
+
+def beam_from_quadratic(A, B, C, cell_rad):
+    """The inverse of `beam_quadratic`: (bmaj_as, bmin_as, bpa_deg) of a positive definite
+    (A, B, C) [cells^-2], bpa in (-90, 90]."""
+    lam, vec = np.linalg.eigh(np.array([[A, B], [B, C]], dtype=np.float64))
+    if not lam[0] > 0.:
+        raise ValueError("beam: (A, B, C) is not positive definite")
+    cell_as = np.degrees(float(cell_rad)) * 3600.
+    ex, ez = vec[:, 0]                             # the major axis: the smaller eigenvalue
+    bpa = np.degrees(np.arctan2(-ex, ez))
+    bpa = bpa - 180. if bpa > 90. else bpa + 180. if bpa <= -90. else bpa
+    return (float(np.sqrt(_FOUR_LN2 / lam[0]) * cell_as),
+            float(np.sqrt(_FOUR_LN2 / lam[1]) * cell_as), float(bpa))
+
+
+def fit_beam(patch):
+    """(A, B, C) [cells^-2] of the Gaussian that fits the main lobe of a dirty beam: `patch` is a
+    2-D array [odd, odd] around the beam's centre pixel; a linear least-squares fit of
+    -ln(patch / centre) = A dx^2 + 2 B dx dz + C dz^2 over the pixels >= half the centre value
+    that are connected to the centre (4-neighbours), as tclean fits its restoring beam."""
+    b = np.asarray(patch, dtype=np.float64)
+    if b.ndim != 2 or b.shape[0] % 2 == 0 or b.shape[1] % 2 == 0:
+        raise ValueError("fit_beam: `patch` must be 2-D with odd sizes")
+    cx, cz = (b.shape[0] - 1) // 2, (b.shape[1] - 1) // 2
+    if not (np.isfinite(b[cx, cz]) and b[cx, cz] > 0.):
+        raise ValueError("fit_beam: the centre of the beam must be positive")
+    b = b / b[cx, cz]
+    lobe = np.zeros(b.shape, dtype=bool)
+    todo = [(cx, cz)]
+    while todo:
+        i, j = todo.pop()
+        if 0 <= i < b.shape[0] and 0 <= j < b.shape[1] and not lobe[i, j] and b[i, j] >= 0.5:
+            lobe[i, j] = True
+            todo += [(i + 1, j), (i - 1, j), (i, j + 1), (i, j - 1)]
+    ii, jj = np.nonzero(lobe)
+    dx, dz = (ii - cx).astype(np.float64), (jj - cz).astype(np.float64)
+    design = np.stack([dx * dx, 2. * dx * dz, dz * dz], axis=1)
+    if np.linalg.matrix_rank(design) < 3:
+        raise ValueError("fit_beam: the main lobe covers too few pixels (the beam is not resolved "
+                         "by the cell)")
+    sol = np.linalg.lstsq(design, -np.log(b[ii, jj]), rcond=None)[0]
+    A, B, C = (float(x) for x in sol)
+    if not (A > 0. and C > 0. and A * C > B * B):
+        raise ValueError("fit_beam: the fitted form is not positive definite")
+    return A, B, C
 
 
 def ff_channel_coeffs(freqs, csize_au, dist_pc, gff_mode, gff_values=None):
