@@ -775,6 +775,60 @@ int64_t rjp_restore(rjp_ctx* ctx, const int32_t* d_cpix, const double* d_cflux,
                     const double* h_beam, const double* d_add, int32_t nx, int32_t nz,
                     double* d_out, void* stream);
 
+/* ---- K14: Gaussian fits of a stack of images (imfit) ----------------------------------------------
+ * The reference measures its synthetic images outside itself: CASA imfit on the restored image
+ * (classes.py:2790-2840).  This entry point fits one elliptical Gaussian per map by
+ * Levenberg-Marquardt, one fused launch per iteration for the whole stack and nothing going to the
+ * host until the end:
+ *   G(ix, iz) = S exp(-(A dx^2 + 2 B dx dz + C dz^2)),  dx = ix - x0, dz = iz - z0,
+ * theta = (S, x0, z0, A, B, C): peak [the image's unit, may be negative], centre [pixels], and the
+ * quadratic form in cells^-2 (A > 0, C > 0, A C > B^2), no offset.  exp to < 1e-14 relative, an exact
+ * 0 below an exponent of -700.
+ *   d_img [n_maps][nx nz]    the images (READ ONLY), pixel order p = ix nz + iz
+ *   h_box [4]                HOST: (i0, i1, j0, j1), inclusive corners of the fitting box
+ *   d_mask [nx nz]           uint8, non-zero = the pixel counts; NULL = all; one mask for all maps
+ *   d_theta [n_maps][6]      the start on entry, the fit on exit (IN PLACE)
+ *   lambda0, xtol            finite and > 0;  n_iter >= 1
+ *   d_chi2 [n_maps], d_cov [n_maps][21], d_npix, d_niter, d_status [n_maps] (int32)
+ *   d_trace [n_maps][n_iter][9]   (optional) per iteration (chi^2 of the trial, the lambda that
+ *                            proposed it, accepted 0 / 1, the trial's six parameters); rows at and
+ *                            beyond d_niter[m] are not written
+ * A pixel counts when it lies in the box, is non-zero in the mask and finite in the image.  With
+ * r = I - G and J = dG / dtheta over the counting pixels: chi^2 = sum r^2, N = J^T J, g = J^T r.
+ * Iteration t = 1, 2, ... evaluates one trial (the first: the start, with chi^2_cur = +inf) and
+ * decides, in this order:
+ *   1. accept iff the trial is positive definite, its chi^2 is finite and < chi^2_cur; on accept
+ *      theta_cur, chi^2_cur, N, g become the trial's and lambda <- max(lambda / 10, 1e-12) (accepting
+ *      the start leaves lambda0); on reject lambda <- 10 lambda;
+ *   2. chi^2_cur = 0 -> status 1.  Else delta from (N + lambda diag N) delta = g by a 6 x 6
+ *      Cholesky; a pivot that is not > 0 counts as a reject (lambda <- 10 lambda, again);
+ *      lambda > 1e12 -> status 2 (stalled);
+ *   3. max_i |delta_i| / s_i <= xtol, s = (max(|S|, 1e-300), 1, 1, A + C, A + C, A + C) -> status 1 (converged;
+ *      tested on every proposed step); n_iter trials done -> status 0; else the next trial is
+ *      theta_cur + delta.
+ * status 3 (degenerate): a start that is not finite and positive definite, a first chi^2 that is
+ * not finite, or fewer than 6 counting pixels; d_status[m] = 3 and NOTHING else of that map is
+ * written.  Otherwise d_theta / d_chi2 are theta_cur / chi^2_cur, d_cov the packed upper triangle
+ * (row by row) of N at theta_cur, NOT inverted, d_npix the counting pixels, d_niter the trials
+ * evaluated.  Calling again with the returned d_theta continues the fit (lambda starts over).
+ * Tiles of 1024 consecutive pixels of the box in the box's row-major order; every sum in a fixed
+ * order, no atomics: a repeated call gives the same bits in every output.  The workspace holds the
+ * 29 partial sums per tile and 48 doubles of state per map, both double buffered.  n_iter + 1
+ * launches are enqueued back to back without a host synchronisation.
+ * RETURNS, like rjp_clean, the number of workgroups of one iteration's launch, > 0 --
+ * n_maps x ceil(box pixels / 1024) -- or a negative RJP_ERR_*.  Everything is validated before
+ * anything is enqueued, and no output or workspace byte is touched on a refusal: RJP_ERR_ARG for a
+ * NULL ctx, d_img, h_box, d_theta, d_chi2, d_cov, d_npix, d_niter or d_status; n_maps, nx or nz < 1;
+ * nx nz > 2^31 - 1; a box outside the image or with i1 < i0 or j1 < j0; lambda0 or xtol not finite
+ * and positive; n_iter < 1; more than 2^31 - 1 workgroups.  RJP_ERR_WORKSPACE for a d_work smaller
+ * than the workspace query (0 from it = a bad argument). */
+size_t rjp_gaussfit_workspace(int32_t n_maps, int32_t box_pixels);
+int64_t rjp_gaussfit(rjp_ctx* ctx, const double* d_img, int32_t n_maps, int32_t nx, int32_t nz,
+                     const int32_t* h_box, const uint8_t* d_mask, double* d_theta, double lambda0,
+                     double xtol, int32_t n_iter, double* d_chi2, double* d_cov, int32_t* d_npix,
+                     int32_t* d_niter, int32_t* d_status, double* d_trace, void* d_work,
+                     size_t work_bytes, void* stream);
+
 /* ---- K4: geometry -> fields on the device --------------------------------------------
  * Replaces the lazily cached grids of JetModel (fill_factor/areas classes.py:657-669,
  * 763-764; grid_rwp 521-525; rreff 549-555; _nd 877-897; ion_fraction 915-934;

@@ -125,8 +125,25 @@ def _load_params_file(py_file, checker):
 
 
 # what `JetModel.clean_image_ff` / `clean_image_rrl` return
-CleanResult = collections.namedtuple(
-    "CleanResult", ["image", "residual", "model", "components", "beam", "peak_residual"])
+class CleanResult(collections.namedtuple(
+        "CleanResult", ["image", "residual", "model", "components", "beam", "peak_residual"])):
+    """The six products of a CLEAN as a tuple, and `imfit`: None, or with the `imfit` keyword one
+    dict per map (`engine.gauss_results`) -- an attribute beside the tuple, so that code which
+    unpacks the six products keeps working.  `_replace` carries `imfit` over (and takes it as a
+    keyword); `_make`, which builds from the six values alone, leaves it None."""
+
+    def __new__(cls, *args, imfit=None, **kw):
+        self = super().__new__(cls, *args, **kw)
+        self.imfit = imfit
+        return self
+
+    imfit = None
+
+    def _replace(self, **kw):
+        imfit = kw.pop("imfit", self.imfit)
+        out = super()._replace(**kw)
+        out.imfit = imfit
+        return out
 
 
 class JetModel:
@@ -1186,7 +1203,7 @@ class JetModel:
         return m != 0
 
     def _clean_images(self, V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
-                      threshold_jy, mask, beam, psf_shape):
+                      threshold_jy, mask, beam, psf_shape, imfit=None):
         """Hogbom CLEAN of the dirty images of `V` (see `clean_image_ff`), in chunks of channels
         whose dirty images AND beams stay under VIS_STACK_BYTES.  Per chunk, on the device:
         `_dirty_images` of V and of unit visibilities (the beams, on the `psf_shape` grid),
@@ -1209,9 +1226,10 @@ class JetModel:
         ones = torch.zeros(F, K, 2, dtype=torch.float64, device=eng.device)
         ones[..., 0] = 1.0
         ones = torch.view_as_complex(ones)
+        fit_opts = self._imfit_options(imfit, mask, ni, nj)
         res = CleanResult(image=np.zeros((n_out, ni, nj)), residual=np.zeros((n_out, ni, nj)),
                           model=np.zeros((n_out, ni, nj)), components=[], beam=[],
-                          peak_residual=np.zeros(n_out))
+                          peak_residual=np.zeros(n_out), imfit=None if fit_opts is None else [])
         step = F if mfs else max(1, self.VIS_STACK_BYTES // ((ni * nj * 3 + pi_ * pj) * 8))
         hi, hj = min(self.BEAM_PATCH, pi_) // 2, min(self.BEAM_PATCH, pj) // 2
         for f0 in range(0, F, step):
@@ -1232,6 +1250,8 @@ class JetModel:
                                                  float(threshold_jy), mask=mk, model=model)
             image = eng.restore(cpix, cflux, ncomp, abc, ni, nj, add=dirty)
             o = slice(f0, f0 + M)
+            if fit_opts is not None:
+                res.imfit.extend(self._imfit_images(image, ni, nj, abc, cell, fit_opts, o))
             res.image[o] = image.cpu().numpy().reshape(M, ni, nj)
             res.residual[o] = dirty.cpu().numpy().reshape(M, ni, nj)
             res.model[o] = model.cpu().numpy().reshape(M, ni, nj)
@@ -1247,7 +1267,7 @@ class JetModel:
 
     def clean_image_ff(self, u_m, v_m, freq, weights=None, shape=None, cell_as=None, formal=False,
                        mfs=False, niter=500, gain=0.1, threshold_jy=0.0, mask=None, beam=None,
-                       psf_shape=None):
+                       psf_shape=None, imfit=None):
         """CLEANed, restored images [Jy / clean beam] of the `flux_ff` maps as an array with the
         baselines (`u_m`, `v_m`) in metres sees them: `dirty_image_ff` and `dirty_beam` (same
         arguments, kept on the device), Hogbom's CLEAN of every image with its own beam
@@ -1262,7 +1282,13 @@ class JetModel:
         array: where components may lie.  `beam`: None = fitted to the main lobe of every map's
         dirty beam (`engine.fit_beam`), or (bmaj_as, bmin_as, bpa_deg).  `psf_shape`: the (odd)
         grid the dirty beam is computed on, None = (2 ni - 1, 2 nj - 1), full Hogbom; smaller =
-        the subtraction is windowed.  Everything else as `dirty_image_ff`.  Calling rank only."""
+        the subtraction is windowed.  Everything else as `dirty_image_ff`.  Calling rank only.
+        `imfit`: None = no fit; True, or a dict of `box` (i0, i1, j0, j1), `theta0` ([F, 6] or one
+        start), `n_iter`, `rms` [Jy / beam] = one elliptical Gaussian is fitted to every restored
+        image on the device (`RTEngine.gaussfit`, rjp_gaussfit; start: `engine.gauss_start`) before
+        it is copied -- what the reference gets from CASA imfit (classes.py:2790-2840) -- and
+        `CleanResult.imfit` holds one dict per map (`engine.gauss_results`).  The default box is
+        the bounding box of `mask`, the whole image without one."""
         freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
         eng = self.engine
         u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
@@ -1270,11 +1296,11 @@ class JetModel:
         su, sv = self._vis_scales(freqs)
         V = eng.vis(maps.reshape(len(freqs), -1), self.nx, self.nz, su, sv, u_d, v_d)
         return self._clean_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
-                                  threshold_jy, mask, beam, psf_shape)
+                                  threshold_jy, mask, beam, psf_shape, imfit)
 
     def clean_image_rrl(self, rrl, u_m, v_m, freq, weights=None, shape=None, cell_as=None,
                         contsub=True, formal=False, mfs=False, niter=500, gain=0.1,
-                        threshold_jy=0.0, mask=None, beam=None, psf_shape=None):
+                        threshold_jy=0.0, mask=None, beam=None, psf_shape=None, imfit=None):
         """CLEANed, restored images of the `flux_rrl` maps (same arguments) -> `CleanResult`; see
         `clean_image_ff`."""
         freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
@@ -1284,7 +1310,87 @@ class JetModel:
         su, sv = self._vis_scales(freqs)
         V = eng.vis(maps.reshape(len(freqs), -1), self.nx, self.nz, su, sv, u_d, v_d)
         return self._clean_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
-                                  threshold_jy, mask, beam, psf_shape)
+                                  threshold_jy, mask, beam, psf_shape, imfit)
+
+    # ------------------------------------------------------------------ imfit ----
+    def _imfit_options(self, imfit, mask, ni, nj):
+        """The `imfit` keyword of `clean_image_*` / `imfit` -> None or a dict (box, theta0,
+        n_iter, rms); the default box is the bounding box of `mask` (as `_clean_mask` reads it)."""
+        if imfit is None or imfit is False:
+            return None
+        opts = {} if imfit is True else dict(imfit)
+        bad = set(opts) - {"box", "theta0", "n_iter", "rms"}
+        if bad:
+            raise ValueError("imfit: unknown option(s) %s" % sorted(bad))
+        box = opts.get("box")
+        if box is None:
+            mk = self._clean_mask(mask, ni, nj)
+            if mk is not None and mk.any():
+                ii, jj = np.nonzero(mk)
+                box = (int(ii.min()), int(ii.max()), int(jj.min()), int(jj.max()))
+            else:
+                box = (0, ni - 1, 0, nj - 1)
+        box = tuple(int(x) for x in np.ravel(box))
+        if len(box) != 4 or not (0 <= box[0] <= box[1] < ni and 0 <= box[2] <= box[3] < nj):
+            raise ValueError("imfit: the box (i0, i1, j0, j1) must lie inside the image")
+        return {"box": box, "theta0": opts.get("theta0"), "n_iter": int(opts.get("n_iter", 60)),
+                "rms": opts.get("rms")}
+
+    def _imfit_images(self, image, ni, nj, abc, cell, opts, sl=None):
+        """One Gaussian per image of the device stack `image` [M, ni * nj] (`RTEngine.gaussfit`)
+        -> list of M dicts (`engine.gauss_results`).  `abc`: the clean beams, one per map; `sl`:
+        the rows of a `theta0` / `rms` given per map that belong to this stack."""
+        from . import engine as E
+        eng = self.engine
+        M = int(image.shape[0])
+        import torch
+
+        def pick(a, w):
+            # (a start or an rms per map: a host array or a tensor; else one for all)
+            if a is None or sl is None:
+                return a
+            if isinstance(a, torch.Tensor):
+                return a[sl] if a.dim() >= w else a
+            return np.asarray(a)[sl] if np.ndim(a) >= w else a
+        theta0 = pick(opts["theta0"], 2)
+        if theta0 is None:
+            theta0 = E.gauss_start(image, ni, nj, abc, box=opts["box"])
+        fit = eng.gaussfit(image, ni, nj, theta0, box=opts["box"], n_iter=opts["n_iter"])
+        host = {k: v.cpu().numpy() for k, v in fit.items()}
+        rms = pick(opts["rms"], 1)
+        if isinstance(rms, torch.Tensor):
+            rms = rms.detach().cpu().numpy()
+        return E.gauss_results(host["theta"], host["cov"], host["chi2"], host["npix"], abc, cell,
+                               rms=rms, shape=(ni, nj), status=host["status"])
+
+    def imfit(self, images, beam, cell_as=None, box=None, theta0=None, n_iter=60, rms=None):
+        """One elliptical Gaussian fitted to each of `images` -- (F, ni, nj) or (ni, nj), a host
+        array or a device tensor, such as a `CleanResult.image` -- on the device
+        (`RTEngine.gaussfit`) -> list of dicts, one per image (`engine.gauss_results`); what the
+        reference gets from CASA imfit (classes.py:2790-2840).  `beam`: the clean beam
+        (bmaj_as, bmin_as, bpa_deg), one or one per image (`CleanResult.beam`); `cell_as`: the
+        cell in arcsec, None = the model's; `box`, `theta0`, `n_iter`, `rms` as the `imfit`
+        keyword of `clean_image_ff`.  Calling rank only."""
+        import torch
+        from . import engine as E
+        eng = self.engine
+        if isinstance(images, torch.Tensor):
+            img = images.to(device=eng.device, dtype=torch.float64)
+        else:
+            img = torch.from_numpy(np.ascontiguousarray(images, dtype=np.float64)).to(eng.device)
+        if img.dim() == 2:
+            img = img.unsqueeze(0)
+        if img.dim() != 3:
+            raise ValueError("imfit: `images` must be (F, ni, nj) or (ni, nj)")
+        M, ni, nj = (int(x) for x in img.shape)
+        _, _, cell = self._image_grid((ni, nj), cell_as)
+        beams = np.asarray(beam, dtype=np.float64).reshape(-1, 3)
+        if beams.shape[0] not in (1, M):
+            raise ValueError("imfit: `beam` must be one (bmaj_as, bmin_as, bpa_deg) or one per image")
+        abc = [E.beam_quadratic(b[0], b[1], b[2], cell) for b in np.broadcast_to(beams, (M, 3))]
+        opts = self._imfit_options({"box": box, "theta0": theta0, "n_iter": n_iter, "rms": rms},
+                                   None, ni, nj)
+        return self._imfit_images(img.reshape(M, ni * nj).contiguous(), ni, nj, abc, cell, opts)
 
     # ------------------------------------------------------------------ products ----
     FORMAL_HISTORY ="Formal solution along the line of sight, observer at iy = 0"

@@ -186,4 +186,27 @@ inline int check_restore(const int32_t* d_cpix, const double* d_cflux, const int
   return RJP_OK;
 }
 
+// What rjp_gaussfit takes, in the order it refuses: NULL pointers, sizes below 1, the image size,
+// the box, lambda0 and xtol, n_iter.  (`d_mask` and `d_trace` may be NULL; the grid and the workspace
+// are checked where the tiling lives.)
+inline int check_gaussfit(const double* d_img, int n_maps, int nx, int nz, const int32_t* h_box,
+                          const double* d_theta, double lambda0, double xtol, int n_iter,
+                          const double* d_chi2, const double* d_cov, const int32_t* d_npix,
+                          const int32_t* d_niter, const int32_t* d_status, std::string& err) {
+  if (!d_img || !h_box || !d_theta || !d_chi2 || !d_cov || !d_npix || !d_niter || !d_status)
+    return refuse(err, "rjp_gaussfit: NULL images, box, parameters or outputs");
+  if (n_maps < 1 || nx < 1 || nz < 1)
+    return refuse(err, "rjp_gaussfit: n_maps, nx and nz must be positive");
+  if ((int64_t)nx * nz > (int64_t)INT32_MAX)
+    return refuse(err, "rjp_gaussfit: nx * nz exceeds 2^31 - 1");
+  if (h_box[0] < 0 || h_box[1] >= nx || h_box[1] < h_box[0] || h_box[2] < 0 || h_box[3] >= nz ||
+      h_box[3] < h_box[2])
+    return refuse(err, "rjp_gaussfit: the box (i0, i1, j0, j1) must lie inside the image, "
+                       "i0 <= i1 and j0 <= j1");
+  if (!(lambda0 > 0.0) || !std::isfinite(lambda0) || !(xtol > 0.0) || !std::isfinite(xtol))
+    return refuse(err, "rjp_gaussfit: lambda0 and xtol must be finite and positive");
+  if (n_iter < 1) return refuse(err, "rjp_gaussfit: n_iter < 1");
+  return RJP_OK;
+}
+
 }  // namespace rjp_args

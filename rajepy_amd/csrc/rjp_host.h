@@ -1,6 +1,6 @@
 // Host-side interface between the translation units of librjprt (rjprt.hip = the C-ABI,
 // ff_scan.hip, ff_scan_inst.hip x 5, fields.hip, rrl_scan.hip, rrl_formal.hip, ff_grad.hip,
-// ff_formal_sweep.hip, ff_formal_grad.hip, vis.hip, vis_adjoint.hip, clean.hip, ...): launch
+// ff_formal_sweep.hip, ff_formal_grad.hip, vis.hip, vis_adjoint.hip, clean.hip, imfit.hip, ...): launch
 // wrappers and the small structs they exchange.  Nothing here is exported; the library's surface is include/rjprt.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -256,6 +256,21 @@ int64_t restore_workgroups(int n_maps, int nx, int nz);
 hipError_t restore_launch(const int32_t* cpix, const double* cflux, const int32_t* ncomp,
                           int n_maps, int comp_stride, const double* d_beam, const double* add,
                           int nx, int nz, double* out, hipStream_t st);
+
+// ---- imfit.hip: Levenberg-Marquardt fits of one elliptical Gaussian per map (K14) ----------------
+struct GaussfitTiling {
+  int64_t tiles;                // of 1024 consecutive pixels of the box, per map
+  int64_t workgroups;           // n_maps x tiles: the grid of every iteration's launch
+};
+GaussfitTiling gaussfit_tiling(int n_maps, int64_t box_pixels);
+// 0: does not fit a size_t
+size_t gaussfit_workspace_bytes(int n_maps, int64_t box_pixels);
+// `box`: HOST (i0, i1, j0, j1); `mask`, `trace` may be nullptr; n_iter + 1 launches, no host
+// synchronisation
+hipError_t gaussfit_launch(const double* img, int n_maps, int nx, int nz, const int32_t* box,
+                           const uint8_t* mask, double* theta, double lambda0, double xtol,
+                           int n_iter, double* chi2, double* cov, int32_t* npix, int32_t* niter,
+                           int32_t* status, double* trace, void* work, hipStream_t st);
 
 // ---- ff_scan_inst.hip: one slice of the K1 kernel family per translation unit -------------
 #define RJP_SCAN_SLICE_ARGS                                                                  \

@@ -1116,6 +1116,36 @@ int64_t rjp_restore(rjp_ctx* ctx, const int32_t* d_cpix, const double* d_cflux,
   return r ? r : wgs;
 }
 
+size_t rjp_gaussfit_workspace(int32_t n_maps, int32_t box_pixels) {
+  if (n_maps <= 0 || box_pixels <= 0) return 0;
+  return rjp::gaussfit_workspace_bytes(n_maps, box_pixels);
+}
+
+int64_t rjp_gaussfit(rjp_ctx* ctx, const double* d_img, int32_t n_maps, int32_t nx, int32_t nz,
+                     const int32_t* h_box, const uint8_t* d_mask, double* d_theta, double lambda0,
+                     double xtol, int32_t n_iter, double* d_chi2, double* d_cov, int32_t* d_npix,
+                     int32_t* d_niter, int32_t* d_status, double* d_trace, void* d_work,
+                     size_t work_bytes, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_gaussfit(d_img, n_maps, nx, nz, h_box, d_theta, lambda0, xtol,
+                                        n_iter, d_chi2, d_cov, d_npix, d_niter, d_status, m);
+      }))
+    return r;
+  const int64_t nbox = (int64_t)(h_box[1] - h_box[0] + 1) * (h_box[3] - h_box[2] + 1);
+  const rjp::GaussfitTiling t = rjp::gaussfit_tiling(n_maps, nbox);
+  if (t.workgroups > (int64_t)INT32_MAX)
+    return fail(ctx, RJP_ERR_ARG, "rjp_gaussfit: more than 2^31 - 1 workgroups");
+  const size_t need = rjp::gaussfit_workspace_bytes(n_maps, nbox);
+  if (!d_work || work_bytes < need)
+    return fail(ctx, RJP_ERR_WORKSPACE,
+                "rjp_gaussfit: workspace smaller than rjp_gaussfit_workspace()");
+  RJP_HIP(ctx, rjp::gaussfit_launch(d_img, n_maps, nx, nz, h_box, d_mask, d_theta, lambda0, xtol,
+                                    n_iter, d_chi2, d_cov, d_npix, d_niter, d_status, d_trace,
+                                    d_work, (hipStream_t)stream));
+  return t.workgroups;
+}
+
 int rjp_rrl_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
                    double time_s, int32_t gff_mode, const rjp_line* line, const double* h_nu,
                    const double* h_ctau, const double* h_csrc, const double* h_hnu_k,

@@ -1220,6 +1220,75 @@ class RTEngine:
             self._check(int(wgs), self.ctx, "rjp_restore")
         return out
 
+    # -- K14 -------------------------------------------------------------------------------------
+    def gaussfit(self, img, nx, nz, theta0, box=None, mask=None, n_iter=60, lambda0=1e-3,
+                 xtol=1e-12, trace=False):
+        """Levenberg-Marquardt fits of one elliptical Gaussian per map (rjp_gaussfit), one fused
+        launch per iteration for the whole stack, nothing going to the host -> dict of device
+        tensors: `theta` [M, 6] = (S, x0, z0, A, B, C) of S exp(-(A dx^2 + 2 B dx dz + C dz^2)),
+        dx = ix - x0, dz = iz - z0 (the form of `beam_quadratic`, cells^-2), `chi2` [M], `cov`
+        [M, 21] (the packed upper triangle of J^T J at `theta`, NOT inverted: `gauss_results`),
+        `npix`, `niter`, `status` [M] int32 -- 1 converged, 0 `n_iter` exhausted, 2 stalled
+        (lambda > 1e12), 3 degenerate (start not finite and positive definite, or fewer than 6
+        counting pixels: `theta` keeps the start, the other outputs of that map are NaN / -1) --
+        and with `trace` the rows [M, n_iter, 9] of (chi^2 of the trial, lambda, accepted, the
+        trial), NaN beyond `niter`.  `img`: float64 device tensor of M * nx * nz values (read
+        only); `theta0`: [M, 6] or one start for all (`gauss_start`); `box`: (i0, i1, j0, j1),
+        inclusive, None = the whole image; `mask`: None or nx * nz values, non-zero = the pixel
+        counts.  Non-finite pixels are skipped.  The same bits on every call.  The number of
+        workgroups per iteration is kept in `last_gaussfit_tiles`."""
+        torch = _torch()
+        nx, nz, n_iter = int(nx), int(nz), int(n_iter)
+        if nx < 1 or nz < 1 or n_iter < 1:
+            raise ValueError("gaussfit: nx, nz and n_iter must be positive")
+        if not (isinstance(img, torch.Tensor) and img.numel() >= nx * nz and
+                img.numel() % (nx * nz) == 0):
+            raise ValueError("gaussfit: `img` must hold a whole number (>= 1) of nx * nz images")
+        M = img.numel() // (nx * nz)
+        self._stack_f64("gaussfit", "img", img, M * nx * nz)
+        b = (0, nx - 1, 0, nz - 1) if box is None else tuple(int(x) for x in np.ravel(box))
+        if len(b) != 4 or not (0 <= b[0] <= b[1] < nx and 0 <= b[2] <= b[3] < nz):
+            raise ValueError("gaussfit: the box (i0, i1, j0, j1) must lie inside the image")
+        if not (np.isfinite(lambda0) and lambda0 > 0. and np.isfinite(xtol) and xtol > 0.):
+            raise ValueError("gaussfit: `lambda0` and `xtol` must be finite and positive")
+        dmask = None
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor):
+                mask = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0))
+            dmask = (mask != 0).to(device=self.device, dtype=torch.uint8).reshape(-1).contiguous()
+            if dmask.numel() != nx * nz:
+                raise ValueError("gaussfit: `mask` must have nx * nz entries")
+        if isinstance(theta0, torch.Tensor):
+            theta = theta0.to(device=self.device, dtype=torch.float64).reshape(-1, 6)
+        else:
+            theta = torch.from_numpy(np.ascontiguousarray(theta0, dtype=np.float64)
+                                     .reshape(-1, 6)).to(self.device)
+        if theta.shape[0] == 1:
+            theta = theta.expand(M, 6)
+        if theta.shape[0] != M:
+            raise ValueError("gaussfit: `theta0` must be one start (6 values) or one per map (%d)" % M)
+        theta = theta.contiguous().clone()
+        chi2 = torch.full((M,), float("nan"), dtype=torch.float64, device=self.device)
+        cov = torch.full((M, 21), float("nan"), dtype=torch.float64, device=self.device)
+        npix, niter, status = (torch.full((M,), -1, dtype=torch.int32, device=self.device)
+                               for _ in range(3))
+        tr = (torch.full((M, n_iter, 9), float("nan"), dtype=torch.float64, device=self.device)
+              if trace else None)
+        nbox = (b[1] - b[0] + 1) * (b[3] - b[2] + 1)
+        work = self._workspace(max(1, self.lib.rjp_gaussfit_workspace(M, nbox)))
+        tiles = self.lib.rjp_gaussfit(self.ctx, img.data_ptr(), M, nx, nz, (C.c_int32 * 4)(*b),
+                                      _ptr(dmask), theta.data_ptr(), float(lambda0), float(xtol),
+                                      n_iter, chi2.data_ptr(), cov.data_ptr(), npix.data_ptr(),
+                                      niter.data_ptr(), status.data_ptr(), _ptr(tr),
+                                      work.data_ptr(), work.numel(), self._stream())
+        if tiles <= 0:
+            self._check(int(tiles), self.ctx, "rjp_gaussfit")
+        self.last_gaussfit_tiles = int(tiles)
+        out = dict(theta=theta, chi2=chi2, cov=cov, npix=npix, niter=niter, status=status)
+        if trace:
+            out["trace"] = tr
+        return out
+
     def rrl_cells(self, fields, bursts, time_s, line, nus):
         """collapse=False: per-cell RRL optical depths -> device tensor [F, N]."""
         F = len(nus)
@@ -1377,6 +1446,120 @@ def fit_beam(patch):
     if not (A > 0. and C > 0. and A * C > B * B):
         raise ValueError("fit_beam: the fitted form is not positive definite")
     return A, B, C
+
+
+def gauss_start(img, nx, nz, beam_abc, box=None, mask=None):
+    """The default start of `RTEngine.gaussfit` -> tensor [M, 6] beside `img`: per map the
+    counting pixel (inside `box`, non-zero in `mask`, finite) of largest |I|, its value and
+    position, and the clean beam's (A, B, C) -- a point source as the beam sees it.  `img`: a
+    float64 tensor of M * nx * nz values; `beam_abc`: one (A, B, C) or one per map.  Plain torch,
+    batched, nothing goes to the host.  A map without a counting pixel gets a NaN peak, which
+    `gaussfit` reports as status 3.  (The reference's own estimate comes from the model's
+    tau = 1 surface, classes.py:2718-2743; a caller may pass any start instead.)"""
+    torch = _torch()
+    nx, nz = int(nx), int(nz)
+    t = img.reshape(-1, nx, nz)
+    M = int(t.shape[0])
+    ok = torch.zeros(nx, nz, dtype=torch.bool, device=t.device)
+    i0, i1, j0, j1 = (0, nx - 1, 0, nz - 1) if box is None else (int(x) for x in np.ravel(box))
+    ok[i0:i1 + 1, j0:j1 + 1] = True
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor):
+            mask = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0))
+        ok &= (mask != 0).to(t.device).reshape(nx, nz)
+    ok = ok.unsqueeze(0) & torch.isfinite(t)
+    mag = torch.where(ok, t.abs(), torch.full_like(t, -1.0)).reshape(M, -1)
+    top, idx = mag.max(dim=1)
+    val = t.reshape(M, -1).gather(1, idx.unsqueeze(1)).squeeze(1)
+    val = torch.where(top >= 0, val, torch.full_like(val, float("nan")))
+    abc = np.asarray(beam_abc, dtype=np.float64).reshape(-1, 3)
+    if abc.shape[0] not in (1, M):
+        raise ValueError("gauss_start: `beam_abc` must be one (A, B, C) or one per map (%d)" % M)
+    abc = torch.from_numpy(np.array(np.broadcast_to(abc, (M, 3)))).to(t.device)
+    pos = torch.stack([torch.div(idx, nz, rounding_mode="floor"), idx % nz], dim=1)
+    return torch.cat([val.unsqueeze(1), pos.to(torch.float64), abc], dim=1).contiguous()
+
+
+def gauss_results(theta, cov, chi2, npix, beam_abc, cell_rad, rms=None, shape=None, status=None):
+    """What CASA imfit reports, from the outputs of `RTEngine.gaussfit` (host arrays; pure NumPy)
+    -> one dict per map.  Conventions as in `beam_quadratic`; `beam_abc`: the clean beam, one
+    (A, B, C) or one per map; `cell_rad`: the cell in radians.
+      * 'peak' [Jy / beam] = S;  'I' = {'val': S sqrt(det Q_beam / det Q_fit), 'unit': 'Jy'}, the
+        integrated flux (Q = [[A, B], [B, C]]);
+      * 'x0', 'z0' [pixels]; with `shape` = (nx, nz) also 'east_as', 'north_as', the offsets from
+        the map centre ((nx-1)/2, (nz-1)/2) in arcsec under the sky convention of `vis_scales`
+        (East = DECREASING ix, North = +z);
+      * 'maj_as', 'min_as', 'pa_deg': the fitted size (`beam_from_quadratic`);
+      * 'deconvolved': {'maj_as', 'min_as', 'pa_deg'} of Sigma_src = (2 Q_fit)^-1 - (2 Q_beam)^-1,
+        or None with 'point_source' True where that is not positive definite;
+      * with `rms` [Jy / beam] (one number or one per map) the 1-sigma errors 'peak_err',
+        'x0_err', 'z0_err', 'abc_err' and 'Ierr' = {'val', 'unit'} from the covariance
+        rms^2 Omega_b (J^T J)^-1, Omega_b = pi / sqrt(det Q_beam) cells: the usual inflation for
+        noise that is correlated over a beam; Ierr by first-order propagation through
+        I(S, A, B, C).  This is a STATED APPROXIMATION, not the expressions of Condon (1997)
+        that CASA uses.  Without `rms`: None;
+      * 'chi2', 'npix', and 'status' where given.
+    A map whose fit is not finite and positive definite (status 3) gets NaN / None entries."""
+    theta = np.asarray(theta, dtype=np.float64).reshape(-1, 6)
+    M = theta.shape[0]
+    cov = np.asarray(cov, dtype=np.float64).reshape(M, 21)
+    chi2, npix = np.asarray(chi2, dtype=np.float64).reshape(M), np.asarray(npix).reshape(M)
+    beam = np.broadcast_to(np.asarray(beam_abc, dtype=np.float64).reshape(-1, 3), (M, 3))
+    rms_m = None if rms is None else np.broadcast_to(np.asarray(rms, dtype=np.float64), (M,))
+    cell_as = np.degrees(float(cell_rad)) * 3600.
+    nan = float("nan")
+    out = []
+    for m in range(M):
+        S, x0, z0, A, B, C = (float(v) for v in theta[m])
+        bA, bB, bC = (float(v) for v in beam[m])
+        det, bdet = A * C - B * B, bA * bC - bB * bB
+        d = {"peak": S, "x0": x0, "z0": z0, "chi2": float(chi2[m]), "npix": int(npix[m]),
+             "I": {"val": nan, "unit": "Jy"}, "Ierr": {"val": None, "unit": "Jy"},
+             "maj_as": nan, "min_as": nan, "pa_deg": nan, "deconvolved": None,
+             "point_source": False, "peak_err": None, "x0_err": None, "z0_err": None,
+             "abc_err": None}
+        if status is not None:
+            d["status"] = int(np.asarray(status).reshape(M)[m])
+        if shape is not None:
+            d["east_as"] = float(-(x0 - (int(shape[0]) - 1) / 2.) * cell_as)
+            d["north_as"] = float((z0 - (int(shape[1]) - 1) / 2.) * cell_as)
+        good = np.all(np.isfinite(theta[m])) and A > 0. and C > 0. and det > 0. and bdet > 0.
+        if not good:
+            out.append(d)
+            continue
+        flux = S * np.sqrt(bdet / det)
+        d["I"]["val"] = float(flux)
+        d["maj_as"], d["min_as"], d["pa_deg"] = beam_from_quadratic(A, B, C, cell_rad)
+        # covariance matrices of the Gaussians: Sigma = (2 Q)^-1
+        sig = (np.array([[C, -B], [-B, A]]) / (2. * det)
+               - np.array([[bC, -bB], [-bB, bA]]) / (2. * bdet))
+        sdet = sig[0, 0] * sig[1, 1] - sig[0, 1] * sig[1, 0]
+        if sig[0, 0] > 0. and sig[1, 1] > 0. and sdet > 0.:
+            q = np.array([[sig[1, 1], -sig[0, 1]], [-sig[0, 1], sig[0, 0]]]) / (2. * sdet)
+            mj, mn, pa = beam_from_quadratic(q[0, 0], q[0, 1], q[1, 1], cell_rad)
+            d["deconvolved"] = {"maj_as": mj, "min_as": mn, "pa_deg": pa}
+        else:
+            d["point_source"] = True
+        if rms_m is not None and np.all(np.isfinite(cov[m])):
+            N = np.zeros((6, 6))
+            k = 0
+            for i in range(6):
+                for j in range(i, 6):
+                    N[i, j] = N[j, i] = cov[m, k]
+                    k += 1
+            try:
+                P = rms_m[m] ** 2 * (np.pi / np.sqrt(bdet)) * np.linalg.inv(N)
+            except np.linalg.LinAlgError:
+                P = None
+            if P is not None and np.all(np.diag(P) >= 0.):
+                sd = np.sqrt(np.diag(P))
+                d["peak_err"], d["x0_err"], d["z0_err"] = float(sd[0]), float(sd[1]), float(sd[2])
+                d["abc_err"] = (float(sd[3]), float(sd[4]), float(sd[5]))
+                grad = np.array([flux / S if S != 0. else np.sqrt(bdet / det), 0., 0.,
+                                 -flux * C / (2. * det), flux * B / det, -flux * A / (2. * det)])
+                d["Ierr"]["val"] = float(np.sqrt(grad @ P @ grad))
+        out.append(d)
+    return out
 
 
 def ff_channel_coeffs(freqs, csize_au, dist_pc, gff_mode, gff_values=None):
