@@ -829,6 +829,52 @@ int64_t rjp_gaussfit(rjp_ctx* ctx, const double* d_img, int32_t n_maps, int32_t 
                      int32_t* d_niter, int32_t* d_status, double* d_trace, void* d_work,
                      size_t work_bytes, void* stream);
 
+/* ---- K15: uniform and Briggs imaging weights from the (u, v) density -------------------------------
+ * The reference weights its visibilities outside itself: CASA tclean(weighting='briggs', robust=0.5)
+ * (classes.py:2775-2776).  CASA is not at hand, so this comment IS the definition; parity with
+ * CASA is not claimed.  Per map m on an imaging grid of nx x nz cells, hx = nx / 2, hz = nz / 2
+ * (integer division), for n_vis visibilities shared by all maps:
+ *   gu = rint((h_su[m] d_u[k]) nx),  gv = rint((h_sv[m] d_v[k]) nz)   float64 products in this order,
+ *                            ties to even: the Fourier plane binned at 1 / (nx cell)
+ *   FLAGGED: d_u[k], d_v[k] or d_w[k] not finite, or d_w[k] < 0 (d_w = NULL: all ones)
+ *   IN RANGE: |gu| <= hx and |gv| <= hz, compared in double: a symmetric grid of
+ *                            (2 hx + 1)(2 hz + 1) cells that holds the mirror of each of its cells
+ *   COUNTED = not flagged and in range; every other visibility adds nothing and gets the weight 0
+ *   W(c) = S(c) + S(-c), S(c) the sum of the counted weights in cell c (Hermitian gridding: the origin
+ *                            cell counts its visibilities twice), summed in FIXED POINT:
+ *                            w_max = the largest counted weight of the call (any map), w_max < 2^e
+ *                            (frexp), L = ceil(log2(2 n_vis)), s = 62 - e - L, q_k = (int64) rint(w_k 2^s),
+ *                            W(c) = (double)(sum q) 2^-s with one correctly rounded conversion; the
+ *                            total of a map stays below 2^62.  w_max = 0: s = 0 and all outputs 0
+ *   mode 1, uniform:         w'_k = w_k / W(c_k)   (0 where W(c_k) = 0: weights below 2^-s-1 only)
+ *   mode 2, Briggs (Briggs 1995, casacore's "norm" form): f2 = (5 10^-robust)^2 (2 sum_k w_k) /
+ *                            sum_c W(c)^2, k over the map's counted visibilities with sum_k w_k =
+ *                            (sum q) 2^-s, c over all cells;  w'_k = w_k / fma(f2, W(c_k), 1)
+ *   d_wout [n_maps][n_vis]   the weights
+ *   d_stats [n_maps][6]      (optional) sum_k w_k (exact), sum_c W^2, f2 (0 in mode 1), the counted
+ *                            visibilities, the unflagged ones out of range, s
+ *   d_density [n_maps][(2 hx + 1)(2 hz + 1)]   (optional) W(c) at (gu + hx)(2 hz + 1) + (gv + hz)
+ * The integer sums have no order, sum_c W^2 is a float64 sum in a fixed order (tiles of 1024 cells
+ * in tile order) and there are no floating-point atomics: a repeated call gives the same bits, a
+ * permutation of the visibilities permutes the weights and changes nothing else, and replacing any
+ * (u, v) by (-u, -v) changes nothing.  A map without a counted visibility gets zeros and f2 = 0.
+ * One memset (the density and the counters) and five launches for the whole stack, no host
+ * synchronisation.
+ * RETURNS, like rjp_vis_adjoint, the number of workgroups of the scatter launch, > 0 -- n_maps x
+ * ceil(n_vis / 256) -- or a negative RJP_ERR_*.  Everything is validated before anything is enqueued,
+ * and no output or workspace byte is touched on a refusal: RJP_ERR_ARG for a NULL ctx, h_su, h_sv,
+ * d_u, d_v or d_wout; n_maps, n_vis, nx or nz < 1; a non-finite h_su / h_sv; a mode other than 1 or
+ * 2; in mode 2 a robust that is not finite or outside [-2, 2]; more than 2^31 - 1 density cells per
+ * map or workgroups in a launch.  RJP_ERR_WORKSPACE for a d_work smaller than the workspace query
+ * (256 bytes, 32 per map, 8 per tile of 1024 cells and 8 per cell; 0 from it = a bad argument or
+ * a grid of more than 2^31 - 1 cells). */
+size_t rjp_uv_weights_workspace(int32_t n_maps, int32_t nx, int32_t nz, int32_t n_vis);
+int64_t rjp_uv_weights(rjp_ctx* ctx, int32_t n_maps, int32_t n_vis, const double* h_su,
+                       const double* h_sv, const double* d_u, const double* d_v, const double* d_w,
+                       int32_t nx, int32_t nz, int32_t mode, double robust, double* d_wout,
+                       double* d_stats, double* d_density, void* d_work, size_t work_bytes,
+                       void* stream);
+
 /* ---- K4: geometry -> fields on the device --------------------------------------------
  * Replaces the lazily cached grids of JetModel (fill_factor/areas classes.py:657-669,
  * 763-764; grid_rwp 521-525; rreff 549-555; _nd 877-897; ion_fraction 915-934;

@@ -146,6 +146,55 @@ class CleanResult(collections.namedtuple(
         return out
 
 
+class Weighting(collections.namedtuple("Weighting", ["scheme", "robust", "weights"])):
+    """An imaging-weight scheme as ONE value for the `weights` of `JetModel.dirty_image_ff`, whose
+    parameter list is fixed: `scheme` None / "natural" / "uniform" / "briggs", `robust` (Briggs
+    only) and the data `weights` [K] the scheme starts from (None = all ones).  The other imaging
+    methods take `weighting=` and `robust=` beside their `weights`."""
+    __slots__ = ()
+
+    def __new__(cls, scheme="briggs", robust=0.5, weights=None):
+        return super().__new__(cls, scheme, robust, weights)
+
+
+def _split_weights(weights):
+    """The `weights` of `dirty_image_ff` -> the data weights, the scheme and its robustness: a
+    `Weighting` carries all three, anything else is data weights, naturally weighted."""
+    weighting, robust = None, 0.5
+    if isinstance(weights, Weighting):
+        weights, weighting, robust = weights.weights, weights.scheme, weights.robust
+    _weighting_mode(weighting)
+    return weights, weighting, robust
+
+
+def _weighting_mode(weighting):
+    """None for natural weights (None or "natural": no kernel, the path as it was), else the mode
+    of `RTEngine.uv_weights`."""
+    if weighting is None or weighting == "natural":
+        return None
+    if weighting not in ("uniform", "briggs"):
+        raise ValueError("imaging weights: `weighting` must be None, 'natural', 'uniform' or "
+                         "'briggs'")
+    return weighting
+
+
+def _col(eng, s):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(s, dtype=np.float64)).to(eng.device)[:, None]
+
+
+def _imaging_weights(eng, u_d, v_d, su, sv, w_d, ni, nj, mode, robust, mfs):
+    """The imaging weights of one chunk of channels from ONE `RTEngine.uv_weights` call on the
+    ni x nj image grid -> device tensor [F, K], a density per channel; `mfs`: [1, F K], one
+    density over all F K points in cycles per cell (scale 1), as `_dirty_images` images them."""
+    if not mfs:
+        return eng.uv_weights(u_d, v_d, su, sv, ni, nj, w=w_d, mode=mode, robust=robust)
+    ua = (_col(eng, su) * u_d[None, :]).reshape(-1)
+    va = (_col(eng, sv) * v_d[None, :]).reshape(-1)
+    wa = w_d.repeat(len(su)) if w_d is not None else None
+    return eng.uv_weights(ua, va, [1.0], [1.0], ni, nj, w=wa, mode=mode, robust=robust)
+
+
 class JetModel:
     """Physical model of an ionised jet + its line-of-sight radiative transfer."""
     _arr_indexing = 'ij'
@@ -1090,13 +1139,20 @@ class JetModel:
                 raise ValueError("dirty image: `cell_as` must be a positive number of arcseconds")
         return ni, nj, float(cell)
 
-    def _dirty_images(self, V, u_d, v_d, freqs, weights, shape, cell_as, mfs, device=False):
+    def _dirty_images(self, V, u_d, v_d, freqs, weights, shape, cell_as, mfs, device=False,
+                      weighting=None, robust=0.5, iw=None):
         """Dirty images [Jy / beam] of the visibilities `V` (complex device tensor [F, K]) at the
         baselines (`u_d`, `v_d`) [m] -> host array (F, ni, nj), or (1, ni, nj) with `mfs`;
         `device=True`: the same numbers as a device tensor [F or 1, ni * nj] (for `_clean_images`).
         `RTEngine.vis_adjoint` on chunks of channels whose images stay under VIS_STACK_BYTES
         (K10's `_vis_chunk` rule on the imaging grid), divided by the sum of the weights of the
-        baselines that are not flagged; nothing but the images leaves the device."""
+        baselines that are not flagged; nothing but the images leaves the device.
+        `weighting` "uniform" / "briggs" (with `robust`): the imaging weights of every chunk come
+        from ONE `RTEngine.uv_weights` call on this image's grid, a density per channel (one over
+        all F K points with `mfs`), are multiplied into V on the device and the image is divided
+        by the channel's own sum of them; the chunks then also keep the [F, K] weights under
+        VIS_STACK_BYTES.  `iw`: those weights already made ([F, K], or [1, F K] with `mfs`: what
+        `_clean_images` shares between the image and the larger beam grid)."""
         import torch
         from . import engine as E
         eng = self.engine
@@ -1106,6 +1162,31 @@ class JetModel:
         w_d = eng._device_f64(weights) if weights is not None else None
         if w_d is not None and w_d.numel() != K:
             raise ValueError("dirty image: `weights` must have one entry per baseline (%d)" % K)
+        mode = _weighting_mode(weighting)
+        if mode is not None or iw is not None:
+            if mfs:
+                if iw is None:
+                    iw = _imaging_weights(eng, u_d, v_d, su, sv, w_d, ni, nj, mode, robust, True)
+                img = eng.vis_adjoint((V.reshape(1, F * K) * iw).contiguous(), ni, nj, [1.0], [1.0],
+                                      (_col(eng, su) * u_d[None, :]).reshape(-1),
+                                      (_col(eng, sv) * v_d[None, :]).reshape(-1), None)
+                img = img / iw.sum()
+                return img if device else img.cpu().numpy().reshape(1, ni, nj)
+            out = [] if device else np.zeros((F, ni, nj))
+            step = max(1, min(self.VIS_STACK_BYTES // (ni * nj * 8), self.VIS_STACK_BYTES // (K * 8)))
+            for f0 in range(0, F, step):
+                sl = slice(f0, f0 + step)
+                wc = iw[sl] if iw is not None else _imaging_weights(
+                    eng, u_d, v_d, su[sl], sv[sl], w_d, ni, nj, mode, robust, False)
+                img = eng.vis_adjoint((V[sl] * wc).contiguous(), ni, nj, su[sl], sv[sl], u_d, v_d,
+                                      None)
+                img = img / wc.sum(dim=1)[:, None]
+                if device:
+                    out.append(img)
+                else:
+                    out[sl] = img.cpu().numpy().reshape(-1, ni, nj)
+                del img, wc
+            return torch.cat(out, dim=0) if device else out
         good = torch.isfinite(u_d) & torch.isfinite(v_d)
         if w_d is not None:
             good = good & torch.isfinite(w_d)
@@ -1146,40 +1227,115 @@ class JetModel:
         convention: `engine.image_scales`.  `formal`: as `flux_ff`.  `mfs=True`: the channels go
         into ONE image (1, ni, nj), every channel at its own (u, v) / lambda, as tclean
         specmode='mfs' combines them.  A baseline with a non-finite u, v or weight is flagged.
+        Uniform or Briggs weights -- the reference's tclean(weighting='briggs', robust=0.5),
+        classes.py:2775-2776 -- come from `weights=Weighting("briggs", robust=0.5, weights=w)`
+        (this method's parameter list is fixed; `dirty_image_rrl`, `dirty_beam` and the
+        `clean_image_*` methods take `weighting=` and `robust=` instead): the imaging weights are
+        computed on the device (`RTEngine.uv_weights`, rjp_uv_weights) from the density of the
+        (u, v) points on this image's grid, one density per channel -- with `mfs` one over all
+        channels' points --, `w` being the data weights the scheme starts from; a baseline outside
+        the grid's Fourier cells (more than half a cycle per cell) or with a negative weight is
+        then flagged too.  A plain array, None or scheme "natural" is the natural weighting.
         Calling rank only."""
         freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
         eng = self.engine
+        weights, weighting, robust = _split_weights(weights)
         u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
         maps = self._ff_products(freqs, flux=True, device=True, formal=formal)
         su, sv = self._vis_scales(freqs)
         V = eng.vis(maps.reshape(len(freqs), -1), self.nx, self.nz, su, sv, u_d, v_d)
-        return self._dirty_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs)
+        return self._dirty_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs,
+                                  weighting=weighting, robust=robust)
 
     def dirty_image_rrl(self, rrl, u_m, v_m, freq, weights=None, shape=None, cell_as=None,
-                        contsub=True, formal=False, mfs=False):
+                        contsub=True, formal=False, mfs=False, weighting=None, robust=0.5):
         """Dirty images [Jy / beam] of the `flux_rrl` maps (same arguments) -> (F, ni, nj); see
-        `dirty_image_ff`."""
+        `dirty_image_ff`.  `weighting`: None / "natural", "uniform" or "briggs" (with `robust`)."""
         freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
         eng = self.engine
+        _weighting_mode(weighting)            # (refuses an unknown scheme before any work)
         u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
         maps = self._rrl_flux(rrl, freqs, True, contsub, formal=formal, device=True)
         su, sv = self._vis_scales(freqs)
         V = eng.vis(maps.reshape(len(freqs), -1), self.nx, self.nz, su, sv, u_d, v_d)
-        return self._dirty_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs)
+        return self._dirty_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs,
+                                  weighting=weighting, robust=robust)
 
-    def dirty_beam(self, u_m, v_m, freq, weights=None, shape=None, cell_as=None, mfs=False):
+    def dirty_beam(self, u_m, v_m, freq, weights=None, shape=None, cell_as=None, mfs=False,
+                   weighting=None, robust=0.5):
         """The dirty beam (point-spread function) of the (u, v) coverage at every frequency ->
         float64 (F, ni, nj), or (1, ni, nj) with `mfs`: `dirty_image_ff` of visibilities that are
         all 1.  At the centre pixel of an odd-sized grid every phase is exactly 0 and the beam
-        is 1 (to the last bit with unit weights); it is symmetric under point reflection."""
+        is 1 (to the last bit with unit weights); it is symmetric under point reflection.
+        `weighting`, `robust`: as `dirty_image_rrl`; the weights are those of an IMAGE on this
+        grid."""
         import torch
         freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
         eng = self.engine
+        _weighting_mode(weighting)            # (refuses an unknown scheme before any work)
         u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
         V = torch.zeros(len(freqs), int(u_d.numel()), 2, dtype=torch.float64, device=eng.device)
         V[..., 0] = 1.0
         return self._dirty_images(torch.view_as_complex(V), u_d, v_d, freqs, weights, shape,
-                                  cell_as, mfs)
+                                  cell_as, mfs, weighting=weighting, robust=robust)
+
+    def imaging_weights(self, u_m, v_m, freq, weights=None, shape=None, cell_as=None,
+                        weighting="briggs", robust=0.5, mfs=False):
+        """The imaging weights the `dirty_image_*` / `clean_image_*` methods use with these
+        arguments -> (float64 host array (F, K), dict): one row per channel (with `mfs` the
+        [F, K] weights of the one density over all channels' points), computed on the device
+        (`RTEngine.uv_weights`) in chunks of channels that stay under VIS_STACK_BYTES.  The dict
+        holds one array [F] (one entry with `mfs`) per statistic: 'sum_w' (the counted data
+        weights), 'sum_w2' (sum of the squared density), 'f2' (0 unless Briggs), 'counted',
+        'out_of_range', 'shift', 'sum_wout' and 'noise_factor' =
+        sqrt(sum(w'^2 / w) sum(w)) / sum(w') over the counted visibilities with w > 0: the
+        thermal rms relative to natural weighting, >= 1.  "natural" / None returns the data
+        weights with the flagged ones set to 0 and a factor of 1."""
+        import torch
+        from . import engine as E
+        eng = self.engine
+        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
+        _weighting_mode(weighting)            # (refuses an unknown scheme before any work)
+        mode = _weighting_mode(weighting)
+        ni, nj, cell = self._image_grid(shape, cell_as)
+        su, sv = E.image_scales(freqs, cell)
+        u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
+        F, K = len(freqs), int(u_d.numel())
+        w_d = eng._device_f64(weights) if weights is not None else None
+        if v_d.numel() != K or (w_d is not None and w_d.numel() != K):
+            raise ValueError("imaging weights: u, v and weights must have one entry per baseline")
+        w1 = w_d if w_d is not None else torch.ones(K, dtype=torch.float64, device=eng.device)
+        names = ("sum_w", "sum_w2", "f2", "counted", "out_of_range", "shift")
+        if mode is None:
+            ok = torch.isfinite(u_d) & torch.isfinite(v_d) & torch.isfinite(w1) & (w1 >= 0)
+            row = torch.where(ok, w1, torch.zeros_like(w1)).cpu().numpy()
+            n = 1 if mfs else F
+            st = {k: np.zeros(n) for k in names}
+            st["sum_w"][:] = row.sum() * (F if mfs else 1)
+            st["counted"][:] = np.count_nonzero(ok.cpu().numpy()) * (F if mfs else 1)
+            st["sum_wout"], st["noise_factor"] = st["sum_w"].copy(), np.ones(n)
+            return np.tile(row, (F, 1)), st
+        out, stats, extra = np.zeros((F, K)), [], []
+        step = F if mfs else max(1, self.VIS_STACK_BYTES // (K * 8))
+        for f0 in range(0, F, step):
+            sl = slice(f0, f0 + step)
+            iw = _imaging_weights(eng, u_d, v_d, su[sl], sv[sl], w_d, ni, nj, mode, robust, mfs)
+            wd = w1.repeat(F)[None, :] if mfs else w1[None, :]
+            live = (iw > 0) & (wd > 0)
+            ratio = torch.where(live, iw * iw / torch.where(live, wd, torch.ones_like(wd)),
+                                torch.zeros_like(iw))
+            extra.append(torch.stack([iw.sum(dim=1), ratio.sum(dim=1),
+                                      torch.where(live, wd.expand_as(iw), torch.zeros_like(iw))
+                                      .sum(dim=1)], dim=1).cpu().numpy())
+            stats.append(eng.last_uv_weight_stats.cpu().numpy())
+            out[sl] = iw.cpu().numpy().reshape(-1, K)
+            del iw
+        stats, extra = np.concatenate(stats, axis=0), np.concatenate(extra, axis=0)
+        st = {k: stats[:, i].copy() for i, k in enumerate(names)}
+        st["sum_wout"] = extra[:, 0]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            st["noise_factor"] = np.sqrt(extra[:, 1] * extra[:, 2]) / extra[:, 0]
+        return out, st
 
     # ------------------------------------------------------------------ CLEAN ----
     BEAM_PATCH = 33          # side of the central patch of the dirty beam that `fit_beam` sees
@@ -1203,12 +1359,15 @@ class JetModel:
         return m != 0
 
     def _clean_images(self, V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
-                      threshold_jy, mask, beam, psf_shape, imfit=None):
+                      threshold_jy, mask, beam, psf_shape, imfit=None, weighting=None, robust=0.5):
         """Hogbom CLEAN of the dirty images of `V` (see `clean_image_ff`), in chunks of channels
         whose dirty images AND beams stay under VIS_STACK_BYTES.  Per chunk, on the device:
         `_dirty_images` of V and of unit visibilities (the beams, on the `psf_shape` grid),
         `RTEngine.clean`, `RTEngine.restore`; only the central patch of each beam goes to the
-        host before the end (for `fit_beam`)."""
+        host before the end (for `fit_beam`).  With `weighting` "uniform" / "briggs" the chunk's
+        imaging weights are computed ONCE, on the image's grid (never the larger beam grid), and
+        image and beam share them; the chunks then also keep the [F, K] weights under
+        VIS_STACK_BYTES."""
         import torch
         from . import engine as E
         eng = self.engine
@@ -1232,12 +1391,24 @@ class JetModel:
                           peak_residual=np.zeros(n_out), imfit=None if fit_opts is None else [])
         step = F if mfs else max(1, self.VIS_STACK_BYTES // ((ni * nj * 3 + pi_ * pj) * 8))
         hi, hj = min(self.BEAM_PATCH, pi_) // 2, min(self.BEAM_PATCH, pj) // 2
+        mode = _weighting_mode(weighting)
+        if mode is not None:
+            w_d = eng._device_f64(weights) if weights is not None else None
+            if w_d is not None and w_d.numel() != K:
+                raise ValueError("dirty image: `weights` must have one entry per baseline (%d)" % K)
+            if not mfs:
+                step = max(1, min(step, self.VIS_STACK_BYTES // (K * 8)))
         for f0 in range(0, F, step):
             sl = slice(f0, f0 + step)
+            iw = None
+            if mode is not None:
+                isu, isv = E.image_scales(freqs[sl], cell)
+                iw = _imaging_weights(eng, u_d, v_d, isu, isv, w_d, ni, nj, mode, robust, mfs)
             dirty = self._dirty_images(V[sl], u_d, v_d, freqs[sl], weights, (ni, nj), cell_as,
-                                       mfs, device=True)
+                                       mfs, device=True, iw=iw)
             psf = self._dirty_images(ones[sl], u_d, v_d, freqs[sl], weights, (pi_, pj), cell_as,
-                                     mfs, device=True)
+                                     mfs, device=True, iw=iw)
+            del iw
             M = int(dirty.shape[0])
             if beam is None:
                 ci, cj = (pi_ - 1) // 2, (pj - 1) // 2
@@ -1267,7 +1438,7 @@ class JetModel:
 
     def clean_image_ff(self, u_m, v_m, freq, weights=None, shape=None, cell_as=None, formal=False,
                        mfs=False, niter=500, gain=0.1, threshold_jy=0.0, mask=None, beam=None,
-                       psf_shape=None, imfit=None):
+                       psf_shape=None, imfit=None, weighting=None, robust=0.5):
         """CLEANed, restored images [Jy / clean beam] of the `flux_ff` maps as an array with the
         baselines (`u_m`, `v_m`) in metres sees them: `dirty_image_ff` and `dirty_beam` (same
         arguments, kept on the device), Hogbom's CLEAN of every image with its own beam
@@ -1288,29 +1459,39 @@ class JetModel:
         image on the device (`RTEngine.gaussfit`, rjp_gaussfit; start: `engine.gauss_start`) before
         it is copied -- what the reference gets from CASA imfit (classes.py:2790-2840) -- and
         `CleanResult.imfit` holds one dict per map (`engine.gauss_results`).  The default box is
-        the bounding box of `mask`, the whole image without one."""
+        the bounding box of `mask`, the whole image without one.
+        `weighting`: None / "natural" (the path as it was), "uniform" or "briggs" with `robust` --
+        the reference's tclean(weighting='briggs', robust=0.5), classes.py:2775-2776: imaging
+        weights from the (u, v) density on the IMAGE's grid (`RTEngine.uv_weights`), one density
+        per channel (one over all channels with `mfs`), shared by the image and its beam;
+        `weights` are the data weights the scheme starts from (see `dirty_image_ff`)."""
         freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
         eng = self.engine
+        _weighting_mode(weighting)            # (refuses an unknown scheme before any work)
         u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
         maps = self._ff_products(freqs, flux=True, device=True, formal=formal)
         su, sv = self._vis_scales(freqs)
         V = eng.vis(maps.reshape(len(freqs), -1), self.nx, self.nz, su, sv, u_d, v_d)
         return self._clean_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
-                                  threshold_jy, mask, beam, psf_shape, imfit)
+                                  threshold_jy, mask, beam, psf_shape, imfit, weighting=weighting,
+                                  robust=robust)
 
     def clean_image_rrl(self, rrl, u_m, v_m, freq, weights=None, shape=None, cell_as=None,
                         contsub=True, formal=False, mfs=False, niter=500, gain=0.1,
-                        threshold_jy=0.0, mask=None, beam=None, psf_shape=None, imfit=None):
+                        threshold_jy=0.0, mask=None, beam=None, psf_shape=None, imfit=None,
+                        weighting=None, robust=0.5):
         """CLEANed, restored images of the `flux_rrl` maps (same arguments) -> `CleanResult`; see
         `clean_image_ff`."""
         freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
         eng = self.engine
+        _weighting_mode(weighting)            # (refuses an unknown scheme before any work)
         u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
         maps = self._rrl_flux(rrl, freqs, True, contsub, formal=formal, device=True)
         su, sv = self._vis_scales(freqs)
         V = eng.vis(maps.reshape(len(freqs), -1), self.nx, self.nz, su, sv, u_d, v_d)
         return self._clean_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
-                                  threshold_jy, mask, beam, psf_shape, imfit)
+                                  threshold_jy, mask, beam, psf_shape, imfit, weighting=weighting,
+                                  robust=robust)
 
     # ------------------------------------------------------------------ imfit ----
     def _imfit_options(self, imfit, mask, ni, nj):

@@ -209,4 +209,24 @@ inline int check_gaussfit(const double* d_img, int n_maps, int nx, int nz, const
   return RJP_OK;
 }
 
+// What rjp_uv_weights takes, in the order it refuses: NULL pointers, counts below 1, a non-finite
+// scale, the mode, the robustness.  (`d_w`, `d_stats` and `d_density` may be NULL; the grids and the
+// workspace are checked where the tiling lives.)
+inline int check_uv_weights(int n_maps, int n_vis, const double* h_su, const double* h_sv,
+                            const double* d_u, const double* d_v, int nx, int nz, int mode,
+                            double robust, const double* d_wout, std::string& err) {
+  if (!h_su || !h_sv || !d_u || !d_v || !d_wout)
+    return refuse(err, "rjp_uv_weights: NULL scales, baselines or output");
+  if (n_maps < 1 || n_vis < 1 || nx < 1 || nz < 1)
+    return refuse(err, "rjp_uv_weights: n_maps, n_vis, nx and nz must be positive");
+  for (int m = 0; m < n_maps; ++m)
+    if (!std::isfinite(h_su[m]) || !std::isfinite(h_sv[m]))
+      return refuse(err, "rjp_uv_weights: non-finite h_su / h_sv");
+  if (mode != 1 && mode != 2)
+    return refuse(err, "rjp_uv_weights: mode must be 1 (uniform) or 2 (Briggs)");
+  if (mode == 2 && !(robust >= -2.0 && robust <= 2.0))
+    return refuse(err, "rjp_uv_weights: robust must be finite and lie in [-2, 2]");
+  return RJP_OK;
+}
+
 }  // namespace rjp_args

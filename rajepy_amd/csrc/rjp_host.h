@@ -1,6 +1,6 @@
 // Host-side interface between the translation units of librjprt (rjprt.hip = the C-ABI,
 // ff_scan.hip, ff_scan_inst.hip x 5, fields.hip, rrl_scan.hip, rrl_formal.hip, ff_grad.hip,
-// ff_formal_sweep.hip, ff_formal_grad.hip, vis.hip, vis_adjoint.hip, clean.hip, imfit.hip, ...): launch
+// ff_formal_sweep.hip, ff_formal_grad.hip, vis.hip, vis_adjoint.hip, clean.hip, imfit.hip, uv_weight.hip, ...): launch
 // wrappers and the small structs they exchange.  Nothing here is exported; the library's surface is include/rjprt.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -271,6 +271,22 @@ hipError_t gaussfit_launch(const double* img, int n_maps, int nx, int nz, const 
                            const uint8_t* mask, double* theta, double lambda0, double xtol,
                            int n_iter, double* chi2, double* cov, int32_t* npix, int32_t* niter,
                            int32_t* status, double* trace, void* work, hipStream_t st);
+
+// ---- uv_weight.hip: uniform and Briggs imaging weights from the (u, v) density (K15) -------------
+struct UvWeightTiling {
+  int64_t cells;                // (2 (nx / 2) + 1)(2 (nz / 2) + 1), per map (INT64_MAX: beyond int64)
+  int64_t workgroups;           // n_maps x ceil(n_vis / 256): the grid of the scatter launch
+  int64_t square_workgroups;    // n_maps x tiles of 1024 cells: the grid of the sum of W^2
+};
+UvWeightTiling uv_weights_tiling(int n_maps, int nx, int nz, int n_vis);
+// 0: does not fit a size_t
+size_t uv_weights_workspace_bytes(int n_maps, int nx, int nz, int n_vis);
+// `c2` = (5 10^-robust)^2 (mode 2); `w`, `stats`, `density` may be nullptr; one memset and five
+// launches, no host synchronisation
+hipError_t uv_weights_launch(int n_maps, int n_vis, const double* d_su, const double* d_sv,
+                             const double* u, const double* v, const double* w, int nx, int nz,
+                             int mode, double c2, double* wout, double* stats, double* density,
+                             void* work, hipStream_t st);
 
 // ---- ff_scan_inst.hip: one slice of the K1 kernel family per translation unit -------------
 #define RJP_SCAN_SLICE_ARGS                                                                  \

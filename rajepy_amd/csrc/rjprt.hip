@@ -1146,6 +1146,48 @@ int64_t rjp_gaussfit(rjp_ctx* ctx, const double* d_img, int32_t n_maps, int32_t 
   return t.workgroups;
 }
 
+size_t rjp_uv_weights_workspace(int32_t n_maps, int32_t nx, int32_t nz, int32_t n_vis) {
+  if (n_maps <= 0 || nx <= 0 || nz <= 0 || n_vis <= 0) return 0;
+  return rjp::uv_weights_workspace_bytes(n_maps, nx, nz, n_vis);
+}
+
+int64_t rjp_uv_weights(rjp_ctx* ctx, int32_t n_maps, int32_t n_vis, const double* h_su,
+                       const double* h_sv, const double* d_u, const double* d_v, const double* d_w,
+                       int32_t nx, int32_t nz, int32_t mode, double robust, double* d_wout,
+                       double* d_stats, double* d_density, void* d_work, size_t work_bytes,
+                       void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_uv_weights(n_maps, n_vis, h_su, h_sv, d_u, d_v, nx, nz, mode, robust,
+                                          d_wout, m);
+      }))
+    return r;
+  const rjp::UvWeightTiling t = rjp::uv_weights_tiling(n_maps, nx, nz, n_vis);
+  if (t.cells > (int64_t)INT32_MAX)
+    return fail(ctx, RJP_ERR_ARG, "rjp_uv_weights: more than 2^31 - 1 density cells");
+  if (t.workgroups > (int64_t)INT32_MAX || t.square_workgroups > (int64_t)INT32_MAX)
+    return fail(ctx, RJP_ERR_ARG, "rjp_uv_weights: more than 2^31 - 1 workgroups");
+  const size_t need = rjp::uv_weights_workspace_bytes(n_maps, nx, nz, n_vis);
+  if (need == 0) return fail(ctx, RJP_ERR_ARG, "rjp_uv_weights: the workspace size overflows");
+  if (!d_work || work_bytes < need)
+    return fail(ctx, RJP_ERR_WORKSPACE,
+                "rjp_uv_weights: workspace smaller than rjp_uv_weights_workspace()");
+  double c2 = 0.0;
+  if (mode == 2) {
+    const double f = 5.0 * std::pow(10.0, -robust);
+    c2 = f * f;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int r = staged(ctx, st, "uv_weights_launch", nullptr,
+                       {{h_su, (size_t)n_maps}, {h_sv, (size_t)n_maps}},
+                       [&](double* const* d, const double*) {
+                         return rjp::uv_weights_launch(n_maps, n_vis, d[0], d[1], d_u, d_v, d_w, nx,
+                                                       nz, mode, c2, d_wout, d_stats, d_density,
+                                                       d_work, st);
+                       });
+  return r ? r : t.workgroups;
+}
+
 int rjp_rrl_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
                    double time_s, int32_t gff_mode, const rjp_line* line, const double* h_nu,
                    const double* h_ctau, const double* h_csrc, const double* h_hnu_k,

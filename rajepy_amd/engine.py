@@ -1289,6 +1289,61 @@ class RTEngine:
             out["trace"] = tr
         return out
 
+    # -- K15 -------------------------------------------------------------------------------------
+    UV_WEIGHT_MODES = {"uniform": 1, "briggs": 2}
+
+    def uv_weights(self, u, v, su, sv, nx, nz, w=None, mode="briggs", robust=0.5,
+                   want_density=False):
+        """Uniform or Briggs imaging weights (rjp_uv_weights) of `n_vis` visibilities for each of
+        M imaging grids -> float64 device tensor [M, K].  `u`, `v`, `w` [K]: host arrays or device
+        tensors, `w` (the data weights the scheme starts from) None = all ones; `su`, `sv` [M]:
+        cycles per cell per unit of `u`, `v` of the nx x nz IMAGE the weights are for
+        (`image_scales`).  The cell of a visibility is (rint((su u) nx), rint((sv v) nz)) on the
+        symmetric grid of (2 (nx // 2) + 1)(2 (nz // 2) + 1) cells; the density W of a cell is the
+        sum of the weights in it and in its mirror cell, summed in fixed point (order-free, the
+        same bits on every call); uniform: w / W, Briggs: w / (1 + f2 W) with
+        f2 = (5 10^-robust)^2 (2 sum w) / sum W^2.  A visibility with a non-finite u, v or w, a
+        negative w, or a cell outside the grid gets 0.  Nothing goes to the host:
+        `last_uv_weight_stats` is a device tensor [M, 6] of (sum w, sum W^2, f2, counted, out of
+        range, the fixed-point shift s), `last_uv_weight_density` the density [M, cells] when
+        `want_density` (else None), `last_uv_weight_tiles` the workgroups of the scatter."""
+        torch = _torch()
+        nx, nz = int(nx), int(nz)
+        if nx < 1 or nz < 1:
+            raise ValueError("uv_weights: nx and nz must be positive")
+        if mode not in self.UV_WEIGHT_MODES:
+            raise ValueError("uv_weights: `mode` must be 'uniform' or 'briggs' (natural weights "
+                             "need no kernel)")
+        robust = float(robust)
+        if mode == "briggs" and not (-2. <= robust <= 2.):
+            raise ValueError("uv_weights: `robust` must lie in [-2, 2]")
+        su = np.ascontiguousarray(su, dtype=np.float64).reshape(-1)
+        sv = np.ascontiguousarray(sv, dtype=np.float64).reshape(-1)
+        M = su.size
+        if M < 1 or sv.size != M:
+            raise ValueError("uv_weights: su and sv must have the same length >= 1")
+        du, dv = self._device_f64(u), self._device_f64(v)
+        dw = self._device_f64(w) if w is not None else None
+        K = du.numel()
+        if K < 1 or dv.numel() != K or (dw is not None and dw.numel() != K):
+            raise ValueError("uv_weights: u, v and w must have the same length >= 1")
+        cells = (2 * (nx // 2) + 1) * (2 * (nz // 2) + 1)
+        out = self._f64(M, K)
+        stats = self._f64(M, 6)
+        dens = self._f64(M, cells) if want_density else None
+        work = self._workspace(max(1, self.lib.rjp_uv_weights_workspace(M, nx, nz, K)))
+        tiles = self.lib.rjp_uv_weights(self.ctx, M, K, _lib.dbl_array(su), _lib.dbl_array(sv),
+                                        du.data_ptr(), dv.data_ptr(), _ptr(dw), nx, nz,
+                                        self.UV_WEIGHT_MODES[mode], robust, out.data_ptr(),
+                                        stats.data_ptr(), _ptr(dens), work.data_ptr(),
+                                        work.numel(), self._stream())
+        if tiles <= 0:
+            self._check(int(tiles), self.ctx, "rjp_uv_weights")
+        self.last_uv_weight_tiles = int(tiles)
+        self.last_uv_weight_stats = stats
+        self.last_uv_weight_density = dens
+        return out
+
     def rrl_cells(self, fields, bursts, time_s, line, nus):
         """collapse=False: per-cell RRL optical depths -> device tensor [F, N]."""
         F = len(nus)
