@@ -267,8 +267,10 @@ __global__ __launch_bounds__(kRB) void rrl_maps_kernel(
   const int64_t o = (int64_t)fch * npix + p;
   double s = 0.0;
   if (live) {
-    // B_nu(T) ~ 1/(exp(h nu/kT) - 1)   (physics.py:571-574)
-    const double bnu = 1.0 / (exp(hnu_k[fch] / tavg[p]) - 1.0);
+    // B_nu(T) ~ 1/(exp(h nu/kT) - 1)   (physics.py:571-574), through expm1 as in rrl_formal.hip:
+    // h nu/kT is 2e-6 ... 1e-3 at radio frequencies, where exp() - 1 cancels 5 to 6 digits
+    // (the original does; this stage differs from it by up to ~5e-11 there)
+    const double bnu = 1.0 / expm1(hnu_k[fch] / tavg[p]);
     // rrls.py:445-447
     s = cflux[fch] * bnu * exp(-tau_ff[o]) * one_minus_exp_neg(tau_rrl[o]);
     if (flux_ff) s += flux_ff[o];
