@@ -879,6 +879,63 @@ int64_t rjp_uv_weights(rjp_ctx* ctx, int32_t n_maps, int32_t n_vis, const double
                        double* d_stats, double* d_density, void* d_work, size_t work_bytes,
                        void* stream);
 
+/* ---- K16: synthetic observations -- (u, v, w) tracks of an array and thermal noise ---------------
+ * The reference observes its models outside itself: CASA simobserve (classes.py:2490-2650).  CASA is
+ * not at hand, so this comment IS the definition; parity with simobserve is not claimed.
+ *
+ * TRACKS.  Earth-rotation synthesis of n_ant antennas over n_t integrations:
+ *   h_xyz [n_ant][3]   geocentric (ITRF) antenna positions [m]
+ *   h_gha [n_t]        Greenwich hour angle of the phase centre per integration, in TURNS; it is
+ *                      reduced exactly, g = gha - rint(gha), and G = 2 pi g is evaluated by the
+ *                      library's sine / cosine of an argument in turns (truncation < 2e-14 / 1e-15)
+ *   sin_dec, cos_dec   of the phase centre's declination
+ *   h_up [n_ant][3]    (optional) unit local verticals;  sin_min_el: sine of the elevation limit
+ *   d_u, d_v, d_w [n_t][n_bl]   [m]; d_w may be NULL.  n_bl = n_ant (n_ant - 1) / 2, the pairs (i < j)
+ *                      in i-major order -- (0,1), (0,2), ..., (1,2), ... -- with b = xyz_j - xyz_i:
+ *   u =          sinG bx +         cosG by
+ *   v = -sin_dec cosG bx + sin_dec sinG by + cos_dec bz
+ *   w =  cos_dec cosG bx - cos_dec sinG by + sin_dec bz
+ * The source direction in the ITRF frame is s = (cos_dec cosG, -cos_dec sinG, sin_dec).
+ * FLAGS: with h_up, antenna i is below the limit at integration t when up_i . s(t) < sin_min_el
+ * (float64; a NaN limit flags nothing); a baseline with either antenna below it gets u = v = w = NaN
+ * -- the flag the chain honours: rjp_vis writes a NaN visibility there, rjp_vis_adjoint and
+ * rjp_uv_weights drop it.  A non-finite h_gha[t] flags the whole integration t.  The ABI carries no
+ * geography beyond this: no dates, no longitude (GHA = local hour angle - east longitude is the
+ * caller's).  One launch, one thread per (t, baseline), no atomics: the same bits on every call.
+ * RETURNS the number of workgroups of the launch, > 0 -- n_t x ceil(n_bl / 256) -- or a negative
+ * RJP_ERR_*.  Everything is validated before anything is enqueued, and no output byte is touched on
+ * a refusal: RJP_ERR_ARG for a NULL ctx, h_xyz, h_gha, d_u or d_v; n_ant < 2; n_t < 1; a non-finite
+ * h_xyz, sin_dec or cos_dec; |sin_dec^2 + cos_dec^2 - 1| > 1e-12; n_t n_bl > 2^31 - 1.
+ *
+ * NOISE.  Thermal noise that is a pure function of (seed, map, visibility), on the
+ * [n_maps][n_vis][2] layout (re, im) of rjp_vis's output:
+ *   d_out[m][k] = d_vis[m][k] + h_sigma[m] s_k (g1 + i g2),   s_k = d_s[k] (d_s = NULL: all ones)
+ * d_out may be d_vis (in place).  (g1, g2) come from ONE block of Philox4x32-10 (Salmon et al. 2011;
+ * multipliers D2511F53 / CD9E8D57, Weyl constants 9E3779B9 / BB67AE85):
+ *   key     = (low, high 32 bits of seed)
+ *   counter = (low 32 bits of k0 + k, high 32 bits of k0 + k, m0 + m, 0)
+ * k0 (int64) and m0 (int32) are the offsets of this call's chunk inside the whole data set, so that
+ * chunked calls reproduce the unchunked bits.  The output words x0 .. x3 give
+ *   n1 = (x0 << 20) | (x1 >> 12)  (52 bits),  u1 = (2 n1 + 1) 2^-53,  u2 likewise from x2, x3
+ * -- exact in float64 and strictly inside (0, 1) -- and Box-Muller
+ *   r = sqrt(-2 log(u1)),  g1 = r cos(2 pi u2),  g2 = r sin(2 pi u2)
+ * with the same sine / cosine of an argument in turns; the real part is fma((sigma s_k) r, cos, Re V),
+ * the imaginary part likewise with the sine.  A map whose h_sigma[m] is 0 is copied bit for bit
+ * (V + 0 g would turn -0.0 into +0.0).  NaN visibilities stay NaN.  A non-finite d_s[k] makes
+ * visibility k NaN in EVERY map, those with sigma = 0 included (it flags the visibility).  No
+ * atomics and no dependence on the launch shape: a repeated call, a call split into chunks with
+ * k0 / m0, and in place against out of place all give identical bits.  One launch.
+ * RETURNS the number of workgroups of the launch, > 0 -- n_maps x ceil(n_vis / 256) -- or a negative
+ * RJP_ERR_*, validated like the tracks: RJP_ERR_ARG for a NULL ctx, d_vis, h_sigma or d_out; n_maps
+ * or n_vis < 1; a negative or non-finite h_sigma; k0 < 0 or k0 + n_vis > 2^63 - 1; m0 < 0 or
+ * m0 + n_maps > 2^31 - 1; more than 2^31 - 1 workgroups. */
+int64_t rjp_uv_tracks(rjp_ctx* ctx, const double* h_xyz, int32_t n_ant, const double* h_gha,
+                      int32_t n_t, double sin_dec, double cos_dec, const double* h_up,
+                      double sin_min_el, double* d_u, double* d_v, double* d_w, void* stream);
+int64_t rjp_vis_noise(rjp_ctx* ctx, const double* d_vis, int32_t n_maps, int32_t n_vis,
+                      const double* h_sigma, const double* d_s, uint64_t seed, int64_t k0,
+                      int32_t m0, double* d_out, void* stream);
+
 /* ---- K4: geometry -> fields on the device --------------------------------------------
  * Replaces the lazily cached grids of JetModel (fill_factor/areas classes.py:657-669,
  * 763-764; grid_rwp 521-525; rreff 549-555; _nd 877-897; ion_fraction 915-934;

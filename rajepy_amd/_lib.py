@@ -162,6 +162,10 @@ SIGNATURES = {
     "rjp_uv_weights_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "rjp_uv_weights": (C.c_int64, [_P, C.c_int32, C.c_int32, _DP, _DP, _P, _P, _P, C.c_int32,
                                    C.c_int32, C.c_int32, C.c_double, _P, _P, _P, _P, C.c_size_t, _P]),
+    "rjp_uv_tracks": (C.c_int64, [_P, _DP, C.c_int32, _DP, C.c_int32, C.c_double, C.c_double, _DP,
+                                  C.c_double, _P, _P, _P, _P]),
+    "rjp_vis_noise": (C.c_int64, [_P, _P, C.c_int32, C.c_int32, _DP, _P, C.c_uint64, C.c_int64,
+                                  C.c_int32, _P, _P]),
     "rjp_rrl_formal": (C.c_int, [_P, C.POINTER(Fields), C.POINTER(Bursts), C.c_double, C.c_int32,
                                  C.POINTER(Line), _DP, _DP, _DP, _DP, C.c_int32, _P, _P, _P]),
     "rjp_rrl_cells": (C.c_int, [_P, C.POINTER(Fields), C.POINTER(Bursts), C.c_double,

@@ -146,6 +146,15 @@ class CleanResult(collections.namedtuple(
         return out
 
 
+# what `JetModel.uv_tracks` returns: device tensors u_m, v_m, w_m [n_t * n_bl] (visibility
+# k = t n_bl + b), host arrays ha_h, day [n_t] and ant1, ant2 [n_bl], and the longest baseline
+UVTracks = collections.namedtuple("UVTracks", ["u_m", "v_m", "w_m", "ha_h", "day", "ant1", "ant2",
+                                               "max_baseline_m"])
+# what `JetModel.observe_ff` / `observe_rrl` return
+Observation = collections.namedtuple("Observation", ["tracks", "vis_clean", "vis", "sigma",
+                                                     "image_rms", "clean"])
+
+
 class Weighting(collections.namedtuple("Weighting", ["scheme", "robust", "weights"])):
     """An imaging-weight scheme as ONE value for the `weights` of `JetModel.dirty_image_ff`, whose
     parameter list is fixed: `scheme` None / "natural" / "uniform" / "briggs", `robust` (Briggs
@@ -1377,7 +1386,10 @@ class JetModel:
         if pi_ < 1 or pj < 1 or pi_ % 2 == 0 or pj % 2 == 0:
             raise ValueError("clean: `psf_shape` must be two odd positive sizes")
         niter = int(niter)
-        if niter < 1 or not (0. < float(gain) <= 1.) or not (float(threshold_jy) >= 0.):
+        # (one threshold, or one per image: what `observe_ff` derives from each image's own rms)
+        thr = np.asarray(threshold_jy, dtype=np.float64).reshape(-1)
+        if niter < 1 or not (0. < float(gain) <= 1.) or not np.all(thr >= 0.) or \
+                thr.size not in (1, 1 if mfs else int(V.shape[0])):
             raise ValueError("clean: niter >= 1, 0 < gain <= 1 and threshold_jy >= 0")
         mk = self._clean_mask(mask, ni, nj)
         F, K = int(V.shape[0]), int(V.shape[1])
@@ -1418,7 +1430,8 @@ class JetModel:
                 abc = [E.beam_quadratic(beam[0], beam[1], beam[2], cell)] * M
             model = torch.zeros_like(dirty)
             cpix, cflux, ncomp, peak = eng.clean(dirty, ni, nj, psf, pi_, pj, niter, gain,
-                                                 float(threshold_jy), mask=mk, model=model)
+                                                 float(thr[0]) if thr.size == 1 else thr[f0:f0 + M],
+                                                 mask=mk, model=model)
             image = eng.restore(cpix, cflux, ncomp, abc, ni, nj, add=dirty)
             o = slice(f0, f0 + M)
             if fit_opts is not None:
@@ -1492,6 +1505,143 @@ class JetModel:
         return self._clean_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
                                   threshold_jy, mask, beam, psf_shape, imfit, weighting=weighting,
                                   robust=robust)
+
+    # ------------------------------------------------------------------ synthetic observations ----
+    def uv_tracks(self, antennalist, t_obs_s, t_int_s, min_el_deg=None, hourangle_h=0.):
+        """The (u, v, w) tracks of an array observing this model's target -> `UVTracks`: what the
+        reference leaves to CASA simobserve (classes.py:2490-2608), without dates.
+        `antennalist`: the path of an antenna list (`engine.read_antenna_config`) or an
+        `engine.AntennaConfig`.  The target's declination comes from `params['target']`; the
+        array's latitude and longitude are those of its mean position (`engine.geodetic`); the
+        integrations are those of `engine.observing_plan` for `t_obs_s` seconds on source in
+        integrations of `t_int_s`, every day centred on the LOCAL hour angle `hourangle_h`, and
+        the Greenwich hour angle is the local one minus the east longitude.  `min_el_deg`: the
+        elevation limit -- it sets the time per day the target is up, and a baseline with an
+        antenna below it (by that antenna's own vertical) is NaN in u, v and w, the flag every
+        imaging method honours; None = the horizon for the plan and no flags.
+        `u_m`, `v_m`, `w_m`: float64 DEVICE tensors [n_t * n_bl], visibility k = t n_bl + b
+        (`RTEngine.uv_tracks`, rjp_uv_tracks); `ha_h` [n_t] (hours) and `day` [n_t]: host arrays
+        per integration; `ant1`, `ant2` [n_bl]: the antennas of baseline b = xyz[ant2] -
+        xyz[ant1]; `max_baseline_m`.  Calling rank only."""
+        from . import engine as E
+        cfg = antennalist if isinstance(antennalist, E.AntennaConfig) else \
+            E.read_antenna_config(antennalist)
+        geo = E.geodetic(cfg.xyz)
+        tg = self.params['target']
+        _, dec_deg = miscf.sexagesimal_to_deg(tg['ra'], tg['dec'])
+        ha, day = E.observing_plan(dec_deg, geo.lat0_deg, t_obs_s, t_int_s,
+                                   0. if min_el_deg is None else min_el_deg, hourangle_h)
+        flags = dict(up=geo.up, min_el_rad=np.radians(min_el_deg)) if min_el_deg is not None else {}
+        u, v, w = self.engine.uv_tracks(cfg.xyz, ha - geo.lon0_deg / 360., np.radians(dec_deg),
+                                        **flags)
+        a1, a2 = np.triu_indices(len(cfg.names), 1)
+        bmax = float(np.sqrt(((cfg.xyz[a2] - cfg.xyz[a1]) ** 2).sum(axis=1)).max())
+        return UVTracks(u.reshape(-1), v.reshape(-1), w.reshape(-1), ha * 24., day,
+                        a1.astype(np.int32), a2.astype(np.int32), bmax)
+
+    def _observe(self, maps, freqs, tracks, t_int_s, sigma_jy, sefd_jy, chanwidth_hz, seed,
+                 nsigma, img):
+        """`observe_ff` / `observe_rrl` after the maps: visibilities, noise, image rms, CLEAN."""
+        import torch
+        from . import engine as E
+        eng = self.engine
+        F = len(freqs)
+        if sigma_jy is not None and sefd_jy is not None:
+            raise ValueError("observe: give `sigma_jy` or `sefd_jy`, not both")
+        if sefd_jy is not None:
+            if chanwidth_hz is None:
+                raise ValueError("observe: `sefd_jy` needs `chanwidth_hz`")
+            sigma_jy = E.thermal_sigma(sefd_jy, chanwidth_hz, t_int_s)
+        sigma = np.asarray(0. if sigma_jy is None else sigma_jy, dtype=np.float64).reshape(-1)
+        if sigma.size not in (1, F) or not np.all(np.isfinite(sigma) & (sigma >= 0.)):
+            raise ValueError("observe: `sigma_jy` must be one finite rms >= 0 or one per channel")
+        sigma = np.broadcast_to(sigma, (F,)).copy()
+        if not (float(nsigma) >= 0.):
+            raise ValueError("observe: `nsigma` must be >= 0")
+        u_d, v_d = tracks.u_m, tracks.v_m
+        su, sv = self._vis_scales(freqs)
+        V0 = eng.vis(maps.reshape(F, -1), self.nx, self.nz, su, sv, u_d, v_d)
+        noisy = bool(np.any(sigma > 0.))
+        # (every visibility has its own counter k = t n_bl + b: an independent draw per day,
+        # integration, baseline and channel)
+        V = eng.vis_noise(V0, sigma, seed=seed) if noisy else V0
+        mfs = img["mfs"]
+        rms = np.zeros(1 if mfs else F)
+        if noisy:
+            iw, _ = self.imaging_weights(u_d, v_d, freqs, weights=img["weights"], shape=img["shape"],
+                                         cell_as=img["cell_as"], weighting=img["weighting"],
+                                         robust=img["robust"], mfs=mfs)
+            rms = E.image_rms(iw.reshape(1, -1), np.repeat(sigma, iw.shape[1])) if mfs else \
+                E.image_rms(iw, sigma[:, None])
+            del iw
+        thr = img["threshold_jy"]
+        if float(nsigma) > 0.:
+            thr = np.maximum(float(thr), float(nsigma) * np.where(np.isfinite(rms), rms, 0.))
+        fit = img["imfit"]
+        if fit is not None and fit is not False and noisy:
+            fit = {} if fit is True else dict(fit)
+            if fit.get("rms") is None:
+                fit["rms"] = rms
+        res = self._clean_images(V, u_d, v_d, freqs, img["weights"], img["shape"], img["cell_as"],
+                                 mfs, img["niter"], img["gain"], thr, img["mask"], img["beam"],
+                                 img["psf_shape"], fit, weighting=img["weighting"],
+                                 robust=img["robust"])
+        host = lambda t: t.cpu().numpy()
+        v0 = host(V0)
+        return Observation(tracks, v0, host(V) if noisy else v0.copy(), sigma, rms, res)
+
+    def _tracks_of(self, antennalist, t_obs_s, t_int_s, min_el_deg, hourangle_h):
+        if isinstance(antennalist, UVTracks):
+            return antennalist
+        return self.uv_tracks(antennalist, t_obs_s, t_int_s, min_el_deg, hourangle_h)
+
+    def observe_ff(self, antennalist, freq, t_obs_s, t_int_s, min_el_deg=None, hourangle_h=0.,
+                   sigma_jy=None, sefd_jy=None, chanwidth_hz=None, seed=0, nsigma=0.,
+                   weights=None, shape=None, cell_as=None, formal=False, mfs=False, niter=500,
+                   gain=0.1, threshold_jy=0.0, mask=None, beam=None, psf_shape=None, imfit=None,
+                   weighting=None, robust=0.5):
+        """A synthetic observation of the `flux_ff` maps, start to end on the device -- the
+        reference's simobserve -> tclean -> imfit chain (classes.py:2490-2850) -> `Observation`:
+        `tracks` (`uv_tracks` of `antennalist`, `t_obs_s`, `t_int_s`, `min_el_deg`,
+        `hourangle_h`; a `UVTracks` made earlier is taken as it is), `vis_clean` (complex host
+        array (F, K), `visibilities_ff` at the tracks; NaN at flagged baselines), `vis` (the same
+        plus thermal noise: `RTEngine.vis_noise`, rjp_vis_noise, keyed by `seed`; channel f is
+        map f and visibility k = t n_bl + b of the counter, so every day, integration, baseline
+        and channel has its own draw and a seed reproduces the bits), `sigma` [F] (the rms [Jy]
+        of the real and of the imaginary part of one visibility), `image_rms` (per image,
+        `engine.image_rms` of the imaging weights actually used; 0 without noise) and `clean`
+        (the `CleanResult` of the NOISY visibilities, every imaging keyword as `clean_image_ff`).
+        Noise: `sigma_jy` (one rms or one per channel), or `sefd_jy` with `chanwidth_hz`
+        (`engine.thermal_sigma` at `t_int_s`, two polarisations); neither = noise-free, and the
+        result equals `clean_image_ff` at the same tracks bit for bit.  `nsigma` > 0: the CLEAN
+        threshold of every image is max(threshold_jy, nsigma image_rms), tclean's `nsigma` with
+        the analytic rms in place of CASA's robust estimate.  With `imfit` and noise, `image_rms`
+        is the fit's default `rms`.  Calling rank only."""
+        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
+        _weighting_mode(weighting)            # (refuses an unknown scheme before any work)
+        tracks = self._tracks_of(antennalist, t_obs_s, t_int_s, min_el_deg, hourangle_h)
+        maps = self._ff_products(freqs, flux=True, device=True, formal=formal)
+        img = dict(weights=weights, shape=shape, cell_as=cell_as, mfs=mfs, niter=niter, gain=gain,
+                   threshold_jy=threshold_jy, mask=mask, beam=beam, psf_shape=psf_shape,
+                   imfit=imfit, weighting=weighting, robust=robust)
+        return self._observe(maps, freqs, tracks, t_int_s, sigma_jy, sefd_jy, chanwidth_hz, seed,
+                             nsigma, img)
+
+    def observe_rrl(self, rrl, antennalist, freq, t_obs_s, t_int_s, min_el_deg=None,
+                    hourangle_h=0., sigma_jy=None, sefd_jy=None, chanwidth_hz=None, seed=0,
+                    nsigma=0., weights=None, shape=None, cell_as=None, contsub=True, formal=False,
+                    mfs=False, niter=500, gain=0.1, threshold_jy=0.0, mask=None, beam=None,
+                    psf_shape=None, imfit=None, weighting=None, robust=0.5):
+        """A synthetic observation of the `flux_rrl` maps -> `Observation`; see `observe_ff`."""
+        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
+        _weighting_mode(weighting)            # (refuses an unknown scheme before any work)
+        tracks = self._tracks_of(antennalist, t_obs_s, t_int_s, min_el_deg, hourangle_h)
+        maps = self._rrl_flux(rrl, freqs, True, contsub, formal=formal, device=True)
+        img = dict(weights=weights, shape=shape, cell_as=cell_as, mfs=mfs, niter=niter, gain=gain,
+                   threshold_jy=threshold_jy, mask=mask, beam=beam, psf_shape=psf_shape,
+                   imfit=imfit, weighting=weighting, robust=robust)
+        return self._observe(maps, freqs, tracks, t_int_s, sigma_jy, sefd_jy, chanwidth_hz, seed,
+                             nsigma, img)
 
     # ------------------------------------------------------------------ imfit ----
     def _imfit_options(self, imfit, mask, ni, nj):
@@ -1908,7 +2058,7 @@ class Pipeline:
                          'log': self.log}, f)
 
     def execute(self, simobserve=True, verbose=True, dryrun=False, resume=True, clobber=False,
-                formal=False, formal_rrl=False):
+                formal=False, formal_rrl=False, antenna_configs=None, sefd_jy=None, seed=0):
         """Radiative transfer for every run; writes EM/Tau/Flux FITS products, records
         `results['flux']`, pickles model and pipeline state (classes.py:2296-2479).
         `formal=True`: the flux cubes of continuum runs (and `results['flux']` from them) by the
@@ -1916,7 +2066,12 @@ class Pipeline:
         `formal_rrl=True`: those of radio-recombination-line runs by
         `JetModel.flux_rrl(formal=True)`; the Tau products are unchanged.  `formal=True` alone
         covers continuum runs only: a run table with an RRL run is then refused before any run
-        starts; `formal=True, formal_rrl=True` makes both kinds of run formal."""
+        starts; `formal=True, formal_rrl=True` makes both kinds of run formal.
+        `simobserve=True` with `antenna_configs` -- a directory of antenna lists, by default the
+        environment variable RAJEPY_ANTENNA_CONFIGS; this package ships none -- observes every run
+        that names a telescope on the device (`_synthetic_observation`): `sefd_jy` sets the
+        thermal noise (None = noise-free), `seed` its draw (run #i uses seed + i - 1).  Without
+        a directory the synthetic observations are skipped with a warning, as before."""
         if formal and not formal_rrl and any(r.obs_type != 'continuum' for r in self.runs):
             raise ValueError("formal=True: the formal solution covers continuum runs only; the "
                              "run table holds radio-recombination-line runs (formal_rrl=True "
@@ -1924,9 +2079,15 @@ class Pipeline:
         self.log.add_entry("INFO", "Beginning pipeline execution")
         if verbose != self.log.verbose:
             self.log.verbose = verbose
-        if simobserve:
+        if antenna_configs is None:
+            antenna_configs = os.environ.get("RAJEPY_ANTENNA_CONFIGS") or None
+        self._observe = None
+        if simobserve and antenna_configs is None:
             self.log.add_entry("WARNING", "CASA synthetic observations are outside the "
                                           "radiative-transfer core and are skipped")
+        elif simobserve:
+            self._observe = {"dir": os.path.expanduser(str(antenna_configs)), "sefd_jy": sefd_jy,
+                             "seed": int(seed)}
         if resume and os.path.exists(self.model_file):
             self.model = JetModel.load_model(self.model_file, engine=self.model._engine)
 
@@ -1977,6 +2138,8 @@ class Pipeline:
                         self.model.prefetch_epochs(pending[k:k + 32])
                         del pending[:k + 32]
                     self._radiative_transfer(idx, run, clobber)
+                    if self._observe is not None and run.simobserve:
+                        self._synthetic_observation(idx, run)
             except KeyboardInterrupt:
                 self.log.add_entry("ERROR", "Pipeline interrupted by user, saving state")
                 failure = (idx, "KeyboardInterrupt", "Pipeline interrupted by user")
@@ -2078,3 +2241,137 @@ class Pipeline:
             if not os.path.exists(self.model_file):
                 m.save(self.model_file)
             self.save(self.save_file, absolute_directories=True)
+
+    # the reference's imaging of a synthetic observation (classes.py:2770-2782)
+    OBSERVE_IMAGING = {"weighting": "briggs", "robust": 0.5, "niter": 500, "nsigma": 3.}
+
+    def _observation_setup(self, run, max_baseline_m):
+        """(cell [arcsec], side [cells], box) a run is imaged with: `engine.observation_grid` for
+        the model's larger angular extent, and the box (i0, i1, j0, j1) of the model's extent
+        about the image centre -- the mask the reference hands tclean (classes.py:2688-2759)."""
+        from . import engine as E
+        m = self.model
+        cm_as = np.degrees(np.arctan(m.csize * con.au /
+                                     (m.params['target']['dist'] * con.parsec))) * 3600.
+        cell_as, side = E.observation_grid(max_baseline_m, run.freq, max(m.nx, m.nz) * cm_as)
+        c = (side - 1) / 2.
+        hx, hz = 0.5 * m.nx * cm_as / cell_as, 0.5 * m.nz * cm_as / cell_as
+        box = (max(0, int(np.floor(c - hx))), min(side - 1, int(np.ceil(c + hx))),
+               max(0, int(np.floor(c - hz))), min(side - 1, int(np.ceil(c + hz))))
+        return cell_as, side, box
+
+    def _synthetic_observation(self, idx, run):
+        """The synthetic observation of one run on the device -- tracks of the run's array,
+        model visibilities, thermal noise, Briggs-weighted CLEAN down to 3 sigma inside the
+        model's box and, for continuum runs, a Gaussian fit (`JetModel.observe_ff` /
+        `observe_rrl`): the reference's simobserve -> tclean -> imfit script
+        (classes.py:2490-2850) without CASA.  Continuum runs are imaged as one multi-frequency
+        image, line runs as a cube.  Products: `clean_image` (FITS), `ms_clean` and `ms_noisy`
+        (.npz of u, v, w [m], vis [F, K], sigma [F], freqs [F], ant1, ant2 [K]; not measurement
+        sets); `results['imfit']` for continuum runs.  An antenna list that is missing or cannot
+        be read, or a target that never rises, is an ERROR entry and `results['imfit'] = None`,
+        as the reference reacts to a failed script."""
+        from . import engine as E
+        m, so = self.model, self._observe
+        tscop, t_cfg = (str(x) for x in run.tscop)
+        rrl = run.obs_type != 'continuum'
+        path = E.antenna_config_path(so["dir"], tscop, t_cfg)
+        try:
+            if path is None:
+                raise ValueError("no antenna list for (%s, %s) in %s" % (tscop, t_cfg, so["dir"]))
+            cfg = E.read_antenna_config(path)
+            tracks = m.uv_tracks(cfg, run.t_obs, run.t_int, min_el_deg=self.params['min_el'])
+        except (ValueError, OSError) as exc:
+            self.log.add_entry("ERROR", "Run #{}'s synthetic observation failed: {}"
+                                        "".format(idx + 1, exc))
+            run.results['imfit'] = None
+            return
+        cell_as, side, box = self._observation_setup(run, tracks.max_baseline_m)
+        freqs = run.chan_freqs
+        self.log.add_entry("INFO", "Synthetic observation with {} ({} antennas, {} integrations): "
+                                   "cell size of {:.2e}arcsec on {} x {} cells"
+                                   "".format(os.path.basename(path), len(cfg.names),
+                                             len(tracks.ha_h), cell_as, side, side),
+                           timestamp=False)
+        im = self.OBSERVE_IMAGING
+        kw = dict(sefd_jy=so["sefd_jy"], chanwidth_hz=run.chanwidth if so["sefd_jy"] is not None
+                  else None, seed=(so["seed"] + idx) % 2 ** 64, nsigma=im["nsigma"],
+                  shape=(side, side), cell_as=cell_as, niter=im["niter"], mask=box,
+                  weighting=im["weighting"], robust=im["robust"])
+        if rrl:
+            obs = m.observe_rrl(run.line, tracks, freqs, run.t_obs, run.t_int, contsub=False,
+                                formal=getattr(self, "_formal_rrl", False), mfs=False, **kw)
+        else:
+            obs = m.observe_ff(tracks, freqs, run.t_obs, run.t_int, mfs=True, imfit=True,
+                               formal=getattr(self, "_formal", False), **kw)
+        stem = 'SynObs.' + os.path.basename(path)[:-len('.cfg')]
+        dcy = run.rt_dcy + os.sep + 'SynObs'
+        os.makedirs(dcy, exist_ok=True)
+        ms_clean, ms_noisy = (dcy + os.sep + stem + tail for tail in ('.ms.npz', '.noisy.ms.npz'))
+        n_t = len(tracks.ha_h)
+        common = dict(u=_to_host(tracks.u_m), v=_to_host(tracks.v_m), w=_to_host(tracks.w_m),
+                      sigma=obs.sigma, freqs=np.asarray(freqs, dtype=np.float64),
+                      ant1=np.tile(tracks.ant1, n_t), ant2=np.tile(tracks.ant2, n_t))
+        _save_npz(ms_clean, vis=obs.vis_clean, **common)
+        _save_npz(ms_noisy, vis=obs.vis, **common)
+        fitsfile = run.rt_dcy + os.sep + stem + '.noisy.imaging.fits'
+        self._save_clean_image(fitsfile, obs, freqs, cell_as, rrl)
+        if not rrl:
+            run.results['imfit'] = obs.clean.imfit[0]
+        run.products['ms_noisy'], run.products['ms_clean'] = ms_noisy, ms_clean
+        run.products['clean_image'] = fitsfile
+        self.log.add_entry("INFO", "Run #{}'s synthetic observations completed with noisy "
+                                   "visibilities saved to {}, clean visibilities saved to {}, and "
+                                   "final, clean image saved to {}"
+                                   "".format(idx + 1, ms_noisy, ms_clean, fitsfile))
+
+    def _save_clean_image(self, filename, obs, freqs, cell_as, cube):
+        """The restored image(s) of an `Observation` as FITS: (F or 1, dec, ra) in Jy / beam on
+        the imaging grid of `cell_as`, the first image's clean beam in BMAJ / BMIN / BPA."""
+        tg = self.model.params['target']
+        _, dec_deg = miscf.sexagesimal_to_deg(tg['ra'], tg['dec'])
+        ra_deg = miscf.parse_sexagesimal(tg['ra']) * ((15. * (np.pi / 180.)) / (np.pi / 180.))
+        img = obs.clean.image
+        n, ni, nj = img.shape
+        h = _fits.Header()
+        h.set('OBJECT', tg['name'])
+        h.set('CTYPE1', 'RA---TAN', 'x-coord type is RA Tan Gnomonic projection')
+        h.set('CTYPE2', 'DEC--TAN', 'y-coord type is DEC Tan Gnomonic projection')
+        h.set('EQUINOX', 2000., 'Equinox of coordinates')
+        h.set('CRPIX1', ni / 2 + 0.5, 'Reference pixel in RA')
+        h.set('CRPIX2', nj / 2 + 0.5, 'Reference pixel in DEC')
+        h.set('CRVAL1', ra_deg, 'Reference pixel value in RA (deg)')
+        h.set('CRVAL2', dec_deg, 'Reference pixel value in DEC (deg)')
+        h.set('CDELT1', -cell_as / 3600., 'Pixel increment in RA (deg)')
+        h.set('CDELT2', cell_as / 3600., 'Pixel size in DEC (deg)')
+        h.set('CTYPE3', 'FREQ', 'Spectral axis (frequency)')
+        if cube and n > 1:
+            dnu = float(freqs[1] - freqs[0])
+            h.set('CRPIX3', 1., 'Reference frequency (channel number)')
+            h.set('CRVAL3', float(freqs[0]), 'Reference frequency (Hz)')
+            h.set('CDELT3', dnu, 'Frequency increment (Hz)')
+        else:
+            h.set('CRPIX3', 1., 'Reference frequency (channel number)')
+            h.set('CRVAL3', float(np.mean(freqs)), 'Reference frequency (Hz)')
+            h.set('CDELT3', float(np.ptp(freqs)) if len(freqs) > 1 else 1.,
+                  'Frequency increment (Hz)')
+        bmaj, bmin, bpa = obs.clean.beam[0]
+        h.set('BMAJ', bmaj / 3600., 'Clean beam major axis FWHM (deg)')
+        h.set('BMIN', bmin / 3600., 'Clean beam minor axis FWHM (deg)')
+        h.set('BPA', bpa, 'Clean beam position angle (deg)')
+        h.set('BUNIT', 'Jy/beam')
+        h.set('NOISERMS', float(obs.image_rms[0]), 'Thermal rms of the first image (Jy/beam)')
+        lines = self.model.__str__().split('\n')
+        h.add_history((' ' * (72 - len(lines[0]))).join(lines))
+        _fits.writeto(filename, np.transpose(img, (0, 2, 1)), h)
+
+
+def _save_npz(filename, **arrays):
+    """An uncompressed .npz whose bytes depend on the arrays alone (np.savez stamps every member
+    with the time of writing): two runs with the same seed write identical files."""
+    import zipfile
+    with zipfile.ZipFile(filename, "w", zipfile.ZIP_STORED, allowZip64=True) as z:
+        for name in sorted(arrays):
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            with z.open(info, "w", force_zip64=True) as f:
+                np.lib.format.write_array(f, np.asanyarray(arrays[name]), allow_pickle=False)

@@ -229,4 +229,44 @@ inline int check_uv_weights(int n_maps, int n_vis, const double* h_su, const dou
   return RJP_OK;
 }
 
+// What rjp_uv_tracks takes, in the order it refuses: NULL pointers, the counts, a non-finite
+// position or declination, (sin, cos) off the unit circle, the size of the outputs.  (`d_w` and
+// `h_up` may be NULL; a non-finite h_gha[t] is no refusal: it flags integration t.)
+inline int check_uv_tracks(const double* h_xyz, int n_ant, const double* h_gha, int n_t,
+                           double sin_dec, double cos_dec, const double* d_u, const double* d_v,
+                           std::string& err) {
+  if (!h_xyz || !h_gha || !d_u || !d_v)
+    return refuse(err, "rjp_uv_tracks: NULL positions, hour angles or outputs");
+  if (n_ant < 2) return refuse(err, "rjp_uv_tracks: n_ant < 2");
+  if (n_t < 1) return refuse(err, "rjp_uv_tracks: n_t < 1");
+  for (int64_t i = 0; i < 3 * (int64_t)n_ant; ++i)
+    if (!std::isfinite(h_xyz[i])) return refuse(err, "rjp_uv_tracks: non-finite h_xyz");
+  if (!std::isfinite(sin_dec) || !std::isfinite(cos_dec))
+    return refuse(err, "rjp_uv_tracks: non-finite sin_dec / cos_dec");
+  if (!(std::fabs(sin_dec * sin_dec + cos_dec * cos_dec - 1.0) <= 1e-12))
+    return refuse(err, "rjp_uv_tracks: sin_dec^2 + cos_dec^2 differs from 1 by more than 1e-12");
+  const int64_t n_bl = (int64_t)n_ant * (n_ant - 1) / 2;
+  if (n_bl > (int64_t)INT32_MAX / n_t)
+    return refuse(err, "rjp_uv_tracks: n_t * n_bl exceeds 2^31 - 1");
+  return RJP_OK;
+}
+
+// What rjp_vis_noise takes, in the order it refuses: NULL pointers, the counts, the rms values,
+// the offsets.  (`d_s` may be NULL.)
+inline int check_vis_noise(const double* d_vis, int n_maps, int n_vis, const double* h_sigma,
+                           int64_t k0, int32_t m0, const double* d_out, std::string& err) {
+  if (!d_vis || !h_sigma || !d_out)
+    return refuse(err, "rjp_vis_noise: NULL visibilities, sigmas or output");
+  if (n_maps < 1 || n_vis < 1)
+    return refuse(err, "rjp_vis_noise: n_maps and n_vis must be positive");
+  for (int m = 0; m < n_maps; ++m)
+    if (!(h_sigma[m] >= 0.0) || !std::isfinite(h_sigma[m]))
+      return refuse(err, "rjp_vis_noise: negative or non-finite h_sigma");
+  if (k0 < 0 || k0 > INT64_MAX - (int64_t)n_vis)
+    return refuse(err, "rjp_vis_noise: k0 must be >= 0 and k0 + n_vis at most 2^63 - 1");
+  if (m0 < 0 || m0 > INT32_MAX - n_maps)
+    return refuse(err, "rjp_vis_noise: m0 must be >= 0 and m0 + n_maps at most 2^31 - 1");
+  return RJP_OK;
+}
+
 }  // namespace rjp_args

@@ -1,6 +1,6 @@
 // Host-side interface between the translation units of librjprt (rjprt.hip = the C-ABI,
 // ff_scan.hip, ff_scan_inst.hip x 5, fields.hip, rrl_scan.hip, rrl_formal.hip, ff_grad.hip,
-// ff_formal_sweep.hip, ff_formal_grad.hip, vis.hip, vis_adjoint.hip, clean.hip, imfit.hip, uv_weight.hip, ...): launch
+// ff_formal_sweep.hip, ff_formal_grad.hip, vis.hip, vis_adjoint.hip, clean.hip, imfit.hip, uv_weight.hip, observe.hip, ...): launch
 // wrappers and the small structs they exchange.  Nothing here is exported; the library's surface is include/rjprt.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -287,6 +287,21 @@ hipError_t uv_weights_launch(int n_maps, int n_vis, const double* d_su, const do
                              const double* u, const double* v, const double* w, int nx, int nz,
                              int mode, double c2, double* wout, double* stats, double* density,
                              void* work, hipStream_t st);
+
+// ---- observe.hip: (u, v, w) tracks of an array and thermal noise on visibilities (K16) ------------
+// n_t x ceil(n_bl / 256), n_bl = n_ant (n_ant - 1) / 2
+int64_t uv_tracks_workgroups(int n_ant, int n_t);
+// d_xyz[n_ant][3], d_gha[n_t], d_up[n_ant][3] (or nullptr): device copies of the host tables; `w`
+// may be nullptr; one launch
+hipError_t uv_tracks_launch(const double* d_xyz, int n_ant, const double* d_gha, int n_t,
+                            double sin_dec, double cos_dec, const double* d_up, double sin_min_el,
+                            double* u, double* v, double* w, hipStream_t st);
+// n_maps x ceil(n_vis / 256)
+int64_t vis_noise_workgroups(int n_maps, int n_vis);
+// d_sigma[n_maps]: device copy of the rms per map; `s` may be nullptr; `out` may be `vis`; one launch
+hipError_t vis_noise_launch(const double* vis, int n_maps, int n_vis, const double* d_sigma,
+                            const double* s, uint64_t seed, int64_t k0, int m0, double* out,
+                            hipStream_t st);
 
 // ---- ff_scan_inst.hip: one slice of the K1 kernel family per translation unit -------------
 #define RJP_SCAN_SLICE_ARGS                                                                  \

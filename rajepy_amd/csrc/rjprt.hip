@@ -1188,6 +1188,47 @@ int64_t rjp_uv_weights(rjp_ctx* ctx, int32_t n_maps, int32_t n_vis, const double
   return r ? r : t.workgroups;
 }
 
+int64_t rjp_uv_tracks(rjp_ctx* ctx, const double* h_xyz, int32_t n_ant, const double* h_gha,
+                      int32_t n_t, double sin_dec, double cos_dec, const double* h_up,
+                      double sin_min_el, double* d_u, double* d_v, double* d_w, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_uv_tracks(h_xyz, n_ant, h_gha, n_t, sin_dec, cos_dec, d_u, d_v, m);
+      }))
+    return r;
+  const int64_t wgs = rjp::uv_tracks_workgroups(n_ant, n_t);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t A = 3 * (size_t)n_ant;
+  const int r = staged(ctx, st, "uv_tracks_launch", nullptr,
+                       {{h_xyz, A}, {h_gha, (size_t)n_t}, {h_up ? h_up : h_xyz, h_up ? A : 0}},
+                       [&](double* const* d, const double*) {
+                         return rjp::uv_tracks_launch(d[0], n_ant, d[1], n_t, sin_dec, cos_dec,
+                                                      h_up ? d[2] : nullptr, sin_min_el, d_u, d_v,
+                                                      d_w, st);
+                       });
+  return r ? r : wgs;
+}
+
+int64_t rjp_vis_noise(rjp_ctx* ctx, const double* d_vis, int32_t n_maps, int32_t n_vis,
+                      const double* h_sigma, const double* d_s, uint64_t seed, int64_t k0,
+                      int32_t m0, double* d_out, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_vis_noise(d_vis, n_maps, n_vis, h_sigma, k0, m0, d_out, m);
+      }))
+    return r;
+  const int64_t wgs = rjp::vis_noise_workgroups(n_maps, n_vis);
+  if (wgs > (int64_t)INT32_MAX)
+    return fail(ctx, RJP_ERR_ARG, "rjp_vis_noise: more than 2^31 - 1 workgroups");
+  hipStream_t st = (hipStream_t)stream;
+  const int r = staged(ctx, st, "vis_noise_launch", nullptr, {{h_sigma, (size_t)n_maps}},
+                       [&](double* const* d, const double*) {
+                         return rjp::vis_noise_launch(d_vis, n_maps, n_vis, d[0], d_s, seed, k0,
+                                                      m0, d_out, st);
+                       });
+  return r ? r : wgs;
+}
+
 int rjp_rrl_formal(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
                    double time_s, int32_t gff_mode, const rjp_line* line, const double* h_nu,
                    const double* h_ctau, const double* h_csrc, const double* h_hnu_k,

@@ -4,8 +4,10 @@ PyTorch (ROCm) is used for device memory, streams and (elsewhere) torch.distribu
 arithmetic on the RT path happens inside librjprt's HIP kernels.  Nothing here falls back to
 the CPU: without a GPU or without the built library, construction raises.
 """
+import collections
 import ctypes as C
 import os
+import re
 import weakref
 
 import numpy as np
@@ -1344,6 +1346,88 @@ class RTEngine:
         self.last_uv_weight_density = dens
         return out
 
+    # -- K16 -------------------------------------------------------------------------------------
+    def uv_tracks(self, xyz, gha_turns, dec_rad, up=None, min_el_rad=None, want_w=True):
+        """(u, v, w) [m] of every baseline of an array at every integration (rjp_uv_tracks) ->
+        three float64 device tensors [n_t, n_bl] (`w` None without `want_w`); n_bl =
+        n_ant (n_ant - 1) / 2, pairs (i < j) in i-major order, b = xyz_j - xyz_i.  `xyz`
+        [n_ant, 3]: geocentric (ITRF) positions [m]; `gha_turns` [n_t]: the Greenwich hour angle
+        of the phase centre in TURNS (local hour angle minus east longitude); `dec_rad`: its
+        declination.  With `up` [n_ant, 3] (unit local verticals: `geodetic`) and `min_el_rad`,
+        a baseline with an antenna below the elevation limit is NaN in all three -- the flag
+        `vis`, `vis_adjoint` and `uv_weights` honour; a non-finite hour angle flags its whole
+        integration.  The same bits on every call; `last_uv_tracks_tiles`: the workgroups."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+        gha = np.ascontiguousarray(gha_turns, dtype=np.float64).reshape(-1)
+        if xyz.ndim != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 2:
+            raise ValueError("uv_tracks: `xyz` must be [n_ant >= 2, 3]")
+        if gha.size < 1:
+            raise ValueError("uv_tracks: `gha_turns` must hold at least one integration")
+        A, T = int(xyz.shape[0]), int(gha.size)
+        if (up is None) != (min_el_rad is None):
+            raise ValueError("uv_tracks: `up` and `min_el_rad` go together")
+        hup, sme = None, 0.0
+        if up is not None:
+            up = np.ascontiguousarray(up, dtype=np.float64)
+            if up.shape != xyz.shape:
+                raise ValueError("uv_tracks: `up` must have the shape of `xyz`")
+            hup, sme = _lib.dbl_array(up), float(np.sin(min_el_rad))
+        B = A * (A - 1) // 2
+        if T * B > 2 ** 31 - 1:
+            raise ValueError("uv_tracks: n_t * n_bl exceeds 2^31 - 1")
+        u, v = self._f64(T, B), self._f64(T, B)
+        w = self._f64(T, B) if want_w else None
+        wgs = self.lib.rjp_uv_tracks(self.ctx, _lib.dbl_array(xyz), A, _lib.dbl_array(gha), T,
+                                     float(np.sin(dec_rad)), float(np.cos(dec_rad)), hup, sme,
+                                     u.data_ptr(), v.data_ptr(), _ptr(w), self._stream())
+        if wgs <= 0:
+            self._check(int(wgs), self.ctx, "rjp_uv_tracks")
+        self.last_uv_tracks_tiles = int(wgs)
+        return u, v, w
+
+    def vis_noise(self, vis, sigma, seed=0, s=None, k0=0, m0=0, out=None):
+        """Thermal noise added to a stack of visibility sets (rjp_vis_noise):
+        out[m, k] = vis[m, k] + sigma[m] s[k] (g1 + i g2) with (g1, g2) one Box-Muller pair of
+        the Philox4x32-10 block keyed by `seed` and counted by (k0 + k, m0 + m) -- a pure function
+        of (seed, map, visibility): chunks called with their offsets `k0`, `m0` reproduce the
+        bits of the whole.  `vis`: complex128 [M, K] or float64 [M, K, 2] device tensor; `sigma`:
+        one rms [the unit of `vis`] of the real and of the imaginary part, or one per map (0 =
+        that map is copied bit for bit); `s` [K]: per-visibility factors (host or device; None =
+        ones; a non-finite one makes its visibility NaN in every map); `out`: None = a new
+        tensor, or `vis` itself (in place).  Returns a tensor of the type of `vis`.
+        `last_vis_noise_tiles`: the workgroups."""
+        torch = _torch()
+        cplx = isinstance(vis, torch.Tensor) and vis.dtype == torch.complex128
+        v3 = torch.view_as_real(vis) if cplx else vis
+        if not (isinstance(v3, torch.Tensor) and v3.dtype == torch.float64 and
+                v3.device == self.device and v3.is_contiguous() and v3.dim() == 3 and
+                v3.shape[2] == 2 and v3.shape[0] >= 1 and v3.shape[1] >= 1):
+            raise ValueError("vis_noise: `vis` must be a contiguous complex128 [M, K] or float64 "
+                             "[M, K, 2] tensor on %s" % self.device)
+        M, K = int(v3.shape[0]), int(v3.shape[1])
+        sg = np.asarray(sigma, dtype=np.float64).reshape(-1)
+        if sg.size not in (1, M):
+            raise ValueError("vis_noise: `sigma` must be one number or one per map (%d)" % M)
+        sg = np.ascontiguousarray(np.broadcast_to(sg, (M,)))
+        ds = self._device_f64(s) if s is not None else None
+        if ds is not None and ds.numel() != K:
+            raise ValueError("vis_noise: `s` must have one entry per visibility (%d)" % K)
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("vis_noise: `seed` must fit 64 unsigned bits")
+        if out is None:
+            o3 = torch.empty_like(v3)
+        elif out is vis:
+            o3 = v3
+        else:
+            raise ValueError("vis_noise: `out` must be None or `vis` itself")
+        wgs = self.lib.rjp_vis_noise(self.ctx, v3.data_ptr(), M, K, _lib.dbl_array(sg), _ptr(ds),
+                                     seed, int(k0), int(m0), o3.data_ptr(), self._stream())
+        if wgs <= 0:
+            self._check(int(wgs), self.ctx, "rjp_vis_noise")
+        self.last_vis_noise_tiles = int(wgs)
+        return torch.view_as_complex(o3) if cplx else o3
+
     def rrl_cells(self, fields, bursts, time_s, line, nus):
         """collapse=False: per-cell RRL optical depths -> device tensor [F, N]."""
         F = len(nus)
@@ -1435,6 +1519,186 @@ def image_scales(freqs, cell_rad):
     freqs = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
     cell = float(cell_rad)
     return -cell * freqs / con.c, cell * freqs / con.c
+
+
+# -- synthetic observations (K16): the host side ------------------------------------------------
+SIDEREAL_DAY_S = 86164.0905        # the hour angle of a fixed direction advances one turn in this
+WGS84_A, WGS84_F = 6378137.0, 1. / 298.257223563
+
+AntennaConfig = collections.namedtuple("AntennaConfig", ["names", "xyz", "diameters", "observatory"])
+Geodetic = collections.namedtuple("Geodetic", ["lat_deg", "lon_deg", "up", "lat0_deg", "lon0_deg",
+                                               "up0"])
+
+
+def read_antenna_config(path):
+    """An antenna list in the format CASA simobserve reads -> `AntennaConfig` (names [A], xyz
+    [A, 3] in metres, diameters [A] in metres, observatory).  `#` lines form the header and carry
+    `observatory=` and `coordsys=`; every other non-blank line is `x y z diameter name`.  Only
+    `coordsys=XYZ` (geocentric ITRF positions) is read: `UTM` and `LOC` lists, which need a datum
+    or a site position, raise ValueError naming the system, as does a malformed line."""
+    obs, coordsys, names, xyz, diam = None, None, [], [], []
+    with open(path, "rt") as f:
+        for no, line in enumerate(f, 1):
+            text = line.strip()
+            if not text:
+                continue
+            if text.startswith("#"):
+                for key, val in re.findall(r"(\w+)\s*=\s*(\S+)", text[1:]):
+                    if key.lower() == "observatory":
+                        obs = val
+                    elif key.lower() == "coordsys":
+                        coordsys = val.upper()
+                continue
+            cols = text.split()
+            if len(cols) < 5:
+                raise ValueError("%s:%d: expected `x y z diameter name`, found %d columns"
+                                 % (path, no, len(cols)))
+            try:
+                vals = [float(c) for c in cols[:4]]
+            except ValueError:
+                raise ValueError("%s:%d: x, y, z and diameter must be numbers" % (path, no)) from None
+            if not np.all(np.isfinite(vals)) or not vals[3] > 0.:
+                raise ValueError("%s:%d: non-finite position or non-positive diameter" % (path, no))
+            xyz.append(vals[:3])
+            diam.append(vals[3])
+            names.append(cols[4])
+    if coordsys is None:
+        raise ValueError("%s: no `# coordsys=` header line" % path)
+    if not coordsys.startswith("XYZ"):
+        raise ValueError("%s: coordsys=%s is not supported (geocentric XYZ lists only)"
+                         % (path, coordsys))
+    if len(names) < 2:
+        raise ValueError("%s: fewer than two antennas" % path)
+    if len(set(names)) != len(names):
+        raise ValueError("%s: antenna names are not unique" % path)
+    return AntennaConfig(names, np.array(xyz, dtype=np.float64), np.array(diam, dtype=np.float64),
+                         obs)
+
+
+def _geodetic_one(x, y, z):
+    """WGS84 latitude, east longitude [rad] of geocentric (x, y, z) [m]: the fixed point of
+    lat = atan2(z, p (1 - e^2 N / (N + h))), which contracts by ~e^2 per step."""
+    e2 = WGS84_F * (2. - WGS84_F)
+    p = np.hypot(x, y)
+    lon = np.arctan2(y, x)
+    lat = np.arctan2(z, p * (1. - e2))
+    for _ in range(12):
+        n = WGS84_A / np.sqrt(1. - e2 * np.sin(lat) ** 2)
+        h = p / np.cos(lat) - n if abs(np.cos(lat)) > 1e-8 else abs(z) - n * (1. - e2)
+        lat = np.arctan2(z, p * (1. - e2 * n / (n + h)))
+    return lat, lon
+
+
+def geodetic(xyz):
+    """WGS84 geodetic latitude and EAST longitude [deg] and the unit local vertical (the ellipsoid
+    normal, in the geocentric frame of `xyz`) of every antenna of `xyz` [A, 3] [m], and the same
+    three of the mean position -> `Geodetic`.  The verticals are what `RTEngine.uv_tracks` takes
+    as `up`; lat0 / lon0 place the array for `observing_plan` and the hour angle."""
+    xyz = np.asarray(xyz, dtype=np.float64).reshape(-1, 3)
+    pts = np.vstack([xyz, xyz.mean(axis=0)[None, :]])
+    ll = np.array([_geodetic_one(*p) for p in pts])
+    lat, lon = ll[:, 0], ll[:, 1]
+    up = np.stack([np.cos(lat) * np.cos(lon), np.cos(lat) * np.sin(lon), np.sin(lat)], axis=1)
+    return Geodetic(np.degrees(lat[:-1]), np.degrees(lon[:-1]), up[:-1], float(np.degrees(lat[-1])),
+                    float(np.degrees(lon[-1])), up[-1])
+
+
+def observing_plan(dec_deg, lat_deg, t_obs_s, t_int_s, min_el_deg, hourangle_h=0.):
+    """The integrations of `t_obs_s` seconds on a target at declination `dec_deg` from latitude
+    `lat_deg` -> (local hour angles in TURNS [n], day of each [n]) -- the reference's rule for
+    splitting an observation over days (classes.py:2510-2550), stated here:
+      * `time_up` = 86400 s if the target is above `min_el_deg` at lower culmination, else
+        int(7200 H) with H = arccos((sin el - sin lat sin dec) / (cos lat cos dec)) in hours;
+        ValueError if the target never reaches the limit;
+      * the days last [time_up] * (t_obs // time_up) and then the remainder WHEN IT IS NOT ZERO
+        (the reference appends a day of length zero);
+      * every day is centred on `hourangle_h` and holds max(1, floor(T / t_int)) integrations of
+        `t_int_s`, placed symmetrically about the centre and taken at their mid-points;
+      * the hour angle advances one turn per SIDEREAL_DAY_S.
+    The reference's eight-scan split of the last day for east-west arrays is not made."""
+    t_obs, t_int = float(t_obs_s), float(t_int_s)
+    if not (t_obs > 0. and t_int > 0. and np.isfinite(t_obs) and np.isfinite(t_int)):
+        raise ValueError("observing_plan: t_obs_s and t_int_s must be positive")
+    dec, lat, el = np.radians(dec_deg), np.radians(lat_deg), np.radians(min_el_deg)
+    low = np.arcsin(np.clip(np.sin(lat) * np.sin(dec) - np.cos(lat) * np.cos(dec), -1., 1.))
+    if low > el:
+        time_up = 86400
+    else:
+        den = np.cos(lat) * np.cos(dec)
+        ch = (np.sin(el) - np.sin(lat) * np.sin(dec)) / den if den != 0. else np.inf
+        if not ch <= 1.:
+            raise ValueError("observing_plan: a target at declination %.3f deg never reaches an "
+                             "elevation of %.3f deg from latitude %.3f deg"
+                             % (dec_deg, min_el_deg, lat_deg))
+        time_up = int(7200. * np.degrees(np.arccos(max(ch, -1.))) / 15.)
+        if time_up < 1:
+            raise ValueError("observing_plan: the target is above %.3f deg for less than a second "
+                             "a day" % min_el_deg)
+    days = [float(time_up)] * int(t_obs // time_up)
+    rest = t_obs - (t_obs // time_up) * time_up
+    if rest > 0.:
+        days.append(rest)
+    ha, day = [], []
+    for d, T in enumerate(days):
+        n = max(1, int(np.floor(T / t_int)))
+        mid = (np.arange(n) + 0.5 - 0.5 * n) * t_int
+        ha.append(float(hourangle_h) / 24. + mid / SIDEREAL_DAY_S)
+        day.append(np.full(n, d, dtype=np.int64))
+    return np.concatenate(ha), np.concatenate(day)
+
+
+def thermal_sigma(sefd_jy, chanwidth_hz, t_int_s, n_pol=2, efficiency=1.):
+    """The rms [Jy] of the real and of the imaginary part of ONE visibility -- one baseline, one
+    channel of `chanwidth_hz`, one integration of `t_int_s`, `n_pol` polarisations averaged --
+    of an array of identical antennas of system-equivalent flux density `sefd_jy`:
+    SEFD / (efficiency sqrt(2 n_pol chanwidth t_int))."""
+    sefd, dnu, t = (np.asarray(x, dtype=np.float64) for x in (sefd_jy, chanwidth_hz, t_int_s))
+    if np.any(~(sefd >= 0.)) or np.any(~(dnu > 0.)) or np.any(~(t > 0.)) or n_pol < 1 or \
+            not efficiency > 0.:
+        raise ValueError("thermal_sigma: sefd_jy >= 0, chanwidth_hz, t_int_s, n_pol and "
+                         "efficiency > 0")
+    return sefd / (float(efficiency) * np.sqrt(2. * n_pol * dnu * t))
+
+
+def image_rms(iw, sigma_k):
+    """The thermal rms [Jy / beam] of a dirty image made with the imaging weights `iw` ([K], or
+    [M, K] -> one value per map) from visibilities whose real and imaginary parts have the rms
+    `sigma_k` (one number, [K], [M, 1] or [M, K]): sqrt(sum w'^2 sigma^2) / sum w'.  Flagged
+    visibilities carry the weight 0 and drop out; a map without weights gives NaN."""
+    w = np.atleast_2d(np.asarray(iw, dtype=np.float64))
+    s = np.broadcast_to(np.asarray(sigma_k, dtype=np.float64), w.shape)
+    live = w > 0.
+    num = np.sqrt(np.sum(np.where(live, (w * s) ** 2, 0.), axis=1))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return num / np.sum(np.where(live, w, 0.), axis=1)
+
+
+def antenna_config_path(directory, telescope, config):
+    """The antenna list of (`telescope`, `config`) in `directory`, found by name without regard
+    to case: `<tel>.<cfg>.cfg`, `<tel>_<cfg>.cfg`, or `<tel>.cfg` when the configuration is
+    '0' (a telescope with one) -> its path, or None."""
+    tel, cfg = str(telescope).lower(), str(config).lower()
+    want = [tel + "." + cfg + ".cfg", tel + "_" + cfg + ".cfg"] + ([tel + ".cfg"] if cfg == "0" else [])
+    try:
+        have = {name.lower(): name for name in sorted(os.listdir(directory), reverse=True)}
+    except OSError:
+        return None
+    for name in want:
+        if name in have:
+            return os.path.join(directory, have[name])
+    return None
+
+
+def observation_grid(max_baseline_m, freq_hz, extent_as):
+    """(cell [arcsec], image side [cells]) the reference images a synthetic observation on
+    (classes.py:2674-2678, 2753-2759): the cell is a quarter of 1 / (longest baseline in
+    wavelengths), rounded to 1e-6 arcsec; the side is ceil(2 extent / cell) for a model that
+    spans `extent_as`, and at least 500."""
+    beam_as = np.degrees(1. / (float(max_baseline_m) * float(freq_hz) / con.c)) * 3600.
+    cell_as = float("%.6f" % (beam_as / 4.))
+    if not cell_as > 0.:
+        raise ValueError("observation_grid: the cell rounds to 0 at 1e-6 arcsec")
+    return cell_as, max(500, int(np.ceil(2. * float(extent_as) / cell_as)))
 
 
 _FOUR_LN2 = 4. * np.log(2.)

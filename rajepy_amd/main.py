@@ -2,6 +2,10 @@
 
     python -m rajepy_amd.main [-v] [-rt] [-so] [-r] [-c] model_params.py pipeline_params.py
 
+`-so` observes every run that names a telescope on the device when `--antenna-configs DIR` (or the
+environment variable RAJEPY_ANTENNA_CONFIGS) names a directory of simobserve antenna lists:
+`--sefd JY` sets the thermal noise, `--seed N` its draw (`Pipeline.execute`).
+
 `--formal` (not in the reference) writes the flux cubes of continuum runs by the formal solution
 along the line of sight instead of the isothermal T_avg (1 - e^-tau); `--formal-rrl` does the same
 for the flux cubes of radio-recombination-line runs (instead of B(T_avg) e^-tau_ff (1 - e^-tau_rrl)).
@@ -31,7 +35,16 @@ def main(argv=None):
     parser.add_argument("-rt", "--radiative-transfer", action="store_true",
                         help="Compute radiative transfer solutions")
     parser.add_argument("-so", "--simobserve", action="store_true",
-                        help="Conduct synthetic observations using CASA (not part of this core)")
+                        help="Conduct synthetic observations on the device (needs "
+                             "--antenna-configs or RAJEPY_ANTENNA_CONFIGS; skipped without)")
+    parser.add_argument("--antenna-configs", default=None, metavar="DIR",
+                        help="Directory of simobserve antenna lists (<tel>.<cfg>.cfg); default: "
+                             "the environment variable RAJEPY_ANTENNA_CONFIGS")
+    parser.add_argument("--sefd", type=float, default=None, metavar="JY",
+                        help="System-equivalent flux density of one antenna [Jy] for the thermal "
+                             "noise of the synthetic observations (default: noise-free)")
+    parser.add_argument("--seed", type=int, default=0,
+                        help="Seed of the thermal noise (run #i uses seed + i - 1)")
     parser.add_argument("-r", "--resume", action="store_true",
                         help="Resume previous pipeline run if present")
     parser.add_argument("-c", "--clobber", action="store_true",
@@ -76,7 +89,8 @@ def main(argv=None):
                                 "pipeline parameters defined in {}".format(jet_file, pline_file))
     pline.execute(resume=args.resume, clobber=args.clobber, simobserve=args.simobserve,
                   verbose=args.verbose, dryrun=not args.radiative_transfer, formal=args.formal,
-                  formal_rrl=args.formal_rrl)
+                  formal_rrl=args.formal_rrl, antenna_configs=args.antenna_configs,
+                  sefd_jy=args.sefd, seed=args.seed)
     for f in (jet_file, pline_file) if rank == 0 else ():
         dest = os.path.expanduser(os.sep.join([pline.params['dcys']['model_dcy'],
                                                os.path.basename(f)]))
