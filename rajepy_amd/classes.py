@@ -23,6 +23,9 @@ from . import _constants as con
 from . import _lib
 from . import fits as _fits
 from . import logger
+# the imaging chain and its result types live in imaging.py; `JetModel` is a front to it
+from .imaging import (CleanResult, Imager, Observation, UVTracks, Weighting,  # noqa: F401
+                      _split_weights, _weighting_mode, vis_scales)
 from .maths import geometry as mgeom
 from .maths import physics as mphys
 from .maths import rrls as mrrl
@@ -124,84 +127,6 @@ def _load_params_file(py_file, checker):
     return params
 
 
-# what `JetModel.clean_image_ff` / `clean_image_rrl` return
-class CleanResult(collections.namedtuple(
-        "CleanResult", ["image", "residual", "model", "components", "beam", "peak_residual"])):
-    """The six products of a CLEAN as a tuple, and `imfit`: None, or with the `imfit` keyword one
-    dict per map (`engine.gauss_results`) -- an attribute beside the tuple, so that code which
-    unpacks the six products keeps working.  `_replace` carries `imfit` over (and takes it as a
-    keyword); `_make`, which builds from the six values alone, leaves it None."""
-
-    def __new__(cls, *args, imfit=None, **kw):
-        self = super().__new__(cls, *args, **kw)
-        self.imfit = imfit
-        return self
-
-    imfit = None
-
-    def _replace(self, **kw):
-        imfit = kw.pop("imfit", self.imfit)
-        out = super()._replace(**kw)
-        out.imfit = imfit
-        return out
-
-
-# what `JetModel.uv_tracks` returns: device tensors u_m, v_m, w_m [n_t * n_bl] (visibility
-# k = t n_bl + b), host arrays ha_h, day [n_t] and ant1, ant2 [n_bl], and the longest baseline
-UVTracks = collections.namedtuple("UVTracks", ["u_m", "v_m", "w_m", "ha_h", "day", "ant1", "ant2",
-                                               "max_baseline_m"])
-# what `JetModel.observe_ff` / `observe_rrl` return
-Observation = collections.namedtuple("Observation", ["tracks", "vis_clean", "vis", "sigma",
-                                                     "image_rms", "clean"])
-
-
-class Weighting(collections.namedtuple("Weighting", ["scheme", "robust", "weights"])):
-    """An imaging-weight scheme as ONE value for the `weights` of `JetModel.dirty_image_ff`, whose
-    parameter list is fixed: `scheme` None / "natural" / "uniform" / "briggs", `robust` (Briggs
-    only) and the data `weights` [K] the scheme starts from (None = all ones).  The other imaging
-    methods take `weighting=` and `robust=` beside their `weights`."""
-    __slots__ = ()
-
-    def __new__(cls, scheme="briggs", robust=0.5, weights=None):
-        return super().__new__(cls, scheme, robust, weights)
-
-
-def _split_weights(weights):
-    """The `weights` of `dirty_image_ff` -> the data weights, the scheme and its robustness: a
-    `Weighting` carries all three, anything else is data weights, naturally weighted."""
-    weighting, robust = None, 0.5
-    if isinstance(weights, Weighting):
-        weights, weighting, robust = weights.weights, weights.scheme, weights.robust
-    _weighting_mode(weighting)
-    return weights, weighting, robust
-
-
-def _weighting_mode(weighting):
-    """None for natural weights (None or "natural": no kernel, the path as it was), else the mode
-    of `RTEngine.uv_weights`."""
-    if weighting is None or weighting == "natural":
-        return None
-    if weighting not in ("uniform", "briggs"):
-        raise ValueError("imaging weights: `weighting` must be None, 'natural', 'uniform' or "
-                         "'briggs'")
-    return weighting
-
-
-def _col(eng, s):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(s, dtype=np.float64)).to(eng.device)[:, None]
-
-
-def _imaging_weights(eng, u_d, v_d, su, sv, w_d, ni, nj, mode, robust, mfs):
-    """The imaging weights of one chunk of channels from ONE `RTEngine.uv_weights` call on the
-    ni x nj image grid -> device tensor [F, K], a density per channel; `mfs`: [1, F K], one
-    density over all F K points in cycles per cell (scale 1), as `_dirty_images` images them."""
-    if not mfs:
-        return eng.uv_weights(u_d, v_d, su, sv, ni, nj, w=w_d, mode=mode, robust=robust)
-    ua = (_col(eng, su) * u_d[None, :]).reshape(-1)
-    va = (_col(eng, sv) * v_d[None, :]).reshape(-1)
-    wa = w_d.repeat(len(su)) if w_d is not None else None
-    return eng.uv_weights(ua, va, [1.0], [1.0], ni, nj, w=wa, mode=mode, robust=robust)
 
 
 class JetModel:
@@ -1026,13 +951,45 @@ class JetModel:
     VIS_STACK_BYTES = 1 << 30    # most bytes of maps one `RTEngine.vis` call of a sweep transforms
 
     def _vis_scales(self, freqs):
-        from . import engine as E
-        return E.vis_scales(freqs, self.csize, self.params["target"]["dist"])
+        return vis_scales(freqs, self.csize, self.params["target"]["dist"])
 
     def _vis_chunk(self, maps_per_epoch):
         """Epochs per chunk of a sweep so that the map stack stays under VIS_STACK_BYTES."""
         per = int(maps_per_epoch) * self.nx * self.nz * 8
         return max(1, self.VIS_STACK_BYTES // per)
+
+    @property
+    def _imager(self):
+        """`imaging.Imager` on this model's grid, made at every use: VIS_STACK_BYTES as it is then."""
+        return Imager(self.engine, self.nx, self.nz, self.csize, self.params["target"]["dist"],
+                      self.VIS_STACK_BYTES)
+
+    def _flux_maps(self, freqs, rrl=None, contsub=True, formal=False):
+        """The `flux_ff` maps, or with `rrl` the `flux_rrl` maps -> device stack [F, nx * nz]."""
+        if rrl is None:
+            maps = self._ff_products(freqs, flux=True, device=True, formal=formal)
+        else:
+            maps = self._rrl_flux(rrl, freqs, True, contsub, formal=formal, device=True)
+        return maps.reshape(len(freqs), -1)
+
+    def _model_vis(self, u_m, v_m, freq, weighting=None, maps=True, **which):
+        """What the `visibilities_*`, `dirty_*` and `clean_image_*` methods start with -> (the
+        imager, V, u_d, v_d, freqs), the last four as its methods take them, on the device: V the
+        model visibilities [F, K] of `_flux_maps(freqs, **which)`; None without `maps`."""
+        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
+        _weighting_mode(weighting)            # (refuses an unknown scheme before any work)
+        im = self._imager
+        u_d, v_d = im.engine._device_f64(u_m), im.engine._device_f64(v_m)
+        V = im.model_vis(self._flux_maps(freqs, **which), freqs, u_d, v_d) if maps else None
+        return im, V, u_d, v_d, freqs
+
+    def _observe(self, which, antennalist, freq, t_obs_s, t_int_s, min_el_deg, hourangle_h, *args):
+        """`observe_ff` / `observe_rrl`: the tracks and the maps `_flux_maps(freqs, **which)`, then
+        `Imager._observe` with `args`, the noise and imaging arguments in its order."""
+        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
+        tracks = antennalist if isinstance(antennalist, UVTracks) else \
+            self.uv_tracks(antennalist, t_obs_s, t_int_s, min_el_deg, hourangle_h)
+        return self._imager._observe(self._flux_maps(freqs, **which), freqs, tracks, t_int_s, *args)
 
     def visibilities_ff(self, u_m, v_m, freq, formal=False):
         """Noise-free model visibilities [Jy] of the `flux_ff` maps at the model's time, at the
@@ -1041,20 +998,13 @@ class JetModel:
         `engine.vis_scales` -- phase centre = map centre, RA decreasing with ix); the maps stay on
         the device.  V(0, 0) is the total flux `flux_vs_time` returns.  `formal`: as `flux_ff`.
         Inside a torch.distributed group the call runs on the calling rank only."""
-        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
-        maps = self._ff_products(freqs, flux=True, device=True, formal=formal)
-        su, sv = self._vis_scales(freqs)
-        return self.engine.vis(maps.reshape(len(freqs), -1), self.nx, self.nz, su, sv,
-                               u_m, v_m).cpu().numpy()
+        return self._model_vis(u_m, v_m, freq, formal=formal)[1].cpu().numpy()
 
     def visibilities_rrl(self, rrl, u_m, v_m, freq, contsub=True, formal=False):
         """Model visibilities [Jy] of the `flux_rrl` maps (same arguments) -> complex (F, K); see
         `visibilities_ff`."""
-        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
-        maps = self._rrl_flux(rrl, freqs, True, contsub, formal=formal, device=True)
-        su, sv = self._vis_scales(freqs)
-        return self.engine.vis(maps.reshape(len(freqs), -1), self.nx, self.nz, su, sv,
-                               u_m, v_m).cpu().numpy()
+        V = self._model_vis(u_m, v_m, freq, rrl=rrl, contsub=contsub, formal=formal)[1]
+        return V.cpu().numpy()
 
     def visibilities_vs_time(self, times_s, u_m, v_m, freq, formal=False):
         """Model visibilities [Jy] of the continuum at every (model time, frequency, baseline)
@@ -1135,94 +1085,6 @@ class JetModel:
         return V, dV
 
     # ------------------------------------------------------------------ dirty images ----
-    def _image_grid(self, shape, cell_as):
-        """(ni, nj, cell [rad]) of an imaging grid: the model's own by default."""
-        ni, nj = (self.nx, self.nz) if shape is None else (int(shape[0]), int(shape[1]))
-        if ni < 1 or nj < 1:
-            raise ValueError("dirty image: `shape` must be two positive sizes")
-        if cell_as is None:
-            cell = np.arctan((self.csize * con.au) / (self.params["target"]["dist"] * con.parsec))
-        else:
-            cell = np.radians(float(cell_as) / 3600.)
-            if not (np.isfinite(cell) and cell > 0.):
-                raise ValueError("dirty image: `cell_as` must be a positive number of arcseconds")
-        return ni, nj, float(cell)
-
-    def _dirty_images(self, V, u_d, v_d, freqs, weights, shape, cell_as, mfs, device=False,
-                      weighting=None, robust=0.5, iw=None):
-        """Dirty images [Jy / beam] of the visibilities `V` (complex device tensor [F, K]) at the
-        baselines (`u_d`, `v_d`) [m] -> host array (F, ni, nj), or (1, ni, nj) with `mfs`;
-        `device=True`: the same numbers as a device tensor [F or 1, ni * nj] (for `_clean_images`).
-        `RTEngine.vis_adjoint` on chunks of channels whose images stay under VIS_STACK_BYTES
-        (K10's `_vis_chunk` rule on the imaging grid), divided by the sum of the weights of the
-        baselines that are not flagged; nothing but the images leaves the device.
-        `weighting` "uniform" / "briggs" (with `robust`): the imaging weights of every chunk come
-        from ONE `RTEngine.uv_weights` call on this image's grid, a density per channel (one over
-        all F K points with `mfs`), are multiplied into V on the device and the image is divided
-        by the channel's own sum of them; the chunks then also keep the [F, K] weights under
-        VIS_STACK_BYTES.  `iw`: those weights already made ([F, K], or [1, F K] with `mfs`: what
-        `_clean_images` shares between the image and the larger beam grid)."""
-        import torch
-        from . import engine as E
-        eng = self.engine
-        ni, nj, cell = self._image_grid(shape, cell_as)
-        su, sv = E.image_scales(freqs, cell)
-        F, K = int(V.shape[0]), int(V.shape[1])
-        w_d = eng._device_f64(weights) if weights is not None else None
-        if w_d is not None and w_d.numel() != K:
-            raise ValueError("dirty image: `weights` must have one entry per baseline (%d)" % K)
-        mode = _weighting_mode(weighting)
-        if mode is not None or iw is not None:
-            if mfs:
-                if iw is None:
-                    iw = _imaging_weights(eng, u_d, v_d, su, sv, w_d, ni, nj, mode, robust, True)
-                img = eng.vis_adjoint((V.reshape(1, F * K) * iw).contiguous(), ni, nj, [1.0], [1.0],
-                                      (_col(eng, su) * u_d[None, :]).reshape(-1),
-                                      (_col(eng, sv) * v_d[None, :]).reshape(-1), None)
-                img = img / iw.sum()
-                return img if device else img.cpu().numpy().reshape(1, ni, nj)
-            out = [] if device else np.zeros((F, ni, nj))
-            step = max(1, min(self.VIS_STACK_BYTES // (ni * nj * 8), self.VIS_STACK_BYTES // (K * 8)))
-            for f0 in range(0, F, step):
-                sl = slice(f0, f0 + step)
-                wc = iw[sl] if iw is not None else _imaging_weights(
-                    eng, u_d, v_d, su[sl], sv[sl], w_d, ni, nj, mode, robust, False)
-                img = eng.vis_adjoint((V[sl] * wc).contiguous(), ni, nj, su[sl], sv[sl], u_d, v_d,
-                                      None)
-                img = img / wc.sum(dim=1)[:, None]
-                if device:
-                    out.append(img)
-                else:
-                    out[sl] = img.cpu().numpy().reshape(-1, ni, nj)
-                del img, wc
-            return torch.cat(out, dim=0) if device else out
-        good = torch.isfinite(u_d) & torch.isfinite(v_d)
-        if w_d is not None:
-            good = good & torch.isfinite(w_d)
-        wsum = (torch.where(good, w_d, torch.zeros_like(w_d)).sum() if w_d is not None
-                else good.sum().to(torch.float64))
-        if mfs:
-            # one visibility set of F K points, baselines in cycles per cell, scale 1
-            dsu = torch.from_numpy(np.ascontiguousarray(su)).to(eng.device)
-            dsv = torch.from_numpy(np.ascontiguousarray(sv)).to(eng.device)
-            ua = (dsu[:, None] * u_d[None, :]).reshape(-1)
-            va = (dsv[:, None] * v_d[None, :]).reshape(-1)
-            wa = w_d.repeat(F) if w_d is not None else None
-            img = eng.vis_adjoint(V.reshape(1, F * K), ni, nj, [1.0], [1.0], ua, va, wa)
-            img = img / (wsum * F)
-            return img if device else img.cpu().numpy().reshape(1, ni, nj)
-        out = [] if device else np.zeros((F, ni, nj))
-        step = max(1, self.VIS_STACK_BYTES // (ni * nj * 8))
-        for f0 in range(0, F, step):
-            img = eng.vis_adjoint(V[f0:f0 + step].contiguous(), ni, nj, su[f0:f0 + step],
-                                  sv[f0:f0 + step], u_d, v_d, w_d)
-            if device:
-                out.append(img / wsum)
-            else:
-                out[f0:f0 + step] = (img / wsum).cpu().numpy().reshape(-1, ni, nj)
-            del img
-        return torch.cat(out, dim=0) if device else out
-
     def dirty_image_ff(self, u_m, v_m, freq, weights=None, shape=None, cell_as=None, formal=False,
                        mfs=False):
         """Dirty images [Jy / beam] of the `flux_ff` maps as an array with the baselines (`u_m`,
@@ -1246,29 +1108,16 @@ class JetModel:
         the grid's Fourier cells (more than half a cycle per cell) or with a negative weight is
         then flagged too.  A plain array, None or scheme "natural" is the natural weighting.
         Calling rank only."""
-        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
-        eng = self.engine
         weights, weighting, robust = _split_weights(weights)
-        u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
-        maps = self._ff_products(freqs, flux=True, device=True, formal=formal)
-        su, sv = self._vis_scales(freqs)
-        V = eng.vis(maps.reshape(len(freqs), -1), self.nx, self.nz, su, sv, u_d, v_d)
-        return self._dirty_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs,
-                                  weighting=weighting, robust=robust)
+        im, *vis = self._model_vis(u_m, v_m, freq, weighting, formal=formal)
+        return im._dirty_images(*vis, weights, shape, cell_as, mfs, weighting=weighting, robust=robust)
 
     def dirty_image_rrl(self, rrl, u_m, v_m, freq, weights=None, shape=None, cell_as=None,
                         contsub=True, formal=False, mfs=False, weighting=None, robust=0.5):
         """Dirty images [Jy / beam] of the `flux_rrl` maps (same arguments) -> (F, ni, nj); see
         `dirty_image_ff`.  `weighting`: None / "natural", "uniform" or "briggs" (with `robust`)."""
-        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
-        eng = self.engine
-        _weighting_mode(weighting)            # (refuses an unknown scheme before any work)
-        u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
-        maps = self._rrl_flux(rrl, freqs, True, contsub, formal=formal, device=True)
-        su, sv = self._vis_scales(freqs)
-        V = eng.vis(maps.reshape(len(freqs), -1), self.nx, self.nz, su, sv, u_d, v_d)
-        return self._dirty_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs,
-                                  weighting=weighting, robust=robust)
+        im, *vis = self._model_vis(u_m, v_m, freq, weighting, rrl=rrl, contsub=contsub, formal=formal)
+        return im._dirty_images(*vis, weights, shape, cell_as, mfs, weighting=weighting, robust=robust)
 
     def dirty_beam(self, u_m, v_m, freq, weights=None, shape=None, cell_as=None, mfs=False,
                    weighting=None, robust=0.5):
@@ -1278,15 +1127,9 @@ class JetModel:
         is 1 (to the last bit with unit weights); it is symmetric under point reflection.
         `weighting`, `robust`: as `dirty_image_rrl`; the weights are those of an IMAGE on this
         grid."""
-        import torch
-        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
-        eng = self.engine
-        _weighting_mode(weighting)            # (refuses an unknown scheme before any work)
-        u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
-        V = torch.zeros(len(freqs), int(u_d.numel()), 2, dtype=torch.float64, device=eng.device)
-        V[..., 0] = 1.0
-        return self._dirty_images(torch.view_as_complex(V), u_d, v_d, freqs, weights, shape,
-                                  cell_as, mfs, weighting=weighting, robust=robust)
+        im, _, u_d, v_d, freqs = self._model_vis(u_m, v_m, freq, weighting, maps=False)
+        return im._dirty_images(im._unit_vis(len(freqs), int(u_d.numel())), u_d, v_d, freqs, weights,
+                                shape, cell_as, mfs, weighting=weighting, robust=robust)
 
     def imaging_weights(self, u_m, v_m, freq, weights=None, shape=None, cell_as=None,
                         weighting="briggs", robust=0.5, mfs=False):
@@ -1300,155 +1143,10 @@ class JetModel:
         sqrt(sum(w'^2 / w) sum(w)) / sum(w') over the counted visibilities with w > 0: the
         thermal rms relative to natural weighting, >= 1.  "natural" / None returns the data
         weights with the flagged ones set to 0 and a factor of 1."""
-        import torch
-        from . import engine as E
-        eng = self.engine
-        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
-        _weighting_mode(weighting)            # (refuses an unknown scheme before any work)
-        mode = _weighting_mode(weighting)
-        ni, nj, cell = self._image_grid(shape, cell_as)
-        su, sv = E.image_scales(freqs, cell)
-        u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
-        F, K = len(freqs), int(u_d.numel())
-        w_d = eng._device_f64(weights) if weights is not None else None
-        if v_d.numel() != K or (w_d is not None and w_d.numel() != K):
-            raise ValueError("imaging weights: u, v and weights must have one entry per baseline")
-        w1 = w_d if w_d is not None else torch.ones(K, dtype=torch.float64, device=eng.device)
-        names = ("sum_w", "sum_w2", "f2", "counted", "out_of_range", "shift")
-        if mode is None:
-            ok = torch.isfinite(u_d) & torch.isfinite(v_d) & torch.isfinite(w1) & (w1 >= 0)
-            row = torch.where(ok, w1, torch.zeros_like(w1)).cpu().numpy()
-            n = 1 if mfs else F
-            st = {k: np.zeros(n) for k in names}
-            st["sum_w"][:] = row.sum() * (F if mfs else 1)
-            st["counted"][:] = np.count_nonzero(ok.cpu().numpy()) * (F if mfs else 1)
-            st["sum_wout"], st["noise_factor"] = st["sum_w"].copy(), np.ones(n)
-            return np.tile(row, (F, 1)), st
-        out, stats, extra = np.zeros((F, K)), [], []
-        step = F if mfs else max(1, self.VIS_STACK_BYTES // (K * 8))
-        for f0 in range(0, F, step):
-            sl = slice(f0, f0 + step)
-            iw = _imaging_weights(eng, u_d, v_d, su[sl], sv[sl], w_d, ni, nj, mode, robust, mfs)
-            wd = w1.repeat(F)[None, :] if mfs else w1[None, :]
-            live = (iw > 0) & (wd > 0)
-            ratio = torch.where(live, iw * iw / torch.where(live, wd, torch.ones_like(wd)),
-                                torch.zeros_like(iw))
-            extra.append(torch.stack([iw.sum(dim=1), ratio.sum(dim=1),
-                                      torch.where(live, wd.expand_as(iw), torch.zeros_like(iw))
-                                      .sum(dim=1)], dim=1).cpu().numpy())
-            stats.append(eng.last_uv_weight_stats.cpu().numpy())
-            out[sl] = iw.cpu().numpy().reshape(-1, K)
-            del iw
-        stats, extra = np.concatenate(stats, axis=0), np.concatenate(extra, axis=0)
-        st = {k: stats[:, i].copy() for i, k in enumerate(names)}
-        st["sum_wout"] = extra[:, 0]
-        with np.errstate(invalid="ignore", divide="ignore"):
-            st["noise_factor"] = np.sqrt(extra[:, 1] * extra[:, 2]) / extra[:, 0]
-        return out, st
+        return self._imager.imaging_weights(u_m, v_m, freq, weights, shape, cell_as, weighting,
+                                            robust, mfs)
 
     # ------------------------------------------------------------------ CLEAN ----
-    BEAM_PATCH = 33          # side of the central patch of the dirty beam that `fit_beam` sees
-
-    def _clean_mask(self, mask, ni, nj):
-        """None, a box (i0, i1, j0, j1) of inclusive pixel corners (as the reference hands
-        tclean a box) or a boolean array (ni, nj) -> None or a bool array (ni, nj)."""
-        if mask is None:
-            return None
-        m = np.asarray(mask)
-        if m.ndim == 1 and m.size == 4:
-            i0, i1, j0, j1 = (int(x) for x in m)
-            if not (0 <= i0 <= i1 < ni and 0 <= j0 <= j1 < nj):
-                raise ValueError("clean: the box (i0, i1, j0, j1) must lie inside the image")
-            out = np.zeros((ni, nj), dtype=bool)
-            out[i0:i1 + 1, j0:j1 + 1] = True
-            return out
-        if m.shape != (ni, nj):
-            raise ValueError("clean: `mask` must be None, a box (i0, i1, j0, j1) or an array of "
-                             "the image's shape (%d, %d)" % (ni, nj))
-        return m != 0
-
-    def _clean_images(self, V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
-                      threshold_jy, mask, beam, psf_shape, imfit=None, weighting=None, robust=0.5):
-        """Hogbom CLEAN of the dirty images of `V` (see `clean_image_ff`), in chunks of channels
-        whose dirty images AND beams stay under VIS_STACK_BYTES.  Per chunk, on the device:
-        `_dirty_images` of V and of unit visibilities (the beams, on the `psf_shape` grid),
-        `RTEngine.clean`, `RTEngine.restore`; only the central patch of each beam goes to the
-        host before the end (for `fit_beam`).  With `weighting` "uniform" / "briggs" the chunk's
-        imaging weights are computed ONCE, on the image's grid (never the larger beam grid), and
-        image and beam share them; the chunks then also keep the [F, K] weights under
-        VIS_STACK_BYTES."""
-        import torch
-        from . import engine as E
-        eng = self.engine
-        ni, nj, cell = self._image_grid(shape, cell_as)
-        pi_, pj = (2 * ni - 1, 2 * nj - 1) if psf_shape is None else (int(psf_shape[0]),
-                                                                      int(psf_shape[1]))
-        if pi_ < 1 or pj < 1 or pi_ % 2 == 0 or pj % 2 == 0:
-            raise ValueError("clean: `psf_shape` must be two odd positive sizes")
-        niter = int(niter)
-        # (one threshold, or one per image: what `observe_ff` derives from each image's own rms)
-        thr = np.asarray(threshold_jy, dtype=np.float64).reshape(-1)
-        if niter < 1 or not (0. < float(gain) <= 1.) or not np.all(thr >= 0.) or \
-                thr.size not in (1, 1 if mfs else int(V.shape[0])):
-            raise ValueError("clean: niter >= 1, 0 < gain <= 1 and threshold_jy >= 0")
-        mk = self._clean_mask(mask, ni, nj)
-        F, K = int(V.shape[0]), int(V.shape[1])
-        n_out = 1 if mfs else F
-        ones = torch.zeros(F, K, 2, dtype=torch.float64, device=eng.device)
-        ones[..., 0] = 1.0
-        ones = torch.view_as_complex(ones)
-        fit_opts = self._imfit_options(imfit, mask, ni, nj)
-        res = CleanResult(image=np.zeros((n_out, ni, nj)), residual=np.zeros((n_out, ni, nj)),
-                          model=np.zeros((n_out, ni, nj)), components=[], beam=[],
-                          peak_residual=np.zeros(n_out), imfit=None if fit_opts is None else [])
-        step = F if mfs else max(1, self.VIS_STACK_BYTES // ((ni * nj * 3 + pi_ * pj) * 8))
-        hi, hj = min(self.BEAM_PATCH, pi_) // 2, min(self.BEAM_PATCH, pj) // 2
-        mode = _weighting_mode(weighting)
-        if mode is not None:
-            w_d = eng._device_f64(weights) if weights is not None else None
-            if w_d is not None and w_d.numel() != K:
-                raise ValueError("dirty image: `weights` must have one entry per baseline (%d)" % K)
-            if not mfs:
-                step = max(1, min(step, self.VIS_STACK_BYTES // (K * 8)))
-        for f0 in range(0, F, step):
-            sl = slice(f0, f0 + step)
-            iw = None
-            if mode is not None:
-                isu, isv = E.image_scales(freqs[sl], cell)
-                iw = _imaging_weights(eng, u_d, v_d, isu, isv, w_d, ni, nj, mode, robust, mfs)
-            dirty = self._dirty_images(V[sl], u_d, v_d, freqs[sl], weights, (ni, nj), cell_as,
-                                       mfs, device=True, iw=iw)
-            psf = self._dirty_images(ones[sl], u_d, v_d, freqs[sl], weights, (pi_, pj), cell_as,
-                                     mfs, device=True, iw=iw)
-            del iw
-            M = int(dirty.shape[0])
-            if beam is None:
-                ci, cj = (pi_ - 1) // 2, (pj - 1) // 2
-                patch = psf.reshape(M, pi_, pj)[:, ci - hi:ci + hi + 1, cj - hj:cj + hj + 1]
-                abc = [E.fit_beam(p) for p in patch.cpu().numpy()]
-            else:
-                abc = [E.beam_quadratic(beam[0], beam[1], beam[2], cell)] * M
-            model = torch.zeros_like(dirty)
-            cpix, cflux, ncomp, peak = eng.clean(dirty, ni, nj, psf, pi_, pj, niter, gain,
-                                                 float(thr[0]) if thr.size == 1 else thr[f0:f0 + M],
-                                                 mask=mk, model=model)
-            image = eng.restore(cpix, cflux, ncomp, abc, ni, nj, add=dirty)
-            o = slice(f0, f0 + M)
-            if fit_opts is not None:
-                res.imfit.extend(self._imfit_images(image, ni, nj, abc, cell, fit_opts, o))
-            res.image[o] = image.cpu().numpy().reshape(M, ni, nj)
-            res.residual[o] = dirty.cpu().numpy().reshape(M, ni, nj)
-            res.model[o] = model.cpu().numpy().reshape(M, ni, nj)
-            res.peak_residual[o] = peak.cpu().numpy()
-            hp, hf, hn = cpix.cpu().numpy(), cflux.cpu().numpy(), ncomp.cpu().numpy()
-            for m in range(M):
-                n = int(hn[m])
-                res.components.append(np.stack([hp[m, :n] // nj, hp[m, :n] % nj, hf[m, :n]],
-                                               axis=1).astype(np.float64).reshape(n, 3))
-                res.beam.append(E.beam_from_quadratic(*abc[m], cell))
-            del dirty, psf, model, image, cpix, cflux, ncomp, peak
-        return res
-
     def clean_image_ff(self, u_m, v_m, freq, weights=None, shape=None, cell_as=None, formal=False,
                        mfs=False, niter=500, gain=0.1, threshold_jy=0.0, mask=None, beam=None,
                        psf_shape=None, imfit=None, weighting=None, robust=0.5):
@@ -1478,16 +1176,9 @@ class JetModel:
         weights from the (u, v) density on the IMAGE's grid (`RTEngine.uv_weights`), one density
         per channel (one over all channels with `mfs`), shared by the image and its beam;
         `weights` are the data weights the scheme starts from (see `dirty_image_ff`)."""
-        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
-        eng = self.engine
-        _weighting_mode(weighting)            # (refuses an unknown scheme before any work)
-        u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
-        maps = self._ff_products(freqs, flux=True, device=True, formal=formal)
-        su, sv = self._vis_scales(freqs)
-        V = eng.vis(maps.reshape(len(freqs), -1), self.nx, self.nz, su, sv, u_d, v_d)
-        return self._clean_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
-                                  threshold_jy, mask, beam, psf_shape, imfit, weighting=weighting,
-                                  robust=robust)
+        im, *vis = self._model_vis(u_m, v_m, freq, weighting, formal=formal)
+        return im._clean_images(*vis, weights, shape, cell_as, mfs, niter, gain, threshold_jy, mask,
+                                beam, psf_shape, imfit, weighting=weighting, robust=robust)
 
     def clean_image_rrl(self, rrl, u_m, v_m, freq, weights=None, shape=None, cell_as=None,
                         contsub=True, formal=False, mfs=False, niter=500, gain=0.1,
@@ -1495,16 +1186,9 @@ class JetModel:
                         weighting=None, robust=0.5):
         """CLEANed, restored images of the `flux_rrl` maps (same arguments) -> `CleanResult`; see
         `clean_image_ff`."""
-        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
-        eng = self.engine
-        _weighting_mode(weighting)            # (refuses an unknown scheme before any work)
-        u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
-        maps = self._rrl_flux(rrl, freqs, True, contsub, formal=formal, device=True)
-        su, sv = self._vis_scales(freqs)
-        V = eng.vis(maps.reshape(len(freqs), -1), self.nx, self.nz, su, sv, u_d, v_d)
-        return self._clean_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
-                                  threshold_jy, mask, beam, psf_shape, imfit, weighting=weighting,
-                                  robust=robust)
+        im, *vis = self._model_vis(u_m, v_m, freq, weighting, rrl=rrl, contsub=contsub, formal=formal)
+        return im._clean_images(*vis, weights, shape, cell_as, mfs, niter, gain, threshold_jy, mask,
+                                beam, psf_shape, imfit, weighting=weighting, robust=robust)
 
     # ------------------------------------------------------------------ synthetic observations ----
     def uv_tracks(self, antennalist, t_obs_s, t_int_s, min_el_deg=None, hourangle_h=0.):
@@ -1523,77 +1207,9 @@ class JetModel:
         (`RTEngine.uv_tracks`, rjp_uv_tracks); `ha_h` [n_t] (hours) and `day` [n_t]: host arrays
         per integration; `ant1`, `ant2` [n_bl]: the antennas of baseline b = xyz[ant2] -
         xyz[ant1]; `max_baseline_m`.  Calling rank only."""
-        from . import engine as E
-        cfg = antennalist if isinstance(antennalist, E.AntennaConfig) else \
-            E.read_antenna_config(antennalist)
-        geo = E.geodetic(cfg.xyz)
         tg = self.params['target']
-        _, dec_deg = miscf.sexagesimal_to_deg(tg['ra'], tg['dec'])
-        ha, day = E.observing_plan(dec_deg, geo.lat0_deg, t_obs_s, t_int_s,
-                                   0. if min_el_deg is None else min_el_deg, hourangle_h)
-        flags = dict(up=geo.up, min_el_rad=np.radians(min_el_deg)) if min_el_deg is not None else {}
-        u, v, w = self.engine.uv_tracks(cfg.xyz, ha - geo.lon0_deg / 360., np.radians(dec_deg),
-                                        **flags)
-        a1, a2 = np.triu_indices(len(cfg.names), 1)
-        bmax = float(np.sqrt(((cfg.xyz[a2] - cfg.xyz[a1]) ** 2).sum(axis=1)).max())
-        return UVTracks(u.reshape(-1), v.reshape(-1), w.reshape(-1), ha * 24., day,
-                        a1.astype(np.int32), a2.astype(np.int32), bmax)
-
-    def _observe(self, maps, freqs, tracks, t_int_s, sigma_jy, sefd_jy, chanwidth_hz, seed,
-                 nsigma, img):
-        """`observe_ff` / `observe_rrl` after the maps: visibilities, noise, image rms, CLEAN."""
-        import torch
-        from . import engine as E
-        eng = self.engine
-        F = len(freqs)
-        if sigma_jy is not None and sefd_jy is not None:
-            raise ValueError("observe: give `sigma_jy` or `sefd_jy`, not both")
-        if sefd_jy is not None:
-            if chanwidth_hz is None:
-                raise ValueError("observe: `sefd_jy` needs `chanwidth_hz`")
-            sigma_jy = E.thermal_sigma(sefd_jy, chanwidth_hz, t_int_s)
-        sigma = np.asarray(0. if sigma_jy is None else sigma_jy, dtype=np.float64).reshape(-1)
-        if sigma.size not in (1, F) or not np.all(np.isfinite(sigma) & (sigma >= 0.)):
-            raise ValueError("observe: `sigma_jy` must be one finite rms >= 0 or one per channel")
-        sigma = np.broadcast_to(sigma, (F,)).copy()
-        if not (float(nsigma) >= 0.):
-            raise ValueError("observe: `nsigma` must be >= 0")
-        u_d, v_d = tracks.u_m, tracks.v_m
-        su, sv = self._vis_scales(freqs)
-        V0 = eng.vis(maps.reshape(F, -1), self.nx, self.nz, su, sv, u_d, v_d)
-        noisy = bool(np.any(sigma > 0.))
-        # (every visibility has its own counter k = t n_bl + b: an independent draw per day,
-        # integration, baseline and channel)
-        V = eng.vis_noise(V0, sigma, seed=seed) if noisy else V0
-        mfs = img["mfs"]
-        rms = np.zeros(1 if mfs else F)
-        if noisy:
-            iw, _ = self.imaging_weights(u_d, v_d, freqs, weights=img["weights"], shape=img["shape"],
-                                         cell_as=img["cell_as"], weighting=img["weighting"],
-                                         robust=img["robust"], mfs=mfs)
-            rms = E.image_rms(iw.reshape(1, -1), np.repeat(sigma, iw.shape[1])) if mfs else \
-                E.image_rms(iw, sigma[:, None])
-            del iw
-        thr = img["threshold_jy"]
-        if float(nsigma) > 0.:
-            thr = np.maximum(float(thr), float(nsigma) * np.where(np.isfinite(rms), rms, 0.))
-        fit = img["imfit"]
-        if fit is not None and fit is not False and noisy:
-            fit = {} if fit is True else dict(fit)
-            if fit.get("rms") is None:
-                fit["rms"] = rms
-        res = self._clean_images(V, u_d, v_d, freqs, img["weights"], img["shape"], img["cell_as"],
-                                 mfs, img["niter"], img["gain"], thr, img["mask"], img["beam"],
-                                 img["psf_shape"], fit, weighting=img["weighting"],
-                                 robust=img["robust"])
-        host = lambda t: t.cpu().numpy()
-        v0 = host(V0)
-        return Observation(tracks, v0, host(V) if noisy else v0.copy(), sigma, rms, res)
-
-    def _tracks_of(self, antennalist, t_obs_s, t_int_s, min_el_deg, hourangle_h):
-        if isinstance(antennalist, UVTracks):
-            return antennalist
-        return self.uv_tracks(antennalist, t_obs_s, t_int_s, min_el_deg, hourangle_h)
+        return self._imager.uv_tracks(antennalist, miscf.sexagesimal_to_deg(tg['ra'], tg['dec'])[1],
+                                      t_obs_s, t_int_s, min_el_deg, hourangle_h)
 
     def observe_ff(self, antennalist, freq, t_obs_s, t_int_s, min_el_deg=None, hourangle_h=0.,
                    sigma_jy=None, sefd_jy=None, chanwidth_hz=None, seed=0, nsigma=0.,
@@ -1617,15 +1233,11 @@ class JetModel:
         threshold of every image is max(threshold_jy, nsigma image_rms), tclean's `nsigma` with
         the analytic rms in place of CASA's robust estimate.  With `imfit` and noise, `image_rms`
         is the fit's default `rms`.  Calling rank only."""
-        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
         _weighting_mode(weighting)            # (refuses an unknown scheme before any work)
-        tracks = self._tracks_of(antennalist, t_obs_s, t_int_s, min_el_deg, hourangle_h)
-        maps = self._ff_products(freqs, flux=True, device=True, formal=formal)
-        img = dict(weights=weights, shape=shape, cell_as=cell_as, mfs=mfs, niter=niter, gain=gain,
-                   threshold_jy=threshold_jy, mask=mask, beam=beam, psf_shape=psf_shape,
-                   imfit=imfit, weighting=weighting, robust=robust)
-        return self._observe(maps, freqs, tracks, t_int_s, sigma_jy, sefd_jy, chanwidth_hz, seed,
-                             nsigma, img)
+        return self._observe(dict(formal=formal), antennalist, freq, t_obs_s, t_int_s, min_el_deg,
+                             hourangle_h, sigma_jy, sefd_jy, chanwidth_hz, seed, nsigma, weights,
+                             shape, cell_as, mfs, niter, gain, threshold_jy, mask, beam, psf_shape,
+                             imfit, weighting, robust)
 
     def observe_rrl(self, rrl, antennalist, freq, t_obs_s, t_int_s, min_el_deg=None,
                     hourangle_h=0., sigma_jy=None, sefd_jy=None, chanwidth_hz=None, seed=0,
@@ -1633,67 +1245,13 @@ class JetModel:
                     mfs=False, niter=500, gain=0.1, threshold_jy=0.0, mask=None, beam=None,
                     psf_shape=None, imfit=None, weighting=None, robust=0.5):
         """A synthetic observation of the `flux_rrl` maps -> `Observation`; see `observe_ff`."""
-        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
         _weighting_mode(weighting)            # (refuses an unknown scheme before any work)
-        tracks = self._tracks_of(antennalist, t_obs_s, t_int_s, min_el_deg, hourangle_h)
-        maps = self._rrl_flux(rrl, freqs, True, contsub, formal=formal, device=True)
-        img = dict(weights=weights, shape=shape, cell_as=cell_as, mfs=mfs, niter=niter, gain=gain,
-                   threshold_jy=threshold_jy, mask=mask, beam=beam, psf_shape=psf_shape,
-                   imfit=imfit, weighting=weighting, robust=robust)
-        return self._observe(maps, freqs, tracks, t_int_s, sigma_jy, sefd_jy, chanwidth_hz, seed,
-                             nsigma, img)
+        return self._observe(dict(rrl=rrl, contsub=contsub, formal=formal), antennalist, freq,
+                             t_obs_s, t_int_s, min_el_deg, hourangle_h, sigma_jy, sefd_jy,
+                             chanwidth_hz, seed, nsigma, weights, shape, cell_as, mfs, niter, gain,
+                             threshold_jy, mask, beam, psf_shape, imfit, weighting, robust)
 
     # ------------------------------------------------------------------ imfit ----
-    def _imfit_options(self, imfit, mask, ni, nj):
-        """The `imfit` keyword of `clean_image_*` / `imfit` -> None or a dict (box, theta0,
-        n_iter, rms); the default box is the bounding box of `mask` (as `_clean_mask` reads it)."""
-        if imfit is None or imfit is False:
-            return None
-        opts = {} if imfit is True else dict(imfit)
-        bad = set(opts) - {"box", "theta0", "n_iter", "rms"}
-        if bad:
-            raise ValueError("imfit: unknown option(s) %s" % sorted(bad))
-        box = opts.get("box")
-        if box is None:
-            mk = self._clean_mask(mask, ni, nj)
-            if mk is not None and mk.any():
-                ii, jj = np.nonzero(mk)
-                box = (int(ii.min()), int(ii.max()), int(jj.min()), int(jj.max()))
-            else:
-                box = (0, ni - 1, 0, nj - 1)
-        box = tuple(int(x) for x in np.ravel(box))
-        if len(box) != 4 or not (0 <= box[0] <= box[1] < ni and 0 <= box[2] <= box[3] < nj):
-            raise ValueError("imfit: the box (i0, i1, j0, j1) must lie inside the image")
-        return {"box": box, "theta0": opts.get("theta0"), "n_iter": int(opts.get("n_iter", 60)),
-                "rms": opts.get("rms")}
-
-    def _imfit_images(self, image, ni, nj, abc, cell, opts, sl=None):
-        """One Gaussian per image of the device stack `image` [M, ni * nj] (`RTEngine.gaussfit`)
-        -> list of M dicts (`engine.gauss_results`).  `abc`: the clean beams, one per map; `sl`:
-        the rows of a `theta0` / `rms` given per map that belong to this stack."""
-        from . import engine as E
-        eng = self.engine
-        M = int(image.shape[0])
-        import torch
-
-        def pick(a, w):
-            # (a start or an rms per map: a host array or a tensor; else one for all)
-            if a is None or sl is None:
-                return a
-            if isinstance(a, torch.Tensor):
-                return a[sl] if a.dim() >= w else a
-            return np.asarray(a)[sl] if np.ndim(a) >= w else a
-        theta0 = pick(opts["theta0"], 2)
-        if theta0 is None:
-            theta0 = E.gauss_start(image, ni, nj, abc, box=opts["box"])
-        fit = eng.gaussfit(image, ni, nj, theta0, box=opts["box"], n_iter=opts["n_iter"])
-        host = {k: v.cpu().numpy() for k, v in fit.items()}
-        rms = pick(opts["rms"], 1)
-        if isinstance(rms, torch.Tensor):
-            rms = rms.detach().cpu().numpy()
-        return E.gauss_results(host["theta"], host["cov"], host["chi2"], host["npix"], abc, cell,
-                               rms=rms, shape=(ni, nj), status=host["status"])
-
     def imfit(self, images, beam, cell_as=None, box=None, theta0=None, n_iter=60, rms=None):
         """One elliptical Gaussian fitted to each of `images` -- (F, ni, nj) or (ni, nj), a host
         array or a device tensor, such as a `CleanResult.image` -- on the device
@@ -1702,26 +1260,7 @@ class JetModel:
         (bmaj_as, bmin_as, bpa_deg), one or one per image (`CleanResult.beam`); `cell_as`: the
         cell in arcsec, None = the model's; `box`, `theta0`, `n_iter`, `rms` as the `imfit`
         keyword of `clean_image_ff`.  Calling rank only."""
-        import torch
-        from . import engine as E
-        eng = self.engine
-        if isinstance(images, torch.Tensor):
-            img = images.to(device=eng.device, dtype=torch.float64)
-        else:
-            img = torch.from_numpy(np.ascontiguousarray(images, dtype=np.float64)).to(eng.device)
-        if img.dim() == 2:
-            img = img.unsqueeze(0)
-        if img.dim() != 3:
-            raise ValueError("imfit: `images` must be (F, ni, nj) or (ni, nj)")
-        M, ni, nj = (int(x) for x in img.shape)
-        _, _, cell = self._image_grid((ni, nj), cell_as)
-        beams = np.asarray(beam, dtype=np.float64).reshape(-1, 3)
-        if beams.shape[0] not in (1, M):
-            raise ValueError("imfit: `beam` must be one (bmaj_as, bmin_as, bpa_deg) or one per image")
-        abc = [E.beam_quadratic(b[0], b[1], b[2], cell) for b in np.broadcast_to(beams, (M, 3))]
-        opts = self._imfit_options({"box": box, "theta0": theta0, "n_iter": n_iter, "rms": rms},
-                                   None, ni, nj)
-        return self._imfit_images(img.reshape(M, ni * nj).contiguous(), ni, nj, abc, cell, opts)
+        return self._imager.imfit(images, beam, cell_as, box, theta0, n_iter, rms)
 
     # ------------------------------------------------------------------ products ----
     FORMAL_HISTORY ="Formal solution along the line of sight, observer at iy = 0"

@@ -99,10 +99,6 @@ __device__ __forceinline__ ClPeak cl_block_best(ClPeak x, double* s_v, int* s_p)
   return r;
 }
 
-__device__ __forceinline__ bool cl_finite(double x) {
-  return __builtin_fabs(x) <= 1.7976931348623157e308;
-}
-
 // a map's peak from its tiles' partials
 __device__ __forceinline__ ClPeak cl_map_peak(const double* __restrict__ pv,
                                               const int* __restrict__ pp, int tiles, double* s_v,
@@ -156,7 +152,7 @@ __device__ __forceinline__ ClPeak cl_thread_best(const double (&r)[4], const int
   x.pix = -1;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    if (p[j] >= npix || !cl_finite(r[j])) continue;
+    if (p[j] >= npix || !finite_d(r[j])) continue;
     if (mask && mask[p[j]] == 0) continue;
     if (x.pix < 0 || __builtin_fabs(r[j]) > __builtin_fabs(x.v)) {
       x.v = r[j];
@@ -249,7 +245,7 @@ __global__ __launch_bounds__(kClB) void clean_step_kernel(
         // (64-bit: an index plus half a beam of up to 2^31 - 1 rows passes 2^31)
         const int64_t bx = (int64_t)ix - ixs + cx, bz = (int64_t)iz - izs + cz;
         if (p[2 * h + j] < npix && bx >= 0 && bx < px && bz >= 0 && bz < pz &&
-            cl_finite(r[2 * h + j])) {
+            finite_d(r[2 * h + j])) {
           r[2 * h + j] = __builtin_fma(-f, bm[bx * pz + bz], r[2 * h + j]);
           hit = true;
         }

@@ -68,10 +68,6 @@ size_t gaussfit_workspace_bytes(int n_maps, int64_t box_pixels) {
   return n > (unsigned __int128)SIZE_MAX ? 0 : (size_t)n;
 }
 
-__device__ __forceinline__ bool gf_finite(double x) {
-  return __builtin_fabs(x) <= 1.7976931348623157e308;
-}
-
 __device__ __forceinline__ bool gf_posdef(double A, double B, double C) {
   return A > 0.0 && C > 0.0 && A * C > B * B;
 }
@@ -171,14 +167,14 @@ __device__ __forceinline__ bool gf_decide(const double* __restrict__ si, const d
   const double npix = first ? tot[28] : si[11];
   int status = kGfRun;
   bool eval = false;
-  if (first && (!(tot[28] >= 6.0) || !gf_finite(chi_t))) {
+  if (first && (!(tot[28] >= 6.0) || !finite_d(chi_t))) {
     if (store) {
       for (int i = 0; i < kGfS; ++i) so[i] = si[i];
       so[9] = 3.0;
     }
     return false;
   }
-  const bool acc = gf_posdef(si[15], si[16], si[17]) && gf_finite(chi_t) && chi_t < chi_cur;
+  const bool acc = gf_posdef(si[15], si[16], si[17]) && finite_d(chi_t) && chi_t < chi_cur;
   if (acc) {
 #pragma unroll
     for (int i = 0; i < 6; ++i) th[i] = si[12 + i];
@@ -288,7 +284,7 @@ __global__ __launch_bounds__(kGfB) void gaussfit_step_kernel(
       bool good = true;
       for (int i = 0; i < 6; ++i) {
         t0[i] = theta[6 * m + i];
-        good = good && gf_finite(t0[i]);
+        good = good && finite_d(t0[i]);
         s_dec[i] = t0[i];
       }
       good = good && gf_posdef(t0[3], t0[4], t0[5]);
@@ -343,7 +339,7 @@ __global__ __launch_bounds__(kGfB) void gaussfit_step_kernel(
     const int64_t p = (int64_t)ix * nz + iz;
     if (mask && mask[p] == 0) continue;
     const double I = im[p];
-    if (!gf_finite(I)) continue;
+    if (!finite_d(I)) continue;
     const double dx = (double)ix - x0, dz = (double)iz - z0;
     const double xx = dx * dx, xz = dx * dz, zz = dz * dz;
     const double e = -(A * xx + B2 * xz + C * zz);

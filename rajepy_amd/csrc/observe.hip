@@ -31,11 +31,6 @@ int64_t vis_noise_workgroups(int n_maps, int n_vis) {
   return (int64_t)n_maps * (((int64_t)n_vis + kObB - 1) / kObB);
 }
 
-// (a comparison, not x - x == 0: see vis_adjoint.hip)
-__device__ __forceinline__ bool ob_finite(double x) {
-  return __builtin_fabs(x) <= 1.7976931348623157e308;
-}
-
 // pairs before row i of the i-major list of (i < j) pairs of n antennas
 __device__ __forceinline__ int64_t ob_row_start(int64_t i, int64_t n) {
   return i * (2 * n - i - 1) / 2;
@@ -59,7 +54,7 @@ __global__ __launch_bounds__(kObB) void uv_tracks_kernel(
   const double nan = __builtin_nan("");
   double uo = nan, vo = nan, wo = nan;
   const double g0 = gha[t];
-  if (ob_finite(g0)) {
+  if (finite_d(g0)) {
     double sG, cG;
     sincos_2pi(g0 - __builtin_rint(g0), sG, cG);
     bool ok = true;
@@ -130,7 +125,7 @@ __global__ __launch_bounds__(kObB) void vis_noise_kernel(
   double2 val = vis[o];           // (read before the store: d_out may be d_vis)
   const double sk = s ? s[k] : 1.0;
   const double sg = sigma[m];
-  if (!ob_finite(sk)) {
+  if (!finite_d(sk)) {
     val.x = val.y = __builtin_nan("");
   } else if (sg != 0.0) {         // sigma = 0: the bits of the input, -0.0 included
     const uint64_t kk = k0 + (uint64_t)k;

@@ -662,6 +662,12 @@ __device__ __forceinline__ void pow_m1p35_batch(const double (&T)[N], double (&o
   }
 }
 
+// x is neither NaN nor infinite (a comparison, not x - x == 0: contracted with the product that
+// formed x, the difference would be that product's rounding error)
+__device__ __forceinline__ bool finite_d(double x) {
+  return __builtin_fabs(x) <= 1.7976931348623157e308;
+}
+
 __device__ __forceinline__ bool signbit_d(double v) {
   return (__double_as_longlong(v) < 0);
 }

@@ -212,6 +212,13 @@ hipError_t ff_formal_grad_launch(const rjp_fields* fl, const rjp_bursts* hb,
                                  double* work, hipStream_t st);
 
 // ---- vis.hip: visibilities of a stack of maps at given (u, v) points (K10) ----------------------
+// rows per thread of K10's and K11's tiles of 16 row groups -- the two tile alike: (nx + 1) / 2
+// rows would idle in a 128-row tile below this
+static inline int vis_rows_per_thread(int nx) { return nx > 64 ? 8 : 4; }
+// out[m][c] = sum over r < n, in that order, of part[(m n + r) per + c] (K10's row tiles, K11's
+// k-splits); one launch
+hipError_t partial_combine_launch(const double* part, int n_maps, int n, int64_t per, double* out,
+                                  hipStream_t st);
 size_t vis_workspace_bytes(int n_maps, int nx, int nz, int n_vis);
 // false: more workgroups than one launch takes
 bool vis_grid_ok(int n_maps, int nx, int n_vis);

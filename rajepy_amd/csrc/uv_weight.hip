@@ -91,11 +91,6 @@ __device__ __forceinline__ int uvw_shift(unsigned long long wmax_bits, int n_vis
   return 62 - e - L;
 }
 
-// (a comparison, not x - x == 0: see vis_adjoint.hip)
-__device__ __forceinline__ bool uvw_finite(double x) {
-  return __builtin_fabs(x) <= 1.7976931348623157e308;
-}
-
 // The cell of visibility (u, v) of a map with the scales (su, sv): -1 = out of range.  The ONE
 // expression the scale pass, the scatter and the apply pass share.
 __device__ __forceinline__ int64_t uvw_cell(double su, double sv, double u, double v, int nx, int nz) {
@@ -107,7 +102,7 @@ __device__ __forceinline__ int64_t uvw_cell(double su, double sv, double u, doub
 }
 
 __device__ __forceinline__ bool uvw_flagged(double u, double v, double w) {
-  return !uvw_finite(u) || !uvw_finite(v) || !uvw_finite(w) || !(w >= 0.0);
+  return !finite_d(u) || !finite_d(v) || !finite_d(w) || !(w >= 0.0);
 }
 
 __device__ __forceinline__ unsigned long long uvw_wave_sum(unsigned long long x) {

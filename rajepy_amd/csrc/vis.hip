@@ -27,7 +27,7 @@
 // thread, which evaluates Ex for its pairs in registers and forms its partial sum over its JR rows;
 // the 16 row groups of a visibility are 16 adjacent lanes and are combined by a butterfly of
 // shuffles.  With one row tile the result is V; with more, the tiles' partials go through the
-// workspace and vis_combine_kernel adds them in tile order.  Every sum runs in a fixed order: no
+// workspace and partial_combine_kernel adds them in tile order.  Every sum runs in a fixed order: no
 // atomics, the same bits on every call.
 // Phase arguments are ONE double product a * (index - centre) (the centre is a half-integer: exact),
 // reduced and evaluated by sincos_2pi; no recurrence, no float.
@@ -39,8 +39,6 @@ constexpr int kVisB = 256;     // threads per workgroup: 16 row groups x 16 visi
 constexpr int kVisV = 64;      // visibilities per workgroup (4 per thread)
 constexpr int kVisZ = 16;      // z-cells per LDS chunk
 
-// (nx + 1) / 2 rows would idle in a 128-row tile below this
-static int vis_rows_per_thread(int nx) { return nx > 64 ? 8 : 4; }
 static int64_t vis_row_tiles(int nx) {
   const int tr = 16 * vis_rows_per_thread(nx);
   return ((int64_t)nx + tr - 1) / tr;
@@ -172,18 +170,26 @@ __global__ __launch_bounds__(kVisB, 2) void vis_kernel(const double* __restrict_
   }
 }
 
-// vis[m][k] = sum over the row tiles, in tile order, of part[m][tile][k] (complex)
-__global__ __launch_bounds__(kVisB) void vis_combine_kernel(const double* __restrict__ part,
-                                                            int64_t n_maps, int nrt, int n_vis,
-                                                            double* __restrict__ vis) {
-  const int64_t per = (int64_t)n_vis * 2;
+// out[m][c] = sum over r < n, in that order, of part[(m n + r) per + c]: K10's row tiles of
+// complex visibilities (per = 2 n_vis) and K11's k-splits of images (per = nx nz)
+__global__ __launch_bounds__(kVisB) void partial_combine_kernel(const double* __restrict__ part,
+                                                                int64_t n_maps, int n, int64_t per,
+                                                                double* __restrict__ out) {
   for (int64_t i = (int64_t)blockIdx.x * kVisB + threadIdx.x; i < n_maps * per;
        i += (int64_t)gridDim.x * kVisB) {
     const int64_t m = i / per, c = i - m * per;
     double s = 0.0;
-    for (int r = 0; r < nrt; ++r) s += part[(m * nrt + r) * per + c];
-    vis[i] = s;
+    for (int r = 0; r < n; ++r) s += part[(m * n + r) * per + c];
+    out[i] = s;
   }
+}
+
+hipError_t partial_combine_launch(const double* part, int n_maps, int n, int64_t per, double* out,
+                                  hipStream_t st) {
+  const int64_t nb = ((int64_t)n_maps * per + kVisB - 1) / kVisB;
+  hipLaunchKernelGGL(partial_combine_kernel, dim3((unsigned)(nb < 65536 ? nb : 65536)),
+                     dim3(kVisB), 0, st, part, (int64_t)n_maps, n, per, out);
+  return hipGetLastError();
 }
 
 bool vis_grid_ok(int n_maps, int nx, int n_vis) {
@@ -208,11 +214,7 @@ hipError_t vis_launch(const double* maps, int n_maps, int nx, int nz, const doub
                        n_vis, nvt, nrt, out);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess || nrt == 1) return err;
-  const int64_t n = (int64_t)n_maps * n_vis * 2;
-  const unsigned nbc = (unsigned)((n + kVisB - 1) / kVisB < 65536 ? (n + kVisB - 1) / kVisB : 65536);
-  hipLaunchKernelGGL(vis_combine_kernel, dim3(nbc), dim3(kVisB), 0, st, part, (int64_t)n_maps, nrt,
-                     n_vis, vis);
-  return hipGetLastError();
+  return partial_combine_launch(part, n_maps, nrt, (int64_t)n_vis * 2, vis, st);
 }
 
 }  // namespace rjp

@@ -28,7 +28,7 @@
 // LDS reads: the 16 lanes a ds_read_b128 serves together hold all 16 column groups and read 256
 // contiguous bytes of Ez (conflict-free), and two row groups of P 16 bytes apart (broadcast).
 // Few tiles (maps x row tiles x column tiles < 256): the visibilities are split over workgroups,
-// at least 64 each, the partial images go to the workspace and vis_adjoint_combine_kernel adds
+// at least 64 each, the partial images go to the workspace and partial_combine_kernel (vis.hip) adds
 // them in split order.  Every sum runs in a fixed order: no atomics, the same bits on every call.
 // Phase arguments are ONE double product a * (index - centre) (the centre is a half-integer: exact),
 // reduced and evaluated by sincos_2pi; no recurrence, no float.
@@ -42,16 +42,13 @@ constexpr int kVaK = 16;         // visibilities per LDS chunk
 constexpr int kVaMinSplit = 64;  // fewest visibilities a k-split is worth
 constexpr int kVaFill = 256;     // workgroups the k-split aims at: one per CU
 
-// (nx + 1) / 2 rows would idle in a 128-row tile below this
-static int va_rows_per_thread(int nx) { return nx > 64 ? 8 : 4; }
-
 // The tiling rule (tests restate it on the host): row tiles of 128 (nx > 64) or 64 rows, column
 // tiles of 128; with T = n_maps x row tiles x column tiles < 256 the visibilities are split
 // min(ceil(256 / T), ceil(n_vis / 64)) ways into ranges of a whole number of 16-chunks, and the
 // split count is what those ranges need to cover n_vis.
 VisAdjointTiling vis_adjoint_tiling(int n_maps, int nx, int nz, int n_vis) {
   VisAdjointTiling t;
-  const int tr = 16 * va_rows_per_thread(nx);
+  const int tr = 16 * vis_rows_per_thread(nx);
   t.row_tiles = (int)(((int64_t)nx + tr - 1) / tr);
   t.col_tiles = (int)(((int64_t)nz + kVaC - 1) / kVaC);
   const unsigned __int128 all = (unsigned __int128)n_maps * (unsigned __int128)t.row_tiles *
@@ -83,12 +80,6 @@ size_t vis_adjoint_workspace_bytes(int n_maps, int nx, int nz, int n_vis) {
   const unsigned __int128 n = (unsigned __int128)n_maps * (unsigned __int128)t.k_splits *
                               (unsigned __int128)nx * (unsigned __int128)nz * 8u;
   return n > (unsigned __int128)SIZE_MAX ? 0 : (size_t)n;
-}
-
-// (a comparison, not x - x == 0: contracted with the product that formed x, the difference would be
-// that product's rounding error)
-__device__ __forceinline__ bool va_finite(double x) {
-  return __builtin_fabs(x) <= 1.7976931348623157e308;
 }
 
 template <int JR>
@@ -146,8 +137,8 @@ __global__ __launch_bounds__(kVaB, 2) void vis_adjoint_kernel(
   double ta, tb, tr, ti;
   auto table = [&](int64_t k) __attribute__((always_inline)) {
     const double a = sum * raw_u, b = svm * raw_v;
-    const bool ok = k < kend && va_finite(a) && va_finite(b) && va_finite(raw_w) &&
-                    va_finite(raw_r) && va_finite(raw_i);
+    const bool ok = k < kend && finite_d(a) && finite_d(b) && finite_d(raw_w) &&
+                    finite_d(raw_r) && finite_d(raw_i);
     ta = ok ? a : 0.0;
     tb = ok ? b : 0.0;
     tr = ok ? raw_w * raw_r : 0.0;
@@ -215,27 +206,13 @@ __global__ __launch_bounds__(kVaB, 2) void vis_adjoint_kernel(
   }
 }
 
-// img[m][p] = sum over the k-splits, in split order, of part[m][split][p]
-__global__ __launch_bounds__(kVaB) void vis_adjoint_combine_kernel(const double* __restrict__ part,
-                                                                   int64_t n_maps, int ns,
-                                                                   int64_t npix,
-                                                                   double* __restrict__ img) {
-  for (int64_t i = (int64_t)blockIdx.x * kVaB + threadIdx.x; i < n_maps * npix;
-       i += (int64_t)gridDim.x * kVaB) {
-    const int64_t m = i / npix, p = i - m * npix;
-    double s = 0.0;
-    for (int r = 0; r < ns; ++r) s += part[(m * ns + r) * npix + p];
-    img[i] = s;
-  }
-}
-
 hipError_t vis_adjoint_launch(const double* vis, int n_maps, int n_vis, const double* d_su,
                               const double* d_sv, const double* u, const double* v, const double* w,
                               int nx, int nz, double* img, double* part, hipStream_t st) {
   const VisAdjointTiling t = vis_adjoint_tiling(n_maps, nx, nz, n_vis);
   const unsigned nb = (unsigned)t.workgroups;
   double* out = t.k_splits > 1 ? part : img;
-  if (va_rows_per_thread(nx) == 8)
+  if (vis_rows_per_thread(nx) == 8)
     hipLaunchKernelGGL(vis_adjoint_kernel<8>, dim3(nb), dim3(kVaB), 0, st, vis, d_su, d_sv, u, v, w,
                        n_vis, t.k_per_split, t.k_splits, nx, nz, t.row_tiles, t.col_tiles, out);
   else
@@ -243,11 +220,8 @@ hipError_t vis_adjoint_launch(const double* vis, int n_maps, int n_vis, const do
                        n_vis, t.k_per_split, t.k_splits, nx, nz, t.row_tiles, t.col_tiles, out);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess || t.k_splits == 1) return err;
-  const int64_t n = (int64_t)n_maps * nx * nz;
-  const unsigned nbc = (unsigned)((n + kVaB - 1) / kVaB < 65536 ? (n + kVaB - 1) / kVaB : 65536);
-  hipLaunchKernelGGL(vis_adjoint_combine_kernel, dim3(nbc), dim3(kVaB), 0, st, part,
-                     (int64_t)n_maps, t.k_splits, (int64_t)nx * nz, img);
-  return hipGetLastError();
+  // img[m][p] = sum over the k-splits, in split order, of part[m][split][p]
+  return partial_combine_launch(part, n_maps, t.k_splits, (int64_t)nx * nz, img, st);
 }
 
 }  // namespace rjp

@@ -4,10 +4,8 @@ PyTorch (ROCm) is used for device memory, streams and (elsewhere) torch.distribu
 arithmetic on the RT path happens inside librjprt's HIP kernels.  Nothing here falls back to
 the CPU: without a GPU or without the built library, construction raises.
 """
-import collections
 import ctypes as C
 import os
-import re
 import weakref
 
 import numpy as np
@@ -15,6 +13,10 @@ import numpy as np
 from . import _constants as con
 from . import _lib
 from ._lib import RJP_F32, RJP_F64, RJP_GFF_POWERLAW, RJP_GFF_SCALAR  # noqa: F401
+from .imaging import (SIDEREAL_DAY_S, AntennaConfig, Geodetic, antenna_config_path,  # noqa: F401
+                      beam_from_quadratic, beam_quadratic, fit_beam, gauss_results, gauss_start,
+                      geodetic, image_rms, image_scales, observation_grid, observing_plan,
+                      read_antenna_config, thermal_sigma, vis_scales)
 
 
 def _torch():
@@ -1051,6 +1053,47 @@ class RTEngine:
             values = torch.from_numpy(np.ascontiguousarray(values, dtype=np.float64).reshape(-1))
         return values.to(device=self.device, dtype=torch.float64).reshape(-1).contiguous()
 
+    def _call_tiles(self, name, *args):
+        """`_call` for the entry points that return their tile count (> 0) or a status (<= 0)."""
+        tiles = getattr(self.lib, name)(self.ctx, *args, self._stream())
+        if tiles <= 0:
+            self._check(int(tiles), self.ctx, name)
+        return int(tiles)
+
+    def _vis_stack(self, who, vis):
+        """A stack of visibility sets, complex128 [M, K] or float64 [M, K, 2] -> the latter."""
+        torch = _torch()
+        if isinstance(vis, torch.Tensor) and vis.dtype == torch.complex128:
+            vis = torch.view_as_real(vis)
+        if not (isinstance(vis, torch.Tensor) and vis.dtype == torch.float64 and
+                vis.device == self.device and vis.is_contiguous() and vis.dim() == 3 and
+                vis.shape[2] == 2 and vis.shape[0] >= 1 and vis.shape[1] >= 1):
+            raise ValueError("%s: `vis` must be a contiguous complex128 [M, K] or float64 "
+                             "[M, K, 2] tensor on %s" % (who, self.device))
+        return vis
+
+    @staticmethod
+    def _map_scales(who, su, sv, M=None):
+        """`su`, `sv` as host float64 vectors with one entry per map (M None: as many as given)."""
+        su, sv = (np.ascontiguousarray(s, dtype=np.float64).reshape(-1) for s in (su, sv))
+        if M is None and (su.size < 1 or sv.size != su.size):
+            raise ValueError("%s: su and sv must have the same length >= 1" % who)
+        if M is not None and (su.size != M or sv.size != M):
+            raise ValueError("%s: su and sv must have one entry per map (%d)" % (who, M))
+        return su, sv
+
+    def _device_mask(self, who, mask, npix):
+        """None, or `mask` (host array or tensor, non-zero = set) as uint8 [npix] on the device."""
+        if mask is None:
+            return None
+        torch = _torch()
+        if not isinstance(mask, torch.Tensor):
+            mask = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0))
+        dmask = (mask != 0).to(device=self.device, dtype=torch.uint8).reshape(-1).contiguous()
+        if dmask.numel() != npix:
+            raise ValueError("%s: `mask` must have nx * nz entries" % who)
+        return dmask
+
     def vis(self, maps, nx, nz, su, sv, u, v):
         """Model visibilities of a stack of maps (rjp_vis): the direct Fourier sum
         V[m, k] = sum_{ix, iz} maps[m, ix nz + iz] exp(-2 pi i (su[m] u[k] (ix - (nx-1)/2) +
@@ -1068,10 +1111,7 @@ class RTEngine:
         if nx < 1 or nz < 1 or maps.numel() == 0 or maps.numel() % (nx * nz):
             raise ValueError("vis: `maps` must hold a whole number (>= 1) of nx * nz maps")
         M = maps.numel() // (nx * nz)
-        su = np.ascontiguousarray(su, dtype=np.float64).reshape(-1)
-        sv = np.ascontiguousarray(sv, dtype=np.float64).reshape(-1)
-        if su.size != M or sv.size != M:
-            raise ValueError("vis: su and sv must have one entry per map (%d)" % M)
+        su, sv = self._map_scales("vis", su, sv, M)
         du, dv = self._device_f64(u), self._device_f64(v)
         K = du.numel()
         if K < 1 or dv.numel() != K:
@@ -1093,35 +1133,22 @@ class RTEngine:
         tensors, `w` None = all ones.  A visibility with a non-finite value, weight or baseline
         adds nothing.  Sums in a fixed order: a repeated call gives the same bits.  The number of
         tiles the call enqueued is kept in `last_vis_adjoint_tiles`."""
-        torch = _torch()
         nx, nz = int(nx), int(nz)
-        if isinstance(vis, torch.Tensor) and vis.dtype == torch.complex128:
-            vis = torch.view_as_real(vis)
-        if not (isinstance(vis, torch.Tensor) and vis.dtype == torch.float64 and
-                vis.device == self.device and vis.is_contiguous() and vis.dim() == 3 and
-                vis.shape[2] == 2 and vis.shape[0] >= 1 and vis.shape[1] >= 1):
-            raise ValueError("vis_adjoint: `vis` must be a contiguous complex128 [M, K] or float64 "
-                             "[M, K, 2] tensor on %s" % self.device)
+        vis = self._vis_stack("vis_adjoint", vis)
         if nx < 1 or nz < 1:
             raise ValueError("vis_adjoint: nx and nz must be positive")
         M, K = int(vis.shape[0]), int(vis.shape[1])
-        su = np.ascontiguousarray(su, dtype=np.float64).reshape(-1)
-        sv = np.ascontiguousarray(sv, dtype=np.float64).reshape(-1)
-        if su.size != M or sv.size != M:
-            raise ValueError("vis_adjoint: su and sv must have one entry per map (%d)" % M)
+        su, sv = self._map_scales("vis_adjoint", su, sv, M)
         du, dv = self._device_f64(u), self._device_f64(v)
         dw = self._device_f64(w) if w is not None else None
         if du.numel() != K or dv.numel() != K or (dw is not None and dw.numel() != K):
             raise ValueError("vis_adjoint: u, v and w must have one entry per visibility (%d)" % K)
         out = self._f64(M, nx * nz)
         work = self._workspace(max(1, self.lib.rjp_vis_adjoint_workspace(M, nx, nz, K)))
-        tiles = self.lib.rjp_vis_adjoint(self.ctx, vis.data_ptr(), M, K, _lib.dbl_array(su),
-                                         _lib.dbl_array(sv), du.data_ptr(), dv.data_ptr(),
-                                         _ptr(dw), nx, nz, out.data_ptr(), work.data_ptr(),
-                                         work.numel(), self._stream())
-        if tiles <= 0:
-            self._check(int(tiles), self.ctx, "rjp_vis_adjoint")
-        self.last_vis_adjoint_tiles = int(tiles)
+        self.last_vis_adjoint_tiles = self._call_tiles(
+            "rjp_vis_adjoint", vis.data_ptr(), M, K, _lib.dbl_array(su), _lib.dbl_array(sv),
+            du.data_ptr(), dv.data_ptr(), _ptr(dw), nx, nz, out.data_ptr(), work.data_ptr(),
+            work.numel())
         return out
 
     # -- K12 / K13 -----------------------------------------------------------------------------
@@ -1162,13 +1189,7 @@ class RTEngine:
         self._stack_f64("clean", "psf", psf, n_psf * px * pz)
         if model is not None:
             self._stack_f64("clean", "model", model, M * nx * nz)
-        dmask = None
-        if mask is not None:
-            if not isinstance(mask, torch.Tensor):
-                mask = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0))
-            dmask = (mask != 0).to(device=self.device, dtype=torch.uint8).reshape(-1).contiguous()
-            if dmask.numel() != nx * nz:
-                raise ValueError("clean: `mask` must have nx * nz entries")
+        dmask = self._device_mask("clean", mask, nx * nz)
         th = np.asarray(thresh, dtype=np.float64).reshape(-1)
         if th.size not in (1, M):
             raise ValueError("clean: `thresh` must be one number or one per map (%d)" % M)
@@ -1178,14 +1199,10 @@ class RTEngine:
         ncomp = torch.empty(M, dtype=torch.int32, device=self.device)
         peak = self._f64(M)
         work = self._workspace(max(1, self.lib.rjp_clean_workspace(M, nx, nz)))
-        tiles = self.lib.rjp_clean(self.ctx, res.data_ptr(), M, nx, nz, psf.data_ptr(), n_psf, px,
-                                   pz, _ptr(dmask), _lib.dbl_array(th), float(gain), n_iter,
-                                   cpix.data_ptr(), cflux.data_ptr(), ncomp.data_ptr(),
-                                   _ptr(model), peak.data_ptr(), work.data_ptr(), work.numel(),
-                                   self._stream())
-        if tiles <= 0:
-            self._check(int(tiles), self.ctx, "rjp_clean")
-        self.last_clean_tiles = int(tiles)
+        self.last_clean_tiles = self._call_tiles(
+            "rjp_clean", res.data_ptr(), M, nx, nz, psf.data_ptr(), n_psf, px, pz, _ptr(dmask),
+            _lib.dbl_array(th), float(gain), n_iter, cpix.data_ptr(), cflux.data_ptr(),
+            ncomp.data_ptr(), _ptr(model), peak.data_ptr(), work.data_ptr(), work.numel())
         return cpix, cflux, ncomp, peak
 
     def restore(self, cpix, cflux, ncomp, beam_abc, nx, nz, add=None):
@@ -1215,11 +1232,8 @@ class RTEngine:
         if add is not None:
             self._stack_f64("restore", "add", add, M * nx * nz)
         out = self._f64(M, nx * nz)
-        wgs = self.lib.rjp_restore(self.ctx, cpix.data_ptr(), cflux.data_ptr(), ncomp.data_ptr(),
-                                   M, S, _lib.dbl_array(abc), _ptr(add), nx, nz, out.data_ptr(),
-                                   self._stream())
-        if wgs <= 0:
-            self._check(int(wgs), self.ctx, "rjp_restore")
+        self._call_tiles("rjp_restore", cpix.data_ptr(), cflux.data_ptr(), ncomp.data_ptr(), M, S,
+                         _lib.dbl_array(abc), _ptr(add), nx, nz, out.data_ptr())
         return out
 
     # -- K14 -------------------------------------------------------------------------------------
@@ -1253,13 +1267,7 @@ class RTEngine:
             raise ValueError("gaussfit: the box (i0, i1, j0, j1) must lie inside the image")
         if not (np.isfinite(lambda0) and lambda0 > 0. and np.isfinite(xtol) and xtol > 0.):
             raise ValueError("gaussfit: `lambda0` and `xtol` must be finite and positive")
-        dmask = None
-        if mask is not None:
-            if not isinstance(mask, torch.Tensor):
-                mask = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0))
-            dmask = (mask != 0).to(device=self.device, dtype=torch.uint8).reshape(-1).contiguous()
-            if dmask.numel() != nx * nz:
-                raise ValueError("gaussfit: `mask` must have nx * nz entries")
+        dmask = self._device_mask("gaussfit", mask, nx * nz)
         if isinstance(theta0, torch.Tensor):
             theta = theta0.to(device=self.device, dtype=torch.float64).reshape(-1, 6)
         else:
@@ -1278,14 +1286,11 @@ class RTEngine:
               if trace else None)
         nbox = (b[1] - b[0] + 1) * (b[3] - b[2] + 1)
         work = self._workspace(max(1, self.lib.rjp_gaussfit_workspace(M, nbox)))
-        tiles = self.lib.rjp_gaussfit(self.ctx, img.data_ptr(), M, nx, nz, (C.c_int32 * 4)(*b),
-                                      _ptr(dmask), theta.data_ptr(), float(lambda0), float(xtol),
-                                      n_iter, chi2.data_ptr(), cov.data_ptr(), npix.data_ptr(),
-                                      niter.data_ptr(), status.data_ptr(), _ptr(tr),
-                                      work.data_ptr(), work.numel(), self._stream())
-        if tiles <= 0:
-            self._check(int(tiles), self.ctx, "rjp_gaussfit")
-        self.last_gaussfit_tiles = int(tiles)
+        self.last_gaussfit_tiles = self._call_tiles(
+            "rjp_gaussfit", img.data_ptr(), M, nx, nz, (C.c_int32 * 4)(*b), _ptr(dmask),
+            theta.data_ptr(), float(lambda0), float(xtol), n_iter, chi2.data_ptr(), cov.data_ptr(),
+            npix.data_ptr(), niter.data_ptr(), status.data_ptr(), _ptr(tr), work.data_ptr(),
+            work.numel())
         out = dict(theta=theta, chi2=chi2, cov=cov, npix=npix, niter=niter, status=status)
         if trace:
             out["trace"] = tr
@@ -1309,7 +1314,6 @@ class RTEngine:
         `last_uv_weight_stats` is a device tensor [M, 6] of (sum w, sum W^2, f2, counted, out of
         range, the fixed-point shift s), `last_uv_weight_density` the density [M, cells] when
         `want_density` (else None), `last_uv_weight_tiles` the workgroups of the scatter."""
-        torch = _torch()
         nx, nz = int(nx), int(nz)
         if nx < 1 or nz < 1:
             raise ValueError("uv_weights: nx and nz must be positive")
@@ -1319,11 +1323,8 @@ class RTEngine:
         robust = float(robust)
         if mode == "briggs" and not (-2. <= robust <= 2.):
             raise ValueError("uv_weights: `robust` must lie in [-2, 2]")
-        su = np.ascontiguousarray(su, dtype=np.float64).reshape(-1)
-        sv = np.ascontiguousarray(sv, dtype=np.float64).reshape(-1)
+        su, sv = self._map_scales("uv_weights", su, sv)
         M = su.size
-        if M < 1 or sv.size != M:
-            raise ValueError("uv_weights: su and sv must have the same length >= 1")
         du, dv = self._device_f64(u), self._device_f64(v)
         dw = self._device_f64(w) if w is not None else None
         K = du.numel()
@@ -1334,14 +1335,10 @@ class RTEngine:
         stats = self._f64(M, 6)
         dens = self._f64(M, cells) if want_density else None
         work = self._workspace(max(1, self.lib.rjp_uv_weights_workspace(M, nx, nz, K)))
-        tiles = self.lib.rjp_uv_weights(self.ctx, M, K, _lib.dbl_array(su), _lib.dbl_array(sv),
-                                        du.data_ptr(), dv.data_ptr(), _ptr(dw), nx, nz,
-                                        self.UV_WEIGHT_MODES[mode], robust, out.data_ptr(),
-                                        stats.data_ptr(), _ptr(dens), work.data_ptr(),
-                                        work.numel(), self._stream())
-        if tiles <= 0:
-            self._check(int(tiles), self.ctx, "rjp_uv_weights")
-        self.last_uv_weight_tiles = int(tiles)
+        self.last_uv_weight_tiles = self._call_tiles(
+            "rjp_uv_weights", M, K, _lib.dbl_array(su), _lib.dbl_array(sv), du.data_ptr(),
+            dv.data_ptr(), _ptr(dw), nx, nz, self.UV_WEIGHT_MODES[mode], robust, out.data_ptr(),
+            stats.data_ptr(), _ptr(dens), work.data_ptr(), work.numel())
         self.last_uv_weight_stats = stats
         self.last_uv_weight_density = dens
         return out
@@ -1377,12 +1374,9 @@ class RTEngine:
             raise ValueError("uv_tracks: n_t * n_bl exceeds 2^31 - 1")
         u, v = self._f64(T, B), self._f64(T, B)
         w = self._f64(T, B) if want_w else None
-        wgs = self.lib.rjp_uv_tracks(self.ctx, _lib.dbl_array(xyz), A, _lib.dbl_array(gha), T,
-                                     float(np.sin(dec_rad)), float(np.cos(dec_rad)), hup, sme,
-                                     u.data_ptr(), v.data_ptr(), _ptr(w), self._stream())
-        if wgs <= 0:
-            self._check(int(wgs), self.ctx, "rjp_uv_tracks")
-        self.last_uv_tracks_tiles = int(wgs)
+        self.last_uv_tracks_tiles = self._call_tiles(
+            "rjp_uv_tracks", _lib.dbl_array(xyz), A, _lib.dbl_array(gha), T, float(np.sin(dec_rad)),
+            float(np.cos(dec_rad)), hup, sme, u.data_ptr(), v.data_ptr(), _ptr(w))
         return u, v, w
 
     def vis_noise(self, vis, sigma, seed=0, s=None, k0=0, m0=0, out=None):
@@ -1398,12 +1392,7 @@ class RTEngine:
         `last_vis_noise_tiles`: the workgroups."""
         torch = _torch()
         cplx = isinstance(vis, torch.Tensor) and vis.dtype == torch.complex128
-        v3 = torch.view_as_real(vis) if cplx else vis
-        if not (isinstance(v3, torch.Tensor) and v3.dtype == torch.float64 and
-                v3.device == self.device and v3.is_contiguous() and v3.dim() == 3 and
-                v3.shape[2] == 2 and v3.shape[0] >= 1 and v3.shape[1] >= 1):
-            raise ValueError("vis_noise: `vis` must be a contiguous complex128 [M, K] or float64 "
-                             "[M, K, 2] tensor on %s" % self.device)
+        v3 = self._vis_stack("vis_noise", vis)
         M, K = int(v3.shape[0]), int(v3.shape[1])
         sg = np.asarray(sigma, dtype=np.float64).reshape(-1)
         if sg.size not in (1, M):
@@ -1421,11 +1410,9 @@ class RTEngine:
             o3 = v3
         else:
             raise ValueError("vis_noise: `out` must be None or `vis` itself")
-        wgs = self.lib.rjp_vis_noise(self.ctx, v3.data_ptr(), M, K, _lib.dbl_array(sg), _ptr(ds),
-                                     seed, int(k0), int(m0), o3.data_ptr(), self._stream())
-        if wgs <= 0:
-            self._check(int(wgs), self.ctx, "rjp_vis_noise")
-        self.last_vis_noise_tiles = int(wgs)
+        self.last_vis_noise_tiles = self._call_tiles(
+            "rjp_vis_noise", v3.data_ptr(), M, K, _lib.dbl_array(sg), _ptr(ds), seed, int(k0),
+            int(m0), o3.data_ptr())
         return torch.view_as_complex(o3) if cplx else o3
 
     def rrl_cells(self, fields, bursts, time_s, line, nus):
@@ -1493,392 +1480,6 @@ class RTEngine:
 # -- host-side per-channel coefficients (scalars; classes.py:1395-1397, 1473-1475, 1519-1521) --
 def solid_angle(csize_au, dist_pc):
     return np.arctan((csize_au * con.au) / (dist_pc * con.parsec)) ** 2.
-
-
-def vis_scales(freqs, csize_au, dist_pc):
-    """su[f], sv[f] of `RTEngine.vis` / rjp_vis for baselines (u, v) in METRES, as measurement sets
-    store them -- the one place that holds the sky convention:
-      * V(u, v) = sum_p I_p exp(-2 pi i (u l_p + v m_p)), (l, m) the direction cosines towards
-        East (RA) and North (Dec), u and v in wavelengths = metres * nu / c;
-      * the phase centre is the map centre, pixel ((nx-1)/2, (nz-1)/2): CRPIX of `save_fits`;
-      * one cell subtends cell = arctan(csize au / (dist pc)) radians (the square root of
-        `solid_angle`); the FITS header `save_fits` writes has CDELT1 < 0 -- RA decreases with
-        ix -- and CDELT2 > 0, so l = -cell (ix - (nx-1)/2), m = +cell (iz - (nz-1)/2):
-        su = -cell nu / c,  sv = +cell nu / c   [cycles per cell per metre]."""
-    freqs = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
-    cell = np.arctan((csize_au * con.au) / (dist_pc * con.parsec))
-    return -cell * freqs / con.c, cell * freqs / con.c
-
-
-def image_scales(freqs, cell_rad):
-    """su[f], sv[f] of an image grid whose cells subtend `cell_rad` radians, for baselines in
-    METRES, under the sky convention of `vis_scales` (phase centre = grid centre, RA decreasing
-    with ix): su = -cell nu / c, sv = +cell nu / c.  `vis_scales` is the special case
-    cell = arctan(csize au / dist).  For `RTEngine.vis_adjoint` (any imaging grid) and
-    `RTEngine.vis`."""
-    freqs = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
-    cell = float(cell_rad)
-    return -cell * freqs / con.c, cell * freqs / con.c
-
-
-# -- synthetic observations (K16): the host side ------------------------------------------------
-SIDEREAL_DAY_S = 86164.0905        # the hour angle of a fixed direction advances one turn in this
-WGS84_A, WGS84_F = 6378137.0, 1. / 298.257223563
-
-AntennaConfig = collections.namedtuple("AntennaConfig", ["names", "xyz", "diameters", "observatory"])
-Geodetic = collections.namedtuple("Geodetic", ["lat_deg", "lon_deg", "up", "lat0_deg", "lon0_deg",
-                                               "up0"])
-
-
-def read_antenna_config(path):
-    """An antenna list in the format CASA simobserve reads -> `AntennaConfig` (names [A], xyz
-    [A, 3] in metres, diameters [A] in metres, observatory).  `#` lines form the header and carry
-    `observatory=` and `coordsys=`; every other non-blank line is `x y z diameter name`.  Only
-    `coordsys=XYZ` (geocentric ITRF positions) is read: `UTM` and `LOC` lists, which need a datum
-    or a site position, raise ValueError naming the system, as does a malformed line."""
-    obs, coordsys, names, xyz, diam = None, None, [], [], []
-    with open(path, "rt") as f:
-        for no, line in enumerate(f, 1):
-            text = line.strip()
-            if not text:
-                continue
-            if text.startswith("#"):
-                for key, val in re.findall(r"(\w+)\s*=\s*(\S+)", text[1:]):
-                    if key.lower() == "observatory":
-                        obs = val
-                    elif key.lower() == "coordsys":
-                        coordsys = val.upper()
-                continue
-            cols = text.split()
-            if len(cols) < 5:
-                raise ValueError("%s:%d: expected `x y z diameter name`, found %d columns"
-                                 % (path, no, len(cols)))
-            try:
-                vals = [float(c) for c in cols[:4]]
-            except ValueError:
-                raise ValueError("%s:%d: x, y, z and diameter must be numbers" % (path, no)) from None
-            if not np.all(np.isfinite(vals)) or not vals[3] > 0.:
-                raise ValueError("%s:%d: non-finite position or non-positive diameter" % (path, no))
-            xyz.append(vals[:3])
-            diam.append(vals[3])
-            names.append(cols[4])
-    if coordsys is None:
-        raise ValueError("%s: no `# coordsys=` header line" % path)
-    if not coordsys.startswith("XYZ"):
-        raise ValueError("%s: coordsys=%s is not supported (geocentric XYZ lists only)"
-                         % (path, coordsys))
-    if len(names) < 2:
-        raise ValueError("%s: fewer than two antennas" % path)
-    if len(set(names)) != len(names):
-        raise ValueError("%s: antenna names are not unique" % path)
-    return AntennaConfig(names, np.array(xyz, dtype=np.float64), np.array(diam, dtype=np.float64),
-                         obs)
-
-
-def _geodetic_one(x, y, z):
-    """WGS84 latitude, east longitude [rad] of geocentric (x, y, z) [m]: the fixed point of
-    lat = atan2(z, p (1 - e^2 N / (N + h))), which contracts by ~e^2 per step."""
-    e2 = WGS84_F * (2. - WGS84_F)
-    p = np.hypot(x, y)
-    lon = np.arctan2(y, x)
-    lat = np.arctan2(z, p * (1. - e2))
-    for _ in range(12):
-        n = WGS84_A / np.sqrt(1. - e2 * np.sin(lat) ** 2)
-        h = p / np.cos(lat) - n if abs(np.cos(lat)) > 1e-8 else abs(z) - n * (1. - e2)
-        lat = np.arctan2(z, p * (1. - e2 * n / (n + h)))
-    return lat, lon
-
-
-def geodetic(xyz):
-    """WGS84 geodetic latitude and EAST longitude [deg] and the unit local vertical (the ellipsoid
-    normal, in the geocentric frame of `xyz`) of every antenna of `xyz` [A, 3] [m], and the same
-    three of the mean position -> `Geodetic`.  The verticals are what `RTEngine.uv_tracks` takes
-    as `up`; lat0 / lon0 place the array for `observing_plan` and the hour angle."""
-    xyz = np.asarray(xyz, dtype=np.float64).reshape(-1, 3)
-    pts = np.vstack([xyz, xyz.mean(axis=0)[None, :]])
-    ll = np.array([_geodetic_one(*p) for p in pts])
-    lat, lon = ll[:, 0], ll[:, 1]
-    up = np.stack([np.cos(lat) * np.cos(lon), np.cos(lat) * np.sin(lon), np.sin(lat)], axis=1)
-    return Geodetic(np.degrees(lat[:-1]), np.degrees(lon[:-1]), up[:-1], float(np.degrees(lat[-1])),
-                    float(np.degrees(lon[-1])), up[-1])
-
-
-def observing_plan(dec_deg, lat_deg, t_obs_s, t_int_s, min_el_deg, hourangle_h=0.):
-    """The integrations of `t_obs_s` seconds on a target at declination `dec_deg` from latitude
-    `lat_deg` -> (local hour angles in TURNS [n], day of each [n]) -- the reference's rule for
-    splitting an observation over days (classes.py:2510-2550), stated here:
-      * `time_up` = 86400 s if the target is above `min_el_deg` at lower culmination, else
-        int(7200 H) with H = arccos((sin el - sin lat sin dec) / (cos lat cos dec)) in hours;
-        ValueError if the target never reaches the limit;
-      * the days last [time_up] * (t_obs // time_up) and then the remainder WHEN IT IS NOT ZERO
-        (the reference appends a day of length zero);
-      * every day is centred on `hourangle_h` and holds max(1, floor(T / t_int)) integrations of
-        `t_int_s`, placed symmetrically about the centre and taken at their mid-points;
-      * the hour angle advances one turn per SIDEREAL_DAY_S.
-    The reference's eight-scan split of the last day for east-west arrays is not made."""
-    t_obs, t_int = float(t_obs_s), float(t_int_s)
-    if not (t_obs > 0. and t_int > 0. and np.isfinite(t_obs) and np.isfinite(t_int)):
-        raise ValueError("observing_plan: t_obs_s and t_int_s must be positive")
-    dec, lat, el = np.radians(dec_deg), np.radians(lat_deg), np.radians(min_el_deg)
-    low = np.arcsin(np.clip(np.sin(lat) * np.sin(dec) - np.cos(lat) * np.cos(dec), -1., 1.))
-    if low > el:
-        time_up = 86400
-    else:
-        den = np.cos(lat) * np.cos(dec)
-        ch = (np.sin(el) - np.sin(lat) * np.sin(dec)) / den if den != 0. else np.inf
-        if not ch <= 1.:
-            raise ValueError("observing_plan: a target at declination %.3f deg never reaches an "
-                             "elevation of %.3f deg from latitude %.3f deg"
-                             % (dec_deg, min_el_deg, lat_deg))
-        time_up = int(7200. * np.degrees(np.arccos(max(ch, -1.))) / 15.)
-        if time_up < 1:
-            raise ValueError("observing_plan: the target is above %.3f deg for less than a second "
-                             "a day" % min_el_deg)
-    days = [float(time_up)] * int(t_obs // time_up)
-    rest = t_obs - (t_obs // time_up) * time_up
-    if rest > 0.:
-        days.append(rest)
-    ha, day = [], []
-    for d, T in enumerate(days):
-        n = max(1, int(np.floor(T / t_int)))
-        mid = (np.arange(n) + 0.5 - 0.5 * n) * t_int
-        ha.append(float(hourangle_h) / 24. + mid / SIDEREAL_DAY_S)
-        day.append(np.full(n, d, dtype=np.int64))
-    return np.concatenate(ha), np.concatenate(day)
-
-
-def thermal_sigma(sefd_jy, chanwidth_hz, t_int_s, n_pol=2, efficiency=1.):
-    """The rms [Jy] of the real and of the imaginary part of ONE visibility -- one baseline, one
-    channel of `chanwidth_hz`, one integration of `t_int_s`, `n_pol` polarisations averaged --
-    of an array of identical antennas of system-equivalent flux density `sefd_jy`:
-    SEFD / (efficiency sqrt(2 n_pol chanwidth t_int))."""
-    sefd, dnu, t = (np.asarray(x, dtype=np.float64) for x in (sefd_jy, chanwidth_hz, t_int_s))
-    if np.any(~(sefd >= 0.)) or np.any(~(dnu > 0.)) or np.any(~(t > 0.)) or n_pol < 1 or \
-            not efficiency > 0.:
-        raise ValueError("thermal_sigma: sefd_jy >= 0, chanwidth_hz, t_int_s, n_pol and "
-                         "efficiency > 0")
-    return sefd / (float(efficiency) * np.sqrt(2. * n_pol * dnu * t))
-
-
-def image_rms(iw, sigma_k):
-    """The thermal rms [Jy / beam] of a dirty image made with the imaging weights `iw` ([K], or
-    [M, K] -> one value per map) from visibilities whose real and imaginary parts have the rms
-    `sigma_k` (one number, [K], [M, 1] or [M, K]): sqrt(sum w'^2 sigma^2) / sum w'.  Flagged
-    visibilities carry the weight 0 and drop out; a map without weights gives NaN."""
-    w = np.atleast_2d(np.asarray(iw, dtype=np.float64))
-    s = np.broadcast_to(np.asarray(sigma_k, dtype=np.float64), w.shape)
-    live = w > 0.
-    num = np.sqrt(np.sum(np.where(live, (w * s) ** 2, 0.), axis=1))
-    with np.errstate(invalid="ignore", divide="ignore"):
-        return num / np.sum(np.where(live, w, 0.), axis=1)
-
-
-def antenna_config_path(directory, telescope, config):
-    """The antenna list of (`telescope`, `config`) in `directory`, found by name without regard
-    to case: `<tel>.<cfg>.cfg`, `<tel>_<cfg>.cfg`, or `<tel>.cfg` when the configuration is
-    '0' (a telescope with one) -> its path, or None."""
-    tel, cfg = str(telescope).lower(), str(config).lower()
-    want = [tel + "." + cfg + ".cfg", tel + "_" + cfg + ".cfg"] + ([tel + ".cfg"] if cfg == "0" else [])
-    try:
-        have = {name.lower(): name for name in sorted(os.listdir(directory), reverse=True)}
-    except OSError:
-        return None
-    for name in want:
-        if name in have:
-            return os.path.join(directory, have[name])
-    return None
-
-
-def observation_grid(max_baseline_m, freq_hz, extent_as):
-    """(cell [arcsec], image side [cells]) the reference images a synthetic observation on
-    (classes.py:2674-2678, 2753-2759): the cell is a quarter of 1 / (longest baseline in
-    wavelengths), rounded to 1e-6 arcsec; the side is ceil(2 extent / cell) for a model that
-    spans `extent_as`, and at least 500."""
-    beam_as = np.degrees(1. / (float(max_baseline_m) * float(freq_hz) / con.c)) * 3600.
-    cell_as = float("%.6f" % (beam_as / 4.))
-    if not cell_as > 0.:
-        raise ValueError("observation_grid: the cell rounds to 0 at 1e-6 arcsec")
-    return cell_as, max(500, int(np.ceil(2. * float(extent_as) / cell_as)))
-
-
-_FOUR_LN2 = 4. * np.log(2.)
-
-
-def beam_quadratic(bmaj_as, bmin_as, bpa_deg, cell_rad):
-    """(A, B, C) [cells^-2] of `RTEngine.restore` / rjp_restore for an elliptical Gaussian clean
-    beam exp(-(A dx^2 + 2 B dx dz + C dz^2)) -- the one place that holds the convention:
-      * `bmaj_as`, `bmin_as` [arcsec] are FWHM: along an axis of FWHM w the beam is
-        exp(-4 ln2 s^2 / w^2);
-      * `bpa_deg` is the position angle of the major axis, from North through East.  North is +z
-        and East is DECREASING ix (RA decreases with ix: `vis_scales`), so the major axis points
-        along (dx, dz) = (-sin bpa, cos bpa): with bpa = 0 it lies along z;
-      * (dx, dz) are in cells of `cell_rad` radians."""
-    cell_as = np.degrees(float(cell_rad)) * 3600.
-    ka = _FOUR_LN2 / (float(bmaj_as) / cell_as) ** 2
-    kb = _FOUR_LN2 / (float(bmin_as) / cell_as) ** 2
-    s, c = np.sin(np.radians(float(bpa_deg))), np.cos(np.radians(float(bpa_deg)))
-    return (float(ka * s * s + kb * c * c), float((kb - ka) * s * c),
-            float(ka * c * c + kb * s * s))
-
-
-def beam_from_quadratic(A, B, C, cell_rad):
-    """The inverse of `beam_quadratic`: (bmaj_as, bmin_as, bpa_deg) of a positive definite
-    (A, B, C) [cells^-2], bpa in (-90, 90]."""
-    lam, vec = np.linalg.eigh(np.array([[A, B], [B, C]], dtype=np.float64))
-    if not lam[0] > 0.:
-        raise ValueError("beam: (A, B, C) is not positive definite")
-    cell_as = np.degrees(float(cell_rad)) * 3600.
-    ex, ez = vec[:, 0]                             # the major axis: the smaller eigenvalue
-    bpa = np.degrees(np.arctan2(-ex, ez))
-    bpa = bpa - 180. if bpa > 90. else bpa + 180. if bpa <= -90. else bpa
-    return (float(np.sqrt(_FOUR_LN2 / lam[0]) * cell_as),
-            float(np.sqrt(_FOUR_LN2 / lam[1]) * cell_as), float(bpa))
-
-
-def fit_beam(patch):
-    """(A, B, C) [cells^-2] of the Gaussian that fits the main lobe of a dirty beam: `patch` is a
-    2-D array [odd, odd] around the beam's centre pixel; a linear least-squares fit of
-    -ln(patch / centre) = A dx^2 + 2 B dx dz + C dz^2 over the pixels >= half the centre value
-    that are connected to the centre (4-neighbours), as tclean fits its restoring beam."""
-    b = np.asarray(patch, dtype=np.float64)
-    if b.ndim != 2 or b.shape[0] % 2 == 0 or b.shape[1] % 2 == 0:
-        raise ValueError("fit_beam: `patch` must be 2-D with odd sizes")
-    cx, cz = (b.shape[0] - 1) // 2, (b.shape[1] - 1) // 2
-    if not (np.isfinite(b[cx, cz]) and b[cx, cz] > 0.):
-        raise ValueError("fit_beam: the centre of the beam must be positive")
-    b = b / b[cx, cz]
-    lobe = np.zeros(b.shape, dtype=bool)
-    todo = [(cx, cz)]
-    while todo:
-        i, j = todo.pop()
-        if 0 <= i < b.shape[0] and 0 <= j < b.shape[1] and not lobe[i, j] and b[i, j] >= 0.5:
-            lobe[i, j] = True
-            todo += [(i + 1, j), (i - 1, j), (i, j + 1), (i, j - 1)]
-    ii, jj = np.nonzero(lobe)
-    dx, dz = (ii - cx).astype(np.float64), (jj - cz).astype(np.float64)
-    design = np.stack([dx * dx, 2. * dx * dz, dz * dz], axis=1)
-    if np.linalg.matrix_rank(design) < 3:
-        raise ValueError("fit_beam: the main lobe covers too few pixels (the beam is not resolved "
-                         "by the cell)")
-    sol = np.linalg.lstsq(design, -np.log(b[ii, jj]), rcond=None)[0]
-    A, B, C = (float(x) for x in sol)
-    if not (A > 0. and C > 0. and A * C > B * B):
-        raise ValueError("fit_beam: the fitted form is not positive definite")
-    return A, B, C
-
-
-def gauss_start(img, nx, nz, beam_abc, box=None, mask=None):
-    """The default start of `RTEngine.gaussfit` -> tensor [M, 6] beside `img`: per map the
-    counting pixel (inside `box`, non-zero in `mask`, finite) of largest |I|, its value and
-    position, and the clean beam's (A, B, C) -- a point source as the beam sees it.  `img`: a
-    float64 tensor of M * nx * nz values; `beam_abc`: one (A, B, C) or one per map.  Plain torch,
-    batched, nothing goes to the host.  A map without a counting pixel gets a NaN peak, which
-    `gaussfit` reports as status 3.  (The reference's own estimate comes from the model's
-    tau = 1 surface, classes.py:2718-2743; a caller may pass any start instead.)"""
-    torch = _torch()
-    nx, nz = int(nx), int(nz)
-    t = img.reshape(-1, nx, nz)
-    M = int(t.shape[0])
-    ok = torch.zeros(nx, nz, dtype=torch.bool, device=t.device)
-    i0, i1, j0, j1 = (0, nx - 1, 0, nz - 1) if box is None else (int(x) for x in np.ravel(box))
-    ok[i0:i1 + 1, j0:j1 + 1] = True
-    if mask is not None:
-        if not isinstance(mask, torch.Tensor):
-            mask = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0))
-        ok &= (mask != 0).to(t.device).reshape(nx, nz)
-    ok = ok.unsqueeze(0) & torch.isfinite(t)
-    mag = torch.where(ok, t.abs(), torch.full_like(t, -1.0)).reshape(M, -1)
-    top, idx = mag.max(dim=1)
-    val = t.reshape(M, -1).gather(1, idx.unsqueeze(1)).squeeze(1)
-    val = torch.where(top >= 0, val, torch.full_like(val, float("nan")))
-    abc = np.asarray(beam_abc, dtype=np.float64).reshape(-1, 3)
-    if abc.shape[0] not in (1, M):
-        raise ValueError("gauss_start: `beam_abc` must be one (A, B, C) or one per map (%d)" % M)
-    abc = torch.from_numpy(np.array(np.broadcast_to(abc, (M, 3)))).to(t.device)
-    pos = torch.stack([torch.div(idx, nz, rounding_mode="floor"), idx % nz], dim=1)
-    return torch.cat([val.unsqueeze(1), pos.to(torch.float64), abc], dim=1).contiguous()
-
-
-def gauss_results(theta, cov, chi2, npix, beam_abc, cell_rad, rms=None, shape=None, status=None):
-    """What CASA imfit reports, from the outputs of `RTEngine.gaussfit` (host arrays; pure NumPy)
-    -> one dict per map.  Conventions as in `beam_quadratic`; `beam_abc`: the clean beam, one
-    (A, B, C) or one per map; `cell_rad`: the cell in radians.
-      * 'peak' [Jy / beam] = S;  'I' = {'val': S sqrt(det Q_beam / det Q_fit), 'unit': 'Jy'}, the
-        integrated flux (Q = [[A, B], [B, C]]);
-      * 'x0', 'z0' [pixels]; with `shape` = (nx, nz) also 'east_as', 'north_as', the offsets from
-        the map centre ((nx-1)/2, (nz-1)/2) in arcsec under the sky convention of `vis_scales`
-        (East = DECREASING ix, North = +z);
-      * 'maj_as', 'min_as', 'pa_deg': the fitted size (`beam_from_quadratic`);
-      * 'deconvolved': {'maj_as', 'min_as', 'pa_deg'} of Sigma_src = (2 Q_fit)^-1 - (2 Q_beam)^-1,
-        or None with 'point_source' True where that is not positive definite;
-      * with `rms` [Jy / beam] (one number or one per map) the 1-sigma errors 'peak_err',
-        'x0_err', 'z0_err', 'abc_err' and 'Ierr' = {'val', 'unit'} from the covariance
-        rms^2 Omega_b (J^T J)^-1, Omega_b = pi / sqrt(det Q_beam) cells: the usual inflation for
-        noise that is correlated over a beam; Ierr by first-order propagation through
-        I(S, A, B, C).  This is a STATED APPROXIMATION, not the expressions of Condon (1997)
-        that CASA uses.  Without `rms`: None;
-      * 'chi2', 'npix', and 'status' where given.
-    A map whose fit is not finite and positive definite (status 3) gets NaN / None entries."""
-    theta = np.asarray(theta, dtype=np.float64).reshape(-1, 6)
-    M = theta.shape[0]
-    cov = np.asarray(cov, dtype=np.float64).reshape(M, 21)
-    chi2, npix = np.asarray(chi2, dtype=np.float64).reshape(M), np.asarray(npix).reshape(M)
-    beam = np.broadcast_to(np.asarray(beam_abc, dtype=np.float64).reshape(-1, 3), (M, 3))
-    rms_m = None if rms is None else np.broadcast_to(np.asarray(rms, dtype=np.float64), (M,))
-    cell_as = np.degrees(float(cell_rad)) * 3600.
-    nan = float("nan")
-    out = []
-    for m in range(M):
-        S, x0, z0, A, B, C = (float(v) for v in theta[m])
-        bA, bB, bC = (float(v) for v in beam[m])
-        det, bdet = A * C - B * B, bA * bC - bB * bB
-        d = {"peak": S, "x0": x0, "z0": z0, "chi2": float(chi2[m]), "npix": int(npix[m]),
-             "I": {"val": nan, "unit": "Jy"}, "Ierr": {"val": None, "unit": "Jy"},
-             "maj_as": nan, "min_as": nan, "pa_deg": nan, "deconvolved": None,
-             "point_source": False, "peak_err": None, "x0_err": None, "z0_err": None,
-             "abc_err": None}
-        if status is not None:
-            d["status"] = int(np.asarray(status).reshape(M)[m])
-        if shape is not None:
-            d["east_as"] = float(-(x0 - (int(shape[0]) - 1) / 2.) * cell_as)
-            d["north_as"] = float((z0 - (int(shape[1]) - 1) / 2.) * cell_as)
-        good = np.all(np.isfinite(theta[m])) and A > 0. and C > 0. and det > 0. and bdet > 0.
-        if not good:
-            out.append(d)
-            continue
-        flux = S * np.sqrt(bdet / det)
-        d["I"]["val"] = float(flux)
-        d["maj_as"], d["min_as"], d["pa_deg"] = beam_from_quadratic(A, B, C, cell_rad)
-        # covariance matrices of the Gaussians: Sigma = (2 Q)^-1
-        sig = (np.array([[C, -B], [-B, A]]) / (2. * det)
-               - np.array([[bC, -bB], [-bB, bA]]) / (2. * bdet))
-        sdet = sig[0, 0] * sig[1, 1] - sig[0, 1] * sig[1, 0]
-        if sig[0, 0] > 0. and sig[1, 1] > 0. and sdet > 0.:
-            q = np.array([[sig[1, 1], -sig[0, 1]], [-sig[0, 1], sig[0, 0]]]) / (2. * sdet)
-            mj, mn, pa = beam_from_quadratic(q[0, 0], q[0, 1], q[1, 1], cell_rad)
-            d["deconvolved"] = {"maj_as": mj, "min_as": mn, "pa_deg": pa}
-        else:
-            d["point_source"] = True
-        if rms_m is not None and np.all(np.isfinite(cov[m])):
-            N = np.zeros((6, 6))
-            k = 0
-            for i in range(6):
-                for j in range(i, 6):
-                    N[i, j] = N[j, i] = cov[m, k]
-                    k += 1
-            try:
-                P = rms_m[m] ** 2 * (np.pi / np.sqrt(bdet)) * np.linalg.inv(N)
-            except np.linalg.LinAlgError:
-                P = None
-            if P is not None and np.all(np.diag(P) >= 0.):
-                sd = np.sqrt(np.diag(P))
-                d["peak_err"], d["x0_err"], d["z0_err"] = float(sd[0]), float(sd[1]), float(sd[2])
-                d["abc_err"] = (float(sd[3]), float(sd[4]), float(sd[5]))
-                grad = np.array([flux / S if S != 0. else np.sqrt(bdet / det), 0., 0.,
-                                 -flux * C / (2. * det), flux * B / det, -flux * A / (2. * det)])
-                d["Ierr"]["val"] = float(np.sqrt(grad @ P @ grad))
-        out.append(d)
-    return out
 
 
 def ff_channel_coeffs(freqs, csize_au, dist_pc, gff_mode, gff_values=None):

@@ -1,0 +1,860 @@
+"""The imaging chain -- the reference's simobserve -> tclean -> imfit, on the device -- as one unit:
+the host-side conventions (scales, beams, antenna lists, observing plans, fit results), the result
+types and the `Imager`, which takes flux maps or visibilities as device tensors through the K10-K16
+wrappers of an `RTEngine`.  `JetModel` is a front to it.  `engine` re-exports the host helpers
+(`engine.image_scales`, `engine.fit_beam`, ...), `classes` the result types; this imports neither.
+"""
+import collections
+import os
+import re
+
+import numpy as np
+
+from . import _constants as con
+
+
+def vis_scales(freqs, csize_au, dist_pc):
+    """su[f], sv[f] of `RTEngine.vis` / rjp_vis for baselines (u, v) in METRES, as measurement sets
+    store them -- the one place that holds the sky convention:
+      * V(u, v) = sum_p I_p exp(-2 pi i (u l_p + v m_p)), (l, m) the direction cosines towards
+        East (RA) and North (Dec), u and v in wavelengths = metres * nu / c;
+      * the phase centre is the map centre, pixel ((nx-1)/2, (nz-1)/2): CRPIX of `save_fits`;
+      * one cell subtends cell = arctan(csize au / (dist pc)) radians (the square root of
+        `solid_angle`); the FITS header `save_fits` writes has CDELT1 < 0 -- RA decreases with
+        ix -- and CDELT2 > 0, so l = -cell (ix - (nx-1)/2), m = +cell (iz - (nz-1)/2):
+        su = -cell nu / c,  sv = +cell nu / c   [cycles per cell per metre]."""
+    freqs = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
+    cell = np.arctan((csize_au * con.au) / (dist_pc * con.parsec))
+    return -cell * freqs / con.c, cell * freqs / con.c
+
+
+def image_scales(freqs, cell_rad):
+    """su[f], sv[f] of an image grid whose cells subtend `cell_rad` radians, for baselines in
+    METRES, under the sky convention of `vis_scales` (phase centre = grid centre, RA decreasing
+    with ix): su = -cell nu / c, sv = +cell nu / c.  `vis_scales` is the special case
+    cell = arctan(csize au / dist).  For `RTEngine.vis_adjoint` (any imaging grid) and
+    `RTEngine.vis`."""
+    freqs = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
+    cell = float(cell_rad)
+    return -cell * freqs / con.c, cell * freqs / con.c
+
+
+# -- synthetic observations (K16): the host side ------------------------------------------------
+SIDEREAL_DAY_S = 86164.0905        # the hour angle of a fixed direction advances one turn in this
+WGS84_A, WGS84_F = 6378137.0, 1. / 298.257223563
+
+AntennaConfig = collections.namedtuple("AntennaConfig", ["names", "xyz", "diameters", "observatory"])
+Geodetic = collections.namedtuple("Geodetic", ["lat_deg", "lon_deg", "up", "lat0_deg", "lon0_deg",
+                                               "up0"])
+
+
+def read_antenna_config(path):
+    """An antenna list in the format CASA simobserve reads -> `AntennaConfig` (names [A], xyz
+    [A, 3] in metres, diameters [A] in metres, observatory).  `#` lines form the header and carry
+    `observatory=` and `coordsys=`; every other non-blank line is `x y z diameter name`.  Only
+    `coordsys=XYZ` (geocentric ITRF positions) is read: `UTM` and `LOC` lists, which need a datum
+    or a site position, raise ValueError naming the system, as does a malformed line."""
+    obs, coordsys, names, xyz, diam = None, None, [], [], []
+    with open(path, "rt") as f:
+        for no, line in enumerate(f, 1):
+            text = line.strip()
+            if not text:
+                continue
+            if text.startswith("#"):
+                for key, val in re.findall(r"(\w+)\s*=\s*(\S+)", text[1:]):
+                    if key.lower() == "observatory":
+                        obs = val
+                    elif key.lower() == "coordsys":
+                        coordsys = val.upper()
+                continue
+            cols = text.split()
+            if len(cols) < 5:
+                raise ValueError("%s:%d: expected `x y z diameter name`, found %d columns"
+                                 % (path, no, len(cols)))
+            try:
+                vals = [float(c) for c in cols[:4]]
+            except ValueError:
+                raise ValueError("%s:%d: x, y, z and diameter must be numbers" % (path, no)) from None
+            if not np.all(np.isfinite(vals)) or not vals[3] > 0.:
+                raise ValueError("%s:%d: non-finite position or non-positive diameter" % (path, no))
+            xyz.append(vals[:3])
+            diam.append(vals[3])
+            names.append(cols[4])
+    if coordsys is None:
+        raise ValueError("%s: no `# coordsys=` header line" % path)
+    if not coordsys.startswith("XYZ"):
+        raise ValueError("%s: coordsys=%s is not supported (geocentric XYZ lists only)"
+                         % (path, coordsys))
+    if len(names) < 2:
+        raise ValueError("%s: fewer than two antennas" % path)
+    if len(set(names)) != len(names):
+        raise ValueError("%s: antenna names are not unique" % path)
+    return AntennaConfig(names, np.array(xyz, dtype=np.float64), np.array(diam, dtype=np.float64),
+                         obs)
+
+
+def _geodetic_one(x, y, z):
+    """WGS84 latitude, east longitude [rad] of geocentric (x, y, z) [m]: the fixed point of
+    lat = atan2(z, p (1 - e^2 N / (N + h))), which contracts by ~e^2 per step."""
+    e2 = WGS84_F * (2. - WGS84_F)
+    p = np.hypot(x, y)
+    lon = np.arctan2(y, x)
+    lat = np.arctan2(z, p * (1. - e2))
+    for _ in range(12):
+        n = WGS84_A / np.sqrt(1. - e2 * np.sin(lat) ** 2)
+        h = p / np.cos(lat) - n if abs(np.cos(lat)) > 1e-8 else abs(z) - n * (1. - e2)
+        lat = np.arctan2(z, p * (1. - e2 * n / (n + h)))
+    return lat, lon
+
+
+def geodetic(xyz):
+    """WGS84 geodetic latitude and EAST longitude [deg] and the unit local vertical (the ellipsoid
+    normal, in the geocentric frame of `xyz`) of every antenna of `xyz` [A, 3] [m], and the same
+    three of the mean position -> `Geodetic`.  The verticals are what `RTEngine.uv_tracks` takes
+    as `up`; lat0 / lon0 place the array for `observing_plan` and the hour angle."""
+    xyz = np.asarray(xyz, dtype=np.float64).reshape(-1, 3)
+    pts = np.vstack([xyz, xyz.mean(axis=0)[None, :]])
+    ll = np.array([_geodetic_one(*p) for p in pts])
+    lat, lon = ll[:, 0], ll[:, 1]
+    up = np.stack([np.cos(lat) * np.cos(lon), np.cos(lat) * np.sin(lon), np.sin(lat)], axis=1)
+    return Geodetic(np.degrees(lat[:-1]), np.degrees(lon[:-1]), up[:-1], float(np.degrees(lat[-1])),
+                    float(np.degrees(lon[-1])), up[-1])
+
+
+def observing_plan(dec_deg, lat_deg, t_obs_s, t_int_s, min_el_deg, hourangle_h=0.):
+    """The integrations of `t_obs_s` seconds on a target at declination `dec_deg` from latitude
+    `lat_deg` -> (local hour angles in TURNS [n], day of each [n]) -- the reference's rule for
+    splitting an observation over days (classes.py:2510-2550), stated here:
+      * `time_up` = 86400 s if the target is above `min_el_deg` at lower culmination, else
+        int(7200 H) with H = arccos((sin el - sin lat sin dec) / (cos lat cos dec)) in hours;
+        ValueError if the target never reaches the limit;
+      * the days last [time_up] * (t_obs // time_up) and then the remainder WHEN IT IS NOT ZERO
+        (the reference appends a day of length zero);
+      * every day is centred on `hourangle_h` and holds max(1, floor(T / t_int)) integrations of
+        `t_int_s`, placed symmetrically about the centre and taken at their mid-points;
+      * the hour angle advances one turn per SIDEREAL_DAY_S.
+    The reference's eight-scan split of the last day for east-west arrays is not made."""
+    t_obs, t_int = float(t_obs_s), float(t_int_s)
+    if not (t_obs > 0. and t_int > 0. and np.isfinite(t_obs) and np.isfinite(t_int)):
+        raise ValueError("observing_plan: t_obs_s and t_int_s must be positive")
+    dec, lat, el = np.radians(dec_deg), np.radians(lat_deg), np.radians(min_el_deg)
+    low = np.arcsin(np.clip(np.sin(lat) * np.sin(dec) - np.cos(lat) * np.cos(dec), -1., 1.))
+    if low > el:
+        time_up = 86400
+    else:
+        den = np.cos(lat) * np.cos(dec)
+        ch = (np.sin(el) - np.sin(lat) * np.sin(dec)) / den if den != 0. else np.inf
+        if not ch <= 1.:
+            raise ValueError("observing_plan: a target at declination %.3f deg never reaches an "
+                             "elevation of %.3f deg from latitude %.3f deg"
+                             % (dec_deg, min_el_deg, lat_deg))
+        time_up = int(7200. * np.degrees(np.arccos(max(ch, -1.))) / 15.)
+        if time_up < 1:
+            raise ValueError("observing_plan: the target is above %.3f deg for less than a second "
+                             "a day" % min_el_deg)
+    days = [float(time_up)] * int(t_obs // time_up)
+    rest = t_obs - (t_obs // time_up) * time_up
+    if rest > 0.:
+        days.append(rest)
+    ha, day = [], []
+    for d, T in enumerate(days):
+        n = max(1, int(np.floor(T / t_int)))
+        mid = (np.arange(n) + 0.5 - 0.5 * n) * t_int
+        ha.append(float(hourangle_h) / 24. + mid / SIDEREAL_DAY_S)
+        day.append(np.full(n, d, dtype=np.int64))
+    return np.concatenate(ha), np.concatenate(day)
+
+
+def thermal_sigma(sefd_jy, chanwidth_hz, t_int_s, n_pol=2, efficiency=1.):
+    """The rms [Jy] of the real and of the imaginary part of ONE visibility -- one baseline, one
+    channel of `chanwidth_hz`, one integration of `t_int_s`, `n_pol` polarisations averaged --
+    of an array of identical antennas of system-equivalent flux density `sefd_jy`:
+    SEFD / (efficiency sqrt(2 n_pol chanwidth t_int))."""
+    sefd, dnu, t = (np.asarray(x, dtype=np.float64) for x in (sefd_jy, chanwidth_hz, t_int_s))
+    if np.any(~(sefd >= 0.)) or np.any(~(dnu > 0.)) or np.any(~(t > 0.)) or n_pol < 1 or \
+            not efficiency > 0.:
+        raise ValueError("thermal_sigma: sefd_jy >= 0, chanwidth_hz, t_int_s, n_pol and "
+                         "efficiency > 0")
+    return sefd / (float(efficiency) * np.sqrt(2. * n_pol * dnu * t))
+
+
+def image_rms(iw, sigma_k):
+    """The thermal rms [Jy / beam] of a dirty image made with the imaging weights `iw` ([K], or
+    [M, K] -> one value per map) from visibilities whose real and imaginary parts have the rms
+    `sigma_k` (one number, [K], [M, 1] or [M, K]): sqrt(sum w'^2 sigma^2) / sum w'.  Flagged
+    visibilities carry the weight 0 and drop out; a map without weights gives NaN."""
+    w = np.atleast_2d(np.asarray(iw, dtype=np.float64))
+    s = np.broadcast_to(np.asarray(sigma_k, dtype=np.float64), w.shape)
+    live = w > 0.
+    num = np.sqrt(np.sum(np.where(live, (w * s) ** 2, 0.), axis=1))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return num / np.sum(np.where(live, w, 0.), axis=1)
+
+
+def antenna_config_path(directory, telescope, config):
+    """The antenna list of (`telescope`, `config`) in `directory`, found by name without regard
+    to case: `<tel>.<cfg>.cfg`, `<tel>_<cfg>.cfg`, or `<tel>.cfg` when the configuration is
+    '0' (a telescope with one) -> its path, or None."""
+    tel, cfg = str(telescope).lower(), str(config).lower()
+    want = [tel + "." + cfg + ".cfg", tel + "_" + cfg + ".cfg"] + ([tel + ".cfg"] if cfg == "0" else [])
+    try:
+        have = {name.lower(): name for name in sorted(os.listdir(directory), reverse=True)}
+    except OSError:
+        return None
+    for name in want:
+        if name in have:
+            return os.path.join(directory, have[name])
+    return None
+
+
+def observation_grid(max_baseline_m, freq_hz, extent_as):
+    """(cell [arcsec], image side [cells]) the reference images a synthetic observation on
+    (classes.py:2674-2678, 2753-2759): the cell is a quarter of 1 / (longest baseline in
+    wavelengths), rounded to 1e-6 arcsec; the side is ceil(2 extent / cell) for a model that
+    spans `extent_as`, and at least 500."""
+    beam_as = np.degrees(1. / (float(max_baseline_m) * float(freq_hz) / con.c)) * 3600.
+    cell_as = float("%.6f" % (beam_as / 4.))
+    if not cell_as > 0.:
+        raise ValueError("observation_grid: the cell rounds to 0 at 1e-6 arcsec")
+    return cell_as, max(500, int(np.ceil(2. * float(extent_as) / cell_as)))
+
+
+_FOUR_LN2 = 4. * np.log(2.)
+
+
+def beam_quadratic(bmaj_as, bmin_as, bpa_deg, cell_rad):
+    """(A, B, C) [cells^-2] of `RTEngine.restore` / rjp_restore for an elliptical Gaussian clean
+    beam exp(-(A dx^2 + 2 B dx dz + C dz^2)) -- the one place that holds the convention:
+      * `bmaj_as`, `bmin_as` [arcsec] are FWHM: along an axis of FWHM w the beam is
+        exp(-4 ln2 s^2 / w^2);
+      * `bpa_deg` is the position angle of the major axis, from North through East.  North is +z
+        and East is DECREASING ix (RA decreases with ix: `vis_scales`), so the major axis points
+        along (dx, dz) = (-sin bpa, cos bpa): with bpa = 0 it lies along z;
+      * (dx, dz) are in cells of `cell_rad` radians."""
+    cell_as = np.degrees(float(cell_rad)) * 3600.
+    ka = _FOUR_LN2 / (float(bmaj_as) / cell_as) ** 2
+    kb = _FOUR_LN2 / (float(bmin_as) / cell_as) ** 2
+    s, c = np.sin(np.radians(float(bpa_deg))), np.cos(np.radians(float(bpa_deg)))
+    return (float(ka * s * s + kb * c * c), float((kb - ka) * s * c),
+            float(ka * c * c + kb * s * s))
+
+
+def beam_from_quadratic(A, B, C, cell_rad):
+    """The inverse of `beam_quadratic`: (bmaj_as, bmin_as, bpa_deg) of a positive definite
+    (A, B, C) [cells^-2], bpa in (-90, 90]."""
+    lam, vec = np.linalg.eigh(np.array([[A, B], [B, C]], dtype=np.float64))
+    if not lam[0] > 0.:
+        raise ValueError("beam: (A, B, C) is not positive definite")
+    cell_as = np.degrees(float(cell_rad)) * 3600.
+    ex, ez = vec[:, 0]                             # the major axis: the smaller eigenvalue
+    bpa = np.degrees(np.arctan2(-ex, ez))
+    bpa = bpa - 180. if bpa > 90. else bpa + 180. if bpa <= -90. else bpa
+    return (float(np.sqrt(_FOUR_LN2 / lam[0]) * cell_as),
+            float(np.sqrt(_FOUR_LN2 / lam[1]) * cell_as), float(bpa))
+
+
+def fit_beam(patch):
+    """(A, B, C) [cells^-2] of the Gaussian that fits the main lobe of a dirty beam: `patch` is a
+    2-D array [odd, odd] around the beam's centre pixel; a linear least-squares fit of
+    -ln(patch / centre) = A dx^2 + 2 B dx dz + C dz^2 over the pixels >= half the centre value
+    that are connected to the centre (4-neighbours), as tclean fits its restoring beam."""
+    b = np.asarray(patch, dtype=np.float64)
+    if b.ndim != 2 or b.shape[0] % 2 == 0 or b.shape[1] % 2 == 0:
+        raise ValueError("fit_beam: `patch` must be 2-D with odd sizes")
+    cx, cz = (b.shape[0] - 1) // 2, (b.shape[1] - 1) // 2
+    if not (np.isfinite(b[cx, cz]) and b[cx, cz] > 0.):
+        raise ValueError("fit_beam: the centre of the beam must be positive")
+    b = b / b[cx, cz]
+    lobe = np.zeros(b.shape, dtype=bool)
+    todo = [(cx, cz)]
+    while todo:
+        i, j = todo.pop()
+        if 0 <= i < b.shape[0] and 0 <= j < b.shape[1] and not lobe[i, j] and b[i, j] >= 0.5:
+            lobe[i, j] = True
+            todo += [(i + 1, j), (i - 1, j), (i, j + 1), (i, j - 1)]
+    ii, jj = np.nonzero(lobe)
+    dx, dz = (ii - cx).astype(np.float64), (jj - cz).astype(np.float64)
+    design = np.stack([dx * dx, 2. * dx * dz, dz * dz], axis=1)
+    if np.linalg.matrix_rank(design) < 3:
+        raise ValueError("fit_beam: the main lobe covers too few pixels (the beam is not resolved "
+                         "by the cell)")
+    sol = np.linalg.lstsq(design, -np.log(b[ii, jj]), rcond=None)[0]
+    A, B, C = (float(x) for x in sol)
+    if not (A > 0. and C > 0. and A * C > B * B):
+        raise ValueError("fit_beam: the fitted form is not positive definite")
+    return A, B, C
+
+
+def gauss_start(img, nx, nz, beam_abc, box=None, mask=None):
+    """The default start of `RTEngine.gaussfit` -> tensor [M, 6] beside `img`: per map the
+    counting pixel (inside `box`, non-zero in `mask`, finite) of largest |I|, its value and
+    position, and the clean beam's (A, B, C) -- a point source as the beam sees it.  `img`: a
+    float64 tensor of M * nx * nz values; `beam_abc`: one (A, B, C) or one per map.  Plain torch,
+    batched, nothing goes to the host.  A map without a counting pixel gets a NaN peak, which
+    `gaussfit` reports as status 3.  (The reference's own estimate comes from the model's
+    tau = 1 surface, classes.py:2718-2743; a caller may pass any start instead.)"""
+    import torch
+    nx, nz = int(nx), int(nz)
+    t = img.reshape(-1, nx, nz)
+    M = int(t.shape[0])
+    ok = torch.zeros(nx, nz, dtype=torch.bool, device=t.device)
+    i0, i1, j0, j1 = (0, nx - 1, 0, nz - 1) if box is None else (int(x) for x in np.ravel(box))
+    ok[i0:i1 + 1, j0:j1 + 1] = True
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor):
+            mask = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0))
+        ok &= (mask != 0).to(t.device).reshape(nx, nz)
+    ok = ok.unsqueeze(0) & torch.isfinite(t)
+    mag = torch.where(ok, t.abs(), torch.full_like(t, -1.0)).reshape(M, -1)
+    top, idx = mag.max(dim=1)
+    val = t.reshape(M, -1).gather(1, idx.unsqueeze(1)).squeeze(1)
+    val = torch.where(top >= 0, val, torch.full_like(val, float("nan")))
+    abc = np.asarray(beam_abc, dtype=np.float64).reshape(-1, 3)
+    if abc.shape[0] not in (1, M):
+        raise ValueError("gauss_start: `beam_abc` must be one (A, B, C) or one per map (%d)" % M)
+    abc = torch.from_numpy(np.array(np.broadcast_to(abc, (M, 3)))).to(t.device)
+    pos = torch.stack([torch.div(idx, nz, rounding_mode="floor"), idx % nz], dim=1)
+    return torch.cat([val.unsqueeze(1), pos.to(torch.float64), abc], dim=1).contiguous()
+
+
+def gauss_results(theta, cov, chi2, npix, beam_abc, cell_rad, rms=None, shape=None, status=None):
+    """What CASA imfit reports, from the outputs of `RTEngine.gaussfit` (host arrays; pure NumPy)
+    -> one dict per map.  Conventions as in `beam_quadratic`; `beam_abc`: the clean beam, one
+    (A, B, C) or one per map; `cell_rad`: the cell in radians.
+      * 'peak' [Jy / beam] = S;  'I' = {'val': S sqrt(det Q_beam / det Q_fit), 'unit': 'Jy'}, the
+        integrated flux (Q = [[A, B], [B, C]]);
+      * 'x0', 'z0' [pixels]; with `shape` = (nx, nz) also 'east_as', 'north_as', the offsets from
+        the map centre ((nx-1)/2, (nz-1)/2) in arcsec under the sky convention of `vis_scales`
+        (East = DECREASING ix, North = +z);
+      * 'maj_as', 'min_as', 'pa_deg': the fitted size (`beam_from_quadratic`);
+      * 'deconvolved': {'maj_as', 'min_as', 'pa_deg'} of Sigma_src = (2 Q_fit)^-1 - (2 Q_beam)^-1,
+        or None with 'point_source' True where that is not positive definite;
+      * with `rms` [Jy / beam] (one number or one per map) the 1-sigma errors 'peak_err',
+        'x0_err', 'z0_err', 'abc_err' and 'Ierr' = {'val', 'unit'} from the covariance
+        rms^2 Omega_b (J^T J)^-1, Omega_b = pi / sqrt(det Q_beam) cells: the usual inflation for
+        noise that is correlated over a beam; Ierr by first-order propagation through
+        I(S, A, B, C).  This is a STATED APPROXIMATION, not the expressions of Condon (1997)
+        that CASA uses.  Without `rms`: None;
+      * 'chi2', 'npix', and 'status' where given.
+    A map whose fit is not finite and positive definite (status 3) gets NaN / None entries."""
+    theta = np.asarray(theta, dtype=np.float64).reshape(-1, 6)
+    M = theta.shape[0]
+    cov = np.asarray(cov, dtype=np.float64).reshape(M, 21)
+    chi2, npix = np.asarray(chi2, dtype=np.float64).reshape(M), np.asarray(npix).reshape(M)
+    beam = np.broadcast_to(np.asarray(beam_abc, dtype=np.float64).reshape(-1, 3), (M, 3))
+    rms_m = None if rms is None else np.broadcast_to(np.asarray(rms, dtype=np.float64), (M,))
+    cell_as = np.degrees(float(cell_rad)) * 3600.
+    nan = float("nan")
+    out = []
+    for m in range(M):
+        S, x0, z0, A, B, C = (float(v) for v in theta[m])
+        bA, bB, bC = (float(v) for v in beam[m])
+        det, bdet = A * C - B * B, bA * bC - bB * bB
+        d = {"peak": S, "x0": x0, "z0": z0, "chi2": float(chi2[m]), "npix": int(npix[m]),
+             "I": {"val": nan, "unit": "Jy"}, "Ierr": {"val": None, "unit": "Jy"},
+             "maj_as": nan, "min_as": nan, "pa_deg": nan, "deconvolved": None,
+             "point_source": False, "peak_err": None, "x0_err": None, "z0_err": None,
+             "abc_err": None}
+        if status is not None:
+            d["status"] = int(np.asarray(status).reshape(M)[m])
+        if shape is not None:
+            d["east_as"] = float(-(x0 - (int(shape[0]) - 1) / 2.) * cell_as)
+            d["north_as"] = float((z0 - (int(shape[1]) - 1) / 2.) * cell_as)
+        good = np.all(np.isfinite(theta[m])) and A > 0. and C > 0. and det > 0. and bdet > 0.
+        if not good:
+            out.append(d)
+            continue
+        flux = S * np.sqrt(bdet / det)
+        d["I"]["val"] = float(flux)
+        d["maj_as"], d["min_as"], d["pa_deg"] = beam_from_quadratic(A, B, C, cell_rad)
+        # covariance matrices of the Gaussians: Sigma = (2 Q)^-1
+        sig = (np.array([[C, -B], [-B, A]]) / (2. * det)
+               - np.array([[bC, -bB], [-bB, bA]]) / (2. * bdet))
+        sdet = sig[0, 0] * sig[1, 1] - sig[0, 1] * sig[1, 0]
+        if sig[0, 0] > 0. and sig[1, 1] > 0. and sdet > 0.:
+            q = np.array([[sig[1, 1], -sig[0, 1]], [-sig[0, 1], sig[0, 0]]]) / (2. * sdet)
+            mj, mn, pa = beam_from_quadratic(q[0, 0], q[0, 1], q[1, 1], cell_rad)
+            d["deconvolved"] = {"maj_as": mj, "min_as": mn, "pa_deg": pa}
+        else:
+            d["point_source"] = True
+        if rms_m is not None and np.all(np.isfinite(cov[m])):
+            N = np.zeros((6, 6))
+            k = 0
+            for i in range(6):
+                for j in range(i, 6):
+                    N[i, j] = N[j, i] = cov[m, k]
+                    k += 1
+            try:
+                P = rms_m[m] ** 2 * (np.pi / np.sqrt(bdet)) * np.linalg.inv(N)
+            except np.linalg.LinAlgError:
+                P = None
+            if P is not None and np.all(np.diag(P) >= 0.):
+                sd = np.sqrt(np.diag(P))
+                d["peak_err"], d["x0_err"], d["z0_err"] = float(sd[0]), float(sd[1]), float(sd[2])
+                d["abc_err"] = (float(sd[3]), float(sd[4]), float(sd[5]))
+                grad = np.array([flux / S if S != 0. else np.sqrt(bdet / det), 0., 0.,
+                                 -flux * C / (2. * det), flux * B / det, -flux * A / (2. * det)])
+                d["Ierr"]["val"] = float(np.sqrt(grad @ P @ grad))
+        out.append(d)
+    return out
+
+
+# -- result types -----------------------------------------------------------------------------------
+# what `JetModel.clean_image_ff` / `clean_image_rrl` return
+class CleanResult(collections.namedtuple(
+        "CleanResult", ["image", "residual", "model", "components", "beam", "peak_residual"])):
+    """The six products of a CLEAN as a tuple, and `imfit`: None, or with the `imfit` keyword one
+    dict per map (`engine.gauss_results`) -- an attribute beside the tuple, so that code which
+    unpacks the six products keeps working.  `_replace` carries `imfit` over (and takes it as a
+    keyword); `_make`, which builds from the six values alone, leaves it None."""
+
+    def __new__(cls, *args, imfit=None, **kw):
+        self = super().__new__(cls, *args, **kw)
+        self.imfit = imfit
+        return self
+
+    imfit = None
+
+    def _replace(self, **kw):
+        imfit = kw.pop("imfit", self.imfit)
+        out = super()._replace(**kw)
+        out.imfit = imfit
+        return out
+
+
+# what `JetModel.uv_tracks` returns: device tensors u_m, v_m, w_m [n_t * n_bl] (visibility
+# k = t n_bl + b), host arrays ha_h, day [n_t] and ant1, ant2 [n_bl], and the longest baseline
+UVTracks = collections.namedtuple("UVTracks", ["u_m", "v_m", "w_m", "ha_h", "day", "ant1", "ant2",
+                                               "max_baseline_m"])
+# what `JetModel.observe_ff` / `observe_rrl` return
+Observation = collections.namedtuple("Observation", ["tracks", "vis_clean", "vis", "sigma",
+                                                     "image_rms", "clean"])
+
+
+class Weighting(collections.namedtuple("Weighting", ["scheme", "robust", "weights"])):
+    """An imaging-weight scheme as ONE value for the `weights` of `JetModel.dirty_image_ff`, whose
+    parameter list is fixed: `scheme` None / "natural" / "uniform" / "briggs", `robust` (Briggs
+    only) and the data `weights` [K] the scheme starts from (None = all ones).  The other imaging
+    methods take `weighting=` and `robust=` beside their `weights`."""
+    __slots__ = ()
+
+    def __new__(cls, scheme="briggs", robust=0.5, weights=None):
+        return super().__new__(cls, scheme, robust, weights)
+
+
+def _split_weights(weights):
+    """The `weights` of `dirty_image_ff` -> the data weights, the scheme and its robustness: a
+    `Weighting` carries all three, anything else is data weights, naturally weighted."""
+    weighting, robust = None, 0.5
+    if isinstance(weights, Weighting):
+        weights, weighting, robust = weights.weights, weights.scheme, weights.robust
+    _weighting_mode(weighting)
+    return weights, weighting, robust
+
+
+def _weighting_mode(weighting):
+    """None for natural weights (None or "natural": no kernel, the path as it was), else the mode
+    of `RTEngine.uv_weights`."""
+    if weighting is None or weighting == "natural":
+        return None
+    if weighting not in ("uniform", "briggs"):
+        raise ValueError("imaging weights: `weighting` must be None, 'natural', 'uniform' or "
+                         "'briggs'")
+    return weighting
+
+
+def _col(eng, s):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(s, dtype=np.float64)).to(eng.device)[:, None]
+
+
+def _mfs_points(eng, u_d, v_d, su, sv, w_d):
+    """The F K points of F channels as ONE visibility set, channel by channel: the baselines in
+    cycles per cell (to be used with the scales [1.0]) and the data weights repeated."""
+    return ((_col(eng, su) * u_d[None, :]).reshape(-1), (_col(eng, sv) * v_d[None, :]).reshape(-1),
+            w_d.repeat(len(su)) if w_d is not None else None)
+
+
+def _imaging_weights(eng, u_d, v_d, su, sv, w_d, ni, nj, mode, robust, mfs):
+    """The imaging weights of one chunk of channels from ONE `RTEngine.uv_weights` call on the
+    ni x nj image grid -> device tensor [F, K], a density per channel; `mfs`: [1, F K], one
+    density over all F K points in cycles per cell (scale 1), as `_dirty_images` images them."""
+    if mfs:
+        u_d, v_d, w_d = _mfs_points(eng, u_d, v_d, su, sv, w_d)
+        su = sv = [1.0]
+    return eng.uv_weights(u_d, v_d, su, sv, ni, nj, w=w_d, mode=mode, robust=robust)
+
+
+class Imager:
+    """Visibilities, images, synthetic observations and Gaussian fits of the flux maps of an
+    nx x nz grid of `csize_au` cells at `dist_pc`, through `engine` (an `RTEngine`).  Maps and
+    visibilities are device tensors; `stack_bytes`: the most one engine call of a chunk loop takes."""
+    BEAM_PATCH = 33          # side of the central patch of the dirty beam that `fit_beam` sees
+
+    def __init__(self, engine, nx, nz, csize_au, dist_pc, stack_bytes):
+        self.engine, self.nx, self.nz = engine, nx, nz
+        self.csize_au, self.dist_pc, self.stack_bytes = csize_au, dist_pc, int(stack_bytes)
+
+    def model_vis(self, maps, freqs, u, v):
+        """`RTEngine.vis` of the flux maps [F, nx * nz] at (`u`, `v`) [m] -> complex device [F, K]."""
+        su, sv = vis_scales(freqs, self.csize_au, self.dist_pc)
+        return self.engine.vis(maps, self.nx, self.nz, su, sv, u, v)
+
+    def _unit_vis(self, F, K):
+        """Visibilities that are all 1 (what a dirty beam is the image of) -> complex [F, K]."""
+        import torch
+        return torch.ones(F, K, dtype=torch.complex128, device=self.engine.device)
+
+    # ------------------------------------------------------------------ dirty images ----
+    def _image_grid(self, shape, cell_as):
+        """(ni, nj, cell [rad]) of an imaging grid: the model's own by default."""
+        ni, nj = (self.nx, self.nz) if shape is None else (int(shape[0]), int(shape[1]))
+        if ni < 1 or nj < 1:
+            raise ValueError("dirty image: `shape` must be two positive sizes")
+        if cell_as is None:
+            cell = np.arctan((self.csize_au * con.au) / (self.dist_pc * con.parsec))
+        else:
+            cell = np.radians(float(cell_as) / 3600.)
+            if not (np.isfinite(cell) and cell > 0.):
+                raise ValueError("dirty image: `cell_as` must be a positive number of arcseconds")
+        return ni, nj, float(cell)
+
+    def _dirty_images(self, V, u_d, v_d, freqs, weights, shape, cell_as, mfs, device=False,
+                      weighting=None, robust=0.5, iw=None):
+        """Dirty images [Jy / beam] of the visibilities `V` (complex device tensor [F, K]) at the
+        baselines (`u_d`, `v_d`) [m] -> host array (F, ni, nj), or (1, ni, nj) with `mfs`;
+        `device=True`: the same numbers as a device tensor [F or 1, ni * nj] (for `_clean_images`).
+        `RTEngine.vis_adjoint` on chunks of channels whose images stay under `stack_bytes`
+        (K10's `_vis_chunk` rule on the imaging grid), divided by the sum of the weights of the
+        baselines that are not flagged; nothing but the images leaves the device, chunk by chunk.
+        `weighting` "uniform" / "briggs" (with `robust`): the imaging weights of every chunk come
+        from ONE `RTEngine.uv_weights` call on this image's grid, a density per channel (one over
+        all F K points with `mfs`), are multiplied into V on the device and the image is divided
+        by the channel's own sum of them; the chunks then also keep the [F, K] weights under
+        `stack_bytes`.  `iw`: those weights already made ([F, K], or [1, F K] with `mfs`: what
+        `_clean_images` shares between the image and the larger beam grid)."""
+        import torch
+        eng = self.engine
+        ni, nj, cell = self._image_grid(shape, cell_as)
+        su, sv = image_scales(freqs, cell)
+        F, K = int(V.shape[0]), int(V.shape[1])
+        w_d = eng._device_f64(weights) if weights is not None else None
+        if w_d is not None and w_d.numel() != K:
+            raise ValueError("dirty image: `weights` must have one entry per baseline (%d)" % K)
+        mode = _weighting_mode(weighting)
+        weighted = mode is not None or iw is not None
+        # what a chunk is.  Natural weights are the engine's `w`, and every image is divided by their
+        # sum over the unflagged baselines; imaging weights go into V, each image's own sum divides.
+        step = self.stack_bytes // (ni * nj * 8)
+        if weighted:
+            step = min(step, self.stack_bytes // (K * 8))
+        else:
+            good = torch.isfinite(u_d) & torch.isfinite(v_d)
+            if w_d is not None:
+                good = good & torch.isfinite(w_d)
+            wsum = (torch.where(good, w_d, torch.zeros_like(w_d)).sum() if w_d is not None
+                    else good.sum().to(torch.float64))
+        if mfs:
+            # one chunk of one image: one visibility set of F K points, baselines in cycles per
+            # cell, scale 1
+            V, step = V.reshape(1, F * K), 1
+            u_d, v_d, w_d = _mfs_points(eng, u_d, v_d, su, sv, w_d)
+            su = sv = [1.0]
+            if not weighted:
+                wsum = wsum * F
+        n, step = int(V.shape[0]), max(1, step)
+        out = [] if device else np.zeros((n, ni, nj))
+        for f0 in range(0, n, step):
+            sl = slice(f0, f0 + step)
+            vis = V[sl]
+            if weighted:
+                wc = iw[sl] if iw is not None else _imaging_weights(
+                    eng, u_d, v_d, su[sl], sv[sl], w_d, ni, nj, mode, robust, False)
+                vis = vis * wc
+                # (a full reduction with `mfs`, row sums without: two reductions, kept apart)
+                wsum = wc.sum() if mfs else wc.sum(dim=1)[:, None]
+                del wc
+            img = eng.vis_adjoint(vis.contiguous(), ni, nj, su[sl], sv[sl], u_d, v_d,
+                                  None if weighted else w_d) / wsum
+            del vis
+            if device:
+                out.append(img)
+            else:
+                out[sl] = img.cpu().numpy().reshape(-1, ni, nj)
+            del img
+        return torch.cat(out, dim=0) if device else out
+
+    def imaging_weights(self, u_m, v_m, freq, weights=None, shape=None, cell_as=None,
+                        weighting="briggs", robust=0.5, mfs=False):
+        """See `JetModel.imaging_weights`."""
+        import torch
+        eng = self.engine
+        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
+        mode = _weighting_mode(weighting)     # (refuses an unknown scheme before any work)
+        ni, nj, cell = self._image_grid(shape, cell_as)
+        su, sv = image_scales(freqs, cell)
+        u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
+        F, K = len(freqs), int(u_d.numel())
+        w_d = eng._device_f64(weights) if weights is not None else None
+        if v_d.numel() != K or (w_d is not None and w_d.numel() != K):
+            raise ValueError("imaging weights: u, v and weights must have one entry per baseline")
+        w1 = w_d if w_d is not None else torch.ones(K, dtype=torch.float64, device=eng.device)
+        names = ("sum_w", "sum_w2", "f2", "counted", "out_of_range", "shift")
+        if mode is None:
+            ok = torch.isfinite(u_d) & torch.isfinite(v_d) & torch.isfinite(w1) & (w1 >= 0)
+            row = torch.where(ok, w1, torch.zeros_like(w1)).cpu().numpy()
+            n = 1 if mfs else F
+            st = {k: np.zeros(n) for k in names}
+            st["sum_w"][:] = row.sum() * (F if mfs else 1)
+            st["counted"][:] = np.count_nonzero(ok.cpu().numpy()) * (F if mfs else 1)
+            st["sum_wout"], st["noise_factor"] = st["sum_w"].copy(), np.ones(n)
+            return np.tile(row, (F, 1)), st
+        out, stats, extra = np.zeros((F, K)), [], []
+        step = F if mfs else max(1, self.stack_bytes // (K * 8))
+        for f0 in range(0, F, step):
+            sl = slice(f0, f0 + step)
+            iw = _imaging_weights(eng, u_d, v_d, su[sl], sv[sl], w_d, ni, nj, mode, robust, mfs)
+            wd = w1.repeat(F)[None, :] if mfs else w1[None, :]
+            live = (iw > 0) & (wd > 0)
+            ratio = torch.where(live, iw * iw / torch.where(live, wd, torch.ones_like(wd)),
+                                torch.zeros_like(iw))
+            extra.append(torch.stack([iw.sum(dim=1), ratio.sum(dim=1),
+                                      torch.where(live, wd.expand_as(iw), torch.zeros_like(iw))
+                                      .sum(dim=1)], dim=1).cpu().numpy())
+            stats.append(eng.last_uv_weight_stats.cpu().numpy())
+            out[sl] = iw.cpu().numpy().reshape(-1, K)
+            del iw
+        stats, extra = np.concatenate(stats, axis=0), np.concatenate(extra, axis=0)
+        st = {k: stats[:, i].copy() for i, k in enumerate(names)}
+        st["sum_wout"] = extra[:, 0]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            st["noise_factor"] = np.sqrt(extra[:, 1] * extra[:, 2]) / extra[:, 0]
+        return out, st
+
+    # ------------------------------------------------------------------ CLEAN ----
+    def _clean_mask(self, mask, ni, nj):
+        """None, a box (i0, i1, j0, j1) of inclusive pixel corners (as the reference hands
+        tclean a box) or a boolean array (ni, nj) -> None or a bool array (ni, nj)."""
+        if mask is None:
+            return None
+        m = np.asarray(mask)
+        if m.ndim == 1 and m.size == 4:
+            i0, i1, j0, j1 = (int(x) for x in m)
+            if not (0 <= i0 <= i1 < ni and 0 <= j0 <= j1 < nj):
+                raise ValueError("clean: the box (i0, i1, j0, j1) must lie inside the image")
+            out = np.zeros((ni, nj), dtype=bool)
+            out[i0:i1 + 1, j0:j1 + 1] = True
+            return out
+        if m.shape != (ni, nj):
+            raise ValueError("clean: `mask` must be None, a box (i0, i1, j0, j1) or an array of "
+                             "the image's shape (%d, %d)" % (ni, nj))
+        return m != 0
+
+    def _clean_images(self, V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
+                      threshold_jy, mask, beam, psf_shape, imfit=None, weighting=None, robust=0.5):
+        """Hogbom CLEAN of the dirty images of `V` (see `JetModel.clean_image_ff`), in chunks of
+        channels whose dirty images AND beams stay under `stack_bytes`.  Per chunk, on the device:
+        `_dirty_images` of V and of unit visibilities (the beams, on the `psf_shape` grid),
+        `RTEngine.clean`, `RTEngine.restore`; only the central patch of each beam goes to the
+        host before the end (for `fit_beam`).  With `weighting` "uniform" / "briggs" the chunk's
+        imaging weights are computed ONCE, on the image's grid (never the larger beam grid), and
+        image and beam share them; the chunks then also keep the [F, K] weights under
+        `stack_bytes`."""
+        import torch
+        eng = self.engine
+        ni, nj, cell = self._image_grid(shape, cell_as)
+        pi_, pj = (2 * ni - 1, 2 * nj - 1) if psf_shape is None else (int(psf_shape[0]),
+                                                                      int(psf_shape[1]))
+        if pi_ < 1 or pj < 1 or pi_ % 2 == 0 or pj % 2 == 0:
+            raise ValueError("clean: `psf_shape` must be two odd positive sizes")
+        niter = int(niter)
+        # (one threshold, or one per image: what `_observe` derives from each image's own rms)
+        thr = np.asarray(threshold_jy, dtype=np.float64).reshape(-1)
+        if niter < 1 or not (0. < float(gain) <= 1.) or not np.all(thr >= 0.) or \
+                thr.size not in (1, 1 if mfs else int(V.shape[0])):
+            raise ValueError("clean: niter >= 1, 0 < gain <= 1 and threshold_jy >= 0")
+        mk = self._clean_mask(mask, ni, nj)
+        F, K = int(V.shape[0]), int(V.shape[1])
+        n_out = 1 if mfs else F
+        ones = self._unit_vis(F, K)
+        fit_opts = self._imfit_options(imfit, mask, ni, nj)
+        res = CleanResult(image=np.zeros((n_out, ni, nj)), residual=np.zeros((n_out, ni, nj)),
+                          model=np.zeros((n_out, ni, nj)), components=[], beam=[],
+                          peak_residual=np.zeros(n_out), imfit=None if fit_opts is None else [])
+        step = F if mfs else max(1, self.stack_bytes // ((ni * nj * 3 + pi_ * pj) * 8))
+        hi, hj = min(self.BEAM_PATCH, pi_) // 2, min(self.BEAM_PATCH, pj) // 2
+        mode = _weighting_mode(weighting)
+        if mode is not None:
+            w_d = eng._device_f64(weights) if weights is not None else None
+            if w_d is not None and w_d.numel() != K:
+                raise ValueError("dirty image: `weights` must have one entry per baseline (%d)" % K)
+            if not mfs:
+                step = max(1, min(step, self.stack_bytes // (K * 8)))
+        for f0 in range(0, F, step):
+            sl = slice(f0, f0 + step)
+            iw = None
+            if mode is not None:
+                isu, isv = image_scales(freqs[sl], cell)
+                iw = _imaging_weights(eng, u_d, v_d, isu, isv, w_d, ni, nj, mode, robust, mfs)
+            dirty = self._dirty_images(V[sl], u_d, v_d, freqs[sl], weights, (ni, nj), cell_as,
+                                       mfs, device=True, iw=iw)
+            psf = self._dirty_images(ones[sl], u_d, v_d, freqs[sl], weights, (pi_, pj), cell_as,
+                                     mfs, device=True, iw=iw)
+            del iw
+            M = int(dirty.shape[0])
+            if beam is None:
+                ci, cj = (pi_ - 1) // 2, (pj - 1) // 2
+                patch = psf.reshape(M, pi_, pj)[:, ci - hi:ci + hi + 1, cj - hj:cj + hj + 1]
+                abc = [fit_beam(p) for p in patch.cpu().numpy()]
+            else:
+                abc = [beam_quadratic(beam[0], beam[1], beam[2], cell)] * M
+            model = torch.zeros_like(dirty)
+            cpix, cflux, ncomp, peak = eng.clean(dirty, ni, nj, psf, pi_, pj, niter, gain,
+                                                 float(thr[0]) if thr.size == 1 else thr[f0:f0 + M],
+                                                 mask=mk, model=model)
+            image = eng.restore(cpix, cflux, ncomp, abc, ni, nj, add=dirty)
+            o = slice(f0, f0 + M)
+            if fit_opts is not None:
+                res.imfit.extend(self._imfit_images(image, ni, nj, abc, cell, fit_opts, o))
+            res.image[o] = image.cpu().numpy().reshape(M, ni, nj)
+            res.residual[o] = dirty.cpu().numpy().reshape(M, ni, nj)
+            res.model[o] = model.cpu().numpy().reshape(M, ni, nj)
+            res.peak_residual[o] = peak.cpu().numpy()
+            hp, hf, hn = cpix.cpu().numpy(), cflux.cpu().numpy(), ncomp.cpu().numpy()
+            for m in range(M):
+                n = int(hn[m])
+                res.components.append(np.stack([hp[m, :n] // nj, hp[m, :n] % nj, hf[m, :n]],
+                                               axis=1).astype(np.float64).reshape(n, 3))
+                res.beam.append(beam_from_quadratic(*abc[m], cell))
+            del dirty, psf, model, image, cpix, cflux, ncomp, peak
+        return res
+
+    # ------------------------------------------------------------------ synthetic observations ----
+    def uv_tracks(self, antennalist, dec_deg, t_obs_s, t_int_s, min_el_deg=None, hourangle_h=0.):
+        """See `JetModel.uv_tracks`, which takes `dec_deg` from the model's target."""
+        cfg = antennalist if isinstance(antennalist, AntennaConfig) else \
+            read_antenna_config(antennalist)
+        geo = geodetic(cfg.xyz)
+        ha, day = observing_plan(dec_deg, geo.lat0_deg, t_obs_s, t_int_s,
+                                 0. if min_el_deg is None else min_el_deg, hourangle_h)
+        flags = dict(up=geo.up, min_el_rad=np.radians(min_el_deg)) if min_el_deg is not None else {}
+        u, v, w = self.engine.uv_tracks(cfg.xyz, ha - geo.lon0_deg / 360., np.radians(dec_deg),
+                                        **flags)
+        a1, a2 = np.triu_indices(len(cfg.names), 1)
+        bmax = float(np.sqrt(((cfg.xyz[a2] - cfg.xyz[a1]) ** 2).sum(axis=1)).max())
+        return UVTracks(u.reshape(-1), v.reshape(-1), w.reshape(-1), ha * 24., day,
+                        a1.astype(np.int32), a2.astype(np.int32), bmax)
+
+    def _observe(self, maps, freqs, tracks, t_int_s, sigma_jy, sefd_jy, chanwidth_hz, seed,
+                 nsigma, weights, shape, cell_as, mfs, niter, gain, threshold_jy, mask, beam,
+                 psf_shape, imfit, weighting, robust):
+        """`JetModel.observe_*` after the maps [F, nx * nz]: visibilities, noise, image rms, CLEAN."""
+        F = len(freqs)
+        if sigma_jy is not None and sefd_jy is not None:
+            raise ValueError("observe: give `sigma_jy` or `sefd_jy`, not both")
+        if sefd_jy is not None:
+            if chanwidth_hz is None:
+                raise ValueError("observe: `sefd_jy` needs `chanwidth_hz`")
+            sigma_jy = thermal_sigma(sefd_jy, chanwidth_hz, t_int_s)
+        sigma = np.asarray(0. if sigma_jy is None else sigma_jy, dtype=np.float64).reshape(-1)
+        if sigma.size not in (1, F) or not np.all(np.isfinite(sigma) & (sigma >= 0.)):
+            raise ValueError("observe: `sigma_jy` must be one finite rms >= 0 or one per channel")
+        sigma = np.broadcast_to(sigma, (F,)).copy()
+        if not (float(nsigma) >= 0.):
+            raise ValueError("observe: `nsigma` must be >= 0")
+        u_d, v_d = tracks.u_m, tracks.v_m
+        V0 = self.model_vis(maps, freqs, u_d, v_d)
+        noisy = bool(np.any(sigma > 0.))
+        # (every visibility has its own counter k = t n_bl + b: an independent draw per day,
+        # integration, baseline and channel)
+        V = self.engine.vis_noise(V0, sigma, seed=seed) if noisy else V0
+        rms = np.zeros(1 if mfs else F)
+        if noisy:
+            iw, _ = self.imaging_weights(u_d, v_d, freqs, weights=weights, shape=shape,
+                                         cell_as=cell_as, weighting=weighting, robust=robust,
+                                         mfs=mfs)
+            rms = image_rms(iw.reshape(1, -1), np.repeat(sigma, iw.shape[1])) if mfs else \
+                image_rms(iw, sigma[:, None])
+            del iw
+        thr = threshold_jy
+        if float(nsigma) > 0.:
+            thr = np.maximum(float(thr), float(nsigma) * np.where(np.isfinite(rms), rms, 0.))
+        if imfit is not None and imfit is not False and noisy:
+            imfit = {} if imfit is True else dict(imfit)
+            if imfit.get("rms") is None:
+                imfit["rms"] = rms
+        res = self._clean_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
+                                 thr, mask, beam, psf_shape, imfit, weighting=weighting,
+                                 robust=robust)
+        v0 = V0.cpu().numpy()
+        return Observation(tracks, v0, V.cpu().numpy() if noisy else v0.copy(), sigma, rms, res)
+
+    # ------------------------------------------------------------------ imfit ----
+    def _imfit_options(self, imfit, mask, ni, nj):
+        """The `imfit` keyword of `clean_image_*` / `imfit` -> None or a dict (box, theta0,
+        n_iter, rms); the default box is the bounding box of `mask` (as `_clean_mask` reads it)."""
+        if imfit is None or imfit is False:
+            return None
+        opts = {} if imfit is True else dict(imfit)
+        bad = set(opts) - {"box", "theta0", "n_iter", "rms"}
+        if bad:
+            raise ValueError("imfit: unknown option(s) %s" % sorted(bad))
+        box = opts.get("box")
+        if box is None:
+            mk = self._clean_mask(mask, ni, nj)
+            if mk is not None and mk.any():
+                ii, jj = np.nonzero(mk)
+                box = (int(ii.min()), int(ii.max()), int(jj.min()), int(jj.max()))
+            else:
+                box = (0, ni - 1, 0, nj - 1)
+        box = tuple(int(x) for x in np.ravel(box))
+        if len(box) != 4 or not (0 <= box[0] <= box[1] < ni and 0 <= box[2] <= box[3] < nj):
+            raise ValueError("imfit: the box (i0, i1, j0, j1) must lie inside the image")
+        return {"box": box, "theta0": opts.get("theta0"), "n_iter": int(opts.get("n_iter", 60)),
+                "rms": opts.get("rms")}
+
+    def _imfit_images(self, image, ni, nj, abc, cell, opts, sl=None):
+        """One Gaussian per image of the device stack `image` [M, ni * nj] (`RTEngine.gaussfit`)
+        -> list of M dicts (`gauss_results`).  `abc`: the clean beams, one per map; `sl`: the
+        rows of a `theta0` / `rms` given per map that belong to this stack."""
+        import torch
+
+        def pick(a, w):
+            # (a start or an rms per map: a host array or a tensor; else one for all)
+            if a is None or sl is None:
+                return a
+            if isinstance(a, torch.Tensor):
+                return a[sl] if a.dim() >= w else a
+            return np.asarray(a)[sl] if np.ndim(a) >= w else a
+        theta0 = pick(opts["theta0"], 2)
+        if theta0 is None:
+            theta0 = gauss_start(image, ni, nj, abc, box=opts["box"])
+        fit = self.engine.gaussfit(image, ni, nj, theta0, box=opts["box"], n_iter=opts["n_iter"])
+        host = {k: v.cpu().numpy() for k, v in fit.items()}
+        rms = pick(opts["rms"], 1)
+        if isinstance(rms, torch.Tensor):
+            rms = rms.detach().cpu().numpy()
+        return gauss_results(host["theta"], host["cov"], host["chi2"], host["npix"], abc, cell,
+                             rms=rms, shape=(ni, nj), status=host["status"])
+
+    def imfit(self, images, beam, cell_as=None, box=None, theta0=None, n_iter=60, rms=None):
+        """See `JetModel.imfit`."""
+        import torch
+        eng = self.engine
+        if isinstance(images, torch.Tensor):
+            img = images.to(device=eng.device, dtype=torch.float64)
+        else:
+            img = torch.from_numpy(np.ascontiguousarray(images, dtype=np.float64)).to(eng.device)
+        if img.dim() == 2:
+            img = img.unsqueeze(0)
+        if img.dim() != 3:
+            raise ValueError("imfit: `images` must be (F, ni, nj) or (ni, nj)")
+        M, ni, nj = (int(x) for x in img.shape)
+        _, _, cell = self._image_grid((ni, nj), cell_as)
+        beams = np.asarray(beam, dtype=np.float64).reshape(-1, 3)
+        if beams.shape[0] not in (1, M):
+            raise ValueError("imfit: `beam` must be one (bmaj_as, bmin_as, bpa_deg) or one per image")
+        abc = [beam_quadratic(b[0], b[1], b[2], cell) for b in np.broadcast_to(beams, (M, 3))]
+        opts = self._imfit_options({"box": box, "theta0": theta0, "n_iter": n_iter, "rms": rms},
+                                   None, ni, nj)
+        return self._imfit_images(img.reshape(M, ni * nj).contiguous(), ni, nj, abc, cell, opts)

@@ -258,9 +258,9 @@ def test_tile_rule_and_workspace_query():
 
 
 def test_python_argument_paths():
-    """What RTEngine.clean / restore and JetModel._clean_mask refuse before any device call."""
-    from rajepy_amd import classes
-    m = classes.JetModel._clean_mask
+    """What RTEngine.clean / restore and Imager._clean_mask refuse before any device call."""
+    from rajepy_amd import classes, imaging
+    m = imaging.Imager._clean_mask
     assert m(None, None, 4, 5) is None
     box = m(None, (1, 2, 0, 3), 4, 5)
     assert box.shape == (4, 5) and box.sum() == 8 and box[1:3, 0:4].all()
@@ -278,4 +278,4 @@ def test_python_argument_paths():
     assert d["mask"] is None and d["beam"] is None and d["psf_shape"] is None and d["mfs"] is False
     rr = inspect.signature(classes.JetModel.clean_image_rrl).parameters
     assert set(sig.parameters) - {"self"} <= set(rr) and "rrl" in rr and "contsub" in rr
-    assert "device" in inspect.signature(classes.JetModel._dirty_images).parameters
+    assert "device" in inspect.signature(imaging.Imager._dirty_images).parameters

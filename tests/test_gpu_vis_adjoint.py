@@ -367,8 +367,8 @@ def test_mfs_is_the_weighted_mean_of_the_channel_images(eng, tmp_path_factory):
     maps = jm._ff_products(freqs, flux=True, device=True)
     V = eng.vis(maps.reshape(2, -1), jm.nx, jm.nz, su, sv, u_d, v_d)
     same = np.array([freqs[1], freqs[1]])
-    per = jm._dirty_images(V, u_d, v_d, same, w, SHAPE, None, False)
-    mfs = jm._dirty_images(V, u_d, v_d, same, w, SHAPE, None, True)
+    per = jm._imager._dirty_images(V, u_d, v_d, same, w, SHAPE, None, False)
+    mfs = jm._imager._dirty_images(V, u_d, v_d, same, w, SHAPE, None, True)
     assert per.shape == (2,) + SHAPE and mfs.shape == (1,) + SHAPE
     assert np.abs(per[0] - per[1]).max() > 0
     Vh = V.cpu().numpy()

@@ -290,16 +290,16 @@ class _RecordingEngine:
 
 def _model(nx, nz):
     from rajepy_amd import classes
-    J = classes.JetModel
 
-    class Model:
-        VIS_STACK_BYTES = J.VIS_STACK_BYTES
-        _vis_scales, _image_grid, _dirty_images = J._vis_scales, J._image_grid, J._dirty_images
-        dirty_image_ff, dirty_image_rrl, dirty_beam = J.dirty_image_ff, J.dirty_image_rrl, J.dirty_beam
+    class Model(classes.JetModel):
+        """A JetModel that holds only what its imaging front reads: the engine, the grid and the
+        distance; the `imaging.Imager` it hands over to is the real one."""
+
+        def __init__(self):
+            self._engine, self._nx, self._nz, self._csize = _RecordingEngine(), nx, nz, 0.5
+            self._params = {"target": {"dist": 120.}}
 
     m = Model()
-    m.engine, m.nx, m.nz, m.csize = _RecordingEngine(), nx, nz, 0.5
-    m.params = {"target": {"dist": 120.}}
     m.asked = []
 
     def ff(freqs, flux=False, device=False, formal=False):
