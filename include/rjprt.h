@@ -320,7 +320,11 @@ int rjp_occupied_cells(rjp_ctx* ctx, const int32_t* d_ylo, const int32_t* d_yhi,
  *   d_tavg [P]    nanmean_y(T where T > 0) [K], NaN on empty sightlines (may be NULL; on the
  *                 tau layout it costs a separate pass over d_temp: ask once, see rjp_tavg)
  * h_epochs_s: model times [s] (JetModel.time), E >= 1.
- * d_work: scratch of at least rjp_ff_scan_workspace() bytes. */
+ * d_work: scratch of at least rjp_ff_scan_workspace() bytes.  (A single-epoch scan that takes the
+ * burst factor from a table may build that table, and the bin coefficients of the bucketed
+ * layout, in memory the context owns instead of in d_work -- on a stream of the context's own,
+ * ordered against `stream` by events, while `stream` still runs earlier work.  The size asked for
+ * here does not depend on that.) */
 size_t rjp_ff_scan_workspace(int32_t nx, int32_t ny, int32_t nz, int32_t n_epochs);
 int rjp_ff_scan(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,
                 const double* h_epochs_s, int32_t n_epochs, int32_t gff_mode,

@@ -976,22 +976,135 @@ size_t chi_table_workspace_bytes(int64_t npix, int ny) {
   return std::max(tau, wide);
 }
 
+// ---- tables ahead of the scan (rjp_host.h: TabRing) ---------------------------------------------
+#ifndef RJP_TABLES_AHEAD
+#define RJP_TABLES_AHEAD 1       /* 0: a build whose table kernels stay on the caller's stream, in front of the scan, for A/B only */
+#endif
+constexpr size_t kRingTab = (size_t)2 * kChiMaxNI * kChiStride;           // doubles
+constexpr size_t kRingW = (size_t)2 * RJP_SRT_MAX_K * kSrtMaxN;           // doubles
+constexpr size_t kRingSlotBytes =
+    ((kRingTab + kRingW) * sizeof(double) + 2 * RJP_SRT_MAX_K * sizeof(int) + 255) / 256 * 256;
+
+void tab_ring_destroy(TabRing& r) {
+  if (r.side) {
+    (void)hipStreamSynchronize(r.side);
+    (void)hipStreamDestroy(r.side);
+  }
+  for (auto& s : r.slot) {
+    if (s.ready) (void)hipEventDestroy(s.ready);
+    if (s.uploaded) (void)hipEventDestroy(s.uploaded);
+  }
+  if (r.mem) (void)hipFree(r.mem);
+  r = TabRing();
+}
+
+void tab_ring_create(TabRing& r) {
+  r = TabRing();
+  bool ok = hipMalloc(&r.mem, TabRing::kSlots * kRingSlotBytes) == hipSuccess;
+  for (int i = 0; ok && i < TabRing::kSlots; ++i) {
+    TabRing::Slot& s = r.slot[i];
+    s.tab = reinterpret_cast<double*>(static_cast<char*>(r.mem) + i * kRingSlotBytes);
+    s.W = s.tab + kRingTab;
+    s.ok = reinterpret_cast<int*>(s.W + kRingW);
+    ok = hipEventCreateWithFlags(&s.ready, hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&s.uploaded, hipEventDisableTiming) == hipSuccess;
+  }
+  ok = ok && hipStreamCreateWithFlags(&r.side, hipStreamNonBlocking) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();      // (not this context's caller's error: the ring is optional)
+    tab_ring_destroy(r);
+  }
+}
+
+// The table kernels of one scan: on the caller's stream, or on the ring's side stream with the
+// events that order a slot.  join() puts the caller's stream behind the tables (once; it is a
+// no-op on the caller's own stream).
+struct TabLaunch {
+  hipStream_t st, ts;             // the caller's stream; the stream of the table kernels
+  TabRing::Slot* slot = nullptr;
+  bool joined = false;
+  hipError_t join() {
+    if (!slot || joined) return hipSuccess;
+    joined = true;
+    hipError_t e = hipEventRecord(slot->ready, ts);
+    if (e == hipSuccess) e = hipStreamWaitEvent(st, slot->ready, 0);
+    return e;
+  }
+};
+
+static hipError_t chi_table_scan_on(const rjp_fields* fl, const ChiPlan& cp, const double* d_stage,
+                                    double t_epoch, int mode, double* sumA, double* em,
+                                    double* tavg, double* ws, size_t work_bytes, int* d_guard,
+                                    hipStream_t st, const SrtPlan* sp, TabLaunch& tl,
+                                    double* d_tab, double* d_W, int* d_ok);
+
 hipError_t chi_table_scan(const rjp_fields* fl, const ChiPlan& cp, const double* d_stage,
                           double t_epoch, int mode, double* sumA, double* em, double* tavg,
                           double* ws, size_t work_bytes, int* d_guard, hipStream_t st,
-                          const SrtPlan* sp) {
+                          const SrtPlan* sp, TabRing* ring, bool* stage_fresh,
+                          hipEvent_t release_ev) {
   const int64_t npix = (int64_t)fl->nx * fl->nz;
-  const int64_t nchunks = npix / 2;
   const size_t tab_doubles = (size_t)2 * cp.ni * kChiStride;
   if (((uintptr_t)ws % 16) != 0 || work_bytes < (2 * npix + tab_doubles) * sizeof(double))
     return hipErrorInvalidValue;
-  // plane 2 of the first y-range (see the plan); behind the 8 x 4 planes of the wide scan
-  double* d_tab = ws + (cp.wide ? 32 : 2) * npix;
   if (cp.wide && work_bytes < (32 * npix + tab_doubles) * sizeof(double)) return hipErrorInvalidValue;
+  // single-stream order: the table in plane 2 of the first y-range (see the plan; behind the
+  // 8 x 4 planes of the wide scan), the hybrid scan's coefficients and verdicts in plane 0
+  TabLaunch tl{st, st};
+  double* d_tab = ws + (cp.wide ? 32 : 2) * npix;
+  double* d_W = nullptr;
+  int* d_ok = nullptr;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusActive;
+  bool ahead = RJP_TABLES_AHEAD && ring && ring->side && release_ev && cp.ni <= kChiMaxNI &&
+               hipStreamIsCapturing(st, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone;
+  if (ahead) {
+    // a caller that waits for every step has nothing to overlap the tables with, and two streams
+    // cost it two more hand-overs: the side stream is taken only while the previous scan of this
+    // context is still enqueued or running
+    const hipEvent_t prev = ring->slot[(ring->next + TabRing::kSlots - 1) % TabRing::kSlots].readers_done;
+    ahead = prev && hipEventQuery(prev) == hipErrorNotReady;
+    (void)hipGetLastError();             // (hipErrorNotReady is no error of this call)
+  }
+  if (ahead) {
+    TabRing::Slot& s = ring->slot[ring->next];
+    hipError_t e = s.readers_done ? hipStreamWaitEvent(ring->side, s.readers_done, 0) : hipSuccess;
+    if (e == hipSuccess && stage_fresh && *stage_fresh) {
+      e = hipEventRecord(s.uploaded, st);
+      if (e == hipSuccess) e = hipStreamWaitEvent(ring->side, s.uploaded, 0);
+      if (e == hipSuccess) *stage_fresh = false;
+    }
+    if (e != hipSuccess) return e;       // (nothing of this scan has been enqueued)
+    tl.ts = ring->side;
+    tl.slot = &s;
+    d_tab = s.tab;
+    d_W = s.W;
+    d_ok = s.ok;
+  }
+  const hipError_t e = chi_table_scan_on(fl, cp, d_stage, t_epoch, mode, sumA, em, tavg, ws,
+                                         work_bytes, d_guard, st, sp, tl, d_tab, d_W, d_ok);
+  // on every path: the slot's kernels may be in flight, and the event the caller records behind
+  // this scan (a failed launch included) has to cover them
+  const hipError_t rel = tl.join();
+  if (ring) {
+    // the slot of this scan, taken or not: what the next call asks for is THIS scan's end
+    ring->slot[ring->next].readers_done = release_ev;
+    ring->next = (ring->next + 1) % TabRing::kSlots;
+  }
+  return e != hipSuccess ? e : rel;
+}
+
+static hipError_t chi_table_scan_on(const rjp_fields* fl, const ChiPlan& cp, const double* d_stage,
+                                    double t_epoch, int mode, double* sumA, double* em,
+                                    double* tavg, double* ws, size_t work_bytes, int* d_guard,
+                                    hipStream_t st, const SrtPlan* sp, TabLaunch& tl,
+                                    double* d_tab, double* d_W, int* d_ok) {
+  const int64_t npix = (int64_t)fl->nx * fl->nz;
+  const int64_t nchunks = npix / 2;
+  const size_t tab_doubles = (size_t)2 * cp.ni * kChiStride;
   ChiTabDev t{cp.ni, cp.lo, cp.inv_h, std::nextafter((double)cp.ni, 0.0), fl->ts_lo, fl->ts_hi,
               d_guard};
-  hipLaunchKernelGGL(chi_table_kernel, dim3((unsigned)((2 * cp.ni + 255) / 256)), dim3(256), 0, st,
-                     d_stage, cp.n[0], cp.n[1], t, d_tab);
+  hipLaunchKernelGGL(chi_table_kernel, dim3((unsigned)((2 * cp.ni + 255) / 256)), dim3(256), 0,
+                     tl.ts, d_stage, cp.n[0], cp.n[1], t, d_tab);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   const int64_t wgs = (nchunks + kBlock - 1) / kBlock;
@@ -1039,22 +1152,28 @@ hipError_t chi_table_scan(const rjp_fields* fl, const ChiPlan& cp, const double*
     const int64_t per = kSrtBlock / RJP_WAVE;
     const dim3 sgrid((unsigned)((groups + per - 1) / per));
     if (sp->N == 0) {
+      e = tl.join();
+      if (e != hipSuccess) return e;
       hipLaunchKernelGGL((ff_scan_sorted_kernel<RJP_SRT_U>), sgrid, dim3(kSrtBlock), shm, st, s, t,
                          t_epoch, (const double*)d_tab, sumA);
       return hipGetLastError();
     }
     // ... with the bins whose chi^2 the moments' interpolant matches contracted: the coefficients
-    // and verdicts of every (jet, bin) go to plane 0 of the workspace (unused by this scan)
+    // and verdicts of every (jet, bin) go to the table slot, or in the single-stream order to
+    // plane 0 of the workspace (unused by this scan)
     const int K = fl->srt_K, N = sp->N;
     // the scan reads the moment planes in 16-byte pairs of sightlines (n_z is even on this path)
     if ((npix & 1) || ((uintptr_t)fl->d_srt_mom % 16) != 0) return hipErrorInvalidValue;
-    double* d_W = ws;
-    int* d_ok = reinterpret_cast<int*>(ws + (size_t)2 * K * N);
+    if (!d_W) {
+      d_W = ws;
+      d_ok = reinterpret_cast<int*>(ws + (size_t)2 * K * N);
+    }
     const SrtCoefDev c{fl->ts_lo, fl->ts_hi > fl->ts_lo ? K / (fl->ts_hi - fl->ts_lo) : 1.0, K, N,
                        {sp->b0[0], sp->b0[1]}, {sp->b1[0], sp->b1[1]}, d_W, d_ok};
-    hipLaunchKernelGGL(srt_coef_kernel, dim3((unsigned)(2 * K)), dim3(kSrtCoefThreads), 0, st,
+    hipLaunchKernelGGL(srt_coef_kernel, dim3((unsigned)(2 * K)), dim3(kSrtCoefThreads), 0, tl.ts,
                        d_stage, cp.n[0], cp.n[1], t, t_epoch, (const double*)d_tab, c);
     e = hipGetLastError();
+    if (e == hipSuccess) e = tl.join();
     if (e != hipSuccess) return e;
     const SrtMomDev m{fl->d_srt_mom, d_W, d_ok, sp->diag};
     switch (N) {
@@ -1074,6 +1193,8 @@ hipError_t chi_table_scan(const rjp_fields* fl, const ChiPlan& cp, const double*
     return hipGetLastError();
   }
   const dim3 grid((unsigned)(wgs * nsplit));
+  e = tl.join();
+  if (e != hipSuccess) return e;
   if (cp.wide) {
     FieldPtrs<double> f{(const double*)fl->d_nd, (const double*)fl->d_xi, (const double*)fl->d_temp,
                         (const double*)fl->d_pf, (const double*)fl->d_ts, fl->d_ylo, fl->d_yhi,

@@ -104,10 +104,42 @@ struct SrtPlan {
 };
 // false: no layout attached, or too large a share of it would be read (the grid order is as fast)
 bool srt_plan(const rjp_fields* fl, const rjp_bursts* hb, double t_epoch, SrtPlan& sp);
+// Tables ahead of the scan: chi_table_kernel and srt_coef_kernel depend on host arguments and the
+// staged burst table only, so a context builds them on a side stream of its own, into one of
+// kSlots table slots, while the caller's stream still runs what was enqueued before.  The slots
+// are ordered by stream events alone: `ready` (side stream, behind the table kernels; the
+// caller's stream waits for it in front of the scan) and `readers_done` (caller's stream, behind
+// the scan; the side stream waits for it before the slot is written again).  An event record
+// costs the stream it is made on about 6 us between two kernels (profiles/README.md, r19), so
+// `readers_done` is no event of the ring's own: it is the event the CALLER records behind the
+// scan anyway (`release_ev`, the release event of the staged burst table), borrowed.  Recorded
+// again by a later scan it only orders the side stream behind that later scan.
+struct TabRing {
+  static constexpr int kSlots = 4;
+  hipStream_t side = nullptr;     // non-blocking; null: the tables stay on the caller's stream
+  void* mem = nullptr;            // one allocation for every slot
+  struct Slot {
+    double* tab = nullptr;        // [2][kChiMaxNI][kChiStride]
+    double* W = nullptr;          // [2 RJP_SRT_MAX_K][kSrtMaxN]
+    int* ok = nullptr;            // [2 RJP_SRT_MAX_K]
+    hipEvent_t ready = nullptr;
+    hipEvent_t readers_done = nullptr;   // borrowed: the release_ev of the slot's last scan
+    hipEvent_t uploaded = nullptr;   // caller's stream, behind a fresh upload of the burst table
+  } slot[kSlots];
+  int next = 0;
+};
+// (a ring that could not be created is left without a side stream: the scans then keep the
+// single-stream order)
+void tab_ring_create(TabRing& r);
+void tab_ring_destroy(TabRing& r);
+// `stage_fresh`: the side stream has not yet been ordered behind the upload of `d_stage`; cleared
+// once it has been.  `release_ev`: the event the caller records on `st` when this returns, on
+// every path (null: the tables stay on the caller's stream)
 hipError_t chi_table_scan(const rjp_fields* fl, const ChiPlan& cp, const double* d_stage,
                           double t_epoch, int mode, double* sumA, double* em, double* tavg,
                           double* ws, size_t work_bytes, int* d_guard, hipStream_t st,
-                          const SrtPlan* sp = nullptr);
+                          const SrtPlan* sp = nullptr, TabRing* ring = nullptr,
+                          bool* stage_fresh = nullptr, hipEvent_t release_ev = nullptr);
 
 // ---- ff_moments.hip: epoch sweeps by launch-time moments --------------------------------------
 #define RJP_MOM_MAX_IDX 1280      /* 2 jets x K bins x N Chebyshev moments <= this (160 KB of LDS

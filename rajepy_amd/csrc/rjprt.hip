@@ -25,6 +25,7 @@ struct rjp_ctx {
   // the device copy: no host-to-device copy between the scan and the map stage.
   rjp::MomPlan mom;               // last moment-path request (its tables are reused)
   rjp::ChiPlan chi;               // the burst-factor table of the last single-epoch scan
+  rjp::TabRing tabs;              // its table slots and the side stream that fills them
   int last_path = 0;              // 0 = epoch tiles, 1 = LDS moments, 2 = launch-time-ordered layout
   int last_layout = 0;            // 0 = grid order, 1 = launch-time-bucketed layout (rjp_last_scan_layout)
   bool last_srt_mom = false;      // the last scan contracted bins from the layout's moments
@@ -38,6 +39,9 @@ struct rjp_ctx {
     size_t cap = 0;               // doubles
     size_t used = 0;              // doubles of valid content (0 = none)
     hipStream_t up_stream = nullptr;   // stream the content was uploaded on
+    bool side_seen = false;       // the table ring's side stream is ordered behind the upload
+    bool fresh = false;           // uploaded by the call in progress
+    bool hot = false;             // read by calls whose end no record of free_ev covers
     hipEvent_t free_ev = nullptr; // recorded after the last kernel that reads `d`
   } slot[kSlots];
   int next_slot = 0;
@@ -147,12 +151,23 @@ static int stage_tables(rjp_ctx* ctx, hipStream_t st, const double* const* src,
     if (!same) continue;
     off = 0;
     for (int i = 0; i < ntab; ++i) { dev_out[i] = c.d + off; off += len[i]; }
+    c.fresh = false;
     ctx->cur_slot = k;
     return RJP_OK;
   }
-  rjp_ctx::Slot& sl = ctx->slot[ctx->next_slot];
-  ctx->cur_slot = ctx->next_slot;
-  ctx->next_slot = (ctx->next_slot + 1) % rjp_ctx::kSlots;
+  // the next slot of the ring that is not hot (a hot slot's readers are covered by no record: it
+  // is kept, its content is in use call after call); all hot: the device is drained once
+  int pick = -1;
+  for (int k = 0; k < rjp_ctx::kSlots && pick < 0; ++k)
+    if (!ctx->slot[(ctx->next_slot + k) % rjp_ctx::kSlots].hot) pick = (ctx->next_slot + k) % rjp_ctx::kSlots;
+  if (pick < 0) {
+    RJP_HIP(ctx, hipDeviceSynchronize());
+    for (auto& c : ctx->slot) c.hot = false;
+    pick = ctx->next_slot;
+  }
+  rjp_ctx::Slot& sl = ctx->slot[pick];
+  ctx->cur_slot = pick;
+  ctx->next_slot = (pick + 1) % rjp_ctx::kSlots;
   RJP_HIP(ctx, hipEventSynchronize(sl.free_ev));     // no-op unless its readers still run
   sl.used = 0;
   if (tot > sl.cap) {
@@ -173,6 +188,8 @@ static int stage_tables(rjp_ctx* ctx, hipStream_t st, const double* const* src,
   RJP_HIP(ctx, hipMemcpyAsync(sl.d, sl.h, tot * sizeof(double), hipMemcpyHostToDevice, st));
   sl.used = tot;
   sl.up_stream = st;
+  sl.side_seen = false;
+  sl.fresh = true;
   return RJP_OK;
 }
 
@@ -189,12 +206,15 @@ constexpr int kMaxScale = 1 + 6 * RJP_SGPR_BURSTS;   // the chain-rule table of 
 // `launch(dev, d_ext)` -> hipError_t with their device copies in the order given, and records
 // the slot's release event on EVERY path -- after a failed launch too, since the slot's upload
 // (and anything enqueued before the failure) may still be in flight when the ring comes round to
-// it again.  `bursts`: the parameters of a single-epoch call's bursts beyond RJP_SGPR_BURSTS
+// it again.  An event record holds the stream up for about 6 us between two kernels, so a call
+// that REUSED a slot records nothing unless `release` asks for it (chi_table_scan's, whose table
+// ring borrows the event): the slot is marked hot instead, and the ring passes hot slots over
+// (stage_tables).  `bursts`: the parameters of a single-epoch call's bursts beyond RJP_SGPR_BURSTS
 // travel as one more table, `d_ext` (nullptr when no jet has that many; always so without
 // `bursts`).  No heap allocation unless there are such bursts.
 template <class Launch>
 static int staged(rjp_ctx* ctx, hipStream_t st, const char* what, const rjp_bursts* bursts,
-                  std::initializer_list<Tab> tabs, Launch&& launch) {
+                  std::initializer_list<Tab> tabs, Launch&& launch, bool release = false) {
   const double* src[kMaxTabs];
   size_t len[kMaxTabs];
   double* dev[kMaxTabs];
@@ -211,7 +231,14 @@ static int staged(rjp_ctx* ctx, hipStream_t st, const char* what, const rjp_burs
   }
   if (int r = stage_tables(ctx, st, src, len, n, dev)) return r;
   const hipError_t e = launch(dev, ext.empty() ? nullptr : dev[n - 1]);
-  const hipError_t rel = hipEventRecord(ctx->slot[ctx->cur_slot].free_ev, st);
+  rjp_ctx::Slot& sl = ctx->slot[ctx->cur_slot];
+  hipError_t rel = hipSuccess;
+  if (sl.fresh || release) {
+    rel = hipEventRecord(sl.free_ev, st);
+    sl.hot = false;
+  } else {
+    sl.hot = true;
+  }
   if (e != hipSuccess) return fail(ctx, RJP_ERR_HIP, what, e);
   if (rel != hipSuccess)
     return fail(ctx, RJP_ERR_HIP, "hipEventRecord(ctx->slot[ctx->cur_slot].free_ev, st)", rel);
@@ -282,6 +309,7 @@ int rjp_ctx_create(int device, rjp_ctx** out) {
     return fail(nullptr, RJP_ERR_HIP, "hipEventCreate / hipHostMalloc failed");
   }
   *c->guard = 0;
+  rjp::tab_ring_create(c->tabs);
   *out = c;
   return RJP_OK;
 }
@@ -301,6 +329,7 @@ int rjp_ctx_destroy(rjp_ctx* ctx) {
   if (ctx->d_count) (void)hipFree(ctx->d_count);
   if (ctx->d_srt_hist) (void)hipFree(ctx->d_srt_hist);
   if (ctx->d_srt_diag) (void)hipFree(ctx->d_srt_diag);
+  rjp::tab_ring_destroy(ctx->tabs);
   rjp::moments_release(ctx->mom);
   delete ctx;
   return RJP_OK;
@@ -534,10 +563,14 @@ static int ff_scan_impl(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts
     return staged(ctx, st, "chi_table_scan", nullptr,
                   {{ctx->chi.stage.data(), ctx->chi.stage.size()}},
                   [&](double* const* d, const double*) {
-                    return rjp::chi_table_scan(fields, ctx->chi, d[0], h_epochs_s[0], gff_mode,
-                                               d_sumA, d_em, d_tavg, (double*)d_work, work_bytes,
-                                               ctx->guard, st, srt ? &sp : nullptr);
-                  });
+                    bool fresh = !ctx->slot[ctx->cur_slot].side_seen;
+                    const hipError_t e = rjp::chi_table_scan(
+                        fields, ctx->chi, d[0], h_epochs_s[0], gff_mode, d_sumA, d_em, d_tavg,
+                        (double*)d_work, work_bytes, ctx->guard, st, srt ? &sp : nullptr,
+                        &ctx->tabs, &fresh, ctx->slot[ctx->cur_slot].free_ev);
+                    ctx->slot[ctx->cur_slot].side_seen = !fresh;
+                    return e;
+                  }, true);
   }
   ctx->last_path = 0;
   rjp::ScanPlan plan;
