@@ -430,12 +430,31 @@ int rjp_srt_moments(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, int32_t N
  * h_ctau[f]  = 0.018 nu^-2 gff(nu,T_0) csize au 100      (scalar mode)
  *            = 0.018 nu^-2 11.95 nu^-0.1 csize au 100    (power-law mode)
  * h_cflux[f] = 2 nu^2 k / c^2 * arctan(csize au / (dist pc))^2 / 1e-26
+ * NaN rule: a NaN in tavg[p] (an empty sightline) or in sumA[e,p] (a sightline the launch-time
+ * range guard poisoned, or a NaN of the caller's own sums) gives flux = NaN, and the pixel adds
+ * nothing to ftot; tau is h_ctau * sumA either way (NaN for a NaN sum).  A NaN sum is never turned
+ * into the finite flux h_cflux * tavg of an optically thick sightline.  sumA = +inf gives
+ * tau = +inf and flux = h_cflux * tavg; sumA = 0 gives +0.0 in both.  h_ctau must be finite.
  * Any of d_tau / d_flux / d_ftot may be NULL.  d_work >= rjp_ff_maps_workspace(). */
 size_t rjp_ff_maps_workspace(int64_t n_pix, int32_t n_epochs, int32_t n_chan);
 int rjp_ff_maps(rjp_ctx* ctx, const double* d_sumA, const double* d_tavg, int64_t n_pix,
                 int32_t n_epochs, const double* h_ctau, const double* h_cflux, int32_t n_chan,
                 double* d_tau, double* d_flux, double* d_ftot,
                 void* d_work, size_t work_bytes, void* stream);
+
+/* What the last rjp_ff_maps / rjp_ff_step of this context launched for its map stage:
+ *   out[0]  the kernel: 0 = the small-map kernel (a lane per VEC pixels, a wave reduction per
+ *           channel), 1 = the cube kernel with per-lane flux accumulators, 2 = totals only (no
+ *           cube was asked for); -1 before the first map stage of the context
+ *   out[1]  VEC, the pixels per lane and load: 2 when n_pix is even and d_sumA, d_tavg, d_tau and
+ *           d_flux are all 16-byte aligned, else 1
+ *   out[2]  KP, the pixel groups a lane walks (1 or 4; 4 for totals only)
+ *   out[3]  the workgroups along the pixel axis (gridDim.x)
+ *   out[4]  the partial sums per (epoch, channel) handed to the fixed-order reduction; 0 when no
+ *           d_ftot was asked for
+ *   out[5]  the channels per workgroup (gridDim.z slices the channel axis)
+ * RJP_ERR_ARG for a NULL argument.  Host-only: it synchronises and enqueues nothing.  For tests. */
+int rjp_last_maps_launch(const rjp_ctx* ctx, int32_t out[6]);
 
 /* ---- K1 + K2 from ONE call ----------------------------------------------------------------
  * rjp_ff_scan followed by rjp_ff_maps on the same stream, for callers whose step is shorter than

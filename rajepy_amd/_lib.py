@@ -121,6 +121,7 @@ SIGNATURES = {
     "rjp_ff_maps_workspace": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "rjp_ff_maps": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, _DP, _DP, C.c_int32,
                               _P, _P, _P, _P, C.c_size_t, _P]),
+    "rjp_last_maps_launch": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "rjp_ff_step": (C.c_int, [_P, C.POINTER(Fields), C.POINTER(Bursts), _DP, C.c_int32,
                               C.c_int32, _P, _DP, _DP, C.c_int32, _P, _P, _P, _P, _P,
                               _P, C.c_size_t, _P, C.c_size_t, _P]),

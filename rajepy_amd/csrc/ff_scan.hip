@@ -126,6 +126,14 @@ hipError_t ff_reduce_launch(const double* ws, int nsplit, int et, int64_t npix, 
 }
 
 // ---- K2 ------------------------------------------------------------------------------
+// The NaN rule of the map stage.  one_minus_exp_neg(NaN) is 1 (its fmax drops the NaN), and a sum
+// IS NaN where the launch-time range guard poisoned its sightline (or in a caller's own sums): the
+// flux of such a pixel is NaN, which the nansum of the totals then leaves out -- never the finite
+// flux cflux * T_avg of an optically thick sightline.  Hoisted out of the channel loop: the pixel's
+// T_avg takes the NaN of its sum ONCE (h_ctau is finite, so ctau * A is NaN exactly where A is),
+// and every channel's T_avg * (1 - e^-tau) is NaN with it.
+__device__ __forceinline__ double maps_tavg(double A, double ta) { return A == A ? ta : A; }
+
 // One thread per VEC adjacent pixels, serial over the channels of its slice: every store
 // instruction is a coalesced row segment of one (epoch, channel) map, 16 B per lane when the
 // map has an even number of pixels.  Write-bound: 16 B per voxel-channel.  The per-channel
@@ -147,6 +155,8 @@ __global__ __launch_bounds__(kBlock) void ff_maps_kernel(
   if (live) {
     load_plain(sumA + (int64_t)e * npix + p, A);
     load_plain(tavg + p, ta);
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) ta[v] = maps_tavg(A[v], ta[v]);
   }
   const int slot = blockIdx.x * (kBlock / RJP_WAVE) + threadIdx.x / RJP_WAVE;
   for (int f = f0; f < f1; ++f) {
@@ -204,6 +214,8 @@ __global__ __launch_bounds__(kBlock) void ff_maps_acc_kernel(
     const int64_t pc = pk[k] < npix ? pk[k] : 0;               // npix % VEC == 0
     load_plain(sumA + (int64_t)e * npix + pc, A[k]);
     load_plain(tavg + pc, ta[k]);
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) ta[k][v] = maps_tavg(A[k][v], ta[k][v]);
   }
 #if RJP_K2_CHOUTER
   // channel after channel: a lane's KP stores of a channel and cube go to ONE map back to back (a
@@ -292,11 +304,12 @@ __global__ __launch_bounds__(kBlock) void ff_ftot_kernel(
     double A[VEC], ta[VEC];
     load_plain(sumA + (int64_t)e * npix + p, A);
     load_plain(tavg + p, ta);
-    // nansum, hoisted: a flux is NaN exactly where T_avg is (an empty sightline; the sums A and
-    // 1 - e^-tau are never NaN) -- such a pixel adds zero to every channel, so its T_avg is
-    // zeroed ONCE and the channel loop is one multiply and one FMA around 1 - e^-tau
+    // nansum, hoisted: a flux is NaN exactly where T_avg is (an empty sightline) or the sum A is
+    // (a sightline the range guard poisoned; h_ctau is finite, so ctau * A is NaN only then) --
+    // such a pixel adds zero to every channel, so its T_avg is zeroed ONCE (one_minus_exp_neg of
+    // a NaN is a finite 1) and the channel loop is one multiply and one FMA around 1 - e^-tau
 #pragma unroll
-    for (int v = 0; v < VEC; ++v) ta[v] = ta[v] == ta[v] ? ta[v] : 0.0;
+    for (int v = 0; v < VEC; ++v) ta[v] = (ta[v] == ta[v] && A[v] == A[v]) ? ta[v] : 0.0;
 #pragma unroll
     for (int j = 0; j < kFtotFC; ++j) {
       if (j < nf) {
@@ -801,7 +814,14 @@ size_t ff_maps_workspace_bytes(int64_t npix, int n_epochs, int n_chan) {
 
 hipError_t ff_maps_launch(const double* sumA, const double* tavg, int64_t npix, int n_epochs,
                           const double* d_ctau, const double* d_cflux, int n_chan, double* tau,
-                          double* flux, double* ftot, double* part, hipStream_t st) {
+                          double* flux, double* ftot, double* part, hipStream_t st,
+                          int32_t* info) {
+  // `info`: (kernel, VEC, KP, blocks, nparts, fchunk) of the launch chosen (rjp_last_maps_launch)
+  auto note = [&](int kernel, int v, int kp, unsigned blocks, int nparts, int fchunk) {
+    if (!info) return;
+    info[0] = kernel; info[1] = v; info[2] = kp;
+    info[3] = (int32_t)blocks; info[4] = nparts; info[5] = fchunk;
+  };
   // two pixels per lane (16-B loads and stores) when every map row pair is 16-B aligned
   bool vec2 = (npix % 2) == 0;
   for (const void* q : {(const void*)sumA, (const void*)tavg, (const void*)tau, (const void*)flux})
@@ -813,6 +833,7 @@ hipError_t ff_maps_launch(const double* sumA, const double* tavg, int64_t npix, 
     const unsigned nb = (unsigned)((lanes + (int64_t)kBlock * kFtotKP - 1) / ((int64_t)kBlock * kFtotKP));
     const int np = (int)nb * (kBlock / RJP_WAVE);
     dim3 g(nb, (unsigned)n_epochs, (unsigned)((n_chan + kFtotFC - 1) / kFtotFC));
+    note(2, vec, kFtotKP, nb, np, kFtotFC);
     if (vec2)
       hipLaunchKernelGGL(ff_ftot_kernel<2>, g, dim3(kBlock), 0, st, sumA, tavg, npix, d_ctau,
                          d_cflux, n_chan, part, np);
@@ -836,6 +857,7 @@ hipError_t ff_maps_launch(const double* sumA, const double* tavg, int64_t npix, 
       const unsigned nbx = kp == 4 ? nb4 : nblk;
       const int np = (int)nbx * (kBlock / RJP_WAVE);
       dim3 g(nbx, (unsigned)n_epochs, nzc);
+      note(1, vec, kp, nbx, ftot ? np : 0, kMapsFC);
       auto go = [&](auto vtag, auto ftag) {
         constexpr int V = decltype(vtag)::value;
         constexpr bool FT = decltype(ftag)::value;
@@ -862,6 +884,7 @@ hipError_t ff_maps_launch(const double* sumA, const double* tavg, int64_t npix, 
   const int fchunk = (n_chan + fsplit - 1) / fsplit;
   fsplit = (n_chan + fchunk - 1) / fchunk;
   dim3 grid(nblk, (unsigned)n_epochs, (unsigned)fsplit);
+  note(0, vec, 1, nblk, ftot ? nparts : 0, fchunk);
   if (vec2)
     hipLaunchKernelGGL(ff_maps_kernel<2>, grid, dim3(kBlock), 0, st, sumA, tavg, npix, d_ctau,
                        d_cflux, n_chan, fchunk, tau, flux, ftot ? part : nullptr, nparts);

@@ -274,8 +274,10 @@ __device__ __forceinline__ double exp_any(double x) {
 // rrls.py:445-447), relative error < 4e-15 for EVERY tau -- also the thin columns where
 // 1 - exp() through libm's exp cancels (tau ~ 1e-6 keeps 10 digits that way): with
 // -tau = k ln2 + r,  1 - e^-tau = (1 - 2^k) - 2^k expm1(r), and 1 - 2^k is exact.  ~21
-// instructions against ~45 for libm's exp and the subtraction; tau = inf gives 1, NaN gives 1
-// (a tau map holds no NaN: its sums are nansums).
+// instructions against ~45 for libm's exp and the subtraction; tau = inf gives 1, and so does
+// NaN (the fmax below drops it).  A caller whose tau CAN be NaN tests for it itself: the sums of
+// a sightline the launch-time range guard poisoned are NaN, so K2 does (maps_tavg, ff_scan.hip);
+// the other callers keep this behaviour bit for bit.
 // (the reduction and expm1(r): s = 2^k, em1 = expm1(r) with -tau = k ln2 + r)
 __device__ __forceinline__ void exp_neg_parts(double tau, double& s, double& em1) {
   const double L2E = 1.4426950408889634074;

@@ -69,7 +69,8 @@ hipError_t ff_formal_sweep_launch(const rjp_fields* fl, const rjp_bursts* hb, co
 size_t ff_maps_workspace_bytes(int64_t npix, int n_epochs, int n_chan);
 hipError_t ff_maps_launch(const double* sumA, const double* tavg, int64_t npix, int n_epochs,
                           const double* d_ctau, const double* d_cflux, int n_chan, double* tau,
-                          double* flux, double* ftot, double* part, hipStream_t st);
+                          double* flux, double* ftot, double* part, hipStream_t st,
+                          int32_t* info = nullptr);
 // out[row] = sum of part[row * nblk .. + nblk) in a fixed order
 hipError_t sum_partials_launch(const double* part, int rows, int nblk, double* out,
                                hipStream_t st);

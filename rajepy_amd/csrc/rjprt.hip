@@ -32,6 +32,9 @@ struct rjp_ctx {
   // (e0, et, uniform, nsplit, vec) of every epoch tile the last scan launched (rjp_last_scan_tiles);
   // empty after a scan on another path
   std::vector<int32_t> last_tiles;
+  // (kernel, VEC, KP, blocks, nparts, fchunk) of the last map stage (rjp_last_maps_launch);
+  // kernel -1 before the first
+  int32_t last_maps[6] = {-1, 0, 0, 0, 0, 0};
   static constexpr int kSlots = 8;
   struct Slot {
     double* h = nullptr;
@@ -631,6 +634,12 @@ int rjp_last_scan_tiles(const rjp_ctx* ctx, int32_t* n_tiles, int32_t* tiles, in
 
 int rjp_last_scan_layout(const rjp_ctx* ctx) { return ctx ? ctx->last_layout : RJP_ERR_ARG; }
 
+int rjp_last_maps_launch(const rjp_ctx* ctx, int32_t out[6]) {
+  if (!ctx || !out) return RJP_ERR_ARG;
+  for (int i = 0; i < 6; ++i) out[i] = ctx->last_maps[i];
+  return RJP_OK;
+}
+
 int rjp_last_srt_bins(rjp_ctx* ctx, int64_t* contracted, int64_t* read) {
   if (int r = bind(ctx)) return r;
   if (!contracted || !read) return fail(ctx, RJP_ERR_ARG, "rjp_last_srt_bins: NULL output");
@@ -804,7 +813,8 @@ static int ff_maps_impl(rjp_ctx* ctx, const double* d_sumA, const double* d_tavg
   return staged(ctx, st, "ff_maps_launch", nullptr, {{h_ctau, F}, {h_cflux, F}},
                 [&](double* const* d, const double*) {
                   return rjp::ff_maps_launch(d_sumA, d_tavg, n_pix, n_epochs, d[0], d[1], n_chan,
-                                             d_tau, d_flux, d_ftot, (double*)d_work, st);
+                                             d_tau, d_flux, d_ftot, (double*)d_work, st,
+                                             ctx->last_maps);
                 });
 }
 

@@ -941,6 +941,17 @@ class RTEngine:
                    _ptr(flux), _ptr(ftot), _ptr(work), work.numel() if work is not None else 0)
         return tau, flux, ftot
 
+    def last_maps_launch(self):
+        """(kernel, VEC, KP, blocks, nparts, fchunk) of the map stage the last `ff_maps` /
+        `ff_step` of this engine launched (rjp_last_maps_launch): kernel 'small' | 'acc' | 'ftot'
+        (None before the first), pixels per lane, pixel groups per lane, workgroups along the
+        pixel axis, partial sums per (epoch, channel) (0 without totals), channels per workgroup.
+        Host-only; for tests."""
+        buf = (C.c_int32 * 6)()
+        self._check(self.lib.rjp_last_maps_launch(self.ctx, buf), self.ctx, "rjp_last_maps_launch")
+        return ({-1: None, 0: "small", 1: "acc", 2: "ftot"}[int(buf[0])],) + \
+            tuple(int(v) for v in buf[1:])
+
     def ff_cells(self, fields, bursts, time_s, gff_mode, ctau):
         """collapse=False: per-cell free-free optical depths -> device tensor [F, N]."""
         F = len(ctau)

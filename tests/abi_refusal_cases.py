@@ -348,6 +348,11 @@ def _(e):
                 _status_only=True, _no_stream=True)
 
 
+@entry("rjp_last_maps_launch", [("ctx NULL", arg(ctx=None))])
+def _(e):
+    return dict(ctx=e.eng.ctx, out=(C.c_int32 * 6)(), _status_only=True, _no_stream=True)
+
+
 @entry("rjp_last_srt_bins", [("contracted NULL", arg(contracted=None)),
                              ("read NULL", arg(read=None))])
 def _(e):
