@@ -802,6 +802,75 @@ int64_t rjp_restore(rjp_ctx* ctx, const int32_t* d_cpix, const double* d_cflux,
                     const double* h_beam, const double* d_add, int32_t nx, int32_t nz,
                     double* d_out, void* stream);
 
+/* ---- A direct 2-D convolution of a stack of images -------------------------------------------------
+ *   out[m][i, j] = add[m][i, j] + sum_{a, b} ker[kappa][a, b] in[m][i - (a - ca), j - (b - cb)]
+ * a true convolution (the index is flipped; not a correlation), pixel order p = i nz + j:
+ *   d_in, d_add, d_out [n_maps][nx nz]   d_add may be NULL (= 0); d_out must not alias d_in
+ *   d_ker [n_ker][kx kz]                 n_ker = n_maps (kappa = m), or 1 for one kernel shared by
+ *                                        all maps; kx and kz ODD, at most RJP_CONV_MAX_K, the centre
+ *                                        (ca, cb) = ((kx-1)/2, (kz-1)/2)
+ * d_in counts as zero outside the image (those terms are taken, as products with 0).  f64
+ * throughout, one fma per term, the terms in kernel order -- a outer, b inner, both ascending --
+ * and d_add is the accumulator's start: the bits are a function of the inputs alone, and a NaN or
+ * infinite pixel propagates by IEEE arithmetic (0 NaN = NaN) to every output its kernel reaches.
+ * A workgroup owns RJP_CONV_TILE_X x RJP_CONV_TILE_Z output pixels and stages its input tile plus
+ * halo through 64 KiB of LDS, a chunk of kernel rows at a time; RJP_CONV_MAX_K is the widest kernel
+ * for which one kernel row plus the tile and its halo fit.
+ * RETURNS the number of workgroups enqueued, > 0 -- n_maps x ceil(nx / 16) x ceil(nz / 64) -- or a
+ * negative RJP_ERR_*; nothing is enqueued or touched on a refusal: RJP_ERR_ARG for a NULL ctx, d_in,
+ * d_ker or d_out; n_maps, nx, nz, kx or kz < 1; an even kx or kz; kx or kz > RJP_CONV_MAX_K; an
+ * n_ker that is neither 1 nor n_maps; nx nz > 2^31 - 1; more than 2^31 - 1 workgroups. */
+#define RJP_CONV_MAX_K 255
+#define RJP_CONV_TILE_X 16
+#define RJP_CONV_TILE_Z 64
+int64_t rjp_convolve2d(rjp_ctx* ctx, const double* d_in, int32_t n_maps, int32_t nx, int32_t nz,
+                       const double* d_ker, int32_t n_ker, int32_t kx, int32_t kz,
+                       const double* d_add, double* d_out, void* stream);
+
+/* ---- K17: multi-scale CLEAN minor cycles on a stack of maps ----------------------------------------
+ * CASA tclean(deconvolver='multiscale', scales=[...]) is what the reference's Tclean task offers for
+ * resolved sources (casa/tasks.py:243-244).  This entry point generalises K12 from one residual
+ * plane per map to n_s planes; it is scale-agnostic, the caller prepares planes and cross beams:
+ *   d_res [n_maps][n_s][nx nz]   the dirty image convolved with each scale kernel on entry, the
+ *                                residual planes on exit (IN PLACE)
+ *   d_xpsf [n_psf][n_s (n_s + 1) / 2][px pz]   the cross beams X[k][l], k <= l (the beam convolved
+ *                                with scale k and scale l), as a packed upper triangle in row order:
+ *                                plane k n_s - k (k - 1) / 2 + (l - k); X[l][k] is the same plane;
+ *                                px and pz ODD; n_psf = n_maps, or 1 for one set shared by all maps
+ *   h_weight [n_maps][n_s]       HOST: finite and >= 0; 0 = the plane is updated but never picked
+ *   d_mask [nx nz]               as K12: one mask for every plane and map; NULL = all pixels
+ *   h_thresh [n_maps], gain, n_iter   as K12
+ *   d_cpix, d_cscale [n_maps][n_iter] int32, d_cflux [n_maps][n_iter], d_ncomp [n_maps]
+ *   d_model [n_maps][n_s][nx nz] (optional) ADDED to: the delta model of each scale
+ *   d_peak [n_maps]              (optional) the final best score, 0 when no pixel qualifies
+ * Iteration t of map m: among the planes with weight > 0 and the pixels that are unmasked and hold a
+ * finite R_k[p], the score is s = weight[k] |R_k[p]| (one rounding).  The largest s is taken, on a tie
+ * the lower k, then the lower p.  With no candidate, or s* <= h_thresh[m], the map is finished and
+ * nothing of it changes any more.  Otherwise f = (gain R_k*[p*]) / X[k*][k*][centre] (one product,
+ * one division, both correctly rounded); (p*, k*, f) goes to slot t, d_model[m][k*][p*] += f, and for
+ * EVERY plane l
+ *   R_l[q] = fma(-f, X[k*][l][q - p* + centre], R_l[q])   for every q inside the beam window.
+ * A map whose X[k][k][centre] is zero or not finite for some k of weight > 0 is finished from the
+ * start: d_ncomp[m] = 0, d_peak[m] = 0.  Slots at and beyond d_ncomp[m] are not written; a non-finite
+ * pixel is never picked and is left as it is; a second call on the planes continues the same clean.
+ * One launch per iteration for the whole stack, grid = tiles x planes x maps, per-tile partial maxima
+ * in a double-buffered workspace (2 x 12 bytes per map, plane and tile of 1024 pixels, rounded up to
+ * 16), no atomics, every reduction in a fixed order: a repeated call gives the same bits.  With
+ * n_s = 1, weight 1 and a beam whose centre is exactly 1.0 every output equals rjp_clean's bit for bit.
+ * RETURNS the number of workgroups of one iteration's launch, > 0 -- n_maps x n_s x
+ * ceil(nx nz / 1024) -- or a negative RJP_ERR_*.  Everything is validated before anything is
+ * enqueued, and no output or workspace byte is touched on a refusal: RJP_ERR_ARG for K12's refusals
+ * (with d_xpsf for d_psf), a NULL h_weight or d_cscale, n_s < 1, a negative or non-finite weight,
+ * more than 2^31 - 1 workgroups.  RJP_ERR_WORKSPACE for a d_work smaller than the workspace query
+ * (0 from it = a bad argument, or a size that overflows). */
+size_t rjp_msclean_workspace(int32_t n_maps, int32_t n_s, int32_t nx, int32_t nz);
+int64_t rjp_msclean(rjp_ctx* ctx, double* d_res, int32_t n_maps, int32_t n_s, int32_t nx,
+                    int32_t nz, const double* d_xpsf, int32_t n_psf, int32_t px, int32_t pz,
+                    const double* h_weight, const uint8_t* d_mask, const double* h_thresh,
+                    double gain, int32_t n_iter, int32_t* d_cpix, int32_t* d_cscale,
+                    double* d_cflux, int32_t* d_ncomp, double* d_model, double* d_peak,
+                    void* d_work, size_t work_bytes, void* stream);
+
 /* ---- K14: Gaussian fits of a stack of images (imfit) ----------------------------------------------
  * The reference measures its synthetic images outside itself: CASA imfit on the restored image
  * (classes.py:2790-2840).  This entry point fits one elliptical Gaussian per map by

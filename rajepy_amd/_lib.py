@@ -156,6 +156,12 @@ SIGNATURES = {
                               C.c_size_t, _P]),
     "rjp_restore": (C.c_int64, [_P, _P, _P, _P, C.c_int32, C.c_int32, _DP, _P, C.c_int32,
                                 C.c_int32, _P, _P]),
+    "rjp_convolve2d": (C.c_int64, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32,
+                                   C.c_int32, _P, _P, _P]),
+    "rjp_msclean_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "rjp_msclean": (C.c_int64, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32,
+                                C.c_int32, C.c_int32, _DP, _P, _DP, C.c_double, C.c_int32, _P, _P,
+                                _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "rjp_gaussfit_workspace": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rjp_gaussfit": (C.c_int64, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P,
                                  _P, C.c_double, C.c_double, C.c_int32, _P, _P, _P, _P, _P, _P, _P,

@@ -1149,7 +1149,8 @@ class JetModel:
     # ------------------------------------------------------------------ CLEAN ----
     def clean_image_ff(self, u_m, v_m, freq, weights=None, shape=None, cell_as=None, formal=False,
                        mfs=False, niter=500, gain=0.1, threshold_jy=0.0, mask=None, beam=None,
-                       psf_shape=None, imfit=None, weighting=None, robust=0.5):
+                       psf_shape=None, imfit=None, weighting=None, robust=0.5, scales=None,
+                       scale_bias=None):
         """CLEANed, restored images [Jy / clean beam] of the `flux_ff` maps as an array with the
         baselines (`u_m`, `v_m`) in metres sees them: `dirty_image_ff` and `dirty_beam` (same
         arguments, kept on the device), Hogbom's CLEAN of every image with its own beam
@@ -1175,20 +1176,33 @@ class JetModel:
         the reference's tclean(weighting='briggs', robust=0.5), classes.py:2775-2776: imaging
         weights from the (u, v) density on the IMAGE's grid (`RTEngine.uv_weights`), one density
         per channel (one over all channels with `mfs`), shared by the image and its beam;
-        `weights` are the data weights the scheme starts from (see `dirty_image_ff`)."""
+        `weights` are the data weights the scheme starts from (see `dirty_image_ff`).
+        `scales`: None = Hogbom as above; a list of scale sizes in IMAGE PIXELS, as tclean takes
+        `scales` = multi-scale CLEAN (K17: `RTEngine.msclean`, rjp_msclean, with the scale kernels
+        of `engine.scale_kernel` applied by `RTEngine.convolve2d`).  Plane 0 is always the delta
+        scale (picked only if 0 is among `scales`), the other scales follow ascending; every
+        component is a scale kernel of unit sum times its flux, picked by bias x flux with the
+        biases `scale_bias` (None = `engine.scale_biases`, 1 - 0.6 s / s_max; else one per plane).
+        `components` rows are then (ix, iz, flux [Jy], scale [pixels]), `model` is the sum of the
+        scales' delta models convolved with their kernels, `residual` the raw (delta-scale)
+        residual, `peak_residual` its masked max, `threshold_jy` bounds the score, and components
+        lie at least the largest kernel's half width from the border (ValueError if the mask
+        leaves no such pixel).  The kernels carry no prolate-spheroidal taper: not CASA's bits."""
         im, *vis = self._model_vis(u_m, v_m, freq, weighting, formal=formal)
         return im._clean_images(*vis, weights, shape, cell_as, mfs, niter, gain, threshold_jy, mask,
-                                beam, psf_shape, imfit, weighting=weighting, robust=robust)
+                                beam, psf_shape, imfit, weighting=weighting, robust=robust,
+                                scales=scales, scale_bias=scale_bias)
 
     def clean_image_rrl(self, rrl, u_m, v_m, freq, weights=None, shape=None, cell_as=None,
                         contsub=True, formal=False, mfs=False, niter=500, gain=0.1,
                         threshold_jy=0.0, mask=None, beam=None, psf_shape=None, imfit=None,
-                        weighting=None, robust=0.5):
+                        weighting=None, robust=0.5, scales=None, scale_bias=None):
         """CLEANed, restored images of the `flux_rrl` maps (same arguments) -> `CleanResult`; see
         `clean_image_ff`."""
         im, *vis = self._model_vis(u_m, v_m, freq, weighting, rrl=rrl, contsub=contsub, formal=formal)
         return im._clean_images(*vis, weights, shape, cell_as, mfs, niter, gain, threshold_jy, mask,
-                                beam, psf_shape, imfit, weighting=weighting, robust=robust)
+                                beam, psf_shape, imfit, weighting=weighting, robust=robust,
+                                scales=scales, scale_bias=scale_bias)
 
     # ------------------------------------------------------------------ synthetic observations ----
     def uv_tracks(self, antennalist, t_obs_s, t_int_s, min_el_deg=None, hourangle_h=0.):
@@ -1215,7 +1229,7 @@ class JetModel:
                    sigma_jy=None, sefd_jy=None, chanwidth_hz=None, seed=0, nsigma=0.,
                    weights=None, shape=None, cell_as=None, formal=False, mfs=False, niter=500,
                    gain=0.1, threshold_jy=0.0, mask=None, beam=None, psf_shape=None, imfit=None,
-                   weighting=None, robust=0.5):
+                   weighting=None, robust=0.5, scales=None, scale_bias=None):
         """A synthetic observation of the `flux_ff` maps, start to end on the device -- the
         reference's simobserve -> tclean -> imfit chain (classes.py:2490-2850) -> `Observation`:
         `tracks` (`uv_tracks` of `antennalist`, `t_obs_s`, `t_int_s`, `min_el_deg`,
@@ -1237,19 +1251,21 @@ class JetModel:
         return self._observe(dict(formal=formal), antennalist, freq, t_obs_s, t_int_s, min_el_deg,
                              hourangle_h, sigma_jy, sefd_jy, chanwidth_hz, seed, nsigma, weights,
                              shape, cell_as, mfs, niter, gain, threshold_jy, mask, beam, psf_shape,
-                             imfit, weighting, robust)
+                             imfit, weighting, robust, scales, scale_bias)
 
     def observe_rrl(self, rrl, antennalist, freq, t_obs_s, t_int_s, min_el_deg=None,
                     hourangle_h=0., sigma_jy=None, sefd_jy=None, chanwidth_hz=None, seed=0,
                     nsigma=0., weights=None, shape=None, cell_as=None, contsub=True, formal=False,
                     mfs=False, niter=500, gain=0.1, threshold_jy=0.0, mask=None, beam=None,
-                    psf_shape=None, imfit=None, weighting=None, robust=0.5):
+                    psf_shape=None, imfit=None, weighting=None, robust=0.5, scales=None,
+                    scale_bias=None):
         """A synthetic observation of the `flux_rrl` maps -> `Observation`; see `observe_ff`."""
         _weighting_mode(weighting)            # (refuses an unknown scheme before any work)
         return self._observe(dict(rrl=rrl, contsub=contsub, formal=formal), antennalist, freq,
                              t_obs_s, t_int_s, min_el_deg, hourangle_h, sigma_jy, sefd_jy,
                              chanwidth_hz, seed, nsigma, weights, shape, cell_as, mfs, niter, gain,
-                             threshold_jy, mask, beam, psf_shape, imfit, weighting, robust)
+                             threshold_jy, mask, beam, psf_shape, imfit, weighting, robust, scales,
+                             scale_bias)
 
     # ------------------------------------------------------------------ imfit ----
     def imfit(self, images, beam, cell_as=None, box=None, theta0=None, n_iter=60, rms=None):

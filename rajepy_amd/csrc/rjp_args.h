@@ -166,6 +166,60 @@ inline int check_clean(const double* d_res, int n_maps, int nx, int nz, const do
   return RJP_OK;
 }
 
+// What rjp_convolve2d takes, in the order it refuses: NULL pointers, sizes below 1, an even kernel
+// size, a kernel beyond RJP_CONV_MAX_K, the kernel count, the image size, the workgroup count of
+// the tile rule (RJP_CONV_TILE_X x RJP_CONV_TILE_Z output pixels).  (`d_add` may be NULL.)
+inline int check_convolve2d(const double* d_in, int n_maps, int nx, int nz, const double* d_ker,
+                            int n_ker, int kx, int kz, const double* d_out, std::string& err) {
+  if (!d_in || !d_ker || !d_out) return refuse(err, "rjp_convolve2d: NULL input, kernels or output");
+  if (n_maps < 1 || nx < 1 || nz < 1 || kx < 1 || kz < 1)
+    return refuse(err, "rjp_convolve2d: n_maps, nx, nz, kx and kz must be positive");
+  if (kx % 2 == 0 || kz % 2 == 0)
+    return refuse(err, "rjp_convolve2d: kx and kz must be odd (the kernel's centre is a pixel)");
+  if (kx > RJP_CONV_MAX_K || kz > RJP_CONV_MAX_K)
+    return refuse(err, "rjp_convolve2d: kx and kz must not exceed RJP_CONV_MAX_K (" +
+                           std::to_string(RJP_CONV_MAX_K) + ")");
+  if (n_ker != 1 && n_ker != n_maps)
+    return refuse(err, "rjp_convolve2d: n_ker must be 1 or n_maps");
+  if ((int64_t)nx * nz > (int64_t)INT32_MAX)
+    return refuse(err, "rjp_convolve2d: nx * nz exceeds 2^31 - 1");
+  const int64_t tiles = (((int64_t)nx + RJP_CONV_TILE_X - 1) / RJP_CONV_TILE_X) *
+                        (((int64_t)nz + RJP_CONV_TILE_Z - 1) / RJP_CONV_TILE_Z);
+  if (tiles > (int64_t)INT32_MAX / n_maps)
+    return refuse(err, "rjp_convolve2d: more than 2^31 - 1 workgroups");
+  return RJP_OK;
+}
+
+// What rjp_msclean takes, in the order it refuses: NULL pointers, sizes below 1, an even beam, the
+// beam count, the image size, the gain, n_iter, the thresholds, the weights.  (`d_mask`, `d_model`,
+// `d_peak` may be NULL; the grid and the workspace are checked where the tiling lives.)
+inline int check_msclean(const double* d_res, int n_maps, int n_s, int nx, int nz,
+                         const double* d_xpsf, int n_psf, int px, int pz, const double* h_weight,
+                         const double* h_thresh, double gain, int n_iter, const int32_t* d_cpix,
+                         const int32_t* d_cscale, const double* d_cflux, const int32_t* d_ncomp,
+                         std::string& err) {
+  if (!d_res || !d_xpsf || !h_weight || !h_thresh || !d_cpix || !d_cscale || !d_cflux || !d_ncomp)
+    return refuse(err, "rjp_msclean: NULL planes, cross beams, weights, thresholds or component "
+                       "outputs");
+  if (n_maps < 1 || n_s < 1 || nx < 1 || nz < 1 || px < 1 || pz < 1)
+    return refuse(err, "rjp_msclean: n_maps, n_s, nx, nz, px and pz must be positive");
+  if (px % 2 == 0 || pz % 2 == 0)
+    return refuse(err, "rjp_msclean: px and pz must be odd (the beam's centre is a pixel)");
+  if (n_psf != 1 && n_psf != n_maps)
+    return refuse(err, "rjp_msclean: n_psf must be 1 or n_maps");
+  if ((int64_t)nx * nz > (int64_t)INT32_MAX)
+    return refuse(err, "rjp_msclean: nx * nz exceeds 2^31 - 1");
+  if (!(gain > 0.0 && gain <= 1.0)) return refuse(err, "rjp_msclean: gain must lie in (0, 1]");
+  if (n_iter < 1) return refuse(err, "rjp_msclean: n_iter < 1");
+  for (int m = 0; m < n_maps; ++m)
+    if (!(h_thresh[m] >= 0.0) || !std::isfinite(h_thresh[m]))
+      return refuse(err, "rjp_msclean: negative or non-finite threshold");
+  for (int64_t i = 0; i < (int64_t)n_maps * n_s; ++i)
+    if (!(h_weight[i] >= 0.0) || !std::isfinite(h_weight[i]))
+      return refuse(err, "rjp_msclean: negative or non-finite weight");
+  return RJP_OK;
+}
+
 // What rjp_restore takes, in the order it refuses: NULL pointers, sizes below 1, the image size, a
 // beam whose quadratic form is not positive definite (or not finite).  (`d_add` may be NULL.)
 inline int check_restore(const int32_t* d_cpix, const double* d_cflux, const int32_t* d_ncomp,

@@ -297,6 +297,36 @@ hipError_t restore_launch(const int32_t* cpix, const double* cflux, const int32_
                           int n_maps, int comp_stride, const double* d_beam, const double* add,
                           int nx, int nz, double* out, hipStream_t st);
 
+// ---- convolve.hip: direct 2-D convolution of a stack of images (rjp_convolve2d) -------------------
+struct ConvTiling {
+  int64_t tiles_x, tiles_z;     // of 16 rows x 64 columns of the output
+  int64_t workgroups;           // n_maps x tiles_x x tiles_z: the grid
+};
+ConvTiling conv_tiling(int n_maps, int nx, int nz);
+// kernel rows per LDS chunk (>= 1 for kz <= RJP_CONV_MAX_K)
+int conv_chunk_rows(int kx, int kz);
+// `add` may be nullptr; one launch
+hipError_t convolve2d_launch(const double* in, int n_maps, int nx, int nz, const double* ker,
+                             int n_ker, int kx, int kz, const double* add, double* out,
+                             hipStream_t st);
+
+// ---- msclean.hip: multi-scale CLEAN on a stack of maps of n_s planes each (K17) ------------------
+struct MsCleanTiling {
+  int64_t tiles;                // of 1024 consecutive pixels, per plane
+  int64_t workgroups;           // n_maps x n_s x tiles: the grid of every iteration's launch
+                                // (INT64_MAX: beyond int64)
+};
+MsCleanTiling msclean_tiling(int n_maps, int n_s, int nx, int nz);
+// >= 16; 0: does not fit a size_t
+size_t msclean_workspace_bytes(int n_maps, int n_s, int nx, int nz);
+// d_weight[n_maps][n_s], d_thresh[n_maps]: device copies; `mask`, `model`, `peak` may be nullptr;
+// 1 + n_iter (+ 1 with `peak`) launches, no host synchronisation
+hipError_t msclean_launch(double* res, int n_maps, int n_s, int nx, int nz, const double* xpsf,
+                          int n_psf, int px, int pz, const double* d_weight, const uint8_t* mask,
+                          const double* d_thresh, double gain, int n_iter, int32_t* cpix,
+                          int32_t* cscale, double* cflux, int32_t* ncomp, double* model,
+                          double* peak, void* work, hipStream_t st);
+
 // ---- imfit.hip: Levenberg-Marquardt fits of one elliptical Gaussian per map (K14) ----------------
 struct GaussfitTiling {
   int64_t tiles;                // of 1024 consecutive pixels of the box, per map

@@ -1159,6 +1159,60 @@ int64_t rjp_restore(rjp_ctx* ctx, const int32_t* d_cpix, const double* d_cflux,
   return r ? r : wgs;
 }
 
+int64_t rjp_convolve2d(rjp_ctx* ctx, const double* d_in, int32_t n_maps, int32_t nx, int32_t nz,
+                       const double* d_ker, int32_t n_ker, int32_t kx, int32_t kz,
+                       const double* d_add, double* d_out, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_convolve2d(d_in, n_maps, nx, nz, d_ker, n_ker, kx, kz, d_out, m);
+      }))
+    return r;
+  const rjp::ConvTiling t = rjp::conv_tiling(n_maps, nx, nz);
+  if (t.workgroups > (int64_t)INT32_MAX || rjp::conv_chunk_rows(kx, kz) < 1)   // (check_convolve2d's)
+    return fail(ctx, RJP_ERR_ARG, "rjp_convolve2d: more than 2^31 - 1 workgroups");
+  const hipError_t e = rjp::convolve2d_launch(d_in, n_maps, nx, nz, d_ker, n_ker, kx, kz, d_add,
+                                              d_out, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ctx, RJP_ERR_HIP, "convolve2d_launch", e);
+  return t.workgroups;
+}
+
+size_t rjp_msclean_workspace(int32_t n_maps, int32_t n_s, int32_t nx, int32_t nz) {
+  if (n_maps <= 0 || n_s <= 0 || nx <= 0 || nz <= 0) return 0;
+  return rjp::msclean_workspace_bytes(n_maps, n_s, nx, nz);
+}
+
+int64_t rjp_msclean(rjp_ctx* ctx, double* d_res, int32_t n_maps, int32_t n_s, int32_t nx,
+                    int32_t nz, const double* d_xpsf, int32_t n_psf, int32_t px, int32_t pz,
+                    const double* h_weight, const uint8_t* d_mask, const double* h_thresh,
+                    double gain, int32_t n_iter, int32_t* d_cpix, int32_t* d_cscale,
+                    double* d_cflux, int32_t* d_ncomp, double* d_model, double* d_peak,
+                    void* d_work, size_t work_bytes, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_msclean(d_res, n_maps, n_s, nx, nz, d_xpsf, n_psf, px, pz, h_weight,
+                                       h_thresh, gain, n_iter, d_cpix, d_cscale, d_cflux, d_ncomp,
+                                       m);
+      }))
+    return r;
+  const rjp::MsCleanTiling t = rjp::msclean_tiling(n_maps, n_s, nx, nz);
+  if (t.workgroups > (int64_t)INT32_MAX)
+    return fail(ctx, RJP_ERR_ARG, "rjp_msclean: more than 2^31 - 1 workgroups");
+  const size_t need = rjp::msclean_workspace_bytes(n_maps, n_s, nx, nz);
+  if (!d_work || need == 0 || work_bytes < need)
+    return fail(ctx, RJP_ERR_WORKSPACE,
+                "rjp_msclean: workspace smaller than rjp_msclean_workspace()");
+  hipStream_t st = (hipStream_t)stream;
+  const int r = staged(ctx, st, "msclean_launch", nullptr,
+                       {{h_weight, (size_t)n_maps * (size_t)n_s}, {h_thresh, (size_t)n_maps}},
+                       [&](double* const* d, const double*) {
+                         return rjp::msclean_launch(d_res, n_maps, n_s, nx, nz, d_xpsf, n_psf, px,
+                                                    pz, d[0], d_mask, d[1], gain, n_iter, d_cpix,
+                                                    d_cscale, d_cflux, d_ncomp, d_model, d_peak,
+                                                    d_work, st);
+                       });
+  return r ? r : t.workgroups;
+}
+
 size_t rjp_gaussfit_workspace(int32_t n_maps, int32_t box_pixels) {
   if (n_maps <= 0 || box_pixels <= 0) return 0;
   return rjp::gaussfit_workspace_bytes(n_maps, box_pixels);

@@ -16,7 +16,7 @@ from ._lib import RJP_F32, RJP_F64, RJP_GFF_POWERLAW, RJP_GFF_SCALAR  # noqa: F4
 from .imaging import (SIDEREAL_DAY_S, AntennaConfig, Geodetic, antenna_config_path,  # noqa: F401
                       beam_from_quadratic, beam_quadratic, fit_beam, gauss_results, gauss_start,
                       geodetic, image_rms, image_scales, observation_grid, observing_plan,
-                      read_antenna_config, thermal_sigma, vis_scales)
+                      read_antenna_config, scale_biases, scale_kernel, thermal_sigma, vis_scales)
 
 
 def _torch():
@@ -1246,6 +1246,93 @@ class RTEngine:
         self._call_tiles("rjp_restore", cpix.data_ptr(), cflux.data_ptr(), ncomp.data_ptr(), M, S,
                          _lib.dbl_array(abc), _ptr(add), nx, nz, out.data_ptr())
         return out
+
+    # -- convolution / K17 -----------------------------------------------------------------------
+    def convolve2d(self, inp, nx, nz, ker, kx, kz, add=None):
+        """A direct 2-D convolution of a stack of images (rjp_convolve2d):
+        out[m][i, j] = add[m][i, j] + sum_{a, b} ker[a, b] inp[m][i - (a - ca), j - (b - cb)],
+        the centre (ca, cb) = ((kx - 1) / 2, (kz - 1) / 2), `inp` zero outside the image -> a new
+        float64 device tensor [M, nx * nz].  `inp`: float64 device tensor of M * nx * nz values;
+        `ker`: one kernel or one per map of kx * kz values, kx and kz odd; `add`: a tensor like
+        `inp` or None.  f64, one fma per term in kernel order: the same bits on every call.
+        Nothing goes to the host.  The workgroup count is kept in `last_convolve2d_workgroups`."""
+        torch = _torch()
+        nx, nz, kx, kz = int(nx), int(nz), int(kx), int(kz)
+        if nx < 1 or nz < 1 or kx < 1 or kz < 1:
+            raise ValueError("convolve2d: nx, nz, kx and kz must be positive")
+        if not (isinstance(inp, torch.Tensor) and inp.numel() >= nx * nz and
+                inp.numel() % (nx * nz) == 0):
+            raise ValueError("convolve2d: `inp` must hold a whole number (>= 1) of nx * nz images")
+        M = inp.numel() // (nx * nz)
+        self._stack_f64("convolve2d", "inp", inp, M * nx * nz)
+        if not (isinstance(ker, torch.Tensor) and ker.numel() in (kx * kz, M * kx * kz)):
+            raise ValueError("convolve2d: `ker` must hold one kernel or one per map of kx * kz "
+                             "values")
+        n_ker = ker.numel() // (kx * kz)
+        self._stack_f64("convolve2d", "ker", ker, n_ker * kx * kz)
+        if add is not None:
+            self._stack_f64("convolve2d", "add", add, M * nx * nz)
+        out = self._f64(M, nx * nz)
+        self.last_convolve2d_workgroups = self._call_tiles(
+            "rjp_convolve2d", inp.data_ptr(), M, nx, nz, ker.data_ptr(), n_ker, kx, kz, _ptr(add),
+            out.data_ptr())
+        return out
+
+    def msclean(self, res, n_s, nx, nz, xpsf, px, pz, weight, n_iter, gain, thresh, mask=None,
+                model=None):
+        """Multi-scale CLEAN minor cycles on a stack of maps of `n_s` planes each (rjp_msclean),
+        one fused launch per iteration for the whole stack, nothing going to the host -> (cpix
+        [M, n_iter] int32, cscale [M, n_iter] int32, cflux [M, n_iter] float64, ncomp [M] int32,
+        peak [M] float64) device tensors; slots at and beyond ncomp[m] are not written.  `res`:
+        float64 device tensor of M * n_s * nx * nz values, the dirty image convolved with each
+        scale on entry and the residual planes on exit (IN PLACE).  `xpsf`: the cross beams
+        X[k][l], k <= l, as a packed upper triangle of n_s (n_s + 1) / 2 planes of px * pz values
+        (odd), one set or one per map.  `weight`: host, [n_s] or [M, n_s], finite and >= 0 (0: the
+        plane is updated, never picked).  `thresh`, `mask` as `clean`; `model`: a tensor like `res`
+        that every component's flux is ADDED to, in the plane of its scale.  Per iteration and
+        map: the largest weight[k] |R_k[p]| (lower k, then lower p on a tie); stop at <= thresh;
+        else f = gain R_k[p] / X[k][k][centre] and R_l -= f X[k][l] shifted to p, for every l.
+        The same bits on every call.  The number of workgroups per iteration is kept in
+        `last_msclean_workgroups`."""
+        torch = _torch()
+        n_s, nx, nz, px, pz, n_iter = int(n_s), int(nx), int(nz), int(px), int(pz), int(n_iter)
+        if n_s < 1 or nx < 1 or nz < 1 or px < 1 or pz < 1 or n_iter < 1:
+            raise ValueError("msclean: n_s, nx, nz, px, pz and n_iter must be positive")
+        per = n_s * nx * nz
+        if not (isinstance(res, torch.Tensor) and res.numel() >= per and res.numel() % per == 0):
+            raise ValueError("msclean: `res` must hold a whole number (>= 1) of n_s * nx * nz maps")
+        M = res.numel() // per
+        self._stack_f64("msclean", "res", res, M * per)
+        tri = n_s * (n_s + 1) // 2 * px * pz
+        if not (isinstance(xpsf, torch.Tensor) and xpsf.numel() in (tri, M * tri)):
+            raise ValueError("msclean: `xpsf` must hold one set of n_s (n_s + 1) / 2 cross beams of "
+                             "px * pz values, or one per map")
+        n_psf = xpsf.numel() // tri
+        self._stack_f64("msclean", "xpsf", xpsf, n_psf * tri)
+        if model is not None:
+            self._stack_f64("msclean", "model", model, M * per)
+        dmask = self._device_mask("msclean", mask, nx * nz)
+        w = np.asarray(weight, dtype=np.float64)
+        if w.size not in (n_s, M * n_s):
+            raise ValueError("msclean: `weight` must be one per plane (%d) or one per map and "
+                             "plane" % n_s)
+        w = np.ascontiguousarray(np.broadcast_to(w.reshape(-1, n_s), (M, n_s)))
+        th = np.asarray(thresh, dtype=np.float64).reshape(-1)
+        if th.size not in (1, M):
+            raise ValueError("msclean: `thresh` must be one number or one per map (%d)" % M)
+        th = np.ascontiguousarray(np.broadcast_to(th, (M,)))
+        cpix = torch.empty(M, n_iter, dtype=torch.int32, device=self.device)
+        cscale = torch.empty(M, n_iter, dtype=torch.int32, device=self.device)
+        cflux = self._f64(M, n_iter)
+        ncomp = torch.empty(M, dtype=torch.int32, device=self.device)
+        peak = self._f64(M)
+        work = self._workspace(max(1, self.lib.rjp_msclean_workspace(M, n_s, nx, nz)))
+        self.last_msclean_workgroups = self._call_tiles(
+            "rjp_msclean", res.data_ptr(), M, n_s, nx, nz, xpsf.data_ptr(), n_psf, px, pz,
+            _lib.dbl_array(w), _ptr(dmask), _lib.dbl_array(th), float(gain), n_iter,
+            cpix.data_ptr(), cscale.data_ptr(), cflux.data_ptr(), ncomp.data_ptr(), _ptr(model),
+            peak.data_ptr(), work.data_ptr(), work.numel())
+        return cpix, cscale, cflux, ncomp, peak
 
     # -- K14 -------------------------------------------------------------------------------------
     def gaussfit(self, img, nx, nz, theta0, box=None, mask=None, n_iter=60, lambda0=1e-3,

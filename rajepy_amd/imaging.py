@@ -485,6 +485,61 @@ def _imaging_weights(eng, u_d, v_d, su, sv, w_d, ni, nj, mode, robust, mfs):
     return eng.uv_weights(u_d, v_d, su, sv, ni, nj, w=w_d, mode=mode, robust=robust)
 
 
+# -- multi-scale CLEAN: the scale kernels and their biases (host) ------------------------------------
+def scale_kernel(s):
+    """The kernel of the scale `s` [image pixels, as tclean takes `scales`] -> float64 array
+    (2 h + 1, 2 h + 1), h = ceil(s) - 1, of unit sum: the truncated paraboloid 1 - (r / s)^2 for
+    r < s, 0 beyond; s <= 0 is the delta [[1.0]].  (CASA multiplies the paraboloid by a
+    prolate-spheroidal taper; this kernel does not: DESIGN section 7.)"""
+    s = float(s)
+    if not np.isfinite(s):
+        raise ValueError("scale_kernel: the scale must be finite")
+    if s <= 0.:
+        return np.ones((1, 1))
+    h = int(np.ceil(s)) - 1
+    d = np.arange(-h, h + 1, dtype=np.float64)
+    r2 = d[:, None] ** 2 + d[None, :] ** 2
+    k = np.where(r2 < s * s, 1. - r2 / (s * s), 0.)
+    return np.ascontiguousarray(k / k.sum())
+
+
+def scale_biases(scales):
+    """The bias of each scale of `scales` [pixels], 1 - 0.6 s / s_max (Cornwell 2008, eq. 21:
+    large scales are held back) -> float64 array; 1 for a single scale (or no scale above 0)."""
+    sc = np.atleast_1d(np.asarray(scales, dtype=np.float64))
+    if sc.size == 0 or not np.all(np.isfinite(sc)):
+        raise ValueError("scale_biases: `scales` must be a non-empty list of finite sizes")
+    sc = np.maximum(sc, 0.)
+    smax = sc.max()
+    if sc.size == 1 or smax == 0.:
+        return np.ones(sc.size)
+    return 1. - 0.6 * sc / smax
+
+
+def _scale_planes(scales, scale_bias):
+    """The `scales=` / `scale_bias=` keywords of a multi-scale CLEAN -> (the scale of every plane
+    [pixels], the bias of every plane, h_max): plane 0 is ALWAYS the delta scale -- bias 1 if 0 is
+    among `scales`, else 0 (the raw residual is updated but never picked) --, the non-zero scales
+    follow, ascending and without repeats.  `scale_bias`: None (`scale_biases` of the planes) or
+    one bias per plane in that order."""
+    sc = np.atleast_1d(np.asarray(scales, dtype=np.float64)).reshape(-1)
+    if sc.size == 0 or not np.all(np.isfinite(sc)):
+        raise ValueError("clean: `scales` must be a non-empty list of finite sizes in pixels")
+    planes = np.concatenate([[0.], np.unique(sc[sc > 0.])])
+    if scale_bias is None:
+        bias = scale_biases(planes)
+    else:
+        bias = np.asarray(scale_bias, dtype=np.float64).reshape(-1).copy()
+        if bias.size != planes.size or not np.all(np.isfinite(bias) & (bias >= 0.)):
+            raise ValueError("clean: `scale_bias` must be one finite bias >= 0 per plane (%d: the "
+                             "delta scale, then the other scales ascending)" % planes.size)
+    if not np.any(sc <= 0.):
+        bias[0] = 0.
+    if not np.any(bias > 0.):
+        raise ValueError("clean: every scale has bias 0")
+    return planes, bias, int(np.ceil(planes.max())) - 1 if planes.max() > 0. else 0
+
+
 class Imager:
     """Visibilities, images, synthetic observations and Gaussian fits of the flux maps of an
     nx x nz grid of `csize_au` cells at `dist_pc`, through `engine` (an `RTEngine`).  Maps and
@@ -651,7 +706,8 @@ class Imager:
         return m != 0
 
     def _clean_images(self, V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
-                      threshold_jy, mask, beam, psf_shape, imfit=None, weighting=None, robust=0.5):
+                      threshold_jy, mask, beam, psf_shape, imfit=None, weighting=None, robust=0.5,
+                      scales=None, scale_bias=None):
         """Hogbom CLEAN of the dirty images of `V` (see `JetModel.clean_image_ff`), in chunks of
         channels whose dirty images AND beams stay under `stack_bytes`.  Per chunk, on the device:
         `_dirty_images` of V and of unit visibilities (the beams, on the `psf_shape` grid),
@@ -659,7 +715,11 @@ class Imager:
         host before the end (for `fit_beam`).  With `weighting` "uniform" / "briggs" the chunk's
         imaging weights are computed ONCE, on the image's grid (never the larger beam grid), and
         image and beam share them; the chunks then also keep the [F, K] weights under
-        `stack_bytes`."""
+        `stack_bytes`.
+        `scales` (pixels, with `scale_bias`: `_scale_planes`): multi-scale CLEAN instead, per
+        chunk `_msclean_chunk` -- `RTEngine.convolve2d`, `RTEngine.msclean` -- and the chunks
+        count the n_s planes and the n_s (n_s + 1) / 2 cross beams; the threshold is then one of
+        the SCORE, bias x component flux."""
         import torch
         eng = self.engine
         ni, nj, cell = self._image_grid(shape, cell_as)
@@ -682,6 +742,22 @@ class Imager:
                           model=np.zeros((n_out, ni, nj)), components=[], beam=[],
                           peak_residual=np.zeros(n_out), imfit=None if fit_opts is None else [])
         step = F if mfs else max(1, self.stack_bytes // ((ni * nj * 3 + pi_ * pj) * 8))
+        ms = None
+        if scales is not None:
+            planes, bias, hmax = _scale_planes(scales, scale_bias)
+            n_s = len(planes)
+            mk = np.ones((ni, nj), dtype=bool) if mk is None else mk.copy()
+            if hmax > 0:
+                # a component nearer than h_max to the border would lose part of its scale kernel
+                mk[:hmax], mk[ni - hmax:], mk[:, :hmax], mk[:, nj - hmax:] = False, False, False, False
+            if not mk.any():
+                raise ValueError("clean: no pixel of the mask lies at least %d pixels (the largest "
+                                 "scale's half width) from the border" % hmax)
+            ms = dict(planes=planes, bias=bias, hmax=hmax, mask=torch.from_numpy(mk).to(eng.device),
+                      ker=[torch.from_numpy(scale_kernel(s)).to(eng.device) for s in planes])
+            if not mfs:
+                step = max(1, self.stack_bytes // (
+                    (ni * nj * (2 * n_s + 1) + n_s * (n_s + 1) // 2 * pi_ * pj) * 8))
         hi, hj = min(self.BEAM_PATCH, pi_) // 2, min(self.BEAM_PATCH, pj) // 2
         mode = _weighting_mode(weighting)
         if mode is not None:
@@ -698,21 +774,32 @@ class Imager:
                 iw = _imaging_weights(eng, u_d, v_d, isu, isv, w_d, ni, nj, mode, robust, mfs)
             dirty = self._dirty_images(V[sl], u_d, v_d, freqs[sl], weights, (ni, nj), cell_as,
                                        mfs, device=True, iw=iw)
-            psf = self._dirty_images(ones[sl], u_d, v_d, freqs[sl], weights, (pi_, pj), cell_as,
-                                     mfs, device=True, iw=iw)
+            grow = 0 if ms is None else 4 * ms["hmax"]
+            psf = self._dirty_images(ones[sl], u_d, v_d, freqs[sl], weights,
+                                     (pi_ + grow, pj + grow), cell_as, mfs, device=True, iw=iw)
             del iw
             M = int(dirty.shape[0])
+            if grow:
+                # (the clean beam is fitted to, and the cross beams cropped to, the `psf_shape` window)
+                big, g = psf, grow // 2
+                psf = big.reshape(M, pi_ + grow, pj + grow)[:, g:g + pi_, g:g + pj].reshape(
+                    M, pi_ * pj).contiguous()
             if beam is None:
                 ci, cj = (pi_ - 1) // 2, (pj - 1) // 2
                 patch = psf.reshape(M, pi_, pj)[:, ci - hi:ci + hi + 1, cj - hj:cj + hj + 1]
                 abc = [fit_beam(p) for p in patch.cpu().numpy()]
             else:
                 abc = [beam_quadratic(beam[0], beam[1], beam[2], cell)] * M
-            model = torch.zeros_like(dirty)
-            cpix, cflux, ncomp, peak = eng.clean(dirty, ni, nj, psf, pi_, pj, niter, gain,
-                                                 float(thr[0]) if thr.size == 1 else thr[f0:f0 + M],
-                                                 mask=mk, model=model)
-            image = eng.restore(cpix, cflux, ncomp, abc, ni, nj, add=dirty)
+            thr_c = float(thr[0]) if thr.size == 1 else thr[f0:f0 + M]
+            cscale = None
+            if ms is None:
+                model = torch.zeros_like(dirty)
+                cpix, cflux, ncomp, peak = eng.clean(dirty, ni, nj, psf, pi_, pj, niter, gain, thr_c,
+                                                     mask=mk, model=model)
+                image = eng.restore(cpix, cflux, ncomp, abc, ni, nj, add=dirty)
+            else:
+                dirty, model, image, cpix, cscale, cflux, ncomp, peak = self._msclean_chunk(
+                    dirty, psf if not grow else big, ni, nj, pi_, pj, ms, abc, niter, gain, thr_c)
             o = slice(f0, f0 + M)
             if fit_opts is not None:
                 res.imfit.extend(self._imfit_images(image, ni, nj, abc, cell, fit_opts, o))
@@ -721,13 +808,71 @@ class Imager:
             res.model[o] = model.cpu().numpy().reshape(M, ni, nj)
             res.peak_residual[o] = peak.cpu().numpy()
             hp, hf, hn = cpix.cpu().numpy(), cflux.cpu().numpy(), ncomp.cpu().numpy()
+            hs = cscale.cpu().numpy() if cscale is not None else None
             for m in range(M):
                 n = int(hn[m])
-                res.components.append(np.stack([hp[m, :n] // nj, hp[m, :n] % nj, hf[m, :n]],
-                                               axis=1).astype(np.float64).reshape(n, 3))
+                cols = [hp[m, :n] // nj, hp[m, :n] % nj, hf[m, :n]]
+                if hs is not None:
+                    cols.append(ms["planes"][hs[m, :n]])          # (ix, iz, flux, scale [pixels])
+                res.components.append(np.stack(cols, axis=1).astype(np.float64)
+                                      .reshape(n, len(cols)))
                 res.beam.append(beam_from_quadratic(*abc[m], cell))
             del dirty, psf, model, image, cpix, cflux, ncomp, peak
         return res
+
+    def _msclean_chunk(self, dirty, beam, ni, nj, pi_, pj, ms, abc, niter, gain, thr):
+        """Multi-scale CLEAN of one chunk's dirty images [M, ni * nj] -> (raw residual, model,
+        image [M, ni * nj], cpix, cscale, cflux, ncomp, peak_residual), all on the device.
+        `beam` [M, (pi_ + 4 h_max)(pj + 4 h_max)]: the dirty beams on the enlarged grid, so that
+        the cross beams X[k][l] = m_k * m_l * B, cropped to the centre (pi_, pj) window, are exact
+        in the window and not truncated at its edge.  Planes R_l = m_l * D; weight[m][k] =
+        bias_k / X_kk(centre), which makes the score the component's flux times the bias (CASA's
+        normalisation); model = sum_k m_k * (delta model k); image = raw residual + sum_k m_k *
+        restore(components of scale k).  `peak_residual`: the masked max of the raw plane."""
+        import torch
+        eng = self.engine
+        planes, ker, hmax = ms["planes"], ms["ker"], ms["hmax"]
+        n_s, M, npix = len(planes), int(dirty.shape[0]), ni * nj
+        bi, bj = pi_ + 4 * hmax, pj + 4 * hmax
+
+        def conv(x, nx, nz, k, add=None):
+            # (the delta scale's kernel is [[1.0]]: the identity, nothing to launch)
+            if ker[k].numel() == 1 and add is None:
+                return x
+            side = int(ker[k].shape[0])
+            return eng.convolve2d(x, nx, nz, ker[k].reshape(-1), side, side, add=add)
+
+        g = 2 * hmax
+        single = [conv(beam, bi, bj, k) for k in range(n_s)]
+        xpsf = torch.stack([conv(single[k], bi, bj, l).reshape(M, bi, bj)[:, g:g + pi_, g:g + pj]
+                            for k in range(n_s) for l in range(k, n_s)], dim=1)
+        xpsf = xpsf.reshape(M, -1, pi_ * pj).contiguous()
+        del single
+        res = torch.stack([conv(dirty, ni, nj, l) for l in range(n_s)], dim=1).contiguous()
+        centre = ((pi_ - 1) // 2) * pj + (pj - 1) // 2
+        diag = [k * n_s - k * (k - 1) // 2 for k in range(n_s)]
+        xkk = xpsf[:, diag, centre].cpu().numpy()                       # [M, n_s]: a few numbers
+        with np.errstate(divide="ignore", invalid="ignore"):
+            weight = np.where(ms["bias"][None, :] > 0., ms["bias"][None, :] / xkk, 0.)
+        if not np.all(np.isfinite(weight) & (weight >= 0.)):
+            raise ValueError("clean: a scale's beam X_kk is not positive at its centre")
+        model = torch.zeros_like(res)
+        cpix, cscale, cflux, ncomp, _ = eng.msclean(res, n_s, ni, nj, xpsf, pi_, pj, weight, niter,
+                                                    gain, thr, mask=ms["mask"], model=model)
+        del xpsf
+        raw = res[:, 0].contiguous()
+        total, image = model[:, 0].contiguous(), raw          # (plane 0 is the delta scale)
+        for k in range(n_s):
+            # K13 with the other scales' fluxes zeroed, then the scale's kernel, chained by `add`
+            fk = torch.where(cscale == k, cflux, torch.zeros_like(cflux))
+            if k == 0:
+                image = eng.restore(cpix, fk, ncomp, abc, ni, nj, add=image)
+                continue
+            total = conv(model[:, k].contiguous(), ni, nj, k, add=total)
+            image = conv(eng.restore(cpix, fk, ncomp, abc, ni, nj), ni, nj, k, add=image)
+        ok = ms["mask"].reshape(1, -1) & torch.isfinite(raw)
+        peak = torch.where(ok, raw.abs(), torch.zeros_like(raw)).amax(dim=1)
+        return raw, total, image, cpix, cscale, cflux, ncomp, peak
 
     # ------------------------------------------------------------------ synthetic observations ----
     def uv_tracks(self, antennalist, dec_deg, t_obs_s, t_int_s, min_el_deg=None, hourangle_h=0.):
@@ -747,7 +892,7 @@ class Imager:
 
     def _observe(self, maps, freqs, tracks, t_int_s, sigma_jy, sefd_jy, chanwidth_hz, seed,
                  nsigma, weights, shape, cell_as, mfs, niter, gain, threshold_jy, mask, beam,
-                 psf_shape, imfit, weighting, robust):
+                 psf_shape, imfit, weighting, robust, scales=None, scale_bias=None):
         """`JetModel.observe_*` after the maps [F, nx * nz]: visibilities, noise, image rms, CLEAN."""
         F = len(freqs)
         if sigma_jy is not None and sefd_jy is not None:
@@ -785,7 +930,7 @@ class Imager:
                 imfit["rms"] = rms
         res = self._clean_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
                                  thr, mask, beam, psf_shape, imfit, weighting=weighting,
-                                 robust=robust)
+                                 robust=robust, scales=scales, scale_bias=scale_bias)
         v0 = V0.cpu().numpy()
         return Observation(tracks, v0, V.cpu().numpy() if noisy else v0.copy(), sigma, rms, res)
 
