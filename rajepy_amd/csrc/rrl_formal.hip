@@ -14,6 +14,7 @@
 // and its absorption of what lies behind it accumulate directly,
 //   e_c = e^-c, om_l = 1 - e^-l, u = 1 - e^-(c + l) = (1 - e_c) + e_c om_l
 //   I += B (e_c om_l Theta_C - u D);  D = e_c (D + (Theta_C - D) om_l);  Theta_C *= e_c.
+// e_c and 1 - e_c both come out of one_minus_exp_neg(c, e_c), each at its own relative accuracy.
 // With a constant T the sum telescopes to B e^-tau_C (1 - e^-tau_L): the reference's product.
 // A cell contributes its c exactly when K5 counts it (formal_b != 0) and its l exactly when K3
 // does (CellLine::C != 0, i.e. path_code != kPathSkip); the output is NaN exactly where T_avg is
@@ -60,8 +61,10 @@ constexpr int kCodeCont = 16;
 // cell without line opacity: the update is then the continuum's alone), c its continuum depth
 __device__ __forceinline__ void formal_line_update(double Bp, double c, double om_l, double& I,
                                                    double& Th, double& D) {
-  const double om_c = one_minus_exp_neg(c);
-  const double e_c = 1.0 - om_c;
+  // e_c at its own relative accuracy: 1 - om_c is off by e^c 2^-53 of it, which a pixel behind a
+  // thick front cell inherits whole (B e^-c (1 - e^-l): 1.7e-4 at c = 30)
+  double e_c;
+  const double om_c = one_minus_exp_neg(c, e_c);
   const double t = e_c * om_l;
   const double u = om_c + t;
   I = __builtin_fma(Bp, __builtin_fma(t, Th, -(u * D)), I);

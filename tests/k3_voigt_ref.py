@@ -63,8 +63,9 @@ def line_term_ref(fields_f64, line, nu, time=0.0):
     values; Re w(x + i y) is scipy.special.wofz of x and y rounded to float64.
 
     -> dict of float64 arrays [len(nu)] + fields' shape: term, x, y, rew, imw, and nu0_is2 (the
-    cell's nu0 / (sigma sqrt 2), what `tol` needs), shaped as the fields.  A NaN term is one the
-    reference's nansum drops."""
+    cell's nu0 / (sigma sqrt 2), what `tol` needs), shaped as the fields; term_ld is the term before
+    its cast to float64 (tests/rrl_formal_ld_ref.py walks it).  A NaN term is one the reference's
+    nansum drops."""
     f = {k: np.asarray(fields_f64[k], dtype=np.float64).astype(LD)
          for k in ("nd", "xi", "temp", "pf", "vy")}
     nu = np.asarray(nu, dtype=np.float64).astype(LD).reshape((-1,) + (1,) * f["nd"].ndim)
@@ -83,7 +84,7 @@ def line_term_ref(fields_f64, line, nu, time=0.0):
         stim = -np.expm1(-LD(line["h_over_k"]) * nu / f["temp"])
         path = LD(fields_f64["csize_au"]) * LD(AU_CM) * f["pf"]
         term = lte * (rew.astype(LD) / (sigma * np.sqrt(2 * LD(np.pi)))) * stim * path
-    return dict(term=term.astype(np.float64), x=x64, y=y64, rew=rew, imw=imw,
+    return dict(term=term.astype(np.float64), term_ld=term, x=x64, y=y64, rew=rew, imw=imw,
                 nu0_is2=(nu0 / s2).astype(np.float64))
 
 

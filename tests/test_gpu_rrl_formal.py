@@ -7,7 +7,11 @@ under test: the oracle's, or rjp_rrl_cells + rjp_ff_cells.
 Tolerance: |got - ref| <= r |ref| + r max_p |ref[f]| with r = gpu_util.k3_rtol(nchan), the
 project's Voigt bound (1e-8 on the wave-uniform paths, 1e-9 on the per-lane path).  The absolute
 term is needed because a pixel is a difference of emission and absorption: a relative Voigt error
-on either does not scale with their difference.  NaN patterns must match exactly."""
+on either does not scale with their difference.  NaN patterns must match exactly.
+
+That absolute term is normalised to the channel's brightest pixel, so a fainter pixel may be off by
+max / |ref| times the bound: tests/test_gpu_rrl_formal_ld.py holds every pixel to a bound of its own
+against a long-double reference."""
 import copy
 import ctypes as C
 import os
