@@ -204,7 +204,26 @@ typedef struct rjp_fields {
    * smallest chi^2 and the truncated interpolant passes the same checks).  The planes are read as
    * 16-byte pairs of sightlines: d_srt_mom must be 16-byte aligned and P even, else the scan
    * fails.  rjp_last_srt_bins() counts both kinds.
-   * The moments belong to the layout: rebuild them with it. */
+   * The moments belong to the layout: rebuild them with it.
+   * Optional with the moments (both NULL = absent): the layout's PACKED state, built by
+   * rjp_srt_pack() from the finished layout -- the same rows in the same (row, lane) arrangement
+   * at 10 bytes per cell.  With r0 = ((d_srt_rowbase[g] + 7) & ~7) + 8 g the first packed row of
+   * group g (every group's rows are rounded up to 8; rjp_srt_packed_rows() rows in all) and r a row
+   * of the group:
+   *   d_srt_pts[((r0 + r) / 2) * 64 + lane] = (ts[r], ts[r + 1])         16 bytes, r even
+   *   d_srt_pw [((r0 + r) / 8) * 64 + lane] = weights of rows r .. r + 7  16 bytes, 16 bits each
+   * A weight is |a0| >= 0 rounded to nearest even to the upper 16 bits below the sign of a float
+   * (8 exponent bits, 8 mantissa bits: relative error <= 2^-9); rows past a lane's length and the
+   * padding hold weight 0.  A bin whose interpolant matches the exact chi^2 but not the table's is
+   * then tested with the table's own error added, E_i(xi) = table^2 - chi^2 fitted per table piece
+   * by a polynomial of degree 8 (f32): where that matches the table to the same 2e-14 at the same
+   * points, the scan contracts the bin from its moments and adds sum |a0| E(ts) over the bin's
+   * cells from the packed state -- that term is <= ~2.2e-13 of the bin's sum, so 8 bits of the
+   * weight do (4.3e-16), while the launch time, which picks the table piece, stays exact -- wherever
+   * 6 bytes x the longest lane run exceed (srt_N - 1) x 8 bytes.  Such a bin counts as read in
+   * rjp_last_srt_bins(); rjp_last_srt_resid() counts them.  Not taken when the chi table and the
+   * error table (128 bytes per piece and jet) exceed 80 KiB of LDS.  Both pointers 16-byte aligned.
+   * The packed state belongs to the layout's cells: rebuild it whenever they change. */
   const void* d_srt_cells;
   const int32_t* d_srt_start;
   const double* d_srt_cum;
@@ -214,6 +233,8 @@ typedef struct rjp_fields {
   const double* d_srt_mom;
   int32_t srt_K;            /* launch-time bins per jet, 1..32 */
   int32_t srt_N;            /* order of d_srt_mom: 16, 20 or 24 (0 = no moments) */
+  const void* d_srt_pts;    /* packed launch times, pairs of rows (rjp_srt_pack) */
+  const void* d_srt_pw;     /* packed 16-bit weights, eight rows per 16 bytes */
 } rjp_fields;
 
 /* Ejection bursts (classes.py:399-463): mdot(t)/mdot_ss = 1 + sum_b amp_rel_b *
@@ -420,6 +441,21 @@ size_t rjp_srt_moment_entries(int32_t nx, int32_t nz, int32_t K, int32_t N);
 int rjp_srt_moments(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, int32_t N,
                     const int32_t* d_start, const int64_t* d_rowbase, const void* d_cells,
                     double* d_mom, void* stream);
+/* The layout's packed state (rjp_fields.d_srt_pts / d_srt_pw): rjp_srt_packed_rows(nx, nz,
+ * total_rows) rows R (a multiple of 8; 0 for a bad shape), d_pts = R * 64 * 8 bytes, d_pw = R * 64 *
+ * 2 bytes, both 16-byte aligned, written by rjp_srt_pack from a layout rjp_srt_fill has built with
+ * the same fields and K: one coalesced pass over the layout's rows.  Returns 1 when every weight
+ * fits the 16-bit format, 2 when some finite non-zero weight lies below 2^-126 or would round to
+ * 2^128 and beyond -- it would be flushed or saturated and its residual lost: do NOT attach the
+ * state then -- or a negative rjp_status: a bad K or fields, a NULL or misaligned pointer.
+ * Synchronises the stream. */
+size_t rjp_srt_packed_rows(int32_t nx, int32_t nz, int64_t total_rows);
+int64_t rjp_srt_pack(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, const int32_t* d_start,
+                     const int64_t* d_rowbase, const void* d_cells, void* d_pts, void* d_pw,
+                     void* stream);
+/* The table-residual (group, jet, bin) triples of the last scan (a subset of rjp_last_srt_bins'
+ * *read), or a negative rjp_status.  SYNCHRONISES the device.  For tests. */
+int64_t rjp_last_srt_resid(rjp_ctx* ctx);
 
 /* ---- K2: per-channel map stage --------------------------------------------------------
  * Replaces the map-level arithmetic of optical_depth_ff / intensity_ff / flux_ff

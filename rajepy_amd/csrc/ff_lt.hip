@@ -492,6 +492,88 @@ hipError_t srt_moments_launch(const rjp_fields* fl, int K, int N, const int32_t*
   return hipGetLastError();
 }
 
+// ---- the packed state of the bucketed layout (rjp_fields.d_srt_pts / d_srt_pw) ------------------
+// The same rows in the same (row, lane) arrangement at 10 bytes per cell, for the bins a
+// single-epoch scan takes as table-residual bins (ff_scan_tab.hip): there the weight multiplies
+// only the table's own error, <= ~2.2e-13 of the bin's sum, and needs 2^-9, not 2^-53; the launch
+// time stays exact (it picks the table piece).  Rows of group g start at srt_packed_row() (a
+// multiple of 8), rounded up to 8 per group:
+//   pts[(row / 2) * 64 + lane] = (ts[row], ts[row + 1])               16 bytes, row even
+//   pw [(row / 8) * 64 + lane] = the weights of rows row .. row + 7   16 bytes, 16 bits each
+// A weight is never negative, so its 16 bits are f32's 8 exponent bits and 8 mantissa bits
+// (bfloat16 with the sign bit spent on the mantissa), rounded to nearest even straight from the
+// f64 bits: |w~ - w| <= 2^-9 w.  Rows past a lane's length (and the padding) hold weight 0, time 0.
+// A weight outside the format's normal range -- below 2^-126, or rounding to 2^128 and beyond --
+// would be flushed or saturated and its residual (up to 6e-14 of its term) lost: the kernel raises
+// `flag` instead and the caller does not attach the state.  One wave per group streams the
+// finished layout once; srt_fill_kernel is untouched.
+__device__ __forceinline__ unsigned srt_pack_weight(double w, bool& bad) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(w);
+  const unsigned long long r = b + ((1ull << 43) - 1ull) + ((b >> 44) & 1ull);
+  const int top = (int)(r >> 44);                      // 11 exponent bits (and the sign), 8 mantissa bits
+  const int e = (top >> 8) - 896;                      // f64's bias -> f32's
+  const bool ok = e >= 1 && e <= 254;
+  bad = !ok && b != 0ull;
+  return ok ? (unsigned)((e << 8) | (top & 255)) : 0u;
+}
+
+__global__ __launch_bounds__(256) void srt_pack_kernel(const rjp_d2* __restrict__ cells,
+                                                       const int32_t* __restrict__ start,
+                                                       const int64_t* __restrict__ rowbase,
+                                                       int64_t npix, int Q,
+                                                       rjp_d2* __restrict__ pts,
+                                                       rjp_u4* __restrict__ pw,
+                                                       int* __restrict__ flag) {
+  constexpr int U = 8;
+  const int lane = threadIdx.x & (kLtLanes - 1);
+  const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g * kLtLanes >= npix) return;                    // (whole waves)
+  const int64_t p = g * kLtLanes + lane;
+  const int len = p < npix ? start[(int64_t)Q * npix + p] : 0;
+  const int64_t rb = rowbase[g];
+  const int nrow = (int)(rowbase[g + 1] - rb);
+  const rjp_d2* base = cells + rb * kLtLanes + lane;
+  const int64_t pb = srt_packed_row(rb, g);
+  rjp_d2* ot = pts + (pb / 2) * kLtLanes + lane;
+  rjp_u4* ow = pw + (pb / 8) * kLtLanes + lane;
+  bool any_bad = false;
+  for (int r = 0; r < nrow; r += U) {
+    rjp_d2 cl[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int rr = r + u < nrow ? r + u : nrow - 1;  // (never past the group's last row)
+      cl[u] = __builtin_nontemporal_load(base + (int64_t)rr * kLtLanes);
+    }
+    unsigned h[U];
+    double tt[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const bool mine = r + u < len;
+      bool bad;
+      h[u] = srt_pack_weight(mine ? cl[u].x : 0.0, bad);
+      tt[u] = mine ? cl[u].y : 0.0;
+      any_bad |= bad;
+    }
+#pragma unroll
+    for (int k = 0; k < U / 2; ++k)
+      ot[(int64_t)(r / 2 + k) * kLtLanes] = rjp_d2{tt[2 * k], tt[2 * k + 1]};
+    ow[(int64_t)(r / 8) * kLtLanes] = rjp_u4{h[0] | (h[1] << 16), h[2] | (h[3] << 16),
+                                            h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
+  }
+  if (any_bad) *flag = 1;
+}
+
+hipError_t srt_pack_launch(const rjp_fields* fl, int K, const int32_t* d_start,
+                           const int64_t* d_rowbase, const void* d_cells, void* d_pts, void* d_pw,
+                           int* d_flag, hipStream_t st) {
+  const int64_t npix = (int64_t)fl->nx * fl->nz;
+  const int64_t G = (npix + kLtLanes - 1) / kLtLanes;
+  hipLaunchKernelGGL(srt_pack_kernel, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, st,
+                     (const rjp_d2*)d_cells, d_start, d_rowbase, npix, 2 * K, (rjp_d2*)d_pts,
+                     (rjp_u4*)d_pw, d_flag);
+  return hipGetLastError();
+}
+
 // ---- the sweep ----------------------------------------------------------------------------------
 __device__ __forceinline__ rjp_d2 lt_load(const rjp_d2* p) { return __builtin_nontemporal_load(p); }
 

@@ -380,11 +380,107 @@ __device__ __forceinline__ double chi_exact(const double* bj, int nb, double tl)
   return chi;
 }
 
-// one workgroup per key q = jet * K + bin; `tab` / `t` / `stage` as chi_table_kernel's
+// ---- table-residual bins -------------------------------------------------------------------------
+// Check (b) rejects the bins on the steep flanks, where the TABLE's interpolation error
+// E_i(xi) = T_i(xi)^2 - F reaches 2e-14 .. 6e-14 of F; there p still matches the exact F to a few
+// 1e-15.  E is a smooth function of the table piece i and the piece coordinate xi alone, so per
+// call srt_err_kernel fits it on every piece by a polynomial of degree 8 (least squares at 12
+// Chebyshev nodes of the exact chi, f64; 9 monomial coefficients stored in f32 at a stride of 48
+// bytes, an odd multiple of 16 like the chi table's 80), and a bin that passes (a) and fails (b) is
+// tested against
+//   (b')  |p + E~_i(xi) - T^2| <= kSrtMomTol T^2   at the same 4 N points,
+// E~ and (i, xi) evaluated exactly as the scan evaluates them (the lookup's f64 index arithmetic,
+// xi rounded to f32, an f32 Horner chain).  For such a bin
+//   sum |a0| T^2(ts) = sum_n W_n M_n + sum_cells |a0| E~_i(xi(ts)):
+// the first term is the contraction of any accepted bin, and the second -- at most ~2.2e-13 of
+// the bin's sum by the table's own bound -- needs the launch time exactly but the weight to 8 bits
+// only: the scan streams it from the layout's packed state (rjp_fields.d_srt_pts / d_srt_pw,
+// ff_lt.hip), 10 bytes per cell instead of 16.  Error budget of a residual bin against the same
+// bin read through the table: kSrtMomTol at the check points + 2^-9 x 2.2e-13 = 4.3e-16 from the
+// weight.  (a), (b), kSrtMomTol, kSrtTailFrac and the table are what they were; the count rule
+// runs with (b') in place of (b) on such a bin.
+#ifndef RJP_SRT_RESID
+#define RJP_SRT_RESID 1          /* 0: a build without table-residual bins (what fails (b) is read cell by cell), for A/B only */
+#endif
+#ifndef RJP_SRT_RESID_BLOCKS
+#define RJP_SRT_RESID_BLOCKS 2   /* blocks of 8 packed rows (5 loads of 16 B) in flight per lane */
+#endif
+constexpr int kErrNC = 9;                    // coefficients per piece (degree 8)
+constexpr int kErrNodes = 12;
+constexpr int kErrStride = 12;               // floats between pieces (48 B)
+// chi table + error table of a scan with residual bins: two workgroups per CU (160 KiB of LDS)
+constexpr size_t kSrtResidShm = 80 * 1024;
+constexpr int kSrtResidFlag = 0x100;         // in srt_coef_kernel's verdict, above the count
+// row n: the monomial coefficients of T_n
+__device__ const double kErrCheb[kErrNC][kErrNC] = {
+    {1, 0, 0, 0, 0, 0, 0, 0, 0},        {0, 1, 0, 0, 0, 0, 0, 0, 0},
+    {-1, 0, 2, 0, 0, 0, 0, 0, 0},       {0, -3, 0, 4, 0, 0, 0, 0, 0},
+    {1, 0, -8, 0, 8, 0, 0, 0, 0},       {0, 5, 0, -20, 0, 16, 0, 0, 0},
+    {-1, 0, 18, 0, -48, 0, 32, 0, 0},   {0, -7, 0, 56, 0, -112, 0, 64, 0},
+    {1, 0, -32, 0, 160, 0, -256, 0, 128}};
+
+// behind chi_table_kernel: E[(jet * ni + k) * kErrStride + c]
+__global__ __launch_bounds__(256) void srt_err_kernel(const double* __restrict__ stage, int nb0,
+                                                      int nb1, ChiTabDev t,
+                                                      const double* __restrict__ tab,
+                                                      float* __restrict__ E) {
+  // sixteen lanes per piece: lane m < 12 takes node m (the kernel sits in the scan's chain of
+  // dependent launches when the tables are not built ahead: one thread per piece, twelve nodes
+  // each, cost the 0.3 yr scan more than its two residual bins saved), then lane q < 9 writes
+  // coefficient q
+  const int tid = blockIdx.x * 256 + threadIdx.x;
+  const int i = tid >> 4, m = tid & 15;
+  const bool piece = i < 2 * t.ni;
+  double e = 0.0;
+  if (piece && m < kErrNodes) {
+    const int j = i / t.ni, k = i - j * t.ni;
+    const int nb = j == 0 ? nb0 : nb1;
+    const double* bj = stage + kChiNC * kChiNC + kChiNC + (j == 0 ? 0 : 3 * nb0);
+    const double* cp = tab + (size_t)i * kChiStride;
+    const double x = cospi((m + 0.5) / kErrNodes);
+    const double chi = chi_exact(bj, nb, t.lo + (k + 0.5 * (x + 1.0)) * (1.0 / t.inv_h));
+    double ct = cp[7];
+    for (int n = 6; n >= 0; --n) ct = __builtin_fma(ct, x, cp[n]);
+    e = ct * ct - chi * chi;
+  }
+  // Chebyshev coefficients c_n = s_n sum_m e_m T_n(x_m), summed over the piece's lanes
+  double c[kErrNC];
+#pragma unroll
+  for (int n = 0; n < kErrNC; ++n) {
+    double v = e * cospi((double)((n * (2 * m + 1)) % (4 * kErrNodes)) / (2 * kErrNodes));
+#pragma unroll
+    for (int d = 8; d > 0; d >>= 1) v += __shfl_xor(v, d, 16);
+    c[n] = v * ((n == 0 ? 1.0 : 2.0) / kErrNodes);
+  }
+  if (!piece || m >= kErrStride) return;
+  double a = 0.0;
+  if (m < kErrNC) {
+#pragma unroll
+    for (int n = 0; n < kErrNC; ++n) a += c[n] * kErrCheb[n][m];
+  }
+  E[(size_t)i * kErrStride + m] = (float)a;
+}
+
+// E~ of a piece at xi: the f32 Horner chain of the scan and of check (b')
+__device__ __forceinline__ float srt_err_eval(const rjp_f4 e0, const rjp_f4 e1, const float e8,
+                                              const float xf) {
+  float v = __builtin_fmaf(e8, xf, e1.w);
+  v = __builtin_fmaf(v, xf, e1.z);
+  v = __builtin_fmaf(v, xf, e1.y);
+  v = __builtin_fmaf(v, xf, e1.x);
+  v = __builtin_fmaf(v, xf, e0.w);
+  v = __builtin_fmaf(v, xf, e0.z);
+  v = __builtin_fmaf(v, xf, e0.y);
+  return __builtin_fmaf(v, xf, e0.x);
+}
+
+// one workgroup per key q = jet * K + bin; `tab` / `t` / `stage` as chi_table_kernel's; `E`:
+// srt_err_kernel's table, or null when the scan takes no residual bins
 __global__ __launch_bounds__(kSrtCoefThreads) void srt_coef_kernel(const double* __restrict__ stage,
                                                                    int nb0, int nb1, ChiTabDev t,
                                                                    double t_epoch,
                                                                    const double* __restrict__ tab,
+                                                                   const float* __restrict__ E,
                                                                    SrtCoefDev c) {
   __shared__ double sF[kSrtMaxN], sW[kSrtMaxN], sFc[4 * kSrtMaxN];
   const int q = blockIdx.x, i = threadIdx.x;
@@ -413,7 +509,7 @@ __global__ __launch_bounds__(kSrtCoefThreads) void srt_coef_kernel(const double*
   __syncthreads();
   // checks (a) and (b) at this thread's point, for the first `cnt` coefficients
   const double x = -1.0 + 2.0 * i / (4 * N - 1);
-  double F = 1.0, T = 1.0;
+  double F = 1.0, T = 1.0, Et = 0.0;
   if (i < 4 * N) {
     const double ts = ts_of(x);
     const double chi = chi_exact(bj, nb, t_epoch - ts);
@@ -428,8 +524,14 @@ __global__ __launch_bounds__(kSrtCoefThreads) void srt_coef_kernel(const double*
     for (int n = 6; n >= 0; --n) ct = __builtin_fma(ct, xi, cp[n]);
     T = ct * ct;
     sFc[i] = F;
+    if (RJP_SRT_RESID && E) {
+      // the fitted table error at this point, piece and xi as the scan takes them
+      const rjp_f4* ep = reinterpret_cast<const rjp_f4*>(E + (size_t)((int)kf + (j == 0 ? 0 : t.ni)) * kErrStride);
+      Et = (double)srt_err_eval(ep[0], ep[1], ep[2].x, (float)xi);
+    }
   }
-  auto passes = [&](int cnt) {
+  // `resid`: check (b') in place of (b)
+  auto passes = [&](int cnt, bool resid) {
     if (i >= 4 * N) return 1;
     double u1 = 0.0, u2 = 0.0;                 // Clenshaw
     for (int n = cnt - 1; n >= 1; --n) {
@@ -437,9 +539,15 @@ __global__ __launch_bounds__(kSrtCoefThreads) void srt_coef_kernel(const double*
       u2 = u1; u1 = un;
     }
     const double pv = __builtin_fma(x, u1, sW[0] - u2);
-    return (int)(__builtin_fabs(pv - F) <= kSrtMomTol * F && __builtin_fabs(pv - T) <= kSrtMomTol * T);
+    const double pt = resid ? pv + Et : pv;
+    return (int)(__builtin_fabs(pv - F) <= kSrtMomTol * F && __builtin_fabs(pt - T) <= kSrtMomTol * T);
   };
-  const int ok = __syncthreads_and(passes(N));         // (the barrier publishes sFc as well)
+  int ok = __syncthreads_and(passes(N, false));        // (the barrier publishes sFc as well)
+  int resid = 0;
+  if (RJP_SRT_RESID && !ok && E) {                     // (uniform: so is the branch)
+    resid = __syncthreads_and(passes(N, true));
+    ok = resid;
+  }
   int m = N;
   if (ok != 0 && RJP_SRT_TRUNC != 0) {
     // every thread finds the same m from the same shared values
@@ -448,9 +556,9 @@ __global__ __launch_bounds__(kSrtCoefThreads) void srt_coef_kernel(const double*
     const double lim = kSrtTailFrac * kSrtMomTol * fmin;
     double tail = 0.0;
     while (m > 1 && (tail += __builtin_fabs(sW[m - 1])) <= lim) --m;
-    if (m < N && !__syncthreads_and(passes(m))) m = N;  // (m is uniform: so is the branch)
+    if (m < N && !__syncthreads_and(passes(m, resid != 0))) m = N;  // (m is uniform: so is the branch)
   }
-  if (i == 0) c.ok[q] = ok ? m : 0;
+  if (i == 0) c.ok[q] = ok ? (m | (resid ? kSrtResidFlag : 0)) : 0;
 }
 
 // The sorted scan with contracted bins: per group and jet, a bin of the support is contracted
@@ -471,23 +579,37 @@ __global__ __launch_bounds__(kSrtCoefThreads) void srt_coef_kernel(const double*
 // wave's chain of dependent loads is the kernel's time: the index rows, verdicts, W_0 and cum
 // steps of eight bins travel together, and a batch of N / 2 plane pairs runs on into the next
 // contracted bin (same-buffer A/B of these shapes: profiles/r08_cfg4_hybrid_ab.json).
+// A table-residual bin ("table-residual bins" above) is contracted in the same batches when the
+// packed state is attached and the longest lane run x 6 B > (N - 1) x 8 B; every maximal run of
+// such bins then streams weight x E~ of its cells from the packed state.  It counts as read.
 struct SrtMomDev {
   const double* mom;                           // [2 K (N - 1)][P]
   const double* W;                             // [2 K][N]
   const int* ok;                               // [2 K]: 0 = read the bin, else the coefficients to sum
-  // (contracted, read) (jet, bin) pairs of every group, [groups][2], or null: lane 0 of a group's
-  // wave stores its own pair, zeros included -- every slot of a scan is written by that scan,
-  // nothing is zeroed in front of it and no two waves share a word
+  // (contracted, read, residual) (jet, bin) counts of every group, [groups][3], or null: lane 0 of
+  // a group's wave stores its own three, zeros included -- every slot of a scan is written by that
+  // scan, nothing is zeroed in front of it and no two waves share a word.  A residual bin counts
+  // as read as well (its cells are read, from the packed state)
   unsigned long long* diag;
+  // table-residual bins: srt_err_kernel's table (null: none are taken) and the packed state
+  const float* E;
+  const rjp_d2* pts;
+  const rjp_u4* pw;
 };
+constexpr int kSrtDiag = 3;
 
 template <int U, int N>
 __global__ __launch_bounds__(kSrtBlock) __attribute__((amdgpu_waves_per_eu(4))) void ff_scan_hybrid_kernel(SrtDev s, SrtMomDev m,
                                                                    ChiTabDev t, double t_epoch,
                                                                    const double* __restrict__ tab,
                                                                    double* __restrict__ out) {
-  extern __shared__ __attribute__((aligned(16))) double s_chi[];       // [2][ni][10]
+  extern __shared__ __attribute__((aligned(16))) double s_chi[];       // [2][ni][10], then [2][ni][12] floats
   for (int i = threadIdx.x; i < 2 * t.ni * kChiStride; i += kSrtBlock) s_chi[i] = tab[i];
+  [[maybe_unused]] float* s_err = reinterpret_cast<float*>(s_chi + 2 * t.ni * kChiStride);
+#if RJP_SRT_RESID
+  if (m.E)
+    for (int i = threadIdx.x; i < 2 * t.ni * kErrStride; i += kSrtBlock) s_err[i] = m.E[i];
+#endif
   __syncthreads();
   const int lane = threadIdx.x & (RJP_WAVE - 1);
   const int64_t g = (int64_t)blockIdx.x * (kSrtBlock / RJP_WAVE) + threadIdx.x / RJP_WAVE;
@@ -495,9 +617,12 @@ __global__ __launch_bounds__(kSrtBlock) __attribute__((amdgpu_waves_per_eu(4))) 
   if (g * RJP_WAVE >= npix) return;                    // (whole waves)
   const int64_t p = g * RJP_WAVE + lane;
   const bool live = p < npix;
-  const rjp_d2* base = s.cells + s.rowbase[g] * RJP_WAVE + lane;
+  const int64_t rowbase = s.rowbase[g];
+  const rjp_d2* base = s.cells + rowbase * RJP_WAVE + lane;
   const double wmax = t.wmax;
   const int K = s.K;
+  unsigned n_res = 0;
+  double racc = 0.0;                                   // sum of weight x E~ over the residual bins' cells
   auto start_at = [&](int q) { return live ? s.start[(int64_t)q * npix + p] : 0; };
   auto cum_at = [&](int q) { return live ? s.cum[(int64_t)q * npix + p] : 0.0; };
   auto wave_max = [](int v) {
@@ -526,6 +651,7 @@ __global__ __launch_bounds__(kSrtBlock) __attribute__((amdgpu_waves_per_eu(4))) 
     // which bins of the support this group contracts, and the M_0 terms of those: eight bins'
     // index rows, verdicts and W_0 per round trip to memory
     unsigned cmask = 0;
+    unsigned rmask = 0;                                // of those, the table-residual bins
     unsigned long long cnt[3] = {0ull, 0ull, 0ull};    // coefficient counts, 5 bits per bin, 12 per word
     auto count_of = [&](int b) {
       return (int)(((b < 12 ? cnt[0] : b < 24 ? cnt[1] : cnt[2]) >> (5 * (b % 12))) & 31u);
@@ -551,9 +677,14 @@ __global__ __launch_bounds__(kSrtBlock) __attribute__((amdgpu_waves_per_eu(4))) 
       for (int u = 0; u < 8; ++u) {
         const int b = bb + u;
         if (b < b1) {
-          const unsigned mb = (unsigned)__builtin_amdgcn_readfirstlane(mo[u]);
-          if (mb && wm[u] * 16 > (N - 1) * 8) {
+          const unsigned mv = (unsigned)__builtin_amdgcn_readfirstlane(mo[u]);
+          const unsigned mb = mv & 0xffu;
+          // a residual bin pays when its packed cells (10 B) cost more than the planes on top of
+          // the 4 B per cell it then does not read: longest run x 6 B > (N - 1) x 8 B
+          const bool rb = RJP_SRT_RESID && (mv & (unsigned)kSrtResidFlag);
+          if (mb && (rb ? (m.E != nullptr && wm[u] * 6 > (N - 1) * 8) : wm[u] * 16 > (N - 1) * 8)) {
             cmask |= 1u << b;
+            if (rb) rmask |= 1u << b;
             acc = __builtin_fma(w0[u], cu[u + 1] - cu[u], acc);
           }
           const unsigned long long bits = (unsigned long long)mb << (5 * (b % 12));
@@ -563,9 +694,10 @@ __global__ __launch_bounds__(kSrtBlock) __attribute__((amdgpu_waves_per_eu(4))) 
         }
       }
     }
-    const int nc = __builtin_popcount(cmask);
+    const int nc = __builtin_popcount(cmask & ~rmask);
     n_con += nc;
     n_read += (b1 - b0) - nc;
+    n_res += __builtin_popcount(rmask);
 #if RJP_SRT_PAIR
     // the planes of the contracted bins, NP plane pairs per round trip, a batch running on into
     // the next contracted bin: with m - 1 = 0 .. 16 planes a bin fills a batch rarely
@@ -618,6 +750,69 @@ __global__ __launch_bounds__(kSrtBlock) __attribute__((amdgpu_waves_per_eu(4))) 
           for (int n = 0; n < N - 1; ++n)
             if (n < m1) sum = __builtin_fma(w[n + 1], v[n], sum);
           pacc.x += sum;
+        }
+#endif
+#if RJP_SRT_RESID
+        if ((rmask >> b) & 1u) {
+          // a maximal run of residual bins [b, e): weight x E~ of every cell, streamed from the
+          // packed state in blocks of 8 rows aligned to 8 -- four 16-byte pairs of launch times
+          // and one 16-byte unit of eight weights per lane, a lane loading only the units that
+          // meet its own run; a row outside the run gets weight zero by predicate, so nothing it
+          // holds can reach the sum (a NaN launch time lands in piece 0, as in the lookup)
+          int e = b + 1;
+#if RJP_SRT_PAIR
+          while (e < b1 && ((rmask >> e) & 1u)) ++e;
+#endif
+          const int rs = start_at(q0 + b), re = start_at(q0 + e);
+          int lo = rs < re ? rs : 0x7fffffff, hi = rs < re ? re : 0;
+#pragma unroll
+          for (int d = RJP_WAVE / 2; d > 0; d >>= 1) {
+            lo = min(lo, __shfl_xor(lo, d, RJP_WAVE));
+            hi = max(hi, __shfl_xor(hi, d, RJP_WAVE));
+          }
+          lo = __builtin_amdgcn_readfirstlane(lo) & ~7;
+          hi = __builtin_amdgcn_readfirstlane(hi);
+          const int64_t pb = srt_packed_row(rowbase, g);
+          const rjp_d2* pt = m.pts + (pb / 2) * RJP_WAVE + lane;
+          const rjp_u4* pq = m.pw + (pb / 8) * RJP_WAVE + lane;
+          constexpr int RB = RJP_SRT_RESID_BLOCKS;       // blocks of 8 rows in flight
+          for (int r = lo; r < hi; r += 8 * RB) {
+            rjp_d2 tt[RB][4];
+            rjp_u4 wq[RB];
+#pragma unroll
+            for (int k = 0; k < RB; ++k) {
+              const int rk = r + 8 * k;
+#pragma unroll
+              for (int u = 0; u < 4; ++u) {
+                tt[k][u] = rjp_d2{0.0, 0.0};
+                if (rk + 2 * u + 1 >= rs && rk + 2 * u < re)
+                  tt[k][u] = __builtin_nontemporal_load(pt + (int64_t)(rk / 2 + u) * RJP_WAVE);
+              }
+              wq[k] = rjp_u4{0u, 0u, 0u, 0u};
+              if (rk + 7 >= rs && rk < re)
+                wq[k] = __builtin_nontemporal_load(pq + (int64_t)(rk / 8) * RJP_WAVE);
+            }
+#pragma unroll
+            for (int k = 0; k < RB; ++k)
+#pragma unroll
+              for (int u = 0; u < 8; ++u) {
+                const int row = r + 8 * k + u;
+                const double tsu = (u & 1) ? tt[k][u / 2].y : tt[k][u / 2].x;
+                const unsigned wd = wq[k][u / 2];
+                const unsigned code = (u & 1) ? (wd >> 16) : (wd & 0xffffu);
+                const float wf = (row >= rs && row < re) ? __uint_as_float(code << 15) : 0.0f;
+                double w = (t_epoch - tsu - t.lo) * t.inv_h;
+                w = __builtin_fmin(__builtin_fmax(w, 0.0), wmax);
+                const double kf = __builtin_floor(w);
+                const double xi = __builtin_fma(2.0, w - kf, -1.0);
+                const rjp_f4* ep = reinterpret_cast<const rjp_f4*>(s_err + ((int)kf + koff) * kErrStride);
+                const rjp_f4 e0 = ep[0], e1 = ep[1];
+                const float e8 = ep[2].x;
+                racc = __builtin_fma((double)wf, (double)srt_err_eval(e0, e1, e8, (float)xi), racc);
+              }
+          }
+          b = e;
+          continue;
         }
 #endif
         ++b;
@@ -680,10 +875,12 @@ __global__ __launch_bounds__(kSrtBlock) __attribute__((amdgpu_waves_per_eu(4))) 
   }
 #if RJP_SRT_DIAG
   if (m.diag && lane == 0) {
-    m.diag[2 * g] = (unsigned long long)n_con;
-    m.diag[2 * g + 1] = (unsigned long long)n_read;
+    m.diag[kSrtDiag * g] = (unsigned long long)n_con;
+    m.diag[kSrtDiag * g + 1] = (unsigned long long)n_read;
+    m.diag[kSrtDiag * g + 2] = (unsigned long long)n_res;
   }
 #endif
+  total += racc;                                       // (+0.0 without residual bins)
 #if RJP_SRT_PAIR
   // both halves of the planes, then sightline l from the pair of lane l / 2 (all lanes are here)
   pacc.x += __shfl_xor(pacc.x, 32, RJP_WAVE);
@@ -952,6 +1149,7 @@ bool srt_plan(const rjp_fields* fl, const rjp_bursts* hb, double t_epoch, SrtPla
   }
   sp.share = all > 0 ? (double)read / (double)all : 0.0;
   sp.N = fl->d_srt_mom && srt_moment_order_ok(fl->srt_N) ? fl->srt_N : 0;
+  sp.packed = sp.N > 0 && fl->d_srt_pts && fl->d_srt_pw;
   return sp.share <= 0.9;
 }
 
@@ -982,8 +1180,10 @@ size_t chi_table_workspace_bytes(int64_t npix, int ny) {
 #endif
 constexpr size_t kRingTab = (size_t)2 * kChiMaxNI * kChiStride;           // doubles
 constexpr size_t kRingW = (size_t)2 * RJP_SRT_MAX_K * kSrtMaxN;           // doubles
+constexpr size_t kRingE = (size_t)2 * kChiMaxNI * kErrStride;              // floats
 constexpr size_t kRingSlotBytes =
-    ((kRingTab + kRingW) * sizeof(double) + 2 * RJP_SRT_MAX_K * sizeof(int) + 255) / 256 * 256;
+    ((kRingTab + kRingW) * sizeof(double) + kRingE * sizeof(float) +
+     2 * RJP_SRT_MAX_K * sizeof(int) + 255) / 256 * 256;
 
 void tab_ring_destroy(TabRing& r) {
   if (r.side) {
@@ -1005,7 +1205,8 @@ void tab_ring_create(TabRing& r) {
     TabRing::Slot& s = r.slot[i];
     s.tab = reinterpret_cast<double*>(static_cast<char*>(r.mem) + i * kRingSlotBytes);
     s.W = s.tab + kRingTab;
-    s.ok = reinterpret_cast<int*>(s.W + kRingW);
+    s.E = reinterpret_cast<float*>(s.W + kRingW);         // (16-byte aligned: read as float4)
+    s.ok = reinterpret_cast<int*>(s.E + kRingE);
     ok = hipEventCreateWithFlags(&s.ready, hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&s.uploaded, hipEventDisableTiming) == hipSuccess;
   }
@@ -1036,7 +1237,7 @@ static hipError_t chi_table_scan_on(const rjp_fields* fl, const ChiPlan& cp, con
                                     double t_epoch, int mode, double* sumA, double* em,
                                     double* tavg, double* ws, size_t work_bytes, int* d_guard,
                                     hipStream_t st, const SrtPlan* sp, TabLaunch& tl,
-                                    double* d_tab, double* d_W, int* d_ok);
+                                    double* d_tab, double* d_W, int* d_ok, float* d_E);
 
 hipError_t chi_table_scan(const rjp_fields* fl, const ChiPlan& cp, const double* d_stage,
                           double t_epoch, int mode, double* sumA, double* em, double* tavg,
@@ -1054,6 +1255,7 @@ hipError_t chi_table_scan(const rjp_fields* fl, const ChiPlan& cp, const double*
   double* d_tab = ws + (cp.wide ? 32 : 2) * npix;
   double* d_W = nullptr;
   int* d_ok = nullptr;
+  float* d_E = nullptr;
   hipStreamCaptureStatus cap = hipStreamCaptureStatusActive;
   bool ahead = RJP_TABLES_AHEAD && ring && ring->side && release_ev && cp.ni <= kChiMaxNI &&
                hipStreamIsCapturing(st, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone;
@@ -1079,9 +1281,10 @@ hipError_t chi_table_scan(const rjp_fields* fl, const ChiPlan& cp, const double*
     d_tab = s.tab;
     d_W = s.W;
     d_ok = s.ok;
+    d_E = s.E;
   }
   const hipError_t e = chi_table_scan_on(fl, cp, d_stage, t_epoch, mode, sumA, em, tavg, ws,
-                                         work_bytes, d_guard, st, sp, tl, d_tab, d_W, d_ok);
+                                         work_bytes, d_guard, st, sp, tl, d_tab, d_W, d_ok, d_E);
   // on every path: the slot's kernels may be in flight, and the event the caller records behind
   // this scan (a failed launch included) has to cover them
   const hipError_t rel = tl.join();
@@ -1097,7 +1300,7 @@ static hipError_t chi_table_scan_on(const rjp_fields* fl, const ChiPlan& cp, con
                                     double t_epoch, int mode, double* sumA, double* em,
                                     double* tavg, double* ws, size_t work_bytes, int* d_guard,
                                     hipStream_t st, const SrtPlan* sp, TabLaunch& tl,
-                                    double* d_tab, double* d_W, int* d_ok) {
+                                    double* d_tab, double* d_W, int* d_ok, float* d_E) {
   const int64_t npix = (int64_t)fl->nx * fl->nz;
   const int64_t nchunks = npix / 2;
   const size_t tab_doubles = (size_t)2 * cp.ni * kChiStride;
@@ -1138,7 +1341,8 @@ static hipError_t chi_table_scan_on(const rjp_fields* fl, const ChiPlan& cp, con
                           (const void*)ff_scan_hybrid_kernel<RJP_SRT_U, 20>,
                           (const void*)ff_scan_hybrid_kernel<RJP_SRT_U, 24>};
     for (const void* f : hyb) {
-      e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxShm);
+      e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              std::max(kMaxShm, (int)kSrtResidShm));
       if (e != hipSuccess) return e;
     }
     cp.attr_set = true;
@@ -1167,26 +1371,41 @@ static hipError_t chi_table_scan_on(const rjp_fields* fl, const ChiPlan& cp, con
     if (!d_W) {
       d_W = ws;
       d_ok = reinterpret_cast<int*>(ws + (size_t)2 * K * N);
+      d_E = reinterpret_cast<float*>(ws + (size_t)2 * RJP_SRT_MAX_K * kSrtMaxN + RJP_SRT_MAX_K);
     }
+    // table-residual bins: with the packed state attached, and only while the chi table and the
+    // error table together leave the CU two workgroups -- else what fails (b) is read as before
+    const size_t err_bytes = (size_t)2 * cp.ni * kErrStride * sizeof(float);
+    const bool resid = RJP_SRT_RESID && sp->packed && ((uintptr_t)fl->d_srt_pts % 16) == 0 &&
+                       ((uintptr_t)fl->d_srt_pw % 16) == 0 && shm + err_bytes <= kSrtResidShm;
+    if (resid) {
+      hipLaunchKernelGGL(srt_err_kernel, dim3((unsigned)((2 * cp.ni * 16 + 255) / 256)), dim3(256), 0,
+                         tl.ts, d_stage, cp.n[0], cp.n[1], t, (const double*)d_tab, d_E);
+      e = hipGetLastError();
+      if (e != hipSuccess) return e;
+    }
+    const float* dE = resid ? d_E : nullptr;
+    const size_t hshm = shm + (resid ? err_bytes : 0);
     const SrtCoefDev c{fl->ts_lo, fl->ts_hi > fl->ts_lo ? K / (fl->ts_hi - fl->ts_lo) : 1.0, K, N,
                        {sp->b0[0], sp->b0[1]}, {sp->b1[0], sp->b1[1]}, d_W, d_ok};
     hipLaunchKernelGGL(srt_coef_kernel, dim3((unsigned)(2 * K)), dim3(kSrtCoefThreads), 0, tl.ts,
-                       d_stage, cp.n[0], cp.n[1], t, t_epoch, (const double*)d_tab, c);
+                       d_stage, cp.n[0], cp.n[1], t, t_epoch, (const double*)d_tab, dE, c);
     e = hipGetLastError();
     if (e == hipSuccess) e = tl.join();
     if (e != hipSuccess) return e;
-    const SrtMomDev m{fl->d_srt_mom, d_W, d_ok, sp->diag};
+    const SrtMomDev m{fl->d_srt_mom, d_W, d_ok, sp->diag, dE, (const rjp_d2*)fl->d_srt_pts,
+                      (const rjp_u4*)fl->d_srt_pw};
     switch (N) {
       case 16:
-        hipLaunchKernelGGL((ff_scan_hybrid_kernel<RJP_SRT_U, 16>), sgrid, dim3(kSrtBlock), shm, st,
+        hipLaunchKernelGGL((ff_scan_hybrid_kernel<RJP_SRT_U, 16>), sgrid, dim3(kSrtBlock), hshm, st,
                            s, m, t, t_epoch, (const double*)d_tab, sumA);
         break;
       case 20:
-        hipLaunchKernelGGL((ff_scan_hybrid_kernel<RJP_SRT_U, 20>), sgrid, dim3(kSrtBlock), shm, st,
+        hipLaunchKernelGGL((ff_scan_hybrid_kernel<RJP_SRT_U, 20>), sgrid, dim3(kSrtBlock), hshm, st,
                            s, m, t, t_epoch, (const double*)d_tab, sumA);
         break;
       default:
-        hipLaunchKernelGGL((ff_scan_hybrid_kernel<RJP_SRT_U, 24>), sgrid, dim3(kSrtBlock), shm, st,
+        hipLaunchKernelGGL((ff_scan_hybrid_kernel<RJP_SRT_U, 24>), sgrid, dim3(kSrtBlock), hshm, st,
                            s, m, t, t_epoch, (const double*)d_tab, sumA);
         break;
     }

@@ -12,6 +12,8 @@
 #define RJP_NT_LOADS 1   /* the fields are streamed exactly once: non-temporal loads, +5 % on cfg4 (6.1 -> 6.4 TB/s) */
 #endif
 typedef double rjp_d2 __attribute__((ext_vector_type(2)));
+typedef unsigned rjp_u4 __attribute__((ext_vector_type(4)));
+typedef float rjp_f4 __attribute__((ext_vector_type(4)));
 typedef float rjp_f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void load_vec(const double* __restrict__ p, double (&out)[2]) {
 #if RJP_NT_LOADS

@@ -100,8 +100,11 @@ struct SrtPlan {
   double share = 0.0;             // the map's cells in those bins / all cells in the layout
   // Chebyshev moments of the layout attached (rjp_fields.d_srt_mom): their order N, else 0.  The
   // bins in the support whose chi^2 the degree-(N-1) interpolant matches are contracted from them
-  unsigned long long* diag = nullptr;   // (contracted, read) bin counters of the scan, a pair per group, or null
+  unsigned long long* diag = nullptr;   // (contracted, read, residual) bin counters of the scan, three per group, or null
   int N = 0;
+  // the packed state is attached (rjp_fields.d_srt_pts / d_srt_pw): bins that fail check (b) alone
+  // may be taken as table-residual bins (ff_scan_tab.hip)
+  bool packed = false;
 };
 // false: no layout attached, or too large a share of it would be read (the grid order is as fast)
 bool srt_plan(const rjp_fields* fl, const rjp_bursts* hb, double t_epoch, SrtPlan& sp);
@@ -123,6 +126,7 @@ struct TabRing {
     double* tab = nullptr;        // [2][kChiMaxNI][kChiStride]
     double* W = nullptr;          // [2 RJP_SRT_MAX_K][kSrtMaxN]
     int* ok = nullptr;            // [2 RJP_SRT_MAX_K]
+    float* E = nullptr;           // [2][kChiMaxNI][kErrStride]: the table's own error, per piece
     hipEvent_t ready = nullptr;
     hipEvent_t readers_done = nullptr;   // borrowed: the release_ev of the slot's last scan
     hipEvent_t uploaded = nullptr;   // caller's stream, behind a fresh upload of the burst table
@@ -219,6 +223,14 @@ size_t srt_moment_entries(int nx, int nz, int K, int N);
 hipError_t srt_moments_launch(const rjp_fields* fl, int K, int N, const int32_t* d_start,
                               const int64_t* d_rowbase, const void* d_cells, double* d_mom,
                               hipStream_t st);
+// the packed state of the layout (rjp_fields.d_srt_pts / d_srt_pw): rows of group g start at
+// srt_packed_row(d_srt_rowbase[g], g), a multiple of 8 that leaves every group its rows rounded
+// up to 8; srt_packed_rows(total, G) rows hold every group
+__host__ __device__ inline int64_t srt_packed_row(int64_t rowbase, int64_t g) { return ((rowbase + 7) & ~(int64_t)7) + 8 * g; }
+inline int64_t srt_packed_rows(int64_t total_rows, int64_t groups) { return srt_packed_row(total_rows, groups); }
+hipError_t srt_pack_launch(const rjp_fields* fl, int K, const int32_t* d_start,
+                           const int64_t* d_rowbase, const void* d_cells, void* d_pts, void* d_pw,
+                           int* d_flag, hipStream_t st);
 hipError_t field_range_launch(const void* d_field, int64_t n, int dtype, double* d_part,
                               hipStream_t st);
 hipError_t range_check_launch(const void* d_field, int64_t n, int dtype, double lo, double hi,

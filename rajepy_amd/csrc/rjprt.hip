@@ -58,9 +58,9 @@ struct rjp_ctx {
   int* guard = nullptr;
   unsigned long long* d_count = nullptr;      // device word of rjp_occupied_cells
   unsigned long long* d_srt_hist = nullptr;   // RJP_SRT_MAX_K * 2 counters of rjp_srt_count
-  // (contracted, read) bins of rjp_last_srt_bins: one pair per group of 64 sightlines, written
+  // (contracted, read, residual) bins of rjp_last_srt_bins / rjp_last_srt_resid: three words per group of 64 sightlines, written
   // by the group's wave with plain stores (ff_scan_hybrid_kernel); grown when a scan has more
-  // groups than it holds.  `srt_diag_groups`: the pairs the last such scan wrote.
+  // groups than it holds.  `srt_diag_groups`: the groups the last such scan wrote.
   unsigned long long* d_srt_diag = nullptr;
   int64_t srt_diag_cap = 0, srt_diag_groups = 0;
   struct RangeKey {
@@ -556,7 +556,7 @@ static int ff_scan_impl(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts
         ctx->d_srt_diag = nullptr;
         ctx->srt_diag_cap = 0;
         RJP_HIP(ctx, hipMalloc((void**)&ctx->d_srt_diag,
-                               (size_t)groups * 2 * sizeof(unsigned long long)));
+                               (size_t)groups * 3 * sizeof(unsigned long long)));
         ctx->srt_diag_cap = groups;
       }
       ctx->srt_diag_groups = groups;
@@ -645,12 +645,12 @@ int rjp_last_srt_bins(rjp_ctx* ctx, int64_t* contracted, int64_t* read) {
   if (!contracted || !read) return fail(ctx, RJP_ERR_ARG, "rjp_last_srt_bins: NULL output");
   *contracted = *read = 0;
   if (!ctx->last_srt_mom) return RJP_OK;
-  std::vector<unsigned long long> h((size_t)ctx->srt_diag_groups * 2);
+  std::vector<unsigned long long> h((size_t)ctx->srt_diag_groups * 3);
   RJP_HIP(ctx, hipDeviceSynchronize());
   RJP_HIP(ctx, hipMemcpy(h.data(), ctx->d_srt_diag, h.size() * sizeof(unsigned long long),
                          hipMemcpyDeviceToHost));
   int64_t con = 0, rd = 0;
-  for (size_t g = 0; g < h.size(); g += 2) {
+  for (size_t g = 0; g < h.size(); g += 3) {
     con += (int64_t)h[g];
     rd += (int64_t)h[g + 1];
   }
@@ -770,6 +770,44 @@ int rjp_srt_moments(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, int32_t N
   RJP_HIP(ctx, rjp::srt_moments_launch(fields, K, N, d_start, d_rowbase, d_cells, d_mom,
                                        (hipStream_t)stream));
   return RJP_OK;
+}
+
+size_t rjp_srt_packed_rows(int32_t nx, int32_t nz, int64_t total_rows) {
+  if (nx <= 0 || nz <= 0 || total_rows < 0) return 0;
+  return (size_t)rjp::srt_packed_rows(total_rows, ((int64_t)nx * nz + 63) / 64);
+}
+
+int64_t rjp_srt_pack(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, const int32_t* d_start,
+                     const int64_t* d_rowbase, const void* d_cells, void* d_pts, void* d_pw,
+                     void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = check_srt(ctx, fields, K)) return r;
+  if (!d_start || !d_rowbase || !d_cells || !d_pts || !d_pw)
+    return fail(ctx, RJP_ERR_ARG, "rjp_srt_pack: NULL argument");
+  if (((uintptr_t)d_pts % 16) != 0 || ((uintptr_t)d_pw % 16) != 0)
+    return fail(ctx, RJP_ERR_ARG, "rjp_srt_pack: d_pts and d_pw must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  // (the out-of-range flag: the context's device word, as rjp_occupied_cells uses it)
+  if (!ctx->d_count) RJP_HIP(ctx, hipMalloc((void**)&ctx->d_count, sizeof(unsigned long long)));
+  RJP_HIP(ctx, hipMemsetAsync(ctx->d_count, 0, sizeof(unsigned long long), st));
+  RJP_HIP(ctx, rjp::srt_pack_launch(fields, K, d_start, d_rowbase, d_cells, d_pts, d_pw,
+                                    reinterpret_cast<int*>(ctx->d_count), st));
+  unsigned long long flag = 0;
+  RJP_HIP(ctx, hipMemcpyAsync(&flag, ctx->d_count, sizeof(flag), hipMemcpyDeviceToHost, st));
+  RJP_HIP(ctx, hipStreamSynchronize(st));
+  return flag ? 2 : 1;
+}
+
+int64_t rjp_last_srt_resid(rjp_ctx* ctx) {
+  if (int r = bind(ctx)) return r;
+  if (!ctx->last_srt_mom) return 0;
+  std::vector<unsigned long long> h((size_t)ctx->srt_diag_groups * 3);
+  RJP_HIP(ctx, hipDeviceSynchronize());
+  RJP_HIP(ctx, hipMemcpy(h.data(), ctx->d_srt_diag, h.size() * sizeof(unsigned long long),
+                         hipMemcpyDeviceToHost));
+  int64_t n = 0;
+  for (size_t g = 2; g < h.size(); g += 3) n += (int64_t)h[g];
+  return n;
 }
 
 int rjp_time_ff_scan(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,

@@ -212,6 +212,11 @@ class RTEngine:
         # them when they do not fit.
         self.use_srt_moments = True
         self.srt_N = 20                # K1 at cfg4, 1 yr: 0.68 / 0.57 / 0.59 ms at N = 16 / 20 / 24
+        # ... and with its packed state (rjp_srt_pack: launch times + 16-bit weights, 10 bytes per
+        # cell), from which the bins that fail only against the table's own error are taken as
+        # table-residual bins; False: those bins are read cell by cell (A/B runs, tests).  Counts
+        # in the srt_min_free rule like the moments.
+        self.use_srt_packed = True
         # keep the launch-time moment maps of a model that is swept repeatedly (2.7 GB at
         # 512 x 512 sightlines): from the second long sweep on only the contraction runs
         self.cache_moments = True
@@ -499,6 +504,10 @@ class RTEngine:
             return None
         if free - need - n_mom * 8 < self.srt_min_free * hbm:
             n_mom = 0                           # the layout fits, its moments do not
+        n_prow = (self.lib.rjp_srt_packed_rows(nx, nz, total.value)
+                  if n_mom and self.use_srt_packed else 0)
+        if free - need - n_mom * 8 - n_prow * 64 * 10 < self.srt_min_free * hbm:
+            n_prow = 0                          # ... or its packed state does not
         cells = torch.empty(max(1, total.value) * 64 * 2, dtype=torch.float64, device=self.device)
         cum = torch.empty(n_idx, dtype=torch.float64, device=self.device)
         aux = torch.empty(3 * fields.npix, dtype=torch.float64, device=self.device)
@@ -514,6 +523,23 @@ class RTEngine:
             self._call("rjp_srt_moments", C.byref(fs), int(K), int(self.srt_N), start.data_ptr(),
                        rowbase.data_ptr(), cells.data_ptr(), mom.data_ptr())
             ev_m[1].record()
+        packed = None
+        if n_prow:
+            # (one allocation of 10 bytes per cell: a freed block the size of a0 would be taken
+            # for the next a0 in place of a0's own)
+            buf = torch.empty(n_prow * 64 * 10, dtype=torch.uint8, device=self.device)
+            pts = buf[:n_prow * 64 * 8].view(torch.float64)
+            pw = buf[n_prow * 64 * 8:].view(torch.int16)
+            ev_p = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev_p[0].record()
+            fits = self._call_tiles("rjp_srt_pack", C.byref(fs), int(K), start.data_ptr(),
+                                    rowbase.data_ptr(), cells.data_ptr(), pts.data_ptr(),
+                                    pw.data_ptr())
+            ev_p[1].record()
+            torch.cuda.synchronize(self.device)
+            if fits == 1:                       # (2: a weight outside the 16-bit format's range)
+                packed = {"pts": pts, "pw": pw, "rows": int(n_prow), "bytes": n_prow * 64 * 10,
+                          "build_ms": ev_p[0].elapsed_time(ev_p[1]), "version": cells._version}
         torch.cuda.synchronize(self.device)
         if mom is not None:
             mom_ms = ev_m[0].elapsed_time(ev_m[1])
@@ -523,7 +549,7 @@ class RTEngine:
                       "build_with_allocation_ms": ev[0].elapsed_time(ev[3]),
                       "bytes": need, "key": self._srt_key(fields, fs),
                       "mom": mom, "N": int(self.srt_N) if mom is not None else 0,
-                      "mom_build_ms": mom_ms, "mom_bytes": n_mom * 8}
+                      "mom_build_ms": mom_ms, "mom_bytes": n_mom * 8, "packed": packed}
         return fields.srt
 
     def _attach_sorted(self, fields):
@@ -716,6 +742,12 @@ class RTEngine:
             if self.use_srt_moments and srt.get("mom") is not None:
                 fs.d_srt_mom = srt["mom"].data_ptr()
                 fs.srt_N = srt["N"]
+                packed = srt.get("packed")
+                # (the packed state restates the cells: cells edited in place detach it)
+                if (self.use_srt_packed and packed is not None and
+                        packed["version"] == srt["cells"]._version):
+                    fs.d_srt_pts = packed["pts"].data_ptr()
+                    fs.d_srt_pw = packed["pw"].data_ptr()
         if not self.use_moments and n_epochs != 1:
             fs.ts_lo = fs.ts_hi = 0.0
         elif self.force_moments:
@@ -898,6 +930,14 @@ class RTEngine:
         self._check(self.lib.rjp_last_srt_bins(self.ctx, C.byref(c), C.byref(r)), self.ctx,
                    "rjp_last_srt_bins")
         return int(c.value), int(r.value)
+
+    def last_srt_resid(self):
+        """The table-residual (group, jet, bin) triples of the last scan, a subset of
+        `last_srt_bins()`'s read ones (rjp_last_srt_resid; synchronises the device)."""
+        n = int(self.lib.rjp_last_srt_resid(self.ctx))
+        if n < 0:
+            self._check(n, self.ctx, "rjp_last_srt_resid")
+        return n
 
     def last_table_build_ms(self):
         """Host wall time of the last coefficient-table build (a new bursts / epochs request)."""

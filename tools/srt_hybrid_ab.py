@@ -48,6 +48,8 @@ def main():
         name, path = spec.split("=", 1)
         lib = C.CDLL(os.path.abspath(path))
         for fn_name, (res, argt) in _lib.SIGNATURES.items():
+            if not hasattr(lib, fn_name):       # (an older build: an entry point added since)
+                continue
             fn = getattr(lib, fn_name)
             fn.restype, fn.argtypes = res, argt
         assert lib.rjp_version() == _lib.RJP_VERSION
@@ -84,6 +86,8 @@ def main():
             assert lib.rjp_last_srt_bins(ctx, C.byref(c), C.byref(r)) == 0
             row[name] = {"ms": [], "layout": int(lib.rjp_last_scan_layout(ctx)),
                          "bins_contracted_read": [int(c.value), int(r.value)]}
+            if hasattr(lib, "rjp_last_srt_resid"):
+                row[name]["bins_residual"] = int(lib.rjp_last_srt_resid(ctx))
         for _ in range(args.rounds):
             for name, lib, ctx in builds:
                 row[name]["ms"].append(run(name, lib, ctx, args.reps))

@@ -55,6 +55,8 @@ def main():
         name, path = spec.split("=", 1)
         lib = C.CDLL(os.path.abspath(path))
         for fn_name, (res, argt) in _lib.SIGNATURES.items():
+            if not hasattr(lib, fn_name):       # (an older build: an entry point added since)
+                continue
             fn = getattr(lib, fn_name)
             fn.restype, fn.argtypes = res, argt
         assert lib.rjp_version() == _lib.RJP_VERSION
@@ -108,6 +110,8 @@ def main():
             for nm, k, t in zip(names, kept, out):
                 row[name][nm + "_bit_equal"] = bool(torch.equal(k.view(torch.int64),
                                                                 t.view(torch.int64)))
+                ok = torch.isfinite(k) & (k != 0)
+                row[name][nm + "_max_rel"] = float(((t - k).abs()[ok] / k.abs()[ok]).max().item())
         res["bits"]["%.1f_yr" % years] = row
         print(json.dumps({"%.1f_yr" % years: row}), flush=True)
     # ---- timing at 1.0 yr, the builds alternating -----------------------------------------------
