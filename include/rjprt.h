@@ -907,6 +907,64 @@ int64_t rjp_msclean(rjp_ctx* ctx, double* d_res, int32_t n_maps, int32_t n_s, in
                     double* d_cflux, int32_t* d_ncomp, double* d_model, double* d_peak,
                     void* d_work, size_t work_bytes, void* stream);
 
+/* ---- K18: the visibilities of a list of clean components -- the forward step of a major cycle -------
+ * CASA tclean alternates minor cycles in the image plane with major cycles that recompute the residual
+ * from the visibilities; the reference's Tclean task carries the controls (cycleniter, cyclefactor,
+ * minpsffraction, maxpsffraction: casa/tasks.py:259-262).  The forward step of a major cycle is the
+ * model's visibilities.  From a component list they cost n_comp x n_vis phasors, where rjp_vis on the
+ * dense model image costs nx nz x n_vis multiply-adds:
+ *   out[m,k] = in[m,k] + sign sum_s G[m,s,k] sum_{c < ncomp[m], cscale[m,c] = s}
+ *              f_c exp(-2 pi i (a (ix_c - (nx-1)/2) + b (iz_c - (nz-1)/2)))
+ *              a = h_su[m] d_u[k],  b = h_sv[m] d_v[k],  p_c = ix_c nz + iz_c
+ *   d_cpix, d_cflux [n_maps][comp_stride], d_ncomp [n_maps]   as rjp_clean / rjp_msclean write them,
+ *                            rows comp_stride apart (d_ncomp[m] is clamped into [0, comp_stride])
+ *   d_cscale [n_maps][comp_stride]   (optional) the scale of each component; NULL = all of scale 0
+ *   n_s                      the number of scales;  nx, nz the grid the pixels index
+ *   h_su, h_sv [n_maps]      HOST, d_u, d_v [n_vis]: as rjp_vis
+ *   d_gvis [n_maps][n_s][n_vis][2]   (optional) G, the transform of each scale's kernel at each
+ *                            visibility: rjp_vis of the kernel images, zero-padded and centred on one
+ *                            odd side.  NULL = G = 1, the Hogbom case, and needs n_s = 1.  The entry
+ *                            point is scale-agnostic, like rjp_msclean
+ *   d_in [n_maps][n_vis][2]  (optional) NULL = 0;  d_out [n_maps][n_vis][2] may be d_in (in place)
+ *   sign                     +1 or -1, applied to the flux (exact): -1 forms V - model
+ * Every phase is ONE double product per factor, a (ix - (nx-1)/2) and b (iz - (nz-1)/2), reduced and
+ * evaluated by the library's sine / cosine of an argument in turns, exactly as rjp_vis forms its
+ * phasors (its ARGUMENT RANGE holds here too); no recurrence, no float.  The sums run in a fixed
+ * order without atomics -- per (map, visibility): the scales ascending; inside a scale four slices
+ * of the list, slice w = the components c with (c mod 256) / 64 = w, each in list order, one fma
+ * per term and part; G multiplies each slice's sum of a scale once (two fmas per part); the four
+ * slices are added in slice order and `in` last -- so a repeated call gives the same bits.
+ * A component adds nothing if its flux is not finite, its pixel lies outside [0, nx nz) or its scale
+ * outside [0, n_s).  A non-finite d_u[k] or d_v[k] makes visibility k NaN in every map and touches no
+ * other visibility.  A non-finite in[m,k] stays non-finite (it is a flag: rjp_vis_adjoint skips it).
+ * A map with ncomp = 0 copies `in` bit for bit, -0.0 included.  One launch, 64 visibilities of one
+ * map per workgroup, no workspace.
+ * RETURNS the number of workgroups enqueued, > 0 -- n_maps x ceil(n_vis / 64) -- or a negative
+ * RJP_ERR_*; nothing is enqueued or touched on a refusal: RJP_ERR_ARG for a NULL ctx, d_cpix, d_cflux,
+ * d_ncomp, h_su, h_sv, d_u, d_v or d_out; n_maps, comp_stride, n_s, nx, nz or n_vis < 1; a sign
+ * other than +1 / -1; a NULL d_gvis with n_s != 1; a non-finite h_su / h_sv; nx nz > 2^31 - 1; more
+ * than 2^31 - 1 workgroups.
+ *
+ * rjp_components_image: the delta model of the same list, one plane per scale,
+ *   out[m][s][q] = sum_{c < ncomp[m]: p_c = q, cscale[m,c] = s} f_c      in list order, from +0.0
+ * -- rjp_restore with a delta beam; d_out [n_maps][n_s][nx nz] is overwritten.  The component rules
+ * are those above.  The model image is thereby a function of the list alone, without atomics, and
+ * equals bit for bit what rjp_clean and rjp_msclean add into a zeroed d_model.
+ * RETURNS the number of workgroups enqueued, > 0 -- n_maps x n_s x ceil(nx nz / 256) -- or a negative
+ * RJP_ERR_*; nothing is enqueued or touched on a refusal: RJP_ERR_ARG for a NULL ctx, d_cpix, d_cflux,
+ * d_ncomp or d_out; n_maps, comp_stride, n_s, nx or nz < 1; nx nz > 2^31 - 1; more than 2^31 - 1
+ * workgroups. */
+int64_t rjp_vis_components(rjp_ctx* ctx, const int32_t* d_cpix, const int32_t* d_cscale,
+                           const double* d_cflux, const int32_t* d_ncomp, int32_t n_maps,
+                           int32_t comp_stride, int32_t n_s, int32_t nx, int32_t nz,
+                           const double* h_su, const double* h_sv, const double* d_u,
+                           const double* d_v, int32_t n_vis, const double* d_gvis,
+                           const double* d_in, int32_t sign, double* d_out, void* stream);
+int64_t rjp_components_image(rjp_ctx* ctx, const int32_t* d_cpix, const int32_t* d_cscale,
+                             const double* d_cflux, const int32_t* d_ncomp, int32_t n_maps,
+                             int32_t comp_stride, int32_t n_s, int32_t nx, int32_t nz,
+                             double* d_out, void* stream);
+
 /* ---- K14: Gaussian fits of a stack of images (imfit) ----------------------------------------------
  * The reference measures its synthetic images outside itself: CASA imfit on the restored image
  * (classes.py:2790-2840).  This entry point fits one elliptical Gaussian per map by

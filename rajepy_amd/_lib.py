@@ -166,6 +166,11 @@ SIGNATURES = {
     "rjp_msclean": (C.c_int64, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32,
                                 C.c_int32, C.c_int32, _DP, _P, _DP, C.c_double, C.c_int32, _P, _P,
                                 _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "rjp_vis_components": (C.c_int64, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_int32, _DP, _DP, _P, _P, C.c_int32, _P, _P,
+                                       C.c_int32, _P, _P]),
+    "rjp_components_image": (C.c_int64, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_int32, _P, _P]),
     "rjp_gaussfit_workspace": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rjp_gaussfit": (C.c_int64, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P,
                                  _P, C.c_double, C.c_double, C.c_int32, _P, _P, _P, _P, _P, _P, _P,

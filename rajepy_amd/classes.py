@@ -1150,7 +1150,8 @@ class JetModel:
     def clean_image_ff(self, u_m, v_m, freq, weights=None, shape=None, cell_as=None, formal=False,
                        mfs=False, niter=500, gain=0.1, threshold_jy=0.0, mask=None, beam=None,
                        psf_shape=None, imfit=None, weighting=None, robust=0.5, scales=None,
-                       scale_bias=None):
+                       scale_bias=None, major_cycles=0, cyclefactor=1.5, cycleniter=None,
+                       min_psf_fraction=0.05, max_psf_fraction=0.8):
         """CLEANed, restored images [Jy / clean beam] of the `flux_ff` maps as an array with the
         baselines (`u_m`, `v_m`) in metres sees them: `dirty_image_ff` and `dirty_beam` (same
         arguments, kept on the device), Hogbom's CLEAN of every image with its own beam
@@ -1187,22 +1188,42 @@ class JetModel:
         scales' delta models convolved with their kernels, `residual` the raw (delta-scale)
         residual, `peak_residual` its masked max, `threshold_jy` bounds the score, and components
         lie at least the largest kernel's half width from the border (ValueError if the mask
-        leaves no such pixel).  The kernels carry no prolate-spheroidal taper: not CASA's bits."""
+        leaves no such pixel).  The kernels carry no prolate-spheroidal taper: not CASA's bits.
+        `major_cycles`: 0 = minor cycles only, as above -- the residual is then the one the minor
+        cycles kept in the image plane, the data's only when `psf_shape` is the full window.
+        N >= 1 = at most N minor runs, and after every one the residual is recomputed from the
+        visibilities: V minus the visibilities of the whole component list (K18:
+        `RTEngine.vis_components`, rjp_vis_components), imaged like the dirty image -- tclean's
+        major cycles (the reference's Tclean task carries the controls, casa/tasks.py:259-262).
+        Every run but the last stops at max(threshold_jy, clip(`cyclefactor` x sidelobe,
+        `min_psf_fraction`, `max_psf_fraction`) x the run's peak residual), the last at
+        `threshold_jy`; `cycleniter` (None = no limit) bounds the iterations of one run, `niter`
+        the whole list.  sidelobe = the largest |dirty beam| in the `psf_shape` window outside
+        twice the clean beam's half-power ellipse: this project's definition, not CASA's.
+        `residual`, `model`, `image` and `peak_residual` are then functions of the final list and
+        the data whatever the window, and `CleanResult.major` holds per map `runs` (dicts `start`,
+        `n`, `peak`, `threshold`), `sidelobe` and `vis_residual` (complex [K]; [F K] with `mfs`)."""
         im, *vis = self._model_vis(u_m, v_m, freq, weighting, formal=formal)
         return im._clean_images(*vis, weights, shape, cell_as, mfs, niter, gain, threshold_jy, mask,
                                 beam, psf_shape, imfit, weighting=weighting, robust=robust,
-                                scales=scales, scale_bias=scale_bias)
+                                scales=scales, scale_bias=scale_bias, major_cycles=major_cycles, cyclefactor=cyclefactor,
+                                cycleniter=cycleniter, min_psf_fraction=min_psf_fraction,
+                                max_psf_fraction=max_psf_fraction)
 
     def clean_image_rrl(self, rrl, u_m, v_m, freq, weights=None, shape=None, cell_as=None,
                         contsub=True, formal=False, mfs=False, niter=500, gain=0.1,
                         threshold_jy=0.0, mask=None, beam=None, psf_shape=None, imfit=None,
-                        weighting=None, robust=0.5, scales=None, scale_bias=None):
+                        weighting=None, robust=0.5, scales=None, scale_bias=None,
+                        major_cycles=0, cyclefactor=1.5, cycleniter=None,
+                        min_psf_fraction=0.05, max_psf_fraction=0.8):
         """CLEANed, restored images of the `flux_rrl` maps (same arguments) -> `CleanResult`; see
         `clean_image_ff`."""
         im, *vis = self._model_vis(u_m, v_m, freq, weighting, rrl=rrl, contsub=contsub, formal=formal)
         return im._clean_images(*vis, weights, shape, cell_as, mfs, niter, gain, threshold_jy, mask,
                                 beam, psf_shape, imfit, weighting=weighting, robust=robust,
-                                scales=scales, scale_bias=scale_bias)
+                                scales=scales, scale_bias=scale_bias, major_cycles=major_cycles, cyclefactor=cyclefactor,
+                                cycleniter=cycleniter, min_psf_fraction=min_psf_fraction,
+                                max_psf_fraction=max_psf_fraction)
 
     # ------------------------------------------------------------------ synthetic observations ----
     def uv_tracks(self, antennalist, t_obs_s, t_int_s, min_el_deg=None, hourangle_h=0.):
@@ -1229,7 +1250,8 @@ class JetModel:
                    sigma_jy=None, sefd_jy=None, chanwidth_hz=None, seed=0, nsigma=0.,
                    weights=None, shape=None, cell_as=None, formal=False, mfs=False, niter=500,
                    gain=0.1, threshold_jy=0.0, mask=None, beam=None, psf_shape=None, imfit=None,
-                   weighting=None, robust=0.5, scales=None, scale_bias=None):
+                   weighting=None, robust=0.5, scales=None, scale_bias=None, major_cycles=0,
+                   cyclefactor=1.5, cycleniter=None, min_psf_fraction=0.05, max_psf_fraction=0.8):
         """A synthetic observation of the `flux_ff` maps, start to end on the device -- the
         reference's simobserve -> tclean -> imfit chain (classes.py:2490-2850) -> `Observation`:
         `tracks` (`uv_tracks` of `antennalist`, `t_obs_s`, `t_int_s`, `min_el_deg`,
@@ -1251,21 +1273,24 @@ class JetModel:
         return self._observe(dict(formal=formal), antennalist, freq, t_obs_s, t_int_s, min_el_deg,
                              hourangle_h, sigma_jy, sefd_jy, chanwidth_hz, seed, nsigma, weights,
                              shape, cell_as, mfs, niter, gain, threshold_jy, mask, beam, psf_shape,
-                             imfit, weighting, robust, scales, scale_bias)
+                             imfit, weighting, robust, scales, scale_bias, major_cycles,
+                             cyclefactor, cycleniter, min_psf_fraction, max_psf_fraction)
 
     def observe_rrl(self, rrl, antennalist, freq, t_obs_s, t_int_s, min_el_deg=None,
                     hourangle_h=0., sigma_jy=None, sefd_jy=None, chanwidth_hz=None, seed=0,
                     nsigma=0., weights=None, shape=None, cell_as=None, contsub=True, formal=False,
                     mfs=False, niter=500, gain=0.1, threshold_jy=0.0, mask=None, beam=None,
                     psf_shape=None, imfit=None, weighting=None, robust=0.5, scales=None,
-                    scale_bias=None):
+                    scale_bias=None, major_cycles=0, cyclefactor=1.5, cycleniter=None,
+                    min_psf_fraction=0.05, max_psf_fraction=0.8):
         """A synthetic observation of the `flux_rrl` maps -> `Observation`; see `observe_ff`."""
         _weighting_mode(weighting)            # (refuses an unknown scheme before any work)
         return self._observe(dict(rrl=rrl, contsub=contsub, formal=formal), antennalist, freq,
                              t_obs_s, t_int_s, min_el_deg, hourangle_h, sigma_jy, sefd_jy,
                              chanwidth_hz, seed, nsigma, weights, shape, cell_as, mfs, niter, gain,
                              threshold_jy, mask, beam, psf_shape, imfit, weighting, robust, scales,
-                             scale_bias)
+                             scale_bias, major_cycles, cyclefactor, cycleniter, min_psf_fraction,
+                             max_psf_fraction)
 
     # ------------------------------------------------------------------ imfit ----
     def imfit(self, images, beam, cell_as=None, box=None, theta0=None, n_iter=60, rms=None):

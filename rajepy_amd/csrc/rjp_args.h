@@ -220,6 +220,48 @@ inline int check_msclean(const double* d_res, int n_maps, int n_s, int nx, int n
   return RJP_OK;
 }
 
+// What rjp_vis_components takes, in the order it refuses: NULL pointers, sizes below 1, the sign, a
+// missing d_gvis with more than one scale, a non-finite scale, the image size, the workgroup count
+// (64 visibilities each).  (`d_cscale`, `d_gvis` and `d_in` may be NULL.)
+inline int check_vis_components(const int32_t* d_cpix, const double* d_cflux,
+                                const int32_t* d_ncomp, int n_maps, int comp_stride, int n_s, int nx,
+                                int nz, const double* h_su, const double* h_sv, const double* d_u,
+                                const double* d_v, int n_vis, const double* d_gvis, int sign,
+                                const double* d_out, std::string& err) {
+  if (!d_cpix || !d_cflux || !d_ncomp || !h_su || !h_sv || !d_u || !d_v || !d_out)
+    return refuse(err, "rjp_vis_components: NULL components, scales, baselines or output");
+  if (n_maps < 1 || comp_stride < 1 || n_s < 1 || nx < 1 || nz < 1 || n_vis < 1)
+    return refuse(err, "rjp_vis_components: n_maps, comp_stride, n_s, nx, nz and n_vis must be "
+                       "positive");
+  if (sign != 1 && sign != -1) return refuse(err, "rjp_vis_components: sign must be +1 or -1");
+  if (!d_gvis && n_s != 1)
+    return refuse(err, "rjp_vis_components: a NULL d_gvis (G = 1) needs n_s = 1");
+  for (int m = 0; m < n_maps; ++m)
+    if (!std::isfinite(h_su[m]) || !std::isfinite(h_sv[m]))
+      return refuse(err, "rjp_vis_components: non-finite h_su / h_sv");
+  if ((int64_t)nx * nz > (int64_t)INT32_MAX)
+    return refuse(err, "rjp_vis_components: nx * nz exceeds 2^31 - 1");
+  if (((int64_t)n_vis + 63) / 64 > (int64_t)INT32_MAX / n_maps)
+    return refuse(err, "rjp_vis_components: more than 2^31 - 1 workgroups");
+  return RJP_OK;
+}
+
+// What rjp_components_image takes, in the order it refuses: NULL pointers, sizes below 1, the image
+// size, the workgroup count (256 pixels of one plane each).  (`d_cscale` may be NULL.)
+inline int check_components_image(const int32_t* d_cpix, const double* d_cflux,
+                                  const int32_t* d_ncomp, int n_maps, int comp_stride, int n_s,
+                                  int nx, int nz, const double* d_out, std::string& err) {
+  if (!d_cpix || !d_cflux || !d_ncomp || !d_out)
+    return refuse(err, "rjp_components_image: NULL components or output");
+  if (n_maps < 1 || comp_stride < 1 || n_s < 1 || nx < 1 || nz < 1)
+    return refuse(err, "rjp_components_image: n_maps, comp_stride, n_s, nx and nz must be positive");
+  if ((int64_t)nx * nz > (int64_t)INT32_MAX)
+    return refuse(err, "rjp_components_image: nx * nz exceeds 2^31 - 1");
+  if ((((int64_t)nx * nz + 255) / 256) * n_s > (int64_t)INT32_MAX / n_maps)
+    return refuse(err, "rjp_components_image: more than 2^31 - 1 workgroups");
+  return RJP_OK;
+}
+
 // What rjp_restore takes, in the order it refuses: NULL pointers, sizes below 1, the image size, a
 // beam whose quadratic form is not positive definite (or not finite).  (`d_add` may be NULL.)
 inline int check_restore(const int32_t* d_cpix, const double* d_cflux, const int32_t* d_ncomp,

@@ -339,6 +339,21 @@ hipError_t msclean_launch(double* res, int n_maps, int n_s, int nx, int nz, cons
                           int32_t* cscale, double* cflux, int32_t* ncomp, double* model,
                           double* peak, void* work, hipStream_t st);
 
+// ---- vis_components.hip: visibilities (K18) and the delta model image of a component list ---------
+int64_t vis_components_workgroups(int n_maps, int n_vis);            // n_maps x ceil(n_vis / 64)
+int64_t components_image_workgroups(int n_maps, int n_s, int nx, int nz);
+// d_su / d_sv[n_maps]: device copies of the scales; `cscale`, `gvis`, `in` may be nullptr; `out` may
+// be `in`; one launch
+hipError_t vis_components_launch(const int32_t* cpix, const int32_t* cscale, const double* cflux,
+                                 const int32_t* ncomp, int n_maps, int comp_stride, int n_s, int nx,
+                                 int nz, const double* d_su, const double* d_sv, const double* u,
+                                 const double* v, int n_vis, const double* gvis, const double* in,
+                                 int sign, double* out, hipStream_t st);
+// `cscale` may be nullptr; one launch
+hipError_t components_image_launch(const int32_t* cpix, const int32_t* cscale, const double* cflux,
+                                   const int32_t* ncomp, int n_maps, int comp_stride, int n_s,
+                                   int nx, int nz, double* out, hipStream_t st);
+
 // ---- imfit.hip: Levenberg-Marquardt fits of one elliptical Gaussian per map (K14) ----------------
 struct GaussfitTiling {
   int64_t tiles;                // of 1024 consecutive pixels of the box, per map

@@ -1251,6 +1251,48 @@ int64_t rjp_msclean(rjp_ctx* ctx, double* d_res, int32_t n_maps, int32_t n_s, in
   return r ? r : t.workgroups;
 }
 
+int64_t rjp_vis_components(rjp_ctx* ctx, const int32_t* d_cpix, const int32_t* d_cscale,
+                           const double* d_cflux, const int32_t* d_ncomp, int32_t n_maps,
+                           int32_t comp_stride, int32_t n_s, int32_t nx, int32_t nz,
+                           const double* h_su, const double* h_sv, const double* d_u,
+                           const double* d_v, int32_t n_vis, const double* d_gvis,
+                           const double* d_in, int32_t sign, double* d_out, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_vis_components(d_cpix, d_cflux, d_ncomp, n_maps, comp_stride, n_s, nx,
+                                              nz, h_su, h_sv, d_u, d_v, n_vis, d_gvis, sign, d_out,
+                                              m);
+      }))
+    return r;
+  hipStream_t st = (hipStream_t)stream;
+  const int r = staged(ctx, st, "vis_components_launch", nullptr,
+                       {{h_su, (size_t)n_maps}, {h_sv, (size_t)n_maps}},
+                       [&](double* const* d, const double*) {
+                         return rjp::vis_components_launch(d_cpix, d_cscale, d_cflux, d_ncomp,
+                                                           n_maps, comp_stride, n_s, nx, nz, d[0],
+                                                           d[1], d_u, d_v, n_vis, d_gvis, d_in, sign,
+                                                           d_out, st);
+                       });
+  return r ? r : rjp::vis_components_workgroups(n_maps, n_vis);
+}
+
+int64_t rjp_components_image(rjp_ctx* ctx, const int32_t* d_cpix, const int32_t* d_cscale,
+                             const double* d_cflux, const int32_t* d_ncomp, int32_t n_maps,
+                             int32_t comp_stride, int32_t n_s, int32_t nx, int32_t nz,
+                             double* d_out, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_components_image(d_cpix, d_cflux, d_ncomp, n_maps, comp_stride, n_s,
+                                                nx, nz, d_out, m);
+      }))
+    return r;
+  const hipError_t e = rjp::components_image_launch(d_cpix, d_cscale, d_cflux, d_ncomp, n_maps,
+                                                    comp_stride, n_s, nx, nz, d_out,
+                                                    (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ctx, RJP_ERR_HIP, "components_image_launch", e);
+  return rjp::components_image_workgroups(n_maps, n_s, nx, nz);
+}
+
 size_t rjp_gaussfit_workspace(int32_t n_maps, int32_t box_pixels) {
   if (n_maps <= 0 || box_pixels <= 0) return 0;
   return rjp::gaussfit_workspace_bytes(n_maps, box_pixels);

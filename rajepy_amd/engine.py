@@ -1374,6 +1374,81 @@ class RTEngine:
             peak.data_ptr(), work.data_ptr(), work.numel())
         return cpix, cscale, cflux, ncomp, peak
 
+    # -- K18 -------------------------------------------------------------------------------------
+    def _component_list(self, who, cpix, cflux, ncomp, cscale):
+        """The component tensors of `clean` / `msclean` ([M, S] int32 / float64, [M] int32, and
+        None or [M, S] int32 scales) checked -> (M, S)."""
+        torch = _torch()
+        ok = lambda t, dt: (isinstance(t, torch.Tensor) and t.dtype == dt and
+                            t.device == self.device and t.is_contiguous())
+        if not (ok(cpix, torch.int32) and ok(cflux, torch.float64) and ok(ncomp, torch.int32) and
+                cpix.dim() == 2 and cpix.shape == cflux.shape and cpix.shape[1] >= 1 and
+                ncomp.numel() == cpix.shape[0] >= 1 and
+                (cscale is None or (ok(cscale, torch.int32) and cscale.shape == cpix.shape))):
+            raise ValueError("%s: cpix [M, S] int32, cflux [M, S] float64, ncomp [M] int32 (and "
+                             "cscale [M, S] int32) must be contiguous tensors on %s"
+                             % (who, self.device))
+        return int(cpix.shape[0]), int(cpix.shape[1])
+
+    def vis_components(self, cpix, cflux, ncomp, nx, nz, su, sv, u, v, cscale=None, n_s=1,
+                       gvis=None, vis_in=None, sign=1, out=None):
+        """The visibilities of a list of clean components, added to (`sign` +1) or taken from
+        (-1) `vis_in` (rjp_vis_components): out[m, k] = vis_in[m, k] + sign sum_s gvis[m, s, k]
+        sum_{c < ncomp[m], cscale[m, c] = s} cflux[m, c] exp(-2 pi i (su[m] u[k] (ix_c - (nx-1)/2) +
+        sv[m] v[k] (iz_c - (nz-1)/2))) -> complex128 device tensor [M, K].  `cpix`, `cflux`
+        [M, S], `ncomp` [M]: what `clean` / `msclean` return (pixel = ix nz + iz); `cscale` [M, S]
+        with `n_s` scales, None = all of scale 0; `gvis`: complex128 [M, n_s, K] (or float64
+        [M, n_s, K, 2]), the transform of each scale's kernel at each visibility, None = 1 (needs
+        n_s = 1); `vis_in`: complex128 [M, K] or None = 0; `out`: None or a tensor like `vis_in`
+        (may be `vis_in` itself); `su`, `sv`, `u`, `v` as `vis`.  n_comp x n_vis phasors, formed
+        as `vis` forms its own; sums in a fixed order: a repeated call gives the same bits.  Nothing
+        goes to the host.  The workgroup count is kept in `last_vis_components_workgroups`."""
+        torch = _torch()
+        nx, nz, n_s, sign = int(nx), int(nz), int(n_s), int(sign)
+        M, S = self._component_list("vis_components", cpix, cflux, ncomp, cscale)
+        if nx < 1 or nz < 1 or n_s < 1:
+            raise ValueError("vis_components: nx, nz and n_s must be positive")
+        su, sv = self._map_scales("vis_components", su, sv, M)
+        du, dv = self._device_f64(u), self._device_f64(v)
+        K = du.numel()
+        if K < 1 or dv.numel() != K:
+            raise ValueError("vis_components: u and v must have the same length >= 1")
+        if gvis is not None:
+            if isinstance(gvis, torch.Tensor) and gvis.dtype == torch.complex128:
+                gvis = torch.view_as_real(gvis)
+            self._stack_f64("vis_components", "gvis", gvis, M * n_s * K * 2)
+        vin = None
+        if vis_in is not None:
+            vin = self._vis_stack("vis_components", vis_in)
+            if tuple(vin.shape) != (M, K, 2):
+                raise ValueError("vis_components: `vis_in` must be [M, K] = [%d, %d]" % (M, K))
+        if out is None:
+            vout = self._f64(M, K, 2)
+        else:
+            vout = self._vis_stack("vis_components", out)
+            if tuple(vout.shape) != (M, K, 2):
+                raise ValueError("vis_components: `out` must be [M, K] = [%d, %d]" % (M, K))
+        self.last_vis_components_workgroups = self._call_tiles(
+            "rjp_vis_components", cpix.data_ptr(), _ptr(cscale), cflux.data_ptr(),
+            ncomp.data_ptr(), M, S, n_s, nx, nz, _lib.dbl_array(su), _lib.dbl_array(sv),
+            du.data_ptr(), dv.data_ptr(), K, _ptr(gvis), _ptr(vin), sign, vout.data_ptr())
+        return torch.view_as_complex(vout)
+
+    def components_image(self, cpix, cflux, ncomp, nx, nz, cscale=None, n_s=1):
+        """The delta model image of a component list (rjp_components_image): out[m, s, q] = the
+        sum, in list order from +0.0, of the fluxes of map m's components at pixel q with scale s
+        -> float64 device tensor [M, n_s, nx * nz].  Arguments as `vis_components`.  A function of
+        the list alone, no atomics: bit for bit what `clean` / `msclean` add into a zeroed
+        `model`.  Nothing goes to the host."""
+        nx, nz, n_s = int(nx), int(nz), int(n_s)
+        M, S = self._component_list("components_image", cpix, cflux, ncomp, cscale)
+        if nx < 1 or nz < 1 or n_s < 1:
+            raise ValueError("components_image: nx, nz and n_s must be positive")
+        out = self._f64(M, n_s, nx * nz)
+        self._call_tiles("rjp_components_image", cpix.data_ptr(), _ptr(cscale), cflux.data_ptr(),
+                         ncomp.data_ptr(), M, S, n_s, nx, nz, out.data_ptr())
+        return out
+
     # -- K14 -------------------------------------------------------------------------------------
     def gaussfit(self, img, nx, nz, theta0, box=None, mask=None, n_iter=60, lambda0=1e-3,
                  xtol=1e-12, trace=False):

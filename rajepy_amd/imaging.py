@@ -406,19 +406,28 @@ class CleanResult(collections.namedtuple(
     """The six products of a CLEAN as a tuple, and `imfit`: None, or with the `imfit` keyword one
     dict per map (`engine.gauss_results`) -- an attribute beside the tuple, so that code which
     unpacks the six products keeps working.  `_replace` carries `imfit` over (and takes it as a
-    keyword); `_make`, which builds from the six values alone, leaves it None."""
+    keyword); `_make`, which builds from the six values alone, leaves it None.
+    `major`, handled the same way: None, or with `major_cycles` >= 1 one dict per map -- `runs` (a
+    list of dicts `start`, `n`, `peak`, `threshold`: where the run's components begin in the map's
+    list, how many it kept, the masked peak it started from and the threshold it ran to),
+    `sidelobe` and `vis_residual` (complex [K], or [F K] with `mfs`: V minus the list's
+    visibilities, what the residual is the image of)."""
 
-    def __new__(cls, *args, imfit=None, **kw):
+    def __new__(cls, *args, imfit=None, major=None, **kw):
         self = super().__new__(cls, *args, **kw)
         self.imfit = imfit
+        self.major = major
         return self
 
     imfit = None
+    major = None
 
     def _replace(self, **kw):
         imfit = kw.pop("imfit", self.imfit)
+        major = kw.pop("major", self.major)
         out = super()._replace(**kw)
         out.imfit = imfit
+        out.major = major
         return out
 
 
@@ -538,6 +547,30 @@ def _scale_planes(scales, scale_bias):
     if not np.any(bias > 0.):
         raise ValueError("clean: every scale has bias 0")
     return planes, bias, int(np.ceil(planes.max())) - 1 if planes.max() > 0. else 0
+
+
+def _major_options(major_cycles, cyclefactor, cycleniter, min_psf_fraction, max_psf_fraction):
+    """The major-cycle keywords of a CLEAN, checked -> None (`major_cycles` = 0: minor cycles
+    only) or a dict of them."""
+    try:
+        n, cf = int(major_cycles), float(cyclefactor)
+        cn = None if cycleniter is None else int(cycleniter)
+        lo, hi = float(min_psf_fraction), float(max_psf_fraction)
+    except (TypeError, ValueError):
+        raise ValueError("clean: major_cycles, cyclefactor, cycleniter, min_psf_fraction and "
+                         "max_psf_fraction must be numbers") from None
+    if n != major_cycles or n < 0:
+        raise ValueError("clean: `major_cycles` must be an integer >= 0")
+    if not (np.isfinite(cf) and cf > 0.):
+        raise ValueError("clean: `cyclefactor` must be finite and > 0")
+    if cn is not None and (cn != cycleniter or cn < 1):
+        raise ValueError("clean: `cycleniter` must be None or an integer >= 1")
+    if not 0. <= lo <= hi <= 1.:
+        raise ValueError("clean: 0 <= min_psf_fraction <= max_psf_fraction <= 1")
+    if n == 0:
+        return None
+    return dict(major_cycles=n, cyclefactor=cf, cycleniter=cn, min_psf_fraction=lo,
+                max_psf_fraction=hi)
 
 
 class Imager:
@@ -707,7 +740,8 @@ class Imager:
 
     def _clean_images(self, V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
                       threshold_jy, mask, beam, psf_shape, imfit=None, weighting=None, robust=0.5,
-                      scales=None, scale_bias=None):
+                      scales=None, scale_bias=None, major_cycles=0, cyclefactor=1.5, cycleniter=None,
+                      min_psf_fraction=0.05, max_psf_fraction=0.8):
         """Hogbom CLEAN of the dirty images of `V` (see `JetModel.clean_image_ff`), in chunks of
         channels whose dirty images AND beams stay under `stack_bytes`.  Per chunk, on the device:
         `_dirty_images` of V and of unit visibilities (the beams, on the `psf_shape` grid),
@@ -719,9 +753,14 @@ class Imager:
         `scales` (pixels, with `scale_bias`: `_scale_planes`): multi-scale CLEAN instead, per
         chunk `_msclean_chunk` -- `RTEngine.convolve2d`, `RTEngine.msclean` -- and the chunks
         count the n_s planes and the n_s (n_s + 1) / 2 cross beams; the threshold is then one of
-        the SCORE, bias x component flux."""
+        the SCORE, bias x component flux.
+        `major_cycles` >= 1 (with `cyclefactor`, `cycleniter`, `min_psf_fraction`,
+        `max_psf_fraction`): per chunk `_major_chunk` -- minor runs alternating with residuals
+        recomputed from the visibilities -- and `CleanResult.major`; 0 is the path as it was."""
         import torch
         eng = self.engine
+        mj = _major_options(major_cycles, cyclefactor, cycleniter, min_psf_fraction,
+                            max_psf_fraction)
         ni, nj, cell = self._image_grid(shape, cell_as)
         pi_, pj = (2 * ni - 1, 2 * nj - 1) if psf_shape is None else (int(psf_shape[0]),
                                                                       int(psf_shape[1]))
@@ -740,7 +779,8 @@ class Imager:
         fit_opts = self._imfit_options(imfit, mask, ni, nj)
         res = CleanResult(image=np.zeros((n_out, ni, nj)), residual=np.zeros((n_out, ni, nj)),
                           model=np.zeros((n_out, ni, nj)), components=[], beam=[],
-                          peak_residual=np.zeros(n_out), imfit=None if fit_opts is None else [])
+                          peak_residual=np.zeros(n_out), imfit=None if fit_opts is None else [],
+                          major=None if mj is None else [])
         step = F if mfs else max(1, self.stack_bytes // ((ni * nj * 3 + pi_ * pj) * 8))
         ms = None
         if scales is not None:
@@ -758,6 +798,14 @@ class Imager:
             if not mfs:
                 step = max(1, self.stack_bytes // (
                     (ni * nj * (2 * n_s + 1) + n_s * (n_s + 1) // 2 * pi_ * pj) * 8))
+        if mj is not None and not mfs:
+            # what `_major_chunk` holds per map beside the above: a run's planes and the re-imaged
+            # residual, the packed lists, V_res and (with scales) G
+            n_p = 1 if ms is None else len(ms["planes"])
+            extra = ni * nj * (n_p + 1) + 2 * niter + 2 * K * (1 + (0 if ms is None else n_p))
+            per = (ni * nj * 3 + pi_ * pj) if ms is None else \
+                (ni * nj * (2 * n_p + 1) + n_p * (n_p + 1) // 2 * pi_ * pj)
+            step = max(1, self.stack_bytes // ((per + extra) * 8))
         hi, hj = min(self.BEAM_PATCH, pi_) // 2, min(self.BEAM_PATCH, pj) // 2
         mode = _weighting_mode(weighting)
         if mode is not None:
@@ -777,7 +825,6 @@ class Imager:
             grow = 0 if ms is None else 4 * ms["hmax"]
             psf = self._dirty_images(ones[sl], u_d, v_d, freqs[sl], weights,
                                      (pi_ + grow, pj + grow), cell_as, mfs, device=True, iw=iw)
-            del iw
             M = int(dirty.shape[0])
             if grow:
                 # (the clean beam is fitted to, and the cross beams cropped to, the `psf_shape` window)
@@ -792,7 +839,12 @@ class Imager:
                 abc = [beam_quadratic(beam[0], beam[1], beam[2], cell)] * M
             thr_c = float(thr[0]) if thr.size == 1 else thr[f0:f0 + M]
             cscale = None
-            if ms is None:
+            if mj is not None:
+                dirty, model, image, cpix, cscale, cflux, ncomp, peak, info = self._major_chunk(
+                    V[sl], u_d, v_d, freqs[sl], weights, ni, nj, cell, cell_as, mfs, iw, dirty,
+                    psf if not grow else big, psf, pi_, pj, ms, abc, mk, niter, gain, thr_c, mj)
+                res.major.extend(info)
+            elif ms is None:
                 model = torch.zeros_like(dirty)
                 cpix, cflux, ncomp, peak = eng.clean(dirty, ni, nj, psf, pi_, pj, niter, gain, thr_c,
                                                      mask=mk, model=model)
@@ -817,8 +869,134 @@ class Imager:
                 res.components.append(np.stack(cols, axis=1).astype(np.float64)
                                       .reshape(n, len(cols)))
                 res.beam.append(beam_from_quadratic(*abc[m], cell))
-            del dirty, psf, model, image, cpix, cflux, ncomp, peak
+            del dirty, psf, model, image, cpix, cflux, ncomp, peak, iw
         return res
+
+    def _major_chunk(self, V, u_d, v_d, freqs, weights, ni, nj, cell, cell_as, mfs, iw, dirty, beam,
+                     psf, pi_, pj, ms, abc, mk, niter, gain, thr, mj):
+        """CLEAN with major cycles of one chunk: N = mj["major_cycles"] minor runs at most, the
+        residual recomputed from the visibilities after every one -> (residual, model, image
+        [M, ni * nj], cpix, cscale (None without scales), cflux [M, niter], ncomp, peak_residual
+        [M], info: per map the dict of `CleanResult.major`), all but `info` on the device.
+        `dirty` [M, ni * nj] and `psf` [M, pi_ * pj] are the chunk's dirty images and beam windows,
+        `beam` what `_msclean_chunk` takes (multi-scale) and `iw` the chunk's imaging weights: all
+        made once.  sidelobe[m] = max |psf| over the window's pixels with A dx^2 + 2 B dx dz +
+        C dz^2 >= 4 ln 2 of the clean beam's form -- outside twice its half-power ellipse; this
+        project's definition, not CASA's -- 0 when there is no such pixel.  Run r = 1 .. N:
+        peak[m] = the masked max of what the minor cycle compares (|R|; the score with scales); a
+        map with no iteration left or peak <= thr is finished, and the loop ends when every map
+        is; the run's threshold is thr[m] on run N, before it max(thr[m], clip(cyclefactor
+        sidelobe[m], min_psf_fraction, max_psf_fraction) peak[m]), and the largest finite double
+        for a finished map; it runs min(cycleniter or niter, max_m left[m]) iterations and a map
+        keeps the first left[m] of what it finds (the picks are sequential: what n_iter = left[m]
+        would have found), appended to its packed list.  Then V_res = V - the visibilities of the
+        WHOLE list (`RTEngine.vis_components` on the original V, never on the previous V_res) and
+        the residual is `_dirty_images` of V_res with the dirty image's weights; with scales the
+        planes are its convolutions.  The products are functions of the final list and the data:
+        the last residual, `RTEngine.components_image` (and the scale kernels), `restore` plus the
+        residual, its masked max."""
+        import torch
+        eng = self.engine
+        M, F, K = int(dirty.shape[0]), int(V.shape[0]), int(V.shape[1])
+        su, sv = image_scales(freqs, cell)
+        if mfs:
+            cu, cv, _ = _mfs_points(eng, u_d, v_d, su, sv, None)
+            su = sv = [1.0]
+            V0 = V.reshape(1, F * K).contiguous()
+        else:
+            cu, cv, V0 = u_d, v_d, V.contiguous()
+        q = torch.from_numpy(np.asarray(abc, dtype=np.float64).reshape(M, 3)).to(eng.device)
+        dx = (torch.arange(pi_, dtype=torch.float64, device=eng.device) - (pi_ - 1) // 2)[None, :, None]
+        dz = (torch.arange(pj, dtype=torch.float64, device=eng.device) - (pj - 1) // 2)[None, None, :]
+        form = q[:, 0, None, None] * dx * dx + 2. * q[:, 1, None, None] * dx * dz + \
+            q[:, 2, None, None] * dz * dz
+        win = psf.reshape(M, pi_, pj).abs()
+        side = torch.where(form >= _FOUR_LN2, win, torch.zeros_like(win)).amax(dim=(1, 2)).cpu().numpy()
+        del form, win
+        n_s, G, cscale_all = 1, None, None
+        if ms is None:
+            dmask = torch.from_numpy(mk).to(eng.device).reshape(1, -1) if mk is not None else None
+        else:
+            n_s, hmax, dmask = len(ms["planes"]), ms["hmax"], ms["mask"].reshape(1, -1)
+            conv, xpsf, weight = self._ms_setup(beam, M, pi_, pj, ms)
+            wd = torch.from_numpy(np.ascontiguousarray(weight)).to(eng.device)
+            # G[m, s, k]: the transform of scale s's kernel, zero-padded and centred on one odd side
+            gs = 2 * hmax + 1
+            kers = torch.zeros(n_s, gs, gs, dtype=torch.float64, device=eng.device)
+            for k, kk in enumerate(ms["ker"]):
+                h = (int(kk.shape[0]) - 1) // 2
+                kers[k, hmax - h:hmax + h + 1, hmax - h:hmax + h + 1] = kk
+            G = eng.vis(kers.reshape(n_s, gs * gs).repeat(M, 1).contiguous(), gs, gs,
+                        np.repeat(su, n_s), np.repeat(sv, n_s), cu, cv).reshape(M, n_s, -1).contiguous()
+            cscale_all = torch.zeros(M, niter, dtype=torch.int32, device=eng.device)
+        cpix_all = torch.zeros(M, niter, dtype=torch.int32, device=eng.device)
+        cflux_all = torch.zeros(M, niter, dtype=torch.float64, device=eng.device)
+        thr = np.array(np.broadcast_to(np.asarray(thr, dtype=np.float64).reshape(-1), (M,)))
+        left, n_all = np.full(M, niter, dtype=np.int64), np.zeros(M, dtype=np.int64)
+        runs = [[] for _ in range(M)]
+        frac = np.clip(mj["cyclefactor"] * side, mj["min_psf_fraction"], mj["max_psf_fraction"])
+        N, R, Vres = mj["major_cycles"], dirty, V0
+
+        def masked(x):
+            ok = torch.isfinite(x) if dmask is None else dmask & torch.isfinite(x)
+            return torch.where(ok, x.abs(), torch.zeros_like(x)).amax(dim=1)
+
+        def count():
+            return torch.from_numpy(n_all.astype(np.int32)).to(eng.device)
+
+        for r in range(1, N + 1):
+            if ms is None:
+                planes = R.clone()
+                peak = masked(planes).cpu().numpy()
+            else:
+                planes = torch.stack([conv(R, ni, nj, l) for l in range(n_s)], dim=1).contiguous()
+                # the score, weight[k] |R_k[p]|, over the planes that may be picked
+                peak = torch.stack([masked(planes[:, l] * wd[:, l, None]) for l in range(n_s)],
+                                   dim=1).amax(dim=1).cpu().numpy()
+            active = (left > 0) & (peak > thr)
+            if not active.any():
+                break
+            t = thr if r == N else np.maximum(thr, frac * peak)
+            t = np.where(active, t, np.finfo(np.float64).max)
+            n_r = int(min(mj["cycleniter"] or niter, left.max()))
+            if ms is None:
+                cp, cf, nc, _ = eng.clean(planes, ni, nj, psf, pi_, pj, n_r, gain, t, mask=mk)
+            else:
+                cp, cs, cf, nc, _ = eng.msclean(planes, n_s, ni, nj, xpsf, pi_, pj, weight, n_r,
+                                                gain, t, mask=ms["mask"])
+            take = np.where(active, np.minimum(nc.cpu().numpy(), left), 0)
+            # one masked scatter: slot j < take[m] of the run goes to slot n_all[m] + j of the list
+            j = torch.arange(n_r, device=eng.device)[None, :]
+            sel = j < torch.from_numpy(take).to(eng.device)[:, None]
+            row = torch.arange(M, device=eng.device)[:, None].expand(M, n_r)[sel]
+            dst = (torch.from_numpy(n_all).to(eng.device)[:, None] + j)[sel]
+            cpix_all[row, dst] = cp[sel]
+            cflux_all[row, dst] = cf[sel]
+            if ms is not None:
+                cscale_all[row, dst] = cs[sel]
+            for m in np.nonzero(active)[0]:
+                runs[m].append(dict(start=int(n_all[m]), n=int(take[m]), peak=float(peak[m]),
+                                    threshold=float(t[m])))
+            n_all += take
+            left -= take
+            del planes, cp, cf, nc, sel, row, dst
+            Vres = eng.vis_components(cpix_all, cflux_all, count(), ni, nj, su, sv, cu, cv,
+                                      cscale=cscale_all, n_s=n_s, gvis=G, vis_in=V0, sign=-1)
+            R = self._dirty_images(Vres.reshape(F, K) if mfs else Vres, u_d, v_d, freqs, weights,
+                                   (ni, nj), cell_as, mfs, device=True, iw=iw)
+        ncomp = count()
+        model = eng.components_image(cpix_all, cflux_all, ncomp, ni, nj, cscale=cscale_all, n_s=n_s)
+        if ms is None:
+            model = model.reshape(M, ni * nj)
+            image = eng.restore(cpix_all, cflux_all, ncomp, abc, ni, nj, add=R)
+            peak = masked(R)
+        else:
+            model, image, peak = self._ms_products(R, model, cpix_all, cscale_all, cflux_all, ncomp,
+                                                   abc, ni, nj, ms, conv)
+        hv = Vres.cpu().numpy()
+        info = [dict(runs=runs[m], sidelobe=float(side[m]), vis_residual=hv[m].copy())
+                for m in range(M)]
+        return R, model, image, cpix_all, cscale_all, cflux_all, ncomp, peak, info
 
     def _msclean_chunk(self, dirty, beam, ni, nj, pi_, pj, ms, abc, niter, gain, thr):
         """Multi-scale CLEAN of one chunk's dirty images [M, ni * nj] -> (raw residual, model,
@@ -831,8 +1009,26 @@ class Imager:
         restore(components of scale k).  `peak_residual`: the masked max of the raw plane."""
         import torch
         eng = self.engine
+        n_s = len(ms["planes"])
+        conv, xpsf, weight = self._ms_setup(beam, int(dirty.shape[0]), pi_, pj, ms)
+        res = torch.stack([conv(dirty, ni, nj, l) for l in range(n_s)], dim=1).contiguous()
+        model = torch.zeros_like(res)
+        cpix, cscale, cflux, ncomp, _ = eng.msclean(res, n_s, ni, nj, xpsf, pi_, pj, weight, niter,
+                                                    gain, thr, mask=ms["mask"], model=model)
+        del xpsf
+        raw = res[:, 0].contiguous()
+        total, image, peak = self._ms_products(raw, model, cpix, cscale, cflux, ncomp, abc, ni, nj,
+                                               ms, conv)
+        return raw, total, image, cpix, cscale, cflux, ncomp, peak
+
+    def _ms_setup(self, beam, M, pi_, pj, ms):
+        """What a multi-scale chunk makes once from its dirty beams (`_msclean_chunk`) -> (conv: the
+        convolution with scale k's kernel, the cross beams [M, n_s (n_s + 1) / 2, pi_ * pj], the
+        weights [M, n_s] on the host)."""
+        import torch
+        eng = self.engine
         planes, ker, hmax = ms["planes"], ms["ker"], ms["hmax"]
-        n_s, M, npix = len(planes), int(dirty.shape[0]), ni * nj
+        n_s = len(planes)
         bi, bj = pi_ + 4 * hmax, pj + 4 * hmax
 
         def conv(x, nx, nz, k, add=None):
@@ -848,7 +1044,6 @@ class Imager:
                             for k in range(n_s) for l in range(k, n_s)], dim=1)
         xpsf = xpsf.reshape(M, -1, pi_ * pj).contiguous()
         del single
-        res = torch.stack([conv(dirty, ni, nj, l) for l in range(n_s)], dim=1).contiguous()
         centre = ((pi_ - 1) // 2) * pj + (pj - 1) // 2
         diag = [k * n_s - k * (k - 1) // 2 for k in range(n_s)]
         xkk = xpsf[:, diag, centre].cpu().numpy()                       # [M, n_s]: a few numbers
@@ -856,13 +1051,15 @@ class Imager:
             weight = np.where(ms["bias"][None, :] > 0., ms["bias"][None, :] / xkk, 0.)
         if not np.all(np.isfinite(weight) & (weight >= 0.)):
             raise ValueError("clean: a scale's beam X_kk is not positive at its centre")
-        model = torch.zeros_like(res)
-        cpix, cscale, cflux, ncomp, _ = eng.msclean(res, n_s, ni, nj, xpsf, pi_, pj, weight, niter,
-                                                    gain, thr, mask=ms["mask"], model=model)
-        del xpsf
-        raw = res[:, 0].contiguous()
+        return conv, xpsf, weight
+
+    def _ms_products(self, raw, model, cpix, cscale, cflux, ncomp, abc, ni, nj, ms, conv):
+        """The products of a multi-scale chunk from its raw residual [M, ni * nj], the delta models
+        [M, n_s, ni * nj] and the component list -> (model, image [M, ni * nj], peak_residual)."""
+        import torch
+        eng = self.engine
         total, image = model[:, 0].contiguous(), raw          # (plane 0 is the delta scale)
-        for k in range(n_s):
+        for k in range(len(ms["planes"])):
             # K13 with the other scales' fluxes zeroed, then the scale's kernel, chained by `add`
             fk = torch.where(cscale == k, cflux, torch.zeros_like(cflux))
             if k == 0:
@@ -872,7 +1069,7 @@ class Imager:
             image = conv(eng.restore(cpix, fk, ncomp, abc, ni, nj), ni, nj, k, add=image)
         ok = ms["mask"].reshape(1, -1) & torch.isfinite(raw)
         peak = torch.where(ok, raw.abs(), torch.zeros_like(raw)).amax(dim=1)
-        return raw, total, image, cpix, cscale, cflux, ncomp, peak
+        return total, image, peak
 
     # ------------------------------------------------------------------ synthetic observations ----
     def uv_tracks(self, antennalist, dec_deg, t_obs_s, t_int_s, min_el_deg=None, hourangle_h=0.):
@@ -892,7 +1089,8 @@ class Imager:
 
     def _observe(self, maps, freqs, tracks, t_int_s, sigma_jy, sefd_jy, chanwidth_hz, seed,
                  nsigma, weights, shape, cell_as, mfs, niter, gain, threshold_jy, mask, beam,
-                 psf_shape, imfit, weighting, robust, scales=None, scale_bias=None):
+                 psf_shape, imfit, weighting, robust, scales=None, scale_bias=None, major_cycles=0,
+                 cyclefactor=1.5, cycleniter=None, min_psf_fraction=0.05, max_psf_fraction=0.8):
         """`JetModel.observe_*` after the maps [F, nx * nz]: visibilities, noise, image rms, CLEAN."""
         F = len(freqs)
         if sigma_jy is not None and sefd_jy is not None:
@@ -930,7 +1128,10 @@ class Imager:
                 imfit["rms"] = rms
         res = self._clean_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
                                  thr, mask, beam, psf_shape, imfit, weighting=weighting,
-                                 robust=robust, scales=scales, scale_bias=scale_bias)
+                                 robust=robust, scales=scales, scale_bias=scale_bias,
+                                 major_cycles=major_cycles, cyclefactor=cyclefactor,
+                                 cycleniter=cycleniter, min_psf_fraction=min_psf_fraction,
+                                 max_psf_fraction=max_psf_fraction)
         v0 = V0.cpu().numpy()
         return Observation(tracks, v0, V.cpu().numpy() if noisy else v0.copy(), sigma, rms, res)
 
