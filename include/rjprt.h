@@ -907,6 +907,52 @@ int64_t rjp_msclean(rjp_ctx* ctx, double* d_res, int32_t n_maps, int32_t n_s, in
                     double* d_cflux, int32_t* d_ncomp, double* d_model, double* d_peak,
                     void* d_work, size_t work_bytes, void* stream);
 
+/* ---- K19: multi-term MFS CLEAN minor cycles on a stack of maps -- spectral-index maps --------------
+ * CASA tclean(deconvolver='mtmfs', nterms=2) is what the reference's Tclean task offers for a band
+ * (`nterms` beside `deconvolver` and `scales`: casa/tasks.py:243-246).  Sault & Wieringa 1994 /
+ * Rau & Cornwell 2011 at a single scale: the sky is I(nu) = sum_t I_t w^t, w = (nu - nu_0) / nu_0,
+ * and the minor cycle works on n_t Taylor residual planes coupled through a small Hessian.  The entry
+ * point is agnostic of frequencies, like rjp_msclean: the caller prepares planes, beams and Hinv.
+ *   d_res [n_maps][n_t][nx nz]   the Taylor residual planes R_t (the dirty image of the visibilities
+ *                                times w^t), updated IN PLACE
+ *   d_spsf [n_psf][2 n_t - 1][px pz]   the spectral beams B_q (the beam of unit visibilities times
+ *                                w^q); px and pz ODD; n_psf = n_maps, or 1 for one set for all maps
+ *   h_hinv [n_maps][n_t][n_t]    HOST: the inverse of the Hessian H[t][q] = B_{t+q}(centre), every
+ *                                entry finite; used as given, row by row (no symmetry is assumed)
+ *   d_mask [nx nz], h_thresh [n_maps], gain, n_iter   as K12
+ *   d_cpix [n_maps][n_iter] int32, d_ccoef [n_maps][n_iter][n_t], d_ncomp [n_maps]
+ *   d_model [n_maps][n_t][nx nz] (optional) ADDED to: the delta model of each Taylor term
+ *   d_peak [n_maps]              (optional) the final masked max |a_0|, 0 when no pixel qualifies
+ * ARITHMETIC.  At a pixel p, term q of the principal solution is
+ *   a_q = Hinv[q][0] R_0[p]  (one product),  then a_q = fma(Hinv[q][t], R_t[p], a_q), t = 1 .. n_t - 1.
+ * Iteration i of map m: among the pixels that are unmasked and finite in ALL n_t planes, p* is the one
+ * with the largest |a_0(p)|, the lowest p on a tie.  With no such pixel, or |a_0(p*)| <= h_thresh[m],
+ * the map is finished and nothing of it changes any more.  Otherwise c_q = gain a_q(p*) (one product)
+ * for every q; (p*, c_0 .. c_{n_t-1}) goes to slot i, d_model[m][t][p*] += c_t, and for every plane t
+ *   r = R_t[x];  r = fma(-c_q, B_{t+q}[x - p* + centre], r)  for q = 0 .. n_t - 1 ascending;  R_t[x] = r
+ * for every x whose beam index lies inside the beam: n_t roundings per update.  A pixel that is
+ * non-finite in plane t is never a candidate; it is left as it is in that plane and updated normally
+ * in the others.  Slots at and beyond d_ncomp[m] are not written.  A second call on the planes
+ * continues the same clean.  No atomics, every reduction in a fixed order: a repeated call gives the
+ * same bits.  With n_t = 1, Hinv = 1.0 and a beam whose centre is exactly 1.0 every output equals
+ * rjp_clean's bit for bit.
+ * One launch per iteration for the whole stack, grid = tiles x maps; one workgroup holds all n_t
+ * planes of its tile of 1024 pixels.  A tile's partial carries the pixel and the n_t plane values at
+ * it, double buffered: 2 x (8 n_t + 4) bytes per map and tile, rounded up to 16.
+ * RETURNS the number of workgroups of one iteration's launch, > 0 -- n_maps x ceil(nx nz / 1024) --
+ * or a negative RJP_ERR_*.  Everything is validated before anything is enqueued, and no output or
+ * workspace byte is touched on a refusal: RJP_ERR_ARG for K12's refusals (with d_spsf for d_psf), a
+ * NULL h_hinv or d_ccoef, n_t outside 1 .. RJP_MTMFS_MAX_NT, a non-finite h_hinv entry, more than
+ * 2^31 - 1 workgroups.  RJP_ERR_WORKSPACE for a d_work smaller than the workspace query (0 from it =
+ * a bad argument, or a size that overflows). */
+#define RJP_MTMFS_MAX_NT 4
+size_t rjp_mtmfs_workspace(int32_t n_maps, int32_t n_t, int32_t nx, int32_t nz);
+int64_t rjp_mtmfs(rjp_ctx* ctx, double* d_res, int32_t n_maps, int32_t n_t, int32_t nx, int32_t nz,
+                  const double* d_spsf, int32_t n_psf, int32_t px, int32_t pz,
+                  const double* h_hinv, const uint8_t* d_mask, const double* h_thresh, double gain,
+                  int32_t n_iter, int32_t* d_cpix, double* d_ccoef, int32_t* d_ncomp,
+                  double* d_model, double* d_peak, void* d_work, size_t work_bytes, void* stream);
+
 /* ---- K18: the visibilities of a list of clean components -- the forward step of a major cycle -------
  * CASA tclean alternates minor cycles in the image plane with major cycles that recompute the residual
  * from the visibilities; the reference's Tclean task carries the controls (cycleniter, cyclefactor,

@@ -166,6 +166,10 @@ SIGNATURES = {
     "rjp_msclean": (C.c_int64, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32,
                                 C.c_int32, C.c_int32, _DP, _P, _DP, C.c_double, C.c_int32, _P, _P,
                                 _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "rjp_mtmfs_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "rjp_mtmfs": (C.c_int64, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32,
+                              C.c_int32, C.c_int32, _DP, _P, _DP, C.c_double, C.c_int32, _P, _P, _P,
+                              _P, _P, _P, C.c_size_t, _P]),
     "rjp_vis_components": (C.c_int64, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_int32, _DP, _DP, _P, _P, C.c_int32, _P, _P,
                                        C.c_int32, _P, _P]),

@@ -1150,7 +1150,8 @@ class JetModel:
     def clean_image_ff(self, u_m, v_m, freq, weights=None, shape=None, cell_as=None, formal=False,
                        mfs=False, niter=500, gain=0.1, threshold_jy=0.0, mask=None, beam=None,
                        psf_shape=None, imfit=None, weighting=None, robust=0.5, scales=None,
-                       scale_bias=None, major_cycles=0, cyclefactor=1.5, cycleniter=None,
+                       scale_bias=None, nterms=1, reffreq_hz=None, alpha_cut_jy=None,
+                       major_cycles=0, cyclefactor=1.5, cycleniter=None,
                        min_psf_fraction=0.05, max_psf_fraction=0.8):
         """CLEANed, restored images [Jy / clean beam] of the `flux_ff` maps as an array with the
         baselines (`u_m`, `v_m`) in metres sees them: `dirty_image_ff` and `dirty_beam` (same
@@ -1189,6 +1190,21 @@ class JetModel:
         residual, `peak_residual` its masked max, `threshold_jy` bounds the score, and components
         lie at least the largest kernel's half width from the border (ValueError if the mask
         leaves no such pixel).  The kernels carry no prolate-spheroidal taper: not CASA's bits.
+        `nterms`: 1 = the path as it was; 2 .. 4 with `mfs` = multi-term MFS CLEAN (K19:
+        `RTEngine.mtmfs`, rjp_mtmfs), tclean(deconvolver='mtmfs', nterms=...) at a single scale
+        (the reference's Tclean task lists `nterms`, casa/tasks.py:243-246; Sault & Wieringa 1994,
+        Rau & Cornwell 2011; this project's definition, no CASA parity).  The sky is I(nu) =
+        sum_t I_t w^t, w = (nu - `reffreq_hz`) / `reffreq_hz` (None = the mid-point of the lowest
+        and the highest channel); the Taylor dirty images and the spectral beams are the `mfs`
+        image of the visibilities times w^t (`engine.taylor_weights`), the Hessian of the beams'
+        centres is inverted on the host (`engine.taylor_hessian_inverse`, which refuses a band
+        too narrow for `nterms`).  `image` is then tt0, `residual` the raw R_0, `model` the tt0
+        delta model, `components` rows (ix, iz, c_0 .. c_{nterms-1}), `peak_residual` and
+        `threshold_jy` act on |a_0|, term 0 of the principal solution, and `CleanResult.taylor`
+        holds per map `tt`, `residual_tt`, `model_tt` (nterms, ni, nj), `alpha` = tt1 / tt0 where
+        tt0 > `alpha_cut_jy` (None = 0.1 of the largest tt0) and NaN elsewhere, `beta` = tt2 / tt0
+        - alpha (alpha - 1) / 2 (None below three terms), `alpha_cut_jy`, `reffreq_hz`, `hessian`
+        and `hinv`.  Not with `scales` or `major_cycles` (ValueError).
         `major_cycles`: 0 = minor cycles only, as above -- the residual is then the one the minor
         cycles kept in the image plane, the data's only when `psf_shape` is the full window.
         N >= 1 = at most N minor runs, and after every one the residual is recomputed from the
@@ -1206,14 +1222,17 @@ class JetModel:
         im, *vis = self._model_vis(u_m, v_m, freq, weighting, formal=formal)
         return im._clean_images(*vis, weights, shape, cell_as, mfs, niter, gain, threshold_jy, mask,
                                 beam, psf_shape, imfit, weighting=weighting, robust=robust,
-                                scales=scales, scale_bias=scale_bias, major_cycles=major_cycles, cyclefactor=cyclefactor,
+                                scales=scales, scale_bias=scale_bias, nterms=nterms, reffreq_hz=reffreq_hz,
+                                alpha_cut_jy=alpha_cut_jy, major_cycles=major_cycles,
+                                cyclefactor=cyclefactor,
                                 cycleniter=cycleniter, min_psf_fraction=min_psf_fraction,
                                 max_psf_fraction=max_psf_fraction)
 
     def clean_image_rrl(self, rrl, u_m, v_m, freq, weights=None, shape=None, cell_as=None,
                         contsub=True, formal=False, mfs=False, niter=500, gain=0.1,
                         threshold_jy=0.0, mask=None, beam=None, psf_shape=None, imfit=None,
-                        weighting=None, robust=0.5, scales=None, scale_bias=None,
+                        weighting=None, robust=0.5, scales=None, scale_bias=None, nterms=1,
+                        reffreq_hz=None, alpha_cut_jy=None,
                         major_cycles=0, cyclefactor=1.5, cycleniter=None,
                         min_psf_fraction=0.05, max_psf_fraction=0.8):
         """CLEANed, restored images of the `flux_rrl` maps (same arguments) -> `CleanResult`; see
@@ -1221,7 +1240,9 @@ class JetModel:
         im, *vis = self._model_vis(u_m, v_m, freq, weighting, rrl=rrl, contsub=contsub, formal=formal)
         return im._clean_images(*vis, weights, shape, cell_as, mfs, niter, gain, threshold_jy, mask,
                                 beam, psf_shape, imfit, weighting=weighting, robust=robust,
-                                scales=scales, scale_bias=scale_bias, major_cycles=major_cycles, cyclefactor=cyclefactor,
+                                scales=scales, scale_bias=scale_bias, nterms=nterms, reffreq_hz=reffreq_hz,
+                                alpha_cut_jy=alpha_cut_jy, major_cycles=major_cycles,
+                                cyclefactor=cyclefactor,
                                 cycleniter=cycleniter, min_psf_fraction=min_psf_fraction,
                                 max_psf_fraction=max_psf_fraction)
 
@@ -1250,7 +1271,8 @@ class JetModel:
                    sigma_jy=None, sefd_jy=None, chanwidth_hz=None, seed=0, nsigma=0.,
                    weights=None, shape=None, cell_as=None, formal=False, mfs=False, niter=500,
                    gain=0.1, threshold_jy=0.0, mask=None, beam=None, psf_shape=None, imfit=None,
-                   weighting=None, robust=0.5, scales=None, scale_bias=None, major_cycles=0,
+                   weighting=None, robust=0.5, scales=None, scale_bias=None, nterms=1,
+                   reffreq_hz=None, alpha_cut_jy=None, major_cycles=0,
                    cyclefactor=1.5, cycleniter=None, min_psf_fraction=0.05, max_psf_fraction=0.8):
         """A synthetic observation of the `flux_ff` maps, start to end on the device -- the
         reference's simobserve -> tclean -> imfit chain (classes.py:2490-2850) -> `Observation`:
@@ -1273,15 +1295,17 @@ class JetModel:
         return self._observe(dict(formal=formal), antennalist, freq, t_obs_s, t_int_s, min_el_deg,
                              hourangle_h, sigma_jy, sefd_jy, chanwidth_hz, seed, nsigma, weights,
                              shape, cell_as, mfs, niter, gain, threshold_jy, mask, beam, psf_shape,
-                             imfit, weighting, robust, scales, scale_bias, major_cycles,
-                             cyclefactor, cycleniter, min_psf_fraction, max_psf_fraction)
+                             imfit, weighting, robust, scales, scale_bias, nterms, reffreq_hz,
+                             alpha_cut_jy, major_cycles, cyclefactor, cycleniter,
+                             min_psf_fraction, max_psf_fraction)
 
     def observe_rrl(self, rrl, antennalist, freq, t_obs_s, t_int_s, min_el_deg=None,
                     hourangle_h=0., sigma_jy=None, sefd_jy=None, chanwidth_hz=None, seed=0,
                     nsigma=0., weights=None, shape=None, cell_as=None, contsub=True, formal=False,
                     mfs=False, niter=500, gain=0.1, threshold_jy=0.0, mask=None, beam=None,
                     psf_shape=None, imfit=None, weighting=None, robust=0.5, scales=None,
-                    scale_bias=None, major_cycles=0, cyclefactor=1.5, cycleniter=None,
+                    scale_bias=None, nterms=1, reffreq_hz=None, alpha_cut_jy=None,
+                    major_cycles=0, cyclefactor=1.5, cycleniter=None,
                     min_psf_fraction=0.05, max_psf_fraction=0.8):
         """A synthetic observation of the `flux_rrl` maps -> `Observation`; see `observe_ff`."""
         _weighting_mode(weighting)            # (refuses an unknown scheme before any work)
@@ -1289,8 +1313,8 @@ class JetModel:
                              t_obs_s, t_int_s, min_el_deg, hourangle_h, sigma_jy, sefd_jy,
                              chanwidth_hz, seed, nsigma, weights, shape, cell_as, mfs, niter, gain,
                              threshold_jy, mask, beam, psf_shape, imfit, weighting, robust, scales,
-                             scale_bias, major_cycles, cyclefactor, cycleniter, min_psf_fraction,
-                             max_psf_fraction)
+                             scale_bias, nterms, reffreq_hz, alpha_cut_jy, major_cycles,
+                             cyclefactor, cycleniter, min_psf_fraction, max_psf_fraction)
 
     # ------------------------------------------------------------------ imfit ----
     def imfit(self, images, beam, cell_as=None, box=None, theta0=None, n_iter=60, rms=None):

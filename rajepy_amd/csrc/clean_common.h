@@ -1,4 +1,4 @@
-// What the CLEAN kernels share (clean.hip: K12 / K13; msclean.hip: K17): the tile of 1024
+// What the CLEAN kernels share (clean.hip: K12 / K13; msclean.hip: K17; mtmfs.hip: K19): the tile of 1024
 // consecutive pixels of a flat image with two pairs of neighbours per thread, the 16-byte pair
 // loads and stores, and the (value, pixel) partial maxima with their fixed-order reductions.
 #pragma once

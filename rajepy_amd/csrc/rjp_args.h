@@ -220,6 +220,38 @@ inline int check_msclean(const double* d_res, int n_maps, int n_s, int nx, int n
   return RJP_OK;
 }
 
+// What rjp_mtmfs takes, in the order it refuses: NULL pointers, sizes below 1, n_t beyond
+// RJP_MTMFS_MAX_NT, an even beam, the beam count, the image size, the gain, n_iter, the thresholds,
+// the inverse Hessians.  (`d_mask`, `d_model`, `d_peak` may be NULL; the grid and the workspace are
+// checked where the tiling lives.)
+inline int check_mtmfs(const double* d_res, int n_maps, int n_t, int nx, int nz,
+                       const double* d_spsf, int n_psf, int px, int pz, const double* h_hinv,
+                       const double* h_thresh, double gain, int n_iter, const int32_t* d_cpix,
+                       const double* d_ccoef, const int32_t* d_ncomp, std::string& err) {
+  if (!d_res || !d_spsf || !h_hinv || !h_thresh || !d_cpix || !d_ccoef || !d_ncomp)
+    return refuse(err, "rjp_mtmfs: NULL planes, spectral beams, inverse Hessians, thresholds or "
+                       "component outputs");
+  if (n_maps < 1 || n_t < 1 || nx < 1 || nz < 1 || px < 1 || pz < 1)
+    return refuse(err, "rjp_mtmfs: n_maps, n_t, nx, nz, px and pz must be positive");
+  if (n_t > RJP_MTMFS_MAX_NT)
+    return refuse(err, "rjp_mtmfs: n_t must not exceed RJP_MTMFS_MAX_NT (" +
+                           std::to_string(RJP_MTMFS_MAX_NT) + ")");
+  if (px % 2 == 0 || pz % 2 == 0)
+    return refuse(err, "rjp_mtmfs: px and pz must be odd (the beam's centre is a pixel)");
+  if (n_psf != 1 && n_psf != n_maps)
+    return refuse(err, "rjp_mtmfs: n_psf must be 1 or n_maps");
+  if ((int64_t)nx * nz > (int64_t)INT32_MAX)
+    return refuse(err, "rjp_mtmfs: nx * nz exceeds 2^31 - 1");
+  if (!(gain > 0.0 && gain <= 1.0)) return refuse(err, "rjp_mtmfs: gain must lie in (0, 1]");
+  if (n_iter < 1) return refuse(err, "rjp_mtmfs: n_iter < 1");
+  for (int m = 0; m < n_maps; ++m)
+    if (!(h_thresh[m] >= 0.0) || !std::isfinite(h_thresh[m]))
+      return refuse(err, "rjp_mtmfs: negative or non-finite threshold");
+  for (int64_t i = 0; i < (int64_t)n_maps * n_t * n_t; ++i)
+    if (!std::isfinite(h_hinv[i])) return refuse(err, "rjp_mtmfs: non-finite h_hinv");
+  return RJP_OK;
+}
+
 // What rjp_vis_components takes, in the order it refuses: NULL pointers, sizes below 1, the sign, a
 // missing d_gvis with more than one scale, a non-finite scale, the image size, the workgroup count
 // (64 visibilities each).  (`d_cscale`, `d_gvis` and `d_in` may be NULL.)

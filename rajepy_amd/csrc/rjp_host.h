@@ -339,6 +339,22 @@ hipError_t msclean_launch(double* res, int n_maps, int n_s, int nx, int nz, cons
                           int32_t* cscale, double* cflux, int32_t* ncomp, double* model,
                           double* peak, void* work, hipStream_t st);
 
+// ---- mtmfs.hip: multi-term MFS CLEAN on a stack of maps of n_t Taylor planes each (K19) ------------
+struct MtmfsTiling {
+  int64_t tiles;                // of 1024 consecutive pixels, per map (a workgroup holds all planes)
+  int64_t workgroups;           // n_maps x tiles: the grid of every iteration's launch
+};
+MtmfsTiling mtmfs_tiling(int n_maps, int nx, int nz);
+// >= 16; 0: does not fit a size_t
+size_t mtmfs_workspace_bytes(int n_maps, int n_t, int nx, int nz);
+// d_hinv[n_maps][n_t][n_t], d_thresh[n_maps]: device copies; `mask`, `model`, `peak` may be nullptr;
+// 1 <= n_t <= RJP_MTMFS_MAX_NT; 1 + n_iter (+ 1 with `peak`) launches, no host synchronisation
+hipError_t mtmfs_launch(double* res, int n_maps, int n_t, int nx, int nz, const double* spsf,
+                        int n_psf, int px, int pz, const double* d_hinv, const uint8_t* mask,
+                        const double* d_thresh, double gain, int n_iter, int32_t* cpix,
+                        double* ccoef, int32_t* ncomp, double* model, double* peak, void* work,
+                        hipStream_t st);
+
 // ---- vis_components.hip: visibilities (K18) and the delta model image of a component list ---------
 int64_t vis_components_workgroups(int n_maps, int n_vis);            // n_maps x ceil(n_vis / 64)
 int64_t components_image_workgroups(int n_maps, int n_s, int nx, int nz);

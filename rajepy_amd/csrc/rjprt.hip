@@ -1251,6 +1251,40 @@ int64_t rjp_msclean(rjp_ctx* ctx, double* d_res, int32_t n_maps, int32_t n_s, in
   return r ? r : t.workgroups;
 }
 
+size_t rjp_mtmfs_workspace(int32_t n_maps, int32_t n_t, int32_t nx, int32_t nz) {
+  if (n_maps <= 0 || n_t <= 0 || n_t > RJP_MTMFS_MAX_NT || nx <= 0 || nz <= 0) return 0;
+  return rjp::mtmfs_workspace_bytes(n_maps, n_t, nx, nz);
+}
+
+int64_t rjp_mtmfs(rjp_ctx* ctx, double* d_res, int32_t n_maps, int32_t n_t, int32_t nx, int32_t nz,
+                  const double* d_spsf, int32_t n_psf, int32_t px, int32_t pz,
+                  const double* h_hinv, const uint8_t* d_mask, const double* h_thresh, double gain,
+                  int32_t n_iter, int32_t* d_cpix, double* d_ccoef, int32_t* d_ncomp,
+                  double* d_model, double* d_peak, void* d_work, size_t work_bytes, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_mtmfs(d_res, n_maps, n_t, nx, nz, d_spsf, n_psf, px, pz, h_hinv,
+                                     h_thresh, gain, n_iter, d_cpix, d_ccoef, d_ncomp, m);
+      }))
+    return r;
+  const rjp::MtmfsTiling t = rjp::mtmfs_tiling(n_maps, nx, nz);
+  if (t.workgroups > (int64_t)INT32_MAX)
+    return fail(ctx, RJP_ERR_ARG, "rjp_mtmfs: more than 2^31 - 1 workgroups");
+  const size_t need = rjp::mtmfs_workspace_bytes(n_maps, n_t, nx, nz);
+  if (!d_work || need == 0 || work_bytes < need)
+    return fail(ctx, RJP_ERR_WORKSPACE, "rjp_mtmfs: workspace smaller than rjp_mtmfs_workspace()");
+  hipStream_t st = (hipStream_t)stream;
+  const int r = staged(ctx, st, "mtmfs_launch", nullptr,
+                       {{h_hinv, (size_t)n_maps * (size_t)n_t * (size_t)n_t},
+                        {h_thresh, (size_t)n_maps}},
+                       [&](double* const* d, const double*) {
+                         return rjp::mtmfs_launch(d_res, n_maps, n_t, nx, nz, d_spsf, n_psf, px, pz,
+                                                  d[0], d_mask, d[1], gain, n_iter, d_cpix, d_ccoef,
+                                                  d_ncomp, d_model, d_peak, d_work, st);
+                       });
+  return r ? r : t.workgroups;
+}
+
 int64_t rjp_vis_components(rjp_ctx* ctx, const int32_t* d_cpix, const int32_t* d_cscale,
                            const double* d_cflux, const int32_t* d_ncomp, int32_t n_maps,
                            int32_t comp_stride, int32_t n_s, int32_t nx, int32_t nz,

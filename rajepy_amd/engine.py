@@ -16,7 +16,8 @@ from ._lib import RJP_F32, RJP_F64, RJP_GFF_POWERLAW, RJP_GFF_SCALAR  # noqa: F4
 from .imaging import (SIDEREAL_DAY_S, AntennaConfig, Geodetic, antenna_config_path,  # noqa: F401
                       beam_from_quadratic, beam_quadratic, fit_beam, gauss_results, gauss_start,
                       geodetic, image_rms, image_scales, observation_grid, observing_plan,
-                      read_antenna_config, scale_biases, scale_kernel, thermal_sigma, vis_scales)
+                      read_antenna_config, scale_biases, scale_kernel, taylor_hessian_inverse,
+                      taylor_weights, thermal_sigma, vis_scales)
 
 
 def _torch():
@@ -1373,6 +1374,60 @@ class RTEngine:
             cpix.data_ptr(), cscale.data_ptr(), cflux.data_ptr(), ncomp.data_ptr(), _ptr(model),
             peak.data_ptr(), work.data_ptr(), work.numel())
         return cpix, cscale, cflux, ncomp, peak
+
+    def mtmfs(self, res, n_t, nx, nz, spsf, px, pz, hinv, n_iter, gain, thresh, mask=None,
+              model=None):
+        """Multi-term MFS CLEAN minor cycles on a stack of maps of `n_t` Taylor planes each
+        (rjp_mtmfs), one fused launch per iteration for the whole stack, nothing going to the host
+        -> (cpix [M, n_iter] int32, ccoef [M, n_iter, n_t] float64, ncomp [M] int32, peak [M]
+        float64) device tensors; slots at and beyond ncomp[m] are not written.  `res`: float64
+        device tensor of M * n_t * nx * nz values, the Taylor residual planes, updated IN PLACE.
+        `spsf`: the spectral beams B_0 .. B_{2 n_t - 2} of px * pz values (odd), one set or one per
+        map.  `hinv`: host, [n_t, n_t] or [M, n_t, n_t], the inverse of H[t][q] = B_{t+q}(centre)
+        (`taylor_hessian_inverse`), every entry finite.  `thresh`, `mask` as `clean`; `model`: a
+        tensor like `res` that every component's coefficients are ADDED to, term by term.  Per
+        iteration and map: a_q = sum_t hinv[q][t] R_t[p]; the largest |a_0| (lower p on a tie);
+        stop at <= thresh; else c_q = gain a_q and R_t -= sum_q c_q B_{t+q} shifted to p, for every
+        t.  `peak`: the final max |a_0|.  The same bits on every call.  The number of workgroups
+        per iteration is kept in `last_mtmfs_workgroups`."""
+        torch = _torch()
+        n_t, nx, nz, px, pz, n_iter = int(n_t), int(nx), int(nz), int(px), int(pz), int(n_iter)
+        if n_t < 1 or nx < 1 or nz < 1 or px < 1 or pz < 1 or n_iter < 1:
+            raise ValueError("mtmfs: n_t, nx, nz, px, pz and n_iter must be positive")
+        per = n_t * nx * nz
+        if not (isinstance(res, torch.Tensor) and res.numel() >= per and res.numel() % per == 0):
+            raise ValueError("mtmfs: `res` must hold a whole number (>= 1) of n_t * nx * nz maps")
+        M = res.numel() // per
+        self._stack_f64("mtmfs", "res", res, M * per)
+        nb = (2 * n_t - 1) * px * pz
+        if not (isinstance(spsf, torch.Tensor) and spsf.numel() in (nb, M * nb)):
+            raise ValueError("mtmfs: `spsf` must hold one set of 2 n_t - 1 spectral beams of "
+                             "px * pz values, or one per map")
+        n_psf = spsf.numel() // nb
+        self._stack_f64("mtmfs", "spsf", spsf, n_psf * nb)
+        if model is not None:
+            self._stack_f64("mtmfs", "model", model, M * per)
+        dmask = self._device_mask("mtmfs", mask, nx * nz)
+        h = np.asarray(hinv, dtype=np.float64)
+        if h.size not in (n_t * n_t, M * n_t * n_t):
+            raise ValueError("mtmfs: `hinv` must be [n_t, n_t] = [%d, %d] or one per map"
+                             % (n_t, n_t))
+        h = np.ascontiguousarray(np.broadcast_to(h.reshape(-1, n_t, n_t), (M, n_t, n_t)))
+        th = np.asarray(thresh, dtype=np.float64).reshape(-1)
+        if th.size not in (1, M):
+            raise ValueError("mtmfs: `thresh` must be one number or one per map (%d)" % M)
+        th = np.ascontiguousarray(np.broadcast_to(th, (M,)))
+        cpix = torch.empty(M, n_iter, dtype=torch.int32, device=self.device)
+        ccoef = self._f64(M, n_iter, n_t)
+        ncomp = torch.empty(M, dtype=torch.int32, device=self.device)
+        peak = self._f64(M)
+        work = self._workspace(max(1, self.lib.rjp_mtmfs_workspace(M, n_t, nx, nz)))
+        self.last_mtmfs_workgroups = self._call_tiles(
+            "rjp_mtmfs", res.data_ptr(), M, n_t, nx, nz, spsf.data_ptr(), n_psf, px, pz,
+            _lib.dbl_array(h), _ptr(dmask), _lib.dbl_array(th), float(gain), n_iter,
+            cpix.data_ptr(), ccoef.data_ptr(), ncomp.data_ptr(), _ptr(model), peak.data_ptr(),
+            work.data_ptr(), work.numel())
+        return cpix, ccoef, ncomp, peak
 
     # -- K18 -------------------------------------------------------------------------------------
     def _component_list(self, who, cpix, cflux, ncomp, cscale):

@@ -411,23 +411,32 @@ class CleanResult(collections.namedtuple(
     list of dicts `start`, `n`, `peak`, `threshold`: where the run's components begin in the map's
     list, how many it kept, the masked peak it started from and the threshold it ran to),
     `sidelobe` and `vis_residual` (complex [K], or [F K] with `mfs`: V minus the list's
-    visibilities, what the residual is the image of)."""
+    visibilities, what the residual is the image of).
+    `taylor`, handled the same way: None, or with `nterms` > 1 one dict per output map -- `tt`,
+    `residual_tt`, `model_tt` (each (n_t, ni, nj): the restored Taylor images, the raw Taylor
+    residual planes and the delta models), `alpha` (tt1 / tt0 where tt0 > `alpha_cut_jy`, NaN
+    elsewhere), `beta` (tt2 / tt0 - alpha (alpha - 1) / 2; None below three terms),
+    `alpha_cut_jy`, `reffreq_hz`, `hessian` and `hinv` (n_t, n_t)."""
 
-    def __new__(cls, *args, imfit=None, major=None, **kw):
+    def __new__(cls, *args, imfit=None, major=None, taylor=None, **kw):
         self = super().__new__(cls, *args, **kw)
         self.imfit = imfit
         self.major = major
+        self.taylor = taylor
         return self
 
     imfit = None
     major = None
+    taylor = None
 
     def _replace(self, **kw):
         imfit = kw.pop("imfit", self.imfit)
         major = kw.pop("major", self.major)
+        taylor = kw.pop("taylor", self.taylor)
         out = super()._replace(**kw)
         out.imfit = imfit
         out.major = major
+        out.taylor = taylor
         return out
 
 
@@ -571,6 +580,85 @@ def _major_options(major_cycles, cyclefactor, cycleniter, min_psf_fraction, max_
         return None
     return dict(major_cycles=n, cyclefactor=cf, cycleniter=cn, min_psf_fraction=lo,
                 max_psf_fraction=hi)
+
+
+# ---- multi-term MFS (K19) ----------------------------------------------------------------------------
+MTMFS_MAX_NT = 4             # RJP_MTMFS_MAX_NT
+# The largest condition number of the Taylor Hessian that `taylor_hessian_inverse` accepts.  The
+# principal solution a = Hinv R loses a factor cond(H) of the planes' accuracy: at 1e10 the
+# coefficients of a noise-free model still hold about six digits in double precision, and any
+# thermal noise is amplified by the same factor -- beyond it the band is too narrow for `nterms`.
+TAYLOR_COND_MAX = 1e10
+
+
+def taylor_weights(freqs, reffreq_hz, n):
+    """The Taylor weights of the channels `freqs` [Hz] about `reffreq_hz` -> float64 array [n, F]:
+    row q is w_f^q, w_f = (nu_f - nu_0) / nu_0 (one subtraction, one division).  Row 0 is exactly
+    1, row q is row q - 1 times w (one rounding each)."""
+    f = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
+    nu0, n = float(reffreq_hz), int(n)
+    if n < 1 or f.ndim != 1 or not (np.isfinite(nu0) and nu0 > 0.) or not np.all(np.isfinite(f)):
+        raise ValueError("taylor_weights: n >= 1, finite `freqs` and a finite `reffreq_hz` > 0")
+    w = (f - nu0) / nu0
+    out = np.ones((n, f.size))
+    for q in range(1, n):
+        out[q] = out[q - 1] * w
+    return out
+
+
+def taylor_hessian_inverse(centres):
+    """The Hessian of a multi-term MFS minor cycle and its inverse from the centre values of the
+    spectral beams, `centres` [2 n_t - 1] = B_0 .. B_{2 n_t - 2} at the centre pixel -> (H, Hinv),
+    float64 [n_t, n_t]: H[t][q] = centres[t + q] (a Hankel matrix, symmetric), Hinv its inverse,
+    symmetrised.  ValueError when H is not positive definite (a band of fewer distinct frequencies
+    than terms makes it singular) or its 2-norm condition number exceeds `TAYLOR_COND_MAX`: the
+    band is too narrow for that many terms."""
+    c = np.asarray(centres, dtype=np.float64).reshape(-1)
+    if c.size < 1 or c.size % 2 == 0 or not np.all(np.isfinite(c)):
+        raise ValueError("taylor_hessian_inverse: `centres` must be 2 n_t - 1 finite numbers")
+    n = (c.size + 1) // 2
+    H = np.array([[c[t + q] for q in range(n)] for t in range(n)])
+    try:
+        np.linalg.cholesky(H)
+    except np.linalg.LinAlgError:
+        raise ValueError("mtmfs: the Taylor Hessian is not positive definite (fewer distinct "
+                         "frequencies than terms, or beams that are not those of one band)") from None
+    cond = float(np.linalg.cond(H))
+    if not cond <= TAYLOR_COND_MAX:
+        raise ValueError("mtmfs: the Taylor Hessian's condition number %.3g exceeds %.3g: the band "
+                         "is too narrow for nterms = %d" % (cond, TAYLOR_COND_MAX, n))
+    Hinv = np.linalg.inv(H)
+    return H, 0.5 * (Hinv + Hinv.T)
+
+
+def _taylor_options(nterms, reffreq_hz, alpha_cut_jy, freqs, mfs, scales, major):
+    """`nterms`, `reffreq_hz`, `alpha_cut_jy` of `clean_image_*` -> None for one term, else a dict
+    (n_t, reffreq_hz, alpha_cut_jy, tw: `taylor_weights` with 2 n_t - 1 rows)."""
+    try:
+        n = int(nterms)
+    except (TypeError, ValueError):
+        raise ValueError("clean: `nterms` must be an integer from 1 to %d" % MTMFS_MAX_NT) from None
+    if n != nterms or not 1 <= n <= MTMFS_MAX_NT:
+        raise ValueError("clean: `nterms` must be an integer from 1 to %d" % MTMFS_MAX_NT)
+    if n == 1:
+        return None
+    if not mfs:
+        raise ValueError("clean: `nterms` > 1 needs `mfs=True` (the Taylor terms are those of one "
+                         "image of the whole band)")
+    if scales is not None:
+        raise ValueError("clean: `nterms` > 1 with `scales` (multi-scale multi-term) is not built")
+    if major is not None:
+        raise ValueError("clean: `nterms` > 1 with `major_cycles` >= 1 is not built")
+    f = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
+    if np.unique(f).size < n:
+        raise ValueError("clean: `nterms` = %d needs at least that many distinct frequencies" % n)
+    nu0 = 0.5 * (f.min() + f.max()) if reffreq_hz is None else float(reffreq_hz)
+    if not (np.isfinite(nu0) and nu0 > 0.):
+        raise ValueError("clean: `reffreq_hz` must be None or a finite frequency > 0")
+    cut = None if alpha_cut_jy is None else float(alpha_cut_jy)
+    if cut is not None and not np.isfinite(cut):
+        raise ValueError("clean: `alpha_cut_jy` must be None or a finite number")
+    return dict(n_t=n, reffreq_hz=nu0, alpha_cut_jy=cut, tw=taylor_weights(f, nu0, 2 * n - 1))
 
 
 class Imager:
@@ -740,7 +828,8 @@ class Imager:
 
     def _clean_images(self, V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
                       threshold_jy, mask, beam, psf_shape, imfit=None, weighting=None, robust=0.5,
-                      scales=None, scale_bias=None, major_cycles=0, cyclefactor=1.5, cycleniter=None,
+                      scales=None, scale_bias=None, nterms=1, reffreq_hz=None, alpha_cut_jy=None,
+                      major_cycles=0, cyclefactor=1.5, cycleniter=None,
                       min_psf_fraction=0.05, max_psf_fraction=0.8):
         """Hogbom CLEAN of the dirty images of `V` (see `JetModel.clean_image_ff`), in chunks of
         channels whose dirty images AND beams stay under `stack_bytes`.  Per chunk, on the device:
@@ -756,11 +845,16 @@ class Imager:
         the SCORE, bias x component flux.
         `major_cycles` >= 1 (with `cyclefactor`, `cycleniter`, `min_psf_fraction`,
         `max_psf_fraction`): per chunk `_major_chunk` -- minor runs alternating with residuals
-        recomputed from the visibilities -- and `CleanResult.major`; 0 is the path as it was."""
+        recomputed from the visibilities -- and `CleanResult.major`; 0 is the path as it was.
+        `nterms` > 1 (with `mfs`; `reffreq_hz`, `alpha_cut_jy`): multi-term MFS CLEAN, the one
+        chunk through `_mtmfs_chunk` -- n_t Taylor dirty images and 2 n_t - 1 spectral beams with
+        the chunk's weights, `RTEngine.mtmfs` -- and `CleanResult.taylor`; 1 is the path as it
+        was."""
         import torch
         eng = self.engine
         mj = _major_options(major_cycles, cyclefactor, cycleniter, min_psf_fraction,
                             max_psf_fraction)
+        ty = _taylor_options(nterms, reffreq_hz, alpha_cut_jy, freqs, mfs, scales, mj)
         ni, nj, cell = self._image_grid(shape, cell_as)
         pi_, pj = (2 * ni - 1, 2 * nj - 1) if psf_shape is None else (int(psf_shape[0]),
                                                                       int(psf_shape[1]))
@@ -780,7 +874,7 @@ class Imager:
         res = CleanResult(image=np.zeros((n_out, ni, nj)), residual=np.zeros((n_out, ni, nj)),
                           model=np.zeros((n_out, ni, nj)), components=[], beam=[],
                           peak_residual=np.zeros(n_out), imfit=None if fit_opts is None else [],
-                          major=None if mj is None else [])
+                          major=None if mj is None else [], taylor=None if ty is None else [])
         step = F if mfs else max(1, self.stack_bytes // ((ni * nj * 3 + pi_ * pj) * 8))
         ms = None
         if scales is not None:
@@ -831,10 +925,18 @@ class Imager:
                 big, g = psf, grow // 2
                 psf = big.reshape(M, pi_ + grow, pj + grow)[:, g:g + pi_, g:g + pj].reshape(
                     M, pi_ * pj).contiguous()
-            if beam is None:
+            spsf = centres = None
+            if ty is not None:
+                # B_0 is `psf` itself; the centres of all the spectral beams travel with the patch
+                spsf = self._taylor_stack(ones[sl], psf, ty["tw"], u_d, v_d, freqs[sl], weights,
+                                          (pi_, pj), cell_as, iw)
+            if beam is None or ty is not None:
                 ci, cj = (pi_ - 1) // 2, (pj - 1) // 2
-                patch = psf.reshape(M, pi_, pj)[:, ci - hi:ci + hi + 1, cj - hj:cj + hj + 1]
-                abc = [fit_beam(p) for p in patch.cpu().numpy()]
+                patch = (psf if spsf is None else spsf).reshape(M, -1, pi_, pj)[
+                    :, :, ci - hi:ci + hi + 1, cj - hj:cj + hj + 1].cpu().numpy()
+                centres = patch[:, :, hi, hj]
+            if beam is None:
+                abc = [fit_beam(p[0]) for p in patch]
             else:
                 abc = [beam_quadratic(beam[0], beam[1], beam[2], cell)] * M
             thr_c = float(thr[0]) if thr.size == 1 else thr[f0:f0 + M]
@@ -844,6 +946,13 @@ class Imager:
                     V[sl], u_d, v_d, freqs[sl], weights, ni, nj, cell, cell_as, mfs, iw, dirty,
                     psf if not grow else big, psf, pi_, pj, ms, abc, mk, niter, gain, thr_c, mj)
                 res.major.extend(info)
+            elif ty is not None:
+                planes = self._taylor_stack(V[sl], dirty, ty["tw"][:ty["n_t"]], u_d, v_d, freqs[sl],
+                                            weights, (ni, nj), cell_as, iw)
+                dirty, model, image, cpix, cflux, ncomp, peak, info = self._mtmfs_chunk(
+                    planes, spsf, centres, ni, nj, pi_, pj, ty, abc, mk, niter, gain, thr_c)
+                res.taylor.extend(info)
+                del planes, spsf
             elif ms is None:
                 model = torch.zeros_like(dirty)
                 cpix, cflux, ncomp, peak = eng.clean(dirty, ni, nj, psf, pi_, pj, niter, gain, thr_c,
@@ -863,7 +972,9 @@ class Imager:
             hs = cscale.cpu().numpy() if cscale is not None else None
             for m in range(M):
                 n = int(hn[m])
-                cols = [hp[m, :n] // nj, hp[m, :n] % nj, hf[m, :n]]
+                # (multi-term: hf is [M, niter, n_t], the rows are (ix, iz, c_0 .. c_{n_t - 1}))
+                cols = [hp[m, :n] // nj, hp[m, :n] % nj] + \
+                    ([hf[m, :n]] if hf.ndim == 2 else [hf[m, :n, t] for t in range(hf.shape[2])])
                 if hs is not None:
                     cols.append(ms["planes"][hs[m, :n]])          # (ix, iz, flux, scale [pixels])
                 res.components.append(np.stack(cols, axis=1).astype(np.float64)
@@ -871,6 +982,64 @@ class Imager:
                 res.beam.append(beam_from_quadratic(*abc[m], cell))
             del dirty, psf, model, image, cpix, cflux, ncomp, peak, iw
         return res
+
+    def _taylor_stack(self, V, first, tw, u_d, v_d, freqs, weights, shape, cell_as, iw):
+        """The `mfs` images of `V` [F, K] times each row of `tw` [n, F] on the grid `shape` -> device
+        [1, n, ni * nj].  Row 0 of `tw` is 1: that image is `first` [1, ni * nj], made before with
+        the same arguments; the others go through `_dirty_images` with the same weights `iw` (or
+        the same natural weights) and hence the same normaliser."""
+        import torch
+        out = [first]
+        for q in range(1, len(tw)):
+            wq = torch.from_numpy(np.ascontiguousarray(tw[q])).to(self.engine.device)
+            out.append(self._dirty_images(V * wq[:, None], u_d, v_d, freqs, weights, shape, cell_as,
+                                          True, device=True, iw=iw))
+        return torch.stack(out, dim=1).contiguous()
+
+    def _mtmfs_chunk(self, planes, spsf, centres, ni, nj, pi_, pj, ty, abc, mk, niter, gain, thr):
+        """Multi-term MFS CLEAN of one chunk: `planes` [M, n_t, ni * nj] the Taylor dirty images,
+        `spsf` [M, 2 n_t - 1, pi_ * pj] the spectral beams, `centres` [M, 2 n_t - 1] their centre
+        values on the host -> (raw R_0, tt0 delta model, tt0 image [M, ni * nj], cpix, ccoef
+        [M, niter, n_t], ncomp, peak [M] = the final max |a_0|, info: per map the dict of
+        `CleanResult.taylor`), all but `info` on the device.  tt[t] = `restore` of (cpix,
+        ccoef[..., t]) plus term t of the principal solution of the final residual planes,
+        sum_q Hinv[t][q] R_q; alpha = tt1 / tt0 where tt0 > the cut (None: 0.1 of the largest tt0),
+        NaN elsewhere; beta = tt2 / tt0 - alpha (alpha - 1) / 2 with three terms or more."""
+        import torch
+        eng = self.engine
+        M, n_t = int(planes.shape[0]), ty["n_t"]
+        hs = [taylor_hessian_inverse(c) for c in centres]
+        hinv = np.stack([h[1] for h in hs])
+        model = torch.zeros_like(planes)
+        cpix, ccoef, ncomp, peak = eng.mtmfs(planes, n_t, ni, nj, spsf, pi_, pj, hinv, niter, gain,
+                                             thr, mask=mk, model=model)
+        hd = torch.from_numpy(hinv).to(eng.device)
+        tt = []
+        for t in range(n_t):
+            ps = hd[:, t, 0, None] * planes[:, 0]
+            for q in range(1, n_t):
+                ps = ps + hd[:, t, q, None] * planes[:, q]
+            tt.append(eng.restore(cpix, ccoef[:, :, t].contiguous(), ncomp, abc, ni, nj, add=ps))
+        h_tt = torch.stack(tt, dim=1).cpu().numpy().reshape(M, n_t, ni, nj)
+        h_res = planes.cpu().numpy().reshape(M, n_t, ni, nj)
+        h_mod = model.cpu().numpy().reshape(M, n_t, ni, nj)
+        info = []
+        for m in range(M):
+            tt0 = h_tt[m, 0]
+            cut = ty["alpha_cut_jy"]
+            if cut is None:
+                top = np.nanmax(tt0) if np.isfinite(tt0).any() else np.nan
+                cut = 0.1 * float(top)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                ok = tt0 > cut
+                alpha = np.where(ok, h_tt[m, 1] / tt0, np.nan)
+                beta = np.where(ok, h_tt[m, 2] / tt0 - alpha * (alpha - 1.) / 2., np.nan) \
+                    if n_t >= 3 else None
+            info.append(dict(tt=h_tt[m], residual_tt=h_res[m], model_tt=h_mod[m], alpha=alpha,
+                             beta=beta, alpha_cut_jy=float(cut), reffreq_hz=ty["reffreq_hz"],
+                             hessian=hs[m][0], hinv=hs[m][1]))
+        return (planes[:, 0].contiguous(), model[:, 0].contiguous(), tt[0], cpix, ccoef, ncomp, peak,
+                info)
 
     def _major_chunk(self, V, u_d, v_d, freqs, weights, ni, nj, cell, cell_as, mfs, iw, dirty, beam,
                      psf, pi_, pj, ms, abc, mk, niter, gain, thr, mj):
@@ -1089,7 +1258,8 @@ class Imager:
 
     def _observe(self, maps, freqs, tracks, t_int_s, sigma_jy, sefd_jy, chanwidth_hz, seed,
                  nsigma, weights, shape, cell_as, mfs, niter, gain, threshold_jy, mask, beam,
-                 psf_shape, imfit, weighting, robust, scales=None, scale_bias=None, major_cycles=0,
+                 psf_shape, imfit, weighting, robust, scales=None, scale_bias=None, nterms=1,
+                 reffreq_hz=None, alpha_cut_jy=None, major_cycles=0,
                  cyclefactor=1.5, cycleniter=None, min_psf_fraction=0.05, max_psf_fraction=0.8):
         """`JetModel.observe_*` after the maps [F, nx * nz]: visibilities, noise, image rms, CLEAN."""
         F = len(freqs)
@@ -1129,6 +1299,7 @@ class Imager:
         res = self._clean_images(V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
                                  thr, mask, beam, psf_shape, imfit, weighting=weighting,
                                  robust=robust, scales=scales, scale_bias=scale_bias,
+                                 nterms=nterms, reffreq_hz=reffreq_hz, alpha_cut_jy=alpha_cut_jy,
                                  major_cycles=major_cycles, cyclefactor=cyclefactor,
                                  cycleniter=cycleniter, min_psf_fraction=min_psf_fraction,
                                  max_psf_fraction=max_psf_fraction)
