@@ -223,7 +223,24 @@ typedef struct rjp_fields {
    * 6 bytes x the longest lane run exceed (srt_N - 1) x 8 bytes.  Such a bin counts as read in
    * rjp_last_srt_bins(); rjp_last_srt_resid() counts them.  Not taken when the chi table and the
    * error table (128 bytes per piece and jet) exceed 80 KiB of LDS.  Both pointers 16-byte aligned.
-   * The packed state belongs to the layout's cells: rebuild it whenever they change. */
+   * The packed state belongs to the layout's cells: rebuild it whenever they change.
+   * Optional with the packed state (NULL = absent): its launch-time CODES, built by
+   * rjp_srt_codes() from the finished layout, 4 bytes per cell in the packed state's rows:
+   *   d_srt_pc [((r0 + r) / 4) * 64 + lane] = codes of rows r .. r + 3    16 bytes, r % 4 == 0
+   *   code = min(floor((ts - ts_lo) * 2^32 / (ts_hi - ts_lo)), 2^32 - 1) as a uint32, in f64 as
+   * written: ts_lo gives 0, the code is monotone in ts and saturates; rows past a lane's length
+   * and the padding hold 0.  With q = (ts_hi - ts_lo) 2^-32 a code c < 2^32 - 1 stands for the
+   * launch times ts_lo + (c - 2^-18) q <= ts < ts_lo + (c + 1 + 2^-18) q (the 2^-18 covers the
+   * f64 roundings of the encoding), 2^32 - 1 for everything from ts_lo + (2^32 - 1 - 2^-18) q on.
+   * With the codes the residual stream reads 6 bytes per cell: the table piece and xi of a cell
+   * come from its code, except where the code's interval, widened to a margin of 2 q per side plus
+   * the roundings of both evaluations, reaches a piece boundary, or the code is saturated -- such a
+   * cell (about 4 q x pieces per unit of launch time of them) is re-read from its 16-byte entry of
+   * d_srt_cells and evaluated as without the codes, so every cell gets the piece its exact launch
+   * time picks; inside a piece xi moves by <= ~1.2e-7 and the cell's term by < 2e-18 of itself.
+   * rjp_last_srt_fallbacks() counts the re-read cells.  d_srt_pts is then not read at all: it is
+   * the stream of a scan WITHOUT the codes.  16-byte aligned (and d_srt_cells with it), else the
+   * scan reads d_srt_pts.  The codes belong to the layout's cells and to ts_lo / ts_hi. */
   const void* d_srt_cells;
   const int32_t* d_srt_start;
   const double* d_srt_cum;
@@ -235,6 +252,7 @@ typedef struct rjp_fields {
   int32_t srt_N;            /* order of d_srt_mom: 16, 20 or 24 (0 = no moments) */
   const void* d_srt_pts;    /* packed launch times, pairs of rows (rjp_srt_pack) */
   const void* d_srt_pw;     /* packed 16-bit weights, eight rows per 16 bytes */
+  const void* d_srt_pc;     /* launch-time codes, four rows per 16 bytes (rjp_srt_codes) */
 } rjp_fields;
 
 /* Ejection bursts (classes.py:399-463): mdot(t)/mdot_ss = 1 + sum_b amp_rel_b *
@@ -453,9 +471,20 @@ size_t rjp_srt_packed_rows(int32_t nx, int32_t nz, int64_t total_rows);
 int64_t rjp_srt_pack(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, const int32_t* d_start,
                      const int64_t* d_rowbase, const void* d_cells, void* d_pts, void* d_pw,
                      void* stream);
+/* The launch-time codes of the packed state (rjp_fields.d_srt_pc): d_pc = R * 64 * 4 bytes for
+ * the R rows of rjp_srt_packed_rows(), 16-byte aligned, written from a layout rjp_srt_fill has
+ * built with the same fields (ts_lo / ts_hi included) and K: one coalesced pass over the layout's
+ * rows.  Returns 1, or a negative rjp_status: a bad K or fields, no launch-time range in the
+ * fields, a NULL pointer, d_cells or d_pc not 16-byte aligned.  Does not synchronise. */
+int64_t rjp_srt_codes(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, const int32_t* d_start,
+                      const int64_t* d_rowbase, const void* d_cells, void* d_pc, void* stream);
 /* The table-residual (group, jet, bin) triples of the last scan (a subset of rjp_last_srt_bins'
  * *read), or a negative rjp_status.  SYNCHRONISES the device.  For tests. */
 int64_t rjp_last_srt_resid(rjp_ctx* ctx);
+/* The cells of the last scan's residual stream that fell back from their launch-time code to
+ * their entry of d_srt_cells (0 for a scan without the codes), or a negative rjp_status.
+ * SYNCHRONISES the device.  For tests. */
+int64_t rjp_last_srt_fallbacks(rjp_ctx* ctx);
 
 /* ---- K2: per-channel map stage --------------------------------------------------------
  * Replaces the map-level arithmetic of optical_depth_ff / intensity_ff / flux_ff

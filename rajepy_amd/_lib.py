@@ -48,7 +48,8 @@ class Fields(C.Structure):
                 ("d_srt_cum", C.c_void_p), ("d_srt_rowbase", C.c_void_p),
                 ("d_srt_aux", C.c_void_p), ("h_srt_hist", C.c_void_p),
                 ("d_srt_mom", C.c_void_p), ("srt_K", C.c_int32), ("srt_N", C.c_int32),
-                ("d_srt_pts", C.c_void_p), ("d_srt_pw", C.c_void_p)]
+                ("d_srt_pts", C.c_void_p), ("d_srt_pw", C.c_void_p),
+                ("d_srt_pc", C.c_void_p)]
 
 
 class Bursts(C.Structure):
@@ -120,6 +121,8 @@ SIGNATURES = {
     "rjp_srt_packed_rows": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64]),
     "rjp_srt_pack": (C.c_int64, [_P, C.POINTER(Fields), C.c_int32, _P, _P, _P, _P, _P, _P]),
     "rjp_last_srt_resid": (C.c_int64, [_P]),
+    "rjp_srt_codes": (C.c_int64, [_P, C.POINTER(Fields), C.c_int32, _P, _P, _P, _P, _P]),
+    "rjp_last_srt_fallbacks": (C.c_int64, [_P]),
     "rjp_srt_moments": (C.c_int, [_P, C.POINTER(Fields), C.c_int32, C.c_int32, _P, _P, _P, _P,
                                   _P]),
     "rjp_ff_maps_workspace": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),

@@ -574,6 +574,70 @@ hipError_t srt_pack_launch(const rjp_fields* fl, int K, const int32_t* d_start,
   return hipGetLastError();
 }
 
+// ---- launch-time codes of the packed state (rjp_fields.d_srt_pc) ---------------------------------
+// The launch times of the same rows in the same arrangement (srt_packed_row, rows of a group
+// rounded up to 8) at 4 bytes per cell:
+//   pc[(row / 4) * 64 + lane] = the codes of rows row .. row + 3        16 bytes, row % 4 == 0
+//   code = (u32) min(floor((ts - ts_lo) * S), 2^32 - 1),   S = fl(2^32 / fl(ts_hi - ts_lo))
+// evaluated in f64 as written (S = 0 for an empty range).  ts_lo gives 0, the code is monotone in
+// ts (a difference, a product by S >= 0 and a floor are) and saturates at 2^32 - 1.  Rows past a
+// lane's length and the padding -- every row of the buffer is written -- hold code 0.
+// Decoding interval.  With q = fl(ts_hi - ts_lo) 2^-32 and u = (ts - ts_lo) / q in exact
+// arithmetic: the difference and S carry one rounding each and the product one more (four granted), so the f64 value
+// that is floored lies within 4 x 2^-53 x 2^32 (1 + 2^-50) < 2^-18 of u.  A code c < 2^32 - 1 therefore stands
+// for launch times with  c - 2^-18 <= u < c + 1 + 2^-18,  and 2^32 - 1 for every  u >= 2^32 - 1 - 2^-18
+// (ts_hi itself, and whatever rjp_srt_count's guard lets pass above it): the scan decides no cell
+// from a saturated code.  Below ts_lo the layout keeps no cell (rjp_srt_count refuses).  A scan
+// that decodes c < 2^32 - 1 to the middle, ts_lo + (c + 1/2) q, is off by at most (1/2 + 2^-18) q:
+// its margin is in ff_scan_tab.hip.  One wave per group streams the finished layout once, as srt_pack_kernel does.
+__global__ __launch_bounds__(256) void srt_codes_kernel(const rjp_d2* __restrict__ cells,
+                                                        const int32_t* __restrict__ start,
+                                                        const int64_t* __restrict__ rowbase,
+                                                        int64_t npix, int Q, double ts_lo,
+                                                        double scale, rjp_u4* __restrict__ pc) {
+  constexpr int U = 8;
+  const int lane = threadIdx.x & (kLtLanes - 1);
+  const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g * kLtLanes >= npix) return;                    // (whole waves)
+  const int64_t p = g * kLtLanes + lane;
+  const int len = p < npix ? start[(int64_t)Q * npix + p] : 0;
+  const int64_t rb = rowbase[g];
+  const int nrow = (int)(rowbase[g + 1] - rb);
+  const rjp_d2* base = cells + rb * kLtLanes + lane;
+  rjp_u4* oc = pc + (srt_packed_row(rb, g) / 4) * kLtLanes + lane;
+  for (int r = 0; r < nrow; r += U) {
+    rjp_d2 cl[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int rr = r + u < nrow ? r + u : nrow - 1;  // (never past the group's last row)
+      cl[u] = __builtin_nontemporal_load(base + (int64_t)rr * kLtLanes);
+    }
+    unsigned c[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      // (fmax first: a NaN, which no kept cell holds, would give 0)
+      const double v = __builtin_floor((cl[u].y - ts_lo) * scale);
+      c[u] = r + u < len ? (unsigned)__builtin_fmin(__builtin_fmax(v, 0.0), 4294967295.0) : 0u;
+    }
+    oc[(int64_t)(r / 4) * kLtLanes] = rjp_u4{c[0], c[1], c[2], c[3]};
+    oc[(int64_t)(r / 4 + 1) * kLtLanes] = rjp_u4{c[4], c[5], c[6], c[7]};
+  }
+  // the rest of the group's packed rows (the rounding to 8 leaves every group 8 .. 15 spare)
+  const int prow = (int)(srt_packed_row(rowbase[g + 1], g + 1) - srt_packed_row(rb, g));
+  for (int r = (nrow + 7) & ~7; r < prow; r += 4) oc[(int64_t)(r / 4) * kLtLanes] = rjp_u4{0u, 0u, 0u, 0u};
+}
+
+hipError_t srt_codes_launch(const rjp_fields* fl, int K, const int32_t* d_start,
+                            const int64_t* d_rowbase, const void* d_cells, void* d_pc,
+                            hipStream_t st) {
+  const int64_t npix = (int64_t)fl->nx * fl->nz;
+  const int64_t G = (npix + kLtLanes - 1) / kLtLanes;
+  hipLaunchKernelGGL(srt_codes_kernel, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, st,
+                     (const rjp_d2*)d_cells, d_start, d_rowbase, npix, 2 * K, fl->ts_lo,
+                     srt_code_scale(fl), (rjp_u4*)d_pc);
+  return hipGetLastError();
+}
+
 // ---- the sweep ----------------------------------------------------------------------------------
 __device__ __forceinline__ rjp_d2 lt_load(const rjp_d2* p) { return __builtin_nontemporal_load(p); }
 

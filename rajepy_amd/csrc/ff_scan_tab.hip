@@ -403,7 +403,39 @@ __device__ __forceinline__ double chi_exact(const double* bj, int nb, double tl)
 #define RJP_SRT_RESID 1          /* 0: a build without table-residual bins (what fails (b) is read cell by cell), for A/B only */
 #endif
 #ifndef RJP_SRT_RESID_BLOCKS
-#define RJP_SRT_RESID_BLOCKS 2   /* blocks of 8 packed rows (5 loads of 16 B) in flight per lane */
+#define RJP_SRT_RESID_BLOCKS 2   /* blocks of 8 packed rows (3 loads of 16 B; 5 without the codes) in flight per lane */
+#endif
+// Launch-time codes (rjp_fields.d_srt_pc, ff_lt.hip): with them attached the residual stream reads
+// a 32-bit code of the launch time instead of the f64, 6 bytes per cell instead of 10.  Inside a
+// table piece E~_i is a polynomial of degree 8 in an f32 xi, and a launch time known to a code step
+// moves xi by about two f32 roundings; only WHICH piece needs the exact time, and only for a cell
+// whose code interval reaches a piece boundary.  Such a cell falls back to its own 16-byte entry
+// of the layout's cells and runs the arithmetic of the 10-byte path, so every cell gets exactly
+// the piece it gets there.
+// The margin.  q = fl(ts_hi - ts_lo) 2^-32, B = fl(q inv_h), A = the f64 value of
+// (t_epoch - ts_lo - lo) inv_h - B / 2, and a cell of code c < 2^32 - 1 takes
+//   w_q = fma(-c, B, A)   for the 10-byte path's   w = fl(fl(fl(t_epoch - ts) - lo) inv_h).
+// In exact arithmetic w_q is the w of the middle of the code's interval, and ts lies within
+// (1/2 + 2^-18) q of it (ff_lt.hip), so the two differ by at most (1/2 + 2^-18) q inv_h.  The
+// roundings, with Tm = |t_epoch| + max(|ts_lo|, |ts_hi|) + |lo| (no intermediate of either chain
+// exceeds Tm, or Tm inv_h): w carries two differences and a product, <= 3 x 2^-53 Tm inv_h; A two
+// differences, a product and the B / 2 step, <= 4 x 2^-53 Tm inv_h; c B inherits B's rounding,
+// <= 2^-53 x 2^32 q inv_h <= 2^-52 Tm inv_h; the fma adds one more 2^-53 Tm inv_h -- ten units in
+// all, and rho = 2^-48 Tm inv_h grants thirty-two.  Hence
+//   |w - w_q| < mg = 2 B + rho    (the code's half-width four times over, plus the roundings),
+// and with f = w_q - floor(w_q) a cell is AMBIGUOUS when |f - 1/2| > 1/2 - mg, or when its code is
+// saturated (2^32 - 1 stands for ts_hi and beyond).  Otherwise floor(w_q) + mg <= w_q and
+// w_q <= floor(w_q) + 1 - mg put w strictly inside [floor(w_q), floor(w_q) + 1): floor(w) =
+// floor(w_q), and clamping both to [0, wmax] keeps the floors equal (floor and clamp are
+// monotone), so the piece is the 10-byte path's.  The test runs on the UNCLAMPED w_q: a cell far
+// outside the table is as rarely ambiguous as one inside.  f is exact for w_q >= 0 and rounds to
+// 1 just below an integer <= 0, which the test then calls ambiguous; f - 1/2 rounds by < 2^-54.
+// The expected ambiguous share of launch times spread evenly over a stretch of w is 2 mg.
+// xi of a decided cell moves by 2 |w - w_q| < (1 + 2^-17) B + 2 rho in f64, plus one f32 rounding
+// on either side; |E~| <= 2.2e-13 F on [-1, 1] gives |E~'| <= 64 x 2.2e-13 F (Markov, degree 8),
+// so a cell's term moves by < 2e-18 of itself at B = 6e-8: far below the 16-bit weight's 4.3e-16.
+#ifndef RJP_SRT_CODES
+#define RJP_SRT_CODES 1          /* 0: a build whose residual stream always reads the f64 launch times (10 bytes per cell), for A/B only */
 #endif
 constexpr int kErrNC = 9;                    // coefficients per piece (degree 8)
 constexpr int kErrNodes = 12;
@@ -586,8 +618,8 @@ struct SrtMomDev {
   const double* mom;                           // [2 K (N - 1)][P]
   const double* W;                             // [2 K][N]
   const int* ok;                               // [2 K]: 0 = read the bin, else the coefficients to sum
-  // (contracted, read, residual) (jet, bin) counts of every group, [groups][3], or null: lane 0 of
-  // a group's wave stores its own three, zeros included -- every slot of a scan is written by that
+  // (contracted, read, residual) (jet, bin) counts and the fallback cells of every group,
+  // [groups][4], or null: lane 0 of a group's wave stores its own four, zeros included -- every slot of a scan is written by that
   // scan, nothing is zeroed in front of it and no two waves share a word.  A residual bin counts
   // as read as well (its cells are read, from the packed state)
   unsigned long long* diag;
@@ -595,8 +627,12 @@ struct SrtMomDev {
   const float* E;
   const rjp_d2* pts;
   const rjp_u4* pw;
+  // the launch-time codes (null: the residual stream reads `pts`) with A, B and 1/2 - mg of
+  // "the margin" above (hm < 0: every cell falls back)
+  const rjp_u4* pc;
+  double cA, cB, hm;
 };
-constexpr int kSrtDiag = 3;
+constexpr int kSrtDiag = kSrtDiagWords;
 
 template <int U, int N>
 __global__ __launch_bounds__(kSrtBlock) __attribute__((amdgpu_waves_per_eu(4))) void ff_scan_hybrid_kernel(SrtDev s, SrtMomDev m,
@@ -622,6 +658,7 @@ __global__ __launch_bounds__(kSrtBlock) __attribute__((amdgpu_waves_per_eu(4))) 
   const double wmax = t.wmax;
   const int K = s.K;
   unsigned n_res = 0;
+  [[maybe_unused]] unsigned n_fb = 0;                  // this lane's cells that fell back to `cells`
   double racc = 0.0;                                   // sum of weight x E~ over the residual bins' cells
   auto start_at = [&](int q) { return live ? s.start[(int64_t)q * npix + p] : 0; };
   auto cum_at = [&](int q) { return live ? s.cum[(int64_t)q * npix + p] : 0.0; };
@@ -776,6 +813,81 @@ __global__ __launch_bounds__(kSrtBlock) __attribute__((amdgpu_waves_per_eu(4))) 
           const rjp_d2* pt = m.pts + (pb / 2) * RJP_WAVE + lane;
           const rjp_u4* pq = m.pw + (pb / 8) * RJP_WAVE + lane;
           constexpr int RB = RJP_SRT_RESID_BLOCKS;       // blocks of 8 rows in flight
+#if RJP_SRT_CODES
+          // with the codes: two 16-byte units of four codes and the weight unit per block of 8
+          // rows.  E~ of every cell first, from the code; then, where any lane of the wave holds
+          // an ambiguous cell of its own run ("the margin" above), those lanes redo theirs from
+          // their own entry of `cells` with the arithmetic of the loop below; then the additions
+          // into racc, in that loop's order
+          if (m.pc) {
+            const rjp_u4* pcq = m.pc + (pb / 4) * RJP_WAVE + lane;
+            for (int r = lo; r < hi; r += 8 * RB) {
+              rjp_u4 cc[RB][2];
+              rjp_u4 wq[RB];
+#pragma unroll
+              for (int k = 0; k < RB; ++k) {
+                const int rk = r + 8 * k;
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                  cc[k][u] = rjp_u4{0u, 0u, 0u, 0u};
+                  if (rk + 4 * u + 3 >= rs && rk + 4 * u < re)
+                    cc[k][u] = __builtin_nontemporal_load(pcq + (int64_t)(rk / 4 + u) * RJP_WAVE);
+                }
+                wq[k] = rjp_u4{0u, 0u, 0u, 0u};
+                if (rk + 7 >= rs && rk < re)
+                  wq[k] = __builtin_nontemporal_load(pq + (int64_t)(rk / 8) * RJP_WAVE);
+              }
+              float ev[8 * RB];
+              unsigned amb = 0;                          // bit 8 k + u: the cell falls back
+#pragma unroll
+              for (int k = 0; k < RB; ++k)
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                  const int row = r + 8 * k + u;
+                  const unsigned c = cc[k][u / 4][u % 4];
+                  const double wv = __builtin_fma(-(double)c, m.cB, m.cA);
+                  const double f = wv - __builtin_floor(wv);
+                  const bool a = (__builtin_fabs(f - 0.5) > m.hm) | (c == 0xffffffffu);
+                  amb |= (a && row >= rs && row < re) ? 1u << (8 * k + u) : 0u;
+                  const double w = __builtin_fmin(__builtin_fmax(wv, 0.0), wmax);
+                  const double kf = __builtin_floor(w);
+                  const double xi = __builtin_fma(2.0, w - kf, -1.0);
+                  const rjp_f4* ep = reinterpret_cast<const rjp_f4*>(s_err + ((int)kf + koff) * kErrStride);
+                  const rjp_f4 e0 = ep[0], e1 = ep[1];
+                  ev[8 * k + u] = srt_err_eval(e0, e1, ep[2].x, (float)xi);
+                }
+              if (__any(amb != 0u)) {                    // (rare: 2 mg of the cells)
+                n_fb += (unsigned)__builtin_popcount(amb);
+                while (amb) {
+                  const int i = __builtin_ctz(amb);
+                  amb &= amb - 1u;
+                  const rjp_d2 cl = __builtin_nontemporal_load(base + (int64_t)(r + i) * RJP_WAVE);
+                  double w = (t_epoch - cl.y - t.lo) * t.inv_h;
+                  w = __builtin_fmin(__builtin_fmax(w, 0.0), wmax);
+                  const double kf = __builtin_floor(w);
+                  const double xi = __builtin_fma(2.0, w - kf, -1.0);
+                  const rjp_f4* ep = reinterpret_cast<const rjp_f4*>(s_err + ((int)kf + koff) * kErrStride);
+                  const rjp_f4 e0 = ep[0], e1 = ep[1];
+                  const float ex = srt_err_eval(e0, e1, ep[2].x, (float)xi);
+#pragma unroll
+                  for (int u = 0; u < 8 * RB; ++u) ev[u] = u == i ? ex : ev[u];
+                }
+              }
+#pragma unroll
+              for (int k = 0; k < RB; ++k)
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                  const int row = r + 8 * k + u;
+                  const unsigned wd = wq[k][u / 2];
+                  const unsigned code = (u & 1) ? (wd >> 16) : (wd & 0xffffu);
+                  const float wf = (row >= rs && row < re) ? __uint_as_float(code << 15) : 0.0f;
+                  racc = __builtin_fma((double)wf, (double)ev[8 * k + u], racc);
+                }
+            }
+            b = e;
+            continue;
+          }
+#endif
           for (int r = lo; r < hi; r += 8 * RB) {
             rjp_d2 tt[RB][4];
             rjp_u4 wq[RB];
@@ -879,6 +991,13 @@ __global__ __launch_bounds__(kSrtBlock) __attribute__((amdgpu_waves_per_eu(4))) 
     m.diag[kSrtDiag * g + 1] = (unsigned long long)n_read;
     m.diag[kSrtDiag * g + 2] = (unsigned long long)n_res;
   }
+#if RJP_SRT_RESID && RJP_SRT_CODES
+  if (m.diag) {                                        // (uniform; all lanes are here)
+#pragma unroll
+    for (int d = RJP_WAVE / 2; d > 0; d >>= 1) n_fb += (unsigned)__shfl_xor((int)n_fb, d, RJP_WAVE);
+  }
+#endif
+  if (m.diag && lane == 0) m.diag[kSrtDiag * g + 3] = (unsigned long long)n_fb;
 #endif
   total += racc;                                       // (+0.0 without residual bins)
 #if RJP_SRT_PAIR
@@ -1150,6 +1269,7 @@ bool srt_plan(const rjp_fields* fl, const rjp_bursts* hb, double t_epoch, SrtPla
   sp.share = all > 0 ? (double)read / (double)all : 0.0;
   sp.N = fl->d_srt_mom && srt_moment_order_ok(fl->srt_N) ? fl->srt_N : 0;
   sp.packed = sp.N > 0 && fl->d_srt_pts && fl->d_srt_pw;
+  sp.codes = sp.packed && fl->d_srt_pc;
   return sp.share <= 0.9;
 }
 
@@ -1393,8 +1513,18 @@ static hipError_t chi_table_scan_on(const rjp_fields* fl, const ChiPlan& cp, con
     e = hipGetLastError();
     if (e == hipSuccess) e = tl.join();
     if (e != hipSuccess) return e;
+    // ... from the launch-time codes when they are attached: A, B and 1/2 - mg of "the margin"
+    const bool codes = RJP_SRT_CODES && resid && sp->codes && ((uintptr_t)fl->d_srt_pc % 16) == 0 &&
+                       ((uintptr_t)fl->d_srt_cells % 16) == 0;
+    const double cq = std::ldexp(fl->ts_hi - fl->ts_lo, -32);
+    const double cB = cq * cp.inv_h;
+    const double cA = (t_epoch - fl->ts_lo - cp.lo) * cp.inv_h - 0.5 * cB;
+    const double Tm = std::fabs(t_epoch) + std::max(std::fabs(fl->ts_lo), std::fabs(fl->ts_hi)) +
+                      std::fabs(cp.lo);
+    const double mg = 2.0 * cB + std::ldexp(Tm * cp.inv_h, -48);
     const SrtMomDev m{fl->d_srt_mom, d_W, d_ok, sp->diag, dE, (const rjp_d2*)fl->d_srt_pts,
-                      (const rjp_u4*)fl->d_srt_pw};
+                      (const rjp_u4*)fl->d_srt_pw, codes ? (const rjp_u4*)fl->d_srt_pc : nullptr,
+                      cA, cB, mg < 0.5 ? 0.5 - mg : -1.0};
     switch (N) {
       case 16:
         hipLaunchKernelGGL((ff_scan_hybrid_kernel<RJP_SRT_U, 16>), sgrid, dim3(kSrtBlock), hshm, st,

@@ -6,6 +6,7 @@
 // live with the kernels (RJP_SGPR_BURSTS, RJP_LT_MAX_K, RJP_SRT_MAX_K) are passed in.
 #pragma once
 #include <cmath>
+#include <cstdint>
 #include <string>
 
 #include "../../include/rjprt.h"
@@ -123,6 +124,20 @@ inline int check_layout(const rjp_fields* f, int K, const char* name, int max_K,
   if (!(f->ts_hi >= f->ts_lo) || !std::isfinite(f->ts_lo) || !std::isfinite(f->ts_hi) ||
       (f->ts_lo == 0.0 && f->ts_hi == 0.0))
     return refuse(err, w + ": fields.ts_lo / ts_hi (rjp_field_range) required");
+  return RJP_OK;
+}
+
+// What rjp_srt_codes takes, in the order it refuses: check_layout's refusals (NULL fields, storage,
+// dimensions, K, no launch-time range), a NULL pointer, a pointer read or written in 16-byte units
+// that is not 16-byte aligned.
+inline int check_srt_codes(const rjp_fields* f, int K, int max_K, const void* d_start,
+                           const void* d_rowbase, const void* d_cells, const void* d_pc,
+                           std::string& err) {
+  if (int r = check_layout(f, K, "launch-time-bucketed layout", max_K, 0, err)) return r;
+  if (!d_start || !d_rowbase || !d_cells || !d_pc)
+    return refuse(err, "rjp_srt_codes: NULL argument");
+  if (((uintptr_t)d_cells % 16) != 0 || ((uintptr_t)d_pc % 16) != 0)
+    return refuse(err, "rjp_srt_codes: d_cells and d_pc must be 16-byte aligned");
   return RJP_OK;
 }
 

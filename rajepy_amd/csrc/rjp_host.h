@@ -94,17 +94,21 @@ bool chi_table_plan(const rjp_fields* fl, const rjp_bursts* hb, const double* ep
                     int mode, bool want_em, size_t work_bytes, ChiPlan& cp);
 // the bins a single-epoch scan reads from the launch-time-bucketed layout: per jet [b0, b1) (the
 // bins that meet the jet's bursts' support at the epoch; empty for a jet without bursts)
+constexpr int kSrtDiagWords = 4;  // words per group in SrtPlan::diag
 struct SrtPlan {
   int b0[2] = {0, 0}, b1[2] = {0, 0};
   int hb[2] = {0, 0};             // the jet has bursts
   double share = 0.0;             // the map's cells in those bins / all cells in the layout
   // Chebyshev moments of the layout attached (rjp_fields.d_srt_mom): their order N, else 0.  The
   // bins in the support whose chi^2 the degree-(N-1) interpolant matches are contracted from them
-  unsigned long long* diag = nullptr;   // (contracted, read, residual) bin counters of the scan, three per group, or null
+  unsigned long long* diag = nullptr;   // (contracted, read, residual) bin and fallback-cell counters of the scan, four per group, or null
   int N = 0;
   // the packed state is attached (rjp_fields.d_srt_pts / d_srt_pw): bins that fail check (b) alone
   // may be taken as table-residual bins (ff_scan_tab.hip)
   bool packed = false;
+  // ... and with it its launch-time codes (rjp_fields.d_srt_pc): the residual stream reads 6 bytes
+  // per cell, not 10
+  bool codes = false;
 };
 // false: no layout attached, or too large a share of it would be read (the grid order is as fast)
 bool srt_plan(const rjp_fields* fl, const rjp_bursts* hb, double t_epoch, SrtPlan& sp);
@@ -231,6 +235,15 @@ inline int64_t srt_packed_rows(int64_t total_rows, int64_t groups) { return srt_
 hipError_t srt_pack_launch(const rjp_fields* fl, int K, const int32_t* d_start,
                            const int64_t* d_rowbase, const void* d_cells, void* d_pts, void* d_pw,
                            int* d_flag, hipStream_t st);
+// the launch-time codes of the packed state (rjp_fields.d_srt_pc, ff_lt.hip): 4 bytes per cell in
+// the packed state's rows, code = floor((ts - ts_lo) * srt_code_scale), saturating at 2^32 - 1
+inline double srt_code_scale(const rjp_fields* fl) {
+  const double span = fl->ts_hi - fl->ts_lo;
+  return span > 0.0 ? 4294967296.0 / span : 0.0;
+}
+hipError_t srt_codes_launch(const rjp_fields* fl, int K, const int32_t* d_start,
+                            const int64_t* d_rowbase, const void* d_cells, void* d_pc,
+                            hipStream_t st);
 hipError_t field_range_launch(const void* d_field, int64_t n, int dtype, double* d_part,
                               hipStream_t st);
 hipError_t range_check_launch(const void* d_field, int64_t n, int dtype, double lo, double hi,

@@ -58,7 +58,8 @@ struct rjp_ctx {
   int* guard = nullptr;
   unsigned long long* d_count = nullptr;      // device word of rjp_occupied_cells
   unsigned long long* d_srt_hist = nullptr;   // RJP_SRT_MAX_K * 2 counters of rjp_srt_count
-  // (contracted, read, residual) bins of rjp_last_srt_bins / rjp_last_srt_resid: three words per group of 64 sightlines, written
+  // (contracted, read, residual) bins of rjp_last_srt_bins / rjp_last_srt_resid and the fallback
+  // cells of rjp_last_srt_fallbacks: kSrtDiagWords words per group of 64 sightlines, written
   // by the group's wave with plain stores (ff_scan_hybrid_kernel); grown when a scan has more
   // groups than it holds.  `srt_diag_groups`: the groups the last such scan wrote.
   unsigned long long* d_srt_diag = nullptr;
@@ -556,7 +557,7 @@ static int ff_scan_impl(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts
         ctx->d_srt_diag = nullptr;
         ctx->srt_diag_cap = 0;
         RJP_HIP(ctx, hipMalloc((void**)&ctx->d_srt_diag,
-                               (size_t)groups * 3 * sizeof(unsigned long long)));
+                               (size_t)groups * rjp::kSrtDiagWords * sizeof(unsigned long long)));
         ctx->srt_diag_cap = groups;
       }
       ctx->srt_diag_groups = groups;
@@ -645,12 +646,12 @@ int rjp_last_srt_bins(rjp_ctx* ctx, int64_t* contracted, int64_t* read) {
   if (!contracted || !read) return fail(ctx, RJP_ERR_ARG, "rjp_last_srt_bins: NULL output");
   *contracted = *read = 0;
   if (!ctx->last_srt_mom) return RJP_OK;
-  std::vector<unsigned long long> h((size_t)ctx->srt_diag_groups * 3);
+  std::vector<unsigned long long> h((size_t)ctx->srt_diag_groups * rjp::kSrtDiagWords);
   RJP_HIP(ctx, hipDeviceSynchronize());
   RJP_HIP(ctx, hipMemcpy(h.data(), ctx->d_srt_diag, h.size() * sizeof(unsigned long long),
                          hipMemcpyDeviceToHost));
   int64_t con = 0, rd = 0;
-  for (size_t g = 0; g < h.size(); g += 3) {
+  for (size_t g = 0; g < h.size(); g += rjp::kSrtDiagWords) {
     con += (int64_t)h[g];
     rd += (int64_t)h[g + 1];
   }
@@ -798,16 +799,33 @@ int64_t rjp_srt_pack(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, const in
   return flag ? 2 : 1;
 }
 
-int64_t rjp_last_srt_resid(rjp_ctx* ctx) {
+// word `slot` of every group's counters of the last scan, summed
+static int64_t srt_diag_sum(rjp_ctx* ctx, int slot) {
   if (int r = bind(ctx)) return r;
   if (!ctx->last_srt_mom) return 0;
-  std::vector<unsigned long long> h((size_t)ctx->srt_diag_groups * 3);
+  std::vector<unsigned long long> h((size_t)ctx->srt_diag_groups * rjp::kSrtDiagWords);
   RJP_HIP(ctx, hipDeviceSynchronize());
   RJP_HIP(ctx, hipMemcpy(h.data(), ctx->d_srt_diag, h.size() * sizeof(unsigned long long),
                          hipMemcpyDeviceToHost));
   int64_t n = 0;
-  for (size_t g = 2; g < h.size(); g += 3) n += (int64_t)h[g];
+  for (size_t g = slot; g < h.size(); g += rjp::kSrtDiagWords) n += (int64_t)h[g];
   return n;
+}
+
+int64_t rjp_last_srt_resid(rjp_ctx* ctx) { return srt_diag_sum(ctx, 2); }
+
+int64_t rjp_last_srt_fallbacks(rjp_ctx* ctx) { return srt_diag_sum(ctx, 3); }
+
+int64_t rjp_srt_codes(rjp_ctx* ctx, const rjp_fields* fields, int32_t K, const int32_t* d_start,
+                      const int64_t* d_rowbase, const void* d_cells, void* d_pc, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_srt_codes(fields, K, RJP_SRT_MAX_K, d_start, d_rowbase, d_cells, d_pc, m);
+      }))
+    return r;
+  RJP_HIP(ctx, rjp::srt_codes_launch(fields, K, d_start, d_rowbase, d_cells, d_pc,
+                                     (hipStream_t)stream));
+  return 1;
 }
 
 int rjp_time_ff_scan(rjp_ctx* ctx, const rjp_fields* fields, const rjp_bursts* bursts,

@@ -218,6 +218,10 @@ class RTEngine:
         # table-residual bins; False: those bins are read cell by cell (A/B runs, tests).  Counts
         # in the srt_min_free rule like the moments.
         self.use_srt_packed = True
+        # ... and with the packed state its launch-time codes (rjp_srt_codes: 4 bytes per cell),
+        # from which the table-residual bins stream 6 bytes per cell instead of 10; False: they
+        # read the packed f64 launch times (A/B runs, tests).  Counts in the srt_min_free rule.
+        self.use_srt_codes = True
         # keep the launch-time moment maps of a model that is swept repeatedly (2.7 GB at
         # 512 x 512 sightlines): from the second long sweep on only the contraction runs
         self.cache_moments = True
@@ -473,7 +477,9 @@ class RTEngine:
         change (a stale layout is never attached: the key holds the tensors' versions).
         With `use_srt_moments` the layout's Chebyshev moments of order `srt_N` are built with it
         (rjp_srt_moments: 2 K (srt_N - 1) doubles per sightline, "mom" in the returned dict, None
-        when they would break the `srt_min_free` rule)."""
+        when they would break the `srt_min_free` rule); with `use_srt_packed` the packed state
+        ("packed"), and with `use_srt_codes` its launch-time codes (["packed"]["pc"], with
+        "pc_bytes" and "pc_build_ms"), each under the same rule."""
         torch = _torch()
         fields.srt = None
         if fields.a0 is None or fields.ts is None or fields.dtype != RJP_F64:
@@ -509,6 +515,9 @@ class RTEngine:
                   if n_mom and self.use_srt_packed else 0)
         if free - need - n_mom * 8 - n_prow * 64 * 10 < self.srt_min_free * hbm:
             n_prow = 0                          # ... or its packed state does not
+        n_crow = n_prow if self.use_srt_codes else 0
+        if free - need - n_mom * 8 - n_prow * 64 * 10 - n_crow * 64 * 4 < self.srt_min_free * hbm:
+            n_crow = 0                          # ... or its launch-time codes do not
         cells = torch.empty(max(1, total.value) * 64 * 2, dtype=torch.float64, device=self.device)
         cum = torch.empty(n_idx, dtype=torch.float64, device=self.device)
         aux = torch.empty(3 * fields.npix, dtype=torch.float64, device=self.device)
@@ -540,7 +549,18 @@ class RTEngine:
             torch.cuda.synchronize(self.device)
             if fits == 1:                       # (2: a weight outside the 16-bit format's range)
                 packed = {"pts": pts, "pw": pw, "rows": int(n_prow), "bytes": n_prow * 64 * 10,
-                          "build_ms": ev_p[0].elapsed_time(ev_p[1]), "version": cells._version}
+                          "build_ms": ev_p[0].elapsed_time(ev_p[1]), "version": cells._version,
+                          "pc": None}
+            if packed is not None and n_crow:
+                pc = torch.empty(n_crow * 64, dtype=torch.int32, device=self.device)
+                ev_c = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                ev_c[0].record()
+                self._call_tiles("rjp_srt_codes", C.byref(fs), int(K), start.data_ptr(),
+                                 rowbase.data_ptr(), cells.data_ptr(), pc.data_ptr())
+                ev_c[1].record()
+                torch.cuda.synchronize(self.device)
+                packed.update(pc=pc, pc_bytes=n_crow * 64 * 4,
+                              pc_build_ms=ev_c[0].elapsed_time(ev_c[1]))
         torch.cuda.synchronize(self.device)
         if mom is not None:
             mom_ms = ev_m[0].elapsed_time(ev_m[1])
@@ -749,6 +769,9 @@ class RTEngine:
                         packed["version"] == srt["cells"]._version):
                     fs.d_srt_pts = packed["pts"].data_ptr()
                     fs.d_srt_pw = packed["pw"].data_ptr()
+                    # (the codes share the packed state's version key)
+                    if self.use_srt_codes and packed.get("pc") is not None:
+                        fs.d_srt_pc = packed["pc"].data_ptr()
         if not self.use_moments and n_epochs != 1:
             fs.ts_lo = fs.ts_hi = 0.0
         elif self.force_moments:
@@ -938,6 +961,15 @@ class RTEngine:
         n = int(self.lib.rjp_last_srt_resid(self.ctx))
         if n < 0:
             self._check(n, self.ctx, "rjp_last_srt_resid")
+        return n
+
+    def last_srt_fallbacks(self):
+        """The cells of the last scan's table-residual bins that were re-read from the layout's
+        cells because their launch-time code could not decide the table piece
+        (rjp_last_srt_fallbacks; synchronises the device).  0 for a scan without the codes."""
+        n = int(self.lib.rjp_last_srt_fallbacks(self.ctx))
+        if n < 0:
+            self._check(n, self.ctx, "rjp_last_srt_fallbacks")
         return n
 
     def last_table_build_ms(self):

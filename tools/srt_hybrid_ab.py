@@ -3,14 +3,15 @@
 the SAME fields, bucketed layout and moments (cfg4, 512 x 4096 x 512, the example bursts) in ONE
 process, alternating, at 1.0, 0.3 and 2.6 yr (the last takes the grid order in every build).  Per
 build: the time of one rjp_ff_scan (chi table + coefficients + scan, HIP events, `--reps` launches
-per round), the (contracted, read) counters, and the worst relative difference of its map from
-the first named build's.
+per round), the (contracted, read) counters with the residual bins and fallback cells where the build has
+them, and the worst relative difference of its map from the first named build's.
 
     python tools/srt_hybrid_ab.py --out ab.json parent=rajepy_amd/librjprt_parent.so \\
         trunc=rajepy_amd/librjprt_trunc.so pair=rajepy_amd/librjprt_pair.so
 
 (the default build takes part as "new"; the variants are builds with -DRJP_SRT_PAIR=0 /
--DRJP_SRT_TRUNC=0 / -DRJP_SRT_DIAG=0 / -DRJP_SRT_OWNROWS=0, see ff_scan_tab.hip; a build without
+-DRJP_SRT_TRUNC=0 / -DRJP_SRT_DIAG=0 / -DRJP_SRT_OWNROWS=0 / -DRJP_SRT_CODES=0, see
+ff_scan_tab.hip -- three libraries on one allocation: parent=..., codes0=... and "new"; a build without
 the counters, RJP_SRT_DIAG=0, reports whatever its slots held; --no-moments times the moment-free
 ff_scan_sorted_kernel of every build instead)
 """
@@ -68,6 +69,10 @@ def main():
     fs = eng._scan_struct(fields, bursts, 1)
     res = {"shape": SHAPE, "K": fields.srt["K"], "N": int(fs.srt_N), "reps": args.reps,
            "rounds": args.rounds, "epochs": {}}
+    packed = fields.srt.get("packed") or {}
+    res["build_ms"] = {"layout": fields.srt["build_ms"], "moments": fields.srt["mom_build_ms"],
+                       "packed": packed.get("build_ms"), "codes": packed.get("pc_build_ms")}
+    res["codes_attached"] = bool(fs.d_srt_pc)
     for years in (1.0, 0.3, 2.6):
         ep = _lib.dbl_array([years * orc.YEAR])
         maps = {name: eng._f64(1, P) for name, _, _ in builds}
@@ -88,6 +93,8 @@ def main():
                          "bins_contracted_read": [int(c.value), int(r.value)]}
             if hasattr(lib, "rjp_last_srt_resid"):
                 row[name]["bins_residual"] = int(lib.rjp_last_srt_resid(ctx))
+            if hasattr(lib, "rjp_last_srt_fallbacks"):
+                row[name]["cells_fallback"] = int(lib.rjp_last_srt_fallbacks(ctx))
         for _ in range(args.rounds):
             for name, lib, ctx in builds:
                 row[name]["ms"].append(run(name, lib, ctx, args.reps))
