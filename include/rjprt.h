@@ -1197,6 +1197,84 @@ int64_t rjp_vis_noise(rjp_ctx* ctx, const double* d_vis, int32_t n_maps, int32_t
                       const double* h_sigma, const double* d_s, uint64_t seed, int64_t k0,
                       int32_t m0, double* d_out, void* stream);
 
+/* ---- K20: point and Gaussian components fitted to visibilities (uvmodelfit) -----------------------
+ * Radio astronomers measure barely resolved sources in the uv plane (CASA uvmodelfit, difmap
+ * modelfit): the data are independent, the weights thermal, no beam enters and a point source is an
+ * ordinary point of the parameter space.  CASA is not at hand, so this comment IS the definition;
+ * parity with uvmodelfit is not claimed.  This entry point fits n_comp components per map by
+ * Levenberg-Marquardt, one fused launch per iteration for the whole stack and nothing going to the
+ * host until the end.  For map m and visibility k, in float64,
+ *   a = h_su[m] * d_u[k],  b = h_sv[m] * d_v[k]      cycles per cell (the convention of rjp_vis;
+ *                                                     the ABI carries no sky convention)
+ * and per component c with theta_c = (F, x, z, sxx, sxz, szz) -- flux [the visibilities' unit],
+ * offset from the phase centre [cells; ix - (nx - 1) / 2, iz - (nz - 1) / 2 of rjp_vis] and the
+ * sky-plane covariance [cells^2]; a point source is sxx = sxz = szz = 0 --
+ *   ph = fma(a, x, b * z)                             phase in turns, |ph| < 2^30; sine and cosine
+ *                                                     of 2 pi ph to < 2e-14 / 1e-15 absolute
+ *   q  = fma(sxx, a * a, fma(2 sxz, a * b, szz * (b * b)))
+ *   e  = q * -19.739208802178716                      (-2 pi^2; one rounding)
+ *   E  = exp(e) to < 1e-14 relative, an exact 0 for e < -700
+ *   M[m][k] = sum_c (F E) (cos - i sin)               = sum_c F exp(-2 pi^2 q) exp(-2 pi i ph),
+ *                                                     added in component order
+ * This is the transform of K14's S exp(-(A dx^2 + 2 B dx dz + C dz^2)) with Sigma = (2 Q)^-1 and
+ * F = S pi / sqrt(det Q).
+ *   d_vis [n_maps][n_vis][2]  the data (READ ONLY), (re, im) as rjp_vis writes them
+ *   d_u, d_v [n_vis];  h_su, h_sv [n_maps]  HOST, finite
+ *   d_w                       NULL (all ones) or [w_maps][n_vis], w_maps 1 (shared) or n_maps
+ *   n_comp                    1 .. RJP_UVFIT_MAX_COMP;  P = 6 n_comp parameters per map
+ *   h_free [n_comp][6]        HOST uint8, non-zero = the parameter is fitted; one pattern for all
+ *                             maps; NULL = all free; at least one must be free
+ *   d_theta [n_maps][P]       the start on entry, the fit on exit (IN PLACE)
+ *   lambda0, xtol             finite and > 0;  n_iter >= 1
+ *   d_chi2 [n_maps], d_cov [n_maps][P (P + 1) / 2], d_nvis, d_niter, d_status [n_maps] (int32)
+ *   d_trace [n_maps][n_iter][3 + P]   (optional) per iteration (chi^2 of the trial, the lambda that
+ *                             proposed it, accepted 0 / 1, the trial's P parameters); rows at and
+ *                             beyond d_niter[m] are not written
+ * Visibility k of map m counts when Re V, Im V, u, v and w are finite and w > 0.  With r = V - M and
+ * J = dM / dtheta over the counting visibilities:
+ *   chi^2 = sum w |r|^2,  N = Re(J^H W J),  g = Re(J^H W r).
+ * A fixed parameter keeps its start value: its row and column of N are replaced by the identity's
+ * and its g by 0, so that its step is exactly 0.  This is how a point component is fitted (sizes
+ * fixed at 0) and how a position is held.
+ * Iteration t = 1, 2, ... evaluates one trial (the first: the start, with chi^2_cur = +inf) and
+ * decides, in this order:
+ *   1. accept iff every component of the trial is positive SEMI-definite (sxx >= 0, szz >= 0,
+ *      sxx szz >= sxz^2), its chi^2 is finite and < chi^2_cur; on accept theta_cur, chi^2_cur, N, g
+ *      become the trial's and lambda <- max(lambda / 10, 1e-12) (accepting the start leaves
+ *      lambda0); on reject lambda <- 10 lambda;
+ *   2. chi^2_cur = 0 -> status 1.  Else delta from (N + lambda diag N) delta = g by a P x P
+ *      Cholesky; a pivot that is not > 0 counts as a reject (lambda <- 10 lambda, again);
+ *      lambda > 1e12 -> status 2 (stalled);
+ *   3. max_i |delta_i| / s_i <= xtol, s = (max(|F|, 1e-300), 1, 1, t, t, t) with t = max(sxx + szz, 1)
+ *      per component -> status 1 (converged; tested on every proposed step); n_iter trials done ->
+ *      status 0; else the next trial is theta_cur + delta.
+ * status 3 (degenerate): a start that is not finite or not positive semi-definite, a first chi^2
+ * that is not finite, or 2 x (counting visibilities) < the number of free parameters; d_status[m] =
+ * 3 and NOTHING else of that map is written.  Otherwise d_theta / d_chi2 are theta_cur / chi^2_cur,
+ * d_cov the packed upper triangle (row by row) of N at theta_cur with the identity's rows for fixed
+ * parameters, NOT inverted, d_nvis the counting visibilities, d_niter the trials evaluated.  Calling
+ * again with the returned d_theta continues the fit (lambda starts over).
+ * Tiles of 1024 consecutive visibilities; every sum in a fixed order, no atomics: a repeated call
+ * gives the same bits in every output.  The workspace holds 1 + P (P + 1) / 2 + P + 1 partial sums
+ * per tile (29, 92) and 48 / 120 doubles of state per map, both double buffered.  n_iter + 1
+ * launches are enqueued back to back without a host synchronisation.
+ * RETURNS, like the K14 entry point, the number of workgroups of one iteration's launch, > 0 --
+ * n_maps x ceil(n_vis / 1024) -- or a negative RJP_ERR_*.  Everything is validated before anything
+ * is enqueued, and no output or workspace byte is touched on a refusal: RJP_ERR_ARG for a NULL ctx,
+ * d_vis, h_su, h_sv, d_u, d_v, d_theta, d_chi2, d_cov, d_nvis, d_niter or d_status; n_maps or
+ * n_vis < 1; n_comp outside 1 .. RJP_UVFIT_MAX_COMP; with d_w a w_maps that is neither 1 nor n_maps;
+ * a non-finite h_su / h_sv; no free parameter; lambda0 or xtol not finite and positive; n_iter < 1;
+ * more than 2^31 - 1 workgroups.  RJP_ERR_WORKSPACE for a d_work smaller than the workspace query
+ * (0 from it = a bad argument). */
+#define RJP_UVFIT_MAX_COMP 2
+size_t rjp_uvfit_workspace(int32_t n_maps, int32_t n_vis, int32_t n_comp);
+int64_t rjp_uvfit(rjp_ctx* ctx, const double* d_vis, int32_t n_maps, int32_t n_vis,
+                  const double* h_su, const double* h_sv, const double* d_u, const double* d_v,
+                  const double* d_w, int32_t w_maps, int32_t n_comp, const uint8_t* h_free,
+                  double* d_theta, double lambda0, double xtol, int32_t n_iter, double* d_chi2,
+                  double* d_cov, int32_t* d_nvis, int32_t* d_niter, int32_t* d_status,
+                  double* d_trace, void* d_work, size_t work_bytes, void* stream);
+
 /* ---- K4: geometry -> fields on the device --------------------------------------------
  * Replaces the lazily cached grids of JetModel (fill_factor/areas classes.py:657-669,
  * 763-764; grid_rwp 521-525; rreff 549-555; _nd 877-897; ion_fraction 915-934;

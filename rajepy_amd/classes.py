@@ -25,7 +25,7 @@ from . import fits as _fits
 from . import logger
 # the imaging chain and its result types live in imaging.py; `JetModel` is a front to it
 from .imaging import (CleanResult, Imager, Observation, UVTracks, Weighting,  # noqa: F401
-                      _split_weights, _weighting_mode, vis_scales)
+                      _split_weights, _weighting_mode, image_scales, vis_scales)
 from .maths import geometry as mgeom
 from .maths import physics as mphys
 from .maths import rrls as mrrl
@@ -127,6 +127,39 @@ def _load_params_file(py_file, checker):
     return params
 
 
+def _vis_vs_time_chunks(self, times, u_d, v_d, freq, formal):
+    """The chunks of `JetModel.visibilities_vs_time` on the device, for it and for
+    `uvmodelfit_vs_time`: yields (first epoch, epochs, V), V the complex tensor [epochs * F, K]
+    of the chunk, epoch-major.  `self`: the model."""
+    eng = self.engine
+    freqs, (ctau, cflux) = self._channel_coeffs(freq)
+    F = len(freqs)
+    su, sv = self._vis_scales(freqs)
+    step = self._vis_chunk(F)
+    if not formal:
+        step = min(step, self.SCAN_CACHE_EPOCHS)     # what one prefetch keeps resident
+    for e0 in range(0, len(times), step):
+        chunk = times[e0:e0 + step]
+        if formal:
+            maps, _ = eng.ff_formal_sweep(self.device_fields, self._rjp_bursts(), chunk,
+                                          self.gff_mode, ctau, cflux, want_maps=True,
+                                          want_totals=False)
+        else:
+            import torch
+            self.prefetch_epochs(chunk, want_em=False)
+            rows = []
+            for t in chunk:
+                if t not in self._scan_cache:    # evicted by the chunk's own new epochs
+                    self.prefetch_epochs([t], want_em=False)
+                rows.append(self._scan_cache[t][0])
+            sumA = torch.cat(rows, dim=0)
+            maps = eng.ff_maps(sumA, self._model_tavg(), ctau, cflux, want_tau=False,
+                               want_ftot=False)[1]
+        V = eng.vis(maps.reshape(len(chunk) * F, -1), self.nx, self.nz,
+                    np.tile(su, len(chunk)), np.tile(sv, len(chunk)), u_d, v_d)
+        del maps
+        yield e0, len(chunk), V
+        del V
 
 
 class JetModel:
@@ -1012,37 +1045,13 @@ class JetModel:
         `model.time`.  `formal=True`: the maps of one line-of-sight walk per chunk of epochs
         (`RTEngine.ff_formal_sweep`), else the isothermal maps (`prefetch_epochs` + `ff_maps`);
         epochs are processed in chunks whose map stack stays under 1 GiB.  Calling rank only."""
-        eng = self.engine
         times = [float(t) for t in np.atleast_1d(np.asarray(times_s, float))]
-        freqs, (ctau, cflux) = self._channel_coeffs(freq)
-        F = len(freqs)
-        su, sv = self._vis_scales(freqs)
-        u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
-        out = np.zeros((len(times), F, int(u_d.numel())), dtype=np.complex128)
-        step = self._vis_chunk(F)
-        if not formal:
-            step = min(step, self.SCAN_CACHE_EPOCHS)     # what one prefetch keeps resident
-        for e0 in range(0, len(times), step):
-            chunk = times[e0:e0 + step]
-            if formal:
-                maps, _ = eng.ff_formal_sweep(self.device_fields, self._rjp_bursts(), chunk,
-                                              self.gff_mode, ctau, cflux, want_maps=True,
-                                              want_totals=False)
-            else:
-                import torch
-                self.prefetch_epochs(chunk, want_em=False)
-                rows = []
-                for t in chunk:
-                    if t not in self._scan_cache:    # evicted by the chunk's own new epochs
-                        self.prefetch_epochs([t], want_em=False)
-                    rows.append(self._scan_cache[t][0])
-                sumA = torch.cat(rows, dim=0)
-                maps = eng.ff_maps(sumA, self._model_tavg(), ctau, cflux, want_tau=False,
-                                   want_ftot=False)[1]
-            V = eng.vis(maps.reshape(len(chunk) * F, -1), self.nx, self.nz,
-                        np.tile(su, len(chunk)), np.tile(sv, len(chunk)), u_d, v_d)
-            out[e0:e0 + len(chunk)] = V.cpu().numpy().reshape(len(chunk), F, -1)
-            del maps, V
+        freqs = self._channel_coeffs(freq)[0]
+        u_d, v_d = self.engine._device_f64(u_m), self.engine._device_f64(v_m)
+        out = np.zeros((len(times), len(freqs), int(u_d.numel())), dtype=np.complex128)
+        for e0, n, V in _vis_vs_time_chunks(self, times, u_d, v_d, freq, formal):
+            out[e0:e0 + n] = V.cpu().numpy().reshape(n, len(freqs), -1)
+            del V
         return out
 
     def visibilities_vs_time_jac(self, times_s, u_m, v_m, freq):
@@ -1326,6 +1335,75 @@ class JetModel:
         cell in arcsec, None = the model's; `box`, `theta0`, `n_iter`, `rms` as the `imfit`
         keyword of `clean_image_ff`.  Calling rank only."""
         return self._imager.imfit(images, beam, cell_as, box, theta0, n_iter, rms)
+
+    # ------------------------------------------------------------------ uvmodelfit ----
+    def uvmodelfit(self, vis, u_m, v_m, freq, weights=None, cell_as=None, comps=1, comptype=None,
+                   theta0=None, free=None, mfs=False, n_iter=60):
+        """Point / elliptical-Gaussian components fitted to the visibilities `vis` -- (F, K)
+        complex, a host array or a device tensor, such as `Observation.vis` -- in the uv plane on
+        the device (`RTEngine.uvfit`, rjp_uvfit) -> one list of component dicts per channel
+        (`engine.uvfit_results`): what radio astronomers get from CASA uvmodelfit or difmap
+        modelfit; no weighting scheme, CLEAN or beam enters.  `u_m`, `v_m` [K]: baselines in
+        metres; `freq`: the F channels; `weights`: None, [K] or [F, K], the data weights (1 /
+        sigma^2 makes the errors exact); `cell_as`: the cell the parameters are counted in, None =
+        the model's; `comps`: 1 or 2 components; `comptype`: None (Gaussians) or 'G' / 'P' per
+        component, a 'P' being a point whose sizes are held at 0; `theta0`: the start, [6 comps]
+        or [F, 6 comps] (`engine.uvfit_theta` builds a component), None = `engine.uvfit_start`
+        (one component only); `free`: None or 6 comps flags, one pattern for all channels (a
+        cleared flag holds the parameter at its start); `mfs=True`: ONE model for all channels --
+        they are concatenated into one set of F K visibilities with the baselines in cycles per
+        cell -- and one list is returned.  Nothing goes to the host before the fit ends.  Calling
+        rank only."""
+        return self._imager.uvmodelfit(vis, u_m, v_m, freq, weights, cell_as, comps, comptype,
+                                       theta0, free, mfs, n_iter)
+
+    def uvmodelfit_ff(self, u_m, v_m, freq, formal=False, weights=None, cell_as=None, comps=1,
+                      comptype=None, theta0=None, free=None, mfs=False, n_iter=60):
+        """`uvmodelfit` of the model's own noise-free `visibilities_ff` (same bits), which stay on
+        the device.  `formal`: as `flux_ff`.  Calling rank only."""
+        im, V, u_d, v_d, freqs = self._model_vis(u_m, v_m, freq, formal=formal)
+        return im.uvmodelfit(V, u_d, v_d, freqs, weights, cell_as, comps, comptype, theta0, free,
+                             mfs, n_iter)
+
+    def uvmodelfit_vs_time(self, times_s, u_m, v_m, freq, formal=False, weights=None, cell_as=None,
+                           comps=1, comptype=None, theta0=None, free=None, n_iter=60):
+        """`uvmodelfit` of `visibilities_vs_time` at every (model time, frequency) -> results
+        indexed [E][F][component]: one `RTEngine.uvfit` call per chunk of epochs, the
+        visibilities staying on the device -- the proper motion of a knot from a sweep of epochs.
+        `theta0`: None, one start [6 comps] or one per (epoch, channel) [E, F, 6 comps]; `weights`:
+        None, [K] or [F, K]; the other arguments as `uvmodelfit`.  Calling rank only."""
+        import torch
+        im = self._imager
+        eng = im.engine
+        times = [float(t) for t in np.atleast_1d(np.asarray(times_s, float))]
+        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
+        F = len(freqs)
+        nc, fr, point = im._uvfit_options(comps, comptype, theta0, free)
+        cell = im._image_grid(None, cell_as)[2]
+        su, sv = image_scales(freqs, cell)
+        u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
+        K = int(u_d.numel())
+        w_d = eng._device_f64(weights) if weights is not None else None
+        if w_d is not None and w_d.numel() not in (K, F * K):
+            raise ValueError("uvmodelfit: `weights` must be [K] or [F, K] = [%d, %d]" % (F, K))
+        th = None
+        if theta0 is not None:
+            th = theta0 if isinstance(theta0, torch.Tensor) else \
+                torch.from_numpy(np.ascontiguousarray(theta0, dtype=np.float64))
+            th = th.to(eng.device)
+            if th.dim() not in (1, 3) or (th.dim() == 3 and
+                                          tuple(th.shape[:2]) != (len(times), F)):
+                raise ValueError("uvmodelfit_vs_time: `theta0` must be [6 comps] or [E, F, 6 comps]")
+        out = []
+        for e0, n, V in _vis_vs_time_chunks(self, times, u_d, v_d, freqs, formal):
+            w_c = w_d.reshape(F, K).repeat(n, 1) if w_d is not None and w_d.numel() == F * K and \
+                F > 1 else w_d
+            th_c = th[e0:e0 + n].reshape(n * F, -1) if th is not None and th.dim() == 3 else th
+            res = im._uvfit_stack(V, np.tile(su, n), np.tile(sv, n), u_d, v_d, w_c, th_c, fr,
+                                  point, int(n_iter), cell)[0]
+            out += [res[i * F:(i + 1) * F] for i in range(n)]
+            del V
+        return out
 
     # ------------------------------------------------------------------ products ----
     FORMAL_HISTORY ="Formal solution along the line of sight, observer at iy = 0"

@@ -352,6 +352,41 @@ inline int check_gaussfit(const double* d_img, int n_maps, int nx, int nz, const
   return RJP_OK;
 }
 
+// What rjp_uvfit takes, in the order it refuses: NULL pointers, counts below 1, n_comp, w_maps, a
+// non-finite scale, no free parameter, lambda0 and xtol, n_iter, the workgroup count (1024
+// visibilities each).  (`d_w`, `h_free` and `d_trace` may be NULL; the workspace is checked where
+// the tiling lives.)
+inline int check_uvfit(const double* d_vis, int n_maps, int n_vis, const double* h_su,
+                       const double* h_sv, const double* d_u, const double* d_v, const double* d_w,
+                       int w_maps, int n_comp, const uint8_t* h_free, const double* d_theta,
+                       double lambda0, double xtol, int n_iter, const double* d_chi2,
+                       const double* d_cov, const int32_t* d_nvis, const int32_t* d_niter,
+                       const int32_t* d_status, std::string& err) {
+  if (!d_vis || !h_su || !h_sv || !d_u || !d_v || !d_theta || !d_chi2 || !d_cov || !d_nvis ||
+      !d_niter || !d_status)
+    return refuse(err, "rjp_uvfit: NULL visibilities, scales, baselines, parameters or outputs");
+  if (n_maps < 1 || n_vis < 1) return refuse(err, "rjp_uvfit: n_maps and n_vis must be positive");
+  if (n_comp < 1 || n_comp > RJP_UVFIT_MAX_COMP)
+    return refuse(err, "rjp_uvfit: n_comp must lie in 1 .. RJP_UVFIT_MAX_COMP (" +
+                           std::to_string(RJP_UVFIT_MAX_COMP) + ")");
+  if (d_w && w_maps != 1 && w_maps != n_maps)
+    return refuse(err, "rjp_uvfit: w_maps must be 1 or n_maps");
+  for (int m = 0; m < n_maps; ++m)
+    if (!std::isfinite(h_su[m]) || !std::isfinite(h_sv[m]))
+      return refuse(err, "rjp_uvfit: non-finite h_su / h_sv");
+  if (h_free) {
+    bool any = false;
+    for (int i = 0; i < 6 * n_comp; ++i) any = any || h_free[i] != 0;
+    if (!any) return refuse(err, "rjp_uvfit: no free parameter");
+  }
+  if (!(lambda0 > 0.0) || !std::isfinite(lambda0) || !(xtol > 0.0) || !std::isfinite(xtol))
+    return refuse(err, "rjp_uvfit: lambda0 and xtol must be finite and positive");
+  if (n_iter < 1) return refuse(err, "rjp_uvfit: n_iter < 1");
+  if (((int64_t)n_vis + 1023) / 1024 > (int64_t)INT32_MAX / n_maps)
+    return refuse(err, "rjp_uvfit: more than 2^31 - 1 workgroups");
+  return RJP_OK;
+}
+
 // What rjp_uv_weights takes, in the order it refuses: NULL pointers, counts below 1, a non-finite
 // scale, the mode, the robustness.  (`d_w`, `d_stats` and `d_density` may be NULL; the grids and the
 // workspace are checked where the tiling lives.)

@@ -398,6 +398,23 @@ hipError_t gaussfit_launch(const double* img, int n_maps, int nx, int nz, const 
                            int n_iter, double* chi2, double* cov, int32_t* npix, int32_t* niter,
                            int32_t* status, double* trace, void* work, hipStream_t st);
 
+// ---- uvfit.hip: Levenberg-Marquardt fits of point / Gaussian components to visibilities (K20) ----
+struct UvfitTiling {
+  int64_t tiles;                // of 1024 consecutive visibilities, per map
+  int64_t workgroups;           // n_maps x tiles: the grid of every iteration's launch
+};
+UvfitTiling uvfit_tiling(int n_maps, int64_t n_vis);
+// n_comp 1 or 2; 0: does not fit a size_t
+size_t uvfit_workspace_bytes(int n_maps, int64_t n_vis, int n_comp);
+// d_su / d_sv[n_maps]: device copies of the scales; `free_bits`: bit i set = parameter i is fitted;
+// `w`, `trace` may be nullptr; n_comp 1 or 2; n_iter + 1 launches, no host synchronisation
+hipError_t uvfit_launch(const double* vis, int n_maps, int n_vis, const double* d_su,
+                        const double* d_sv, const double* u, const double* v, const double* w,
+                        int w_maps, int n_comp, unsigned free_bits, double* theta, double lambda0,
+                        double xtol, int n_iter, double* chi2, double* cov, int32_t* nvis,
+                        int32_t* niter, int32_t* status, double* trace, void* work,
+                        hipStream_t st);
+
 // ---- uv_weight.hip: uniform and Briggs imaging weights from the (u, v) density (K15) -------------
 struct UvWeightTiling {
   int64_t cells;                // (2 (nx / 2) + 1)(2 (nz / 2) + 1), per map (INT64_MAX: beyond int64)

@@ -1375,6 +1375,43 @@ int64_t rjp_gaussfit(rjp_ctx* ctx, const double* d_img, int32_t n_maps, int32_t 
   return t.workgroups;
 }
 
+size_t rjp_uvfit_workspace(int32_t n_maps, int32_t n_vis, int32_t n_comp) {
+  if (n_maps <= 0 || n_vis <= 0 || n_comp < 1 || n_comp > RJP_UVFIT_MAX_COMP) return 0;
+  return rjp::uvfit_workspace_bytes(n_maps, n_vis, n_comp);
+}
+
+int64_t rjp_uvfit(rjp_ctx* ctx, const double* d_vis, int32_t n_maps, int32_t n_vis,
+                  const double* h_su, const double* h_sv, const double* d_u, const double* d_v,
+                  const double* d_w, int32_t w_maps, int32_t n_comp, const uint8_t* h_free,
+                  double* d_theta, double lambda0, double xtol, int32_t n_iter, double* d_chi2,
+                  double* d_cov, int32_t* d_nvis, int32_t* d_niter, int32_t* d_status,
+                  double* d_trace, void* d_work, size_t work_bytes, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_uvfit(d_vis, n_maps, n_vis, h_su, h_sv, d_u, d_v, d_w, w_maps,
+                                     n_comp, h_free, d_theta, lambda0, xtol, n_iter, d_chi2, d_cov,
+                                     d_nvis, d_niter, d_status, m);
+      }))
+    return r;
+  const rjp::UvfitTiling t = rjp::uvfit_tiling(n_maps, n_vis);
+  const size_t need = rjp::uvfit_workspace_bytes(n_maps, n_vis, n_comp);
+  if (!d_work || work_bytes < need)
+    return fail(ctx, RJP_ERR_WORKSPACE, "rjp_uvfit: workspace smaller than rjp_uvfit_workspace()");
+  unsigned free_bits = 0;
+  for (int i = 0; i < 6 * n_comp; ++i)
+    if (!h_free || h_free[i]) free_bits |= 1u << i;
+  hipStream_t st = (hipStream_t)stream;
+  const int r = staged(ctx, st, "uvfit_launch", nullptr,
+                       {{h_su, (size_t)n_maps}, {h_sv, (size_t)n_maps}},
+                       [&](double* const* d, const double*) {
+                         return rjp::uvfit_launch(d_vis, n_maps, n_vis, d[0], d[1], d_u, d_v, d_w,
+                                                  w_maps, n_comp, free_bits, d_theta, lambda0, xtol,
+                                                  n_iter, d_chi2, d_cov, d_nvis, d_niter, d_status,
+                                                  d_trace, d_work, st);
+                       });
+  return r ? r : t.workgroups;
+}
+
 size_t rjp_uv_weights_workspace(int32_t n_maps, int32_t nx, int32_t nz, int32_t n_vis) {
   if (n_maps <= 0 || nx <= 0 || nz <= 0 || n_vis <= 0) return 0;
   return rjp::uv_weights_workspace_bytes(n_maps, nx, nz, n_vis);

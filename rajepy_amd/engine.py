@@ -18,6 +18,8 @@ from .imaging import (SIDEREAL_DAY_S, AntennaConfig, Geodetic, antenna_config_pa
                       geodetic, image_rms, image_scales, observation_grid, observing_plan,
                       read_antenna_config, scale_biases, scale_kernel, taylor_hessian_inverse,
                       taylor_weights, thermal_sigma, vis_scales)
+from .imaging import (UVFIT_MAX_COMP, uvfit_components, uvfit_results, uvfit_start,  # noqa: F401
+                      uvfit_theta, uvfit_theta_from_imfit)
 
 
 def _torch():
@@ -1592,6 +1594,85 @@ class RTEngine:
             npix.data_ptr(), niter.data_ptr(), status.data_ptr(), _ptr(tr), work.data_ptr(),
             work.numel())
         out = dict(theta=theta, chi2=chi2, cov=cov, npix=npix, niter=niter, status=status)
+        if trace:
+            out["trace"] = tr
+        return out
+
+    # -- K20 -------------------------------------------------------------------------------------
+    def uvfit(self, vis, su, sv, u, v, theta0, weights=None, free=None, n_iter=60, lambda0=1e-3,
+              xtol=1e-10, trace=False):
+        """Levenberg-Marquardt fits of point / elliptical-Gaussian components to a stack of
+        visibility sets (rjp_uvfit), one fused launch per iteration for the whole stack, nothing
+        going to the host -> dict of device tensors: `theta` [M, P], P = 6 n_comp, per component
+        (F, x, z, sxx, sxz, szz) of F exp(-2 pi^2 (sxx a^2 + 2 sxz a b + szz b^2)) exp(-2 pi i (a x +
+        b z)), a = su[m] u[k], b = sv[m] v[k] in cycles per cell (flux, offset from the phase centre
+        in cells, covariance in cells^2: `uvfit_theta`); `chi2` [M]; `cov` [M, P (P + 1) / 2] (the
+        packed upper triangle of Re(J^H W J) at `theta`, identity rows for fixed parameters, NOT
+        inverted: `uvfit_results`); `nvis`, `niter`, `status` [M] int32 -- 1 converged, 0 `n_iter`
+        exhausted, 2 stalled (lambda > 1e12), 3 degenerate (start not finite or not positive
+        semi-definite, or fewer than n_free / 2 counting visibilities: `theta` keeps the start,
+        the other outputs of that map are NaN / -1) -- and with `trace` the rows [M, n_iter, 3 + P]
+        of (chi^2 of the trial, lambda, accepted, the trial), NaN beyond `niter`.  `vis`: complex128
+        [M, K] or float64 [M, K, 2] device tensor (read only); `su`, `sv` [M]; `u`, `v` [K]: host
+        arrays or device tensors; `theta0`: [M, P] or one start [P] for all, P = 6 or 12;
+        `weights`: None (all ones), [K] (shared) or [M, K]; `free`: None (all free) or P flags, one
+        pattern for all maps -- a fixed parameter keeps its start (sizes fixed at 0: a point).  A
+        visibility counts when Re V, Im V, u, v and the weight are finite and the weight > 0.  The
+        same bits on every call.  The number of workgroups per iteration is kept in
+        `last_uvfit_tiles`."""
+        torch = _torch()
+        n_iter = int(n_iter)
+        if n_iter < 1:
+            raise ValueError("uvfit: n_iter must be positive")
+        dvis = self._vis_stack("uvfit", vis)
+        M, K = int(dvis.shape[0]), int(dvis.shape[1])
+        su, sv = self._map_scales("uvfit", su, sv, M)
+        du, dv = self._device_f64(u), self._device_f64(v)
+        if du.numel() != K or dv.numel() != K:
+            raise ValueError("uvfit: u and v must have one entry per visibility (%d)" % K)
+        if not (np.isfinite(lambda0) and lambda0 > 0. and np.isfinite(xtol) and xtol > 0.):
+            raise ValueError("uvfit: `lambda0` and `xtol` must be finite and positive")
+        if isinstance(theta0, torch.Tensor):
+            theta = theta0.to(device=self.device, dtype=torch.float64)
+        else:
+            theta = torch.from_numpy(np.ascontiguousarray(theta0, dtype=np.float64)).to(self.device)
+        if theta.dim() == 1:
+            theta = theta.reshape(1, -1)
+        P = int(theta.shape[-1]) if theta.dim() == 2 else 0
+        if P < 6 or P % 6 != 0 or P // 6 > UVFIT_MAX_COMP:
+            raise ValueError("uvfit: `theta0` must hold 6 values per component, 1 to %d components"
+                             % UVFIT_MAX_COMP)
+        if theta.shape[0] == 1:
+            theta = theta.expand(M, P)
+        if theta.shape[0] != M:
+            raise ValueError("uvfit: `theta0` must be one start or one per map (%d)" % M)
+        theta = theta.contiguous().clone()
+        dw, w_maps = None, 1
+        if weights is not None:
+            dw = self._device_f64(weights)
+            if dw.numel() not in (K, M * K):
+                raise ValueError("uvfit: `weights` must be [K] or [M, K] = [%d, %d]" % (M, K))
+            w_maps = dw.numel() // K
+        hfree = None
+        if free is not None:
+            fr = np.ascontiguousarray(np.asarray(free) != 0, dtype=np.uint8).reshape(-1)
+            if fr.size != P or not fr.any():
+                raise ValueError("uvfit: `free` must hold %d flags, at least one of them set" % P)
+            hfree = (C.c_uint8 * P)(*fr)
+        T = P * (P + 1) // 2
+        chi2 = torch.full((M,), float("nan"), dtype=torch.float64, device=self.device)
+        cov = torch.full((M, T), float("nan"), dtype=torch.float64, device=self.device)
+        nvis, niter, status = (torch.full((M,), -1, dtype=torch.int32, device=self.device)
+                               for _ in range(3))
+        tr = (torch.full((M, n_iter, 3 + P), float("nan"), dtype=torch.float64, device=self.device)
+              if trace else None)
+        work = self._workspace(max(1, self.lib.rjp_uvfit_workspace(M, K, P // 6)))
+        self.last_uvfit_tiles = self._call_tiles(
+            "rjp_uvfit", dvis.data_ptr(), M, K, _lib.dbl_array(su), _lib.dbl_array(sv),
+            du.data_ptr(), dv.data_ptr(), _ptr(dw), w_maps, P // 6, hfree, theta.data_ptr(),
+            float(lambda0), float(xtol), n_iter, chi2.data_ptr(), cov.data_ptr(), nvis.data_ptr(),
+            niter.data_ptr(), status.data_ptr(), _ptr(tr), work.data_ptr(), work.numel())
+        out = dict(theta=theta, chi2=chi2, cov=cov, nvis=nvis, niter=niter, status=status)
         if trace:
             out["trace"] = tr
         return out

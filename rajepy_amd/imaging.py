@@ -399,6 +399,212 @@ def gauss_results(theta, cov, chi2, npix, beam_abc, cell_rad, rms=None, shape=No
     return out
 
 
+# -- fits in the uv plane (K20): the host side ------------------------------------------------------
+UVFIT_MAX_COMP = 2           # RJP_UVFIT_MAX_COMP
+_FWHM_PER_SIGMA = float(np.sqrt(8. * np.log(2.)))
+
+
+def uvfit_theta(flux, east_as, north_as, maj_as, min_as, pa_deg, cell_rad):
+    """(F, x, z, sxx, sxz, szz) of `RTEngine.uvfit` / rjp_uvfit for one component, under the
+    conventions of `vis_scales` and `beam_quadratic`: `flux` in the visibilities' unit; the offset
+    from the phase centre (`east_as`, `north_as`) [arcsec] with East = DECREASING ix and North =
+    +z, so x = -east / cell, z = north / cell; `maj_as`, `min_as` FWHM [arcsec] and `pa_deg` the
+    position angle of the major axis from North through East: the major axis points along
+    (dx, dz) = (-sin pa, cos pa), and Sigma = sig_maj^2 e e^T + sig_min^2 f f^T [cells^2] with
+    sig = FWHM / sqrt(8 ln 2).  `maj_as` = 0 gives a point (Sigma = 0)."""
+    cell_as = np.degrees(float(cell_rad)) * 3600.
+    if not (float(maj_as) >= 0. and float(min_as) >= 0.):
+        raise ValueError("uvfit_theta: maj_as and min_as must be >= 0")
+    if float(maj_as) == 0.:
+        return np.array([float(flux), -float(east_as) / cell_as, float(north_as) / cell_as,
+                         0., 0., 0.])
+    vM = (float(maj_as) / cell_as / _FWHM_PER_SIGMA) ** 2
+    vm = (float(min_as) / cell_as / _FWHM_PER_SIGMA) ** 2
+    s, c = np.sin(np.radians(float(pa_deg))), np.cos(np.radians(float(pa_deg)))
+    return np.array([float(flux), -float(east_as) / cell_as, float(north_as) / cell_as,
+                     vM * s * s + vm * c * c, (vm - vM) * s * c, vM * c * c + vm * s * s])
+
+
+def uvfit_components(theta, cell_rad):
+    """The inverse of `uvfit_theta` for one component (6 values) -> (flux, east_as, north_as,
+    maj_as, min_as, pa_deg), pa in (-90, 90]; a Sigma that is zero gives maj = min = pa = 0; one
+    that is not positive semi-definite raises ValueError."""
+    F, x, z, sxx, sxz, szz = (float(t) for t in np.asarray(theta, dtype=np.float64).reshape(6))
+    cell_as = np.degrees(float(cell_rad)) * 3600.
+    if sxx == 0. and sxz == 0. and szz == 0.:
+        return F, -x * cell_as, z * cell_as, 0., 0., 0.
+    lam, vec = np.linalg.eigh(np.array([[sxx, sxz], [sxz, szz]], dtype=np.float64))
+    if not lam[0] >= -1e-15 * abs(lam[1]):
+        raise ValueError("uvfit_components: Sigma is not positive semi-definite")
+    ex, ez = vec[:, 1]                              # the major axis: the larger eigenvalue
+    pa = np.degrees(np.arctan2(-ex, ez))
+    pa = pa - 180. if pa > 90. else pa + 180. if pa <= -90. else pa
+    return (F, -x * cell_as, z * cell_as, float(np.sqrt(lam[1]) * _FWHM_PER_SIGMA * cell_as),
+            float(np.sqrt(max(lam[0], 0.)) * _FWHM_PER_SIGMA * cell_as), float(pa))
+
+
+def uvfit_theta_from_imfit(fit, cell_rad):
+    """One component's (F, x, z, sxx, sxz, szz) from one dict of `gauss_results` made with
+    `shape` (it then carries 'east_as' / 'north_as'): the integrated flux 'I', the centre, and
+    the DECONVOLVED size -- or a point where the dict says 'point_source'.  `cell_rad`: the cell
+    the uv fit works in (the scales it gets come from the same cell)."""
+    if "east_as" not in fit or "north_as" not in fit:
+        raise ValueError("uvfit_theta_from_imfit: the fit carries no sky offsets (gauss_results "
+                         "needs `shape`)")
+    dec = fit.get("deconvolved")
+    if dec is None:
+        return uvfit_theta(fit["I"]["val"], fit["east_as"], fit["north_as"], 0., 0., 0., cell_rad)
+    return uvfit_theta(fit["I"]["val"], fit["east_as"], fit["north_as"], dec["maj_as"],
+                       dec["min_as"], dec["pa_deg"], cell_rad)
+
+
+def uvfit_start(vis, su, sv, u, v, weights=None):
+    """A one-component start for `RTEngine.uvfit` -> tensor [M, 6] beside `vis`, in plain torch
+    on the device, nothing going to the host.  With rho^2 = (su u)^2 + (sv v)^2 [cycles per cell,
+    squared] and the counting visibilities (finite V, u, v, weight; weight > 0):
+      * F: the zero-spacing value of the straight line (unweighted least squares) through
+        (rho^2, ln |V|) of the n = max(1, K // 10) points of smallest rho that count and have
+        |V| > 0 (the shortest baselines; their geometric-mean amplitude when they share one rho);
+      * the centre is the phase centre, x = z = 0;
+      * a circular size from the amplitude's fall-off, |V| = F exp(-2 pi^2 s rho^2): the
+        least-squares slope through the origin of ln(F / |V|) against rho^2 over the counting
+        visibilities with 0 < |V| < F, s = sum rho^2 ln(F / |V|) / (2 pi^2 sum rho^4), 0 when
+        there is none; sxx = szz = s, sxz = 0.
+    `vis`: complex128 [M, K] or float64 [M, K, 2]; `su`, `sv` [M]; `u`, `v` [K] device tensors;
+    `weights`: None, [K] or [M, K].  A map without a counting visibility gets a NaN flux, which
+    `uvfit` reports as status 3.  The sums are torch reductions: their order, and with it the last
+    bits of the start, may follow the shape of the stack.  A two-component start is the caller's."""
+    import torch
+    V = vis if vis.dtype == torch.complex128 else torch.view_as_complex(vis.contiguous())
+    M, K = int(V.shape[0]), int(V.shape[1])
+    dev = V.device
+    col = lambda s: torch.from_numpy(np.ascontiguousarray(s, dtype=np.float64).reshape(-1)) \
+        .to(dev)[:, None]
+    a, b = col(su) * u.reshape(1, K), col(sv) * v.reshape(1, K)
+    rho2 = a * a + b * b
+    ok = torch.isfinite(V.real) & torch.isfinite(V.imag) & torch.isfinite(rho2)
+    if weights is not None:
+        w = weights.reshape(-1, K)
+        ok = ok & torch.isfinite(w) & (w > 0)
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    amp = torch.where(ok, V.abs(), zero)
+    key = torch.where(ok, rho2, torch.full_like(rho2, float("inf")))
+    idx = key.topk(max(1, K // 10), dim=1, largest=False).indices
+    x, amp_n = rho2.gather(1, idx), amp.gather(1, idx)
+    sel = ok.gather(1, idx) & (amp_n > 0)
+    near = sel.to(torch.float64)
+    n_near = near.sum(dim=1)
+    y = torch.where(sel, torch.log(torch.where(sel, amp_n, 1. + zero)), zero)
+    x = torch.where(sel, x, zero)
+    mx, my = x.sum(dim=1) / n_near, y.sum(dim=1) / n_near                  # (0 / 0 = NaN: no data)
+    dx = (x - mx[:, None]) * near
+    sxx = (dx * dx).sum(dim=1)
+    slope = torch.where(sxx > 0, (dx * y).sum(dim=1) / torch.where(sxx > 0, sxx, 1. + sxx), zero)
+    flux = torch.exp(my - slope * mx)
+    live = ok & (amp > 0) & (amp < flux[:, None])
+    y = torch.where(live, torch.log(flux[:, None] / torch.where(live, amp, flux[:, None])), zero)
+    r2 = torch.where(live, rho2, zero)
+    den = (r2 * r2).sum(dim=1)
+    s = torch.where(den > 0, (r2 * y).sum(dim=1) / (2. * np.pi ** 2 * torch.where(den > 0, den, 1. + den)),
+                    zero)
+    z = torch.zeros_like(flux)
+    return torch.stack([flux, z, z, s, z, s], dim=1).contiguous()
+
+
+def uvfit_results(theta, cov, chi2, nvis, free, cell_rad, status=None, scale_errors=True):
+    """What a uv-plane model fit reports, from the outputs of `RTEngine.uvfit` (host arrays; pure
+    NumPy) -> one list of component dicts per map.  `free`: None (all free) or the P flags the fit
+    ran with; `cell_rad`: the cell in radians.  Per component:
+      * 'I' = {'val': F, 'unit': 'Jy'} and 'Ierr' = {'val', 'unit'}, as the reference stores them;
+      * 'east_as', 'north_as' (`uvfit_theta`'s convention), 'maj_as', 'min_as', 'pa_deg' (FWHM,
+        North through East), 'point_source' (Sigma = 0), 'theta' (the six raw parameters);
+      * the 1-sigma errors 'Ierr', 'east_err_as', 'north_err_as', 'sigma_err' (of sxx, sxz, szz
+        [cells^2]), 'maj_err_as', 'min_err_as', 'pa_err_deg' from C = (N_ff)^-1, N_ff the rows and
+        columns of `cov` of the free parameters -- exact for weights 1 / sigma^2 -- the last three
+        by first-order propagation through the eigen-decomposition of Sigma (None for a point or
+        fixed sizes; 'pa_err_deg' None for a circle).  A fixed parameter has the error 0.  With
+        `scale_errors` every error is multiplied by sqrt(reduced chi^2), as uvmodelfit does;
+      * 'chi2', 'reduced_chi2' = chi^2 / (2 nvis - n_free) (NaN without a degree of freedom),
+        'nvis', and 'status' where given.
+    A map whose fit is not finite (status 3) gets NaN / None entries."""
+    theta = np.asarray(theta, dtype=np.float64)
+    theta = theta.reshape(-1, theta.shape[-1])
+    M, P = theta.shape
+    nc, T = P // 6, P * (P + 1) // 2
+    if P != 6 * nc or not 1 <= nc <= UVFIT_MAX_COMP:
+        raise ValueError("uvfit_results: `theta` must hold 6 values per component")
+    cov = np.asarray(cov, dtype=np.float64).reshape(M, T)
+    chi2, nvis = np.asarray(chi2, dtype=np.float64).reshape(M), np.asarray(nvis).reshape(M)
+    fr = np.ones(P, dtype=bool) if free is None else (np.asarray(free).reshape(-1) != 0)
+    if fr.size != P:
+        raise ValueError("uvfit_results: `free` must hold %d flags" % P)
+    n_free = int(fr.sum())
+    cell_as = np.degrees(float(cell_rad)) * 3600.
+    nan = float("nan")
+    iu = np.triu_indices(P)
+    out = []
+    for m in range(M):
+        dof = 2 * int(nvis[m]) - n_free
+        red = float(chi2[m]) / dof if dof > 0 and np.isfinite(chi2[m]) else nan
+        C = None
+        if np.all(np.isfinite(cov[m])) and np.all(np.isfinite(theta[m])) and n_free > 0:
+            N = np.zeros((P, P))
+            N[iu] = cov[m]
+            N = N + np.triu(N, 1).T
+            try:
+                Cf = np.linalg.inv(N[np.ix_(fr, fr)])
+            except np.linalg.LinAlgError:
+                Cf = None
+            if Cf is not None and np.all(np.isfinite(Cf)) and np.all(np.diag(Cf) >= 0.):
+                C = np.zeros((P, P))
+                C[np.ix_(fr, fr)] = Cf
+                if scale_errors:
+                    C = C * red if np.isfinite(red) else None
+        comps = []
+        for c in range(nc):
+            th = theta[m, 6 * c:6 * c + 6]
+            d = {"I": {"val": nan, "unit": "Jy"}, "Ierr": {"val": None, "unit": "Jy"},
+                 "east_as": nan, "north_as": nan, "maj_as": nan, "min_as": nan, "pa_deg": nan,
+                 "point_source": False, "theta": th.copy(), "east_err_as": None,
+                 "north_err_as": None, "sigma_err": None, "maj_err_as": None, "min_err_as": None,
+                 "pa_err_deg": None, "chi2": float(chi2[m]), "reduced_chi2": red,
+                 "nvis": int(nvis[m])}
+            if status is not None:
+                d["status"] = int(np.asarray(status).reshape(M)[m])
+            comps.append(d)
+            if not np.all(np.isfinite(th)):
+                continue
+            try:
+                F, east, north, mj, mn, pa = uvfit_components(th, cell_rad)
+            except ValueError:
+                continue
+            d["I"]["val"], d["east_as"], d["north_as"] = F, east, north
+            d["maj_as"], d["min_as"], d["pa_deg"] = mj, mn, pa
+            d["point_source"] = bool(th[3] == 0. and th[4] == 0. and th[5] == 0.)
+            if C is None:
+                continue
+            Cc = C[6 * c:6 * c + 6, 6 * c:6 * c + 6]
+            sd = np.sqrt(np.maximum(np.diag(Cc), 0.))
+            d["Ierr"]["val"] = float(sd[0])
+            d["east_err_as"], d["north_err_as"] = float(sd[1] * cell_as), float(sd[2] * cell_as)
+            d["sigma_err"] = (float(sd[3]), float(sd[4]), float(sd[5]))
+            if d["point_source"] or not fr[6 * c + 3:6 * c + 6].any():
+                continue
+            lam, vec = np.linalg.eigh(np.array([[th[3], th[4]], [th[4], th[5]]]))
+            Cs = Cc[3:, 3:]
+            k = _FWHM_PER_SIGMA * cell_as
+            for name, l, e in (("maj_err_as", lam[1], vec[:, 1]), ("min_err_as", lam[0], vec[:, 0])):
+                if l > 0.:
+                    g = np.array([e[0] * e[0], 2. * e[0] * e[1], e[1] * e[1]])
+                    d[name] = float(k / (2. * np.sqrt(l)) * np.sqrt(max(g @ Cs @ g, 0.)))
+            if lam[1] > lam[0]:
+                e, f = vec[:, 1], vec[:, 0]
+                g = np.array([f[0] * e[0], f[0] * e[1] + f[1] * e[0], f[1] * e[1]]) / (lam[1] - lam[0])
+                d["pa_err_deg"] = float(np.degrees(np.sqrt(max(g @ Cs @ g, 0.))))
+        out.append(comps)
+    return out
+
+
 # -- result types -----------------------------------------------------------------------------------
 # what `JetModel.clean_image_ff` / `clean_image_rrl` return
 class CleanResult(collections.namedtuple(
@@ -1375,3 +1581,86 @@ class Imager:
         opts = self._imfit_options({"box": box, "theta0": theta0, "n_iter": n_iter, "rms": rms},
                                    None, ni, nj)
         return self._imfit_images(img.reshape(M, ni * nj).contiguous(), ni, nj, abc, cell, opts)
+
+    # ------------------------------------------------------------------ uvmodelfit ----
+    @staticmethod
+    def _uvfit_options(comps, comptype, theta0, free):
+        """(n_comp, the P free flags or None, the sizes to zero [P] bool) of the `comps`,
+        `comptype` and `free` of `uvmodelfit`.  `comptype`: None (all Gaussians) or one of 'G' /
+        'P' per component; a 'P' component is a point: its sizes start at 0 and stay fixed."""
+        nc = int(comps)
+        if nc != comps or not 1 <= nc <= UVFIT_MAX_COMP:
+            raise ValueError("uvmodelfit: `comps` must be an integer from 1 to %d" % UVFIT_MAX_COMP)
+        if theta0 is None and nc != 1:
+            raise ValueError("uvmodelfit: a start for more than one component is the caller's "
+                             "(`theta0`)")
+        P = 6 * nc
+        fr = None if free is None else (np.asarray(free).reshape(-1) != 0)
+        if fr is not None and fr.size != P:
+            raise ValueError("uvmodelfit: `free` must hold %d flags" % P)
+        point = np.zeros(P, dtype=bool)
+        if comptype is not None:
+            kinds = [comptype] * nc if isinstance(comptype, str) else list(comptype)
+            if len(kinds) != nc or any(k not in ("G", "P") for k in kinds):
+                raise ValueError("uvmodelfit: `comptype` must be 'G' or 'P', one per component")
+            for c, k in enumerate(kinds):
+                point[6 * c + 3:6 * c + 6] = k == "P"
+            if point.any():
+                fr = (np.ones(P, dtype=bool) if fr is None else fr) & ~point
+        if fr is not None and not fr.any():
+            raise ValueError("uvmodelfit: at least one parameter must be free")
+        return nc, fr, point
+
+    def _uvfit_stack(self, V, su, sv, u_d, v_d, w_d, theta0, fr, point, n_iter, cell):
+        """One `RTEngine.uvfit` call on the device stack `V` [M, K] -> (`uvfit_results` lists, the
+        device outputs).  `theta0`: None (`uvfit_start`), or a start as `RTEngine.uvfit` takes it."""
+        import torch
+        eng = self.engine
+        if theta0 is None:
+            theta0 = uvfit_start(V, su, sv, u_d, v_d, w_d)
+        elif not isinstance(theta0, torch.Tensor):
+            theta0 = torch.from_numpy(np.ascontiguousarray(theta0, dtype=np.float64)).to(eng.device)
+        if point.any():
+            theta0 = theta0.clone()
+            theta0[..., torch.from_numpy(point).to(theta0.device)] = 0.
+        fit = eng.uvfit(V, su, sv, u_d, v_d, theta0, weights=w_d, free=fr, n_iter=n_iter)
+        host = {k: t.cpu().numpy() for k, t in fit.items()}
+        return uvfit_results(host["theta"], host["cov"], host["chi2"], host["nvis"], fr, cell,
+                             status=host["status"]), fit
+
+    def uvmodelfit(self, vis, u_m, v_m, freq, weights=None, cell_as=None, comps=1, comptype=None,
+                   theta0=None, free=None, mfs=False, n_iter=60):
+        """See `JetModel.uvmodelfit`."""
+        import torch
+        eng = self.engine
+        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
+        nc, fr, point = self._uvfit_options(comps, comptype, theta0, free)
+        _, _, cell = self._image_grid(None, cell_as)
+        if isinstance(vis, torch.Tensor):
+            V = vis.to(device=eng.device)
+            V = V if V.dtype == torch.complex128 else torch.view_as_complex(
+                V.to(torch.float64).contiguous())
+        else:
+            V = torch.from_numpy(np.ascontiguousarray(vis, dtype=np.complex128)).to(eng.device)
+        if V.dim() == 1:
+            V = V.unsqueeze(0)
+        F = len(freqs)
+        if V.dim() != 2 or int(V.shape[0]) != F:
+            raise ValueError("uvmodelfit: `vis` must be (F, K) with one row per frequency (%d)" % F)
+        K = int(V.shape[1])
+        u_d, v_d = eng._device_f64(u_m), eng._device_f64(v_m)
+        if u_d.numel() != K or v_d.numel() != K:
+            raise ValueError("uvmodelfit: u and v must have one entry per baseline (%d)" % K)
+        w_d = eng._device_f64(weights) if weights is not None else None
+        if w_d is not None and w_d.numel() not in (K, F * K):
+            raise ValueError("uvmodelfit: `weights` must be [K] or [F, K] = [%d, %d]" % (F, K))
+        su, sv = image_scales(freqs, cell)
+        if mfs:
+            # one map of F K points, baselines in cycles per cell, unit scales
+            # (weights [K] are repeated per channel; [F, K] are already in that order)
+            shared = w_d is not None and w_d.numel() == K
+            u_d, v_d, w_rep = _mfs_points(eng, u_d, v_d, su, sv, w_d if shared else None)
+            w_d = w_rep if shared else w_d
+            V, su, sv = V.reshape(1, F * K), [1.0], [1.0]
+        return self._uvfit_stack(V.contiguous(), su, sv, u_d, v_d, w_d, theta0, fr, point,
+                                 int(n_iter), cell)[0]
