@@ -1275,6 +1275,104 @@ int64_t rjp_uvfit(rjp_ctx* ctx, const double* d_vis, int32_t n_maps, int32_t n_v
                   double* d_cov, int32_t* d_nvis, int32_t* d_niter, int32_t* d_status,
                   double* d_trace, void* d_work, size_t work_bytes, void* stream);
 
+/* ---- K21: moment maps and per-sightline line fits of a cube (immoments, specfit) -----------------
+ * What an astronomer wants of a recombination-line cube: the integrated line flux, the velocity
+ * field, the line width, and a line profile fitted per sightline (CASA immoments and specfit, the
+ * third fitting task after imfit = K14 and uvmodelfit = K20).  CASA is not at hand, so this
+ * comment IS the definition; parity is not claimed.  Shared by both entry points:
+ *   d_cube [n_chan][n_pix]    float64 channel planes (READ ONLY): the memory of a (F, nx, nz)
+ *                             stack; 8-byte alignment suffices (an odd n_pix puts every other
+ *                             plane 8 bytes off a 16-byte boundary)
+ *   h_x [n_chan]              HOST, the spectral axis: finite, any unit, any order, need not be
+ *                             uniform;  x_ref: a finite origin (the mid-channel, say)
+ *   n_chan                    1 .. RJP_SPECFIT_MAX_CHAN
+ *   d_mask [n_pix]            (optional) uint8, non-zero = the pixel is live; a masked pixel is a
+ *                             pixel without counted channels
+ * One lane per pixel walks the channels in ascending order; every sum is a chain in channel order
+ * (from +0.0), no atomics, no cross-lane reduction, no workspace: the bits of a pixel's outputs are
+ * a function of its spectrum and the tables alone -- not of n_pix, of where the pixel lies or of its
+ * neighbours -- and the same on every call.
+ * BOTH RETURN the number of workgroups enqueued, ceil(n_pix / 64) > 0, or a negative RJP_ERR_*.
+ * Everything is validated before anything is enqueued, and no output byte is touched on a refusal.
+ *
+ * rjp_cube_moments.  h_dx [n_chan] HOST, finite and >= 0: the channel widths; clip finite, >= 0.
+ * Channel c of pixel p counts when y = d_cube[c][p] is finite and |y| >= clip.  Pass 1 over the
+ * counted channels:
+ *   m0 = fma(y, dx_c, m0);  s1 = fma(y * dx_c, x_c - x_ref, s1);  the count;
+ *   the peak = the largest y, on a tie the lowest channel (y > peak, from -inf), ipeak its channel
+ * then m1 = x_ref + s1 / m0, and pass 2 (same launch, same lane, same channels):
+ *   s2 = fma(y * dx_c, (x_c - m1) * (x_c - m1), s2);  m2 = sqrt(s2 / m0), NaN for s2 / m0 < 0
+ *   (emission and absorption mixed).
+ * No counted channel (a masked pixel included) or m0 == 0: m0 = +0.0, m1 = m2 = peak = NaN,
+ * ipeak = -1.
+ *   d_mom [4][n_pix]          m0, m1, m2, peak
+ *   d_ipeak, d_count [n_pix]  int32, either may be NULL
+ * RJP_ERR_ARG for a NULL ctx, d_cube, h_x, h_dx or d_mom; n_pix or n_chan < 1; n_chan above the
+ * limit; a non-finite h_x; an h_dx that is negative or not finite; a non-finite x_ref; a clip that
+ * is negative or not finite; more than 2^31 - 1 workgroups.
+ *
+ * rjp_specfit.  Per pixel, n_comp Gaussians plus a linear baseline,
+ *   y(x) = sum_c A_c exp(-(x - x0_c)^2 / (2 s_c^2)) + b0 + b1 (x - x_ref),
+ * P = 3 n_comp + 2 parameters, theta = (A_0, x0_0, s_0, [A_1, x0_1, s_1,] b0, b1).  Per counted
+ * channel and component, in float64:
+ *   d = x_c - x0;  z = d / s (the one division of a channel);  e = -0.5 * (z * z)
+ *   E = exp(e) to < 1e-14 relative, an exact 0 for e < -700;  the component is A * E
+ *   model = the components added in order, then + fma(b1, x_c - x_ref, b0)
+ *   Jacobian: dA = E;  dx0 = ((A * E) * z) * r, r = 1 / s rounded once per trial;
+ *             ds = dx0 * z;  db0 = 1;  db1 = x_c - x_ref
+ *   h_w [n_chan]              HOST weights (1 / sigma_c^2; 0 = ignore the channel), finite and
+ *                             >= 0; NULL = all ones
+ *   n_comp                    1 .. RJP_SPECFIT_MAX_COMP
+ *   h_free [P]                HOST uint8, non-zero = the parameter is fitted; one pattern for all
+ *                             pixels; NULL = all free; at least one must be free.  b0 = b1 = 0
+ *                             held: the fit of a continuum-subtracted cube
+ *   d_theta [P][n_pix]        parameter planes: the start on entry, the fit on exit (IN PLACE)
+ *   lambda0, xtol             finite and > 0;  n_iter >= 1
+ *   d_chi2 [n_pix], d_cov [P (P + 1) / 2][n_pix], d_nchan, d_niter, d_status [n_pix] (int32)
+ *   d_trace [n_pix][n_iter][3 + P]   (optional) per iteration (chi^2 of the trial, the lambda that
+ *                             proposed it, accepted 0 / 1, the trial's P parameters); rows at and
+ *                             beyond d_niter[p] are not written
+ * Channel c counts when y is finite and w_c > 0.  With r = y - model over the counted channels,
+ *   chi^2 = sum w r^2,  N = J^T W J,  g = J^T W r,
+ * accumulated per channel as fma(w * r, r, .), fma(w * J_i, J_j, .) (i <= j) and fma(w * J_i, r, .).
+ * A fixed parameter keeps its start value: its row and column of N are replaced by the identity's
+ * and its g by 0, so that its step is exactly 0.
+ * The iteration is rjp_uvfit's (K20), word for word: iteration t = 1, 2, ... evaluates one trial
+ * (the first: the start, with chi^2_cur = +inf) and decides, in this order:
+ *   1. accept iff every s_c of the trial is finite and > 0, its chi^2 is finite and < chi^2_cur; on
+ *      accept theta_cur, chi^2_cur, N, g become the trial's and lambda <- max(lambda / 10, 1e-12)
+ *      (accepting the start leaves lambda0); on reject lambda <- 10 lambda;
+ *   2. chi^2_cur = 0 -> status 1.  Else delta from (N + lambda diag N) delta = g by a P x P
+ *      Cholesky; a pivot that is not > 0 counts as a reject (lambda <- 10 lambda, again);
+ *      lambda > 1e12 -> status 2 (stalled);
+ *   3. max_i |delta_i| / s_i <= xtol, s = (max(|A|, 1e-300), max(s, 1e-300), max(s, 1e-300)) per
+ *      component and max(|b0|, 1e-300), max(|b1|, 1e-300), at theta_cur -> status 1 (converged;
+ *      tested on every proposed step); n_iter trials done -> status 0; else the next trial is
+ *      theta_cur + delta.
+ * status 3 (degenerate): a masked pixel, a start that is not finite or has an s_c <= 0, a first
+ * chi^2 that is not finite, or fewer counted channels than free parameters; d_status[p] = 3 and
+ * NOTHING else of that pixel is written.  Otherwise d_theta / d_chi2 are theta_cur / chi^2_cur,
+ * d_cov the packed upper triangle (row by row) of N at theta_cur with the identity's rows for fixed
+ * parameters, NOT inverted, d_nchan the counted channels, d_niter the trials evaluated.  Calling
+ * again with the returned d_theta continues the fit (lambda starts over).
+ * The whole fit of a pixel runs in ONE launch: a lane re-reads its spectrum once per trial, keeps
+ * chi^2, N and g in registers, and idles once finished; a wave leaves with its last lane.
+ * RJP_ERR_ARG for a NULL ctx, d_cube, h_x, d_theta, d_chi2, d_cov, d_nchan, d_niter or d_status;
+ * n_pix or n_chan < 1; n_chan above the limit; n_comp outside 1 .. RJP_SPECFIT_MAX_COMP; a
+ * non-finite h_x or x_ref; an h_w that is negative or not finite; no free parameter; lambda0 or
+ * xtol not finite and positive; n_iter < 1; more than 2^31 - 1 workgroups. */
+#define RJP_SPECFIT_MAX_CHAN 4096
+#define RJP_SPECFIT_MAX_COMP 2
+int64_t rjp_cube_moments(rjp_ctx* ctx, const double* d_cube, int64_t n_pix, int32_t n_chan,
+                         const double* h_x, const double* h_dx, double x_ref, double clip,
+                         const uint8_t* d_mask, double* d_mom, int32_t* d_ipeak, int32_t* d_count,
+                         void* stream);
+int64_t rjp_specfit(rjp_ctx* ctx, const double* d_cube, int64_t n_pix, int32_t n_chan,
+                    const double* h_x, double x_ref, const double* h_w, const uint8_t* d_mask,
+                    int32_t n_comp, const uint8_t* h_free, double* d_theta, double lambda0,
+                    double xtol, int32_t n_iter, double* d_chi2, double* d_cov, int32_t* d_nchan,
+                    int32_t* d_niter, int32_t* d_status, double* d_trace, void* stream);
+
 /* ---- K4: geometry -> fields on the device --------------------------------------------
  * Replaces the lazily cached grids of JetModel (fill_factor/areas classes.py:657-669,
  * 763-764; grid_rwp 521-525; rreff 549-555; _nd 877-897; ion_fraction 915-934;

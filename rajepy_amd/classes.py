@@ -26,6 +26,7 @@ from . import logger
 # the imaging chain and its result types live in imaging.py; `JetModel` is a front to it
 from .imaging import (CleanResult, Imager, Observation, UVTracks, Weighting,  # noqa: F401
                       _split_weights, _weighting_mode, image_scales, vis_scales)
+from .spectra import Spectra, velocity_axis
 from .maths import geometry as mgeom
 from .maths import physics as mphys
 from .maths import rrls as mrrl
@@ -1404,6 +1405,59 @@ class JetModel:
             out += [res[i * F:(i + 1) * F] for i in range(n)]
             del V
         return out
+
+    # ------------------------------------------------------------------ spectral axis ----
+    def _rrl_velocity_axis(self, rrl, freq):
+        element, n, dn = mrrl.rrl_parser(rrl)
+        return velocity_axis(freq, mrrl.rrl_nu_0(element, n, dn))
+
+    def moments(self, cube, x, dx=None, clip=0., mask=None):
+        """Moment maps of any line cube `cube` -- (F, ni, nj), a host array or a device tensor,
+        such as `clean_image_rrl(...).image` -- along its axis `x` [F] on the device
+        (`RTEngine.cube_moments`, rjp_cube_moments) -> dict of device tensors (ni, nj): 'm0' (the
+        integrated line, sum y dx), 'm1' (the intensity-weighted axis value: the velocity field),
+        'm2' (the intensity-weighted dispersion: the line width), 'peak', 'ipeak', 'count' -- what
+        radio astronomers get from CASA immoments.  `dx`: the channel widths, None = half the
+        distance between the neighbours (`engine.velocity_axis`); `clip`: only channels with |y|
+        >= clip count; `mask`: None or (ni, nj), non-zero = live.  Calling rank only."""
+        return Spectra(self.engine).moments(cube, x, dx, clip, mask)
+
+    def specfit(self, cube, x, weights=None, comps=1, theta0=None, free=None, n_iter=40,
+                mask=None, scale_errors=True):
+        """One or two Gaussians plus a linear baseline fitted to every sightline of any line cube
+        (as `moments`) on the device (`RTEngine.specfit`, rjp_specfit) -> dict of device tensors
+        (ni, nj) (`engine.specfit_results`: 'peak', 'centre', 'sigma', 'fwhm', 'integral' and
+        their 'e_*' errors per component, 'b0', 'b1', 'chi2', 'reduced_chi2', 'nchan', 'status',
+        'niter') -- what radio astronomers get from CASA specfit.  `weights`: None or [F], 1 /
+        sigma^2 per channel (for `sigma` per channel pass `sigma ** -2` and scale_errors=False);
+        `comps`: 1 or 2; `theta0`: the start, [P] or [P, ni * nj], P = 3 comps + 2, None = from the
+        moments (`engine.specfit_start`, one component only); `free`: None or P flags, one pattern
+        for all pixels.  Calling rank only."""
+        return Spectra(self.engine).specfit(cube, x, weights, comps, theta0, free, n_iter, mask,
+                                            scale_errors)
+
+    def moments_rrl(self, rrl, freq, contsub=True, formal=False, clip_jy=0.):
+        """`moments` of the model's own `flux_rrl` cube (same arguments), which stays on the
+        device, along the radio velocity axis of the line [km/s] (`engine.velocity_axis` about
+        `maths.rrls.rrl_nu_0`): 'm0' in Jy km/s per pixel, 'm1' and 'm2' in km/s.  Calling rank
+        only."""
+        v, dv = self._rrl_velocity_axis(rrl, freq)
+        cube = self._flux_maps(np.atleast_1d(np.asarray(freq, dtype=np.float64)), rrl=rrl,
+                               contsub=contsub, formal=formal)
+        return Spectra(self.engine).moments(cube.reshape(len(v), self.nx, self.nz), v, dv, clip_jy)
+
+    def specfit_rrl(self, rrl, freq, contsub=True, formal=False, weights=None, comps=1,
+                    theta0=None, free=None, n_iter=40):
+        """`specfit` of the model's own `flux_rrl` cube (same arguments), which stays on the
+        device, along the radio velocity axis of the line [km/s].  With contsub=True and
+        free=None the baseline is held at 0.  Calling rank only."""
+        v, _ = self._rrl_velocity_axis(rrl, freq)
+        cube = self._flux_maps(np.atleast_1d(np.asarray(freq, dtype=np.float64)), rrl=rrl,
+                               contsub=contsub, formal=formal)
+        if free is None and contsub:
+            free = [1] * (3 * int(comps)) + [0, 0]
+        return Spectra(self.engine).specfit(cube.reshape(len(v), self.nx, self.nz), v, weights,
+                                            comps, theta0, free, n_iter)
 
     # ------------------------------------------------------------------ products ----
     FORMAL_HISTORY ="Formal solution along the line of sight, observer at iy = 0"

@@ -387,6 +387,69 @@ inline int check_uvfit(const double* d_vis, int n_maps, int n_vis, const double*
   return RJP_OK;
 }
 
+// What rjp_cube_moments takes, in the order it refuses: NULL pointers, sizes below 1, the channel
+// limit, the axis, the widths, x_ref, clip, the workgroup count (64 pixels each).  (`d_mask`,
+// `d_ipeak` and `d_count` may be NULL.)
+inline int check_cube_moments(const double* d_cube, int64_t n_pix, int n_chan, const double* h_x,
+                              const double* h_dx, double x_ref, double clip, const double* d_mom,
+                              std::string& err) {
+  if (!d_cube || !h_x || !h_dx || !d_mom)
+    return refuse(err, "rjp_cube_moments: NULL cube, axis, widths or output");
+  if (n_pix < 1 || n_chan < 1)
+    return refuse(err, "rjp_cube_moments: n_pix and n_chan must be positive");
+  if (n_chan > RJP_SPECFIT_MAX_CHAN)
+    return refuse(err, "rjp_cube_moments: n_chan exceeds RJP_SPECFIT_MAX_CHAN (" +
+                           std::to_string(RJP_SPECFIT_MAX_CHAN) + ")");
+  for (int c = 0; c < n_chan; ++c)
+    if (!std::isfinite(h_x[c])) return refuse(err, "rjp_cube_moments: non-finite h_x");
+  for (int c = 0; c < n_chan; ++c)
+    if (!(h_dx[c] >= 0.0) || !std::isfinite(h_dx[c]))
+      return refuse(err, "rjp_cube_moments: negative or non-finite h_dx");
+  if (!std::isfinite(x_ref)) return refuse(err, "rjp_cube_moments: non-finite x_ref");
+  if (!(clip >= 0.0) || !std::isfinite(clip))
+    return refuse(err, "rjp_cube_moments: clip must be finite and >= 0");
+  if ((n_pix + 63) / 64 > (int64_t)INT32_MAX)
+    return refuse(err, "rjp_cube_moments: more than 2^31 - 1 workgroups");
+  return RJP_OK;
+}
+
+// What rjp_specfit takes, in the order it refuses: NULL pointers, sizes below 1, the channel limit,
+// n_comp, the axis, x_ref, the weights, no free parameter, lambda0 and xtol, n_iter, the workgroup
+// count (64 pixels each).  (`h_w`, `h_free`, `d_mask` and `d_trace` may be NULL.)
+inline int check_specfit(const double* d_cube, int64_t n_pix, int n_chan, const double* h_x,
+                         double x_ref, const double* h_w, int n_comp, const uint8_t* h_free,
+                         const double* d_theta, double lambda0, double xtol, int n_iter,
+                         const double* d_chi2, const double* d_cov, const int32_t* d_nchan,
+                         const int32_t* d_niter, const int32_t* d_status, std::string& err) {
+  if (!d_cube || !h_x || !d_theta || !d_chi2 || !d_cov || !d_nchan || !d_niter || !d_status)
+    return refuse(err, "rjp_specfit: NULL cube, axis, parameters or outputs");
+  if (n_pix < 1 || n_chan < 1) return refuse(err, "rjp_specfit: n_pix and n_chan must be positive");
+  if (n_chan > RJP_SPECFIT_MAX_CHAN)
+    return refuse(err, "rjp_specfit: n_chan exceeds RJP_SPECFIT_MAX_CHAN (" +
+                           std::to_string(RJP_SPECFIT_MAX_CHAN) + ")");
+  if (n_comp < 1 || n_comp > RJP_SPECFIT_MAX_COMP)
+    return refuse(err, "rjp_specfit: n_comp must lie in 1 .. RJP_SPECFIT_MAX_COMP (" +
+                           std::to_string(RJP_SPECFIT_MAX_COMP) + ")");
+  for (int c = 0; c < n_chan; ++c)
+    if (!std::isfinite(h_x[c])) return refuse(err, "rjp_specfit: non-finite h_x");
+  if (!std::isfinite(x_ref)) return refuse(err, "rjp_specfit: non-finite x_ref");
+  if (h_w)
+    for (int c = 0; c < n_chan; ++c)
+      if (!(h_w[c] >= 0.0) || !std::isfinite(h_w[c]))
+        return refuse(err, "rjp_specfit: negative or non-finite h_w");
+  if (h_free) {
+    bool any = false;
+    for (int i = 0; i < 3 * n_comp + 2; ++i) any = any || h_free[i] != 0;
+    if (!any) return refuse(err, "rjp_specfit: no free parameter");
+  }
+  if (!(lambda0 > 0.0) || !std::isfinite(lambda0) || !(xtol > 0.0) || !std::isfinite(xtol))
+    return refuse(err, "rjp_specfit: lambda0 and xtol must be finite and positive");
+  if (n_iter < 1) return refuse(err, "rjp_specfit: n_iter < 1");
+  if ((n_pix + 63) / 64 > (int64_t)INT32_MAX)
+    return refuse(err, "rjp_specfit: more than 2^31 - 1 workgroups");
+  return RJP_OK;
+}
+
 // What rjp_uv_weights takes, in the order it refuses: NULL pointers, counts below 1, a non-finite
 // scale, the mode, the robustness.  (`d_w`, `d_stats` and `d_density` may be NULL; the grids and the
 // workspace are checked where the tiling lives.)

@@ -415,6 +415,21 @@ hipError_t uvfit_launch(const double* vis, int n_maps, int n_vis, const double* 
                         int32_t* niter, int32_t* status, double* trace, void* work,
                         hipStream_t st);
 
+// ---- specfit.hip: moment maps and per-sightline Gaussian fits of a line cube (K21) ---------------
+// workgroups of 64 pixels, one lane per pixel: the grid of both launches
+int64_t specfit_workgroups(int64_t n_pix);
+// d_x, d_dx [n_chan]: device copies of the tables; `mask`, `ipeak`, `count` may be nullptr
+hipError_t cube_moments_launch(const double* cube, int64_t n_pix, int n_chan, const double* d_x,
+                               const double* d_dx, double x_ref, double clip, const uint8_t* mask,
+                               double* mom, int32_t* ipeak, int32_t* count, hipStream_t st);
+// d_w (nullptr: all ones), `mask`, `trace` may be nullptr; n_comp 1 or 2; `free_bits`: bit i set =
+// parameter i is fitted; ONE launch, no host synchronisation
+hipError_t specfit_launch(const double* cube, int64_t n_pix, int n_chan, const double* d_x,
+                          const double* d_w, double x_ref, const uint8_t* mask, int n_comp,
+                          unsigned free_bits, double* theta, double lambda0, double xtol,
+                          int n_iter, double* chi2, double* cov, int32_t* nchan, int32_t* niter,
+                          int32_t* status, double* trace, hipStream_t st);
+
 // ---- uv_weight.hip: uniform and Briggs imaging weights from the (u, v) density (K15) -------------
 struct UvWeightTiling {
   int64_t cells;                // (2 (nx / 2) + 1)(2 (nz / 2) + 1), per map (INT64_MAX: beyond int64)

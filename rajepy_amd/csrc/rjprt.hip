@@ -1412,6 +1412,54 @@ int64_t rjp_uvfit(rjp_ctx* ctx, const double* d_vis, int32_t n_maps, int32_t n_v
   return r ? r : t.workgroups;
 }
 
+int64_t rjp_cube_moments(rjp_ctx* ctx, const double* d_cube, int64_t n_pix, int32_t n_chan,
+                         const double* h_x, const double* h_dx, double x_ref, double clip,
+                         const uint8_t* d_mask, double* d_mom, int32_t* d_ipeak, int32_t* d_count,
+                         void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_cube_moments(d_cube, n_pix, n_chan, h_x, h_dx, x_ref, clip, d_mom,
+                                            m);
+      }))
+    return r;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t F = (size_t)n_chan;
+  const int r = staged(ctx, st, "cube_moments_launch", nullptr, {{h_x, F}, {h_dx, F}},
+                       [&](double* const* d, const double*) {
+                         return rjp::cube_moments_launch(d_cube, n_pix, n_chan, d[0], d[1], x_ref,
+                                                         clip, d_mask, d_mom, d_ipeak, d_count, st);
+                       });
+  return r ? r : rjp::specfit_workgroups(n_pix);
+}
+
+int64_t rjp_specfit(rjp_ctx* ctx, const double* d_cube, int64_t n_pix, int32_t n_chan,
+                    const double* h_x, double x_ref, const double* h_w, const uint8_t* d_mask,
+                    int32_t n_comp, const uint8_t* h_free, double* d_theta, double lambda0,
+                    double xtol, int32_t n_iter, double* d_chi2, double* d_cov, int32_t* d_nchan,
+                    int32_t* d_niter, int32_t* d_status, double* d_trace, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_specfit(d_cube, n_pix, n_chan, h_x, x_ref, h_w, n_comp, h_free,
+                                       d_theta, lambda0, xtol, n_iter, d_chi2, d_cov, d_nchan,
+                                       d_niter, d_status, m);
+      }))
+    return r;
+  unsigned free_bits = 0;
+  for (int i = 0; i < 3 * n_comp + 2; ++i)
+    if (!h_free || h_free[i]) free_bits |= 1u << i;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t F = (size_t)n_chan;
+  const int r = staged(ctx, st, "specfit_launch", nullptr, {{h_x, F}, {h_w ? h_w : h_x, h_w ? F : 0}},
+                       [&](double* const* d, const double*) {
+                         return rjp::specfit_launch(d_cube, n_pix, n_chan, d[0],
+                                                    h_w ? d[1] : nullptr, x_ref, d_mask, n_comp,
+                                                    free_bits, d_theta, lambda0, xtol, n_iter,
+                                                    d_chi2, d_cov, d_nchan, d_niter, d_status,
+                                                    d_trace, st);
+                       });
+  return r ? r : rjp::specfit_workgroups(n_pix);
+}
+
 size_t rjp_uv_weights_workspace(int32_t n_maps, int32_t nx, int32_t nz, int32_t n_vis) {
   if (n_maps <= 0 || nx <= 0 || nz <= 0 || n_vis <= 0) return 0;
   return rjp::uv_weights_workspace_bytes(n_maps, nx, nz, n_vis);

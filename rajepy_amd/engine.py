@@ -20,6 +20,8 @@ from .imaging import (SIDEREAL_DAY_S, AntennaConfig, Geodetic, antenna_config_pa
                       taylor_weights, thermal_sigma, vis_scales)
 from .imaging import (UVFIT_MAX_COMP, uvfit_components, uvfit_results, uvfit_start,  # noqa: F401
                       uvfit_theta, uvfit_theta_from_imfit)
+from .spectra import (SPECFIT_MAX_CHAN, SPECFIT_MAX_COMP, channel_widths,  # noqa: F401
+                      specfit_results, specfit_start, velocity_axis)
 
 
 def _torch():
@@ -1673,6 +1675,121 @@ class RTEngine:
             float(lambda0), float(xtol), n_iter, chi2.data_ptr(), cov.data_ptr(), nvis.data_ptr(),
             niter.data_ptr(), status.data_ptr(), _ptr(tr), work.data_ptr(), work.numel())
         out = dict(theta=theta, chi2=chi2, cov=cov, nvis=nvis, niter=niter, status=status)
+        if trace:
+            out["trace"] = tr
+        return out
+
+    # -- K21 -------------------------------------------------------------------------------------
+    def _line_cube(self, who, cube, x):
+        """A cube [F, ...] of float64 channel planes on this device and its axis -> (cube, the
+        axis as a host vector, F, n_pix)."""
+        torch = _torch()
+        x = np.ascontiguousarray(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x,
+                                 dtype=np.float64).reshape(-1)
+        F = x.size
+        if not (isinstance(cube, torch.Tensor) and cube.dtype == torch.float64 and
+                cube.device == self.device and cube.is_contiguous() and cube.dim() >= 2 and
+                F >= 1 and cube.shape[0] == F and cube.numel() >= F):
+            raise ValueError("%s: `cube` must be a contiguous float64 tensor [F, ...] on %s with one "
+                             "plane per entry of `x` (%d)" % (who, self.device, F))
+        if F > SPECFIT_MAX_CHAN:
+            raise ValueError("%s: at most %d channels" % (who, SPECFIT_MAX_CHAN))
+        return cube, x, F, cube.numel() // F
+
+    def cube_moments(self, cube, x, dx, x_ref, clip=0., mask=None):
+        """Moment maps of a line cube (rjp_cube_moments), one lane per pixel, nothing going to
+        the host -> (`mom` [4, n_pix] float64 = (m0, m1, m2, peak), `ipeak` [n_pix] int32, `count`
+        [n_pix] int32) device tensors.  `cube`: float64 device tensor [F, ...] of channel planes
+        (read only: a `flux_rrl` stack, a `CleanResult.image`); `x`, `dx` [F]: HOST axis (any unit,
+        any order, need not be uniform) and channel widths (>= 0: `velocity_axis`); `x_ref`: the
+        origin the first moment is accumulated about (the mid-channel); `clip`: a channel counts
+        when it is finite and |y| >= clip; `mask`: None or n_pix values, non-zero = live.  Over
+        the counted channels in ascending order m0 = sum y dx, m1 = x_ref + sum y dx (x - x_ref) /
+        m0, m2 = sqrt(sum y dx (x - m1)^2 / m0) (NaN below 0), the peak = the largest y (the lowest
+        channel on a tie); no counted channel or m0 == 0: m0 = +0.0, the rest NaN, ipeak -1.  The
+        bits of a pixel depend on its spectrum and the tables alone.  The number of workgroups is
+        kept in `last_specfit_workgroups`."""
+        torch = _torch()
+        cube, x, F, npix = self._line_cube("cube_moments", cube, x)
+        dx = np.ascontiguousarray(dx, dtype=np.float64).reshape(-1)
+        if dx.size != F:
+            raise ValueError("cube_moments: `dx` must have one entry per channel (%d)" % F)
+        dmask = self._device_mask("cube_moments", mask, npix)
+        mom = self._f64(4, npix)
+        ipeak = torch.empty(npix, dtype=torch.int32, device=self.device)
+        count = torch.empty(npix, dtype=torch.int32, device=self.device)
+        self.last_specfit_workgroups = self._call_tiles(
+            "rjp_cube_moments", cube.data_ptr(), npix, F, _lib.dbl_array(x), _lib.dbl_array(dx),
+            float(x_ref), float(clip), _ptr(dmask), mom.data_ptr(), ipeak.data_ptr(),
+            count.data_ptr())
+        return mom, ipeak, count
+
+    def specfit(self, cube, x, theta, x_ref, weights=None, free=None, n_comp=1, lambda0=1e-3,
+                xtol=1e-10, n_iter=40, mask=None, trace=False):
+        """One Levenberg-Marquardt fit per pixel of `n_comp` Gaussians plus a linear baseline,
+        y(x) = sum_c A_c exp(-(x - x0_c)^2 / (2 s_c^2)) + b0 + b1 (x - x_ref), to a line cube
+        (rjp_specfit): the whole fit of a pixel in ONE launch, one lane per pixel, nothing going to
+        the host -> dict of device tensors: `theta` [P, n_pix], P = 3 n_comp + 2 parameter planes
+        (A_0, x0_0, s_0, [A_1, x0_1, s_1,] b0, b1); `chi2` [n_pix]; `cov` [P (P + 1) / 2, n_pix]
+        (the packed upper triangle of J^T W J at `theta`, identity rows for fixed parameters, NOT
+        inverted: `specfit_results`); `nchan`, `niter`, `status` [n_pix] int32 -- 1 converged, 0
+        `n_iter` exhausted, 2 stalled (lambda > 1e12), 3 degenerate (masked, a start that is not
+        finite or has s <= 0, fewer counted channels than free parameters: `theta` keeps the
+        start, the other outputs of that pixel are NaN / -1) -- and with `trace` the rows [n_pix,
+        n_iter, 3 + P] of (chi^2 of the trial, lambda, accepted, the trial), NaN beyond `niter`.
+        `cube`, `x`, `x_ref`, `mask` as `cube_moments`; `theta`: the start, [P, n_pix] or [P] for
+        all (`specfit_start`; it is copied); `weights`: None (all ones) or [F] HOST values >= 0 (1
+        / sigma^2 per channel, 0 = ignore); `free`: None (all free) or P flags, one pattern for
+        all pixels -- b0 = b1 = 0 held is the fit of a continuum-subtracted cube.  A channel
+        counts when it is finite and its weight > 0.  The iteration is `uvfit`'s.  The bits of a
+        pixel depend on its spectrum and the tables alone."""
+        torch = _torch()
+        n_iter, n_comp = int(n_iter), int(n_comp)
+        if n_iter < 1:
+            raise ValueError("specfit: n_iter must be positive")
+        if not 1 <= n_comp <= SPECFIT_MAX_COMP:
+            raise ValueError("specfit: n_comp must be 1 to %d" % SPECFIT_MAX_COMP)
+        cube, x, F, npix = self._line_cube("specfit", cube, x)
+        if not (np.isfinite(lambda0) and lambda0 > 0. and np.isfinite(xtol) and xtol > 0.):
+            raise ValueError("specfit: `lambda0` and `xtol` must be finite and positive")
+        P = 3 * n_comp + 2
+        if isinstance(theta, torch.Tensor):
+            th = theta.to(device=self.device, dtype=torch.float64)
+        else:
+            th = torch.from_numpy(np.ascontiguousarray(theta, dtype=np.float64)).to(self.device)
+        if th.dim() == 1:
+            th = th.reshape(-1, 1).expand(-1, npix)
+        if th.shape[0] != P or th.numel() != P * npix:
+            raise ValueError("specfit: `theta` must be [P] or [P, n_pix] = [%d, %d]" % (P, npix))
+        th = th.reshape(P, npix).contiguous().clone()
+        hw = None
+        if weights is not None:
+            wv = np.ascontiguousarray(weights.detach().cpu().numpy()
+                                      if isinstance(weights, torch.Tensor) else weights,
+                                      dtype=np.float64).reshape(-1)
+            if wv.size != F:
+                raise ValueError("specfit: `weights` must have one entry per channel (%d)" % F)
+            hw = _lib.dbl_array(wv)
+        hfree = None
+        if free is not None:
+            fr = np.ascontiguousarray(np.asarray(free) != 0, dtype=np.uint8).reshape(-1)
+            if fr.size != P or not fr.any():
+                raise ValueError("specfit: `free` must hold %d flags, at least one of them set" % P)
+            hfree = (C.c_uint8 * P)(*fr)
+        dmask = self._device_mask("specfit", mask, npix)
+        T = P * (P + 1) // 2
+        chi2 = torch.full((npix,), float("nan"), dtype=torch.float64, device=self.device)
+        cov = torch.full((T, npix), float("nan"), dtype=torch.float64, device=self.device)
+        nchan, niter, status = (torch.full((npix,), -1, dtype=torch.int32, device=self.device)
+                                for _ in range(3))
+        tr = (torch.full((npix, n_iter, 3 + P), float("nan"), dtype=torch.float64,
+                         device=self.device) if trace else None)
+        self.last_specfit_workgroups = self._call_tiles(
+            "rjp_specfit", cube.data_ptr(), npix, F, _lib.dbl_array(x), float(x_ref), hw,
+            _ptr(dmask), n_comp, hfree, th.data_ptr(), float(lambda0), float(xtol), n_iter,
+            chi2.data_ptr(), cov.data_ptr(), nchan.data_ptr(), niter.data_ptr(),
+            status.data_ptr(), _ptr(tr))
+        out = dict(theta=th, chi2=chi2, cov=cov, nchan=nchan, niter=niter, status=status)
         if trace:
             out["trace"] = tr
         return out
