@@ -383,12 +383,14 @@ hipError_t components_image_launch(const int32_t* cpix, const int32_t* cscale, c
                                    const int32_t* ncomp, int n_maps, int comp_stride, int n_s,
                                    int nx, int nz, double* out, hipStream_t st);
 
-// ---- imfit.hip: Levenberg-Marquardt fits of one elliptical Gaussian per map (K14) ----------------
-struct GaussfitTiling {
-  int64_t tiles;                // of 1024 consecutive pixels of the box, per map
+// ---- lm_common.h: what the Levenberg-Marquardt fits share; the tiling of K14 and K20 -------------
+struct LmTiling {
+  int64_t tiles;                // of 1024 consecutive items (pixels of the box, visibilities), per map
   int64_t workgroups;           // n_maps x tiles: the grid of every iteration's launch
 };
-GaussfitTiling gaussfit_tiling(int n_maps, int64_t box_pixels);
+
+// ---- imfit.hip: Levenberg-Marquardt fits of one elliptical Gaussian per map (K14) ----------------
+LmTiling gaussfit_tiling(int n_maps, int64_t box_pixels);
 // 0: does not fit a size_t
 size_t gaussfit_workspace_bytes(int n_maps, int64_t box_pixels);
 // `box`: HOST (i0, i1, j0, j1); `mask`, `trace` may be nullptr; n_iter + 1 launches, no host
@@ -399,11 +401,7 @@ hipError_t gaussfit_launch(const double* img, int n_maps, int nx, int nz, const 
                            int32_t* status, double* trace, void* work, hipStream_t st);
 
 // ---- uvfit.hip: Levenberg-Marquardt fits of point / Gaussian components to visibilities (K20) ----
-struct UvfitTiling {
-  int64_t tiles;                // of 1024 consecutive visibilities, per map
-  int64_t workgroups;           // n_maps x tiles: the grid of every iteration's launch
-};
-UvfitTiling uvfit_tiling(int n_maps, int64_t n_vis);
+LmTiling uvfit_tiling(int n_maps, int64_t n_vis);
 // n_comp 1 or 2; 0: does not fit a size_t
 size_t uvfit_workspace_bytes(int n_maps, int64_t n_vis, int n_comp);
 // d_su / d_sv[n_maps]: device copies of the scales; `free_bits`: bit i set = parameter i is fitted;

@@ -1362,7 +1362,7 @@ int64_t rjp_gaussfit(rjp_ctx* ctx, const double* d_img, int32_t n_maps, int32_t 
       }))
     return r;
   const int64_t nbox = (int64_t)(h_box[1] - h_box[0] + 1) * (h_box[3] - h_box[2] + 1);
-  const rjp::GaussfitTiling t = rjp::gaussfit_tiling(n_maps, nbox);
+  const rjp::LmTiling t = rjp::gaussfit_tiling(n_maps, nbox);
   if (t.workgroups > (int64_t)INT32_MAX)
     return fail(ctx, RJP_ERR_ARG, "rjp_gaussfit: more than 2^31 - 1 workgroups");
   const size_t need = rjp::gaussfit_workspace_bytes(n_maps, nbox);
@@ -1393,7 +1393,7 @@ int64_t rjp_uvfit(rjp_ctx* ctx, const double* d_vis, int32_t n_maps, int32_t n_v
                                      d_nvis, d_niter, d_status, m);
       }))
     return r;
-  const rjp::UvfitTiling t = rjp::uvfit_tiling(n_maps, n_vis);
+  const rjp::LmTiling t = rjp::uvfit_tiling(n_maps, n_vis);
   const size_t need = rjp::uvfit_workspace_bytes(n_maps, n_vis, n_comp);
   if (!d_work || work_bytes < need)
     return fail(ctx, RJP_ERR_WORKSPACE, "rjp_uvfit: workspace smaller than rjp_uvfit_workspace()");

@@ -15,12 +15,18 @@
 //
 // Fit: the whole fit of a pixel in one launch.  A lane keeps theta_cur, the trial, chi^2, N and g
 // of theta_cur and the trial's sums in registers, re-reads its spectrum once per trial, and takes
-// K20's decision (uvfit.hip, uf_decide) for itself after every trial.  A finished lane idles; the
-// wave leaves when its last lane is finished.  The kernel is templated on n_comp and on whether a
-// baseline parameter is free (BL): with both held, the sums and the Cholesky run on the 3 n_comp
-// line parameters alone (the identity's rows of the baseline would change no bit of the others:
+// lm_common.h's decision for itself after every trial, in its own loop: feasible = every width
+// finite and > 0; the step scales (max(|A|, 1e-300), s, s) per line, s = max(sigma, 1e-300), and
+// max(|b|, 1e-300) for a free baseline parameter; enough = count >= the number of free parameters.
+// lm_tri, lm_solve and lm_step_converged are the header's; the take-over of a trial's sums and the
+// breakdown loop are lm_take_sums and lm_damped_solve WRITTEN OUT here: through the calls the
+// same arithmetic is allocated 4 to 16 VGPRs more (162 / 118 / 288 / 212 against 158 / 112 / 272 /
+// 200 for <1, true>, <1, false>, <2, true>, <2, false>).  A finished lane idles; the wave leaves
+// when its last lane is finished.  The kernel is templated on n_comp and on whether a baseline
+// parameter is free (BL): with both held, the sums and the Cholesky run on the 3 n_comp line
+// parameters alone (the identity's rows of the baseline would change no bit of the others:
 // they come last, their L entries and steps are exact zeros), the baseline still enters the model.
-#include "rjp_host.h"
+#include "lm_common.h"
 
 namespace rjp {
 
@@ -87,54 +93,6 @@ hipError_t cube_moments_launch(const double* cube, int64_t n_pix, int n_chan, co
   hipLaunchKernelGGL(cube_moments_kernel, dim3((unsigned)specfit_workgroups(n_pix)), dim3(kSfB), 0,
                      st, cube, n_pix, n_chan, d_x, d_dx, x_ref, clip, mask, mom, ipeak, count);
   return hipGetLastError();
-}
-
-// index of (i, j), i <= j, in the packed upper triangle of a P x P matrix, row by row
-template <int P>
-__device__ __forceinline__ constexpr int sf_tri(int i, int j) {
-  return i * P - i * (i - 1) / 2 + (j - i);
-}
-
-// (N + lam diag N) delta = g by Cholesky, everything in registers at compile-time indices (K20's
-// uf_solve); false: a pivot is not > 0
-template <int P>
-__device__ __forceinline__ bool sf_solve(const double (&N)[P * (P + 1) / 2], const double (&g)[P],
-                                         double lam, double (&delta)[P]) {
-  double L[P * (P + 1) / 2];                         // L^T, packed like N: L[tri(k, i)] = l_ik
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    const double njj = N[sf_tri<P>(j, j)];
-    double d = __builtin_fma(lam, njj, njj);
-#pragma unroll
-    for (int k = 0; k < j; ++k) d = __builtin_fma(-L[sf_tri<P>(k, j)], L[sf_tri<P>(k, j)], d);
-    ok = ok && d > 0.0;
-    const double l = __builtin_sqrt(d);
-    L[sf_tri<P>(j, j)] = l;
-#pragma unroll
-    for (int i = j + 1; i < P; ++i) {
-      double s = N[sf_tri<P>(j, i)];
-#pragma unroll
-      for (int k = 0; k < j; ++k) s = __builtin_fma(-L[sf_tri<P>(k, i)], L[sf_tri<P>(k, j)], s);
-      L[sf_tri<P>(j, i)] = s / l;
-    }
-  }
-  double y[P];
-#pragma unroll
-  for (int i = 0; i < P; ++i) {
-    double s = g[i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) s = __builtin_fma(-L[sf_tri<P>(k, i)], y[k], s);
-    y[i] = s / L[sf_tri<P>(i, i)];
-  }
-#pragma unroll
-  for (int i = P - 1; i >= 0; --i) {
-    double s = y[i];
-#pragma unroll
-    for (int k = i + 1; k < P; ++k) s = __builtin_fma(-L[sf_tri<P>(i, k)], delta[k], s);
-    delta[i] = s / L[sf_tri<P>(i, i)];
-  }
-  return ok;
 }
 
 template <int NC, bool BL>
@@ -219,7 +177,7 @@ __global__ __launch_bounds__(kSfB) void specfit_kernel(
         const double wj = wc * J[i];
 #pragma unroll
         for (int j = i; j < PA; ++j)
-          Nt[sf_tri<PA>(i, j)] = __builtin_fma(wj, J[j], Nt[sf_tri<PA>(i, j)]);
+          Nt[lm_tri<PA>(i, j)] = __builtin_fma(wj, J[j], Nt[lm_tri<PA>(i, j)]);
         gt[i] = __builtin_fma(wj, r, gt[i]);
       }
       ++n;
@@ -231,7 +189,7 @@ __global__ __launch_bounds__(kSfB) void specfit_kernel(
         return;
       }
     }
-    // the decision: K20's, with "feasible" = every width finite and > 0
+    // the decision (lm_common.h)
     bool feas = true;
 #pragma unroll
     for (int c = 0; c < NC; ++c) feas = feas && finite_d(th_t[3 * c + 2]) && th_t[3 * c + 2] > 0.0;
@@ -247,13 +205,14 @@ __global__ __launch_bounds__(kSfB) void specfit_kernel(
     if (acc) {
 #pragma unroll
       for (int i = 0; i < P; ++i) th_c[i] = th_t[i];
+      // (lm_take_sums)
 #pragma unroll
       for (int i = 0; i < PA; ++i) {
         const bool fi = (free_bits >> i) & 1u;
 #pragma unroll
         for (int j = i; j < PA; ++j)
-          Nc[sf_tri<PA>(i, j)] =
-              (fi && ((free_bits >> j) & 1u)) ? Nt[sf_tri<PA>(i, j)] : (i == j ? 1.0 : 0.0);
+          Nc[lm_tri<PA>(i, j)] =
+              (fi && ((free_bits >> j) & 1u)) ? Nt[lm_tri<PA>(i, j)] : (i == j ? 1.0 : 0.0);
         gc[i] = fi ? gt[i] : 0.0;
       }
       chi_c = chi_t;
@@ -265,12 +224,12 @@ __global__ __launch_bounds__(kSfB) void specfit_kernel(
       status = 1;
       break;
     }
-    double delta[PA];
+    double delta[PA], scale[PA];
     bool ok = false;
-    // (at most 25 rounds: lambda >= 1e-12 grows tenfold per breakdown)
+    // (lm_damped_solve)
     while (true) {
       if (lam > 1e12) break;
-      if (sf_solve<PA>(Nc, gc, lam, delta)) {
+      if (lm_solve<PA>(Nc, gc, lam, delta)) {
         ok = true;
         break;
       }
@@ -280,25 +239,14 @@ __global__ __launch_bounds__(kSfB) void specfit_kernel(
       status = 2;
       break;
     }
-    double worst = 0.0;
-    bool nan = false;
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-      const double s = __builtin_fmax(th_c[3 * c + 2], 1e-300);
-      worst = __builtin_fmax(worst, __builtin_fabs(delta[3 * c]) /
-                                        __builtin_fmax(__builtin_fabs(th_c[3 * c]), 1e-300));
-      worst = __builtin_fmax(worst, __builtin_fabs(delta[3 * c + 1]) / s);
-      worst = __builtin_fmax(worst, __builtin_fabs(delta[3 * c + 2]) / s);
-    }
-    if (BL) {
-#pragma unroll
-      for (int i = PA - 2; i < PA; ++i)
-        worst = __builtin_fmax(worst, __builtin_fabs(delta[i]) /
-                                          __builtin_fmax(__builtin_fabs(th_c[i]), 1e-300));
+      scale[3 * c] = __builtin_fmax(__builtin_fabs(th_c[3 * c]), 1e-300);
+      scale[3 * c + 1] = scale[3 * c + 2] = __builtin_fmax(th_c[3 * c + 2], 1e-300);
     }
 #pragma unroll
-    for (int i = 0; i < PA; ++i) nan = nan || delta[i] != delta[i];
-    if (!nan && worst <= xtol) {
+    for (int i = 3 * NC; i < PA; ++i) scale[i] = __builtin_fmax(__builtin_fabs(th_c[i]), 1e-300);
+    if (lm_step_converged<PA>(delta, scale, xtol)) {
       status = 1;
       break;
     }
@@ -324,7 +272,7 @@ __global__ __launch_bounds__(kSfB) void specfit_kernel(
 #pragma unroll
       for (int j = i; j < P; ++j, ++q)
         cov[(int64_t)q * n_pix + p] =
-            (i < PA && j < PA) ? Nc[sf_tri<PA>(i < PA ? i : 0, j < PA ? j : 0)] : (i == j ? 1.0 : 0.0);
+            (i < PA && j < PA) ? Nc[lm_tri<PA>(i < PA ? i : 0, j < PA ? j : 0)] : (i == j ? 1.0 : 0.0);
   }
   o_nchan[p] = cnt;
   o_niter[p] = it;

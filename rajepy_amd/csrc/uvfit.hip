@@ -19,355 +19,70 @@
 // accumulated per visibility as fma(w * Re, Re, .) then fma(w * Im, Im, .), the weight on the left
 // factor (for N: the column with the lower index).  P = 6 n_comp.
 //
-// Structure: K14's (imfit.hip).  One launch per iteration for the whole stack, grid = tiles x maps;
-// a tile is kUfT = 1024 consecutive visibilities, thread tid owns t0 + tid + 256 j, j < 4.  Launch
-// k = 0 .. n_iter; a workgroup of launch k >= 1
-//   1. reduces the Q = 1 + T + P + 1 partial sums (chi^2, N, g, count) that launch k - 1 left per
-//      tile of its map -- every workgroup redundantly and in the same order, thread i the tiles
-//      i, i + 256, ..., then the block sum;
-//   2. thread 0 decides the iteration (uf_decide) and broadcasts the next trial through LDS;
-//   3. every thread evaluates that trial on its visibilities; the block sum goes to the other half
-//      of the double-buffered partials;
-//   4. (tile 0 only) writes the map's state to the other half of the double-buffered state, the
-//      trace row, and in launch n_iter the outputs.
-// No atomics; every sum in a fixed order: the same bits on every call.  The block sum goes through
-// LDS in chunks of 29 sums (K14's rows of 8 x 33 doubles), four chunks for two components.  The
-// partial sums of a thread live in registers (92 doubles for two components); thread 0 factorises
-// with L in registers and N, g in LDS, everything at compile-time indices: no scratch.
-//
-// The decision is K14's, word for word, with: "positive definite" -> every component's Sigma is
-// positive SEMI-definite (sxx >= 0, szz >= 0, sxx szz >= sxz^2); the step scale s = (max(|F|,
-// 1e-300), 1, 1, t, t, t), t = max(sxx + szz, 1) per component; status 3 for a start that is not
-// finite or not PSD, a first chi^2 that is not finite, or 2 count < the number of free parameters;
-// a P x P Cholesky.  A fixed parameter (bit i of `free_bits` clear) has its row and column of N
-// replaced by the identity's and g_i by 0 when a trial's sums are taken over: delta_i = 0 exactly.
-#include "rjp_host.h"
+// The launches, the block sum (four passes for two components) and the decision are lm_common.h's;
+// a tile is 1024 consecutive visibilities, and the partial sums of a thread live in registers (92
+// doubles for two components).  The policy: feasible = every component's Sigma is positive
+// SEMI-definite (sxx >= 0, szz >= 0, sxx szz >= sxz^2); the step scales s = (max(|F|, 1e-300), 1,
+// 1, t, t, t), t = max(sxx + szz, 1) per component; enough = 2 count >= the number of free
+// parameters; `free_bits` is the caller's.
+#include "lm_common.h"
 
 namespace rjp {
 
-constexpr int kUfB = 256;          // threads per workgroup
-constexpr int kUfT = 1024;         // visibilities per tile: four per thread
-constexpr int kUfC = 29;           // sums per pass of the block sum
-constexpr int kUfRow = 8 * 33;     // LDS row of the block sum: 8 parts of 32 + 1 pad
-constexpr int kUfRun = -1;         // status while the fit goes on
 constexpr double kUfM2Pi2 = -19.739208802178716;   // -2 pi^2
 constexpr double kUfM4Pi2 = -39.478417604357432;   // -4 pi^2
 constexpr double kUf2Pi = 6.283185307179586;
 
-// sizes and the layout of a map's state for NC components:
-// theta_cur 0..P-1, chi_cur, lambda, lambda of the trial, status, trials, count, theta_t, N, g
 template <int NC>
-struct Uf {
-  static constexpr int P = 6 * NC, T = P * (P + 1) / 2, Q = 1 + T + P + 1;
-  static constexpr int oChi = P, oLam = P + 1, oLamT = P + 2, oStat = P + 3, oIt = P + 4,
-                       oCnt = P + 5, oTt = P + 6, oN = 2 * P + 6, oG = 2 * P + 6 + T;
-  static constexpr int S = (oG + P + 7) / 8 * 8;    // doubles of state per map: 48, 120
+struct UfPolicy {
+  static constexpr int P = 6 * NC;
+  static __device__ __forceinline__ bool feasible(const double* th) {
+    bool psd = true;
+    for (int c = 0; c < NC; ++c) {
+      const double sxx = th[6 * c + 3], sxz = th[6 * c + 4], szz = th[6 * c + 5];
+      psd = psd && sxx >= 0.0 && szz >= 0.0 && sxx * szz >= sxz * sxz;
+    }
+    return psd;
+  }
+  // (|F| = 0 would make 0 / 0, which fmax drops: the floor keeps F in the test)
+  static __device__ __forceinline__ void scales(const double* th, double (&s)[P]) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      s[6 * c] = __builtin_fmax(__builtin_fabs(th[6 * c]), 1e-300);
+      s[6 * c + 1] = s[6 * c + 2] = 1.0;
+      s[6 * c + 3] = s[6 * c + 4] = s[6 * c + 5] = __builtin_fmax(th[6 * c + 3] + th[6 * c + 5], 1.0);
+    }
+  }
+  static __device__ __forceinline__ bool enough(double count, unsigned free_bits) {
+    return 2.0 * count >= (double)__builtin_popcount(free_bits);
+  }
 };
 
-static int uf_sums(int n_comp) { return n_comp == 1 ? Uf<1>::Q : Uf<2>::Q; }
-static int uf_state(int n_comp) { return n_comp == 1 ? Uf<1>::S : Uf<2>::S; }
+LmTiling uvfit_tiling(int n_maps, int64_t n_vis) { return lm_tiling(n_maps, n_vis); }
 
-UvfitTiling uvfit_tiling(int n_maps, int64_t n_vis) {
-  UvfitTiling t;
-  t.tiles = (n_vis + kUfT - 1) / kUfT;
-  t.workgroups = t.tiles * n_maps;
-  return t;
-}
-
-// two halves of (Q sums per tile, S doubles of state per map); 0: no size_t holds it
 size_t uvfit_workspace_bytes(int n_maps, int64_t n_vis, int n_comp) {
-  const UvfitTiling t = uvfit_tiling(n_maps, n_vis);
-  const unsigned __int128 n = ((unsigned __int128)t.workgroups * (unsigned)uf_sums(n_comp) +
-                               (unsigned __int128)n_maps * (unsigned)uf_state(n_comp)) * 2u * 8u;
-  return n > (unsigned __int128)SIZE_MAX ? 0 : (size_t)n;
+  return lm_workspace_bytes(lm_tiling(n_maps, n_vis), n_maps,
+                            n_comp == 1 ? LmState<6>::Q : LmState<12>::Q,
+                            n_comp == 1 ? LmState<6>::S : LmState<12>::S);
 }
 
-__device__ __forceinline__ bool uf_psd(double sxx, double sxz, double szz) {
-  return sxx >= 0.0 && szz >= 0.0 && sxx * szz >= sxz * sxz;
-}
-
-// index of (i, j), i <= j, in the packed upper triangle of a P x P matrix, row by row
-template <int P>
-__device__ __forceinline__ constexpr int uf_tri(int i, int j) {
-  return i * P - i * (i - 1) / 2 + (j - i);
-}
-
-// s_tot[q] = sum over the workgroup of v[q], valid in every thread on return
-template <int Q>
-__device__ __forceinline__ void uf_block_sum(const double (&v)[Q], double* s_a, double* s_b,
-                                             double* s_tot) {
-  const int tid = threadIdx.x;
-  const int slot = (tid >> 5) * 33 + (tid & 31);
-#pragma unroll
-  for (int c0 = 0; c0 < Q; c0 += kUfC) {
-    const int n = Q - c0 < kUfC ? Q - c0 : kUfC;
-    __syncthreads();                                // earlier readers of s_a / s_tot are done
-#pragma unroll
-    for (int q = 0; q < kUfC; ++q)
-      if (c0 + q < Q) s_a[q * kUfRow + slot] = v[c0 + q < Q ? c0 + q : 0];
-    __syncthreads();
-    if (tid < n * 8) {
-      const double* p = s_a + (tid >> 3) * kUfRow + (tid & 7) * 33;
-      double a = p[0];
-      for (int i = 1; i < 32; ++i) a += p[i];
-      s_b[tid] = a;
-    }
-    __syncthreads();
-    if (tid < n) {
-      double a = s_b[tid * 8];
-#pragma unroll
-      for (int i = 1; i < 8; ++i) a += s_b[tid * 8 + i];
-      s_tot[c0 + tid] = a;
-    }
-  }
-  __syncthreads();
-}
-
-// (N + lam diag N) delta = g by Cholesky; N, g in LDS, L in registers, everything at compile-time
-// indices; false: a pivot is not > 0
-template <int P>
-__device__ __forceinline__ bool uf_solve(const double* N, const double* g, double lam,
-                                         double (&delta)[P]) {
-  double L[P * (P + 1) / 2];                         // L^T, packed like N: L[tri(k, i)] = l_ik
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    const double njj = N[uf_tri<P>(j, j)];
-    double d = __builtin_fma(lam, njj, njj);
-#pragma unroll
-    for (int k = 0; k < j; ++k) d = __builtin_fma(-L[uf_tri<P>(k, j)], L[uf_tri<P>(k, j)], d);
-    ok = ok && d > 0.0;
-    const double l = __builtin_sqrt(d);
-    L[uf_tri<P>(j, j)] = l;
-#pragma unroll
-    for (int i = j + 1; i < P; ++i) {
-      double s = N[uf_tri<P>(j, i)];
-#pragma unroll
-      for (int k = 0; k < j; ++k) s = __builtin_fma(-L[uf_tri<P>(k, i)], L[uf_tri<P>(k, j)], s);
-      L[uf_tri<P>(j, i)] = s / l;
-    }
-  }
-  double y[P];
-#pragma unroll
-  for (int i = 0; i < P; ++i) {
-    double s = g[i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) s = __builtin_fma(-L[uf_tri<P>(k, i)], y[k], s);
-    y[i] = s / L[uf_tri<P>(i, i)];
-  }
-#pragma unroll
-  for (int i = P - 1; i >= 0; --i) {
-    double s = y[i];
-#pragma unroll
-    for (int k = i + 1; k < P; ++k) s = __builtin_fma(-L[uf_tri<P>(i, k)], delta[k], s);
-    delta[i] = s / L[uf_tri<P>(i, i)];
-  }
-  return ok;
-}
-
-// the outputs of a map from its final state (status 3: the status alone)
 template <int NC>
-__device__ __forceinline__ void uf_outputs(const double* __restrict__ s, int m,
-                                           double* __restrict__ theta, double* __restrict__ chi2,
-                                           double* __restrict__ cov, int* __restrict__ nvis,
-                                           int* __restrict__ niter, int* __restrict__ status) {
-  using U = Uf<NC>;
-  const int st = (int)s[U::oStat];
-  status[m] = st == kUfRun ? 0 : st;
-  if (st == 3) return;
-  for (int i = 0; i < U::P; ++i) theta[U::P * m + i] = s[i];
-  chi2[m] = s[U::oChi];
-  for (int i = 0; i < U::T; ++i) cov[(int64_t)U::T * m + i] = s[U::oN + i];
-  nvis[m] = (int)s[U::oCnt];
-  niter[m] = (int)s[U::oIt];
-}
-
-// Step 2 of launch `it` >= 1 in thread 0: the state `si` and the trial's sums `tot` -> the state
-// `so` (tile 0 stores it), the trace row, and the next trial in dec[0..P-1]; true: evaluate it.
-// s_th [P], s_N [T], s_g [P]: LDS of thread 0's own.
-template <int NC>
-__device__ __forceinline__ bool uf_decide(const double* __restrict__ si, const double* tot,
-                                          double* __restrict__ so, bool store, int it, int n_iter,
-                                          double xtol, unsigned free_bits,
-                                          double* __restrict__ trace_row, double* dec, double* s_th,
-                                          double* s_N, double* s_g) {
-  using U = Uf<NC>;
-  constexpr int P = U::P, T = U::T;
-  const bool first = it == 1;
-  const double chi_t = tot[0], lam_used = si[U::oLamT];
-  double lam = si[U::oLam], chi_cur = si[U::oChi];
-  const double cnt = first ? tot[U::Q - 1] : si[U::oCnt];
-  int status = kUfRun;
-  bool eval = false;
-  if (first && (!(2.0 * cnt >= (double)__builtin_popcount(free_bits)) || !finite_d(chi_t))) {
-    if (store) {
-      for (int i = 0; i < U::S; ++i) so[i] = si[i];
-      so[U::oStat] = 3.0;
-    }
-    return false;
-  }
-  bool psd = true;
-  for (int c = 0; c < NC; ++c)
-    psd = psd && uf_psd(si[U::oTt + 6 * c + 3], si[U::oTt + 6 * c + 4], si[U::oTt + 6 * c + 5]);
-  const bool acc = psd && finite_d(chi_t) && chi_t < chi_cur;
-  if (acc) {
-    for (int i = 0; i < P; ++i) s_th[i] = si[U::oTt + i];
-    int q = 0;
-    for (int i = 0; i < P; ++i) {
-      const bool fi = (free_bits >> i) & 1u;
-      for (int j = i; j < P; ++j, ++q)
-        s_N[q] = (fi && ((free_bits >> j) & 1u)) ? tot[1 + q] : (i == j ? 1.0 : 0.0);
-      s_g[i] = fi ? tot[1 + T + i] : 0.0;
-    }
-    chi_cur = chi_t;
-    if (!first) lam = __builtin_fmax(lam / 10.0, 1e-12);
-  } else {
-    for (int i = 0; i < P; ++i) s_th[i] = si[i];
-    for (int i = 0; i < T; ++i) s_N[i] = si[U::oN + i];
-    for (int i = 0; i < P; ++i) s_g[i] = si[U::oG + i];
-    lam *= 10.0;
-  }
-  if (store && trace_row) {
-    trace_row[0] = chi_t;
-    trace_row[1] = lam_used;
-    trace_row[2] = acc ? 1.0 : 0.0;
-    for (int i = 0; i < P; ++i) trace_row[3 + i] = si[U::oTt + i];
-  }
-  for (int i = 0; i < P; ++i) dec[i] = si[U::oTt + i];
-  if (chi_cur == 0.0) {
-    status = 1;
-  } else {
-    double delta[P];
-    bool ok = false;
-    // (at most 25 rounds: lambda >= 1e-12 grows tenfold per breakdown)
-    while (true) {
-      if (lam > 1e12) {
-        status = 2;
-        break;
-      }
-      if (uf_solve<P>(s_N, s_g, lam, delta)) {
-        ok = true;
-        break;
-      }
-      lam *= 10.0;
-    }
-    if (ok) {
-      double worst = 0.0;
-      bool nan = false;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const double t = __builtin_fmax(s_th[6 * c + 3] + s_th[6 * c + 5], 1.0);
-        // (|F| = 0 would make 0 / 0, which fmax drops: the floor keeps F in the test)
-        worst = __builtin_fmax(worst, __builtin_fabs(delta[6 * c]) /
-                                          __builtin_fmax(__builtin_fabs(s_th[6 * c]), 1e-300));
-        worst = __builtin_fmax(worst, __builtin_fmax(__builtin_fabs(delta[6 * c + 1]),
-                                                     __builtin_fabs(delta[6 * c + 2])));
-#pragma unroll
-        for (int i = 3; i < 6; ++i)
-          worst = __builtin_fmax(worst, __builtin_fabs(delta[6 * c + i]) / t);
-      }
-#pragma unroll
-      for (int i = 0; i < P; ++i) nan = nan || delta[i] != delta[i];
-      if (!nan && worst <= xtol) {
-        status = 1;
-      } else if (it == n_iter) {
-        status = 0;
-      } else {
-#pragma unroll
-        for (int i = 0; i < P; ++i) dec[i] = s_th[i] + delta[i];
-        eval = true;
-      }
-    }
-  }
-  if (store) {
-    for (int i = 0; i < P; ++i) so[i] = s_th[i];
-    so[U::oChi] = chi_cur;
-    so[U::oLam] = lam;
-    so[U::oLamT] = eval ? lam : lam_used;
-    so[U::oStat] = (double)status;
-    so[U::oIt] = (double)it;
-    so[U::oCnt] = cnt;
-    for (int i = 0; i < P; ++i) so[U::oTt + i] = dec[i];
-    for (int i = 0; i < T; ++i) so[U::oN + i] = s_N[i];
-    for (int i = 0; i < P; ++i) so[U::oG + i] = s_g[i];
-    for (int i = U::oG + P; i < U::S; ++i) so[i] = 0.0;
-  }
-  return eval;
-}
-
-// launch `it` of n_iter + 1: partials p_in -> p_out ([n_maps][Q][tiles]), state s_in -> s_out
-template <int NC>
-__global__ __launch_bounds__(kUfB) void uvfit_step_kernel(
+__global__ __launch_bounds__(kLmB) void uvfit_step_kernel(
     const double* __restrict__ vis, const double* __restrict__ u, const double* __restrict__ v,
     const double* __restrict__ w, int64_t w_stride, const double* __restrict__ su,
-    const double* __restrict__ sv, int n_vis, int tiles, unsigned free_bits, double lambda0,
-    double xtol, int it, int n_iter, const double* __restrict__ p_in, double* __restrict__ p_out,
-    const double* __restrict__ s_in, double* __restrict__ s_out, double* __restrict__ theta,
-    double* __restrict__ chi2, double* __restrict__ cov, int* __restrict__ o_nvis,
-    int* __restrict__ o_niter, int* __restrict__ o_status, double* __restrict__ trace) {
-  using U = Uf<NC>;
+    const double* __restrict__ sv, int n_vis, unsigned free_bits, LmLaunch lm,
+    const double* __restrict__ p_in, double* __restrict__ p_out, const double* __restrict__ s_in,
+    double* __restrict__ s_out) {
+  using U = LmState<6 * NC>;
   constexpr int P = U::P, T = U::T, Q = U::Q;
-  __shared__ double s_a[kUfC * kUfRow];
-  __shared__ double s_b[kUfC * 8];
-  __shared__ double s_tot[Q];
-  __shared__ double s_dec[P + 1];
-  __shared__ double s_th[P];
-  __shared__ double s_N[T];
-  __shared__ double s_g[P];
+  __shared__ LmLds<P> l;
+  __shared__ LmCur<P> cur;
   const int tid = threadIdx.x;
-  const int tile = (int)(blockIdx.x % (unsigned)tiles), m = (int)(blockIdx.x / (unsigned)tiles);
-  const double* __restrict__ si = s_in + (int64_t)m * U::S;
-  double* __restrict__ so = s_out + (int64_t)m * U::S;
-  const bool store = tile == 0;
-  if (it == 0) {
-    if (tid == 0) {
-      bool good = true;
-      for (int i = 0; i < P; ++i) {
-        const double t = theta[P * m + i];
-        good = good && finite_d(t);
-        s_dec[i] = t;
-      }
-      for (int c = 0; c < NC; ++c)
-        good = good && uf_psd(s_dec[6 * c + 3], s_dec[6 * c + 4], s_dec[6 * c + 5]);
-      s_dec[P] = good ? 1.0 : 0.0;
-      if (store) {
-        for (int i = 0; i < U::S; ++i) so[i] = 0.0;
-        for (int i = 0; i < P; ++i) so[i] = so[U::oTt + i] = s_dec[i];
-        so[U::oChi] = __builtin_inf();
-        so[U::oLam] = so[U::oLamT] = lambda0;
-        so[U::oStat] = good ? (double)kUfRun : 3.0;
-      }
-    }
-  } else if ((int)si[U::oStat] != kUfRun) {
-    // a finished map: nothing but the carry (the status is workgroup-uniform)
-    if (store && tid == 0) {
-      for (int i = 0; i < U::S; ++i) so[i] = si[i];
-      if (it == n_iter) uf_outputs<NC>(so, m, theta, chi2, cov, o_nvis, o_niter, o_status);
-    }
-    return;
-  } else {
-    double acc[Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) acc[q] = 0.0;
-    const double* __restrict__ pm = p_in + (int64_t)m * Q * tiles;
-    for (int i = tid; i < tiles; i += kUfB) {
-#pragma unroll
-      for (int q = 0; q < Q; ++q) acc[q] += pm[(int64_t)q * tiles + i];
-    }
-    uf_block_sum<Q>(acc, s_a, s_b, s_tot);
-    if (tid == 0) {
-      double* row = trace ? trace + ((int64_t)m * n_iter + (it - 1)) * (3 + P) : nullptr;
-      const bool eval = uf_decide<NC>(si, s_tot, so, store, it, n_iter, xtol, free_bits, row, s_dec,
-                                      s_th, s_N, s_g);
-      s_dec[P] = eval ? 1.0 : 0.0;
-      if (store && it == n_iter) uf_outputs<NC>(so, m, theta, chi2, cov, o_nvis, o_niter, o_status);
-    }
-  }
-  __syncthreads();
-  if (s_dec[P] == 0.0) return;                       // (workgroup-uniform)
+  const int tile = (int)(blockIdx.x % (unsigned)lm.tiles), m = (int)(blockIdx.x / (unsigned)lm.tiles);
+  if (!lm_begin<UfPolicy<NC>>(lm, p_in, s_in, s_out, tile, m, free_bits, l, cur)) return;
   double th[P];
 #pragma unroll
-  for (int i = 0; i < P; ++i) th[i] = s_dec[i];
+  for (int i = 0; i < P; ++i) th[i] = l.dec[i];
   const double sum = su[m], svm = sv[m];
   const double* __restrict__ vm = vis + (int64_t)m * n_vis * 2;
   const double* __restrict__ wm = w ? w + (int64_t)m * w_stride : nullptr;
@@ -377,7 +92,7 @@ __global__ __launch_bounds__(kUfB) void uvfit_step_kernel(
 #pragma unroll 1
   for (int j = 0; j < 4; ++j) {
     // (64-bit: tile * 1024 + 1023 may pass 2^31 for n_vis near it)
-    const int64_t k = (int64_t)tile * kUfT + (tid + kUfB * j);
+    const int64_t k = (int64_t)tile * kLmT + (tid + kLmB * j);
     if (k >= n_vis) continue;
     const double uk = u[k], vk = v[k], wk = wm ? wm[k] : 1.0;
     const double vr = vm[2 * k], vi = vm[2 * k + 1];
@@ -424,9 +139,9 @@ __global__ __launch_bounds__(kUfB) void uvfit_step_kernel(
       const double wr = wk * Jr[p], wi = wk * Ji[p];
 #pragma unroll
       for (int c = p; c < P; ++c) {
-        double s = acc[1 + uf_tri<P>(p, c)];
+        double s = acc[1 + lm_tri<P>(p, c)];
         s = __builtin_fma(wr, Jr[c], s);
-        acc[1 + uf_tri<P>(p, c)] = __builtin_fma(wi, Ji[c], s);
+        acc[1 + lm_tri<P>(p, c)] = __builtin_fma(wi, Ji[c], s);
       }
       double s = acc[1 + T + p];
       s = __builtin_fma(wr, rr, s);
@@ -434,36 +149,23 @@ __global__ __launch_bounds__(kUfB) void uvfit_step_kernel(
     }
     acc[Q - 1] += 1.0;
   }
-  uf_block_sum<Q>(acc, s_a, s_b, s_tot);
-  for (int q = tid; q < Q; q += kUfB) p_out[((int64_t)m * Q + q) * tiles + tile] = s_tot[q];
+  lm_store_partials<Q>(acc, p_out, lm.tiles, tile, m, l);
 }
 
 template <int NC>
 static hipError_t uvfit_launch_n(const double* vis, int n_maps, int n_vis, const double* d_su,
                                  const double* d_sv, const double* u, const double* v,
-                                 const double* w, int w_maps, unsigned free_bits, double* theta,
-                                 double lambda0, double xtol, int n_iter, double* chi2, double* cov,
-                                 int32_t* nvis, int32_t* niter, int32_t* status, double* trace,
-                                 void* work, hipStream_t st) {
-  using U = Uf<NC>;
-  const UvfitTiling t = uvfit_tiling(n_maps, n_vis);
-  const int tiles = (int)t.tiles;
-  const unsigned nb = (unsigned)t.workgroups;
-  // workspace: sums [2][n_maps][Q][tiles], then state [2][n_maps][S]
-  const int64_t ph = t.workgroups * U::Q, sh = (int64_t)n_maps * U::S;
-  double* pv = (double*)work;
-  double* sv = pv + 2 * ph;
-  const int64_t w_stride = w && w_maps == n_maps && n_maps > 1 ? n_vis : 0;
-  hipError_t err = hipSuccess;
-  for (int it = 0; it <= n_iter && err == hipSuccess; ++it) {
-    const int in = (it + 1) & 1, out = it & 1;
-    hipLaunchKernelGGL(uvfit_step_kernel<NC>, dim3(nb), dim3(kUfB), 0, st, vis, u, v, w, w_stride,
-                       d_su, d_sv, n_vis, tiles, free_bits, lambda0, xtol, it, n_iter, pv + in * ph,
-                       pv + out * ph, sv + in * sh, sv + out * sh, theta, chi2, cov, nvis, niter,
-                       status, trace);
-    err = hipGetLastError();
-  }
-  return err;
+                                 const double* w, int64_t w_stride, unsigned free_bits,
+                                 const LmTiling& t, double* theta, double lambda0, double xtol,
+                                 int n_iter, double* chi2, double* cov, int32_t* nvis, int32_t* niter,
+                                 int32_t* status, double* trace, void* work, hipStream_t st) {
+  using U = LmState<6 * NC>;
+  return lm_launch_loop(
+      t, n_maps, U::Q, U::S, lambda0, xtol, n_iter, theta, chi2, cov, nvis, niter, status, trace, work,
+      [&](const LmLaunch& a, const double* p_in, double* p_out, const double* s_in, double* s_out) {
+        hipLaunchKernelGGL(uvfit_step_kernel<NC>, dim3((unsigned)t.workgroups), dim3(kLmB), 0, st, vis,
+                           u, v, w, w_stride, d_su, d_sv, n_vis, free_bits, a, p_in, p_out, s_in, s_out);
+      });
 }
 
 hipError_t uvfit_launch(const double* vis, int n_maps, int n_vis, const double* d_su,
@@ -472,10 +174,12 @@ hipError_t uvfit_launch(const double* vis, int n_maps, int n_vis, const double* 
                         double xtol, int n_iter, double* chi2, double* cov, int32_t* nvis,
                         int32_t* niter, int32_t* status, double* trace, void* work,
                         hipStream_t st) {
+  const LmTiling t = lm_tiling(n_maps, n_vis);
+  const int64_t w_stride = w && w_maps == n_maps && n_maps > 1 ? n_vis : 0;
   if (n_comp == 1)
-    return uvfit_launch_n<1>(vis, n_maps, n_vis, d_su, d_sv, u, v, w, w_maps, free_bits, theta,
+    return uvfit_launch_n<1>(vis, n_maps, n_vis, d_su, d_sv, u, v, w, w_stride, free_bits, t, theta,
                              lambda0, xtol, n_iter, chi2, cov, nvis, niter, status, trace, work, st);
-  return uvfit_launch_n<2>(vis, n_maps, n_vis, d_su, d_sv, u, v, w, w_maps, free_bits, theta,
+  return uvfit_launch_n<2>(vis, n_maps, n_vis, d_su, d_sv, u, v, w, w_stride, free_bits, t, theta,
                            lambda0, xtol, n_iter, chi2, cov, nvis, niter, status, trace, work, st);
 }
 

@@ -42,12 +42,12 @@ for every iteration t (u = 2^-53):
 `follow` returns the worst error / bound it saw; anything else fails an assertion."""
 import numpy as np
 
-LD = np.longdouble
-U53 = 2.0 ** -53
+from tests.lm_ref import (LAM_MAX, LAM_MIN, LD, U53, cholesky_solve, damped, pack, pivots_clear,
+                          tri_list, unpack)
+
 TILE, REDUCE_PASS, NSUM, NSTATE = 1024, 256, 29, 48
 EXP_RTOL = 1e-14
 C_CHOL = 22.0
-LAM_MIN, LAM_MAX = 1e-12, 1e12
 # the library's refusals, in the order check_gaussfit makes them; the workspace comes last
 MSG = {"nulls": "rjp_gaussfit: NULL images, box, parameters or outputs",
        "sizes": "rjp_gaussfit: n_maps, nx and nz must be positive",
@@ -62,18 +62,10 @@ PARTS = {}                   # the worst error / bound of checks (a), (c) and d_
 
 def tri(i, j):
     """Index of (i, j), i <= j, in the packed upper triangle, row by row."""
-    return i * 6 - i * (i - 1) // 2 + (j - i)
+    return tri_list(6).index((i, j))
 
 
-TRI = [(i, j) for i in range(6) for j in range(i, 6)]
-
-
-def unpack(cov):
-    """The symmetric 6 x 6 matrix of a packed upper triangle."""
-    M = np.zeros((6, 6), dtype=np.asarray(cov).dtype)
-    for k, (i, j) in enumerate(TRI):
-        M[i, j] = M[j, i] = cov[k]
-    return M
+TRI = tri_list(6)
 
 
 def box_pixels(box):
@@ -160,43 +152,12 @@ class Sums:
                          aG * (np.abs(2 * B * dx) + np.abs(2 * C * dz)), aG * dx * dx,
                          2 * aG * np.abs(dx * dz), aG * dz * dz])
         eJ = Jabs * (relG + 6 * u) + LD(1e-300)
-        pack = lambda F: np.array([F[a, b] for a, b in TRI], dtype=LD)
         ar = np.abs(r)
         self.N = pack(J @ J.T)
         cross = Jabs @ eJ.T
         self.bN = LD(1.01) * pack(cross + cross.T + eJ @ eJ.T + (u + D) * (Jabs @ Jabs.T))
         self.g = J @ r
         self.bg = LD(1.01) * (Jabs @ er + eJ @ ar + eJ @ er + (u + D) * (Jabs @ ar))
-
-
-def damped(N, lam, identity=False):
-    """M = N + lam diag N as a 6 x 6 matrix (in N's dtype)."""
-    M = unpack(N)
-    d = np.diag(M).copy()
-    for i in range(6):
-        M[i, i] = d[i] + type(d[i])(lam) * (1 if identity else d[i])
-    return M
-
-
-def cholesky_solve(M, g):
-    """(delta, ok) by an unblocked Cholesky in M's dtype; ok False: a pivot is not > 0."""
-    dt = M.dtype.type
-    L = np.zeros((6, 6), dtype=M.dtype)
-    ok = True
-    with np.errstate(all="ignore"):
-        for j in range(6):
-            d = M[j, j] - np.dot(L[j, :j], L[j, :j])
-            ok = ok and bool(d > 0)
-            L[j, j] = np.sqrt(d)
-            for i in range(j + 1, 6):
-                L[i, j] = (M[i, j] - np.dot(L[i, :j], L[j, :j])) / L[j, j]
-        y = np.zeros(6, dtype=M.dtype)
-        for i in range(6):
-            y[i] = (dt(g[i]) - np.dot(L[i, :i], y[:i])) / L[i, i]
-        x = np.zeros(6, dtype=M.dtype)
-        for i in range(5, -1, -1):
-            x[i] = (y[i] - np.dot(L[i + 1:, i], x[i + 1:])) / L[i, i]
-    return x, ok
 
 
 def scales(th):
@@ -206,9 +167,9 @@ def scales(th):
 
 def step_bound(s, lam, delta, theta_next):
     """The bound of (c) on |M delta - g|, per component (long double)."""
-    M = damped(s.N, LD(lam))
+    M = damped(unpack(s.N, 6), LD(lam))
     ad = np.abs(np.asarray(delta, dtype=LD))
-    bM = unpack(s.bN)
+    bM = unpack(s.bN, 6)
     for i in range(6):
         bM[i, i] *= 1 + LD(lam)
     u = LD(U53)
@@ -260,7 +221,7 @@ def emulate(img, box, mask, theta0, lambda0, xtol, n_iter, poison=None, mistake=
             if lam > LAM_MAX:
                 status = 2
                 break
-            delta, ok = cholesky_solve(damped(N, lam, identity=mistake == "lam_identity"), g)
+            delta, ok = cholesky_solve(damped(unpack(N, 6), lam, identity=mistake == "lam_identity"), g)
             if ok:
                 break
             lam = lam * f(10.0)
@@ -337,7 +298,7 @@ def follow(img, box, mask, theta0, lambda0, xtol, n_iter, out, poison):
         if last:
             # (the device's own breakdowns are not on record: a lambda whose pivots are all clear
             # cannot have broken down)
-            while lam <= LAM_MAX and status == 2 and not _pivots_clear(damped(s_cur.N, LD(lam))):
+            while lam <= LAM_MAX and status == 2 and not pivots_clear(damped(unpack(s_cur.N, 6), LD(lam))):
                 lam = lam * np.float64(10.0)
             assert (status == 2) == bool(lam > LAM_MAX), ("status 2 iff lambda > 1e12", status, lam)
             if status == 2:
@@ -346,11 +307,11 @@ def follow(img, box, mask, theta0, lambda0, xtol, n_iter, out, poison):
             j = 0
             while lam != trace[t + 1, 1]:
                 assert j < 25 and lam < trace[t + 1, 1] and \
-                    not _pivots_clear(damped(s_cur.N, LD(lam))), \
+                    not pivots_clear(damped(unpack(s_cur.N, 6), LD(lam))), \
                     ("lambda of row %d" % (t + 1), trace[t + 1, 1], lam)
                 lam, j = lam * np.float64(10.0), j + 1
             assert lam <= LAM_MAX
-        M = damped(s_cur.N, LD(lam))
+        M = damped(unpack(s_cur.N, 6), LD(lam))
         d_ref, ok = cholesky_solve(M, s_cur.g)
         if last and not ok:
             break                                     # (a breakdown in the last launch: no step to judge)
@@ -387,17 +348,3 @@ def follow(img, box, mask, theta0, lambda0, xtol, n_iter, out, poison):
     assert ratio <= 1.0, ("d_cov", ratio)
     PARTS["cov"] = max(PARTS.get("cov", 0.0), ratio)
     return max(worst, ratio)
-
-
-def _pivots_clear(M):
-    """Every Cholesky pivot of M (long double) above 1e-6 of its diagonal entry."""
-    L = np.zeros((6, 6), dtype=M.dtype)
-    with np.errstate(all="ignore"):
-        for j in range(6):
-            d = M[j, j] - np.dot(L[j, :j], L[j, :j])
-            if not d > LD(1e-6) * M[j, j]:
-                return False
-            L[j, j] = np.sqrt(d)
-            for i in range(j + 1, 6):
-                L[i, j] = (M[i, j] - np.dot(L[i, :j], L[j, :j])) / L[j, j]
-    return True

@@ -69,10 +69,10 @@ them:
 `follow` returns the worst error / bound it saw; anything else fails an assertion."""
 import numpy as np
 
-LD = np.longdouble
-U53 = 2.0 ** -53
+from tests.lm_ref import (LAM_MAX, LAM_MIN, LD, U53, cholesky_solve, damped, pack, pivots_clear,
+                          tri_list, unpack)
+
 EXP_RTOL = 1e-14
-LAM_MIN, LAM_MAX = 1e-12, 1e12
 MAX_COMP, MAX_CHAN, LANES = 2, 4096, 64
 MSG_M = {"nulls": "rjp_cube_moments: NULL cube, axis, widths or output",
          "sizes": "rjp_cube_moments: n_pix and n_chan must be positive",
@@ -102,21 +102,6 @@ def _part(k, r):
 
 def workgroups(n_pix):
     return (n_pix + LANES - 1) // LANES
-
-
-def tri_list(P):
-    return [(i, j) for i in range(P) for j in range(i, P)]
-
-
-def unpack(cov, P):
-    M = np.zeros((P, P), dtype=np.asarray(cov).dtype)
-    for k, (i, j) in enumerate(tri_list(P)):
-        M[i, j] = M[j, i] = cov[k]
-    return M
-
-
-def pack(F):
-    return np.array([F[a, b] for a, b in tri_list(F.shape[0])], dtype=F.dtype)
 
 
 # ---- moments -----------------------------------------------------------------------------------
@@ -320,53 +305,6 @@ class Sums:
         return s
 
 
-def damped(N, lam, identity=False):
-    """M = N + lam diag N ([..., P, P], in N's dtype)."""
-    M = np.array(N, copy=True)
-    P = M.shape[-1]
-    for i in range(P):
-        M[..., i, i] = N[..., i, i] + M.dtype.type(1) * lam * (1 if identity else N[..., i, i])
-    return M
-
-
-def cholesky_solve(M, g, want_L=False):
-    """(delta, ok) by an unblocked Cholesky in M's dtype, batched over leading axes; ok False: a
-    pivot is not > 0.  `want_L`: (delta, ok, L)."""
-    M, g = np.asarray(M), np.asarray(g, dtype=M.dtype)
-    P = M.shape[-1]
-    L = np.zeros_like(M)
-    ok = np.ones(M.shape[:-2], dtype=bool)
-    with np.errstate(all="ignore"):
-        for j in range(P):
-            d = M[..., j, j] - np.sum(L[..., j, :j] * L[..., j, :j], axis=-1)
-            ok &= d > 0
-            L[..., j, j] = np.sqrt(d)
-            for i in range(j + 1, P):
-                L[..., i, j] = (M[..., i, j] - np.sum(L[..., i, :j] * L[..., j, :j], axis=-1)) / L[..., j, j]
-        y = np.zeros_like(g)
-        for i in range(P):
-            y[..., i] = (g[..., i] - np.sum(L[..., i, :i] * y[..., :i], axis=-1)) / L[..., i, i]
-        x = np.zeros_like(g)
-        for i in range(P - 1, -1, -1):
-            x[..., i] = (y[..., i] - np.sum(L[..., i + 1:, i] * x[..., i + 1:], axis=-1)) / L[..., i, i]
-    return (x, ok, L) if want_L else (x, ok)
-
-
-def _pivots_clear(M):
-    """Every Cholesky pivot of M (long double) above 1e-6 of its diagonal entry."""
-    P = M.shape[0]
-    L = np.zeros((P, P), dtype=M.dtype)
-    with np.errstate(all="ignore"):
-        for j in range(P):
-            d = M[j, j] - np.dot(L[j, :j], L[j, :j])
-            if not d > LD(1e-6) * M[j, j]:
-                return False
-            L[j, j] = np.sqrt(d)
-            for i in range(j + 1, P):
-                L[i, j] = (M[i, j] - np.dot(L[i, :j], L[j, :j])) / L[j, j]
-    return True
-
-
 def step_bound(s, lam, delta, theta_next):
     """The bound of (c) on |M delta - g|, per component (long double)."""
     P = len(delta)
@@ -555,7 +493,7 @@ def follow(y, x, w, x_ref, theta0, free, lambda0, xtol, n_iter, out, poison, sum
         if last:
             # (the device's own breakdowns are not on record: a lambda whose pivots are all clear
             # cannot have broken down)
-            while lam <= LAM_MAX and status == 2 and not _pivots_clear(damped(s_cur.N, LD(lam))):
+            while lam <= LAM_MAX and status == 2 and not pivots_clear(damped(s_cur.N, LD(lam))):
                 lam = lam * np.float64(10.0)
             assert (status == 2) == bool(lam > LAM_MAX), ("status 2 iff lambda > 1e12", status, lam)
             if status == 2:
@@ -564,7 +502,7 @@ def follow(y, x, w, x_ref, theta0, free, lambda0, xtol, n_iter, out, poison, sum
             j = 0
             while lam != trace[t + 1, 1]:
                 assert j < 25 and lam < trace[t + 1, 1] and \
-                    not _pivots_clear(damped(s_cur.N, LD(lam))), \
+                    not pivots_clear(damped(s_cur.N, LD(lam))), \
                     ("lambda of row %d" % (t + 1), trace[t + 1, 1], lam)
                 lam, j = lam * np.float64(10.0), j + 1
             assert lam <= LAM_MAX

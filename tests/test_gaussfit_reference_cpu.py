@@ -71,7 +71,7 @@ def test_two_pixels_by_hand():
     J0 = np.array([0.5, 0, -2 * ln2, 0, 0, -1], dtype=LD)
     J1 = np.array([1, 0, 0, 0, 0, 0], dtype=LD)
     N = np.outer(J0, J0) + np.outer(J1, J1)
-    assert np.max(np.abs(K.unpack(s.N) - N)) <= 1e-15
+    assert np.max(np.abs(K.unpack(s.N, 6) - N)) <= 1e-15
     assert np.max(np.abs(s.g - J0 * LD(-0.5))) <= 1e-15
     assert s.bchi > 0 and np.all(s.bN > 0) and np.all(s.bg > 0)
     # fewer than 6 counting pixels: degenerate, nothing but the status
@@ -191,7 +191,7 @@ def test_gauss_results_sizes_and_flux():
     src = E.beam_quadratic(0.50, 0.25, -20., CELL)
     q = np.linalg.inv(2 * (_sigma(beam) + _sigma(src)))
     conv = [q[0, 0], q[0, 1], q[1, 1]]
-    eye = K.unpack(np.zeros(21))
+    eye = K.unpack(np.zeros(21), 6)
     cov = [1.0 if i == j else 0.0 for i, j in K.TRI]
     r, p = E.gauss_results([[1.5, 30.2, 40.7] + conv, [1.5, 30.2, 40.7] + list(beam)], [cov, cov],
                            [0.0, 0.0], [100, 100], beam, CELL, shape=(64, 80), status=[1, 1])

@@ -52,11 +52,11 @@ iteration t (u = 2^-53, P = 6 n_comp):
 `follow` returns the worst error / bound it saw; anything else fails an assertion."""
 import numpy as np
 
-LD = np.longdouble
-U53 = 2.0 ** -53
+from tests.lm_ref import (LAM_MAX, LAM_MIN, LD, U53, cholesky_solve, damped, pack, pivots_clear,
+                          tri_list, unpack)
+
 TILE, REDUCE_PASS = 1024, 256
 EXP_RTOL, SINCOS_ATOL = 1e-14, 2.1e-14
-LAM_MIN, LAM_MAX = 1e-12, 1e12
 MAX_COMP = 2
 PI_LD = LD("3.14159265358979323846264338327950288")
 TWO_PI2 = 2 * PI_LD * PI_LD
@@ -79,23 +79,6 @@ def sizes(n_comp):
     P = 6 * n_comp
     T = P * (P + 1) // 2
     return P, T, 1 + T + P + 1, (3 * P + 6 + T + 7) // 8 * 8
-
-
-def tri_list(P):
-    return [(i, j) for i in range(P) for j in range(i, P)]
-
-
-def unpack(cov, P):
-    """The symmetric P x P matrix of a packed upper triangle."""
-    M = np.zeros((P, P), dtype=np.asarray(cov).dtype)
-    for k, (i, j) in enumerate(tri_list(P)):
-        M[i, j] = M[j, i] = cov[k]
-    return M
-
-
-def pack(F):
-    P = F.shape[0]
-    return np.array([F[a, b] for a, b in tri_list(P)], dtype=F.dtype)
 
 
 def tiling(n_maps, n_vis):
@@ -238,37 +221,6 @@ class Sums:
         self.N, self.bN, self.g, self.bg = pack(N), pack(bN), g, bg
 
 
-def damped(N, lam, P, identity=False):
-    """M = N + lam diag N as a P x P matrix (in N's dtype)."""
-    M = unpack(N, P)
-    d = np.diag(M).copy()
-    for i in range(P):
-        M[i, i] = d[i] + type(d[i])(lam) * (1 if identity else d[i])
-    return M
-
-
-def cholesky_solve(M, g):
-    """(delta, ok) by an unblocked Cholesky in M's dtype; ok False: a pivot is not > 0."""
-    dt = M.dtype.type
-    P = M.shape[0]
-    L = np.zeros((P, P), dtype=M.dtype)
-    ok = True
-    with np.errstate(all="ignore"):
-        for j in range(P):
-            d = M[j, j] - np.dot(L[j, :j], L[j, :j])
-            ok = ok and bool(d > 0)
-            L[j, j] = np.sqrt(d)
-            for i in range(j + 1, P):
-                L[i, j] = (M[i, j] - np.dot(L[i, :j], L[j, :j])) / L[j, j]
-        y = np.zeros(P, dtype=M.dtype)
-        for i in range(P):
-            y[i] = (dt(g[i]) - np.dot(L[i, :i], y[:i])) / L[i, i]
-        x = np.zeros(P, dtype=M.dtype)
-        for i in range(P - 1, -1, -1):
-            x[i] = (y[i] - np.dot(L[i + 1:, i], x[i + 1:])) / L[i, i]
-    return x, ok
-
-
 def scales(th):
     out = []
     for c in range(len(th) // 6):
@@ -280,7 +232,7 @@ def scales(th):
 def step_bound(s, lam, delta, theta_next):
     """The bound of (c) on |M delta - g|, per component (long double)."""
     P = len(delta)
-    M = damped(s.N, LD(lam), P)
+    M = damped(unpack(s.N, P), LD(lam))
     ad = np.abs(np.asarray(delta, dtype=LD))
     bM = unpack(s.bN, P)
     for i in range(P):
@@ -347,7 +299,7 @@ def emulate(data, n_vis, theta0, free, lambda0, xtol, n_iter, poison=None, mista
             if lam > LAM_MAX:
                 status = 2
                 break
-            delta, ok = cholesky_solve(damped(N, lam, P, identity=mistake == "lam_identity"), g)
+            delta, ok = cholesky_solve(damped(unpack(N, P), lam, identity=mistake == "lam_identity"), g)
             if ok:
                 break
             lam = lam * f(10.0)
@@ -427,7 +379,7 @@ def follow(data, n_vis, theta0, free, lambda0, xtol, n_iter, out, poison):
         if last:
             # (the device's own breakdowns are not on record: a lambda whose pivots are all clear
             # cannot have broken down)
-            while lam <= LAM_MAX and status == 2 and not _pivots_clear(damped(s_cur.N, LD(lam), P)):
+            while lam <= LAM_MAX and status == 2 and not pivots_clear(damped(unpack(s_cur.N, P), LD(lam))):
                 lam = lam * np.float64(10.0)
             assert (status == 2) == bool(lam > LAM_MAX), ("status 2 iff lambda > 1e12", status, lam)
             if status == 2:
@@ -436,11 +388,11 @@ def follow(data, n_vis, theta0, free, lambda0, xtol, n_iter, out, poison):
             j = 0
             while lam != trace[t + 1, 1]:
                 assert j < 25 and lam < trace[t + 1, 1] and \
-                    not _pivots_clear(damped(s_cur.N, LD(lam), P)), \
+                    not pivots_clear(damped(unpack(s_cur.N, P), LD(lam))), \
                     ("lambda of row %d" % (t + 1), trace[t + 1, 1], lam)
                 lam, j = lam * np.float64(10.0), j + 1
             assert lam <= LAM_MAX
-        M = damped(s_cur.N, LD(lam), P)
+        M = damped(unpack(s_cur.N, P), LD(lam))
         d_ref, ok = cholesky_solve(M, s_cur.g)
         if last and not ok:
             break                                     # (a breakdown in the last launch: no step to judge)
@@ -481,18 +433,3 @@ def follow(data, n_vis, theta0, free, lambda0, xtol, n_iter, out, poison):
     assert ratio <= 1.0, ("d_cov", ratio)
     PARTS["cov"] = max(PARTS.get("cov", 0.0), ratio)
     return max(worst, ratio)
-
-
-def _pivots_clear(M):
-    """Every Cholesky pivot of M (long double) above 1e-6 of its diagonal entry."""
-    P = M.shape[0]
-    L = np.zeros((P, P), dtype=M.dtype)
-    with np.errstate(all="ignore"):
-        for j in range(P):
-            d = M[j, j] - np.dot(L[j, :j], L[j, :j])
-            if not d > LD(1e-6) * M[j, j]:
-                return False
-            L[j, j] = np.sqrt(d)
-            for i in range(j + 1, P):
-                L[i, j] = (M[i, j] - np.dot(L[i, :j], L[j, :j])) / L[j, j]
-    return True
