@@ -1373,6 +1373,94 @@ int64_t rjp_specfit(rjp_ctx* ctx, const double* d_cube, int64_t n_pix, int32_t n
                     double xtol, int32_t n_iter, double* d_chi2, double* d_cov, int32_t* d_nchan,
                     int32_t* d_niter, int32_t* d_status, double* d_trace, void* stream);
 
+/* ---- K22: antenna-based complex gains (corrupt, gaincal, applycal) ------------------------------
+ * The one corruption that dominates real centimetre-wave data, and the step that removes it: per
+ * antenna and per solution interval a complex gain, D_pq = g_p conj(g_q) M_pq.  (CASA simobserve's
+ * `corrupt`, gaincal and applycal; CASA is not at hand: THIS COMMENT IS THE DEFINITION, no parity
+ * is claimed.)
+ *
+ * Layouts.  Visibilities [n_maps][n_t][n_bl][2] (Re, Im) as rjp_vis writes them for the n_t n_bl
+ * points of rjp_uv_tracks: n_bl = n_ant (n_ant - 1) / 2 pairs (p < q), p-major ((0,1), (0,2), ...,
+ * (1,2), ...).  Gains [g_maps][n_sol][n_ant][2].  h_sol [n_t] (HOST, int32): the solution interval
+ * of every integration, h_sol[0] = 0, rising in steps of 0 or 1, n_sol = h_sol[n_t - 1] + 1 -- every
+ * interval is a non-empty contiguous range of integrations.  2 <= n_ant <= RJP_GAINCAL_MAX_ANT.
+ *
+ * rjp_gain_apply.  One launch, one thread per visibility, no atomics.  With g_p = (pr, pi), g_q =
+ * (qr, qi) of the visibility's interval (map 0's when g_maps = 1) and V = (vr, vi):
+ *   cr = fma(pr, qr, pi qi)       ci = fma(pi, qr, -(pr qi))                  (c = g_p conj g_q)
+ *   mode 0 (corrupt)   out = (fma(cr, vr, -(ci vi)), fma(cr, vi, ci vr))      (c V)
+ *   mode 1 (correct)   n2 = fma(cr, cr, ci ci)
+ *                      out = (fma(vr, cr, vi ci) / n2, fma(vi, cr, -(vr ci)) / n2)   (V conj c / |c|^2)
+ * d_out may be d_vis.  A NaN gain or a NaN visibility gives a NaN visibility: the flag that
+ * rjp_vis_adjoint, rjp_uv_weights and rjp_uvfit honour.  Returns the workgroups of its launch.
+ *
+ * rjp_gaincal.  StefCal (Salvini & Wijnholds 2014) for every (map m, interval s) at once.
+ *   d_model [model_maps][n_t][n_bl][2], model_maps 1 or n_maps; d_w NULL (all ones) or
+ *   [w_maps][n_t][n_bl], w_maps 1 or n_maps; d_gains [n_maps][n_sol][n_ant][2] IN PLACE.
+ * A visibility (m, t, pq) COUNTS when Re D, Im D, Re M, Im M and w are finite, w > 0 and
+ * m2 = fma(Mr, Mr, Mi Mi) > 0.
+ * 1. Accumulate (the pass over the data).  Per (m, s, pq), over the counting integrations of the
+ *    interval in ascending t, from 0:
+ *      Ar = fma(w, fma(Dr, Mr, Di Mi), Ar)   Ai = fma(w, fma(Di, Mr, -(Dr Mi)), Ai)   (w D conj M)
+ *      B  = fma(w, m2, B)                    n_pq += 1
+ *    and A_qp = conj(A_pq), B_qp = B_pq.  They go to the workspace: [n_maps n_sol][3][n_bl]
+ *    doubles (Re A, Im A, B), then [n_maps n_sol][n_ant][2] doubles (the start gains of the
+ *    solutions that were solved), then [n_maps n_sol][n_bl] int32 (n_pq).
+ * 2. Live antennas.  All antennas start live.  In a sweep every live antenna p counts its partners
+ *    q != p that are live and have B_pq > 0, by the flags as they stood BEFORE the sweep; all with
+ *    fewer than min_bl leave together; sweeps repeat until one removes nothing.  (The set is the
+ *    largest one in which every member has min_bl such partners; no other order reaches another.)
+ *    Fewer than 3 live antennas (mode 0, amplitude and phase) or 2 (mode 1, phase only), or a live
+ *    antenna whose start gain is not finite or is (0, 0): status 3 -- every gain of that solution
+ *    becomes NaN, d_nvis and d_status are written, NOTHING else of that solution is.
+ * 3. Iterate.  For k = 1, 2, ... and every live p, over the live q != p in ascending q as FOUR
+ *    chains, q mod 4 = 0, 1, 2, 3, each from 0, combined (c0 + c1) + (c2 + c3) -- an order that
+ *    depends on n_ant and the live set alone.  With A_pq = (ar, ai), g_q = (qr, qi):
+ *      nr = fma(qr, ar, nr); nr = fma(-qi, ai, nr); ni = fma(qr, ai, ni); ni = fma(qi, ar, ni)
+ *      mode 0:  dn = fma(fma(qr, qr, qi qi), B_pq, dn)
+ *      div = dn (mode 0) or sqrt(fma(nr, nr, ni ni)) (mode 1);   h = (nr / div, ni / div)
+ *      g' = h for odd k, (0.5 (hr + gr), 0.5 (hi + gi)) for even k.
+ *    A div that is not finite and > 0, or an h that is not finite, at any live antenna: status 2,
+ *    the gains stay at g, d_niter = k - 1.  Else g <- g', d_niter = k, and with |z| =
+ *    sqrt(fma(zr, zr, zi zi)): max_p |g'_p - g_p| <= tol max_p |g'_p| gives status 1; k = n_iter
+ *    gives status 0.  A second call continues from the gains of the first (k starts over).
+ * 4. Reference antenna.  r = refant if it is live, else the lowest live antenna; a = |g_r|,
+ *    (cr, ci) = (gr_r / a, -(gi_r / a)); every live gain becomes (fma(gr, cr, -(gi ci)), fma(gr, ci,
+ *    gi cr)), Im g_r exactly +0.0; dead antennas get NaN.
+ * 5. Residual.  d_chi2[m][s][0 / 1] = sum w |D - c M|^2 over the counting visibilities of the
+ *    pairs with both antennas live, c = g_p conj g_q (cr, ci as in rjp_gain_apply) of the start
+ *    gains (0) and of the gains as written (1).  Lane l of 256 takes the pairs pq = l, l + 256, ...
+ *    in ascending order and of each the interval's integrations in ascending t, ONE chain from 0:
+ *      er = Dr - fma(cr, Mr, -(ci Mi));  ei = Di - fma(cr, Mi, ci Mr)
+ *      x = fma(w er, er, x);  x = fma(w ei, ei, x)
+ *    then the 256 partials are folded by halves: x[l] += x[l + h] for h = 128, 64, ..., 1.
+ * Outputs: d_nvis (the sum of n_pq over ALL pairs), d_niter, d_status [n_maps][n_sol] int32;
+ * d_live [n_maps][n_sol][n_ant] uint8; optional d_trace [n_maps][n_sol][n_iter][n_ant][2]: the
+ * gains after each step BEFORE referencing (NaN for a dead antenna); rows at and beyond d_niter are
+ * not written.  No atomics, every sum in the order stated: a repeated call gives identical bits,
+ * and the bits of a solution depend on its own interval's data alone, not on what else is in the
+ * call.  Three launches (accumulate; one wave per (m, s), one lane per antenna, the triangle of
+ * A and B in LDS and the whole iteration in one launch; residual), nothing on the host.
+ * RJP_GAINCAL_MAX_ANT = 64: a triangle of 2016 x 24 B = 48 KiB fits static LDS.
+ * Both return the workgroups they enqueued.  Everything is validated before anything is enqueued;
+ * a refusal touches no output and no workspace byte.  RJP_ERR_ARG for a NULL ctx, d_vis, d_gains,
+ * h_sol, d_out / d_model, d_chi2, d_nvis, d_niter, d_status, d_live; n_maps, n_t or n_sol < 1;
+ * n_ant < 2 or above the cap; a malformed h_sol; g_maps / model_maps / w_maps neither 1 nor
+ * n_maps; a mode other than 0 and 1; refant outside 0 .. n_ant - 1; min_bl < 1; tol not finite and
+ * positive; n_iter < 1; more than 2^31 - 1 workgroups.  RJP_ERR_WORKSPACE for a d_work that is NULL
+ * or smaller than rjp_gaincal_workspace() (0 for arguments it would refuse). */
+#define RJP_GAINCAL_MAX_ANT 64
+int64_t rjp_gain_apply(rjp_ctx* ctx, const double* d_vis, int32_t n_maps, int32_t n_t,
+                       int32_t n_ant, const double* d_gains, int32_t g_maps, const int32_t* h_sol,
+                       int32_t n_sol, int32_t mode, double* d_out, void* stream);
+size_t rjp_gaincal_workspace(int32_t n_maps, int32_t n_sol, int32_t n_ant);
+int64_t rjp_gaincal(rjp_ctx* ctx, const double* d_vis, int32_t n_maps, int32_t n_t, int32_t n_ant,
+                    const double* d_model, int32_t model_maps, const double* d_w, int32_t w_maps,
+                    const int32_t* h_sol, int32_t n_sol, int32_t mode, int32_t refant,
+                    int32_t min_bl, double tol, int32_t n_iter, double* d_gains, double* d_chi2,
+                    int32_t* d_nvis, int32_t* d_niter, int32_t* d_status, uint8_t* d_live,
+                    double* d_trace, void* d_work, size_t work_bytes, void* stream);
+
 /* ---- K4: geometry -> fields on the device --------------------------------------------
  * Replaces the lazily cached grids of JetModel (fill_factor/areas classes.py:657-669,
  * 763-764; grid_rwp 521-525; rreff 549-555; _nd 877-897; ion_fraction 915-934;

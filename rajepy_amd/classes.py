@@ -27,6 +27,7 @@ from . import logger
 from .imaging import (CleanResult, Imager, Observation, UVTracks, Weighting,  # noqa: F401
                       _split_weights, _weighting_mode, image_scales, vis_scales)
 from .spectra import Spectra, velocity_axis
+from .calibration import Calibrator, SelfcalResult  # noqa: F401
 from .maths import geometry as mgeom
 from .maths import physics as mphys
 from .maths import rrls as mrrl
@@ -1458,6 +1459,55 @@ class JetModel:
             free = [1] * (3 * int(comps)) + [0, 0]
         return Spectra(self.engine).specfit(cube.reshape(len(v), self.nx, self.nz), v, weights,
                                             comps, theta0, free, n_iter)
+
+    # ------------------------------------------------------------------ antenna gains (K22) ----
+    def corrupt_gains(self, vis, tracks, gains, h_sol):
+        """The visibilities `vis` -- (F, K) complex, a host array or a device tensor in the order
+        of `tracks` (`uv_tracks`), such as `observe_ff(...).vis` -- times antenna gains: V_pq g_p
+        conj(g_q) (`RTEngine.gain_apply`, rjp_gain_apply) -> complex128 device tensor (F, K); what
+        CASA simobserve's `corrupt` does for gains.  `gains`: complex (n_sol, n_ant), shared by the
+        channels, or (F, n_sol, n_ant) (`engine.random_gains` draws some); `h_sol` [n_t]: the
+        interval of every integration (`engine.solution_intervals`).  A NaN gain flags the
+        visibilities of its antenna.  Calling rank only."""
+        return Calibrator(self.engine).corrupt(vis, tracks, gains, h_sol)
+
+    def gaincal(self, vis, model_vis, tracks, solint_s="int", calmode="ap", refant=0,
+                minblperant=4, weights=None, tol=1e-10, n_iter=300):
+        """Antenna gains per channel and solution interval that bring `model_vis` to `vis` (both
+        (F, K) as in `corrupt_gains`; `model_vis` may be (1, K)), D_pq = g_p conj(g_q) M_pq, by
+        StefCal on the device (`RTEngine.gaincal`, rjp_gaincal: one launch iterates every
+        (channel, interval) to the end) -> (gains, results): complex128 device tensor (F, n_sol,
+        n_ant), NaN for an antenna without a solution, and `engine.gain_results` (device tensors
+        'amp', 'phase_deg', 'live', 'status', 'chi2_start', 'chi2', 'nvis', 'niter') plus 'h_sol',
+        the host interval table to apply them with -- what radio astronomers get from CASA gaincal.
+        `solint_s`: seconds, 'int' or 'inf' (`engine.solution_intervals`; never across two days);
+        `calmode`: 'ap' or 'p' (phase only); `refant`: the antenna of phase 0; `minblperant`: an
+        antenna with fewer baselines with data in an interval gets no solution there; `weights`:
+        None, [K] or [F, K]; status 1 converged (`tol`, relative), 0 `n_iter` exhausted, 2 broken
+        down, 3 too few antennas.  This project's definition, no CASA parity.  Calling rank only."""
+        return Calibrator(self.engine).gaincal(vis, model_vis, tracks, solint_s, calmode, refant,
+                                               minblperant, weights, tol, n_iter)
+
+    def applycal(self, vis, tracks, gains, h_sol):
+        """`vis` corrected by antenna gains, V_pq / (g_p conj(g_q)) (arguments and result as
+        `corrupt_gains`, whose inverse it is) -- CASA applycal.  Calling rank only."""
+        return Calibrator(self.engine).applycal(vis, tracks, gains, h_sol)
+
+    def selfcal_ff(self, vis, tracks, freq, rounds=(dict(solint_s="inf", calmode="p"),),
+                   **clean_kwargs):
+        """Self-calibration of the visibilities `vis` (F, K) at the channels `freq` -> `SelfcalResult`
+        (`clean`, `vis`, `gains`, `history`).  Every round -- a dict of `gaincal`'s keywords --
+        CLEANs the current data as `clean_image_ff` does (keywords `weights`, `shape`, `cell_as`,
+        `mfs`, `niter`, `gain`, `threshold_jy`, `mask`, `beam`, `psf_shape`, `weighting`,
+        `robust`), forms the visibilities of the component list (`RTEngine.vis_components`),
+        solves `gaincal` of the current data against them and corrects the ORIGINAL data by the
+        product of all gains so far; `clean` is one more CLEAN, of the corrected data `vis`.
+        `gains`: complex128 device tensor (F, n_t, n_ant), the product per integration (apply
+        with h_sol = arange(n_t)); `history`: per round 'peak_residual' of its CLEAN, 'chi2_start'
+        and 'chi2' summed over the solved solutions, 'status' (how many solutions ended with
+        each).  An antenna without a solution flags its data.  Calling rank only."""
+        return Calibrator(self.engine, self._imager).selfcal(vis, tracks, freq, list(rounds),
+                                                             **clean_kwargs)
 
     # ------------------------------------------------------------------ products ----
     FORMAL_HISTORY ="Formal solution along the line of sight, observer at iy = 0"

@@ -450,6 +450,76 @@ inline int check_specfit(const double* d_cube, int64_t n_pix, int n_chan, const 
   return RJP_OK;
 }
 
+// The interval table of K22: h_sol[0] = 0, steps of 0 or 1, n_sol = h_sol[n_t - 1] + 1.
+inline bool sol_ok(const int32_t* h_sol, int n_t, int n_sol) {
+  if (h_sol[0] != 0) return false;
+  for (int t = 1; t < n_t; ++t)
+    if (h_sol[t] != h_sol[t - 1] && h_sol[t] != h_sol[t - 1] + 1) return false;
+  return h_sol[n_t - 1] + 1 == n_sol;
+}
+
+// What rjp_gain_apply takes, in the order it refuses: NULL pointers, counts below 1, n_ant, the
+// interval table, g_maps, the mode, the workgroup count (256 visibilities each).
+inline int check_gain_apply(const double* d_vis, int n_maps, int n_t, int n_ant,
+                            const double* d_gains, int g_maps, const int32_t* h_sol, int n_sol,
+                            int mode, const double* d_out, std::string& err) {
+  if (!d_vis || !d_gains || !h_sol || !d_out)
+    return refuse(err, "rjp_gain_apply: NULL visibilities, gains, intervals or output");
+  if (n_maps < 1 || n_t < 1 || n_sol < 1)
+    return refuse(err, "rjp_gain_apply: n_maps, n_t and n_sol must be positive");
+  if (n_ant < 2 || n_ant > RJP_GAINCAL_MAX_ANT)
+    return refuse(err, "rjp_gain_apply: n_ant must lie in 2 .. RJP_GAINCAL_MAX_ANT (" +
+                           std::to_string(RJP_GAINCAL_MAX_ANT) + ")");
+  if (!sol_ok(h_sol, n_t, n_sol))
+    return refuse(err, "rjp_gain_apply: h_sol must start at 0, rise in steps of 0 or 1 and end at "
+                       "n_sol - 1");
+  if (g_maps != 1 && g_maps != n_maps)
+    return refuse(err, "rjp_gain_apply: g_maps must be 1 or n_maps");
+  if (mode != 0 && mode != 1)
+    return refuse(err, "rjp_gain_apply: mode must be 0 (corrupt) or 1 (correct)");
+  const int64_t n_bl = (int64_t)n_ant * (n_ant - 1) / 2;
+  if (((int64_t)n_maps * n_t * n_bl + 255) / 256 > (int64_t)INT32_MAX)
+    return refuse(err, "rjp_gain_apply: more than 2^31 - 1 workgroups");
+  return RJP_OK;
+}
+
+// What rjp_gaincal takes, in the order it refuses: NULL pointers, counts below 1, n_ant, the
+// interval table, model_maps and w_maps, the mode, refant, min_bl, tol, n_iter, the workgroup
+// count.  (`d_w` and `d_trace` may be NULL; the workspace is checked where its size lives.)
+inline int check_gaincal(const double* d_vis, int n_maps, int n_t, int n_ant,
+                         const double* d_model, int model_maps, const double* d_w, int w_maps,
+                         const int32_t* h_sol, int n_sol, int mode, int refant, int min_bl,
+                         double tol, int n_iter, const double* d_gains, const double* d_chi2,
+                         const int32_t* d_nvis, const int32_t* d_niter, const int32_t* d_status,
+                         const uint8_t* d_live, std::string& err) {
+  if (!d_vis || !d_model || !h_sol || !d_gains || !d_chi2 || !d_nvis || !d_niter || !d_status ||
+      !d_live)
+    return refuse(err, "rjp_gaincal: NULL visibilities, model, intervals, gains or outputs");
+  if (n_maps < 1 || n_t < 1 || n_sol < 1)
+    return refuse(err, "rjp_gaincal: n_maps, n_t and n_sol must be positive");
+  if (n_ant < 2 || n_ant > RJP_GAINCAL_MAX_ANT)
+    return refuse(err, "rjp_gaincal: n_ant must lie in 2 .. RJP_GAINCAL_MAX_ANT (" +
+                           std::to_string(RJP_GAINCAL_MAX_ANT) + ")");
+  if (!sol_ok(h_sol, n_t, n_sol))
+    return refuse(err, "rjp_gaincal: h_sol must start at 0, rise in steps of 0 or 1 and end at "
+                       "n_sol - 1");
+  if (model_maps != 1 && model_maps != n_maps)
+    return refuse(err, "rjp_gaincal: model_maps must be 1 or n_maps");
+  if (d_w && w_maps != 1 && w_maps != n_maps)
+    return refuse(err, "rjp_gaincal: w_maps must be 1 or n_maps");
+  if (mode != 0 && mode != 1)
+    return refuse(err, "rjp_gaincal: mode must be 0 (amplitude and phase) or 1 (phase only)");
+  if (refant < 0 || refant >= n_ant) return refuse(err, "rjp_gaincal: refant outside 0 .. n_ant - 1");
+  if (min_bl < 1) return refuse(err, "rjp_gaincal: min_bl < 1");
+  if (!(tol > 0.0) || !std::isfinite(tol))
+    return refuse(err, "rjp_gaincal: tol must be finite and positive");
+  if (n_iter < 1) return refuse(err, "rjp_gaincal: n_iter < 1");
+  const int64_t n_bl = (int64_t)n_ant * (n_ant - 1) / 2, n_ms = (int64_t)n_maps * n_sol;
+  if ((n_ms * n_bl + 255) / 256 + 2 * n_ms > (int64_t)INT32_MAX)
+    return refuse(err, "rjp_gaincal: more than 2^31 - 1 workgroups");
+  return RJP_OK;
+}
+
 // What rjp_uv_weights takes, in the order it refuses: NULL pointers, counts below 1, a non-finite
 // scale, the mode, the robustness.  (`d_w`, `d_stats` and `d_density` may be NULL; the grids and the
 // workspace are checked where the tiling lives.)

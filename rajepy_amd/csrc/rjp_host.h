@@ -428,6 +428,24 @@ hipError_t specfit_launch(const double* cube, int64_t n_pix, int n_chan, const d
                           int n_iter, double* chi2, double* cov, int32_t* nchan, int32_t* niter,
                           int32_t* status, double* trace, hipStream_t st);
 
+// ---- gaincal.hip: antenna-based complex gains (K22) ----------------------------------------------
+// one thread per visibility, workgroups of 256
+int64_t gain_apply_workgroups(int n_maps, int n_t, int n_ant);
+// accumulate (256 (m, s, pq) each) + one solve and one residual workgroup per (m, s)
+int64_t gaincal_workgroups(int n_maps, int n_sol, int n_ant);
+size_t gaincal_workspace_bytes(int n_maps, int n_sol, int n_ant);
+// d_sol [n_t]: the interval of every integration, as doubles; `out` may be `vis`
+hipError_t gain_apply_launch(const double* vis, int n_maps, int n_t, int n_ant, const double* gains,
+                             int g_maps, int n_sol, const double* d_sol, int mode, double* out,
+                             hipStream_t st);
+// d_t0 [n_sol + 1]: the first integration of every interval and n_t, as doubles; `w`, `trace` may
+// be nullptr; three launches, no host synchronisation
+hipError_t gaincal_launch(const double* vis, const double* model, int model_maps, const double* w,
+                          int w_maps, int n_maps, int n_t, int n_ant, int n_sol, const double* d_t0,
+                          int mode, int refant, int min_bl, double tol, int n_iter, double* gains,
+                          double* chi2, int32_t* nvis, int32_t* niter, int32_t* status,
+                          uint8_t* live, double* trace, void* work, hipStream_t st);
+
 // ---- uv_weight.hip: uniform and Briggs imaging weights from the (u, v) density (K15) -------------
 struct UvWeightTiling {
   int64_t cells;                // (2 (nx / 2) + 1)(2 (nz / 2) + 1), per map (INT64_MAX: beyond int64)

@@ -1460,6 +1460,60 @@ int64_t rjp_specfit(rjp_ctx* ctx, const double* d_cube, int64_t n_pix, int32_t n
   return r ? r : rjp::specfit_workgroups(n_pix);
 }
 
+int64_t rjp_gain_apply(rjp_ctx* ctx, const double* d_vis, int32_t n_maps, int32_t n_t,
+                       int32_t n_ant, const double* d_gains, int32_t g_maps, const int32_t* h_sol,
+                       int32_t n_sol, int32_t mode, double* d_out, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_gain_apply(d_vis, n_maps, n_t, n_ant, d_gains, g_maps, h_sol, n_sol,
+                                          mode, d_out, m);
+      }))
+    return r;
+  std::vector<double> sol(h_sol, h_sol + n_t);
+  hipStream_t st = (hipStream_t)stream;
+  const int r = staged(ctx, st, "gain_apply_launch", nullptr, {{sol.data(), sol.size()}},
+                       [&](double* const* d, const double*) {
+                         return rjp::gain_apply_launch(d_vis, n_maps, n_t, n_ant, d_gains, g_maps,
+                                                       n_sol, d[0], mode, d_out, st);
+                       });
+  return r ? r : rjp::gain_apply_workgroups(n_maps, n_t, n_ant);
+}
+
+size_t rjp_gaincal_workspace(int32_t n_maps, int32_t n_sol, int32_t n_ant) {
+  if (n_maps <= 0 || n_sol <= 0 || n_ant < 2 || n_ant > RJP_GAINCAL_MAX_ANT) return 0;
+  return rjp::gaincal_workspace_bytes(n_maps, n_sol, n_ant);
+}
+
+int64_t rjp_gaincal(rjp_ctx* ctx, const double* d_vis, int32_t n_maps, int32_t n_t, int32_t n_ant,
+                    const double* d_model, int32_t model_maps, const double* d_w, int32_t w_maps,
+                    const int32_t* h_sol, int32_t n_sol, int32_t mode, int32_t refant,
+                    int32_t min_bl, double tol, int32_t n_iter, double* d_gains, double* d_chi2,
+                    int32_t* d_nvis, int32_t* d_niter, int32_t* d_status, uint8_t* d_live,
+                    double* d_trace, void* d_work, size_t work_bytes, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_gaincal(d_vis, n_maps, n_t, n_ant, d_model, model_maps, d_w, w_maps,
+                                       h_sol, n_sol, mode, refant, min_bl, tol, n_iter, d_gains,
+                                       d_chi2, d_nvis, d_niter, d_status, d_live, m);
+      }))
+    return r;
+  if (!d_work || work_bytes < rjp::gaincal_workspace_bytes(n_maps, n_sol, n_ant))
+    return fail(ctx, RJP_ERR_WORKSPACE,
+                "rjp_gaincal: workspace smaller than rjp_gaincal_workspace()");
+  // the first integration of every interval, and n_t
+  std::vector<double> t0((size_t)n_sol + 1, (double)n_t);
+  for (int t = n_t - 1; t >= 0; --t) t0[h_sol[t]] = (double)t;
+  hipStream_t st = (hipStream_t)stream;
+  const int r = staged(ctx, st, "gaincal_launch", nullptr, {{t0.data(), t0.size()}},
+                       [&](double* const* d, const double*) {
+                         return rjp::gaincal_launch(d_vis, d_model, model_maps, d_w, w_maps, n_maps,
+                                                    n_t, n_ant, n_sol, d[0], mode, refant, min_bl,
+                                                    tol, n_iter, d_gains, d_chi2, d_nvis, d_niter,
+                                                    d_status, d_live, d_trace, d_work, st);
+                       });
+  return r ? r : rjp::gaincal_workgroups(n_maps, n_sol, n_ant);
+}
+
 size_t rjp_uv_weights_workspace(int32_t n_maps, int32_t nx, int32_t nz, int32_t n_vis) {
   if (n_maps <= 0 || nx <= 0 || nz <= 0 || n_vis <= 0) return 0;
   return rjp::uv_weights_workspace_bytes(n_maps, nx, nz, n_vis);

@@ -22,6 +22,8 @@ from .imaging import (UVFIT_MAX_COMP, uvfit_components, uvfit_results, uvfit_sta
                       uvfit_theta, uvfit_theta_from_imfit)
 from .spectra import (SPECFIT_MAX_CHAN, SPECFIT_MAX_COMP, channel_widths,  # noqa: F401
                       specfit_results, specfit_start, velocity_axis)
+from .calibration import (GAINCAL_MAX_ANT, gain_results, random_gains,  # noqa: F401
+                          solution_intervals)
 
 
 def _torch():
@@ -1794,8 +1796,137 @@ class RTEngine:
             out["trace"] = tr
         return out
 
+    # -- K22 -------------------------------------------------------------------------------------
+    GAIN_APPLY_MODES = {"corrupt": 0, "correct": 1}
+    GAINCAL_MODES = {"ap": 0, "p": 1}
+
+    def _gain_layout(self, who, vis, h_sol, n_ant):
+        """A visibility stack [M, n_t n_bl] and the host interval table -> (float64 [M, K, 2], M,
+        n_t, n_sol, the table as a ctypes int32 pointer into an array it keeps alive)."""
+        dvis = self._vis_stack(who, vis)
+        n_ant = int(n_ant)
+        if not 2 <= n_ant <= GAINCAL_MAX_ANT:
+            raise ValueError("%s: n_ant must be 2 to %d" % (who, GAINCAL_MAX_ANT))
+        sol = np.ascontiguousarray(h_sol, dtype=np.int32).reshape(-1)
+        n_t, n_bl = sol.size, n_ant * (n_ant - 1) // 2
+        if n_t < 1 or int(dvis.shape[1]) != n_t * n_bl:
+            raise ValueError("%s: `vis` must hold n_t x n_bl = %d x %d visibilities per map, in the "
+                             "order of `uv_tracks`" % (who, n_t, n_bl))
+        if sol[0] != 0 or np.any((np.diff(sol) != 0) & (np.diff(sol) != 1)):
+            raise ValueError("%s: `h_sol` must start at 0 and rise in steps of 0 or 1" % who)
+        ptr = sol.ctypes.data_as(C.POINTER(C.c_int32))
+        ptr._keep = sol                          # (the table may be long: no element-wise copy)
+        return dvis, int(dvis.shape[0]), n_t, int(sol[-1]) + 1, ptr
+
+    def _gain_stack(self, who, gains, n_sol, n_ant):
+        torch = _torch()
+        if isinstance(gains, torch.Tensor) and gains.dtype == torch.complex128:
+            gains = torch.view_as_real(gains)
+        if not (isinstance(gains, torch.Tensor) and gains.dtype == torch.float64 and
+                gains.device == self.device and gains.is_contiguous() and gains.dim() == 4 and
+                tuple(gains.shape[1:]) == (n_sol, n_ant, 2) and gains.shape[0] >= 1):
+            raise ValueError("%s: `gains` must be a contiguous complex128 [G, n_sol, n_ant] or "
+                             "float64 [G, n_sol, n_ant, 2] = [G, %d, %d, 2] tensor on %s"
+                             % (who, n_sol, n_ant, self.device))
+        return gains
+
+    def gain_apply(self, vis, gains, h_sol, n_ant, mode="corrupt", out=None):
+        """Antenna gains times a stack of visibility sets (rjp_gain_apply), one thread per
+        visibility, nothing going to the host -> complex128 device tensor [M, n_t n_bl].  `vis`:
+        complex128 [M, n_t n_bl] (or float64 [..., 2]) in the order of `uv_tracks` (integration by
+        integration, the pairs (p < q) p-major); `gains`: complex128 [G, n_sol, n_ant] (or float64
+        [..., 2]), G = 1 (shared) or M; `h_sol` [n_t]: the HOST interval table
+        (`solution_intervals`); `mode`: 'corrupt' (V g_p conj g_q) or 'correct' (V conj(c) / |c|^2,
+        c = g_p conj g_q); `out`: None or a tensor like `vis` (may be `vis` itself).  A NaN gain or
+        visibility gives a NaN visibility.  The workgroup count is kept in
+        `last_gain_apply_workgroups`."""
+        torch = _torch()
+        if mode not in self.GAIN_APPLY_MODES:
+            raise ValueError("gain_apply: mode must be 'corrupt' or 'correct'")
+        dvis, M, n_t, n_sol, sol = self._gain_layout("gain_apply", vis, h_sol, n_ant)
+        g = self._gain_stack("gain_apply", gains, n_sol, int(n_ant))
+        if g.shape[0] not in (1, M):
+            raise ValueError("gain_apply: `gains` must hold one set or one per map (%d)" % M)
+        if out is None:
+            vout = self._f64(*dvis.shape)
+        else:
+            vout = self._vis_stack("gain_apply", out)
+            if tuple(vout.shape) != tuple(dvis.shape):
+                raise ValueError("gain_apply: `out` must be shaped like `vis`")
+        self.last_gain_apply_workgroups = self._call_tiles(
+            "rjp_gain_apply", dvis.data_ptr(), M, n_t, int(n_ant), g.data_ptr(), int(g.shape[0]),
+            sol, n_sol, self.GAIN_APPLY_MODES[mode], vout.data_ptr())
+        return torch.view_as_complex(vout)
+
+    def gaincal(self, vis, model, h_sol, n_ant, gains=None, weights=None, mode="ap", refant=0,
+                min_bl=4, tol=1e-10, n_iter=300, trace=False):
+        """Antenna gains of every (map, solution interval) of a stack of visibility sets against
+        model visibilities (rjp_gaincal: StefCal, D_pq = g_p conj(g_q) M_pq), three launches and
+        nothing going to the host -> dict of device tensors: `gains` complex128 [M, n_sol, n_ant]
+        (NaN for a dead antenna and for every antenna of a status-3 solution; the reference
+        antenna real and positive), `chi2` [M, n_sol, 2] (sum w |D - g_p conj(g_q) M|^2 at the
+        start and at the solution), `nvis`, `niter`, `status` [M, n_sol] int32 -- 1 converged, 0
+        `n_iter` exhausted, 2 a vanishing or non-finite denominator, 3 degenerate (too few live
+        antennas, or a live antenna's start gain 0 or not finite: `chi2` NaN, `niter` -1) --,
+        `live` [M, n_sol, n_ant] uint8 (0 for status 3), and with `trace` the gains after every
+        step before referencing, float64 [M, n_sol, n_iter, n_ant, 2], NaN beyond `niter`.
+        `vis`, `h_sol`, `n_ant` as `gain_apply`; `model`: complex128 [1 or M, n_t n_bl];
+        `gains`: None (ones) or the start, complex128 [M, n_sol, n_ant] (it is copied: pass a
+        result's `gains` to continue); `weights`: None, [n_t n_bl] or [M, n_t n_bl]; `mode`: 'ap'
+        (amplitude and phase) or 'p' (phase only: every |g| = 1); `refant`: the antenna whose
+        phase is 0, the lowest live one where it is dead; `min_bl`: an antenna with fewer
+        partners with data is dead (applied until nothing changes).  A visibility counts when
+        data, model and weight are finite, the weight > 0 and the model is not 0.  The same bits
+        on every call; a solution's bits depend on its own interval alone."""
+        torch = _torch()
+        if mode not in self.GAINCAL_MODES:
+            raise ValueError("gaincal: mode must be 'ap' or 'p'")
+        n_iter, n_ant, refant, min_bl = int(n_iter), int(n_ant), int(refant), int(min_bl)
+        if n_iter < 1 or min_bl < 1:
+            raise ValueError("gaincal: n_iter and min_bl must be positive")
+        if not (np.isfinite(tol) and tol > 0.):
+            raise ValueError("gaincal: `tol` must be finite and positive")
+        dvis, M, n_t, n_sol, sol = self._gain_layout("gaincal", vis, h_sol, n_ant)
+        if not 0 <= refant < n_ant:
+            raise ValueError("gaincal: refant must be 0 to n_ant - 1")
+        K = int(dvis.shape[1])
+        dmod = self._vis_stack("gaincal", model)
+        if int(dmod.shape[1]) != K or dmod.shape[0] not in (1, M):
+            raise ValueError("gaincal: `model` must be [1 or M, K] = [%d, %d]" % (M, K))
+        dw, w_maps = None, 1
+        if weights is not None:
+            dw = self._device_f64(weights)
+            if dw.numel() not in (K, M * K):
+                raise ValueError("gaincal: `weights` must be [K] or [M, K] = [%d, %d]" % (M, K))
+            w_maps = dw.numel() // K
+        if gains is None:
+            g = torch.zeros((M, n_sol, n_ant, 2), dtype=torch.float64, device=self.device)
+            g[..., 0] = 1.
+        else:
+            g = self._gain_stack("gaincal", gains, n_sol, n_ant)
+            if g.shape[0] != M:
+                raise ValueError("gaincal: `gains` must hold one start per map (%d)" % M)
+            g = g.clone()
+        chi2 = torch.full((M, n_sol, 2), float("nan"), dtype=torch.float64, device=self.device)
+        nvis, niter, status = (torch.full((M, n_sol), -1, dtype=torch.int32, device=self.device)
+                               for _ in range(3))
+        live = torch.zeros((M, n_sol, n_ant), dtype=torch.uint8, device=self.device)
+        tr = (torch.full((M, n_sol, n_iter, n_ant, 2), float("nan"), dtype=torch.float64,
+                         device=self.device) if trace else None)
+        work = self._workspace(max(1, self.lib.rjp_gaincal_workspace(M, n_sol, n_ant)))
+        self.last_gaincal_workgroups = self._call_tiles(
+            "rjp_gaincal", dvis.data_ptr(), M, n_t, n_ant, dmod.data_ptr(), int(dmod.shape[0]),
+            _ptr(dw), w_maps, sol, n_sol, self.GAINCAL_MODES[mode], refant, min_bl, float(tol),
+            n_iter, g.data_ptr(), chi2.data_ptr(), nvis.data_ptr(), niter.data_ptr(),
+            status.data_ptr(), live.data_ptr(), _ptr(tr), work.data_ptr(), work.numel())
+        out = dict(gains=torch.view_as_complex(g), chi2=chi2, nvis=nvis, niter=niter,
+                   status=status, live=live)
+        if trace:
+            out["trace"] = tr
+        return out
+
     # -- K15 -------------------------------------------------------------------------------------
-    UV_WEIGHT_MODES = {"uniform": 1, "briggs": 2}
+    UV_WEIGHT_MODES ={"uniform": 1, "briggs": 2}
 
     def uv_weights(self, u, v, su, sv, nx, nz, w=None, mode="briggs", robust=0.5,
                    want_density=False):
