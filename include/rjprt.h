@@ -1461,6 +1461,53 @@ int64_t rjp_gaincal(rjp_ctx* ctx, const double* d_vis, int32_t n_maps, int32_t n
                     int32_t* d_nvis, int32_t* d_niter, int32_t* d_status, uint8_t* d_live,
                     double* d_trace, void* d_work, size_t work_bytes, void* stream);
 
+/* ---- K23: normal equations from data, model and derivative stacks ---------------------------------
+ * The reduction a least-squares fit of the MODEL'S OWN parameters needs: data, model and the
+ * model's derivatives are stacks on the device (light curves and their Jacobian from
+ * rjp_ff_grad / rjp_ff_formal_grad, visibilities from rjp_vis on flux and derivative maps); this
+ * entry point reduces them to chi^2, the gradient and the Gauss-Newton matrix.  This comment IS
+ * the definition.
+ *   n_part                    2: complex samples stored (re, im) as rjp_vis writes them; 1: real
+ *                             samples (a light curve, with n_vis = 1: d_ftot / d_dftot as they are)
+ *   d_data, d_model           [n_rows][n_vis][n_part]   (READ ONLY)
+ *   d_dmodel                  [n_rows][n_par][n_vis][n_part]: plane j of a row is d model / d theta_j
+ *   h_sel [n_sel]             HOST, distinct indices in [0, n_par): the planes that take part, in
+ *                             the order of the outputs; a plane that is not named is never read.
+ *                             n_sel = 0: chi^2 and the count only (d_dmodel and h_sel may be NULL)
+ *   d_w                       NULL (all ones) or [w_rows][n_vis], w_rows 1 (shared) or n_rows
+ *   d_out [1 + P + P (P + 1) / 2], P = n_sel: chi^2, then g[P], then the packed upper triangle of N
+ *                             row by row (the order of rjp_uvfit's d_cov);  d_count: one int64
+ *   d_work                    8-byte aligned, like every double buffer
+ * Sample (row, k) counts when every part of its datum and its weight are finite and w > 0.  With
+ * r = data - model (one rounding per part) and J_p the selected plane p, over the counting samples
+ *   chi^2 = sum w |r|^2,   g_p = sum w Re(conj(J_p) r),   N_pq = sum w Re(conj(J_p) J_q),
+ * *d_count their number.  A sample that does not count adds nothing, whatever its model or
+ * derivatives hold; a counting sample with a non-finite model or derivative propagates by IEEE
+ * rules (into the entries that touch it, and no others).
+ * The order of every sum.  With column P standing for r, every entry is G[p][q], p <= q <= P.  A
+ * tile is 512 consecutive flattened samples s = row n_vis + k; sample i of a tile belongs to slice
+ * i mod 16.  A slice starts at +0 and takes its counting samples in increasing i, part 0 then part
+ * 1, each as one fused multiply-add G[p][q] <- fma(a_p, w a_q, G[p][q]) with w a_q rounded once
+ * (the weight on the column with the higher index).  The 16 slices are added in slice order, ((s0 +
+ * s1) + s2) + ..., into the tile's partial; a second launch adds the partials in tile order,
+ * starting from tile 0's.  No atomics: a repeated call gives the same bits, and the value of a sum
+ * depends on the inputs and these two constants, not on n_sel, n_par or the device.
+ * RETURNS the workgroups of the first launch, ceil(n_rows n_vis / 512) > 0, or a negative
+ * RJP_ERR_*.  Everything is validated before anything is enqueued, and no output or workspace byte
+ * is touched on a refusal: RJP_ERR_ARG for a NULL ctx, d_data, d_model, d_out or d_count; n_rows or
+ * n_vis < 1; n_part not 1 or 2; n_sel outside 0 .. RJP_NORMAL_EQ_MAX_SEL; n_sel > 0 with a NULL
+ * d_dmodel or h_sel; n_par < n_sel; an index outside [0, n_par); a repeated index; with d_w a w_rows
+ * that is neither 1 nor n_rows; more than 2^31 - 1 workgroups.  RJP_ERR_WORKSPACE for a d_work that
+ * is NULL or smaller than the workspace query (n_tiles x (1 + P + P (P + 1) / 2 + 1) x 8 bytes; 0
+ * from it = a bad argument). */
+#define RJP_NORMAL_EQ_MAX_SEL 48          /* 3 x (8 + 8) bursts: what K9 allows */
+size_t rjp_normal_eq_workspace(int64_t n_rows, int32_t n_vis, int32_t n_sel);
+int64_t rjp_normal_eq(rjp_ctx* ctx, const double* d_data, const double* d_model,
+                      const double* d_dmodel, int64_t n_rows, int32_t n_vis, int32_t n_part,
+                      int32_t n_par, const int32_t* h_sel, int32_t n_sel, const double* d_w,
+                      int64_t w_rows, double* d_out, int64_t* d_count, void* d_work,
+                      size_t work_bytes, void* stream);
+
 /* ---- K4: geometry -> fields on the device --------------------------------------------
  * Replaces the lazily cached grids of JetModel (fill_factor/areas classes.py:657-669,
  * 763-764; grid_rwp 521-525; rreff 549-555; _nd 877-897; ion_fraction 915-934;

@@ -198,6 +198,10 @@ SIGNATURES = {
                                 C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
                                 C.c_int32, C.c_double, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P,
                                 C.c_size_t, _P]),
+    "rjp_normal_eq_workspace": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "rjp_normal_eq": (C.c_int64, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                  C.POINTER(C.c_int32), C.c_int32, _P, C.c_int64, _P, _P, _P,
+                                  C.c_size_t, _P]),
     "rjp_uv_weights_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "rjp_uv_weights": (C.c_int64, [_P, C.c_int32, C.c_int32, _DP, _DP, _P, _P, _P, C.c_int32,
                                    C.c_int32, C.c_int32, C.c_double, _P, _P, _P, _P, C.c_size_t, _P]),

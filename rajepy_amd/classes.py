@@ -28,6 +28,7 @@ from .imaging import (CleanResult, Imager, Observation, UVTracks, Weighting,  # 
                       _split_weights, _weighting_mode, image_scales, vis_scales)
 from .spectra import Spectra, velocity_axis
 from .calibration import Calibrator, SelfcalResult  # noqa: F401
+from .inference import BurstFit, EjectionFit  # noqa: F401
 from .maths import geometry as mgeom
 from .maths import physics as mphys
 from .maths import rrls as mrrl
@@ -117,6 +118,15 @@ def ejection_chain_rule(t_0, peak_jml, half_life, ss_jml):
     inv2s2 = 1. / (2. * sigma ** 2.)
     return ((t_0, (peak_jml - ss_jml) / ss_jml, inv2s2),
             (1., 1. / ss_jml, -2. * inv2s2 / half_life))
+
+
+def ejection_burst(t_0, peak_jml, half_life, ss_jml):
+    """One ejection event as `JetModel._bursts` and `engine.make_bursts` hold it: (t_0 [s], amp_rel,
+    sigma [s]) with amp_rel = (peak_jml - ss_jml) / ss_jml and sigma = half_life 2 / (2 sqrt(2 ln 2))
+    (classes.py:442-448) -- the one place `add_ejection_event`, `set_ejection_event` and the trial
+    bursts of a fit (`inference.BurstFit`) take it from."""
+    sigma = half_life * 2. / (2. * np.sqrt(2. * np.log(2.)))
+    return (t_0, (peak_jml - ss_jml) / ss_jml, sigma)
 
 
 def _load_params_file(py_file, checker):
@@ -368,10 +378,28 @@ class JetModel:
         if which not in ('R', 'B'):
             raise ValueError("which must be 'R' or 'B'")
         ss = self._ss_jml_bj if which == 'B' else self._ss_jml_rj
-        sigma = half_life * 2. / (2. * np.sqrt(2. * np.log(2.)))
-        self._bursts[which].append((t_0, (peak_jml - ss) / ss, sigma))
+        self._bursts[which].append(ejection_burst(t_0, peak_jml, half_life, ss))
         self._ejections[str(len(self._ejections) + 1)] = {
             't_0': t_0, 'peak_jml': peak_jml, 'half_life': half_life, 'which': which}
+        self._invalidate()
+
+    def set_ejection_event(self, key, t_0=None, peak_jml=None, half_life=None):
+        """Change the ejection event `key` of `model.ejections` in place: the values given ([s],
+        [kg/s], [s]; None keeps one) replace its entry and its burst as `add_ejection_event` would
+        have made them, and what that invalidates is invalidated.  Its jet cannot change."""
+        key = str(key)
+        if key not in self._ejections:
+            raise KeyError("no ejection event %r" % key)
+        ej = self._ejections[key]
+        which = ej['which']
+        idx = [k for k, e in self._ejections.items() if e['which'] == which].index(key)
+        new = dict(ej)
+        for name, val in (('t_0', t_0), ('peak_jml', peak_jml), ('half_life', half_life)):
+            if val is not None:
+                new[name] = val
+        ss = self._ss_jml_bj if which == 'B' else self._ss_jml_rj
+        self._bursts[which][idx] = ejection_burst(new['t_0'], new['peak_jml'], new['half_life'], ss)
+        self._ejections[key] = new
         self._invalidate()
 
     def jml_t(self, which):
@@ -1508,6 +1536,46 @@ class JetModel:
         each).  An antenna without a solution flags its data.  Calling rank only."""
         return Calibrator(self.engine, self._imager).selfcal(vis, tracks, freq, list(rounds),
                                                              **clean_kwargs)
+
+    # ------------------------------------------------------------------ burst fits (K23) ----
+    def fit_ejections_flux(self, times_s, freq, flux, sigma=None, formal=False, free=None, tie=None,
+                           theta0=None, n_iter=30, lambda0=1e-3, xtol=1e-8, update=False,
+                           trace=False):
+        """The (t_0 [s], peak_jml [kg/s], half_life [s]) of every entry of `model.ejections`
+        fitted to the light curves `flux` (E, F) [Jy] at `times_s` [s] and `freq` -- the mass-loss
+        history behind multi-epoch fluxes -> `EjectionFit`.  Levenberg-Marquardt on the host
+        (`inference.lm_minimise`, the rule of the device fits) around the exact derivatives of
+        `flux_vs_time_jac` (`formal`: as there), reduced to normal equations on the device
+        (`RTEngine.normal_eq`, rjp_normal_eq); a rejected trial costs one sweep and no
+        derivatives.  `sigma`: None, a number or (E, F), the errors of `flux` (weights 1 /
+        sigma^2); a NaN flux is skipped.  `free`, `tie`, `theta0`: `BurstFit.layout` -- `free`
+        None (all), boolean [n_ej, 3] or {key: names}: of a named ejection only these are fitted; `tie` groups of
+        (key, name) sharing one fit value (tie the two halves of an 'RB' event: a light curve
+        cannot separate them); `theta0` the start, None = the model's values.  Feasible:
+        everything finite, peak_jml > 0, half_life > 0.  Result: `ejections` (like
+        `model.ejections`, plus e_t_0, e_peak_jml, e_half_life: sqrt(diag N^-1 x reduced chi^2)),
+        `theta` [n_ej, 3], `cov` = N^-1 over the free fit parameters (exact for weights 1 /
+        sigma^2), `chi2`, `reduced_chi2`, `ndata`, `status` (1 converged: the step below `xtol`
+        of half_life, |peak_jml|, half_life; 0 `n_iter` trials; 2 stalled; 3 an infeasible start
+        or too few data: nothing fitted), `niter`, `trace`.  The model is not touched during the
+        fit; `update` writes the result back (`set_ejection_event`).  A model without ejections
+        or with f32 storage raises ValueError.  Calling rank only."""
+        return BurstFit(self).fit_flux(times_s, freq, flux, sigma, formal, free, tie, theta0,
+                                       n_iter, lambda0, xtol, update, trace)
+
+    def fit_ejections_vis(self, times_s, u_m, v_m, freq, vis, weights=None, free=None, tie=None,
+                          theta0=None, n_iter=30, lambda0=1e-3, xtol=1e-8, update=False,
+                          trace=False):
+        """As `fit_ejections_flux`, to visibilities `vis` (E, F, K) complex [Jy] (host array or
+        device tensor) at the baselines `u_m`, `v_m` [m]: [K] shared by the epochs, or [E, K] when
+        every epoch has its own coverage (pad with weight 0; one `RTEngine.vis` call per epoch
+        then).  Formal solution only, as `visibilities_vs_time_jac`, whose model and derivatives
+        these are: chunks of epochs whose derivative maps stay under 1 GiB go through
+        `ff_formal_grad(want_maps=True)`, `vis` and `normal_eq`; no map, visibility or derivative
+        goes to the host.  `weights`: None, [K], [E, K] or [E, F, K]; a visibility with a NaN part
+        or a weight that is not finite and positive is skipped.  Calling rank only."""
+        return BurstFit(self).fit_vis(times_s, u_m, v_m, freq, vis, weights, free, tie, theta0,
+                                      n_iter, lambda0, xtol, update, trace)
 
     # ------------------------------------------------------------------ products ----
     FORMAL_HISTORY ="Formal solution along the line of sight, observer at iy = 0"

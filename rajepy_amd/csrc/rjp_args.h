@@ -520,6 +520,37 @@ inline int check_gaincal(const double* d_vis, int n_maps, int n_t, int n_ant,
   return RJP_OK;
 }
 
+// What rjp_normal_eq takes, in the order it refuses: NULL pointers, counts below 1, n_part, n_sel,
+// the derivative stack and selection it needs, n_par, the indices, w_rows, the workgroup count
+// (512 samples each).  (`d_w` may be NULL; the workspace is checked where its size lives.)
+inline int check_normal_eq(const double* d_data, const double* d_model, const double* d_dmodel,
+                           int64_t n_rows, int n_vis, int n_part, int n_par, const int32_t* h_sel,
+                           int n_sel, const double* d_w, int64_t w_rows, const double* d_out,
+                           const int64_t* d_count, std::string& err) {
+  if (!d_data || !d_model || !d_out || !d_count)
+    return refuse(err, "rjp_normal_eq: NULL data, model or outputs");
+  if (n_rows < 1 || n_vis < 1) return refuse(err, "rjp_normal_eq: n_rows and n_vis must be positive");
+  if (n_part != 1 && n_part != 2)
+    return refuse(err, "rjp_normal_eq: n_part must be 1 (real) or 2 (complex)");
+  if (n_sel < 0 || n_sel > RJP_NORMAL_EQ_MAX_SEL)
+    return refuse(err, "rjp_normal_eq: n_sel must lie in 0 .. RJP_NORMAL_EQ_MAX_SEL (" +
+                           std::to_string(RJP_NORMAL_EQ_MAX_SEL) + ")");
+  if (n_sel > 0 && (!d_dmodel || !h_sel))
+    return refuse(err, "rjp_normal_eq: NULL derivatives or selection with n_sel > 0");
+  if (n_par < n_sel) return refuse(err, "rjp_normal_eq: n_par < n_sel");
+  for (int i = 0; i < n_sel; ++i) {
+    if (h_sel[i] < 0 || h_sel[i] >= n_par)
+      return refuse(err, "rjp_normal_eq: h_sel outside 0 .. n_par - 1");
+    for (int j = 0; j < i; ++j)
+      if (h_sel[j] == h_sel[i]) return refuse(err, "rjp_normal_eq: h_sel repeats an index");
+  }
+  if (d_w && w_rows != 1 && w_rows != n_rows)
+    return refuse(err, "rjp_normal_eq: w_rows must be 1 or n_rows");
+  if (n_rows > ((int64_t)INT32_MAX * 512) / n_vis)
+    return refuse(err, "rjp_normal_eq: more than 2^31 - 1 workgroups");
+  return RJP_OK;
+}
+
 // What rjp_uv_weights takes, in the order it refuses: NULL pointers, counts below 1, a non-finite
 // scale, the mode, the robustness.  (`d_w`, `d_stats` and `d_density` may be NULL; the grids and the
 // workspace are checked where the tiling lives.)

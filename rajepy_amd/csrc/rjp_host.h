@@ -446,6 +446,17 @@ hipError_t gaincal_launch(const double* vis, const double* model, int model_maps
                           double* chi2, int32_t* nvis, int32_t* niter, int32_t* status,
                           uint8_t* live, double* trace, void* work, hipStream_t st);
 
+// ---- normal_eq.hip: normal equations from data, model and derivative stacks (K23) ---------------
+// tiles of 512 consecutive flattened samples = the workgroups of the first launch
+int64_t normal_eq_tiles(int64_t n_rows, int n_vis);
+size_t normal_eq_workspace_bytes(int64_t n_rows, int n_vis, int n_sel);
+// `dmodel`, `h_sel` may be nullptr with n_sel = 0, `w` may be nullptr; two launches, no host
+// synchronisation (h_sel travels as a kernel argument)
+hipError_t normal_eq_launch(const double* data, const double* model, const double* dmodel,
+                            int64_t n_rows, int n_vis, int n_part, int n_par, const int32_t* h_sel,
+                            int n_sel, const double* w, int64_t w_rows, double* out, int64_t* count,
+                            void* work, hipStream_t st);
+
 // ---- uv_weight.hip: uniform and Briggs imaging weights from the (u, v) density (K15) -------------
 struct UvWeightTiling {
   int64_t cells;                // (2 (nx / 2) + 1)(2 (nz / 2) + 1), per map (INT64_MAX: beyond int64)

@@ -1514,6 +1514,33 @@ int64_t rjp_gaincal(rjp_ctx* ctx, const double* d_vis, int32_t n_maps, int32_t n
   return r ? r : rjp::gaincal_workgroups(n_maps, n_sol, n_ant);
 }
 
+size_t rjp_normal_eq_workspace(int64_t n_rows, int32_t n_vis, int32_t n_sel) {
+  if (n_rows < 1 || n_vis < 1 || n_sel < 0 || n_sel > RJP_NORMAL_EQ_MAX_SEL ||
+      n_rows > ((int64_t)INT32_MAX * 512) / n_vis)
+    return 0;
+  return rjp::normal_eq_workspace_bytes(n_rows, n_vis, n_sel);
+}
+
+int64_t rjp_normal_eq(rjp_ctx* ctx, const double* d_data, const double* d_model,
+                      const double* d_dmodel, int64_t n_rows, int32_t n_vis, int32_t n_part,
+                      int32_t n_par, const int32_t* h_sel, int32_t n_sel, const double* d_w,
+                      int64_t w_rows, double* d_out, int64_t* d_count, void* d_work,
+                      size_t work_bytes, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_normal_eq(d_data, d_model, d_dmodel, n_rows, n_vis, n_part, n_par,
+                                         h_sel, n_sel, d_w, w_rows, d_out, d_count, m);
+      }))
+    return r;
+  if (!d_work || work_bytes < rjp::normal_eq_workspace_bytes(n_rows, n_vis, n_sel))
+    return fail(ctx, RJP_ERR_WORKSPACE,
+                "rjp_normal_eq: workspace smaller than rjp_normal_eq_workspace()");
+  RJP_HIP(ctx, rjp::normal_eq_launch(d_data, d_model, d_dmodel, n_rows, n_vis, n_part, n_par, h_sel,
+                                     n_sel, d_w, w_rows, d_out, d_count, d_work,
+                                     (hipStream_t)stream));
+  return rjp::normal_eq_tiles(n_rows, n_vis);
+}
+
 size_t rjp_uv_weights_workspace(int32_t n_maps, int32_t nx, int32_t nz, int32_t n_vis) {
   if (n_maps <= 0 || nx <= 0 || nz <= 0 || n_vis <= 0) return 0;
   return rjp::uv_weights_workspace_bytes(n_maps, nx, nz, n_vis);

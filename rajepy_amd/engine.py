@@ -24,6 +24,8 @@ from .spectra import (SPECFIT_MAX_CHAN, SPECFIT_MAX_COMP, channel_widths,  # noq
                       specfit_results, specfit_start, velocity_axis)
 from .calibration import (GAINCAL_MAX_ANT, gain_results, random_gains,  # noqa: F401
                           solution_intervals)
+from .inference import (NORMAL_EQ_MAX_SEL, BurstFit, EjectionFit, LMResult,  # noqa: F401
+                        lm_minimise, unpack_triangle)
 
 
 def _torch():
@@ -1924,6 +1926,71 @@ class RTEngine:
         if trace:
             out["trace"] = tr
         return out
+
+    # -- K23 -------------------------------------------------------------------------------------
+    def _sample_stack(self, who, name, t, lead):
+        """A stack of complex (complex128 [...] or float64 [..., 2]) or real (float64 [...])
+        samples with `lead` leading dimensions -> (float64 tensor, n_part)."""
+        torch = _torch()
+        if isinstance(t, torch.Tensor) and t.dtype == torch.complex128:
+            t = torch.view_as_real(t)
+        n_part = 2 if isinstance(t, torch.Tensor) and t.dim() == lead + 1 else 1
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and
+                t.device == self.device and t.is_contiguous() and t.dim() == lead + n_part - 1 and
+                t.numel() >= 1 and (n_part == 1 or t.shape[-1] == 2)):
+            raise ValueError("%s: `%s` must be a contiguous complex128 or float64 tensor with %d "
+                             "dimensions (float64 complex samples: one more, of 2) on %s"
+                             % (who, name, lead, self.device))
+        return t, n_part
+
+    def normal_eq(self, data, model, dmodel, sel, weights=None):
+        """The normal equations of a least-squares fit from stacks on the device (rjp_normal_eq),
+        two launches and nothing going to the host -> (chi2, g[P], N_packed[P (P + 1) / 2], count)
+        device tensors (float64; `count` int64), P = len(sel): chi^2 = sum w |data - model|^2,
+        g_p = sum w Re(conj(J_p) r), N_pq = sum w Re(conj(J_p) J_q) (packed upper triangle, row by
+        row) over the samples that count -- datum and weight finite, w > 0 -- and their number.
+        `data`, `model`: complex128 [n_rows, n_vis] (or float64 [n_rows, n_vis, 2]) as `vis`
+        returns them, or float64 [n_rows, n_vis] for real samples (a light curve: n_vis = 1);
+        `dmodel`: [n_rows, n_par, n_vis] of the same kind, plane j = d model / d theta_j (`vis` of
+        the derivative maps of `ff_formal_grad`, or its `dftot` as [E F, n_par, 1]); `sel`: the
+        planes that take part, distinct, at most NORMAL_EQ_MAX_SEL -- the others are never read;
+        with no plane (chi^2 and the count alone) `dmodel` may be None; `weights`: None, [n_vis]
+        (shared by the rows) or [n_rows, n_vis].  Every sum in the order include/rjprt.h states:
+        the same bits on every call.  The workgroup count is kept in `last_normal_eq_workgroups`."""
+        torch = _torch()
+        d, n_part = self._sample_stack("normal_eq", "data", data, 2)
+        m, m_part = self._sample_stack("normal_eq", "model", model, 2)
+        if m_part != n_part or tuple(m.shape) != tuple(d.shape):
+            raise ValueError("normal_eq: `model` must be shaped like `data`")
+        n_rows, n_vis = int(d.shape[0]), int(d.shape[1])
+        sel = np.ascontiguousarray(sel, dtype=np.int32).reshape(-1)
+        P = int(sel.size)
+        if P > NORMAL_EQ_MAX_SEL:
+            raise ValueError("normal_eq: at most %d planes" % NORMAL_EQ_MAX_SEL)
+        n_par, dj = 0, None
+        if P or dmodel is not None:
+            dj, j_part = self._sample_stack("normal_eq", "dmodel", dmodel, 3)
+            n_par = int(dj.shape[1])
+            if j_part != n_part or (int(dj.shape[0]), int(dj.shape[2])) != (n_rows, n_vis):
+                raise ValueError("normal_eq: `dmodel` must be [n_rows, n_par, n_vis] = [%d, n_par, "
+                                 "%d] of the kind of `data`" % (n_rows, n_vis))
+            if P and (sel.min() < 0 or sel.max() >= n_par or np.unique(sel).size != P):
+                raise ValueError("normal_eq: `sel` must hold distinct planes in [0, %d)" % n_par)
+        dw, w_rows = None, 1
+        if weights is not None:
+            dw = self._device_f64(weights)
+            if dw.numel() not in (n_vis, n_rows * n_vis):
+                raise ValueError("normal_eq: `weights` must be [n_vis] or [n_rows, n_vis] = [%d, %d]"
+                                 % (n_rows, n_vis))
+            w_rows = dw.numel() // n_vis
+        out = self._f64(1 + P + P * (P + 1) // 2)
+        count = torch.empty(1, dtype=torch.int64, device=self.device)
+        work = self._workspace(max(1, self.lib.rjp_normal_eq_workspace(n_rows, n_vis, P)))
+        self.last_normal_eq_workgroups = self._call_tiles(
+            "rjp_normal_eq", d.data_ptr(), m.data_ptr(), _ptr(dj), n_rows, n_vis, n_part, n_par,
+            sel.ctypes.data_as(C.POINTER(C.c_int32)), P, _ptr(dw), w_rows, out.data_ptr(),
+            count.data_ptr(), work.data_ptr(), work.numel())
+        return out[0], out[1:1 + P], out[1 + P:], count[0]
 
     # -- K15 -------------------------------------------------------------------------------------
     UV_WEIGHT_MODES ={"uniform": 1, "briggs": 2}
