@@ -1508,6 +1508,53 @@ int64_t rjp_normal_eq(rjp_ctx* ctx, const double* d_data, const double* d_model,
                       int64_t w_rows, double* d_out, int64_t* d_count, void* d_work,
                       size_t work_bytes, void* stream);
 
+/* ---- K24: per-sightline Voigt fits of a line cube ---------------------------------------------------
+ * rjp_specfit (K21) fits Gaussians; the model's own lines (K3, K6) are Voigt profiles, a thermal
+ * Doppler core with pressure-broadened Lorentz wings, and an observer wants T from the Doppler width
+ * and n_e from the Lorentz width.  CASA is not at hand, so this comment IS the definition; parity is
+ * not claimed.
+ *
+ * rjp_voigtfit.  Per pixel, n_comp area-normalised Voigt components plus a linear baseline,
+ *   y(x) = sum_c F_c K(u_c, a_c) / (s_c sqrt(2 pi)) + b0 + b1 (x - x_ref),
+ *   q_c = 1 / (sqrt(2) s_c),  u_c = (x - x0_c) q_c,  a_c = g_c q_c,  K + i L = w(u + i a),
+ * w the Faddeeva function exp(-z^2) erfc(-i z).  P = 4 n_comp + 2 parameters,
+ * theta = (F_0, x0_0, s_0, g_0, [F_1, x0_1, s_1, g_1,] b0, b1): s the Doppler dispersion, g the
+ * Lorentz HWHM, both in the unit of the axis, F the component's integral over x (the area, not
+ * K21's peak: in the Lorentz limit only peak x s is determined, the area stays well conditioned).
+ * The derivatives are exact, from w' = -2 z w + 2 i / sqrt(pi).  Per trial and component, in float64:
+ *   rs = 1 / s (the one reciprocal);  q = rs * 0.70710678118654752440;  a = g * q;
+ *   cn = rs * 0.39894228040143267794
+ * and per counted channel and component:
+ *   u = (x_c - x0) * q;  (K, L) = w(u + i a) to |w_dev - w| <= 2.0e-15 |w| (both parts against the
+ *       modulus; a = 0 included)
+ *   Rw = -2 * fma(u, K, -(a * L));  Iw = fma(-2, fma(u, L, a * K), 2 / sqrt(pi))
+ *   c = F * cn;  cq = c * q;  the component is c * K
+ *   model = the components added in order, then + fma(b1, x_c - x_ref, b0)
+ *   Jacobian: dF = K * cn;  dx0 = -(cq * Rw);  ds = -(c * rs) * fma(-a, Iw, fma(u, Rw, K));
+ *             dg = -(cq * Iw);  db0 = 1;  db1 = x_c - x_ref
+ * Everything else is rjp_specfit's, word for word (see there, and lm_common.h's iteration): d_cube,
+ * h_x, x_ref, h_w, d_mask; the counted channels (y finite and w_c > 0); chi^2, N, g as fma chains in
+ * channel order with the weight on the left factor, fma(w * r, r, .), fma(w * J_i, J_j, .) (i <= j),
+ * fma(w * J_i, r, .); the fixed-parameter rule and h_free [P] (g held at 0: a Gaussian fit in area
+ * form; s held at a known thermal width); the iteration and the statuses 0 - 3; d_theta [P][n_pix]
+ * IN PLACE, d_chi2, d_cov [P (P + 1) / 2][n_pix] packed and NOT inverted, d_nchan, d_niter,
+ * d_status, the optional d_trace [n_pix][n_iter][3 + P]; the whole fit of a pixel in ONE launch, one
+ * lane per pixel, the bits of a pixel a function of its spectrum and the tables alone.  It differs in:
+ *   feasible    every s_c finite and > 0 AND every g_c finite and >= 0 (a trial with a g < 0 is
+ *               rejected)
+ *   the scales  per component max(|F|, 1e-300) for F and max(s, g, 1e-300) for x0, s and g; max(|b0|,
+ *               1e-300), max(|b1|, 1e-300)
+ *   status 3    also for a start with a g_c < 0
+ *   n_comp      1 .. RJP_VOIGTFIT_MAX_COMP; n_chan 1 .. RJP_SPECFIT_MAX_CHAN
+ * RETURNS ceil(n_pix / 64) > 0 or a negative RJP_ERR_*; nothing is written on a refusal.
+ * RJP_ERR_ARG: rjp_specfit's list with these limits. */
+#define RJP_VOIGTFIT_MAX_COMP 2
+int64_t rjp_voigtfit(rjp_ctx* ctx, const double* d_cube, int64_t n_pix, int32_t n_chan,
+                     const double* h_x, double x_ref, const double* h_w, const uint8_t* d_mask,
+                     int32_t n_comp, const uint8_t* h_free, double* d_theta, double lambda0,
+                     double xtol, int32_t n_iter, double* d_chi2, double* d_cov, int32_t* d_nchan,
+                     int32_t* d_niter, int32_t* d_status, double* d_trace, void* stream);
+
 /* ---- K4: geometry -> fields on the device --------------------------------------------
  * Replaces the lazily cached grids of JetModel (fill_factor/areas classes.py:657-669,
  * 763-764; grid_rwp 521-525; rreff 549-555; _nd 877-897; ion_fraction 915-934;

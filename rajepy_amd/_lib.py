@@ -191,6 +191,9 @@ SIGNATURES = {
     "rjp_specfit": (C.c_int64, [_P, _P, C.c_int64, C.c_int32, _DP, C.c_double, _DP, _P, C.c_int32,
                                 C.POINTER(C.c_uint8), _P, C.c_double, C.c_double, C.c_int32, _P, _P,
                                 _P, _P, _P, _P, _P]),
+    "rjp_voigtfit": (C.c_int64, [_P, _P, C.c_int64, C.c_int32, _DP, C.c_double, _DP, _P, C.c_int32,
+                                 C.POINTER(C.c_uint8), _P, C.c_double, C.c_double, C.c_int32, _P, _P,
+                                 _P, _P, _P, _P, _P]),
     "rjp_gain_apply": (C.c_int64, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32,
                                    C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P, _P]),
     "rjp_gaincal_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),

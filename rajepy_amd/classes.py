@@ -1488,6 +1488,41 @@ class JetModel:
         return Spectra(self.engine).specfit(cube.reshape(len(v), self.nx, self.nz), v, weights,
                                             comps, theta0, free, n_iter)
 
+    def voigtfit(self, cube, x, weights=None, comps=1, theta0=None, free=None, n_iter=40,
+                 mask=None, scale_errors=True):
+        """One or two Voigt profiles plus a linear baseline fitted to every sightline of any line
+        cube (as `moments`) on the device (`RTEngine.voigtfit`, rjp_voigtfit) -> dict of device
+        tensors (ni, nj) (`engine.voigt_results`: 'integral', 'centre', 'sigma', 'fwhm_g',
+        'hwhm_l', 'fwhm_l', 'peak', 'fwhm' and their 'e_*' errors per component, 'b0', 'b1',
+        'chi2', 'reduced_chi2', 'nchan', 'status', 'niter'): the Doppler width gives T, the
+        Lorentz width n_e.  Arguments as `specfit`'s with P = 4 comps + 2 parameters (F, x0, s, g
+        per component, b0, b1); `theta0` None = `engine.voigt_start` (one component only).
+        Calling rank only."""
+        return Spectra(self.engine).voigtfit(cube, x, weights, comps, theta0, free, n_iter, mask,
+                                             scale_errors)
+
+    def voigtfit_rrl(self, rrl, freq, quantity="flux", contsub=True, formal=False, weights=None,
+                     comps=1, theta0=None, free=None, n_iter=40):
+        """`voigtfit` of one of the model's own cubes of the line `rrl` over the channels `freq`,
+        which stays on the device, along the radio velocity axis of the line [km/s].
+        quantity="flux": the `flux_rrl` cube (`contsub`, `formal` as there); quantity="tau": the
+        line's optical-depth cube (no flux is computed) -- tau(nu) of a thin uniform sightline is
+        one exact Voigt profile, so the fitted widths mean something there.  With free=None the
+        baseline is held at 0 for "tau" and for a continuum-subtracted "flux".  Calling rank
+        only."""
+        if quantity not in ("flux", "tau"):
+            raise ValueError("voigtfit_rrl: `quantity` must be 'flux' or 'tau'")
+        v, _ = self._rrl_velocity_axis(rrl, freq)
+        freqs = np.atleast_1d(np.asarray(freq, dtype=np.float64))
+        if quantity == "tau":
+            cube = self._rrl_tau_device(rrl, freqs)
+        else:
+            cube = self._flux_maps(freqs, rrl=rrl, contsub=contsub, formal=formal)
+        if free is None and (quantity == "tau" or contsub):
+            free = [1] * (4 * int(comps)) + [0, 0]
+        return Spectra(self.engine).voigtfit(cube.reshape(len(v), self.nx, self.nz), v, weights,
+                                             comps, theta0, free, n_iter)
+
     # ------------------------------------------------------------------ antenna gains (K22) ----
     def corrupt_gains(self, vis, tracks, gains, h_sol):
         """The visibilities `vis` -- (F, K) complex, a host array or a device tensor in the order

@@ -450,6 +450,41 @@ inline int check_specfit(const double* d_cube, int64_t n_pix, int n_chan, const 
   return RJP_OK;
 }
 
+// What rjp_voigtfit takes: rjp_specfit's list in rjp_specfit's order, with 4 n_comp + 2 parameters.
+inline int check_voigtfit(const double* d_cube, int64_t n_pix, int n_chan, const double* h_x,
+                          double x_ref, const double* h_w, int n_comp, const uint8_t* h_free,
+                          const double* d_theta, double lambda0, double xtol, int n_iter,
+                          const double* d_chi2, const double* d_cov, const int32_t* d_nchan,
+                          const int32_t* d_niter, const int32_t* d_status, std::string& err) {
+  if (!d_cube || !h_x || !d_theta || !d_chi2 || !d_cov || !d_nchan || !d_niter || !d_status)
+    return refuse(err, "rjp_voigtfit: NULL cube, axis, parameters or outputs");
+  if (n_pix < 1 || n_chan < 1) return refuse(err, "rjp_voigtfit: n_pix and n_chan must be positive");
+  if (n_chan > RJP_SPECFIT_MAX_CHAN)
+    return refuse(err, "rjp_voigtfit: n_chan exceeds RJP_SPECFIT_MAX_CHAN (" +
+                           std::to_string(RJP_SPECFIT_MAX_CHAN) + ")");
+  if (n_comp < 1 || n_comp > RJP_VOIGTFIT_MAX_COMP)
+    return refuse(err, "rjp_voigtfit: n_comp must lie in 1 .. RJP_VOIGTFIT_MAX_COMP (" +
+                           std::to_string(RJP_VOIGTFIT_MAX_COMP) + ")");
+  for (int c = 0; c < n_chan; ++c)
+    if (!std::isfinite(h_x[c])) return refuse(err, "rjp_voigtfit: non-finite h_x");
+  if (!std::isfinite(x_ref)) return refuse(err, "rjp_voigtfit: non-finite x_ref");
+  if (h_w)
+    for (int c = 0; c < n_chan; ++c)
+      if (!(h_w[c] >= 0.0) || !std::isfinite(h_w[c]))
+        return refuse(err, "rjp_voigtfit: negative or non-finite h_w");
+  if (h_free) {
+    bool any = false;
+    for (int i = 0; i < 4 * n_comp + 2; ++i) any = any || h_free[i] != 0;
+    if (!any) return refuse(err, "rjp_voigtfit: no free parameter");
+  }
+  if (!(lambda0 > 0.0) || !std::isfinite(lambda0) || !(xtol > 0.0) || !std::isfinite(xtol))
+    return refuse(err, "rjp_voigtfit: lambda0 and xtol must be finite and positive");
+  if (n_iter < 1) return refuse(err, "rjp_voigtfit: n_iter < 1");
+  if ((n_pix + 63) / 64 > (int64_t)INT32_MAX)
+    return refuse(err, "rjp_voigtfit: more than 2^31 - 1 workgroups");
+  return RJP_OK;
+}
+
 // The interval table of K22: h_sol[0] = 0, steps of 0 or 1, n_sol = h_sol[n_t - 1] + 1.
 inline bool sol_ok(const int32_t* h_sol, int n_t, int n_sol) {
   if (h_sol[0] != 0) return false;

@@ -428,6 +428,15 @@ hipError_t specfit_launch(const double* cube, int64_t n_pix, int n_chan, const d
                           int n_iter, double* chi2, double* cov, int32_t* nchan, int32_t* niter,
                           int32_t* status, double* trace, hipStream_t st);
 
+// ---- voigtfit.hip: per-sightline Voigt fits of a line cube (K24) ---------------------------------
+// specfit_launch's arguments and grid (specfit_workgroups); `free_bits` over the 4 n_comp + 2
+// parameters (F, x0, s, g per component, b0, b1)
+hipError_t voigtfit_launch(const double* cube, int64_t n_pix, int n_chan, const double* d_x,
+                           const double* d_w, double x_ref, const uint8_t* mask, int n_comp,
+                           unsigned free_bits, double* theta, double lambda0, double xtol,
+                           int n_iter, double* chi2, double* cov, int32_t* nchan, int32_t* niter,
+                           int32_t* status, double* trace, hipStream_t st);
+
 // ---- gaincal.hip: antenna-based complex gains (K22) ----------------------------------------------
 // one thread per visibility, workgroups of 256
 int64_t gain_apply_workgroups(int n_maps, int n_t, int n_ant);

@@ -1460,6 +1460,34 @@ int64_t rjp_specfit(rjp_ctx* ctx, const double* d_cube, int64_t n_pix, int32_t n
   return r ? r : rjp::specfit_workgroups(n_pix);
 }
 
+int64_t rjp_voigtfit(rjp_ctx* ctx, const double* d_cube, int64_t n_pix, int32_t n_chan,
+                     const double* h_x, double x_ref, const double* h_w, const uint8_t* d_mask,
+                     int32_t n_comp, const uint8_t* h_free, double* d_theta, double lambda0,
+                     double xtol, int32_t n_iter, double* d_chi2, double* d_cov, int32_t* d_nchan,
+                     int32_t* d_niter, int32_t* d_status, double* d_trace, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_voigtfit(d_cube, n_pix, n_chan, h_x, x_ref, h_w, n_comp, h_free,
+                                        d_theta, lambda0, xtol, n_iter, d_chi2, d_cov, d_nchan,
+                                        d_niter, d_status, m);
+      }))
+    return r;
+  unsigned free_bits = 0;
+  for (int i = 0; i < 4 * n_comp + 2; ++i)
+    if (!h_free || h_free[i]) free_bits |= 1u << i;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t F = (size_t)n_chan;
+  const int r = staged(ctx, st, "voigtfit_launch", nullptr, {{h_x, F}, {h_w ? h_w : h_x, h_w ? F : 0}},
+                       [&](double* const* d, const double*) {
+                         return rjp::voigtfit_launch(d_cube, n_pix, n_chan, d[0],
+                                                     h_w ? d[1] : nullptr, x_ref, d_mask, n_comp,
+                                                     free_bits, d_theta, lambda0, xtol, n_iter,
+                                                     d_chi2, d_cov, d_nchan, d_niter, d_status,
+                                                     d_trace, st);
+                       });
+  return r ? r : rjp::specfit_workgroups(n_pix);
+}
+
 int64_t rjp_gain_apply(rjp_ctx* ctx, const double* d_vis, int32_t n_maps, int32_t n_t,
                        int32_t n_ant, const double* d_gains, int32_t g_maps, const int32_t* h_sol,
                        int32_t n_sol, int32_t mode, double* d_out, void* stream) {

@@ -20,8 +20,9 @@ from .imaging import (SIDEREAL_DAY_S, AntennaConfig, Geodetic, antenna_config_pa
                       taylor_weights, thermal_sigma, vis_scales)
 from .imaging import (UVFIT_MAX_COMP, uvfit_components, uvfit_results, uvfit_start,  # noqa: F401
                       uvfit_theta, uvfit_theta_from_imfit)
-from .spectra import (SPECFIT_MAX_CHAN, SPECFIT_MAX_COMP, channel_widths,  # noqa: F401
-                      specfit_results, specfit_start, velocity_axis)
+from .spectra import (SPECFIT_MAX_CHAN, SPECFIT_MAX_COMP, VOIGTFIT_MAX_COMP,  # noqa: F401
+                      channel_widths, specfit_results, specfit_start, velocity_axis, voigt_results,
+                      voigt_start)
 from .calibration import (GAINCAL_MAX_ANT, gain_results, random_gains,  # noqa: F401
                           solution_intervals)
 from .inference import (NORMAL_EQ_MAX_SEL, BurstFit, EjectionFit, LMResult,  # noqa: F401
@@ -1747,16 +1748,24 @@ class RTEngine:
         all pixels -- b0 = b1 = 0 held is the fit of a continuum-subtracted cube.  A channel
         counts when it is finite and its weight > 0.  The iteration is `uvfit`'s.  The bits of a
         pixel depend on its spectrum and the tables alone."""
+        return self._line_fit("specfit", "rjp_specfit", 3, SPECFIT_MAX_COMP, cube, x, theta, x_ref,
+                              weights, free, n_comp, lambda0, xtol, n_iter, mask, trace)
+
+    def _line_fit(self, who, symbol, per_comp, max_comp, cube, x, theta, x_ref, weights, free, n_comp,
+                  lambda0, xtol, n_iter, mask, trace):
+        """What `specfit` (K21) and `voigtfit` (K24) share: the checks, the buffers and the call of
+        `symbol` with P = per_comp n_comp + 2 parameter planes -> the dict both return.  The number
+        of workgroups is kept in `last_specfit_workgroups` (one grid for both: 64 pixels each)."""
         torch = _torch()
         n_iter, n_comp = int(n_iter), int(n_comp)
         if n_iter < 1:
-            raise ValueError("specfit: n_iter must be positive")
-        if not 1 <= n_comp <= SPECFIT_MAX_COMP:
-            raise ValueError("specfit: n_comp must be 1 to %d" % SPECFIT_MAX_COMP)
-        cube, x, F, npix = self._line_cube("specfit", cube, x)
+            raise ValueError(who + ": n_iter must be positive")
+        if not 1 <= n_comp <= max_comp:
+            raise ValueError(who + ": n_comp must be 1 to %d" % max_comp)
+        cube, x, F, npix = self._line_cube(who, cube, x)
         if not (np.isfinite(lambda0) and lambda0 > 0. and np.isfinite(xtol) and xtol > 0.):
-            raise ValueError("specfit: `lambda0` and `xtol` must be finite and positive")
-        P = 3 * n_comp + 2
+            raise ValueError(who + ": `lambda0` and `xtol` must be finite and positive")
+        P = per_comp * n_comp + 2
         if isinstance(theta, torch.Tensor):
             th = theta.to(device=self.device, dtype=torch.float64)
         else:
@@ -1764,7 +1773,7 @@ class RTEngine:
         if th.dim() == 1:
             th = th.reshape(-1, 1).expand(-1, npix)
         if th.shape[0] != P or th.numel() != P * npix:
-            raise ValueError("specfit: `theta` must be [P] or [P, n_pix] = [%d, %d]" % (P, npix))
+            raise ValueError(who + ": `theta` must be [P] or [P, n_pix] = [%d, %d]" % (P, npix))
         th = th.reshape(P, npix).contiguous().clone()
         hw = None
         if weights is not None:
@@ -1772,15 +1781,15 @@ class RTEngine:
                                       if isinstance(weights, torch.Tensor) else weights,
                                       dtype=np.float64).reshape(-1)
             if wv.size != F:
-                raise ValueError("specfit: `weights` must have one entry per channel (%d)" % F)
+                raise ValueError(who + ": `weights` must have one entry per channel (%d)" % F)
             hw = _lib.dbl_array(wv)
         hfree = None
         if free is not None:
             fr = np.ascontiguousarray(np.asarray(free) != 0, dtype=np.uint8).reshape(-1)
             if fr.size != P or not fr.any():
-                raise ValueError("specfit: `free` must hold %d flags, at least one of them set" % P)
+                raise ValueError(who + ": `free` must hold %d flags, at least one of them set" % P)
             hfree = (C.c_uint8 * P)(*fr)
-        dmask = self._device_mask("specfit", mask, npix)
+        dmask = self._device_mask(who, mask, npix)
         T = P * (P + 1) // 2
         chi2 = torch.full((npix,), float("nan"), dtype=torch.float64, device=self.device)
         cov = torch.full((T, npix), float("nan"), dtype=torch.float64, device=self.device)
@@ -1789,7 +1798,7 @@ class RTEngine:
         tr = (torch.full((npix, n_iter, 3 + P), float("nan"), dtype=torch.float64,
                          device=self.device) if trace else None)
         self.last_specfit_workgroups = self._call_tiles(
-            "rjp_specfit", cube.data_ptr(), npix, F, _lib.dbl_array(x), float(x_ref), hw,
+            symbol, cube.data_ptr(), npix, F, _lib.dbl_array(x), float(x_ref), hw,
             _ptr(dmask), n_comp, hfree, th.data_ptr(), float(lambda0), float(xtol), n_iter,
             chi2.data_ptr(), cov.data_ptr(), nchan.data_ptr(), niter.data_ptr(),
             status.data_ptr(), _ptr(tr))
@@ -1797,6 +1806,22 @@ class RTEngine:
         if trace:
             out["trace"] = tr
         return out
+
+    # -- K24 -------------------------------------------------------------------------------------
+    def voigtfit(self, cube, x, theta, x_ref, weights=None, free=None, n_comp=1, lambda0=1e-3,
+                 xtol=1e-10, n_iter=40, mask=None, trace=False):
+        """One Levenberg-Marquardt fit per pixel of `n_comp` area-normalised Voigt profiles plus a
+        linear baseline, y(x) = sum_c F_c Re w(u_c + i a_c) / (s_c sqrt(2 pi)) + b0 + b1 (x -
+        x_ref), u = (x - x0) / (sqrt(2) s), a = g / (sqrt(2) s), to a line cube (rjp_voigtfit):
+        `specfit` with the profile the model's own lines have -> the same dict of device tensors,
+        with P = 4 n_comp + 2 parameter planes (F_0, x0_0, s_0, g_0, [F_1, x0_1, s_1, g_1,] b0,
+        b1): F the component's integral over x, s the Doppler dispersion, g the Lorentz HWHM, both
+        in the unit of `x`.  Every argument as `specfit`'s; `theta`: the start (`voigt_start`),
+        degenerate (status 3) also where a g < 0; `free` may hold g at 0 (a Gaussian fit in area
+        form) or s at a known thermal width.  A trial with an s <= 0 or a g < 0 is rejected.
+        The number of workgroups is kept in `last_specfit_workgroups`."""
+        return self._line_fit("voigtfit", "rjp_voigtfit", 4, VOIGTFIT_MAX_COMP, cube, x, theta, x_ref,
+                              weights, free, n_comp, lambda0, xtol, n_iter, mask, trace)
 
     # -- K22 -------------------------------------------------------------------------------------
     GAIN_APPLY_MODES = {"corrupt": 0, "correct": 1}
