@@ -1555,6 +1555,95 @@ int64_t rjp_voigtfit(rjp_ctx* ctx, const double* d_cube, int64_t n_pix, int32_t 
                      double xtol, int32_t n_iter, double* d_chi2, double* d_cov, int32_t* d_nchan,
                      int32_t* d_niter, int32_t* d_status, double* d_trace, void* stream);
 
+/* ---- K25: robust image statistics, connected components, constrained growth of a mask -------------
+ * What an automatic clean mask (tclean's usemask = 'auto-multithresh') is made of, on stacks that are
+ * already on the device.  Integer and order-statistic work: every output but two sums is a function
+ * of the inputs alone, the same bits on every call.  CASA is not at hand, so this comment IS the
+ * definition; parity is not claimed.
+ * Common to the three: images and masks in the pixel order p = ix nz + iz (K12's); masks are uint8,
+ * non-zero = set; n_mask is 1 (one mask for all maps) or n_maps, as n_psf is in K12; n_maps 1 ..
+ * RJP_REGIONS_MAX_MAPS, nx 1 .. RJP_REGIONS_MAX_NX, nz >= 1, nx nz <= 2^31 - 1; d_work 8-byte
+ * aligned.  No floating-point atomics anywhere; workgroups meet only in integer atomics and at launch
+ * boundaries.  Everything is validated before anything is enqueued, and no output or workspace byte
+ * is touched on a refusal: RJP_ERR_ARG for a NULL ctx or a NULL required pointer, sizes outside the
+ * ranges above, an n_mask that is neither 1 nor n_maps, and what each call adds below;
+ * RJP_ERR_WORKSPACE for a d_work that is NULL, smaller than the call's workspace query (0 from a
+ * query = a bad argument) or not 8-byte aligned.
+ *
+ * rjp_image_stats.  Per map m, over its COUNTING pixels: pixel p counts when d_img[m][p] is finite
+ * and, with a d_mask, (mask[p] != 0) == (sense != 0) -- sense 1 measures inside the mask, 0 outside
+ * it; d_mask NULL: every finite pixel (n_mask and sense are then ignored).
+ *   d_stats [n_maps][8]: count; n_nonfinite (the pixels the mask selects that are NaN or +-inf);
+ *                        min; max; median; mad; sum; sumsq
+ *   order      ascending IEEE total order on the finite values: numerical order, with -0.0 < +0.0
+ *   median     the LOWER median: the element of rank (count - 1) / 2 (integer division, rank 0 the
+ *              smallest).  No two values are averaged: it is an element of the input, no rounding.
+ *   mad        the element of the same rank of fabs(x - median), one rounding per pixel (an
+ *              overflowing difference is +inf and sorts last), formed on the fly from the median that
+ *              the first stage left in d_stats: no host round trip, no temporary image.
+ *   min, max   by the same order (so min of {-0.0, +0.0} is -0.0)
+ *   count = 0  median = mad = min = max = NaN, sum = sumsq = +0.0
+ *   sum, sumsq in a fixed order.  A tile is 2048 consecutive pixels of the map.  Lane t (0 .. 255) of
+ *              a tile starts at +0 and takes the tile's counting pixels t, t + 256, t + 512, ... in
+ *              that order, s <- s + x and q <- fma(x, x, q); the 256 lane values are folded by
+ *              halving, v[t] <- v[t] + v[t + h] for h = 128, 64, ..., 1; the tiles are added in tile
+ *              order starting from tile 0's value.
+ * The selection is an exact radix select on the order-preserving 64-bit key of the double, six digits
+ * of 11, 11, 11, 11, 11 and 9 bits from the top: per digit every workgroup counts its pixels in a
+ * histogram in LDS and adds it to the map's histogram in the workspace (integer atomics both), then
+ * one workgroup per map picks the bin that holds the rank.  26 launches, no host synchronisation.
+ * RETURNS n_maps x ceil(nx nz / 2048) > 0 or a negative RJP_ERR_*.
+ *
+ * rjp_label_regions.  The connected components of the non-zero pixels of d_mask_in [n_mask][nx nz];
+ * connectivity 1: the four edge neighbours, 2: the eight edge and corner neighbours (else
+ * RJP_ERR_ARG).
+ *   d_label [n_maps][nx nz] int32: 0 on background, otherwise 1 + the smallest pixel index p of the
+ *                           pixel's region -- a function of the input alone, whatever order the
+ *                           merges happen in
+ *   d_area  [n_maps][nx nz] int32 or NULL: the pixel count of the region on each of its pixels, 0 on
+ *                           background
+ *   d_nreg  [n_maps] int32: the number of regions
+ * Union-find per tile of 16 x 64 pixels in LDS, a merge of the tile borders in global memory with
+ * atomic minima on the parents, a flatten pass, an area pass (an integer atomic add at the root, then
+ * a gather).  Parents only ever decrease and are bounded below by 0, which ends every loop that
+ * follows parents or retries a union; each such loop is also capped at nx nz iterations and, when a
+ * cap is hit, sets the first int32 of d_work (0 otherwise; cleared by every call) instead of
+ * spinning: the caller reads that word after the call and treats non-zero as an error.
+ * RETURNS n_maps x ceil(nx / 16) x ceil(nz / 64) > 0 or a negative RJP_ERR_*.
+ *
+ * rjp_mask_grow.  Geodesic dilation IN PLACE on d_seed [n_maps][nx nz] under d_con [n_mask][nx nz].
+ * One step is seed <- seed OR (dilate(seed) AND con), dilate by the neighbours of `connectivity`, the
+ * outside of the image unset: scipy.ndimage.binary_dilation(seed, structure, iterations = n_iter,
+ * mask = con).  A seed pixel outside the constraint stays.
+ *   n_iter = 0   nothing is done: d_seed keeps its bytes
+ *   n_iter > 0   exactly n_iter steps, ceil(n_iter / RJP_GROW_HALO) launches: a tile with a halo of
+ *                RJP_GROW_HALO pixels is staged in LDS and advanced that many steps per launch, the
+ *                last launch the remainder; the launches alternate between d_seed and a plane of the
+ *                workspace.  On return every pixel of d_seed is 0 or 1.
+ *   n_iter < 0   until stable (morphological reconstruction), not a loop of launches: d_con is
+ *                labelled as by rjp_label_regions; a region is kept when one of its pixels is a seed
+ *                or a neighbour of a seed (an integer flag at the root); d_seed <- 1 on the kept
+ *                regions, its other bytes as they were.  A d_con that all maps share (n_mask =
+ *                1) is labelled once.  The cap flag as above.
+ * RETURNS n_maps x ceil(nx / 16) x ceil(nz / 64) > 0 or a negative RJP_ERR_*; RJP_ERR_ARG also for a
+ * connectivity that is neither 1 nor 2. */
+#define RJP_REGIONS_MAX_MAPS 65535
+#define RJP_REGIONS_MAX_NX 1048560        /* 16 x 65535 */
+#define RJP_GROW_HALO 8
+size_t rjp_image_stats_workspace(int32_t n_maps, int32_t nx, int32_t nz);
+int64_t rjp_image_stats(rjp_ctx* ctx, const double* d_img, int32_t n_maps, int32_t nx, int32_t nz,
+                        const uint8_t* d_mask, int32_t n_mask, int32_t sense, double* d_stats,
+                        void* d_work, size_t work_bytes, void* stream);
+size_t rjp_label_regions_workspace(int32_t n_maps, int32_t nx, int32_t nz);
+int64_t rjp_label_regions(rjp_ctx* ctx, const uint8_t* d_mask_in, int32_t n_mask, int32_t n_maps,
+                          int32_t nx, int32_t nz, int32_t connectivity, int32_t* d_label,
+                          int32_t* d_area, int32_t* d_nreg, void* d_work, size_t work_bytes,
+                          void* stream);
+size_t rjp_mask_grow_workspace(int32_t n_maps, int32_t nx, int32_t nz);
+int64_t rjp_mask_grow(rjp_ctx* ctx, uint8_t* d_seed, const uint8_t* d_con, int32_t n_mask,
+                      int32_t n_maps, int32_t nx, int32_t nz, int32_t n_iter, int32_t connectivity,
+                      void* d_work, size_t work_bytes, void* stream);
+
 /* ---- K4: geometry -> fields on the device --------------------------------------------
  * Replaces the lazily cached grids of JetModel (fill_factor/areas classes.py:657-669,
  * 763-764; grid_rwp 521-525; rreff 549-555; _nd 877-897; ion_fraction 915-934;

@@ -205,6 +205,15 @@ SIGNATURES = {
     "rjp_normal_eq": (C.c_int64, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                   C.POINTER(C.c_int32), C.c_int32, _P, C.c_int64, _P, _P, _P,
                                   C.c_size_t, _P]),
+    "rjp_image_stats_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "rjp_image_stats": (C.c_int64, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32,
+                                    _P, _P, C.c_size_t, _P]),
+    "rjp_label_regions_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "rjp_label_regions": (C.c_int64, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                      _P, _P, _P, _P, C.c_size_t, _P]),
+    "rjp_mask_grow_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "rjp_mask_grow": (C.c_int64, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                  C.c_int32, _P, C.c_size_t, _P]),
     "rjp_uv_weights_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "rjp_uv_weights": (C.c_int64, [_P, C.c_int32, C.c_int32, _DP, _DP, _P, _P, _P, C.c_int32,
                                    C.c_int32, C.c_int32, C.c_double, _P, _P, _P, _P, C.c_size_t, _P]),

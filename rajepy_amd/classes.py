@@ -1188,8 +1188,8 @@ class JetModel:
     # ------------------------------------------------------------------ CLEAN ----
     def clean_image_ff(self, u_m, v_m, freq, weights=None, shape=None, cell_as=None, formal=False,
                        mfs=False, niter=500, gain=0.1, threshold_jy=0.0, mask=None, beam=None,
-                       psf_shape=None, imfit=None, weighting=None, robust=0.5, scales=None,
-                       scale_bias=None, nterms=1, reffreq_hz=None, alpha_cut_jy=None,
+                       psf_shape=None, imfit=None, weighting=None, robust=0.5, automask=None,
+                       scales=None, scale_bias=None, nterms=1, reffreq_hz=None, alpha_cut_jy=None,
                        major_cycles=0, cyclefactor=1.5, cycleniter=None,
                        min_psf_fraction=0.05, max_psf_fraction=0.8):
         """CLEANed, restored images [Jy / clean beam] of the `flux_ff` maps as an array with the
@@ -1257,7 +1257,23 @@ class JetModel:
         twice the clean beam's half-power ellipse: this project's definition, not CASA's.
         `residual`, `model`, `image` and `peak_residual` are then functions of the final list and
         the data whatever the window, and `CleanResult.major` holds per map `runs` (dicts `start`,
-        `n`, `peak`, `threshold`), `sidelobe` and `vis_residual` (complex [K]; [F K] with `mfs`)."""
+        `n`, `peak`, `threshold`), `sidelobe` and `vis_residual` (complex [K]; [F K] with `mfs`).
+        `automask`: None = the mask is `mask`, as above.  True, or a dict of `sidelobe_threshold`
+        (3.0), `noise_threshold` (5.0), `low_noise_threshold` (1.5), `min_beam_frac` (0.3),
+        `grow_iterations` (75), `connectivity` (1), `nsigma` (0.0) = every map is cleaned under a
+        mask of its own, made on the device from its residual (K25: `RTEngine.image_stats`,
+        `label_regions`, `mask_grow`; the convention is `engine.automask_step`) and bounded by
+        `mask` -- tclean's usemask='auto-multithresh' without its smoothing, second prune and
+        negative threshold; this project's definition, no CASA parity.  Seeds are the pixels above
+        max(sidelobe_threshold x sidelobe x peak, median + noise_threshold x sigma), sigma = 1.4826
+        x the MAD of the residual outside the mask so far; seed regions smaller than
+        `min_beam_frac` of the beam area are dropped and the rest grown `grow_iterations` steps
+        inside the pixels above the low threshold.  Without major cycles the mask is made once,
+        from the dirty image; with them at the top of every run, and it only grows.  `nsigma` > 0:
+        a run also stops at nsigma x that update's sigma (tclean's `nsigma` on a robust noise from
+        the residual).  One `RTEngine.clean` call per map instead of one per chunk.
+        `CleanResult.automask` holds per map `mask` (bool (ni, nj)) and `runs` (one dict per
+        update).  Not with `scales` or `nterms` > 1 (ValueError)."""
         im, *vis = self._model_vis(u_m, v_m, freq, weighting, formal=formal)
         return im._clean_images(*vis, weights, shape, cell_as, mfs, niter, gain, threshold_jy, mask,
                                 beam, psf_shape, imfit, weighting=weighting, robust=robust,
@@ -1265,13 +1281,16 @@ class JetModel:
                                 alpha_cut_jy=alpha_cut_jy, major_cycles=major_cycles,
                                 cyclefactor=cyclefactor,
                                 cycleniter=cycleniter, min_psf_fraction=min_psf_fraction,
-                                max_psf_fraction=max_psf_fraction)
+                                max_psf_fraction=max_psf_fraction,
+                                # (named only when set: without it the call is the one it was, also for
+                                # a stand-in `Imager` with the earlier parameter list)
+                                **({} if automask is None else dict(automask=automask)))
 
     def clean_image_rrl(self, rrl, u_m, v_m, freq, weights=None, shape=None, cell_as=None,
                         contsub=True, formal=False, mfs=False, niter=500, gain=0.1,
                         threshold_jy=0.0, mask=None, beam=None, psf_shape=None, imfit=None,
-                        weighting=None, robust=0.5, scales=None, scale_bias=None, nterms=1,
-                        reffreq_hz=None, alpha_cut_jy=None,
+                        weighting=None, robust=0.5, automask=None, scales=None, scale_bias=None,
+                        nterms=1, reffreq_hz=None, alpha_cut_jy=None,
                         major_cycles=0, cyclefactor=1.5, cycleniter=None,
                         min_psf_fraction=0.05, max_psf_fraction=0.8):
         """CLEANed, restored images of the `flux_rrl` maps (same arguments) -> `CleanResult`; see
@@ -1283,7 +1302,10 @@ class JetModel:
                                 alpha_cut_jy=alpha_cut_jy, major_cycles=major_cycles,
                                 cyclefactor=cyclefactor,
                                 cycleniter=cycleniter, min_psf_fraction=min_psf_fraction,
-                                max_psf_fraction=max_psf_fraction)
+                                max_psf_fraction=max_psf_fraction,
+                                # (named only when set: without it the call is the one it was, also for
+                                # a stand-in `Imager` with the earlier parameter list)
+                                **({} if automask is None else dict(automask=automask)))
 
     # ------------------------------------------------------------------ synthetic observations ----
     def uv_tracks(self, antennalist, t_obs_s, t_int_s, min_el_deg=None, hourangle_h=0.):
@@ -1310,8 +1332,8 @@ class JetModel:
                    sigma_jy=None, sefd_jy=None, chanwidth_hz=None, seed=0, nsigma=0.,
                    weights=None, shape=None, cell_as=None, formal=False, mfs=False, niter=500,
                    gain=0.1, threshold_jy=0.0, mask=None, beam=None, psf_shape=None, imfit=None,
-                   weighting=None, robust=0.5, scales=None, scale_bias=None, nterms=1,
-                   reffreq_hz=None, alpha_cut_jy=None, major_cycles=0,
+                   weighting=None, robust=0.5, automask=None, scales=None, scale_bias=None,
+                   nterms=1, reffreq_hz=None, alpha_cut_jy=None, major_cycles=0,
                    cyclefactor=1.5, cycleniter=None, min_psf_fraction=0.05, max_psf_fraction=0.8):
         """A synthetic observation of the `flux_ff` maps, start to end on the device -- the
         reference's simobserve -> tclean -> imfit chain (classes.py:2490-2850) -> `Observation`:
@@ -1334,16 +1356,16 @@ class JetModel:
         return self._observe(dict(formal=formal), antennalist, freq, t_obs_s, t_int_s, min_el_deg,
                              hourangle_h, sigma_jy, sefd_jy, chanwidth_hz, seed, nsigma, weights,
                              shape, cell_as, mfs, niter, gain, threshold_jy, mask, beam, psf_shape,
-                             imfit, weighting, robust, scales, scale_bias, nterms, reffreq_hz,
-                             alpha_cut_jy, major_cycles, cyclefactor, cycleniter,
+                             imfit, weighting, robust, automask, scales, scale_bias, nterms,
+                             reffreq_hz, alpha_cut_jy, major_cycles, cyclefactor, cycleniter,
                              min_psf_fraction, max_psf_fraction)
 
     def observe_rrl(self, rrl, antennalist, freq, t_obs_s, t_int_s, min_el_deg=None,
                     hourangle_h=0., sigma_jy=None, sefd_jy=None, chanwidth_hz=None, seed=0,
                     nsigma=0., weights=None, shape=None, cell_as=None, contsub=True, formal=False,
                     mfs=False, niter=500, gain=0.1, threshold_jy=0.0, mask=None, beam=None,
-                    psf_shape=None, imfit=None, weighting=None, robust=0.5, scales=None,
-                    scale_bias=None, nterms=1, reffreq_hz=None, alpha_cut_jy=None,
+                    psf_shape=None, imfit=None, weighting=None, robust=0.5, automask=None,
+                    scales=None, scale_bias=None, nterms=1, reffreq_hz=None, alpha_cut_jy=None,
                     major_cycles=0, cyclefactor=1.5, cycleniter=None,
                     min_psf_fraction=0.05, max_psf_fraction=0.8):
         """A synthetic observation of the `flux_rrl` maps -> `Observation`; see `observe_ff`."""
@@ -1351,9 +1373,29 @@ class JetModel:
         return self._observe(dict(rrl=rrl, contsub=contsub, formal=formal), antennalist, freq,
                              t_obs_s, t_int_s, min_el_deg, hourangle_h, sigma_jy, sefd_jy,
                              chanwidth_hz, seed, nsigma, weights, shape, cell_as, mfs, niter, gain,
-                             threshold_jy, mask, beam, psf_shape, imfit, weighting, robust, scales,
-                             scale_bias, nterms, reffreq_hz, alpha_cut_jy, major_cycles,
-                             cyclefactor, cycleniter, min_psf_fraction, max_psf_fraction)
+                             threshold_jy, mask, beam, psf_shape, imfit, weighting, robust,
+                             automask, scales, scale_bias, nterms, reffreq_hz, alpha_cut_jy,
+                             major_cycles, cyclefactor, cycleniter, min_psf_fraction,
+                             max_psf_fraction)
+
+    # ------------------------------------------------------------------ imstat, automask ----
+    def imstat(self, images, mask=None, inside=True):
+        """Robust statistics of each of `images` -- (F, ni, nj) or (ni, nj), a host array or a
+        device tensor, such as a `CleanResult.residual` -- on the device (`RTEngine.image_stats`,
+        rjp_image_stats) -> list of dicts, one per image (`engine.image_stats_results`): `npts`,
+        `min`, `max`, `median` (the lower median), `medabsdevmed`, `sigma_robust`, `sum`, `mean`,
+        `rms`, `sigma`, over the finite pixels.  `mask`: None, or (ni, nj) / (F, ni, nj), non-zero
+        = set: the pixels inside it count, with `inside=False` those outside.  Calling rank only."""
+        return self._imager.imstat(images, mask, inside)
+
+    def automask(self, images, beam, sidelobe=0., mask=None, prev=None, **options):
+        """One update of the automatic clean mask for images already made -> (masks bool
+        (F, ni, nj), info: one dict per image); see the `automask` keyword of `clean_image_ff`,
+        whose options `options` are.  `beam`: the clean beam (bmaj_as, bmin_as, bpa_deg), one or
+        one per image; `sidelobe`: the beam's sidelobe level, one or one per image
+        (`CleanResult.major[m]['sidelobe']`); `mask`: None or (ni, nj), what bounds the automatic
+        mask; `prev`: None or (F, ni, nj), the masks so far.  Calling rank only."""
+        return self._imager.automask(images, beam, sidelobe, mask, prev, options)
 
     # ------------------------------------------------------------------ imfit ----
     def imfit(self, images, beam, cell_as=None, box=None, theta0=None, n_iter=60, rms=None):

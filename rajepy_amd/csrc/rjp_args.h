@@ -646,4 +646,60 @@ inline int check_vis_noise(const double* d_vis, int n_maps, int n_vis, const dou
   return RJP_OK;
 }
 
+// The stack sizes K25's three calls share, in the order they refuse: the counts, the limits of the
+// launch grid, the pixel index.
+inline int check_region_sizes(const char* who, int n_maps, int nx, int nz, std::string& err) {
+  const std::string w = who;
+  if (n_maps < 1 || nx < 1 || nz < 1)
+    return refuse(err, w + ": n_maps, nx and nz must be positive");
+  if (n_maps > RJP_REGIONS_MAX_MAPS)
+    return refuse(err, w + ": n_maps exceeds RJP_REGIONS_MAX_MAPS (" +
+                           std::to_string(RJP_REGIONS_MAX_MAPS) + ")");
+  if (nx > RJP_REGIONS_MAX_NX)
+    return refuse(err, w + ": nx exceeds RJP_REGIONS_MAX_NX (" +
+                           std::to_string(RJP_REGIONS_MAX_NX) + ")");
+  if ((int64_t)nx * nz > (int64_t)INT32_MAX) return refuse(err, w + ": nx * nz exceeds 2^31 - 1");
+  return RJP_OK;
+}
+
+// What rjp_image_stats takes, in the order it refuses: NULL pointers, the sizes, n_mask with a mask,
+// the workgroups.  (`d_mask` may be NULL; `sense` is any integer.)
+inline int check_image_stats(const double* d_img, int n_maps, int nx, int nz, const uint8_t* d_mask,
+                             int n_mask, const double* d_stats, std::string& err) {
+  if (!d_img || !d_stats) return refuse(err, "rjp_image_stats: NULL image or output");
+  if (int r = check_region_sizes("rjp_image_stats", n_maps, nx, nz, err)) return r;
+  if (d_mask && n_mask != 1 && n_mask != n_maps)
+    return refuse(err, "rjp_image_stats: n_mask must be 1 or n_maps");
+  if (((int64_t)nx * nz + 2047) / 2048 * n_maps > (int64_t)INT32_MAX)
+    return refuse(err, "rjp_image_stats: more than 2^31 - 1 workgroups");
+  return RJP_OK;
+}
+
+// What rjp_label_regions takes, in the order it refuses: NULL pointers, the sizes, n_mask, the
+// connectivity.  (`d_area` may be NULL.)
+inline int check_label_regions(const uint8_t* d_mask_in, int n_mask, int n_maps, int nx, int nz,
+                               int connectivity, const int32_t* d_label, const int32_t* d_nreg,
+                               std::string& err) {
+  if (!d_mask_in || !d_label || !d_nreg) return refuse(err, "rjp_label_regions: NULL mask or outputs");
+  if (int r = check_region_sizes("rjp_label_regions", n_maps, nx, nz, err)) return r;
+  if (n_mask != 1 && n_mask != n_maps)
+    return refuse(err, "rjp_label_regions: n_mask must be 1 or n_maps");
+  if (connectivity != 1 && connectivity != 2)
+    return refuse(err, "rjp_label_regions: connectivity must be 1 (four neighbours) or 2 (eight)");
+  return RJP_OK;
+}
+
+// What rjp_mask_grow takes, in the order it refuses: NULL pointers, the sizes, n_mask, the
+// connectivity.  (`n_iter` is any integer: 0 nothing, > 0 that many steps, < 0 until stable.)
+inline int check_mask_grow(const uint8_t* d_seed, const uint8_t* d_con, int n_mask, int n_maps,
+                           int nx, int nz, int connectivity, std::string& err) {
+  if (!d_seed || !d_con) return refuse(err, "rjp_mask_grow: NULL seed or constraint");
+  if (int r = check_region_sizes("rjp_mask_grow", n_maps, nx, nz, err)) return r;
+  if (n_mask != 1 && n_mask != n_maps)
+    return refuse(err, "rjp_mask_grow: n_mask must be 1 or n_maps");
+  if (connectivity != 1 && connectivity != 2)
+    return refuse(err, "rjp_mask_grow: connectivity must be 1 (four neighbours) or 2 (eight)");
+  return RJP_OK;
+}
+
 }  // namespace rjp_args

@@ -466,6 +466,27 @@ hipError_t normal_eq_launch(const double* data, const double* model, const doubl
                             int n_sel, const double* w, int64_t w_rows, double* out, int64_t* count,
                             void* work, hipStream_t st);
 
+// ---- regions.hip: robust image statistics, connected components, constrained growth (K25) -------
+// n_maps x tiles of 2048 consecutive pixels: the grid of the statistics' tile launches
+int64_t image_stats_workgroups(int n_maps, int nx, int nz);
+// n_maps x tiles of 16 x 64 pixels: the grid of the labelling's and the growth's tile launches
+int64_t regions_workgroups(int n_maps, int nx, int nz);
+size_t image_stats_workspace_bytes(int n_maps, int nx, int nz);
+size_t label_regions_workspace_bytes(int n_maps, int nx, int nz);
+size_t mask_grow_workspace_bytes(int n_maps, int nx, int nz);
+// `mask` may be nullptr; 26 launches, no host synchronisation
+hipError_t image_stats_launch(const double* img, int n_maps, int nx, int nz, const uint8_t* mask,
+                              int n_mask, int sense, double* stats, void* work, hipStream_t st);
+// `area` may be nullptr; up to three memsets and four launches, no host synchronisation.  The first
+// int32 of `work` is the cap flag (0 = no loop ran into its cap)
+hipError_t label_regions_launch(const uint8_t* mask, int n_mask, int n_maps, int nx, int nz,
+                                int conn, int32_t* label, int32_t* area, int32_t* nreg, void* work,
+                                hipStream_t st);
+// n_iter > 0: ceil(n_iter / RJP_GROW_HALO) launches; < 0: the labelling's launches and two more; the
+// cap flag as above
+hipError_t mask_grow_launch(uint8_t* seed, const uint8_t* con, int n_mask, int n_maps, int nx,
+                            int nz, int n_iter, int conn, void* work, hipStream_t st);
+
 // ---- uv_weight.hip: uniform and Briggs imaging weights from the (u, v) density (K15) -------------
 struct UvWeightTiling {
   int64_t cells;                // (2 (nx / 2) + 1)(2 (nz / 2) + 1), per map (INT64_MAX: beyond int64)

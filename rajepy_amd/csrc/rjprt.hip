@@ -1569,6 +1569,79 @@ int64_t rjp_normal_eq(rjp_ctx* ctx, const double* d_data, const double* d_model,
   return rjp::normal_eq_tiles(n_rows, n_vis);
 }
 
+static bool region_sizes_ok(int32_t n_maps, int32_t nx, int32_t nz) {
+  std::string m;
+  return rjp_args::check_region_sizes("", n_maps, nx, nz, m) == RJP_OK;
+}
+
+size_t rjp_image_stats_workspace(int32_t n_maps, int32_t nx, int32_t nz) {
+  return region_sizes_ok(n_maps, nx, nz) ? rjp::image_stats_workspace_bytes(n_maps, nx, nz) : 0;
+}
+
+int64_t rjp_image_stats(rjp_ctx* ctx, const double* d_img, int32_t n_maps, int32_t nx, int32_t nz,
+                        const uint8_t* d_mask, int32_t n_mask, int32_t sense, double* d_stats,
+                        void* d_work, size_t work_bytes, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_image_stats(d_img, n_maps, nx, nz, d_mask, n_mask, d_stats, m);
+      }))
+    return r;
+  if (!d_work || work_bytes < rjp::image_stats_workspace_bytes(n_maps, nx, nz))
+    return fail(ctx, RJP_ERR_WORKSPACE,
+                "rjp_image_stats: workspace smaller than rjp_image_stats_workspace()");
+  if ((uintptr_t)d_work & 7)
+    return fail(ctx, RJP_ERR_WORKSPACE, "rjp_image_stats: d_work is not 8-byte aligned");
+  RJP_HIP(ctx, rjp::image_stats_launch(d_img, n_maps, nx, nz, d_mask, d_mask ? n_mask : 1, sense,
+                                       d_stats, d_work, (hipStream_t)stream));
+  return rjp::image_stats_workgroups(n_maps, nx, nz);
+}
+
+size_t rjp_label_regions_workspace(int32_t n_maps, int32_t nx, int32_t nz) {
+  return region_sizes_ok(n_maps, nx, nz) ? rjp::label_regions_workspace_bytes(n_maps, nx, nz) : 0;
+}
+
+int64_t rjp_label_regions(rjp_ctx* ctx, const uint8_t* d_mask_in, int32_t n_mask, int32_t n_maps,
+                          int32_t nx, int32_t nz, int32_t connectivity, int32_t* d_label,
+                          int32_t* d_area, int32_t* d_nreg, void* d_work, size_t work_bytes,
+                          void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_label_regions(d_mask_in, n_mask, n_maps, nx, nz, connectivity,
+                                             d_label, d_nreg, m);
+      }))
+    return r;
+  if (!d_work || work_bytes < rjp::label_regions_workspace_bytes(n_maps, nx, nz))
+    return fail(ctx, RJP_ERR_WORKSPACE,
+                "rjp_label_regions: workspace smaller than rjp_label_regions_workspace()");
+  if ((uintptr_t)d_work & 7)
+    return fail(ctx, RJP_ERR_WORKSPACE, "rjp_label_regions: d_work is not 8-byte aligned");
+  RJP_HIP(ctx, rjp::label_regions_launch(d_mask_in, n_mask, n_maps, nx, nz, connectivity, d_label,
+                                         d_area, d_nreg, d_work, (hipStream_t)stream));
+  return rjp::regions_workgroups(n_maps, nx, nz);
+}
+
+size_t rjp_mask_grow_workspace(int32_t n_maps, int32_t nx, int32_t nz) {
+  return region_sizes_ok(n_maps, nx, nz) ? rjp::mask_grow_workspace_bytes(n_maps, nx, nz) : 0;
+}
+
+int64_t rjp_mask_grow(rjp_ctx* ctx, uint8_t* d_seed, const uint8_t* d_con, int32_t n_mask,
+                      int32_t n_maps, int32_t nx, int32_t nz, int32_t n_iter, int32_t connectivity,
+                      void* d_work, size_t work_bytes, void* stream) {
+  if (int r = bind(ctx)) return r;
+  if (int r = checked(ctx, [&](std::string& m) {
+        return rjp_args::check_mask_grow(d_seed, d_con, n_mask, n_maps, nx, nz, connectivity, m);
+      }))
+    return r;
+  if (!d_work || work_bytes < rjp::mask_grow_workspace_bytes(n_maps, nx, nz))
+    return fail(ctx, RJP_ERR_WORKSPACE,
+                "rjp_mask_grow: workspace smaller than rjp_mask_grow_workspace()");
+  if ((uintptr_t)d_work & 7)
+    return fail(ctx, RJP_ERR_WORKSPACE, "rjp_mask_grow: d_work is not 8-byte aligned");
+  RJP_HIP(ctx, rjp::mask_grow_launch(d_seed, d_con, n_mask, n_maps, nx, nz, n_iter, connectivity,
+                                     d_work, (hipStream_t)stream));
+  return rjp::regions_workgroups(n_maps, nx, nz);
+}
+
 size_t rjp_uv_weights_workspace(int32_t n_maps, int32_t nx, int32_t nz, int32_t n_vis) {
   if (n_maps <= 0 || nx <= 0 || nz <= 0 || n_vis <= 0) return 0;
   return rjp::uv_weights_workspace_bytes(n_maps, nx, nz, n_vis);

@@ -20,6 +20,8 @@ from .imaging import (SIDEREAL_DAY_S, AntennaConfig, Geodetic, antenna_config_pa
                       taylor_weights, thermal_sigma, vis_scales)
 from .imaging import (UVFIT_MAX_COMP, uvfit_components, uvfit_results, uvfit_start,  # noqa: F401
                       uvfit_theta, uvfit_theta_from_imfit)
+from .imaging import (AUTOMASK_DEFAULTS, automask_options, automask_step,  # noqa: F401
+                      image_stats_results)
 from .spectra import (SPECFIT_MAX_CHAN, SPECFIT_MAX_COMP, VOIGTFIT_MAX_COMP,  # noqa: F401
                       channel_widths, specfit_results, specfit_start, velocity_axis, voigt_results,
                       voigt_start)
@@ -2016,6 +2018,98 @@ class RTEngine:
             sel.ctypes.data_as(C.POINTER(C.c_int32)), P, _ptr(dw), w_rows, out.data_ptr(),
             count.data_ptr(), work.data_ptr(), work.numel())
         return out[0], out[1:1 + P], out[1 + P:], count[0]
+
+    # -- K25 -------------------------------------------------------------------------------------
+    def _mask_stack(self, who, name, mask, npix, M=None):
+        """`mask` (device tensor, any dtype, non-zero = set) -> (uint8 tensor [n, npix], n); with
+        `M`, n must be 1 or M."""
+        torch = _torch()
+        if not (isinstance(mask, torch.Tensor) and mask.device == self.device and
+                mask.numel() >= npix and mask.numel() % npix == 0):
+            raise ValueError("%s: `%s` must be a tensor of a whole number (>= 1) of nx * nz masks "
+                             "on %s" % (who, name, self.device))
+        if mask.dtype != torch.uint8:
+            mask = (mask != 0).to(torch.uint8)
+        mask = mask.reshape(-1, npix).contiguous()
+        n = int(mask.shape[0])
+        if M is not None and n not in (1, M):
+            raise ValueError("%s: `%s` must hold one mask or one per map (%d)" % (who, name, M))
+        return mask, n
+
+    def _check_cap_flag(self, who, work):
+        """The first int32 of a K25 workspace: non-zero when a loop of the labelling ran into its
+        cap (include/rjprt.h).  One 4-byte read, which waits for the call."""
+        if int(work[:4].view(_torch().int32).item()) != 0:
+            raise _lib.RjprtError("%s: a union-find loop ran into its iteration cap (the labels "
+                                  "are not valid)" % who)
+
+    def image_stats(self, img, nx, nz, mask=None, inside=True):
+        """Robust statistics of a stack of images (rjp_image_stats), nothing going to the host ->
+        float64 device tensor [M, 8]: count, n_nonfinite, min, max, median, mad, sum, sumsq per
+        map, over the finite pixels that `mask` (None, one [nx * nz] or one per map; non-zero =
+        set) selects -- inside it, or with `inside=False` outside it.  The median is the LOWER
+        median (an element of the input), the MAD the same rank of |x - median|; an exact radix
+        select, the same bits on every call (`image_stats_results` names the numbers).  The
+        workgroup count is kept in `last_image_stats_workgroups`."""
+        torch = _torch()
+        nx, nz = int(nx), int(nz)
+        if nx < 1 or nz < 1:
+            raise ValueError("image_stats: nx and nz must be positive")
+        if not (isinstance(img, torch.Tensor) and img.numel() >= nx * nz and
+                img.numel() % (nx * nz) == 0):
+            raise ValueError("image_stats: `img` must hold a whole number (>= 1) of nx * nz images")
+        M = img.numel() // (nx * nz)
+        self._stack_f64("image_stats", "img", img, M * nx * nz)
+        dmask, n_mask = (None, 1) if mask is None else \
+            self._mask_stack("image_stats", "mask", mask, nx * nz, M)
+        stats = self._f64(M, 8)
+        work = self._workspace(max(1, self.lib.rjp_image_stats_workspace(M, nx, nz)))
+        self.last_image_stats_workgroups = self._call_tiles(
+            "rjp_image_stats", img.data_ptr(), M, nx, nz, _ptr(dmask), n_mask, 1 if inside else 0,
+            stats.data_ptr(), work.data_ptr(), work.numel())
+        return stats
+
+    def label_regions(self, mask, nx, nz, connectivity=1):
+        """Connected components of a stack of masks (rjp_label_regions) -> (label[M, nx * nz] int32,
+        area[M, nx * nz] int32, nreg[M] int32) device tensors: 0 on background, otherwise 1 + the
+        smallest pixel index of the pixel's region; the region's pixel count on each of its pixels;
+        the number of regions.  `mask`: device tensor of M * nx * nz values, non-zero = set;
+        `connectivity` 1 (four neighbours) or 2 (eight).  Reads the workspace's cap flag (4 bytes)
+        and raises if a loop ran into its cap."""
+        torch = _torch()
+        nx, nz = int(nx), int(nz)
+        if nx < 1 or nz < 1:
+            raise ValueError("label_regions: nx and nz must be positive")
+        dmask, M = self._mask_stack("label_regions", "mask", mask, nx * nz)
+        label = torch.empty(M, nx * nz, dtype=torch.int32, device=self.device)
+        area = torch.empty(M, nx * nz, dtype=torch.int32, device=self.device)
+        nreg = torch.empty(M, dtype=torch.int32, device=self.device)
+        work = self._workspace(max(1, self.lib.rjp_label_regions_workspace(M, nx, nz)))
+        self.last_label_regions_workgroups = self._call_tiles(
+            "rjp_label_regions", dmask.data_ptr(), M, M, nx, nz, int(connectivity),
+            label.data_ptr(), area.data_ptr(), nreg.data_ptr(), work.data_ptr(), work.numel())
+        self._check_cap_flag("label_regions", work)
+        return label, area, nreg
+
+    def mask_grow(self, seed, constraint, nx, nz, n_iter, connectivity=1):
+        """Geodesic dilation of a stack of masks (rjp_mask_grow) -> uint8 device tensor [M, nx * nz]
+        (a new tensor; `seed` is not changed): `n_iter` steps of seed | (dilate(seed) & constraint),
+        scipy.ndimage.binary_dilation(seed, structure, iterations=n_iter, mask=constraint); a seed
+        pixel outside the constraint stays.  `n_iter` 0: the seed itself; < 0: until stable.
+        `seed`: M * nx * nz values; `constraint`: one mask or one per map; non-zero = set."""
+        nx, nz = int(nx), int(nz)
+        if nx < 1 or nz < 1:
+            raise ValueError("mask_grow: nx and nz must be positive")
+        dseed, M = self._mask_stack("mask_grow", "seed", seed, nx * nz)
+        dcon, n_con = self._mask_stack("mask_grow", "constraint", constraint, nx * nz, M)
+        out = (dseed != 0).to(dseed.dtype)
+        work = self._workspace(max(1, self.lib.rjp_mask_grow_workspace(M, nx, nz)))
+        self.last_mask_grow_workgroups = self._call_tiles(
+            "rjp_mask_grow", out.data_ptr(), dcon.data_ptr(), n_con, M, nx, nz, int(n_iter),
+            int(connectivity), work.data_ptr(), work.numel())
+        if int(n_iter) < 0:
+            self._check_cap_flag("mask_grow", work)
+        return out
 
     # -- K15 -------------------------------------------------------------------------------------
     UV_WEIGHT_MODES ={"uniform": 1, "briggs": 2}

@@ -605,6 +605,133 @@ def uvfit_results(theta, cov, chi2, nvis, free, cell_rad, status=None, scale_err
     return out
 
 
+# -- K25: robust statistics and the automatic clean mask ----------------------------------------------
+MAD_TO_SIGMA = 1.4826            # sigma of a normal distribution = 1.4826 x its MAD
+# tclean's usemask = 'auto-multithresh' defaults, where the step exists here; `nsigma` is the stop of
+# a minor run at nsigma x the update's robust sigma (0: off)
+AUTOMASK_DEFAULTS = dict(sidelobe_threshold=3.0, noise_threshold=5.0, low_noise_threshold=1.5,
+                         min_beam_frac=0.3, grow_iterations=75, connectivity=1, nsigma=0.0)
+
+
+def automask_options(automask):
+    """None (or False) -> None; True -> the defaults (`AUTOMASK_DEFAULTS`); a dict -> the defaults
+    with its entries, validated: an unknown key, a threshold, fraction or `nsigma` that is negative
+    or not finite, a `grow_iterations` that is no integer (< 0 = until stable) or a `connectivity`
+    other than 1 or 2 raise ValueError."""
+    if automask is None or automask is False:
+        return None
+    if automask is True:
+        automask = {}
+    if not isinstance(automask, dict):
+        raise ValueError("automask: None, True or a dict of options (%s)"
+                         % ", ".join(sorted(AUTOMASK_DEFAULTS)))
+    unknown = sorted(set(automask) - set(AUTOMASK_DEFAULTS))
+    if unknown:
+        raise ValueError("automask: unknown option(s) %s (known: %s)"
+                         % (", ".join(map(str, unknown)), ", ".join(sorted(AUTOMASK_DEFAULTS))))
+    out = dict(AUTOMASK_DEFAULTS)
+    out.update(automask)
+    for k in ("sidelobe_threshold", "noise_threshold", "low_noise_threshold", "min_beam_frac", "nsigma"):
+        v = out[k]
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or \
+                not np.isfinite(v) or v < 0:
+            raise ValueError("automask: `%s` must be a finite number >= 0" % k)
+        out[k] = float(v)
+    g = out["grow_iterations"]
+    if isinstance(g, bool) or not isinstance(g, (int, np.integer)):
+        raise ValueError("automask: `grow_iterations` must be an integer (< 0: until stable)")
+    out["grow_iterations"] = int(g)
+    if isinstance(out["connectivity"], bool) or out["connectivity"] not in (1, 2):
+        raise ValueError("automask: `connectivity` must be 1 (four neighbours) or 2 (eight)")
+    out["connectivity"] = int(out["connectivity"])
+    return out
+
+
+def image_stats_results(stats):
+    """`RTEngine.image_stats`' [M, 8] (tensor or array) -> one dict per map, named as imstat names
+    them: `npts`, `min`, `max`, `median` (the LOWER median), `medabsdevmed`, `sigma_robust`
+    (1.4826 x MAD), `sum`, `mean`, `rms` (sqrt(sumsq / npts)) and `sigma` (the standard deviation
+    from sum and sumsq, npts - 1 in the denominator; 0 for one point).  No point: NaN but for npts,
+    sum = 0."""
+    st = stats.cpu().numpy() if hasattr(stats, "cpu") else np.asarray(stats, dtype=np.float64)
+    out = []
+    for count, _, lo, hi, med, mad, s, q in st.reshape(-1, 8):
+        n = int(count)
+        d = dict(npts=n, min=float(lo), max=float(hi), median=float(med), medabsdevmed=float(mad),
+                 sigma_robust=MAD_TO_SIGMA * float(mad), sum=float(s), mean=np.nan, rms=np.nan,
+                 sigma=np.nan)
+        if n:
+            d["mean"] = float(s) / n
+            d["rms"] = float(np.sqrt(float(q) / n))
+            d["sigma"] = float(np.sqrt(max(0., (float(q) - float(s) * float(s) / n) / (n - 1)))) \
+                if n > 1 else 0.
+        out.append(d)
+    return out
+
+
+def automask_step(eng, R, prev, user_mask, sidelobe, abc, opts, shape=None):
+    """One update of the automatic clean masks of a stack of residuals -> (masks uint8 device tensor
+    [M, ni nj], info: one dict per map).  `R`: float64 device tensor [M, ni, nj], or [M, ni nj] with
+    `shape` = (ni, nj); `prev`: the masks so far, [M, ni nj] on the device (None: empty);
+    `user_mask`: None or a device tensor [ni nj] that bounds the automatic mask; `sidelobe` [M]:
+    the beams' sidelobe levels; `abc` [M][3]: the clean beams' quadratic forms; `opts`: what
+    `automask_options` returns.  Four engine calls (`image_stats` twice, `label_regions`,
+    `mask_grow`) and torch comparisons; the formulas are evaluated in float64 on the host, in this
+    order, from the numbers the device returned:
+      noise   median and MAD of the finite pixels OUTSIDE prev[m] (none: of all finite pixels);
+              sigma = 1.4826 * mad;  peak = the largest finite R[m], signed
+      t_noise = median + noise_threshold * sigma;  t_side = sidelobe_threshold * sidelobe[m] * peak
+      T = max(t_side, t_noise);  T_low = min(T, median + low_noise_threshold * sigma)
+      seed = finite & (R > T) & user_mask;  constraint = finite & (R > T_low) & user_mask
+      min_pixels = max(1, ceil(min_beam_frac * Omega_b)), Omega_b = pi / sqrt(A C - B^2) pixels;
+              a region of the seed (`connectivity`) stays when its area >= min_pixels
+      grown = `mask_grow`(kept, constraint, grow_iterations);  mask = prev | grown
+    info[m]: `median`, `sigma`, `peak`, `T`, `T_low`, `n_regions`, `n_kept`, `n_seed`, `n_mask`."""
+    import torch
+    if shape is None:
+        if R.dim() != 3:
+            raise ValueError("automask_step: `R` must be [M, ni, nj], or [M, ni nj] with `shape`")
+        shape = (int(R.shape[1]), int(R.shape[2]))
+    ni, nj = int(shape[0]), int(shape[1])
+    R = R.reshape(-1, ni * nj)
+    M = int(R.shape[0])
+    if prev is None:
+        prev = torch.zeros(M, ni * nj, dtype=torch.uint8, device=R.device)
+    prev = (prev.reshape(M, ni * nj) != 0)
+    st_all = eng.image_stats(R, ni, nj).cpu().numpy()
+    st_out = eng.image_stats(R, ni, nj, mask=prev.to(torch.uint8), inside=False).cpu().numpy()
+    T, T_low, noise, min_pix = np.zeros(M), np.zeros(M), [], np.zeros(M, dtype=np.int64)
+    for m in range(M):
+        st = st_out[m] if st_out[m, 0] > 0 else st_all[m]
+        median, sigma, peak = float(st[4]), MAD_TO_SIGMA * float(st[5]), float(st_all[m, 3])
+        t_noise = median + opts["noise_threshold"] * sigma
+        t_side = opts["sidelobe_threshold"] * float(sidelobe[m]) * peak
+        T[m] = max(t_side, t_noise)
+        T_low[m] = min(T[m], median + opts["low_noise_threshold"] * sigma)
+        A, B, C = (float(v) for v in abc[m])
+        omega = np.pi / np.sqrt(A * C - B * B)
+        min_pix[m] = max(1, int(np.ceil(opts["min_beam_frac"] * omega)))
+        noise.append((median, sigma, peak))
+    ok = torch.isfinite(R)
+    if user_mask is not None:
+        ok = ok & (user_mask.reshape(1, ni * nj) != 0)
+    dev = R.device
+    seed = ok & (R > torch.from_numpy(T).to(dev)[:, None])
+    con = ok & (R > torch.from_numpy(T_low).to(dev)[:, None])
+    label, area, nreg = eng.label_regions(seed, ni, nj, opts["connectivity"])
+    big = area >= torch.from_numpy(min_pix).to(device=dev, dtype=torch.int32)[:, None]
+    kept = seed & big
+    root = label == torch.arange(1, ni * nj + 1, dtype=torch.int32, device=dev)[None, :]
+    grown = eng.mask_grow(kept, con, ni, nj, opts["grow_iterations"], opts["connectivity"])
+    masks = (prev | (grown != 0)).to(torch.uint8)
+    counts = torch.stack([nreg.to(torch.int64), (root & big).sum(dim=1), seed.sum(dim=1),
+                          masks.sum(dim=1, dtype=torch.int64)], dim=1).cpu().numpy()
+    info = [dict(median=noise[m][0], sigma=noise[m][1], peak=noise[m][2], T=float(T[m]),
+                 T_low=float(T_low[m]), n_regions=int(counts[m, 0]), n_kept=int(counts[m, 1]),
+                 n_seed=int(counts[m, 2]), n_mask=int(counts[m, 3])) for m in range(M)]
+    return masks, info
+
+
 # -- result types -----------------------------------------------------------------------------------
 # what `JetModel.clean_image_ff` / `clean_image_rrl` return
 class CleanResult(collections.namedtuple(
@@ -622,27 +749,35 @@ class CleanResult(collections.namedtuple(
     `residual_tt`, `model_tt` (each (n_t, ni, nj): the restored Taylor images, the raw Taylor
     residual planes and the delta models), `alpha` (tt1 / tt0 where tt0 > `alpha_cut_jy`, NaN
     elsewhere), `beta` (tt2 / tt0 - alpha (alpha - 1) / 2; None below three terms),
-    `alpha_cut_jy`, `reffreq_hz`, `hessian` and `hinv` (n_t, n_t)."""
+    `alpha_cut_jy`, `reffreq_hz`, `hessian` and `hinv` (n_t, n_t).
+    `automask`, handled the same way: None, or with the `automask` keyword one dict per map --
+    `mask` (bool (ni, nj): the final automatic mask) and `runs` (one dict per update, what
+    `automask_step` reports: `median`, `sigma`, `peak`, `T`, `T_low`, `n_regions`, `n_kept`,
+    `n_seed`, `n_mask`; and `start`, the length of the map's component list at that update)."""
 
-    def __new__(cls, *args, imfit=None, major=None, taylor=None, **kw):
+    def __new__(cls, *args, imfit=None, major=None, taylor=None, automask=None, **kw):
         self = super().__new__(cls, *args, **kw)
         self.imfit = imfit
         self.major = major
         self.taylor = taylor
+        self.automask = automask
         return self
 
     imfit = None
     major = None
     taylor = None
+    automask = None
 
     def _replace(self, **kw):
         imfit = kw.pop("imfit", self.imfit)
         major = kw.pop("major", self.major)
         taylor = kw.pop("taylor", self.taylor)
+        automask = kw.pop("automask", self.automask)
         out = super()._replace(**kw)
         out.imfit = imfit
         out.major = major
         out.taylor = taylor
+        out.automask = automask
         return out
 
 
@@ -1034,7 +1169,8 @@ class Imager:
 
     def _clean_images(self, V, u_d, v_d, freqs, weights, shape, cell_as, mfs, niter, gain,
                       threshold_jy, mask, beam, psf_shape, imfit=None, weighting=None, robust=0.5,
-                      scales=None, scale_bias=None, nterms=1, reffreq_hz=None, alpha_cut_jy=None,
+                      automask=None, scales=None, scale_bias=None, nterms=1, reffreq_hz=None,
+                      alpha_cut_jy=None,
                       major_cycles=0, cyclefactor=1.5, cycleniter=None,
                       min_psf_fraction=0.05, max_psf_fraction=0.8):
         """Hogbom CLEAN of the dirty images of `V` (see `JetModel.clean_image_ff`), in chunks of
@@ -1055,12 +1191,21 @@ class Imager:
         `nterms` > 1 (with `mfs`; `reffreq_hz`, `alpha_cut_jy`): multi-term MFS CLEAN, the one
         chunk through `_mtmfs_chunk` -- n_t Taylor dirty images and 2 n_t - 1 spectral beams with
         the chunk's weights, `RTEngine.mtmfs` -- and `CleanResult.taylor`; 1 is the path as it
-        was."""
+        was.
+        `automask` (`automask_options`; not with `scales` or `nterms` > 1): every map is cleaned
+        under a mask of its own that `automask_step` makes from its residual, inside `mask` -- once
+        from the dirty image without major cycles, at the top of every run with them (`_major_chunk`
+        with `am`) -- one `RTEngine.clean` call per map (`_clean_per_map`), and
+        `CleanResult.automask`; None makes no new call: the path as it was."""
         import torch
         eng = self.engine
         mj = _major_options(major_cycles, cyclefactor, cycleniter, min_psf_fraction,
                             max_psf_fraction)
         ty = _taylor_options(nterms, reffreq_hz, alpha_cut_jy, freqs, mfs, scales, mj)
+        am = automask_options(automask)
+        if am is not None and (scales is not None or ty is not None):
+            raise ValueError("clean: `automask` goes with Hogbom CLEAN only, not with `scales` or "
+                             "`nterms` > 1")
         ni, nj, cell = self._image_grid(shape, cell_as)
         pi_, pj = (2 * ni - 1, 2 * nj - 1) if psf_shape is None else (int(psf_shape[0]),
                                                                       int(psf_shape[1]))
@@ -1080,7 +1225,8 @@ class Imager:
         res = CleanResult(image=np.zeros((n_out, ni, nj)), residual=np.zeros((n_out, ni, nj)),
                           model=np.zeros((n_out, ni, nj)), components=[], beam=[],
                           peak_residual=np.zeros(n_out), imfit=None if fit_opts is None else [],
-                          major=None if mj is None else [], taylor=None if ty is None else [])
+                          major=None if mj is None else [], taylor=None if ty is None else [],
+                          automask=None if am is None else [])
         step = F if mfs else max(1, self.stack_bytes // ((ni * nj * 3 + pi_ * pj) * 8))
         ms = None
         if scales is not None:
@@ -1150,8 +1296,31 @@ class Imager:
             if mj is not None:
                 dirty, model, image, cpix, cscale, cflux, ncomp, peak, info = self._major_chunk(
                     V[sl], u_d, v_d, freqs[sl], weights, ni, nj, cell, cell_as, mfs, iw, dirty,
-                    psf if not grow else big, psf, pi_, pj, ms, abc, mk, niter, gain, thr_c, mj)
+                    psf if not grow else big, psf, pi_, pj, ms, abc, mk, niter, gain, thr_c, mj,
+                    # (named only when set: without it the call is, argument for argument, the one
+                    # it was, also for a stand-in with the earlier parameter list)
+                    **({} if am is None else dict(am=am)))
+                if am is not None:
+                    res.automask.extend(i.pop("automask") for i in info)
                 res.major.extend(info)
+            elif am is not None:
+                # one mask per map from its dirty image, then one minor run
+                side = self._sidelobe_levels(psf, abc, M, pi_, pj)
+                um = torch.from_numpy(mk).to(eng.device).reshape(-1) if mk is not None else None
+                masks, upd = automask_step(eng, dirty, None, um, side, abc, am, shape=(ni, nj))
+                t = np.array(np.broadcast_to(np.asarray(thr_c, dtype=np.float64).reshape(-1), (M,)))
+                if am["nsigma"] > 0.:
+                    t = np.maximum(t, am["nsigma"] * np.array([u["sigma"] for u in upd]))
+                model = torch.zeros_like(dirty)
+                live = np.array([u["n_mask"] > 0 for u in upd])
+                cpix, cflux, ncomp = self._clean_per_map(dirty, psf, ni, nj, pi_, pj, niter, gain, t,
+                                                         masks, live, model=model)
+                image = eng.restore(cpix, cflux, ncomp, abc, ni, nj, add=dirty)
+                inside = (masks != 0) & torch.isfinite(dirty)
+                peak = torch.where(inside, dirty.abs(), torch.zeros_like(dirty)).amax(dim=1)
+                hm = (masks != 0).cpu().numpy().reshape(M, ni, nj)
+                res.automask.extend(dict(mask=hm[m].copy(), runs=[dict(upd[m], start=0)])
+                                    for m in range(M))
             elif ty is not None:
                 planes = self._taylor_stack(V[sl], dirty, ty["tw"][:ty["n_t"]], u_d, v_d, freqs[sl],
                                             weights, (ni, nj), cell_as, iw)
@@ -1247,8 +1416,21 @@ class Imager:
         return (planes[:, 0].contiguous(), model[:, 0].contiguous(), tt[0], cpix, ccoef, ncomp, peak,
                 info)
 
+    def _sidelobe_levels(self, psf, abc, M, pi_, pj):
+        """sidelobe[m] of `_major_chunk`'s docstring for the beam windows `psf` [M, pi_ * pj] and
+        the clean beams' forms `abc` -> host array [M]."""
+        import torch
+        eng = self.engine
+        q = torch.from_numpy(np.asarray(abc, dtype=np.float64).reshape(M, 3)).to(eng.device)
+        dx = (torch.arange(pi_, dtype=torch.float64, device=eng.device) - (pi_ - 1) // 2)[None, :, None]
+        dz = (torch.arange(pj, dtype=torch.float64, device=eng.device) - (pj - 1) // 2)[None, None, :]
+        form = q[:, 0, None, None] * dx * dx + 2. * q[:, 1, None, None] * dx * dz + \
+            q[:, 2, None, None] * dz * dz
+        win = psf.reshape(M, pi_, pj).abs()
+        return torch.where(form >= _FOUR_LN2, win, torch.zeros_like(win)).amax(dim=(1, 2)).cpu().numpy()
+
     def _major_chunk(self, V, u_d, v_d, freqs, weights, ni, nj, cell, cell_as, mfs, iw, dirty, beam,
-                     psf, pi_, pj, ms, abc, mk, niter, gain, thr, mj):
+                     psf, pi_, pj, ms, abc, mk, niter, gain, thr, mj, am=None):
         """CLEAN with major cycles of one chunk: N = mj["major_cycles"] minor runs at most, the
         residual recomputed from the visibilities after every one -> (residual, model, image
         [M, ni * nj], cpix, cscale (None without scales), cflux [M, niter], ncomp, peak_residual
@@ -1280,14 +1462,7 @@ class Imager:
             V0 = V.reshape(1, F * K).contiguous()
         else:
             cu, cv, V0 = u_d, v_d, V.contiguous()
-        q = torch.from_numpy(np.asarray(abc, dtype=np.float64).reshape(M, 3)).to(eng.device)
-        dx = (torch.arange(pi_, dtype=torch.float64, device=eng.device) - (pi_ - 1) // 2)[None, :, None]
-        dz = (torch.arange(pj, dtype=torch.float64, device=eng.device) - (pj - 1) // 2)[None, None, :]
-        form = q[:, 0, None, None] * dx * dx + 2. * q[:, 1, None, None] * dx * dz + \
-            q[:, 2, None, None] * dz * dz
-        win = psf.reshape(M, pi_, pj).abs()
-        side = torch.where(form >= _FOUR_LN2, win, torch.zeros_like(win)).amax(dim=(1, 2)).cpu().numpy()
-        del form, win
+        side = self._sidelobe_levels(psf, abc, M, pi_, pj)
         n_s, G, cscale_all = 1, None, None
         if ms is None:
             dmask = torch.from_numpy(mk).to(eng.device).reshape(1, -1) if mk is not None else None
@@ -1319,7 +1494,18 @@ class Imager:
         def count():
             return torch.from_numpy(n_all.astype(np.int32)).to(eng.device)
 
+        am_runs, am_sigma, um = [[] for _ in range(M)], np.zeros(M), None
+        if am is not None:
+            # the automatic masks, one per map, inside the user's; empty before the first update
+            um = dmask
+            dmask = torch.zeros(M, ni * nj, dtype=torch.bool, device=eng.device)
         for r in range(1, N + 1):
+            if am is not None:
+                masks, upd = automask_step(eng, R, dmask, um, side, abc, am, shape=(ni, nj))
+                dmask = masks != 0
+                for m in range(M):
+                    am_runs[m].append(dict(upd[m], start=int(n_all[m])))
+                    am_sigma[m] = upd[m]["sigma"]
             if ms is None:
                 planes = R.clone()
                 peak = masked(planes).cpu().numpy()
@@ -1329,12 +1515,20 @@ class Imager:
                 peak = torch.stack([masked(planes[:, l] * wd[:, l, None]) for l in range(n_s)],
                                    dim=1).amax(dim=1).cpu().numpy()
             active = (left > 0) & (peak > thr)
+            if am is not None:
+                # (a map whose mask is empty is finished for this run)
+                active &= np.array([u["n_mask"] > 0 for u in upd])
             if not active.any():
                 break
             t = thr if r == N else np.maximum(thr, frac * peak)
+            if am is not None and am["nsigma"] > 0.:
+                t = np.maximum(t, am["nsigma"] * am_sigma)
             t = np.where(active, t, np.finfo(np.float64).max)
             n_r = int(min(mj["cycleniter"] or niter, left.max()))
-            if ms is None:
+            if am is not None:
+                cp, cf, nc = self._clean_per_map(planes, psf, ni, nj, pi_, pj, n_r, gain, t, dmask,
+                                                 active)
+            elif ms is None:
                 cp, cf, nc, _ = eng.clean(planes, ni, nj, psf, pi_, pj, n_r, gain, t, mask=mk)
             else:
                 cp, cs, cf, nc, _ = eng.msclean(planes, n_s, ni, nj, xpsf, pi_, pj, weight, n_r,
@@ -1371,7 +1565,39 @@ class Imager:
         hv = Vres.cpu().numpy()
         info = [dict(runs=runs[m], sidelobe=float(side[m]), vis_residual=hv[m].copy())
                 for m in range(M)]
+        if am is not None:
+            hm = dmask.cpu().numpy().reshape(M, ni, nj)
+            for m in range(M):
+                # (`_clean_images` moves this entry to `CleanResult.automask`)
+                info[m]["automask"] = dict(mask=hm[m].copy(), runs=am_runs[m])
         return R, model, image, cpix_all, cscale_all, cflux_all, ncomp, peak, info
+
+    def _clean_per_map(self, planes, psf, ni, nj, pi_, pj, n_iter, gain, thr, masks, active,
+                       model=None):
+        """`RTEngine.clean` of a stack whose maps have masks of their own: rjp_clean takes one mask
+        for all maps, so this is ONE call per map of `active`, in place on that map's row of
+        `planes` (and `model`), with its row of `masks` [M, ni nj] and its threshold -> (cpix
+        [M, n_iter] int32, cflux [M, n_iter], ncomp [M] int32) on the device, zero for the maps
+        that did not run.  M times as many launches as one call on the stack; with `mfs` M = 1."""
+        import torch
+        eng = self.engine
+        M = int(planes.shape[0])
+        cpix = torch.zeros(M, n_iter, dtype=torch.int32, device=eng.device)
+        cflux = torch.zeros(M, n_iter, dtype=torch.float64, device=eng.device)
+        ncomp = torch.zeros(M, dtype=torch.int32, device=eng.device)
+        slot = torch.arange(n_iter, device=eng.device)
+        for m in np.nonzero(active)[0]:
+            m = int(m)
+            cp, cf, nc, _ = eng.clean(planes[m:m + 1], ni, nj, psf[m:m + 1], pi_, pj, n_iter, gain,
+                                      float(thr[m]), mask=masks[m],
+                                      model=None if model is None else model[m:m + 1])
+            # (the slots at and beyond nc are not written by `clean`: they stay zero here; nothing
+            # is read back, so the calls of a run queue up behind each other)
+            found = slot < nc[0]
+            cpix[m] = torch.where(found, cp[0], torch.zeros_like(cp[0]))
+            cflux[m] = torch.where(found, cf[0], torch.zeros_like(cf[0]))
+            ncomp[m] = nc[0]
+        return cpix, cflux, ncomp
 
     def _msclean_chunk(self, dirty, beam, ni, nj, pi_, pj, ms, abc, niter, gain, thr):
         """Multi-scale CLEAN of one chunk's dirty images [M, ni * nj] -> (raw residual, model,
@@ -1464,7 +1690,8 @@ class Imager:
 
     def _observe(self, maps, freqs, tracks, t_int_s, sigma_jy, sefd_jy, chanwidth_hz, seed,
                  nsigma, weights, shape, cell_as, mfs, niter, gain, threshold_jy, mask, beam,
-                 psf_shape, imfit, weighting, robust, scales=None, scale_bias=None, nterms=1,
+                 psf_shape, imfit, weighting, robust, automask=None, scales=None, scale_bias=None,
+                 nterms=1,
                  reffreq_hz=None, alpha_cut_jy=None, major_cycles=0,
                  cyclefactor=1.5, cycleniter=None, min_psf_fraction=0.05, max_psf_fraction=0.8):
         """`JetModel.observe_*` after the maps [F, nx * nz]: visibilities, noise, image rms, CLEAN."""
@@ -1508,7 +1735,9 @@ class Imager:
                                  nterms=nterms, reffreq_hz=reffreq_hz, alpha_cut_jy=alpha_cut_jy,
                                  major_cycles=major_cycles, cyclefactor=cyclefactor,
                                  cycleniter=cycleniter, min_psf_fraction=min_psf_fraction,
-                                 max_psf_fraction=max_psf_fraction)
+                                 max_psf_fraction=max_psf_fraction,
+                                 # (named only when set, as in `_clean_images`' call of `_major_chunk`)
+                                 **({} if automask is None else dict(automask=automask)))
         v0 = V0.cpu().numpy()
         return Observation(tracks, v0, V.cpu().numpy() if noisy else v0.copy(), sigma, rms, res)
 
@@ -1581,6 +1810,63 @@ class Imager:
         opts = self._imfit_options({"box": box, "theta0": theta0, "n_iter": n_iter, "rms": rms},
                                    None, ni, nj)
         return self._imfit_images(img.reshape(M, ni * nj).contiguous(), ni, nj, abc, cell, opts)
+
+    # ------------------------------------------------------------------ imstat, automask ----
+    def _image_stack(self, who, images):
+        """`images` (F, ni, nj) or (ni, nj), host or device -> (float64 device tensor [M, ni nj],
+        M, ni, nj)."""
+        import torch
+        eng = self.engine
+        if isinstance(images, torch.Tensor):
+            img = images.to(device=eng.device, dtype=torch.float64)
+        else:
+            img = torch.from_numpy(np.ascontiguousarray(images, dtype=np.float64)).to(eng.device)
+        if img.dim() == 2:
+            img = img.unsqueeze(0)
+        if img.dim() != 3:
+            raise ValueError("%s: `images` must be (F, ni, nj) or (ni, nj)" % who)
+        M, ni, nj = (int(x) for x in img.shape)
+        return img.reshape(M, ni * nj).contiguous(), M, ni, nj
+
+    def _mask_planes(self, who, name, mask, M, ni, nj, per_map=True):
+        """None, or `mask` (ni, nj) -- with `per_map` also (M, ni, nj) -- host or device -> bool
+        device tensor [1 or M, ni nj]."""
+        import torch
+        if mask is None:
+            return None
+        if not isinstance(mask, torch.Tensor):
+            mask = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0))
+        mask = (mask != 0).to(self.engine.device)
+        ok = [(ni, nj)] + ([(M, ni, nj)] if per_map else [])
+        if tuple(mask.shape) not in ok:
+            raise ValueError("%s: `%s` must have the shape %s" % (who, name, " or ".join(map(str, ok))))
+        return mask.reshape(-1, ni * nj).contiguous()
+
+    def imstat(self, images, mask=None, inside=True):
+        """See `JetModel.imstat`."""
+        img, M, ni, nj = self._image_stack("imstat", images)
+        mk = self._mask_planes("imstat", "mask", mask, M, ni, nj)
+        return image_stats_results(self.engine.image_stats(img, ni, nj, mask=mk, inside=inside))
+
+    def automask(self, images, beam, sidelobe=0., mask=None, prev=None, options=None):
+        """See `JetModel.automask`."""
+        img, M, ni, nj = self._image_stack("automask", images)
+        opts = automask_options(dict(options) if options else True)
+        _, _, cell = self._image_grid((ni, nj), None)
+        beams = np.asarray(beam, dtype=np.float64).reshape(-1, 3)
+        if beams.shape[0] not in (1, M):
+            raise ValueError("automask: `beam` must be one (bmaj_as, bmin_as, bpa_deg) or one per image")
+        abc = [beam_quadratic(b[0], b[1], b[2], cell) for b in np.broadcast_to(beams, (M, 3))]
+        side = np.asarray(sidelobe, dtype=np.float64).reshape(-1)
+        if side.size not in (1, M):
+            raise ValueError("automask: `sidelobe` must be one number or one per image")
+        um = self._mask_planes("automask", "mask", mask, M, ni, nj, per_map=False)
+        pv = self._mask_planes("automask", "prev", prev, M, ni, nj)
+        if pv is not None and int(pv.shape[0]) != M:
+            pv = pv.expand(M, ni * nj).contiguous()
+        masks, info = automask_step(self.engine, img, pv, um, np.broadcast_to(side, (M,)), abc, opts,
+                                    shape=(ni, nj))
+        return (masks != 0).cpu().numpy().reshape(M, ni, nj), info
 
     # ------------------------------------------------------------------ uvmodelfit ----
     @staticmethod
